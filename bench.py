@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: fine-level DoF.sweeps/s of the 2-D Poisson V-cycle on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 Workload (BASELINE.json cfg#4, the size the north-star target is quoted on; it fits one
@@ -16,7 +16,11 @@ per cycle (2*nu + 1) / time: the fine-level sweep rate the whole cycle sustains.
 For N > 1 the fine grid is row-block partitioned over the ranks (strong scaling: the
 problem size is fixed), halos travel over RCCL, see learnmultigrid_amd/dist.py.
 
-Extra objects on the JSON line: `roofline` (the DOMINANT KERNEL OF THE TIMED STEP -- the fused
+A plain run sets up, warms up, times the K steps and prints the headline line (`metric`, `value`, `unit`,
+`ms_per_step`, ...); `--dump-outputs DIR` also writes what the last timed step computed (a fixed, seeded sample of
+the fine-level iterate) as .npy files.  Everything else runs only with `--full`:
+
+Extra objects on the JSON line with --full: `roofline` (the DOMINANT KERNEL OF THE TIMED STEP -- the fused
 fine-level pre-smoothing pass: 3 sweeps + residual + restriction in one launch --, average
 launch duration measured with HIP events on the launch stream, bytes = what the launch has to
 move; the single fine-level Jacobi sweep, the kernel the north-star target is quoted on, is the
@@ -103,6 +107,11 @@ def parse():
     ap.add_argument("--no-extra", action="store_true", help="skip the legs of the other BASELINE configs (#3, #5-style)")
     ap.add_argument("--no-packed", action="store_true", help="plain CSR kernels (no lossless twins at all)")
     ap.add_argument("--no-patterns", action="store_true", help="packed CSR twin only (no row-pattern twin)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs the headline figure does not need: roofline / fused-pass / copy-ceiling timings, "
+                         "CPU baseline, time to solution, other BASELINE configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -368,7 +377,194 @@ def main():
             dt = t.item()
         sweeps_per_step = 2 if args.mode == "sweep" else 2 * nu + 1
         value = n * sweeps_per_step * args.steps / dt
+    if args.dump_outputs:
+        # the fine-level iterate the last step left (and the residual a sweep-mode step returns)
+        if world > 1 or force_dist:
+            got = {"x": D.gather_solution()}
+        else:
+            got = {"x": fine.x.cpu().numpy()}
+            if args.mode == "sweep":
+                got["r"], got["residual_norm2"] = r.cpu().numpy(), H.norm2.cpu().numpy()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, got)
+    kind = fine_format(fine_A)[0]
+    roofline = roofline_legs(args, H, fine_A, stream, dev, dt, world, force_dist) if args.full else None
+    cyc_bytes, coarse_bytes = H.cycle_bytes(nu) if args.mode == "vcycle" and world == 1 else (None, None)
+    if world > 1 or force_dist:
+        out_extra = {"distributed_levels": D.n_dist, "rows_per_rank_fine": n_loc_fine,
+                     "halo_values_fine": D.dl[0].n_lo + D.dl[0].n_hi, "halo_depth": D.halo_depth,
+                     "halo_exchanges_per_cycle": D.n_exchanges / max(1, args.steps + args.warmup)}
+    else:
+        out_extra = {}
 
+    rebuild_ms = None
+    if args.rebuild:
+        # replicated numeric Galerkin rebuild; with several ranks every rank rebuilds its replica and
+        # re-cuts its local operators (no communication)
+        dist_run = world > 1 or force_dist
+        owner = D if dist_run else H
+        newv = H.levels[0].A.vals.clone()
+        torch.cuda.synchronize()
+        with torch.cuda.stream(stream):
+            t0 = time.perf_counter()
+            owner.rebuild_numeric(newv)  # first rebuild: sorts once more and records the product maps
+            torch.cuda.synchronize()
+            rebuild_first_ms = (time.perf_counter() - t0) * 1e3
+            t0 = time.perf_counter()
+            for _ in range(args.rebuild):
+                owner.rebuild_numeric(newv)
+            torch.cuda.synchronize()
+            rebuild_ms = (time.perf_counter() - t0) / args.rebuild * 1e3
+    out = {"metric": "fine-level DoF*sweeps/s, 2-D Poisson V-cycle", "value": value,
+           "unit": "DoF*sweeps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+           "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
+           "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+           "config": {"workload": "%s %dx%d elements (%d DoF, %d nnz, CSR fp64/int32), %d-level V(%d,%d) cycle, "
+                                  "weighted Jacobi omega=%.2f, %s, Galerkin RAP by device SpGEMM"
+                                  % ({"poisson": "2-D structured P1 Poisson",
+                                      "varcoeff": "2-D variable-coefficient P1 stiffness (k = exp(0.5 N(0,1)) smoothed, seed 44)",
+                                      "jittered": "2-D P1 Poisson on a jittered triangulation (7-point, seed 42)"}[args.problem],
+                                     m, m, n, nnz, levels, nu, nu, args.omega,
+                                     {"geometric": "tensor-product geometric transfer",
+                                      "learned": "learned-like transfer (row-stochastic perturbed L2-type Q, seeds 43+level)"}[args.transfer]),
+                      "mode": args.mode, "step": "one full V-cycle" if args.mode == "vcycle"
+                      else "1 Jacobi sweep + 1 residual on the fine level",
+                      "fine_sweeps_per_step": sweeps_per_step,
+                      "hipgraph": (not args.no_graph) and world == 1 and not force_dist and args.mode == "vcycle",
+                      "level_sizes": [int(s) for s in P.level_sizes(m + 1, levels)],
+                      "partition": "row blocks of grid lines over %d rank(s)" % world,
+                      "sweep_variant": ops.tune_get("sweep_variant"),
+                      "packed_csr": not args.no_packed, "fine_level_format": kind},
+           "setup_s": setup_s}
+    if roofline is not None:
+        out["roofline"] = roofline
+    out["config"].update(out_extra)
+    if world > 1:
+        out["scaling"] = "strong"                 # cfg#4 is a fixed-size problem cut into row blocks
+    if rebuild_ms is not None:
+        out["galerkin_rebuild_ms"] = rebuild_ms
+        out["galerkin_rebuild_first_ms"] = rebuild_first_ms
+        out["galerkin_product_map_bytes"] = sum(lev.plan_RA.recorded_bytes() + lev.plan_RAP.recorded_bytes()
+                                                for lev in H.levels[:-1])
+    out["config"]["problem"] = args.problem
+    out["config"]["transfer"] = args.transfer
+    if cyc_bytes is not None:
+        out["cycle_algorithmic_GBps"] = cyc_bytes / (dt / args.steps) / 1e9
+        out["cycle_algorithmic_bytes"] = cyc_bytes
+        out["coarse_dense_bytes"] = coarse_bytes
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
+        out["cpu_baseline"] = cpu_baseline(A, hier, rhs, args)
+    if args.full and rank == 0 and world == 1 and not force_dist and args.mode == "vcycle" and not args.no_tts:
+        # time to solution (||r||_2 <= 1e-10 from x = 0, the scripts' `error=1e-10`): upload + setup + cycles, next to the CPU oracle's
+        # setup + the same number of its timed cycles (same arithmetic, hence the same cycle count)
+        cyc, t_solve, rel = solve_to_tolerance(H, rhs, nu, args.omega)
+        tts = {"this_config": {"cycles": cyc, "final_relative_residual": rel,
+                               "setup_s_cold_incl_upload": setup_s, "solve_s": t_solve,
+                               "time_to_solution_s": setup_s + t_solve}}
+        cb = out.get("cpu_baseline")
+        if cb and cb.get("s_per_cycle"):
+            tts["this_config"]["cpu_time_to_solution_s"] = cb["setup_s"] + cyc * cb["s_per_cycle"]
+            tts["this_config"]["cpu_note"] = "oracle setup + %d x its measured cycle time (1 core)" % cyc
+        if args.problem == "poisson" and args.transfer == "geometric" and args.size != 512:
+            m2 = 512                                                             # cfg#2: 513^2, 3 levels
+            A2, rhs2 = P.poisson_2d_structured(m2)
+            t0 = time.perf_counter()
+            H2 = Hierarchy(A2, P.geometric_hierarchy_2d(m2 + 1, 3), dev)
+            torch.cuda.synchronize()
+            s2 = time.perf_counter() - t0
+            c2, ts2, rel2 = solve_to_tolerance(H2, rhs2, nu, args.omega)
+            tts["cfg2_513x513_3_levels"] = {"cycles": c2, "final_relative_residual": rel2, "setup_s_warm_incl_upload": s2,
+                                            "solve_s": ts2, "time_to_solution_s": s2 + ts2}
+            del H2
+        out["time_to_solution"] = tts
+        # the same hierarchy once more in this process: the WARM setup time (code objects loaded, allocator primed)
+        if args.problem == "poisson" and args.transfer == "geometric":
+            del H
+            torch.cuda.empty_cache()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            Hw = Hierarchy(A, hier, dev, coarse_solver=args.coarse)
+            torch.cuda.synchronize()
+            tts["this_config"]["setup_s_warm_incl_upload"] = time.perf_counter() - t0
+            del Hw
+            torch.cuda.empty_cache()
+    if (args.full and rank == 0 and world == 1 and not force_dist and args.mode == "vcycle" and not args.no_extra
+            and args.problem == "poisson" and args.transfer == "geometric" and args.size == 4096):
+        H = None
+        torch.cuda.empty_cache()
+        # the same cfg#4 cycle with the reference's SHIPPED semantics: forward Gauss-Seidel whatever the smoother's name
+        # (Multigrid.py:79-88, :121), exact lexicographic order on the device
+        Hs = Hierarchy(A, hier, dev, coarse_solver=args.coarse)
+        with torch.cuda.stream(Hs.stream):
+            Hs.levels[0].b.copy_(torch.from_numpy(rhs.ravel().copy()).to(dev))
+            gs_graph = Hs.captured_cycle("GaussSeidel", nu, 1.0, "lexicographic")
+            gs_graph.launch()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(3):
+                gs_graph.launch()
+            torch.cuda.synchronize()
+            t_gs = (time.perf_counter() - t0) / 3
+            Hs.check_smoothers()
+        del Hs, gs_graph
+        torch.cuda.empty_cache()
+        shipped = {"workload": "cfg#4 with the reference's shipped smoother semantics: V(%d,%d), exact forward (lexicographic) "
+                               "Gauss-Seidel on every level, hipGraph replay" % (nu, nu),
+                   "ms_per_cycle": t_gs * 1e3, "DoF_sweeps_per_s": n * (2 * nu + 1) / t_gs, "cycles_timed": 3}
+        out["other_configs"] = {
+            "cfg4_as_shipped_forward_gauss_seidel": shipped,
+            "cfg3_jittered_7pt_1441x1441_learned_q_5_levels": other_config_leg(
+                "BASELINE cfg#3: P1 Poisson on a jittered triangulation, 1441^2 = 2.08 M DoF, learned-like Q, 5 levels",
+                "jittered", 1440, 5, nu, args.omega, dev),
+            "cfg5_style_varcoeff_4097x4097_learned_q_6_levels": other_config_leg(
+                "BASELINE cfg#5 at 4097^2 (one GPU's share of the 8193^2 problem is half of this): variable-coefficient "
+                "stiffness, learned-like Q, 6 levels", "varcoeff", 4096, 6, nu, args.omega, dev, steps=5)}
+    if rank == 0:
+        print(json.dumps(out))
+    if dist.is_initialized():
+        dist.destroy_process_group()
+
+
+DUMP_SAMPLE = 1 << 21          # entries written per vector by --dump-outputs (16 MB in float64)
+
+
+def dump_outputs(out_dir, vectors):
+    """--dump-outputs: what the last timed step computed, as out_dir/<name>.npy in float64.  Vectors longer than
+    DUMP_SAMPLE are written as a fixed, seeded sample of their entries -- the same positions in every run of the same
+    size, listed in index.npy -- so that two builds can be compared output for output within the size budget."""
+    os.makedirs(out_dir, exist_ok=True)
+    idx = {}
+    for name, v in vectors.items():
+        v = np.asarray(v, dtype=np.float64).ravel()
+        if v.size > DUMP_SAMPLE:
+            if v.size not in idx:
+                idx[v.size] = np.sort(np.random.default_rng(1234).choice(v.size, DUMP_SAMPLE, replace=False))
+            v = v[idx[v.size]]
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+    assert len(idx) <= 1, "one sample index per dump"
+    for positions in idx.values():
+        np.save(os.path.join(out_dir, "index.npy"), positions.astype(np.float64))
+
+
+def fine_format(fine_A):
+    """Format the fine-level sweeps run in: (kind, stencil, row-pattern, packed, sliced-ELL twin or None)."""
+    from learnmultigrid_amd import ops
+    st_ = fine_A.stencil if (ops._PACKED_ENABLED and ops._STENCIL_ENABLED) else None
+    rp_ = fine_A.patterns if ops._PACKED_ENABLED else None
+    pk = fine_A.packed if (ops._PACKED_ENABLED and rp_ is None) else None
+    sl = fine_A.sell if (ops._PACKED_ENABLED and rp_ is None and pk is None) else None
+    kind = "stencil" if st_ is not None else ("rpat" if rp_ is not None else ("pcsr" if pk is not None else
+                                                                              ("sell" if sl is not None else "csr")))
+    return kind, st_, rp_, pk, sl
+
+
+def roofline_legs(args, H, fine_A, stream, dev, dt, world, force_dist):
+    """--full only: the roofline of the dominant kernel of the timed step, the single fine-level sweep, the plain-CSR
+    sweep and the device copy ceiling, each from launches of its own on the launch stream (HIP events)."""
+    import torch
+    from learnmultigrid_amd import ops
+    nu = args.nu
+    with torch.cuda.stream(stream):
         # ---- roofline of the dominant kernel (fine-level Jacobi sweep), HIP events on this stream
         xa = torch.zeros(fine_A.shape[1], dtype=torch.float64, device=dev)
         ya = torch.zeros(fine_A.shape[0], dtype=torch.float64, device=dev)
@@ -426,12 +622,7 @@ def main():
         copy_gbps = max(copy_gbps, 2 * cp_src.numel() * 8 / (ev0.elapsed_time(ev1) * 1e-3 / 10) / 1e9)
         del cp_src, cp_dst
     B = sweep_bytes(fine_A.shape[0], fine_A.nnz)
-    st_ = fine_A.stencil if (ops._PACKED_ENABLED and ops._STENCIL_ENABLED) else None
-    rp_ = fine_A.patterns if ops._PACKED_ENABLED else None
-    pk = fine_A.packed if (ops._PACKED_ENABLED and rp_ is None) else None
-    sl = fine_A.sell if (ops._PACKED_ENABLED and rp_ is None and pk is None) else None
-    kind = "stencil" if st_ is not None else ("rpat" if rp_ is not None else ("pcsr" if pk is not None else
-                                                                              ("sell" if sl is not None else "csr")))
+    kind, st_, rp_, pk, sl = fine_format(fine_A)
     # bytes the launch really has to move: the lossless twin of the CSR arrays (DESIGN.md
     # section 3) + x once + b + output
     twin = st_ if st_ is not None else (rp_ if rp_ is not None else (pk if pk is not None else sl))
@@ -532,138 +723,7 @@ def main():
                         "csr_equivalent_GBps": dom["operator_applications_per_launch"] * B / (dom["avg_launch_ms"] * 1e-3) / 1e9,
                         "copy_ceiling_GBps": copy_gbps, "frac_of_copy_ceiling": dom["GBps"] / copy_gbps,
                         "fused_passes_in_the_cycle": fused, "single_sweep": single}
-    cyc_bytes, coarse_bytes = H.cycle_bytes(nu) if args.mode == "vcycle" and world == 1 else (None, None)
-    if world > 1 or force_dist:
-        out_extra = {"distributed_levels": D.n_dist, "rows_per_rank_fine": n_loc_fine,
-                     "halo_values_fine": D.dl[0].n_lo + D.dl[0].n_hi, "halo_depth": D.halo_depth,
-                     "halo_exchanges_per_cycle": D.n_exchanges / max(1, args.steps + args.warmup)}
-    else:
-        out_extra = {}
-
-    rebuild_ms = None
-    if args.rebuild:
-        # replicated numeric Galerkin rebuild; with several ranks every rank rebuilds its replica and
-        # re-cuts its local operators (no communication)
-        dist_run = world > 1 or force_dist
-        owner = D if dist_run else H
-        newv = H.levels[0].A.vals.clone()
-        torch.cuda.synchronize()
-        with torch.cuda.stream(stream):
-            t0 = time.perf_counter()
-            owner.rebuild_numeric(newv)  # first rebuild: sorts once more and records the product maps
-            torch.cuda.synchronize()
-            rebuild_first_ms = (time.perf_counter() - t0) * 1e3
-            t0 = time.perf_counter()
-            for _ in range(args.rebuild):
-                owner.rebuild_numeric(newv)
-            torch.cuda.synchronize()
-            rebuild_ms = (time.perf_counter() - t0) / args.rebuild * 1e3
-    out = {"metric": "fine-level DoF*sweeps/s, 2-D Poisson V-cycle", "value": value,
-           "unit": "DoF*sweeps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-           "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
-           "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-           "config": {"workload": "%s %dx%d elements (%d DoF, %d nnz, CSR fp64/int32), %d-level V(%d,%d) cycle, "
-                                  "weighted Jacobi omega=%.2f, %s, Galerkin RAP by device SpGEMM"
-                                  % ({"poisson": "2-D structured P1 Poisson",
-                                      "varcoeff": "2-D variable-coefficient P1 stiffness (k = exp(0.5 N(0,1)) smoothed, seed 44)",
-                                      "jittered": "2-D P1 Poisson on a jittered triangulation (7-point, seed 42)"}[args.problem],
-                                     m, m, n, nnz, levels, nu, nu, args.omega,
-                                     {"geometric": "tensor-product geometric transfer",
-                                      "learned": "learned-like transfer (row-stochastic perturbed L2-type Q, seeds 43+level)"}[args.transfer]),
-                      "mode": args.mode, "step": "one full V-cycle" if args.mode == "vcycle"
-                      else "1 Jacobi sweep + 1 residual on the fine level",
-                      "fine_sweeps_per_step": sweeps_per_step,
-                      "hipgraph": (not args.no_graph) and world == 1 and not force_dist and args.mode == "vcycle",
-                      "level_sizes": [int(s) for s in P.level_sizes(m + 1, levels)],
-                      "partition": "row blocks of grid lines over %d rank(s)" % world,
-                      "sweep_variant": ops.tune_get("sweep_variant"),
-                      "packed_csr": not args.no_packed, "fine_level_format": kind},
-           "setup_s": setup_s, "roofline": roofline}
-    out["config"].update(out_extra)
-    if world > 1:
-        out["scaling"] = "strong"                 # cfg#4 is a fixed-size problem cut into row blocks
-    if rebuild_ms is not None:
-        out["galerkin_rebuild_ms"] = rebuild_ms
-        out["galerkin_rebuild_first_ms"] = rebuild_first_ms
-        out["galerkin_product_map_bytes"] = sum(lev.plan_RA.recorded_bytes() + lev.plan_RAP.recorded_bytes()
-                                                for lev in H.levels[:-1])
-    out["config"]["problem"] = args.problem
-    out["config"]["transfer"] = args.transfer
-    if cyc_bytes is not None:
-        out["cycle_algorithmic_GBps"] = cyc_bytes / (dt / args.steps) / 1e9
-        out["cycle_algorithmic_bytes"] = cyc_bytes
-        out["coarse_dense_bytes"] = coarse_bytes
-    if rank == 0 and world == 1 and not args.no_cpu:
-        out["cpu_baseline"] = cpu_baseline(A, hier, rhs, args)
-    if rank == 0 and world == 1 and not force_dist and args.mode == "vcycle" and not args.no_tts:
-        # time to solution (||r||_2 <= 1e-10 from x = 0, the scripts' `error=1e-10`): upload + setup + cycles, next to the CPU oracle's
-        # setup + the same number of its timed cycles (same arithmetic, hence the same cycle count)
-        cyc, t_solve, rel = solve_to_tolerance(H, rhs, nu, args.omega)
-        tts = {"this_config": {"cycles": cyc, "final_relative_residual": rel,
-                               "setup_s_cold_incl_upload": setup_s, "solve_s": t_solve,
-                               "time_to_solution_s": setup_s + t_solve}}
-        cb = out.get("cpu_baseline")
-        if cb and cb.get("s_per_cycle"):
-            tts["this_config"]["cpu_time_to_solution_s"] = cb["setup_s"] + cyc * cb["s_per_cycle"]
-            tts["this_config"]["cpu_note"] = "oracle setup + %d x its measured cycle time (1 core)" % cyc
-        if args.problem == "poisson" and args.transfer == "geometric" and args.size != 512:
-            m2 = 512                                                             # cfg#2: 513^2, 3 levels
-            A2, rhs2 = P.poisson_2d_structured(m2)
-            t0 = time.perf_counter()
-            H2 = Hierarchy(A2, P.geometric_hierarchy_2d(m2 + 1, 3), dev)
-            torch.cuda.synchronize()
-            s2 = time.perf_counter() - t0
-            c2, ts2, rel2 = solve_to_tolerance(H2, rhs2, nu, args.omega)
-            tts["cfg2_513x513_3_levels"] = {"cycles": c2, "final_relative_residual": rel2, "setup_s_warm_incl_upload": s2,
-                                            "solve_s": ts2, "time_to_solution_s": s2 + ts2}
-            del H2
-        out["time_to_solution"] = tts
-        # the same hierarchy once more in this process: the WARM setup time (code objects loaded, allocator primed)
-        if args.problem == "poisson" and args.transfer == "geometric":
-            del H
-            torch.cuda.empty_cache()
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            Hw = Hierarchy(A, hier, dev, coarse_solver=args.coarse)
-            torch.cuda.synchronize()
-            tts["this_config"]["setup_s_warm_incl_upload"] = time.perf_counter() - t0
-            del Hw
-            torch.cuda.empty_cache()
-    if (rank == 0 and world == 1 and not force_dist and args.mode == "vcycle" and not args.no_extra
-            and args.problem == "poisson" and args.transfer == "geometric" and args.size == 4096):
-        H = None
-        torch.cuda.empty_cache()
-        # the same cfg#4 cycle with the reference's SHIPPED semantics: forward Gauss-Seidel whatever the smoother's name
-        # (Multigrid.py:79-88, :121), exact lexicographic order on the device
-        Hs = Hierarchy(A, hier, dev, coarse_solver=args.coarse)
-        with torch.cuda.stream(Hs.stream):
-            Hs.levels[0].b.copy_(torch.from_numpy(rhs.ravel().copy()).to(dev))
-            gs_graph = Hs.captured_cycle("GaussSeidel", nu, 1.0, "lexicographic")
-            gs_graph.launch()
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(3):
-                gs_graph.launch()
-            torch.cuda.synchronize()
-            t_gs = (time.perf_counter() - t0) / 3
-            Hs.check_smoothers()
-        del Hs, gs_graph
-        torch.cuda.empty_cache()
-        shipped = {"workload": "cfg#4 with the reference's shipped smoother semantics: V(%d,%d), exact forward (lexicographic) "
-                               "Gauss-Seidel on every level, hipGraph replay" % (nu, nu),
-                   "ms_per_cycle": t_gs * 1e3, "DoF_sweeps_per_s": n * (2 * nu + 1) / t_gs, "cycles_timed": 3}
-        out["other_configs"] = {
-            "cfg4_as_shipped_forward_gauss_seidel": shipped,
-            "cfg3_jittered_7pt_1441x1441_learned_q_5_levels": other_config_leg(
-                "BASELINE cfg#3: P1 Poisson on a jittered triangulation, 1441^2 = 2.08 M DoF, learned-like Q, 5 levels",
-                "jittered", 1440, 5, nu, args.omega, dev),
-            "cfg5_style_varcoeff_4097x4097_learned_q_6_levels": other_config_leg(
-                "BASELINE cfg#5 at 4097^2 (one GPU's share of the 8193^2 problem is half of this): variable-coefficient "
-                "stiffness, learned-like Q, 6 levels", "varcoeff", 4096, 6, nu, args.omega, dev, steps=5)}
-    if rank == 0:
-        print(json.dumps(out))
-    if dist.is_initialized():
-        dist.destroy_process_group()
+    return roofline
 
 
 if __name__ == "__main__":
