@@ -200,23 +200,26 @@ int lmg_stencil_smooth_tiled(int64_t n, int32_t line_stride, const uint8_t *d_pi
                              int32_t hot_pattern, const double *h_hot_val, int sweeps, const double *d_x_in,
                              const double *d_b, double omega, double *d_x_out, double *d_r_out, void *stream);
 /* ... and with the coarse-grid correction folded in, x_out = J^sweeps(x_in + P e_coarse): the tile is loaded as
- * x + P e (row patterns of P as in lmg_stencil_smooth_prolong, no frequent-pair shortcut needed: the correction is
- * formed once per element, with the sums of lmg_rpat_sweep_grid(SPMV, alpha = 1, beta = 1) in order). */
+ * x + P e (row patterns of P and the frequent pairs h_hot_pairs / h_hot_pval as in lmg_stencil_smooth_prolong, both
+ * may be NULL; the correction is formed once per element, with the sums of lmg_rpat_sweep_grid(SPMV, alpha = 1,
+ * beta = 1) in order). */
 int lmg_stencil_smooth_tiled_prolong(int64_t n, int32_t line_stride, const uint8_t *d_pid, int32_t npat,
                                      const double *d_st_val, const int32_t *d_st_mask, uint32_t union_mask,
                                      int32_t hot_pattern, const double *h_hot_val, int sweeps, const double *d_x_in,
                                      const double *d_b, double omega, double *d_x_out, int64_t n_coarse,
                                      int32_t coarse_stride, const double *d_e_coarse, const uint8_t *d_p_pid,
-                                     int32_t p_npat, const double *d_p_val, const int32_t *d_p_mask, void *stream);
+                                     int32_t p_npat, const double *d_p_val, const int32_t *d_p_mask,
+                                     const int32_t *h_hot_pairs, const double *h_hot_pval, void *stream);
 /* ... and with the restriction folded in, b_coarse = R (b - A x_out) instead of the residual (arguments of
- * lmg_stencil_smooth_restrict without the frequent-pattern shortcut): the residual of the tile goes to LDS, every
- * element on an (even line, even column) node sums the nine entries of its row of R in column order. */
+ * lmg_stencil_smooth_restrict; hot_r: a pattern of R with all nine slots, -1 = none): the residual of the tile goes to
+ * LDS, the row of R of every (even line, even column) node sums its nine entries in column order. */
 int lmg_stencil_smooth_tiled_restrict(int64_t n, int32_t line_stride, const uint8_t *d_pid, int32_t npat,
                                       const double *d_st_val, const int32_t *d_st_mask, uint32_t union_mask,
                                       int32_t hot_pattern, const double *h_hot_val, int sweeps, const double *d_x_in,
                                       const double *d_b, double omega, double *d_x_out, int64_t n_coarse,
                                       int32_t coarse_stride, double *d_b_coarse, const uint8_t *d_r_pid,
-                                      int32_t r_npat, const double *d_r_val, const int32_t *d_r_mask, void *stream);
+                                      int32_t r_npat, const double *d_r_val, const int32_t *d_r_mask, int32_t hot_r,
+                                      const double *h_hot_rval, void *stream);
 
 /* ---- fused smoothing passes for grid operators with VARIABLE coefficients (csrc/dia_tile.hip) ------------------------
  * The operators the reference's learned transfers are built for (variable-coefficient / jittered-mesh stiffness

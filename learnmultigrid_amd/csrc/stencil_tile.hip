@@ -70,11 +70,24 @@ struct TArgs {
     const double *rp_val;     // [rp_npat][9]
     const int *rp_mask;       // [rp_npat]
     int rp_npat;
+    // hot-transfer kernels (HX): the usual patterns of P and R, their values in scalar registers.  phot[line parity] =
+    // id of the even-column | id of the odd-column pattern << 8 (-1: none), with exactly the slots of the tensor-product
+    // interpolation (0x1, 0x3 on even lines, 0x5, 0xF on odd ones), phv = their values in that order (as for
+    // lmg_stencil_smooth_prolong); rhot = a pattern of R with all nine slots (-1: none), rhv = its values
+    int phot[2];
+    double phv[9];
+    int rhot;
+    double rhv[9];
 };
 
-template <int S, unsigned UM, bool RESID, bool ZERO, int RR, bool PROL = false, bool REST = false, int RBV = kRB>
+// HX (hot transfers, with PROL or REST): the correction x + P e is formed as each element arrives, from the usual pair
+// of P in scalar registers where a whole wave line has it (else from the table in global memory) -- no 2 x 2 window per
+// element stays live across the pattern staging and barrier; the restriction runs once per coarse node (a thread per
+// node of the tile's inner part, 32 per wave line) instead of being carried by every fine element, with the frequent
+// row of R in scalar registers where a whole wave has it.
+template <int S, unsigned UM, bool RESID, bool ZERO, int RR, bool PROL = false, bool REST = false, int RBV = kRB, bool HX = false>
 // (16-wave workgroups: at most 64 VGPRs, so that two of them share a CU -- the variants with the restriction had 65 - 67)
-__global__ void __launch_bounds__(RR / RBV * LMG_WAVE, (RR / RBV == 16 && !PROL) ? 8 : 1) stencil_tile_kernel(TArgs a)
+__global__ void __launch_bounds__(RR / RBV * LMG_WAVE, (RR / RBV == 16 && (!PROL || HX)) ? 8 : 1) stencil_tile_kernel(TArgs a)
 {
     static_assert(!PROL || (!RESID && !ZERO), "the correction is folded into post-smoothing passes only");
     static_assert(!REST || (RESID && !PROL), "the restriction replaces the store of the residual");
@@ -82,14 +95,16 @@ __global__ void __launch_bounds__(RR / RBV * LMG_WAVE, (RR / RBV == 16 && !PROL)
     constexpr int H = S + (RESID ? 1 : 0) - (ZERO ? 1 : 0) + (REST ? 1 : 0);
     constexpr int kWaves = RR / RBV, kBlock = kWaves * LMG_WAVE;
     static_assert(RR > 2 * H + 1 && kCols > 2 * H && RR % RBV == 0, "tile smaller than its halo / lines per wave");
+    static_assert(!HX || PROL || REST, "hot transfers need a transfer");
+    static_assert(!(REST && HX) || (RR - 2 * H + 1) / 2 <= RR / RBV * 2, "a thread per coarse node of the tile");
     // LDS holds the two iterate buffers only: right-hand side and pattern ids of a wave's own lines never change and
     // stay in its registers (32-line tiles: 39 KB instead of 60, i.e. four workgroups per CU instead of two).
     __shared__ double s_x[2][RR * kLS];
     __shared__ double s_val[kMaxPat * 9];
     __shared__ int s_mask[kMaxPat];
     __shared__ double s_rdiag[kMaxPat];
-    __shared__ double s_pv[PROL ? kMaxPat * 4 : 1];
-    __shared__ int s_pm[PROL ? kMaxPat : 1];
+    __shared__ double s_pv[(PROL && !HX) ? kMaxPat * 4 : 1];
+    __shared__ int s_pm[(PROL && !HX) ? kMaxPat : 1];
     __shared__ double s_rv[REST ? kMaxPat * 9 : 1];
     __shared__ int s_rm[REST ? kMaxPat : 1];
 
@@ -105,8 +120,20 @@ __global__ void __launch_bounds__(RR / RBV * LMG_WAVE, (RR / RBV == 16 && !PROL)
     // ---- the wave's lines are requested first, the pattern table is staged while they are in flight -------------
     double lx[RB], bk[RB];
     int pk[RB];                                                   // pattern id | 0x100 where the element is a row of the matrix
-    double le[PROL ? RB : 1][4];                                  // PROL: the 2 x 2 coarse window of every element
+    double le[(PROL && !HX) ? RB : 1][4];                         // PROL: the 2 x 2 coarse window of every element
     int lq[(PROL || REST) ? RB : 1];                              //       and its pattern id in P / REST: the id of R's row
+    // REST with HX: this thread's coarse node -- line t >> 5, column t & 31 of the even nodes of the inner part
+    int rq = 0, rrow = H, rcol = H;
+    bool rown = false;
+    if (REST && HX) {
+        const int ye0 = (y0 + H + 1) & ~1, xe0 = (c0 + H + 1) & ~1;   // (y0 + H, c0 + H >= 0)
+        const int yf = ye0 + 2 * (t >> 5), xf = xe0 + 2 * (t & 31);
+        rown = yf < y0 + RR - H && yf < a.lines && xf < c0 + kCols - H && xf < W;
+        const int64_t jc = (int64_t)(yf >> 1) * a.Wc + (xf >> 1);
+        rq = (rown && jc < a.nc) ? (int)a.rpid[jc] : 0;
+        rrow = rown ? yf - y0 : H;
+        rcol = rown ? xf - c0 : H;
+    }
 #pragma unroll
     for (int k = 0; k < RB; ++k) {
         const int y = y0 + rb0 + k;
@@ -136,12 +163,41 @@ __global__ void __launch_bounds__(RR / RBV * LMG_WAVE, (RR / RBV == 16 && !PROL)
             const int64_t b0 = ok ? min(base, (int64_t)a.nc - 2) : 0, b1 = ok ? min(base + a.Wc, (int64_t)a.nc - 2) : 0;
             const d2u e01 = *reinterpret_cast<const d2u *>(a.ec + b0), e23 = *reinterpret_cast<const d2u *>(a.ec + b1);
             // (a window clamped at the end of the vector starts one element early: its first slot is the second value)
-            le[k][0] = b0 == base ? e01.a : e01.b;
-            le[k][1] = e01.b;
-            le[k][2] = b1 == base + a.Wc ? e23.a : e23.b;
-            le[k][3] = e23.b;
+            const double w0 = b0 == base ? e01.a : e01.b, w1 = e01.b, w2 = b1 == base + a.Wc ? e23.a : e23.b, w3 = e23.b;
+            if (!HX) {
+                le[k][0] = w0;
+                le[k][1] = w1;
+                le[k][2] = w2;
+                le[k][3] = w3;
+            } else {
+                // x + P e now: the sums of lmg_rpat_sweep_grid(SPMV, alpha = 1, beta = 1) in the same order
+                const int yl = yy & 1, xl = xx & 1;
+                const int hp = a.phot[yl];
+                const bool hotk = !ok || (hp >= 0 && lq[k] == ((xl ? hp >> 8 : hp) & 0xff));
+                double acc = 0.0;
+                if (__all(hotk)) {                                // wave-uniform: the usual pair, slots 0 (1) (2) (3)
+                    const double v0 = yl ? (xl ? a.phv[5] : a.phv[3]) : (xl ? a.phv[1] : a.phv[0]);
+                    const double v1 = yl ? a.phv[6] : a.phv[2], v2 = xl ? a.phv[7] : a.phv[4];
+                    acc = acc + v0 * w0;
+                    double tv = acc + v1 * w1;
+                    acc = xl ? tv : acc;
+                    tv = acc + v2 * w2;
+                    acc = yl ? tv : acc;
+                    tv = acc + a.phv[8] * w3;
+                    acc = (xl & yl) ? tv : acc;
+                } else {
+                    const int q = lq[k], m = a.pp_mask[q];
+                    const double w[4] = {w0, w1, w2, w3};
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) {
+                        const double tv = acc + a.pp_val[q * 4 + s] * w[s];
+                        acc = ((m >> s) & 1) ? tv : acc;
+                    }
+                }
+                lx[k] = (pk[k] >> 8) ? lx[k] + acc : 0.0;
+            }
         }
-        if (REST) {
+        if (REST && !HX) {
             // elements on (even line, even column) of the grid carry a row of R
             const int c = c0 + lane;
             const bool crow = ok && !(y & 1) && !(c & 1) && c >= 0 && c < W;
@@ -161,7 +217,7 @@ __global__ void __launch_bounds__(RR / RBV * LMG_WAVE, (RR / RBV == 16 && !PROL)
         s_x[0][r * kLS + g] = 0.0;
         s_x[1][r * kLS + g] = 0.0;
     }
-    if (PROL) {
+    if (PROL && !HX) {
         for (int i = t; i < a.pp_npat * 4; i += kBlock) s_pv[i] = a.pp_val[i];
         for (int i = t; i < a.pp_npat; i += kBlock) s_pm[i] = a.pp_mask[i];
         __syncthreads();
@@ -297,6 +353,26 @@ __global__ void __launch_bounds__(RR / RBV * LMG_WAVE, (RR / RBV == 16 && !PROL)
             if (r >= H && r < RR - H && col_ok && (pk[k] >> 8)) a.out[(int64_t)(y0 + r) * W + c0 + lane] = xc;
         });
         __syncthreads();
+        if (HX) {
+            // a thread per coarse node; waves without one have nothing left to do
+            if (__any(rown)) {
+                const double *p = rl + rrow * kLS + 1 + rcol;
+                double acc = 0.0;
+                if (__all(!rown || rq == a.rhot)) {
+#pragma unroll
+                    for (int e = 0; e < 9; ++e) acc = acc + a.rhv[e] * p[(e / 3 - 1) * kLS + e % 3 - 1];
+                } else {
+                    const int m = s_rm[rq];
+#pragma unroll
+                    for (int e = 0; e < 9; ++e) {
+                        const double tv = acc + s_rv[rq * 9 + e] * p[(e / 3 - 1) * kLS + e % 3 - 1];
+                        acc = ((m >> e) & 1) ? tv : acc;
+                    }
+                }
+                if (rown) a.bc[(int64_t)((y0 + rrow) >> 1) * a.Wc + ((c0 + rcol) >> 1)] = acc;
+            }
+            return;
+        }
 #pragma unroll
         for (int k = 0; k < RB; ++k) {
             const int r = rb0 + k;
@@ -335,8 +411,12 @@ int g_tile_rows = 16;       // lines per tile (16, 32; 0 = 32) on grids of fewer
 int g_tile_prol_wide_lines = 768;    // grids of at least this many lines: the pass with the correction on 8-wave workgroups
 int g_tile_rows_big = 0;    // the same for grids of at least g_tile_big_lines lines
 int g_tile_big_lines = 600;
+int g_tile_hot_transfers = 1;       // the passes with a transfer folded in run the HX kernels
+int g_tile_prol_wide_lines_hx = 1 << 30;    // g_tile_prol_wide_lines of the HX kernels: at 61 VGPRs the 16-wave variant
+                                            // runs 8 waves / SIMD (4 lines per wave: 87 VGPRs, 5); cfg#4 cycle 0.4698 ->
+                                            // 0.4539 ms without the 4-line variant at 2049^2
 
-template <int S, unsigned UM, bool RESID, bool ZERO, int RR, bool PROL = false, bool REST = false, int RBV = kRB>
+template <int S, unsigned UM, bool RESID, bool ZERO, int RR, bool PROL = false, bool REST = false, int RBV = kRB, bool HX = false>
 int launch5(TArgs a, hipStream_t st)
 {
     constexpr int H = S + (RESID ? 1 : 0) - (ZERO ? 1 : 0) + (REST ? 1 : 0);
@@ -344,8 +424,8 @@ int launch5(TArgs a, hipStream_t st)
     a.tiles_y = (a.lines + (RR - 2 * H) - 1) / (RR - 2 * H);
     const int64_t grid = (int64_t)a.tiles_x * a.tiles_y;
     if (grid > 0x7fffffff) return LMG_ERR_CAPACITY;
-    hipLaunchKernelGGL((stencil_tile_kernel<S, UM, RESID, ZERO, RR, PROL, REST, RBV>), dim3((unsigned)grid), dim3(RR / RBV * LMG_WAVE), 0, st,
-                       a);
+    hipLaunchKernelGGL((stencil_tile_kernel<S, UM, RESID, ZERO, RR, PROL, REST, RBV, HX>), dim3((unsigned)grid),
+                       dim3(RR / RBV * LMG_WAVE), 0, st, a);
     LMG_CHECK_LAUNCH();
     return LMG_OK;
 }
@@ -356,16 +436,26 @@ static int tile_rows_for(const TArgs &a)
     return rr == 0 ? 32 : rr;     // measured in the cycle (cfg#4): 0.672 ms with 32-line tiles (16 waves), 0.688 with 16 (8 waves)
 }
 
-template <int S, unsigned UM, bool RESID, bool ZERO, bool PROL = false, bool REST = false>
-int launch4(TArgs a, hipStream_t st)
+template <int S, unsigned UM, bool RESID, bool ZERO, bool PROL, bool REST, bool HX>
+int launch4x(TArgs a, hipStream_t st)
 {
-    if (tile_rows_for(a) == 16) return launch5<S, UM, RESID, ZERO, 16, PROL, REST>(a, st);
+    if (tile_rows_for(a) == 16) return launch5<S, UM, RESID, ZERO, 16, PROL, REST, kRB, HX>(a, st);
     // the pass with the correction needs 81 VGPRs: a 16-wave workgroup then fills a CU alone; on levels with many tiles
     // it runs 8 waves of four lines each (2049^2, 9-point: 69 instead of 81 us)
     if constexpr (PROL) {
-        if (a.lines >= g_tile_prol_wide_lines) return launch5<S, UM, RESID, ZERO, 32, PROL, REST, 4>(a, st);
+        if (a.lines >= (HX ? g_tile_prol_wide_lines_hx : g_tile_prol_wide_lines))
+            return launch5<S, UM, RESID, ZERO, 32, PROL, REST, 4, HX>(a, st);
     }
-    return launch5<S, UM, RESID, ZERO, 32, PROL, REST>(a, st);
+    return launch5<S, UM, RESID, ZERO, 32, PROL, REST, kRB, HX>(a, st);
+}
+
+template <int S, unsigned UM, bool RESID, bool ZERO, bool PROL = false, bool REST = false>
+int launch4(TArgs a, hipStream_t st)
+{
+    if constexpr (PROL || REST) {
+        if (g_tile_hot_transfers) return launch4x<S, UM, RESID, ZERO, PROL, REST, true>(a, st);
+    }
+    return launch4x<S, UM, RESID, ZERO, PROL, REST, false>(a, st);
 }
 
 template <unsigned UM>
@@ -414,14 +504,19 @@ int lmg_tile_tune_set(const char *key, int v)
         (key[9] ? g_tile_rows_big : g_tile_rows) = v;
         return LMG_OK;
     }
-    if (strcmp(key, "tile_prol_wide_lines") == 0) {
+    if (strcmp(key, "tile_prol_wide_lines") == 0 || strcmp(key, "tile_prol_wide_lines_hx") == 0) {
         if (v < 0) return LMG_ERR_ARG;
-        g_tile_prol_wide_lines = v;
+        (key[20] ? g_tile_prol_wide_lines_hx : g_tile_prol_wide_lines) = v;
         return LMG_OK;
     }
     if (strcmp(key, "tile_big_lines") == 0) {
         if (v < 0) return LMG_ERR_ARG;
         g_tile_big_lines = v;
+        return LMG_OK;
+    }
+    if (strcmp(key, "tile_hot_transfers") == 0) {
+        if (v != 0 && v != 1) return LMG_ERR_ARG;
+        g_tile_hot_transfers = v;
         return LMG_OK;
     }
     return LMG_ERR_ARG;
@@ -432,6 +527,8 @@ int lmg_tile_tune_get(const char *key)
     if (strcmp(key, "tile_rows_big") == 0) return g_tile_rows_big;
     if (strcmp(key, "tile_big_lines") == 0) return g_tile_big_lines;
     if (strcmp(key, "tile_prol_wide_lines") == 0) return g_tile_prol_wide_lines;
+    if (strcmp(key, "tile_hot_transfers") == 0) return g_tile_hot_transfers;
+    if (strcmp(key, "tile_prol_wide_lines_hx") == 0) return g_tile_prol_wide_lines_hx;
     return LMG_ERR_ARG;
 }
 
@@ -479,6 +576,9 @@ static int tile_args(TArgs &a, int64_t n, int32_t line_stride, const uint8_t *pi
     a.rp_val = nullptr;
     a.rp_mask = nullptr;
     a.rp_npat = 0;
+    a.phot[0] = a.phot[1] = -1;
+    a.rhot = -1;
+    for (int k = 0; k < 9; ++k) a.phv[k] = a.rhv[k] = 0.0;
     return 1;                                  // filled: launch
 }
 
@@ -505,7 +605,7 @@ int lmg_stencil_smooth_tiled_prolong(int64_t n, int32_t line_stride, const uint8
                                      const double *h_hot_val, int sweeps, const double *x_in, const double *b, double omega,
                                      double *x_out, int64_t n_coarse, int32_t coarse_stride, const double *e_coarse,
                                      const uint8_t *p_pid, int32_t p_npat, const double *p_val, const int32_t *p_mask,
-                                     void *stream)
+                                     const int32_t *h_hot_pairs, const double *h_hot_pval, void *stream)
 {
     if (!x_in || !e_coarse || !p_pid || !p_val || !p_mask || p_npat < 1 || p_npat > kMaxPat) return LMG_ERR_ARG;
     if (n_coarse < 2 || n_coarse >= (1ll << 31) || coarse_stride < 1 || coarse_stride > n_coarse) return LMG_ERR_ARG;
@@ -521,6 +621,14 @@ int lmg_stencil_smooth_tiled_prolong(int64_t n, int32_t line_stride, const uint8
     a.pp_val = p_val;
     a.pp_mask = p_mask;
     a.pp_npat = p_npat;
+    if (h_hot_pairs && h_hot_pval) {
+        for (int k = 0; k < 2; ++k) {
+            const int hp = h_hot_pairs[k];
+            const bool ok = hp >= 0 && (hp & 0xff) < p_npat && (hp >> 8) < p_npat;
+            a.phot[k] = ok ? hp : -1;
+        }
+        for (int k = 0; k < 9; ++k) a.phv[k] = h_hot_pval[k];
+    }
     hipStream_t st = lmg_stream(stream);
     switch (union_mask) {
     case kMask5: return launch_prol<kMask5>(a, sweeps, st);
@@ -534,7 +642,7 @@ int lmg_stencil_smooth_tiled_restrict(int64_t n, int32_t line_stride, const uint
                                       const double *h_hot_val, int sweeps, const double *x_in, const double *b, double omega,
                                       double *x_out, int64_t n_coarse, int32_t coarse_stride, double *b_coarse,
                                       const uint8_t *r_pid, int32_t r_npat, const double *r_val, const int32_t *r_mask,
-                                      void *stream)
+                                      int32_t hot_r, const double *h_hot_rval, void *stream)
 {
     if (!b_coarse || !r_pid || !r_val || !r_mask || r_npat < 1 || r_npat > kMaxPat) return LMG_ERR_ARG;
     if (n_coarse < 1 || n_coarse >= (1ll << 31) || coarse_stride < 1 || coarse_stride > n_coarse) return LMG_ERR_ARG;
@@ -555,6 +663,10 @@ int lmg_stencil_smooth_tiled_restrict(int64_t n, int32_t line_stride, const uint
     a.rp_val = r_val;
     a.rp_mask = r_mask;
     a.rp_npat = r_npat;
+    if (hot_r >= 0 && hot_r < r_npat && h_hot_rval) {
+        a.rhot = hot_r;
+        for (int k = 0; k < 9; ++k) a.rhv[k] = h_hot_rval[k];
+    }
     hipStream_t st = lmg_stream(stream);
     const bool zero = x_in == nullptr;
     switch (union_mask) {

@@ -911,13 +911,13 @@ def stencil_smooth(A, x_in, b, omega, sweeps, x_out, r_out=None, prolong=None, r
         _vec_ok(bc)
         if T is None or r_out is not None or prolong is not None or T.n != S.n or T.W != S.W or bc.numel() != T.nc:
             raise LmgError("stencil_smooth: this restriction cannot be fused into the pass")
+        hr = None if T._hot_val is None else ctypes.addressof(T._hot_val)
         if _fused_kind(A) == "tile" and not (S.n >= REG_RESTRICT_MIN_ROWS and _lib.lib().lmg_stencil_smooth_prolong_supported(S.umask)):
             check(_lib.lib().lmg_stencil_smooth_tiled_restrict(S.n, S.W, _p(S.pid), S.npat, _p(S.st_val), _p(S.st_mask), S.umask,
                                                                S.hot, hv, int(sweeps), _p(x_in), _p(b), float(omega), _p(x_out),
                                                                T.nc, T.Wc, _p(bc), _p(T.pid), T.npat, _p(T.r_val), _p(T.r_mask),
-                                                               _s(S.pid)), "lmg_stencil_smooth_tiled_restrict")
+                                                               T.hot, hr, _s(S.pid)), "lmg_stencil_smooth_tiled_restrict")
             return
-        hr = None if T._hot_val is None else ctypes.addressof(T._hot_val)
         check(_lib.lib().lmg_stencil_smooth_restrict(S.n, S.W, _p(S.pid), S.npat, _p(S.st_val), _p(S.st_mask), S.umask, S.hot,
                                                      hv, int(sweeps), _p(x_in), _p(b), float(omega), _p(x_out), T.nc, T.Wc,
                                                      _p(bc), _p(T.pid), T.npat, _p(T.r_val), _p(T.r_mask), T.hot, hr, _s(S.pid)),
@@ -933,6 +933,7 @@ def stencil_smooth(A, x_in, b, omega, sweeps, x_out, r_out=None, prolong=None, r
             check(_lib.lib().lmg_stencil_smooth_tiled_prolong(S.n, S.W, _p(S.pid), S.npat, _p(S.st_val), _p(S.st_mask), S.umask,
                                                               S.hot, hv, int(sweeps), _p(x_in), _p(b), float(omega), _p(x_out),
                                                               T.nc, T.Wc, _p(e), _p(T.pid), T.npat, _p(T.p_val), _p(T.p_mask),
+                                                              ctypes.addressof(T._hot_pairs), ctypes.addressof(T._hot_pval),
                                                               _s(S.pid)), "lmg_stencil_smooth_tiled_prolong")
             return
         check(_lib.lib().lmg_stencil_smooth_prolong(S.n, S.W, _p(S.pid), S.npat, _p(S.st_val), _p(S.st_mask), S.umask, S.hot,
