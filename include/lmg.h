@@ -392,6 +392,18 @@ int lmg_stencil_gs_sweep(int64_t n, int32_t line_stride, const uint8_t *d_pid, i
                          const double *d_st_val, const int32_t *d_st_mask, uint32_t union_mask,
                          int32_t hot_pattern, const double *h_hot_val, double *d_x, const double *d_b,
                          void *d_work, int sweeps, void *stream);
+/* Exact BACKWARD Gauss-Seidel (rows n-1 .. 0; pyamg's gauss_seidel with sweep='backward'): the same arguments and
+ * requirements as lmg_stencil_gs_sweep, plus n % line_stride == 0 (LMG_ERR_ARG otherwise; ragged grids take a reversed
+ * level schedule).  The kernels of lmg_stencil_gs_sweep run in mirrored coordinates (row (y, x) -> (lines-1-y, W-1-x)),
+ * so row (y, x) reads the NEW values of (y+1, x-1 .. x+1) and (y, x+1); rsum still runs over the entries in ascending
+ * column order, then (b - rsum) / diag, rows with a zero diagonal untouched: the same bits as lmg_csr_gs_schedule on
+ * the reversed level schedule.  Both directions use the operator's one d_work buffer (its tickets and progress
+ * counters are reset by every launch): all sweeps on one operator, forward or backward, must stay ordered on ONE
+ * stream.  The gsw_* tune keys apply to both directions. */
+int lmg_stencil_gs_sweep_backward(int64_t n, int32_t line_stride, const uint8_t *d_pid, int32_t npat,
+                                  const double *d_st_val, const int32_t *d_st_mask, uint32_t union_mask,
+                                  int32_t hot_pattern, const double *h_hot_val, double *d_x, const double *d_b,
+                                  void *d_work, int sweeps, void *stream);
 
 /* HOST helpers (host pointers, run on the CPU at setup time).
  * level[i] = 1 + max(level[j] : j < i adjacent to i in A + A^T), 0 if none: rows of equal

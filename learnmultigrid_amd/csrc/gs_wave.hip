@@ -23,6 +23,7 @@
 // Same row arithmetic in the same order as gs_update_row (rsum over the off-diagonal entries in column order,
 // (b - rsum) / diag, rows with a zero diagonal untouched): bit-identical to the level-scheduled sweep and to
 // the CPU oracle.  4097^2: one sweep ~1.5 ms instead of 43.7 ms (8191 launches); 513^2 ~0.25 ms instead of 2.5.
+// The BACKWARD sweep (pyamg's sweep='backward': rows n-1 .. 0) is the same kernels in mirrored coordinates (BWD, see pair_off_d).
 #include <math.h>
 #include <string.h>
 #include "lmg_common.hpp"
@@ -80,6 +81,53 @@ __device__ __forceinline__ unsigned pair_off(int64_t i, int n)
     return (j >= 0 && j + 1 < n) ? (unsigned)j * 8u : kOOB;
 }
 
+// BACKWARD sweeps (BWD) run the same kernels in MIRRORED coordinates: with n % W == 0, mirrored row i' = (y', x') is stored
+// row n - 1 - i' = (lines - 1 - y', W - 1 - x'), and relaxing mirrored rows 0 .. n - 1 in order is pyamg's backward sweep
+// (rows n - 1 .. 0).  The mirrored matrix has the same slot set (every supported union mask and the line-end rule of
+// StencilTwin.gs_ok are symmetric under slot k <-> 8 - k), so bands, tickets and progress counters are unchanged; only
+// addresses, the pattern table (loaded with its slots reversed) and the summation order change: pyamg reverses the row
+// loop, not the entry loop, so rsum still runs over ascending ORIGINAL columns = descending mirrored slots.
+template <bool BWD>
+__device__ __forceinline__ unsigned pair_off_d(int64_t i, int n)        // pair_off of mirrored elements i, i+1 (BWD: stored
+{                                                                       // n-1-i, n-2-i = the stored pair at n-2-i, swapped)
+    return pair_off(BWD ? (int64_t)n - 2 - i : i, n);
+}
+// the pattern table of a BWD launch in LDS: the slots of every pattern reversed (value and mask bit k -> 8 - k)
+__device__ __forceinline__ void load_patterns_mirrored(const GArgs &a, double *s_val, int *s_mask, int lane)
+{
+    for (int i = lane; i < a.npat * 9; i += 64) s_val[i] = a.st_val[i + 8 - 2 * (i % 9)];
+    for (int i = lane; i < a.npat; i += 64) s_mask[i] = (int)(__builtin_bitreverse32((unsigned)a.st_mask[i]) >> 23);
+}
+// rsum of a row over its coupled slots (U0 U1 U2 R _ O1 D0 D1 D2 = slots 0 .. 8), in ascending ORIGINAL column order:
+// slot order forward, reversed slot order in mirrored coordinates.  hot: every union slot is coupled (scalar values)
+template <unsigned UM, bool BWD>
+__device__ __forceinline__ double rsum_hot(const double *hv, double U0, double U1, double U2, double R, double O1, double D0,
+                                           double D1, double D2)
+{
+    const double w[9] = {U0, U1, U2, R, 0.0, O1, D0, D1, D2};
+    double rsum = 0.0;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        const int q = BWD ? 8 - k : k;
+        if (q != 4 && ((UM >> q) & 1u)) rsum = rsum + hv[q] * w[q];
+    }
+    return rsum;
+}
+template <unsigned UM, bool BWD>
+__device__ __forceinline__ double rsum_masked(const double *vv, int m, double U0, double U1, double U2, double R, double O1,
+                                              double D0, double D1, double D2)
+{
+    const double w[9] = {U0, U1, U2, R, 0.0, O1, D0, D1, D2};
+    double rsum = 0.0;
+    double t_;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        const int q = BWD ? 8 - k : k;
+        if (q != 4 && ((UM >> q) & 1u)) { t_ = rsum + vv[q] * w[q]; rsum = ((m >> q) & 1) ? t_ : rsum; }
+    }
+    return rsum;
+}
+
 struct Ahead {          // what iteration it + kPF needs (two columns), on its way through memory
     u4 own, down, up, b;
     int pid2, flag, flag_old;
@@ -92,7 +140,8 @@ struct Ahead {          // what iteration it + kPF needs (two columns), on its w
 // smaller tickets, so a band only ever waits for bands that are running or done.  The pipeline fill (64 * SK steps per
 // band, two thirds of a sweep at 4097^2) is paid once per launch instead of once per sweep.  All result stores are
 // write-through and all loads of x bypass the caches in this mode (other workgroups read / wrote them in this launch).
-template <unsigned UM, bool MULTI>
+// BWD: the backward sweep in mirrored coordinates (see pair_off_d): x, y, i below are mirrored, every address is stored n-1-i.
+template <unsigned UM, bool MULTI, bool BWD = false>
 __global__ void __launch_bounds__(64) gs_wavefront_kernel(GArgs a)
 {
     constexpr int SK = (UM & 4u) ? 2 : 1;
@@ -101,8 +150,12 @@ __global__ void __launch_bounds__(64) gs_wavefront_kernel(GArgs a)
     __shared__ int s_mask[kMaxPat];
     __shared__ int s_band;
     const int lane = threadIdx.x;
-    for (int i = lane; i < a.npat * 9; i += 64) s_val[i] = a.st_val[i];
-    for (int i = lane; i < a.npat; i += 64) s_mask[i] = a.st_mask[i];
+    if constexpr (BWD) {
+        load_patterns_mirrored(a, s_val, s_mask, lane);
+    } else {
+        for (int i = lane; i < a.npat * 9; i += 64) s_val[i] = a.st_val[i];
+        for (int i = lane; i < a.npat; i += 64) s_mask[i] = a.st_mask[i];
+    }
     if (lane == 0) s_band = atomicAdd(&a.work[1], 1);
     __syncthreads();
     const int ticket = __builtin_amdgcn_readfirstlane(s_band);
@@ -130,15 +183,16 @@ __global__ void __launch_bounds__(64) gs_wavefront_kernel(GArgs a)
     auto fetch = [&](int itf, Ahead &A) {
         const int xf = 2 * itf - SK * lane;
         const int64_t i = base + xf;
-        A.own = __builtin_amdgcn_raw_buffer_load_b128(rs_x, pair_off(i + 1, n), 0, kXPol);      // old (y, xf+1), (y, xf+2)
-        A.down = __builtin_amdgcn_raw_buffer_load_b128(rs_x, pair_off(i + W + 1, n), 0, kXPol); // old (y+1, xf+1), (y+1, xf+2)
-        A.b = __builtin_amdgcn_raw_buffer_load_b128(rs_b, pair_off(i, n), 0, 0);
+        A.own = __builtin_amdgcn_raw_buffer_load_b128(rs_x, pair_off_d<BWD>(i + 1, n), 0, kXPol);      // old (y, xf+1), (y, xf+2)
+        A.down = __builtin_amdgcn_raw_buffer_load_b128(rs_x, pair_off_d<BWD>(i + W + 1, n), 0, kXPol); // old (y+1, xf+1), (y+1, xf+2)
+        A.b = __builtin_amdgcn_raw_buffer_load_b128(rs_b, pair_off_d<BWD>(i, n), 0, 0);
         {
-            const int64_t j = i + (i == -1 ? 1 : 0) - (i == (int64_t)n - 1 ? 1 : 0);
+            const int64_t im = BWD ? (int64_t)n - 2 - i : i;
+            const int64_t j = im + (im == -1 ? 1 : 0) - (im == (int64_t)n - 1 ? 1 : 0);
             A.pid2 = (int)__builtin_amdgcn_raw_buffer_load_b16(rs_p, (j >= 0 && j + 1 < n) ? (unsigned)j : kOOB, 0, 0);
         }
         // lane 0: new (y-1, xf+SK-1), (y-1, xf+SK) of the previous band, write-through data -> L1 bypass
-        A.up = __builtin_amdgcn_raw_buffer_load_b128(rs_x, lane == 0 ? pair_off(i - W + (SK - 1), n) : kOOB, 0, kSc1);
+        A.up = __builtin_amdgcn_raw_buffer_load_b128(rs_x, lane == 0 ? pair_off_d<BWD>(i - W + (SK - 1), n) : kOOB, 0, kSc1);
         A.flag = __hip_atomic_load(prog_prev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         A.flag_old = MULTI ? __hip_atomic_load(prog_old, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
     };
@@ -183,7 +237,7 @@ __global__ void __launch_bounds__(64) gs_wavefront_kernel(GArgs a)
     {   // windows just before the first step (column x0 = -SK lane): what the first shift moves into place
         const int64_t i0 = base - SK * lane;
         auto one = [&](int64_t i) {
-            const u2 v = __builtin_amdgcn_raw_buffer_load_b64(rs_x, (i >= 0 && i < n) ? (unsigned)i * 8u : kOOB, 0, kSc1);
+            const u2 v = __builtin_amdgcn_raw_buffer_load_b64(rs_x, (i >= 0 && i < n) ? (unsigned)(BWD ? n - 1 - i : i) * 8u : kOOB, 0, kSc1);
             return __hiloint2double((int)v.y, (int)v.x);
         };
         O1 = one(i0);                         // old (y, x0)
@@ -214,15 +268,7 @@ __global__ void __launch_bounds__(64) gs_wavefront_kernel(GArgs a)
         const bool act = line_ok && x >= 0 && x < W && i < n;
         double xn;
         if (__all(act && p_in == hot)) {                       // wave-uniform
-            double rsum = 0.0;
-            if ((UM >> 0) & 1u) rsum = rsum + hv[0] * U0;
-            if ((UM >> 1) & 1u) rsum = rsum + hv[1] * U1;
-            if ((UM >> 2) & 1u) rsum = rsum + hv[2] * U2;
-            if ((UM >> 3) & 1u) rsum = rsum + hv[3] * R;
-            if ((UM >> 5) & 1u) rsum = rsum + hv[5] * O1;
-            if ((UM >> 6) & 1u) rsum = rsum + hv[6] * D0;
-            if ((UM >> 7) & 1u) rsum = rsum + hv[7] * D1;
-            if ((UM >> 8) & 1u) rsum = rsum + hv[8] * D2;
+            const double rsum = rsum_hot<UM, BWD>(hv, U0, U1, U2, R, O1, D0, D1, D2);
             xn = (bval - rsum) / hv[4];
             R = xn;
         } else {
@@ -231,16 +277,7 @@ __global__ void __launch_bounds__(64) gs_wavefront_kernel(GArgs a)
             double vv[9];
 #pragma unroll
             for (int q = 0; q < 9; ++q) vv[q] = ((UM >> q) & 1u) ? s_val[p * 9 + q] : 0.0;     // all reads up front
-            double rsum = 0.0;
-            double t_;
-            if ((UM >> 0) & 1u) { t_ = rsum + vv[0] * U0; rsum = ((m >> 0) & 1) ? t_ : rsum; }
-            if ((UM >> 1) & 1u) { t_ = rsum + vv[1] * U1; rsum = ((m >> 1) & 1) ? t_ : rsum; }
-            if ((UM >> 2) & 1u) { t_ = rsum + vv[2] * U2; rsum = ((m >> 2) & 1) ? t_ : rsum; }
-            if ((UM >> 3) & 1u) { t_ = rsum + vv[3] * R; rsum = ((m >> 3) & 1) ? t_ : rsum; }
-            if ((UM >> 5) & 1u) { t_ = rsum + vv[5] * O1; rsum = ((m >> 5) & 1) ? t_ : rsum; }
-            if ((UM >> 6) & 1u) { t_ = rsum + vv[6] * D0; rsum = ((m >> 6) & 1) ? t_ : rsum; }
-            if ((UM >> 7) & 1u) { t_ = rsum + vv[7] * D1; rsum = ((m >> 7) & 1) ? t_ : rsum; }
-            if ((UM >> 8) & 1u) { t_ = rsum + vv[8] * D2; rsum = ((m >> 8) & 1) ? t_ : rsum; }
+            const double rsum = rsum_masked<UM, BWD>(vv, m, U0, U1, U2, R, O1, D0, D1, D2);
             const double diag = ((m >> 4) & 1) ? vv[4] : 0.0;
             const double q_ = (bval - rsum) / (diag != 0.0 ? diag : 1.0);
             xn = diag != 0.0 ? q_ : O0;
@@ -259,10 +296,15 @@ __global__ void __launch_bounds__(64) gs_wavefront_kernel(GArgs a)
             flag_old_seen = cur.flag_old;
             const int64_t i = base + x;
             // which half of a pair is which (only the pairs straddling element 0 / n-1 are special)
-            auto first = [&](const u4 &v, int64_t ii) { return ii == (int64_t)n - 1 ? hi2(v) : lo2(v); };
-            auto second = [&](const u4 &v, int64_t ii) { return ii == -1 ? lo2(v) : hi2(v); };
-            const int pa = (i == (int64_t)n - 1) ? (cur.pid2 >> 8) & 0xff : cur.pid2 & 0xff;
-            const int pb = (i == -1) ? cur.pid2 & 0xff : (cur.pid2 >> 8) & 0xff;
+            // (BWD: a pair comes in stored order, i.e. the two mirrored elements swapped)
+            auto first = [&](const u4 &v, int64_t ii) {
+                return BWD ? (ii == (int64_t)n - 1 ? lo2(v) : hi2(v)) : (ii == (int64_t)n - 1 ? hi2(v) : lo2(v));
+            };
+            auto second = [&](const u4 &v, int64_t ii) { return BWD ? (ii == -1 ? hi2(v) : lo2(v)) : (ii == -1 ? lo2(v) : hi2(v)); };
+            const int pa = BWD ? ((i == (int64_t)n - 1) ? cur.pid2 & 0xff : (cur.pid2 >> 8) & 0xff)
+                               : ((i == (int64_t)n - 1) ? (cur.pid2 >> 8) & 0xff : cur.pid2 & 0xff);
+            const int pb = BWD ? ((i == -1) ? (cur.pid2 >> 8) & 0xff : cur.pid2 & 0xff)
+                               : ((i == -1) ? cur.pid2 & 0xff : (cur.pid2 >> 8) & 0xff);
             // ---- next loads ----------------------------------------------------------------------------
             wait_for_prev(it + kPF, flag_seen, flag_old_seen);
             fetch(it + kPF, ring[u]);
@@ -281,16 +323,18 @@ __global__ void __launch_bounds__(64) gs_wavefront_kernel(GArgs a)
             // load is counted behind them in vmcnt); all other lanes use plain stores, flushed at the kernel boundary.
             const bool actA = line_ok && x >= 0 && x < W && i < n, actB = line_ok && x + 1 >= 0 && x + 1 < W && i + 1 < n;
             const bool shared = MULTI || lane == last_lane;
+            // (BWD: mirrored elements i, i + 1 are stored n-1-i, n-2-i: the pair goes to n-2-i in stored order)
             u4 v4;
-            v4.x = (unsigned)__double2loint(xa);
-            v4.y = (unsigned)__double2hiint(xa);
-            v4.z = (unsigned)__double2loint(xb);
-            v4.w = (unsigned)__double2hiint(xb);
-            const unsigned off16 = (actA && actB) ? (unsigned)i * 8u : kOOB;
+            v4.x = (unsigned)__double2loint(BWD ? xb : xa);
+            v4.y = (unsigned)__double2hiint(BWD ? xb : xa);
+            v4.z = (unsigned)__double2loint(BWD ? xa : xb);
+            v4.w = (unsigned)__double2hiint(BWD ? xa : xb);
+            const unsigned off16 = (actA && actB) ? (unsigned)(BWD ? (int64_t)n - 2 - i : i) * 8u : kOOB;
             u2 v2;
-            v2.x = actA ? v4.x : v4.z;
-            v2.y = actA ? v4.y : v4.w;
-            const unsigned off8 = (actA != actB) ? (unsigned)(actA ? i : i + 1) * 8u : kOOB;
+            v2.x = actA != BWD ? v4.x : v4.z;
+            v2.y = actA != BWD ? v4.y : v4.w;
+            const int64_t i8 = actA ? i : i + 1;
+            const unsigned off8 = (actA != actB) ? (unsigned)(BWD ? (int64_t)n - 1 - i8 : i8) * 8u : kOOB;
             __builtin_amdgcn_raw_buffer_store_b128(v4, rs_x, shared ? kOOB : off16, 0, 0);
             __builtin_amdgcn_raw_buffer_store_b64(v2, rs_x, shared ? kOOB : off8, 0, 0);
             __builtin_amdgcn_raw_buffer_store_b128(v4, rs_x, shared ? off16 : kOOB, 0, kSc1);
@@ -340,7 +384,10 @@ constexpr int kFlushLag = 5;                               // chunk p - 5 is com
 // band b of sweep s asks for chunk c once band b + 1 of sweep s - 1 -- the last band: band b itself -- has FLUSHED chunk c: then its
 // own 64 lines and the line below hold the previous sweep's final values there, and nobody will read what this band overwrites).
 // Every line is then stored write-through and x comes in past the caches, like the line above always does.
-template <unsigned UM, bool MULTI = false>
+// BWD: the backward sweep in mirrored coordinates (see pair_off_d).  Chunk c then covers stored columns [W - 16 (c+1), W - 16 c) of the
+// stored lines lines - 1 - y (the partial chunk at the low end; the line above a band sits one line BELOW it in memory).  The tile
+// stays in stored order (the DMA destination is lane-linear); a lane reads tile column 15 - (x mod 16) for mirrored column x.
+template <unsigned UM, bool MULTI = false, bool BWD = false>
 __global__ void __launch_bounds__(64) gs_band_lds_kernel(GArgs a)
 {
     // SK = 2 (the upper-right slot is coupled: 9-point operators): lane l relaxes column t - 2 l, and a band has 32 lines (lanes
@@ -353,8 +400,12 @@ __global__ void __launch_bounds__(64) gs_band_lds_kernel(GArgs a)
     __shared__ int s_mask[kMaxPat];
     __shared__ int s_band;
     const int lane = threadIdx.x;
-    for (int i = lane; i < a.npat * 9; i += 64) s_val[i] = a.st_val[i];
-    for (int i = lane; i < a.npat; i += 64) s_mask[i] = a.st_mask[i];
+    if constexpr (BWD) {
+        load_patterns_mirrored(a, s_val, s_mask, lane);
+    } else {
+        for (int i = lane; i < a.npat * 9; i += 64) s_val[i] = a.st_val[i];
+        for (int i = lane; i < a.npat; i += 64) s_mask[i] = a.st_mask[i];
+    }
     if (lane == 0) s_band = atomicAdd(&a.work[1], 1);
     __syncthreads();
     const int ticket = __builtin_amdgcn_readfirstlane(s_band);
@@ -373,6 +424,11 @@ __global__ void __launch_bounds__(64) gs_band_lds_kernel(GArgs a)
     const int *prog_old = has_old ? prog - a.nbands + min(band + 1, a.nbands - 1) : a.work;
     constexpr int kXPol = MULTI ? kSc1 : 0;                           // cache policy of the band's own loads of x
     const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(a.x, 0, (int)((unsigned)n * 8u), 0x00020000);
+    // stored line of (mirrored) line yy, stored column of tile column 0 of chunk c, tile column of (mirrored) column x
+    const int lines = a.lines;
+    auto mline = [&](int yy) -> int64_t { return BWD ? lines - 1 - yy : yy; };
+    auto mcol0 = [&](int c) -> int { return BWD ? W - kCW * (c + 1) : c * kCW; };
+    auto tcol = [&](unsigned x) -> unsigned { return BWD ? (x & 15u) ^ 15u : x & 15u; };
 
     // ---- LDS addressing: plain rows of 128 B.  Lane l reads row l at column t - l: the SKEW of the wavefront spreads the
     // 64 lanes over the banks by itself (30 l + 2 t mod 64 dwords: conflict-free; an XOR swizzle of the pieces made it 5x worse)
@@ -381,35 +437,63 @@ __global__ void __launch_bounds__(64) gs_band_lds_kernel(GArgs a)
     auto taddr = [&](unsigned roff, unsigned f, int col) -> unsigned {
         return (((unsigned)col >> 4) & (kNCH - 1)) * kSlotBytes + roff + ((((unsigned)col >> 1) & 7u) ^ f) * 16u + ((unsigned)col & 1u) * 8u;
     };
-    const unsigned palign = (unsigned)(((int64_t)y * W) & 3);         // byte misalignment of the lane's line in the id array
+    // byte misalignment of the lane's chunks in the id array
+    const unsigned palign = BWD ? (unsigned)((mline(y) * W + mcol0(0)) & 3) : (unsigned)(((int64_t)y * W) & 3);
     auto ldsd = [&](unsigned off) -> double { return *reinterpret_cast<const double *>(s_tile + off); };
 
     // ---- chunk c comes in: 9 + 8 instructions of 8 lines x 128 B, 5 dwords of ids per line, the line above -------------
     auto issue_up = [&](int c) {                                      // the last line of the band above, columns of chunk c
         if (c > cmax || band == 0) return;
         if (lane < 8) {
-            const int64_t idx = (int64_t)(y0 - 1) * W + c * kCW + 2 * lane;
+            const int64_t idx = BWD ? mline(y0 - 1) * W + mcol0(c) + 2 * lane : (int64_t)(y0 - 1) * W + c * kCW + 2 * lane;
             LMG_GLDS(a.x + idx, s_tile + (c & (kNCH - 1)) * kSlotBytes + kXSBytes + kBSBytes + kPSBytes, 16, kSc1);   // written write-through there
         }
     };
     auto issue_chunk = [&](int c, bool with_up) {
         if (c > cmax) return;                                         // uniform
         unsigned char *sb = s_tile + (c & (kNCH - 1)) * kSlotBytes;
-        const int col0 = c * kCW;
-        const int r = lane >> 3, q = lane & 7;
+        if constexpr (!BWD) {
+            const int col0 = c * kCW;
+            const int r = lane >> 3, q = lane & 7;
 #pragma unroll
-        for (int g = 0; g < 9; ++g) {
-            const int row = 8 * g + r;
-            const int pce = q;
-            const int64_t idx = (int64_t)(y0 + row) * W + col0 + 2 * pce;
-            // (a piece that straddles the end of the vector is 16-byte aligned: the vectors are, and n - 1 is even there)
-            if (row <= NL && y0 + row < a.lines && idx < n) LMG_GLDS(a.x + idx, sb + g * 1024, 16, kXPol);
-            if (row < NL && y0 + row < a.lines && idx < n) LMG_GLDS(a.b + idx, sb + kXSBytes + g * 1024, 16, 0);
-        }
-        if (line_ok) {
-            const unsigned char *src = a.pid + ((int64_t)y * W - palign) + col0;
+            for (int g = 0; g < 9; ++g) {
+                const int row = 8 * g + r;
+                const int pce = q;
+                const int64_t idx = (int64_t)(y0 + row) * W + col0 + 2 * pce;
+                // (a piece that straddles the end of the vector is 16-byte aligned: the vectors are, and n - 1 is even there)
+                if (row <= NL && y0 + row < a.lines && idx < n) LMG_GLDS(a.x + idx, sb + g * 1024, 16, kXPol);
+                if (row < NL && y0 + row < a.lines && idx < n) LMG_GLDS(a.b + idx, sb + kXSBytes + g * 1024, 16, 0);
+            }
+            if (line_ok) {
+                const unsigned char *src = a.pid + ((int64_t)y * W - palign) + col0;
 #pragma unroll
-            for (int k = 0; k < 5; ++k) LMG_GLDS(src + 4 * k, sb + kXSBytes + kBSBytes + k * 256, 4, 0);
+                for (int k = 0; k < 5; ++k) LMG_GLDS(src + 4 * k, sb + kXSBytes + kBSBytes + k * 256, 4, 0);
+            }
+        } else {
+            const int col0 = mcol0(c);
+            const int r = lane >> 3, q = lane & 7;
+#pragma unroll
+            for (int g = 0; g < 9; ++g) {
+                const int row = 8 * g + r;
+                const int64_t idx = mline(y0 + row) * W + col0 + 2 * q;
+                // nothing reaches past the end of the vector, but the partial chunk of stored line 0 can start before it
+                if (row <= NL && y0 + row < a.lines && idx >= 0) LMG_GLDS(a.x + idx, sb + g * 1024, 16, kXPol);
+                if (row < NL && y0 + row < a.lines && idx >= 0) LMG_GLDS(a.b + idx, sb + kXSBytes + g * 1024, 16, 0);
+            }
+            // odd W: that chunk starts at stored column -1, its piece (-1, 0) was not requested: element 0 comes in through a
+            // plain load into the piece's second half (only in the band whose tile holds stored line 0)
+            const int rl = a.lines - 1 - y0;                              // tile row of stored line 0
+            if ((W & 1) && c == cmax && rl <= NL && lane == 0) {          // (the condition before lane == 0 is uniform)
+                unsigned char *pc = sb + (rl >> 3) * 1024 + ((rl & 7) * 8 + (-1 - col0) / 2) * 16 + 8;
+                *reinterpret_cast<u2 *>(pc) = __builtin_amdgcn_raw_buffer_load_b64(rs_x, 0u, 0, kXPol);
+                if (rl < NL) *reinterpret_cast<double *>(pc + kXSBytes) = a.b[0];
+            }
+            if (line_ok) {
+                const int64_t po = mline(y) * W - palign + col0;           // below 0 in the partial chunk of stored line 0
+#pragma unroll
+                for (int k = 0; k < 5; ++k)
+                    if (po + 4 * k >= 0) LMG_GLDS(a.pid + po + 4 * k, sb + kXSBytes + kBSBytes + k * 256, 4, 0);
+            }
         }
         if (with_up) issue_up(c);
     };
@@ -417,7 +501,7 @@ __global__ void __launch_bounds__(64) gs_band_lds_kernel(GArgs a)
     auto flush_chunk = [&](int fc) {
         if (fc < 0 || fc > cmax) return;
         const unsigned char *sb = s_tile + (fc & (kNCH - 1)) * kSlotBytes;
-        const int col0 = fc * kCW;
+        const int col0 = BWD ? mcol0(fc) : fc * kCW;
         const int r = lane >> 3, q = lane & 7;
 #pragma unroll
         for (int g = 0; g < 8; ++g) {
@@ -425,13 +509,14 @@ __global__ void __launch_bounds__(64) gs_band_lds_kernel(GArgs a)
             const int row = 8 * g + r;
             const int col = col0 + 2 * q;
             const u4 v = *reinterpret_cast<const u4 *>(sb + g * 1024 + lane * 16);
-            const int64_t i = (int64_t)(y0 + row) * W + col;
+            const int64_t i = BWD ? mline(y0 + row) * W + col : (int64_t)(y0 + row) * W + col;
             const bool rok = row <= last_lane;
-            const unsigned off16 = (rok && col + 1 < W) ? (unsigned)i * 8u : kOOB;
-            const unsigned off8 = (rok && col + 1 == W) ? (unsigned)i * 8u : kOOB;
+            // (BWD: the piece (-1, 0) of a partial chunk keeps only its second element, pieces further left nothing)
+            const unsigned off16 = (rok && (BWD ? col >= 0 : col + 1 < W)) ? (unsigned)i * 8u : kOOB;
+            const unsigned off8 = (rok && (BWD ? col == -1 : col + 1 == W)) ? (unsigned)(BWD ? i + 1 : i) * 8u : kOOB;
             u2 v2;
-            v2.x = v.x;
-            v2.y = v.y;
+            v2.x = BWD ? v.z : v.x;
+            v2.y = BWD ? v.w : v.y;
             if (MULTI || g == (last_lane >> 3)) {                     // uniform: the group with the line the next band reads
                 __builtin_amdgcn_raw_buffer_store_b128(v, rs_x, off16, 0, kSc1);
                 __builtin_amdgcn_raw_buffer_store_b64(v2, rs_x, off8, 0, kSc1);
@@ -485,19 +570,19 @@ __global__ void __launch_bounds__(64) gs_band_lds_kernel(GArgs a)
         In I;
         const unsigned c1 = (unsigned)(x + 1);
         const unsigned s1 = ((c1 >> 4) & (kNCH - 1)) * kSlotBytes, pc1 = (c1 >> 1) & 7u, h1 = (c1 & 1u) * 8u;
-        const unsigned own_addr = s1 + rowoff + pc1 * 16u + h1;
+        const unsigned own_addr = BWD ? s1 + rowoff + tcol(c1) * 8u : s1 + rowoff + pc1 * 16u + h1;
         I.own1 = ldsd(own_addr);
         I.down2 = ldsd(own_addr + 128u);
         I.b = ldsd(own_addr_prev + kXSBytes);
         own_addr_prev = own_addr;
         const unsigned sbo = (((unsigned)x >> 4) & (kNCH - 1)) * kSlotBytes;
-        const unsigned o = palign + ((unsigned)x & 15u);
+        const unsigned o = palign + tcol((unsigned)x);
         I.p = (int)s_tile[sbo + kXSBytes + kBSBytes + (o >> 2) * 256u + (unsigned)lane * 4u + (o & 3u)];
         if (SK == 1) {
-            I.up = ldsd(sbo + kXSBytes + kBSBytes + kPSBytes + ((unsigned)x & 15u) * 8u);
+            I.up = ldsd(sbo + kXSBytes + kBSBytes + kPSBytes + tcol((unsigned)x) * 8u);
         } else {                                                      // the line above at column x + 1 (its upper-right neighbour)
             const unsigned xu = (unsigned)(x + 1);
-            I.up = ldsd(((xu >> 4) & (kNCH - 1)) * kSlotBytes + kXSBytes + kBSBytes + kPSBytes + (xu & 15u) * 8u);
+            I.up = ldsd(((xu >> 4) & (kNCH - 1)) * kSlotBytes + kXSBytes + kBSBytes + kPSBytes + tcol(xu) * 8u);
         }
         return I;
     };
@@ -588,15 +673,20 @@ __global__ void __launch_bounds__(64) gs_band_lds_kernel(GArgs a)
         const bool act = line_ok && x >= 0 && x < W;
         double xn;
         if (__all(act && cur.p == hot)) {                              // wave-uniform
-            double rsum = 0.0;
-            if ((UM >> 0) & 1u) rsum = rsum + hv[0] * U0;
-            if ((UM >> 1) & 1u) rsum = rsum + hv[1] * U1;
-            if ((UM >> 2) & 1u) rsum = rsum + hv[2] * U2;
-            if ((UM >> 3) & 1u) rsum = rsum + hv[3] * R;
-            if ((UM >> 5) & 1u) rsum = rsum + hv[5] * O1;
-            if ((UM >> 6) & 1u) rsum = rsum + hv[6] * D0;
-            if ((UM >> 7) & 1u) rsum = rsum + hv[7] * D1;
-            if ((UM >> 8) & 1u) rsum = rsum + hv[8] * D2;
+            double rsum;
+            if constexpr (BWD) {
+                rsum = rsum_hot<UM, BWD>(hv, U0, U1, U2, R, O1, D0, D1, D2);
+            } else {      // (written out: the forward kernel keeps its code -- through the helper it is scheduled differently)
+                rsum = 0.0;
+                if ((UM >> 0) & 1u) rsum = rsum + hv[0] * U0;
+                if ((UM >> 1) & 1u) rsum = rsum + hv[1] * U1;
+                if ((UM >> 2) & 1u) rsum = rsum + hv[2] * U2;
+                if ((UM >> 3) & 1u) rsum = rsum + hv[3] * R;
+                if ((UM >> 5) & 1u) rsum = rsum + hv[5] * O1;
+                if ((UM >> 6) & 1u) rsum = rsum + hv[6] * D0;
+                if ((UM >> 7) & 1u) rsum = rsum + hv[7] * D1;
+                if ((UM >> 8) & 1u) rsum = rsum + hv[8] * D2;
+            }
             xn = hpow2 ? (cur.b - rsum) * hrc : (cur.b - rsum) / hv[4];
             R = xn;
         } else {
@@ -605,16 +695,21 @@ __global__ void __launch_bounds__(64) gs_band_lds_kernel(GArgs a)
             double vv[9];
 #pragma unroll
             for (int q = 0; q < 9; ++q) vv[q] = ((UM >> q) & 1u) ? s_val[pq * 9 + q] : 0.0;
-            double rsum = 0.0;
-            double t_;
-            if ((UM >> 0) & 1u) { t_ = rsum + vv[0] * U0; rsum = ((m >> 0) & 1) ? t_ : rsum; }
-            if ((UM >> 1) & 1u) { t_ = rsum + vv[1] * U1; rsum = ((m >> 1) & 1) ? t_ : rsum; }
-            if ((UM >> 2) & 1u) { t_ = rsum + vv[2] * U2; rsum = ((m >> 2) & 1) ? t_ : rsum; }
-            if ((UM >> 3) & 1u) { t_ = rsum + vv[3] * R; rsum = ((m >> 3) & 1) ? t_ : rsum; }
-            if ((UM >> 5) & 1u) { t_ = rsum + vv[5] * O1; rsum = ((m >> 5) & 1) ? t_ : rsum; }
-            if ((UM >> 6) & 1u) { t_ = rsum + vv[6] * D0; rsum = ((m >> 6) & 1) ? t_ : rsum; }
-            if ((UM >> 7) & 1u) { t_ = rsum + vv[7] * D1; rsum = ((m >> 7) & 1) ? t_ : rsum; }
-            if ((UM >> 8) & 1u) { t_ = rsum + vv[8] * D2; rsum = ((m >> 8) & 1) ? t_ : rsum; }
+            double rsum;
+            if constexpr (BWD) {
+                rsum = rsum_masked<UM, BWD>(vv, m, U0, U1, U2, R, O1, D0, D1, D2);
+            } else {
+                rsum = 0.0;
+                double t_;
+                if ((UM >> 0) & 1u) { t_ = rsum + vv[0] * U0; rsum = ((m >> 0) & 1) ? t_ : rsum; }
+                if ((UM >> 1) & 1u) { t_ = rsum + vv[1] * U1; rsum = ((m >> 1) & 1) ? t_ : rsum; }
+                if ((UM >> 2) & 1u) { t_ = rsum + vv[2] * U2; rsum = ((m >> 2) & 1) ? t_ : rsum; }
+                if ((UM >> 3) & 1u) { t_ = rsum + vv[3] * R; rsum = ((m >> 3) & 1) ? t_ : rsum; }
+                if ((UM >> 5) & 1u) { t_ = rsum + vv[5] * O1; rsum = ((m >> 5) & 1) ? t_ : rsum; }
+                if ((UM >> 6) & 1u) { t_ = rsum + vv[6] * D0; rsum = ((m >> 6) & 1) ? t_ : rsum; }
+                if ((UM >> 7) & 1u) { t_ = rsum + vv[7] * D1; rsum = ((m >> 7) & 1) ? t_ : rsum; }
+                if ((UM >> 8) & 1u) { t_ = rsum + vv[8] * D2; rsum = ((m >> 8) & 1) ? t_ : rsum; }
+            }
             const double diag = ((m >> 4) & 1) ? vv[4] : 0.0;
             const double q_ = (cur.b - rsum) / (diag != 0.0 ? diag : 1.0);
             xn = diag != 0.0 ? q_ : O0;
@@ -640,24 +735,24 @@ __global__ void __launch_bounds__(64) gs_band_lds_kernel(GArgs a)
     publish(W);
 }
 
-template <unsigned UM>
+template <unsigned UM, bool BWD>
 int launch_lds(GArgs a, hipStream_t st)
 {
     if (a.sweeps > 1)
-        hipLaunchKernelGGL((gs_band_lds_kernel<UM, true>), dim3((unsigned)(a.nbands * a.sweeps)), dim3(64), 0, st, a);
+        hipLaunchKernelGGL((gs_band_lds_kernel<UM, true, BWD>), dim3((unsigned)(a.nbands * a.sweeps)), dim3(64), 0, st, a);
     else
-        hipLaunchKernelGGL((gs_band_lds_kernel<UM, false>), dim3((unsigned)a.nbands), dim3(64), 0, st, a);
+        hipLaunchKernelGGL((gs_band_lds_kernel<UM, false, BWD>), dim3((unsigned)a.nbands), dim3(64), 0, st, a);
     LMG_CHECK_LAUNCH();
     return LMG_OK;
 }
 
-template <unsigned UM>
+template <unsigned UM, bool BWD>
 int launch(GArgs a, hipStream_t st)
 {
     if (a.sweeps > 1)
-        hipLaunchKernelGGL((gs_wavefront_kernel<UM, true>), dim3((unsigned)(a.nbands * a.sweeps)), dim3(64), 0, st, a);
+        hipLaunchKernelGGL((gs_wavefront_kernel<UM, true, BWD>), dim3((unsigned)(a.nbands * a.sweeps)), dim3(64), 0, st, a);
     else
-        hipLaunchKernelGGL((gs_wavefront_kernel<UM, false>), dim3((unsigned)a.nbands), dim3(64), 0, st, a);
+        hipLaunchKernelGGL((gs_wavefront_kernel<UM, false, BWD>), dim3((unsigned)a.nbands), dim3(64), 0, st, a);
     LMG_CHECK_LAUNCH();
     return LMG_OK;
 }
@@ -724,9 +819,14 @@ int64_t lmg_stencil_gs_work_bytes(int64_t n, int32_t line_stride)
     return 4 * (kMaxSweeps * nbands + 3) + 4;
 }
 
-int lmg_stencil_gs_sweep(int64_t n, int32_t line_stride, const uint8_t *pid, int32_t npat, const double *st_val,
-                         const int32_t *st_mask, uint32_t union_mask, int32_t hot_pattern, const double *h_hot_val,
-                         double *x, const double *b, void *work, int sweeps, void *stream)
+}  // extern "C"
+
+namespace {
+
+template <bool BWD>
+int gs_sweep(int64_t n, int32_t line_stride, const uint8_t *pid, int32_t npat, const double *st_val, const int32_t *st_mask,
+             uint32_t union_mask, int32_t hot_pattern, const double *h_hot_val, double *x, const double *b, void *work, int sweeps,
+             void *stream)
 {
     if (n < 0 || n >= (1ll << 29) - 8192 || npat < 1 || npat > kMaxPat || sweeps < 0) return LMG_ERR_ARG;        // 32-bit byte offsets
     if (n == 0 || sweeps == 0) return LMG_OK;
@@ -750,7 +850,7 @@ int lmg_stencil_gs_sweep(int64_t n, int32_t line_stride, const uint8_t *pid, int
     a.hot_rcp = 0.0;
     if (hot_pattern >= 0 && hot_pattern < npat && h_hot_val && h_hot_val[4] != 0.0) {
         a.hot = hot_pattern;
-        for (int k = 0; k < 9; ++k) a.hot_val[k] = h_hot_val[k];
+        for (int k = 0; k < 9; ++k) a.hot_val[k] = h_hot_val[BWD ? 8 - k : k];     // (BWD: mirrored slots, see load_patterns)
         int e = 0;
         const double mant = frexp(h_hot_val[4], &e);
         // +-2^k, with 1 / d still a normal number: t / d and t * (1 / d) are the same correctly rounded number
@@ -779,19 +879,42 @@ int lmg_stencil_gs_sweep(int64_t n, int32_t line_stride, const uint8_t *pid, int
         if (hipMemsetAsync(a.work + 1, 0, 4 * (size_t)(a.sweeps * a.nbands + 2), st) != hipSuccess) return LMG_ERR_LAUNCH;
         int rc;
         if (use_lds) {
-            rc = union_mask == kMask5 ? launch_lds<kMask5>(a, st) : union_mask == kMask7 ? launch_lds<kMask7>(a, st) : launch_lds<kMask9>(a, st);
+            rc = union_mask == kMask5 ? launch_lds<kMask5, BWD>(a, st)
+               : union_mask == kMask7 ? launch_lds<kMask7, BWD>(a, st) : launch_lds<kMask9, BWD>(a, st);
             if (rc != LMG_OK) return rc;
             continue;
         }
         switch (union_mask) {
-        case kMask5: rc = launch<kMask5>(a, st); break;
-        case kMask9: rc = launch<kMask9>(a, st); break;
-        case kMask7: rc = launch<kMask7>(a, st); break;
-        default: rc = launch<kMask1D>(a, st); break;
+        case kMask5: rc = launch<kMask5, BWD>(a, st); break;
+        case kMask9: rc = launch<kMask9, BWD>(a, st); break;
+        case kMask7: rc = launch<kMask7, BWD>(a, st); break;
+        default: rc = launch<kMask1D, BWD>(a, st); break;
         }
         if (rc != LMG_OK) return rc;
     }
     return LMG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lmg_stencil_gs_sweep(int64_t n, int32_t line_stride, const uint8_t *pid, int32_t npat, const double *st_val,
+                         const int32_t *st_mask, uint32_t union_mask, int32_t hot_pattern, const double *h_hot_val,
+                         double *x, const double *b, void *work, int sweeps, void *stream)
+{
+    return gs_sweep<false>(n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val, x, b, work, sweeps,
+                           stream);
+}
+
+int lmg_stencil_gs_sweep_backward(int64_t n, int32_t line_stride, const uint8_t *pid, int32_t npat, const double *st_val,
+                                  const int32_t *st_mask, uint32_t union_mask, int32_t hot_pattern, const double *h_hot_val,
+                                  double *x, const double *b, void *work, int sweeps, void *stream)
+{
+    // mirrored coordinates are a plain reversal of the vector only when every line is whole
+    if (line_stride > 0 && n % line_stride != 0) return LMG_ERR_ARG;
+    return gs_sweep<true>(n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val, x, b, work, sweeps,
+                          stream);
 }
 
 }  // extern "C"

@@ -25,6 +25,21 @@ from .coarse import make_coarse_solver
 from .ops import DeviceCSR, F64
 
 
+GS_SWEEPS = ("forward", "backward", "symmetric")       # pyamg's gauss_seidel(sweep=...)
+
+
+def gs_sweep_pair(gs_sweep):
+    """(pre, post) smoothing directions of a Gauss-Seidel cycle from a pyamg sweep name (used for both) or a pair."""
+    pair = (gs_sweep, gs_sweep) if isinstance(gs_sweep, str) else tuple(gs_sweep)
+    if len(pair) != 2 or any(d not in GS_SWEEPS for d in pair):
+        raise ValueError("gs_sweep must be one of %s or a (pre, post) pair of them, got %r" % (GS_SWEEPS, gs_sweep))
+    return pair
+
+
+def _directions(sweep):
+    return ("forward", "backward") if sweep == "symmetric" else (sweep,)
+
+
 def _to_csr_host(M):
     """csr_matrix(...) exactly like SemiGeometricMG.__init__ (Multigrid.py:182): dense
     inputs lose their zeros, sparse inputs keep explicit zeros."""
@@ -208,8 +223,21 @@ class Hierarchy:
             lev.plan_RM.numeric(lev.R, lev.M, out=lev.RM)
             lev.plan_RMP.numeric(lev.RM, lev.P, out=self.levels[l + 1].M)
 
-    def gs_schedule(self, l, kind):
+    def gs_schedule(self, l, kind, direction="forward"):
+        """Schedule of the Gauss-Seidel sweep on level l, cached per (kind, direction): a backward sweep runs the sets of
+        the forward schedule in reverse order (GSSchedule.reversed), with its own schedule-ordered pattern copy."""
         lev = self.levels[l]
+        if direction != "forward":
+            key = (kind, direction)
+            if key not in lev.gs_sched:
+                if direction != "backward":
+                    raise ValueError("unknown Gauss-Seidel sweep direction %r" % (direction,))
+                sched = self.gs_schedule(l, kind).reversed()
+                prep = getattr(self.ops, "gs_prepare", None)
+                if prep is not None:
+                    prep(lev.A, sched)
+                lev.gs_sched[key] = sched
+            return lev.gs_sched[key]
         if kind not in lev.gs_sched:
             if lev.host_pattern is None:
                 lev.host_pattern = (lev.A.rowptr.cpu().numpy(), lev.A.colidx.cpu().numpy())
@@ -226,10 +254,12 @@ class Hierarchy:
         return lev.gs_sched[kind]
 
     # ------------------------------------------------------------------ solve ----------
-    def smooth(self, l, smoother, steps, omega, gs_mode, x_is_zero=False):
+    def smooth(self, l, smoother, steps, omega, gs_mode, x_is_zero=False, direction="forward"):
         """`steps` smoothing sweeps on level l.  x_is_zero: the iterate is known to be zero
         (coarse levels start from zeros, Multigrid.py:103): the first Jacobi sweep then is
-        x = omega * (D^-1 b) -- same bits, a third of the bytes -- and nobody has to clear x."""
+        x = omega * (D^-1 b) -- same bits, a third of the bytes -- and nobody has to clear x.
+        direction (Gauss-Seidel only): "forward" | "backward" | "symmetric" (pyamg's sweep: a forward then a backward
+        sweep per step -- two launches per step, the backward sweep cannot start before the forward one has finished)."""
         lev = self.levels[l]
         if steps <= 0:
             if x_is_zero:
@@ -238,11 +268,12 @@ class Hierarchy:
         if smoother == "GaussSeidel":
             if x_is_zero:
                 self.ops.zero(lev.x)
-            if self._wavefront_gs(l, gs_mode):
-                # grid-stencil level: exact forward sweep as a pipelined wavefront, no schedule needed
-                self.ops.stencil_gs(lev.A, lev.x, lev.b, steps)
+            if direction == "symmetric":
+                for _ in range(steps):
+                    self._gs(l, gs_mode, 1, "forward")
+                    self._gs(l, gs_mode, 1, "backward")
             else:
-                self.ops.csr_gs_schedule(lev.A, lev.x, lev.b, self.gs_schedule(l, gs_mode), steps)
+                self._gs(l, gs_mode, steps, direction)
         elif smoother == "Jacobi":
             if x_is_zero:
                 if lev.dinv is None:
@@ -256,9 +287,24 @@ class Hierarchy:
         else:
             raise ValueError("unknown smoother %r" % (smoother,))
 
-    def _wavefront_gs(self, l, gs_mode):
+    def _gs(self, l, gs_mode, steps, direction):
+        lev = self.levels[l]
+        if direction not in ("forward", "backward"):
+            raise ValueError("unknown Gauss-Seidel sweep direction %r" % (direction,))
+        if self._wavefront_gs(l, gs_mode, direction):
+            # grid-stencil level: exact sweep as a pipelined wavefront, no schedule needed
+            if direction == "forward":
+                self.ops.stencil_gs(lev.A, lev.x, lev.b, steps)
+            else:
+                self.ops.stencil_gs(lev.A, lev.x, lev.b, steps, direction)
+        else:
+            self.ops.csr_gs_schedule(lev.A, lev.x, lev.b, self.gs_schedule(l, gs_mode, direction), steps)
+
+    def _wavefront_gs(self, l, gs_mode, direction="forward"):
         avail = getattr(self.ops, "stencil_gs_available", None)
-        return gs_mode == "lexicographic" and avail is not None and avail(self.levels[l].A)
+        if gs_mode != "lexicographic" or avail is None:
+            return False
+        return avail(self.levels[l].A) if direction == "forward" else avail(self.levels[l].A, direction)
 
     def _fusable(self, l, smoother, steps):
         avail = getattr(self.ops, "stencil_smooth_available", None)
@@ -300,9 +346,14 @@ class Hierarchy:
                 self.ops.axpby(1.0, lev.tmp, 1.0, lev.x)
 
     def cycle(self, smoother, steps, omega=1.0, gs_mode="lexicographic", l=0, depth=None,
-              after_presmooth=None, x_is_zero=False):
+              after_presmooth=None, x_is_zero=False, gs_sweep=("forward", "forward")):
         """One V(steps, steps) cycle on level l: levels[l].x is the iterate, levels[l].b the
-        right-hand side (Multigrid.py:77-124).  depth = number of grids used."""
+        right-hand side (Multigrid.py:77-124).  depth = number of grids used.
+        gs_sweep: directions of the Gauss-Seidel pre- and post-smoothing, a pyamg sweep name for both or a (pre, post)
+        pair.  ("forward", "backward") with R = P^T, Galerkin coarse operators and the direct coarse solve makes the
+        cycle a symmetric operator (a CG preconditioner); each half is one pipelined launch of the wavefront kernel,
+        while a "symmetric" step costs a launch per direction."""
+        pre, post = gs_sweep_pair(gs_sweep)
         last = (len(self.levels) if depth is None else depth) - 1
         lev, nxt = self.levels[l], self.levels[l + 1]
         fused = self._fusable(l, smoother, steps)
@@ -318,7 +369,7 @@ class Hierarchy:
             if after_presmooth is not None:
                 after_presmooth(lev.x)
         else:
-            self.smooth(l, smoother, steps, omega, gs_mode, x_is_zero)            # :88
+            self.smooth(l, smoother, steps, omega, gs_mode, x_is_zero, pre)       # :88
             if after_presmooth is not None:
                 after_presmooth(lev.x)
             self.ops.csr_residual_norm2(lev.A, lev.x, lev.b, lev.r, None, None)        # :90
@@ -327,7 +378,7 @@ class Hierarchy:
         if l + 1 == last:
             self.coarse_solve()                                               # :106
         else:
-            self.cycle(smoother, steps, omega, gs_mode, l + 1, depth, x_is_zero=True)   # zeros, :103
+            self.cycle(smoother, steps, omega, gs_mode, l + 1, depth, x_is_zero=True, gs_sweep=(pre, post))   # zeros, :103
         pavail = getattr(self.ops, "stencil_smooth_prolong_available", None)
         if fused and pavail is not None and pavail(lev.A, lev.P):
             self.smooth_fused(l, steps, omega, correction=(lev.P, nxt.x))     # :115 + :121 in one pass
@@ -336,7 +387,7 @@ class Hierarchy:
         if fused:
             self.smooth_fused(l, steps, omega)                                # :121
         else:
-            self.smooth(l, smoother, steps, omega, gs_mode)                       # :121
+            self.smooth(l, smoother, steps, omega, gs_mode, direction=post)       # :121
 
     def residual_norm(self, want_vector=True):
         """||b - A x||_2 on the fine level (Multigrid.py:62-63); one 8-byte D2H copy."""
@@ -356,28 +407,33 @@ class Hierarchy:
         for lev in self.levels[:-1]:
             chk(lev.A)
 
-    def prepare_smoother(self, smoother, gs_mode="lexicographic", l_from=0):
+    def prepare_smoother(self, smoother, gs_mode="lexicographic", l_from=0, gs_sweep=("forward", "forward")):
         """Everything a Gauss-Seidel cycle would otherwise do lazily on its first sweep -- the wavefront kernel's eligibility
-        test (a device -> host read) and work buffer, the level schedules -- from level l_from down: nothing of it may happen
-        while a hipGraph is being captured."""
+        test (a device -> host read) and work buffer, the level schedules -- from level l_from down, for every direction
+        gs_sweep uses: nothing of it may happen while a hipGraph is being captured."""
         if smoother != "GaussSeidel":
             return
+        dirs = []
+        for sw in gs_sweep_pair(gs_sweep):
+            dirs += [d for d in _directions(sw) if d not in dirs]
         for l in range(l_from, len(self.levels) - 1):
-            if self._wavefront_gs(l, gs_mode):
-                self.ops.stencil_gs(self.levels[l].A, self.levels[l].tmp, self.levels[l].b, 0)
-            else:
-                self.gs_schedule(l, gs_mode)
+            for d in dirs:
+                if self._wavefront_gs(l, gs_mode, d):
+                    self.ops.stencil_gs(self.levels[l].A, self.levels[l].tmp, self.levels[l].b, 0)
+                else:
+                    self.gs_schedule(l, gs_mode, d)
 
-    def captured_cycle(self, smoother, steps, omega, gs_mode):
-        """The same launch sequence as cycle(), captured once into a hipGraph and replayed."""
-        key = (smoother, steps, omega, gs_mode)
+    def captured_cycle(self, smoother, steps, omega, gs_mode, gs_sweep=("forward", "forward")):
+        """The same launch sequence as cycle(), captured once into a hipGraph and replayed (one graph per sweep pair)."""
+        pair = gs_sweep_pair(gs_sweep)
+        key = (smoother, steps, omega, gs_mode, pair)
         g = self._graphs.get(key)
         if g is None:
-            self.prepare_smoother(smoother, gs_mode)
+            self.prepare_smoother(smoother, gs_mode, gs_sweep=pair)
             before = [(lev.x, lev.tmp) for lev in self.levels]
             g = self.ops.CapturedGraph()
             with g:
-                self.cycle(smoother, steps, omega, gs_mode)
+                self.cycle(smoother, steps, omega, gs_mode, gs_sweep=pair)
             after = [(lev.x, lev.tmp) for lev in self.levels]
             if any(a[0] is not b[0] for a, b in zip(before, after)):
                 raise RuntimeError("ping-pong buffers did not return to their slots")

@@ -1154,6 +1154,14 @@ class GSSchedule:
         self.max_set = int(np.diff(self.h_ptr).max()) if self.nsets else 0
         self.ell = None              # pattern copy in schedule order, built on first use (see _gs_ell)
 
+    def reversed(self):
+        """The same sets in reverse order: on a level schedule (levels of A + A^T) the exact BACKWARD sweep, rows
+        n-1 .. 0; on colour classes backward multicolour Gauss-Seidel.  Every executor of csr_gs_schedule follows the
+        order of d_rows, so no other kernel is needed.  The copy gets its own schedule-ordered pattern (gs_prepare)."""
+        rows = self.d_rows.cpu().numpy()[::-1]
+        ptr = int(self.h_ptr[-1]) - self.h_ptr[::-1] if self.nsets else self.h_ptr
+        return GSSchedule(self.kind, rows, ptr, self.d_rows.device)
+
 
 def gs_schedule_from_labels(kind, labels, nsets, device):
     order = np.argsort(labels, kind="stable").astype(np.int32)      # ascending row inside a set
@@ -1163,8 +1171,9 @@ def gs_schedule_from_labels(kind, labels, nsets, device):
     return GSSchedule(kind, order, ptr, device)
 
 
-def build_gs_schedule(A_scipy_csr, kind, device):
-    """kind = "lexicographic" (level schedule: exact forward sweep) | "multicolor"."""
+def build_gs_schedule(A_scipy_csr, kind, device, reverse=False):
+    """kind = "lexicographic" (level schedule: exact forward sweep) | "multicolor".  reverse=True: the sets in
+    reverse order (exact backward sweep / backward multicolour sweep, see GSSchedule.reversed)."""
     A = A_scipy_csr
     n = A.shape[0]
     rp = np.ascontiguousarray(A.indptr, dtype=np.int32)
@@ -1175,7 +1184,8 @@ def build_gs_schedule(A_scipy_csr, kind, device):
     if fn is None:
         raise ValueError("unknown Gauss-Seidel ordering %r" % (kind,))
     nsets = check(fn(n, rp.ctypes.data, ci.ctypes.data, lab.ctypes.data), "gs schedule")
-    return gs_schedule_from_labels(kind, lab, nsets, device)
+    sched = gs_schedule_from_labels(kind, lab, nsets, device)
+    return sched.reversed() if reverse else sched
 
 
 def csr_gs_rows(A, x, b, rows):
@@ -1224,31 +1234,51 @@ def set_wavefront_gs_enabled(flag):
     _WAVE_GS_ENABLED = bool(flag)
 
 
-def stencil_gs_available(A):
+GS_DIRECTIONS = ("forward", "backward")
+
+
+def _gs_direction(direction):
+    if direction not in GS_DIRECTIONS:
+        raise ValueError("unknown Gauss-Seidel sweep direction %r (expected 'forward' or 'backward')" % (direction,))
+    return direction
+
+
+def stencil_gs_available(A, direction="forward"):
+    """Whether stencil_gs runs on A in this direction.  backward also needs whole lines (n % W == 0): the kernels run
+    in mirrored coordinates, which are a plain reversal of the vector only then (ragged grids: reversed schedules)."""
     S = getattr(A, "stencil", None)
-    return bool(_PACKED_ENABLED and _STENCIL_ENABLED and _WAVE_GS_ENABLED and S is not None and S.gs_ok
-                and S.n < GS_WAVE_MAX_ROWS)
+    ok = bool(_PACKED_ENABLED and _STENCIL_ENABLED and _WAVE_GS_ENABLED and S is not None and S.gs_ok
+              and S.n < GS_WAVE_MAX_ROWS)
+    if _gs_direction(direction) == "backward":
+        ok = ok and S.n % S.W == 0
+    return ok
 
 
-def stencil_gs(A, x, b, sweeps=1):
+def stencil_gs(A, x, b, sweeps=1, direction="forward"):
     """`sweeps` exact forward (lexicographic) Gauss-Seidel sweeps in place on x (lmg_stencil_gs_sweep): the
-    bits of csr_gs_schedule on the level schedule, without a schedule.
+    bits of csr_gs_schedule on the level schedule, without a schedule.  direction="backward": rows n-1 .. 0
+    (lmg_stencil_gs_sweep_backward; pyamg's sweep='backward'), the bits of csr_gs_schedule on the reversed level
+    schedule; needs stencil_gs_available(A, "backward").
 
-    The band tickets and progress counters live in ONE work buffer per operator (`StencilTwin._gs_work`): sweeps on the same
-    operator must be ordered on one stream (the hierarchy's launch stream); two streams sweeping one operator at the same
-    time would race on the counters."""
+    The band tickets and progress counters live in ONE work buffer per operator (`StencilTwin._gs_work`), shared by both
+    directions: sweeps on the same operator must be ordered on one stream (the hierarchy's launch stream); two streams
+    sweeping one operator at the same time would race on the counters."""
     _vec_ok(x, b)
+    bwd = _gs_direction(direction) == "backward"
     S = A.stencil
     if S is None or not S.gs_ok:
         raise LmgError("stencil_gs needs a grid-stencil matrix without coupling across line ends")
+    if bwd and S.n % S.W != 0:
+        raise LmgError("backward stencil_gs needs whole grid lines (n %% W == 0): n = %d, W = %d" % (S.n, S.W))
     if S._gs_work is None:
         nb = int(_lib.lib().lmg_stencil_gs_work_bytes(S.n, S.W))
         S._gs_work = torch.zeros((nb + 7) // 8, dtype=torch.int64, device=x.device)
     if sweeps <= 0:
         return
     hv = None if S._hot_val is None else ctypes.addressof(S._hot_val)
-    check(_lib.lib().lmg_stencil_gs_sweep(S.n, S.W, _p(S.pid), S.npat, _p(S.st_val), _p(S.st_mask), S.umask, S.hot, hv,
-                                          _p(x), _p(b), _p(S._gs_work), int(sweeps), _s(S.pid)), "lmg_stencil_gs_sweep")
+    name = "lmg_stencil_gs_sweep_backward" if bwd else "lmg_stencil_gs_sweep"
+    check(getattr(_lib.lib(), name)(S.n, S.W, _p(S.pid), S.npat, _p(S.st_val), _p(S.st_mask), S.umask, S.hot, hv,
+                                    _p(x), _p(b), _p(S._gs_work), int(sweeps), _s(S.pid)), name)
 
 
 def stencil_gs_check(A):
@@ -1672,6 +1702,7 @@ def register_torch_ops():
     lib.define("operator_residual(int handle, Tensor x, Tensor b) -> (Tensor, Tensor)")
     lib.define("operator_jacobi(int handle, Tensor x, Tensor b, float omega, int sweeps) -> Tensor")
     lib.define("operator_gauss_seidel_(int handle, Tensor(a!) x, Tensor b, int sweeps) -> ()")
+    lib.define("operator_gauss_seidel_backward_(int handle, Tensor(a!) x, Tensor b, int sweeps) -> ()")
 
     def op_spgemm(arp, aci, ava, acols, brp, bci, bva, bcols):
         C = spgemm(_csr(arp, aci, ava, acols), _csr(brp, bci, bva, bcols))
@@ -1692,7 +1723,7 @@ def register_torch_ops():
         A = _csr(rowptr, colidx, vals, ncols)
         A.pack()
         h = 1 + max(handles, default=0)
-        handles[h] = {"A": A, "gs": None}
+        handles[h] = {"A": A, "gs": None, "gs_backward": None}
         return h
 
     def _get(h):
@@ -1756,6 +1787,22 @@ def register_torch_ops():
             ent["gs"] = build_gs_schedule(pat, "lexicographic", A.device)
         csr_gs_schedule(A, x, b, ent["gs"], int(sweeps))
 
+    def op_h_gs_backward_(h, x, b, sweeps):
+        ent = _get(h)
+        A = ent["A"]
+        if stencil_gs_available(A, "backward"):
+            stencil_gs(A, x, b, int(sweeps), "backward")
+            stencil_gs_check(A)
+            return
+        if ent["gs_backward"] is None:
+            if ent["gs"] is None:
+                import scipy.sparse as sp
+                pat = sp.csr_matrix((np.ones(A.nnz, dtype=np.int8), A.colidx.cpu().numpy(), A.rowptr.cpu().numpy()),
+                                    shape=A.shape)
+                ent["gs"] = build_gs_schedule(pat, "lexicographic", A.device)
+            ent["gs_backward"] = ent["gs"].reversed()
+        csr_gs_schedule(A, x, b, ent["gs_backward"], int(sweeps))
+
     lib.impl("spgemm", op_spgemm, "CUDA")
     lib.impl("csr_transpose", op_transpose, "CUDA")
     lib.impl("dense_gemv", op_dense_gemv, "CUDA")
@@ -1766,5 +1813,6 @@ def register_torch_ops():
     lib.impl("operator_residual", op_h_residual, "CUDA")
     lib.impl("operator_jacobi", op_h_jacobi, "CUDA")
     lib.impl("operator_gauss_seidel_", op_h_gs_, "CUDA")
+    lib.impl("operator_gauss_seidel_backward_", op_h_gs_backward_, "CUDA")
     register_torch_ops._lib = lib        # keep alive
     _registered = True

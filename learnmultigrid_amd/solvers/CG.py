@@ -6,7 +6,10 @@ axpby), two 8-byte D2H reads per iteration for alpha and beta.
 
 Build-only extension (keyword-only): `preconditioner=Hierarchy` turns it into multigrid-
 preconditioned CG -- one V(nu,nu) Jacobi cycle from a zero guess per application (the
-"step after the hot path" of SURVEY.md section 8 f4)."""
+"step after the hot path" of SURVEY.md section 8 f4).  precond_smoother="GaussSeidel" smooths with
+nu forward Gauss-Seidel sweeps before and nu backward sweeps after the coarse correction instead:
+with R = P^T, Galerkin coarse operators and the direct coarse solve that cycle is a symmetric
+operator, the standard MG-PCG setup (each half is one pipelined launch of the wavefront kernel)."""
 import math
 
 import numpy as np
@@ -26,7 +29,9 @@ class CG(IterativeSolver):
 
     @on_device
     def solve(self, max_iterations=1000, error=1e-08, initial_guess=None, *, preconditioner=None,
-              precond_steps=2, precond_omega=0.8):
+              precond_steps=2, precond_omega=0.8, precond_smoother="Jacobi"):
+        if precond_smoother not in ("Jacobi", "GaussSeidel"):
+            raise ValueError("precond_smoother must be 'Jacobi' or 'GaussSeidel', got %r" % (precond_smoother,))
         A = self._device_matrix()
         A.pack()
         n = self.dim
@@ -48,7 +53,10 @@ class CG(IterativeSolver):
                 return
             fine = H.levels[0]
             ops.copy(src, fine.b)
-            H.cycle("Jacobi", precond_steps, precond_omega, x_is_zero=True)
+            if precond_smoother == "GaussSeidel":
+                H.cycle("GaussSeidel", precond_steps, 1.0, x_is_zero=True, gs_sweep=("forward", "backward"))
+            else:
+                H.cycle("Jacobi", precond_steps, precond_omega, x_is_zero=True)
             ops.copy(fine.x, dst)
 
         z = torch.empty_like(x)
@@ -79,6 +87,8 @@ class CG(IterativeSolver):
             beta = rz_new / rz                                         # :47
             rz = rz_new
             ops.axpby(1.0, z, beta, p)                                 # :48
+        if H is not None and precond_smoother == "GaussSeidel":
+            H.check_smoothers()            # a timed-out wavefront band raises instead of leaving a wrong solution
         self.solution = self._column(x)
         self.residual_vector = self._column(r)
         self.track_res = np.array(track, dtype=float).reshape(-1, 1)

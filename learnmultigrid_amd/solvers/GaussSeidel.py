@@ -2,7 +2,8 @@
 The reference forms (D+L)^-1 explicitly (O(n^2) fill) and does x += (D+L)^-1 (b - A x);
 that is one lexicographic forward sweep, executed here exactly (level-scheduled HIP
 kernel, same row arithmetic as pyamg's sweep) or, with gs_mode="multicolor", in colour
-order (faster, different ordering)."""
+order (faster, different ordering).  sweep="backward" | "symmetric" (pyamg's gauss_seidel sweep) relaxes
+the rows in reverse order / forward then backward in every iteration."""
 import math
 
 import numpy as np
@@ -21,14 +22,25 @@ class GaussSeidel(IterativeSolver):
         self.label = "Gauss-Seidel"
 
     @on_device
-    def solve(self, max_iterations=1000, error=1e-12, initial_guess=None, *, gs_mode="lexicographic"):
+    def solve(self, max_iterations=1000, error=1e-12, initial_guess=None, *, gs_mode="lexicographic", sweep="forward"):
+        if sweep not in ("forward", "backward", "symmetric"):
+            raise ValueError("sweep must be 'forward', 'backward' or 'symmetric', got %r" % (sweep,))
         A = self._device_matrix()
         n = self.dim
         import scipy.sparse as sp
         if gs_mode == "lexicographic" and A.shape[0] >= 4096:
             A.pack()                       # large grid operators: the wavefront kernel needs the stencil twin
-        wave = gs_mode == "lexicographic" and ops.stencil_gs_available(A)
-        sched = None if wave else ops.build_gs_schedule(sp.csr_matrix(self.matrix), gs_mode, self._device)
+        dirs = ("forward", "backward") if sweep == "symmetric" else (sweep,)
+        # per direction: the wavefront kernel, or the (reversed) schedule
+        plan, fwd_sched = [], None
+        for d in dirs:
+            if gs_mode == "lexicographic" and ops.stencil_gs_available(A, d):
+                plan.append((d, None))
+                continue
+            if fwd_sched is None:
+                fwd_sched = ops.build_gs_schedule(sp.csr_matrix(self.matrix), gs_mode, self._device)
+            plan.append((d, fwd_sched if d == "forward" else fwd_sched.reversed()))
+        wave = any(sc is None for _, sc in plan)
         b = self._to_device(self.rhs)
         x = torch.zeros(n, dtype=F64, device=self._device) if initial_guess is None \
             else self._to_device(initial_guess)
@@ -46,10 +58,13 @@ class GaussSeidel(IterativeSolver):
             if self.residual <= error:
                 self._log("Reached convergence Gauss")
                 break
-            if wave:
-                ops.stencil_gs(A, x, b, 1)                             # :37, pipelined wavefront (gs_wave.hip)
-            else:
-                ops.csr_gs_schedule(A, x, b, sched, 1)                 # :37
+            for d, sched in plan:
+                if sched is None and d == "forward":
+                    ops.stencil_gs(A, x, b, 1)                         # :37, pipelined wavefront (gs_wave.hip)
+                elif sched is None:
+                    ops.stencil_gs(A, x, b, 1, d)
+                else:
+                    ops.csr_gs_schedule(A, x, b, sched, 1)             # :37
         if wave:
             ops.stencil_gs_check(A)
         self.solution = self._column(x)
