@@ -220,6 +220,23 @@ int lmg_stencil_smooth_tiled_restrict(int64_t n, int32_t line_stride, const uint
                                       int32_t coarse_stride, double *d_b_coarse, const uint8_t *d_r_pid,
                                       int32_t r_npat, const double *d_r_val, const int32_t *d_r_mask, int32_t hot_r,
                                       const double *h_hot_rval, void *stream);
+/* ... and both, the TURNAROUND of a repeated level visit (W- and F-cycles): the post-smoothing pass of visit k and the
+ * pre-smoothing pass of visit k + 1 in one pass,
+ *     x_out = J^(sweeps_post + sweeps_pre)(x_in + P e_coarse),   b_coarse = R (b - A x_out),
+ * sweeps_post, sweeps_pre 1..3 each.  Arguments: the union of lmg_stencil_smooth_tiled_prolong's and
+ * lmg_stencil_smooth_tiled_restrict's (one coarse grid: n_coarse, coarse_stride as the restriction demands); b_coarse
+ * must not alias e_coarse.  Same bits as the correcting pass followed by the restricting pass; the halo is
+ * sweeps_post + sweeps_pre + 2 lines and columns, the tile 64 columns x 32 or 64 lines (tune key tile_turnaround_rows). */
+int lmg_stencil_smooth_tiled_turnaround(int64_t n, int32_t line_stride, const uint8_t *d_pid, int32_t npat,
+                                        const double *d_st_val, const int32_t *d_st_mask, uint32_t union_mask,
+                                        int32_t hot_pattern, const double *h_hot_val, int sweeps_post, int sweeps_pre,
+                                        const double *d_x_in, const double *d_b, double omega, double *d_x_out,
+                                        int64_t n_coarse, int32_t coarse_stride, const double *d_e_coarse,
+                                        const uint8_t *d_p_pid, int32_t p_npat, const double *d_p_val,
+                                        const int32_t *d_p_mask, const int32_t *h_hot_pairs, const double *h_hot_pval,
+                                        double *d_b_coarse, const uint8_t *d_r_pid, int32_t r_npat,
+                                        const double *d_r_val, const int32_t *d_r_mask, int32_t hot_r,
+                                        const double *h_hot_rval, void *stream);
 
 /* ---- fused smoothing passes for grid operators with VARIABLE coefficients (csrc/dia_tile.hip) ------------------------
  * The operators the reference's learned transfers are built for (variable-coefficient / jittered-mesh stiffness

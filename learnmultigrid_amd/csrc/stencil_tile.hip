@@ -86,11 +86,15 @@ struct TArgs {
 // node of the tile's inner part, 32 per wave line) instead of being carried by every fine element, with the frequent
 // row of R in scalar registers where a whole wave has it.
 template <int S, unsigned UM, bool RESID, bool ZERO, int RR, bool PROL = false, bool REST = false, int RBV = kRB, bool HX = false>
-// (16-wave workgroups: at most 64 VGPRs, so that two of them share a CU -- the variants with the restriction had 65 - 67)
-__global__ void __launch_bounds__(RR / RBV * LMG_WAVE, (RR / RBV == 16 && (!PROL || HX)) ? 8 : 1) stencil_tile_kernel(TArgs a)
+// (16-wave workgroups: at most 64 VGPRs, so that two of them share a CU -- the variants with the restriction had 65 - 67;
+// the 64-line turnaround, four lines per wave, needs 76 / 89 and spills under that bound)
+__global__ void __launch_bounds__(RR / RBV * LMG_WAVE, (RR / RBV == 16 && (!PROL || HX) && !(PROL && REST && RBV == 4)) ? 8 : 1)
+stencil_tile_kernel(TArgs a)
 {
-    static_assert(!PROL || (!RESID && !ZERO), "the correction is folded into post-smoothing passes only");
-    static_assert(!REST || (RESID && !PROL), "the restriction replaces the store of the residual");
+    // PROL && REST: the turnaround of a repeated level visit -- the post-smoothing pass of visit k (correction, then
+    // its sweeps) and the pre-smoothing pass of visit k + 1 (its sweeps, then the restriction) as one pass of S sweeps
+    static_assert(!PROL || (!ZERO && (!RESID || REST)), "the correction is folded into post-smoothing passes only");
+    static_assert(!REST || RESID, "the restriction replaces the store of the residual");
     // halo: one more with REST -- the residual has to be exact one line / column beyond the stored part
     constexpr int H = S + (RESID ? 1 : 0) - (ZERO ? 1 : 0) + (REST ? 1 : 0);
     constexpr int kWaves = RR / RBV, kBlock = kWaves * LMG_WAVE;
@@ -121,7 +125,8 @@ __global__ void __launch_bounds__(RR / RBV * LMG_WAVE, (RR / RBV == 16 && (!PROL
     double lx[RB], bk[RB];
     int pk[RB];                                                   // pattern id | 0x100 where the element is a row of the matrix
     double le[(PROL && !HX) ? RB : 1][4];                         // PROL: the 2 x 2 coarse window of every element
-    int lq[(PROL || REST) ? RB : 1];                              //       and its pattern id in P / REST: the id of R's row
+    int lq[PROL ? RB : 1];                                        //       and its pattern id in P
+    int lr[(REST && !HX) ? RB : 1];                               // REST: the id of R's row | 0x100 where the element has one
     // REST with HX: this thread's coarse node -- line t >> 5, column t & 31 of the even nodes of the inner part
     int rq = 0, rrow = H, rcol = H;
     bool rown = false;
@@ -202,7 +207,7 @@ __global__ void __launch_bounds__(RR / RBV * LMG_WAVE, (RR / RBV == 16 && (!PROL
             const int c = c0 + lane;
             const bool crow = ok && !(y & 1) && !(c & 1) && c >= 0 && c < W;
             const int64_t jc = (int64_t)(y >> 1) * a.Wc + (c >> 1);
-            lq[k] = crow ? ((int)a.rpid[jc < a.nc ? jc : 0] | 0x100) : 0;
+            lr[k] = crow ? ((int)a.rpid[jc < a.nc ? jc : 0] | 0x100) : 0;
         }
     }
     for (int i = t; i < a.npat * 9; i += kBlock) s_val[i] = a.st_val[i];
@@ -376,7 +381,7 @@ __global__ void __launch_bounds__(RR / RBV * LMG_WAVE, (RR / RBV == 16 && (!PROL
 #pragma unroll
         for (int k = 0; k < RB; ++k) {
             const int r = rb0 + k;
-            const int q = lq[k] & 0xff, m = s_rm[q];
+            const int q = lr[k] & 0xff, m = s_rm[q];
             double acc = 0.0;
 #pragma unroll
             for (int e = 0; e < 9; ++e) {
@@ -384,7 +389,7 @@ __global__ void __launch_bounds__(RR / RBV * LMG_WAVE, (RR / RBV == 16 && (!PROL
                 const double tv = acc + s_rv[q * 9 + e] * rl[rr * kLS + 1 + lane + e % 3 - 1];
                 acc = ((m >> e) & 1) ? tv : acc;
             }
-            if ((lq[k] >> 8) && r >= H && r < RR - H && col_ok)
+            if ((lr[k] >> 8) && r >= H && r < RR - H && col_ok)
                 a.bc[(int64_t)((y0 + r) >> 1) * a.Wc + ((c0 + lane) >> 1)] = acc;
         }
     } else if (RESID) {
@@ -412,6 +417,8 @@ int g_tile_prol_wide_lines = 768;    // grids of at least this many lines: the p
 int g_tile_rows_big = 0;    // the same for grids of at least g_tile_big_lines lines
 int g_tile_big_lines = 600;
 int g_tile_hot_transfers = 1;       // the passes with a transfer folded in run the HX kernels
+int g_tile_turnaround_rows = 0;     // lines per tile of the turnaround pass (32, 64; 0 = 64 on grids of at least
+                                    // g_tile_big_lines lines, 32 below): its halo is s_post + s_pre + 2 lines
 int g_tile_prol_wide_lines_hx = 1 << 30;    // g_tile_prol_wide_lines of the HX kernels: at 61 VGPRs the 16-wave variant
                                             // runs 8 waves / SIMD (4 lines per wave: 87 VGPRs, 5); cfg#4 cycle 0.4698 ->
                                             // 0.4539 ms without the 4-line variant at 2049^2
@@ -468,6 +475,35 @@ int launch_prol(TArgs a, int sweeps, hipStream_t st)
     }
 }
 
+// The turnaround: x + P e, S = s_post + s_pre sweeps, b_coarse = R (b - A x) -- a halo of S + 2 lines and columns.  Its
+// 64-line tiles are 16 waves of four lines (a wave cannot hold more than 1024 threads' worth of 2-line blocks).
+template <int S, unsigned UM, bool HX>
+int launch_turn3(TArgs a, hipStream_t st)
+{
+    const int rr = g_tile_turnaround_rows ? g_tile_turnaround_rows : (a.lines >= g_tile_big_lines ? 64 : 32);
+    if (rr == 64) return launch5<S, UM, true, false, 64, true, true, 4, HX>(a, st);
+    return launch5<S, UM, true, false, 32, true, true, kRB, HX>(a, st);
+}
+
+template <int S, unsigned UM>
+int launch_turn2(TArgs a, hipStream_t st)
+{
+    if (g_tile_hot_transfers) return launch_turn3<S, UM, true>(a, st);
+    return launch_turn3<S, UM, false>(a, st);
+}
+
+template <unsigned UM>
+int launch_turn(TArgs a, int sweeps, hipStream_t st)
+{
+    switch (sweeps) {
+    case 2: return launch_turn2<2, UM>(a, st);
+    case 3: return launch_turn2<3, UM>(a, st);
+    case 4: return launch_turn2<4, UM>(a, st);
+    case 5: return launch_turn2<5, UM>(a, st);
+    default: return launch_turn2<6, UM>(a, st);
+    }
+}
+
 template <unsigned UM>
 int launch_rest(TArgs a, int sweeps, bool zero, hipStream_t st)
 {
@@ -514,6 +550,11 @@ int lmg_tile_tune_set(const char *key, int v)
         g_tile_big_lines = v;
         return LMG_OK;
     }
+    if (strcmp(key, "tile_turnaround_rows") == 0) {
+        if (v != 0 && v != 32 && v != 64) return LMG_ERR_ARG;
+        g_tile_turnaround_rows = v;
+        return LMG_OK;
+    }
     if (strcmp(key, "tile_hot_transfers") == 0) {
         if (v != 0 && v != 1) return LMG_ERR_ARG;
         g_tile_hot_transfers = v;
@@ -529,6 +570,7 @@ int lmg_tile_tune_get(const char *key)
     if (strcmp(key, "tile_prol_wide_lines") == 0) return g_tile_prol_wide_lines;
     if (strcmp(key, "tile_hot_transfers") == 0) return g_tile_hot_transfers;
     if (strcmp(key, "tile_prol_wide_lines_hx") == 0) return g_tile_prol_wide_lines_hx;
+    if (strcmp(key, "tile_turnaround_rows") == 0) return g_tile_turnaround_rows;
     return LMG_ERR_ARG;
 }
 
@@ -672,6 +714,62 @@ int lmg_stencil_smooth_tiled_restrict(int64_t n, int32_t line_stride, const uint
     switch (union_mask) {
     case kMask5: return launch_rest<kMask5>(a, sweeps, zero, st);
     case kMask9: return launch_rest<kMask9>(a, sweeps, zero, st);
+    default: return LMG_ERR_CAPACITY;
+    }
+}
+
+int lmg_stencil_smooth_tiled_turnaround(int64_t n, int32_t line_stride, const uint8_t *pid, int32_t npat, const double *st_val,
+                                        const int32_t *st_mask, uint32_t union_mask, int32_t hot_pattern,
+                                        const double *h_hot_val, int sweeps_post, int sweeps_pre, const double *x_in,
+                                        const double *b, double omega, double *x_out, int64_t n_coarse, int32_t coarse_stride,
+                                        const double *e_coarse, const uint8_t *p_pid, int32_t p_npat, const double *p_val,
+                                        const int32_t *p_mask, const int32_t *h_hot_pairs, const double *h_hot_pval,
+                                        double *b_coarse, const uint8_t *r_pid, int32_t r_npat, const double *r_val,
+                                        const int32_t *r_mask, int32_t hot_r, const double *h_hot_rval, void *stream)
+{
+    if (sweeps_post < 1 || sweeps_post > 3 || sweeps_pre < 1 || sweeps_pre > 3) return LMG_ERR_ARG;
+    // the argument checks of the correcting and of the restricting pass
+    if (!x_in || !e_coarse || !p_pid || !p_val || !p_mask || p_npat < 1 || p_npat > kMaxPat) return LMG_ERR_ARG;
+    if (!b_coarse || !r_pid || !r_val || !r_mask || r_npat < 1 || r_npat > kMaxPat) return LMG_ERR_ARG;
+    if (n_coarse < 2 || n_coarse >= (1ll << 31) || coarse_stride < 1 || coarse_stride > n_coarse) return LMG_ERR_ARG;
+    if (e_coarse == x_out || (const double *)b_coarse == e_coarse || (const double *)b_coarse == x_in || b_coarse == x_out ||
+        (const double *)b_coarse == b)
+        return LMG_ERR_ARG;
+    const int64_t lines = n > 0 ? (n + line_stride - 1) / line_stride : 0;
+    if ((int64_t)coarse_stride != ((int64_t)line_stride + 1) / 2 || (n % line_stride) != 0 || n_coarse != ((lines + 1) / 2) * coarse_stride)
+        return LMG_ERR_ARG;
+    TArgs a;
+    const int rc = tile_args(a, n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val, sweeps_post,
+                             x_in, b, omega, x_out, nullptr);
+    if (rc != 1) return rc;
+    a.ec = e_coarse;
+    a.bc = b_coarse;
+    a.nc = (int)n_coarse;
+    a.Wc = coarse_stride;
+    a.ppid = p_pid;
+    a.pp_val = p_val;
+    a.pp_mask = p_mask;
+    a.pp_npat = p_npat;
+    if (h_hot_pairs && h_hot_pval) {
+        for (int k = 0; k < 2; ++k) {
+            const int hp = h_hot_pairs[k];
+            const bool ok = hp >= 0 && (hp & 0xff) < p_npat && (hp >> 8) < p_npat;
+            a.phot[k] = ok ? hp : -1;
+        }
+        for (int k = 0; k < 9; ++k) a.phv[k] = h_hot_pval[k];
+    }
+    a.rpid = r_pid;
+    a.rp_val = r_val;
+    a.rp_mask = r_mask;
+    a.rp_npat = r_npat;
+    if (hot_r >= 0 && hot_r < r_npat && h_hot_rval) {
+        a.rhot = hot_r;
+        for (int k = 0; k < 9; ++k) a.rhv[k] = h_hot_rval[k];
+    }
+    hipStream_t st = lmg_stream(stream);
+    switch (union_mask) {
+    case kMask5: return launch_turn<kMask5>(a, sweeps_post + sweeps_pre, st);
+    case kMask9: return launch_turn<kMask9>(a, sweeps_post + sweeps_pre, st);
     default: return LMG_ERR_CAPACITY;
     }
 }

@@ -36,6 +36,17 @@ def gs_sweep_pair(gs_sweep):
     return pair
 
 
+CYCLE_SHAPES = ("V", "W", "F")                         # pyamg's multilevel_solver.solve(cycle=...)
+_CHILDREN = {"V": ("V",), "W": ("W", "W"), "F": ("F", "V")}
+
+
+def cycle_children(shape):
+    """The cycles a `shape` cycle runs on the next coarser level, one after the other (pyamg's convention)."""
+    if shape not in _CHILDREN:
+        raise ValueError("cycle shape must be one of %s, got %r" % (CYCLE_SHAPES, shape))
+    return _CHILDREN[shape]
+
+
 def _directions(sweep):
     return ("forward", "backward") if sweep == "symmetric" else (sweep,)
 
@@ -346,15 +357,47 @@ class Hierarchy:
                 self.ops.axpby(1.0, lev.tmp, 1.0, lev.x)
 
     def cycle(self, smoother, steps, omega=1.0, gs_mode="lexicographic", l=0, depth=None,
-              after_presmooth=None, x_is_zero=False, gs_sweep=("forward", "forward")):
+              after_presmooth=None, x_is_zero=False, gs_sweep=("forward", "forward"), shape="V"):
         """One V(steps, steps) cycle on level l: levels[l].x is the iterate, levels[l].b the
         right-hand side (Multigrid.py:77-124).  depth = number of grids used.
         gs_sweep: directions of the Gauss-Seidel pre- and post-smoothing, a pyamg sweep name for both or a (pre, post)
         pair.  ("forward", "backward") with R = P^T, Galerkin coarse operators and the direct coarse solve makes the
         cycle a symmetric operator (a CG preconditioner); each half is one pipelined launch of the wavefront kernel,
-        while a "symmetric" step costs a launch per direction."""
-        pre, post = gs_sweep_pair(gs_sweep)
-        last = (len(self.levels) if depth is None else depth) - 1
+        while a "symmetric" step costs a launch per direction.
+        shape: "V" | "W" | "F" (pyamg's cycle=, CYCLE_SHAPES): what follows the restriction on every level above the
+        second-coarsest -- one V-cycle, two W-cycles, or an F-cycle then a V-cycle on the next level, the second visit
+        starting from the first one's iterate with the same right-hand side; the coarsest level is solved once per
+        visit of the level above it.  Where a level runs the tiled Jacobi passes, the post-smoothing of one visit and
+        the pre-smoothing of the next run as one turnaround pass (ops.stencil_smooth_turnaround)."""
+        children = cycle_children(shape)
+        self._visit(smoother, steps, omega, gs_mode, l, (len(self.levels) if depth is None else depth) - 1, children,
+                    gs_sweep_pair(gs_sweep), x_is_zero, after_presmooth)
+
+    def _visit(self, smoother, steps, omega, gs_mode, l, last, children, pair, x_is_zero=False, after_presmooth=None,
+               entered=False, leave_open=False):
+        """One cycle on level l whose recursion below is `children` (cycle_children of its shape).  entered: the
+        pre-smoothing and the restriction have run already (in a turnaround pass).  leave_open: a visit of the same level
+        follows -- return True without the post-smoothing where a turnaround pass can run it together with that visit's
+        pre-smoothing."""
+        if not entered:
+            self._presmooth(smoother, steps, omega, gs_mode, l, x_is_zero, pair[0], after_presmooth)
+        if l + 1 == last:
+            self.coarse_solve()                                               # :106
+        else:
+            open_ = False
+            for i, sub in enumerate(children):
+                more = i + 1 < len(children)
+                if open_:
+                    self._turnaround(l + 1, steps, omega)
+                open_ = self._visit(smoother, steps, omega, gs_mode, l + 1, last, cycle_children(sub), pair,
+                                    x_is_zero=(i == 0), entered=open_, leave_open=more)     # zeros, :103
+        if leave_open and self._turnaround_ok(l, smoother, steps):
+            return True
+        self._postsmooth(smoother, steps, omega, gs_mode, l, pair[1])
+        return False
+
+    def _presmooth(self, smoother, steps, omega, gs_mode, l, x_is_zero, pre, after_presmooth):
+        """Pre-smoothing of level l, residual, b_(l+1) = R r (Multigrid.py:88-93)."""
         lev, nxt = self.levels[l], self.levels[l + 1]
         fused = self._fusable(l, smoother, steps)
         ravail = getattr(self.ops, "stencil_smooth_restrict_available", None)
@@ -375,10 +418,11 @@ class Hierarchy:
             self.ops.csr_residual_norm2(lev.A, lev.x, lev.b, lev.r, None, None)        # :90
         if not restricted:
             self.ops.csr_spmv(lev.R, lev.r, nxt.b, 1.0, 0.0)                       # :93
-        if l + 1 == last:
-            self.coarse_solve()                                               # :106
-        else:
-            self.cycle(smoother, steps, omega, gs_mode, l + 1, depth, x_is_zero=True, gs_sweep=(pre, post))   # zeros, :103
+
+    def _postsmooth(self, smoother, steps, omega, gs_mode, l, post):
+        """x += P x_(l+1), post-smoothing of level l (Multigrid.py:115-121)."""
+        lev, nxt = self.levels[l], self.levels[l + 1]
+        fused = self._fusable(l, smoother, steps)
         pavail = getattr(self.ops, "stencil_smooth_prolong_available", None)
         if fused and pavail is not None and pavail(lev.A, lev.P):
             self.smooth_fused(l, steps, omega, correction=(lev.P, nxt.x))     # :115 + :121 in one pass
@@ -388,6 +432,19 @@ class Hierarchy:
             self.smooth_fused(l, steps, omega)                                # :121
         else:
             self.smooth(l, smoother, steps, omega, gs_mode, direction=post)       # :121
+
+    def _turnaround_ok(self, l, smoother, steps):
+        avail = getattr(self.ops, "stencil_smooth_turnaround_selected", None)
+        lev = self.levels[l]
+        return (avail is not None and steps <= self.ops.FUSED_MAX_SWEEPS and self._fusable(l, smoother, steps)
+                and avail(lev.A, lev.P, lev.R))
+
+    def _turnaround(self, l, steps, omega):
+        """Post-smoothing of one visit of level l and pre-smoothing of the next, with the restriction, in one pass."""
+        lev, nxt = self.levels[l], self.levels[l + 1]
+        self.ops.stencil_smooth_turnaround(lev.A, lev.x, lev.b, omega, steps, steps, lev.tmp,
+                                           prolong=(lev.P, nxt.x), restrict=(lev.R, nxt.b))
+        lev.x, lev.tmp = lev.tmp, lev.x
 
     def residual_norm(self, want_vector=True):
         """||b - A x||_2 on the fine level (Multigrid.py:62-63); one 8-byte D2H copy."""
@@ -423,20 +480,27 @@ class Hierarchy:
                 else:
                     self.gs_schedule(l, gs_mode, d)
 
-    def captured_cycle(self, smoother, steps, omega, gs_mode, gs_sweep=("forward", "forward")):
-        """The same launch sequence as cycle(), captured once into a hipGraph and replayed (one graph per sweep pair)."""
+    def captured_cycle(self, smoother, steps, omega, gs_mode, gs_sweep=("forward", "forward"), shape="V"):
+        """The same launch sequence as cycle(), captured once into a hipGraph and replayed (one graph per sweep pair and
+        cycle shape)."""
         pair = gs_sweep_pair(gs_sweep)
-        key = (smoother, steps, omega, gs_mode, pair)
+        cycle_children(shape)
+        key = (smoother, steps, omega, gs_mode, pair, shape)
         g = self._graphs.get(key)
         if g is None:
             self.prepare_smoother(smoother, gs_mode, gs_sweep=pair)
             before = [(lev.x, lev.tmp) for lev in self.levels]
             g = self.ops.CapturedGraph()
             with g:
-                self.cycle(smoother, steps, omega, gs_mode, gs_sweep=pair)
-            after = [(lev.x, lev.tmp) for lev in self.levels]
-            if any(a[0] is not b[0] for a, b in zip(before, after)):
+                self.cycle(smoother, steps, omega, gs_mode, gs_sweep=pair, shape=shape)
+            if self.levels[0].x is not before[0][0]:
                 raise RuntimeError("ping-pong buffers did not return to their slots")
+            # a coarse level's first visit starts from a zero iterate, never reading x: a level with turnaround passes
+            # (W- and F-cycles) may end in the other buffer, the graph does not depend on where its iterate starts
+            for lev, (x, tmp) in zip(self.levels, before):
+                if {id(lev.x), id(lev.tmp)} != {id(x), id(tmp)}:
+                    raise RuntimeError("ping-pong buffers did not return to their slots")
+                lev.x, lev.tmp = x, tmp
             self._graphs[key] = g
         return g
 

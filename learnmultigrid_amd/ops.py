@@ -1014,6 +1014,63 @@ def stencil_smooth_restrict_available(A, R):
     return T.nc >= ((lines + 1) // 2 - 1) * T.Wc + (S.W + 1) // 2
 
 
+_FUSED_TURNAROUND_ENABLED = True
+# The hierarchy runs the turnaround of a repeated visit (W- and F-cycles) as one pass on levels of TURNAROUND_MIN_ROWS to
+# TURNAROUND_MAX_ROWS rows and keeps the correcting and the restricting pass elsewhere.  Measured at 3 + 3 sweeps, 9-point
+# Galerkin levels of cfg#4 (tools/time_cycle_shapes.py, us per pair, two passes / one pass): 2049^2 108.7 / 121.9 (64-line
+# tiles; 134.0 with 32), 1025^2 43.3 / 41.7 (64), 513^2 21.5 / 19.8 (32), 257^2 14.6 / 14.8 (32): the extra halo work
+# loses where the passes are instruction-bound and only pays on the latency-bound middle levels.
+TURNAROUND_MIN_ROWS = 100_000
+TURNAROUND_MAX_ROWS = 2_000_000
+
+
+def set_fused_turnaround_enabled(flag):
+    """Whether the turnaround of a repeated level visit -- the post-smoothing pass of visit k, the pre-smoothing pass
+    of visit k + 1 -- may run as one pass (default) or as the correcting and the restricting pass (A/B runs and
+    parity tests)."""
+    global _FUSED_TURNAROUND_ENABLED
+    _FUSED_TURNAROUND_ENABLED = bool(flag)
+
+
+def stencil_smooth_turnaround_available(A, P, R):
+    """True when stencil_smooth_turnaround can run on level operator A with prolongation P and restriction R: A runs
+    the tiled passes, both transfers fold into them and share one coarse grid."""
+    if not (_FUSED_TURNAROUND_ENABLED and _fused_kind(A) == "tile"):
+        return False
+    if not (stencil_smooth_prolong_available(A, P) and stencil_smooth_restrict_available(A, R)):
+        return False
+    S, TP, TR = A.stencil, P.prolong, R.restrict
+    lines = (S.n + S.W - 1) // S.W
+    return bool(TP.nc == TR.nc and TP.Wc == TR.Wc and TR.nc >= 2 and S.n % S.W == 0
+                and TR.Wc == (S.W + 1) // 2 and TR.nc == ((lines + 1) // 2) * TR.Wc)
+
+
+def stencil_smooth_turnaround_selected(A, P, R):
+    """True where the hierarchy runs the turnaround pass: available, and the level's size is one where it was measured
+    to beat the two passes (TURNAROUND_MIN_ROWS .. TURNAROUND_MAX_ROWS)."""
+    return bool(stencil_smooth_turnaround_available(A, P, R) and TURNAROUND_MIN_ROWS <= A.shape[0] <= TURNAROUND_MAX_ROWS)
+
+
+def stencil_smooth_turnaround(A, x_in, b, omega, sweeps_post, sweeps_pre, x_out, prolong, restrict):
+    """x_out = J^(sweeps_post + sweeps_pre)(x_in + P e), b_coarse = R (b - A x_out) in ONE tiled pass
+    (lmg_stencil_smooth_tiled_turnaround): the post-smoothing pass of one visit of a level and the pre-smoothing pass of
+    the next visit, as W- and F-cycles repeat them.  prolong = (P, e), restrict = (R, b_coarse); sweeps 1..3 each.
+    Same bits as stencil_smooth(..., prolong=(P, e)) followed by stencil_smooth(..., restrict=(R, b_coarse))."""
+    (P, e), (R, bc) = prolong, restrict
+    _vec_ok(x_in, b, x_out, e, bc)
+    S, TP, TR = A.stencil, getattr(P, "prolong", None), getattr(R, "restrict", None)
+    if (S is None or TP is None or TR is None or x_in is None or _fused_kind(A) != "tile" or TP.n != S.n or TP.W != S.W
+            or TR.n != S.n or TR.W != S.W or e.numel() != TP.nc or bc.numel() != TR.nc):
+        raise LmgError("stencil_smooth_turnaround: this level and its transfers cannot run the turnaround pass")
+    hv = None if S._hot_val is None else ctypes.addressof(S._hot_val)
+    hr = None if TR._hot_val is None else ctypes.addressof(TR._hot_val)
+    check(_lib.lib().lmg_stencil_smooth_tiled_turnaround(
+        S.n, S.W, _p(S.pid), S.npat, _p(S.st_val), _p(S.st_mask), S.umask, S.hot, hv, int(sweeps_post), int(sweeps_pre),
+        _p(x_in), _p(b), float(omega), _p(x_out), TP.nc, TP.Wc, _p(e), _p(TP.pid), TP.npat, _p(TP.p_val), _p(TP.p_mask),
+        ctypes.addressof(TP._hot_pairs), ctypes.addressof(TP._hot_pval), _p(bc), _p(TR.pid), TR.npat, _p(TR.r_val),
+        _p(TR.r_mask), TR.hot, hr, _s(S.pid)), "lmg_stencil_smooth_tiled_turnaround")
+
+
 def _use_stencil(A, *vecs):
     if not (_PACKED_ENABLED and _STENCIL_ENABLED and A.stencil is not None):
         return False

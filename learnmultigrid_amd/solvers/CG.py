@@ -9,7 +9,9 @@ preconditioned CG -- one V(nu,nu) Jacobi cycle from a zero guess per application
 "step after the hot path" of SURVEY.md section 8 f4).  precond_smoother="GaussSeidel" smooths with
 nu forward Gauss-Seidel sweeps before and nu backward sweeps after the coarse correction instead:
 with R = P^T, Galerkin coarse operators and the direct coarse solve that cycle is a symmetric
-operator, the standard MG-PCG setup (each half is one pipelined launch of the wavefront kernel)."""
+operator, the standard MG-PCG setup (each half is one pipelined launch of the wavefront kernel).
+precond_cycle_shape="W" applies one W-cycle instead (Hierarchy.cycle); it is as symmetric as the V-cycle.  An F-cycle
+is not (its second visits are V-cycles: the F-cycle's adjoint would run them first) and is rejected."""
 import math
 
 import numpy as np
@@ -29,9 +31,12 @@ class CG(IterativeSolver):
 
     @on_device
     def solve(self, max_iterations=1000, error=1e-08, initial_guess=None, *, preconditioner=None,
-              precond_steps=2, precond_omega=0.8, precond_smoother="Jacobi"):
+              precond_steps=2, precond_omega=0.8, precond_smoother="Jacobi", precond_cycle_shape="V"):
         if precond_smoother not in ("Jacobi", "GaussSeidel"):
             raise ValueError("precond_smoother must be 'Jacobi' or 'GaussSeidel', got %r" % (precond_smoother,))
+        if precond_cycle_shape not in ("V", "W"):
+            raise ValueError("precond_cycle_shape must be 'V' or 'W' (CG needs a symmetric preconditioner), got %r"
+                             % (precond_cycle_shape,))
         A = self._device_matrix()
         A.pack()
         n = self.dim
@@ -54,9 +59,10 @@ class CG(IterativeSolver):
             fine = H.levels[0]
             ops.copy(src, fine.b)
             if precond_smoother == "GaussSeidel":
-                H.cycle("GaussSeidel", precond_steps, 1.0, x_is_zero=True, gs_sweep=("forward", "backward"))
+                H.cycle("GaussSeidel", precond_steps, 1.0, x_is_zero=True, gs_sweep=("forward", "backward"),
+                        shape=precond_cycle_shape)
             else:
-                H.cycle("Jacobi", precond_steps, precond_omega, x_is_zero=True)
+                H.cycle("Jacobi", precond_steps, precond_omega, x_is_zero=True, shape=precond_cycle_shape)
             ops.copy(fine.x, dst)
 
         z = torch.empty_like(x)

@@ -28,7 +28,7 @@ import scipy.sparse as sp
 import torch
 
 from .. import ops, problems
-from ..hierarchy import Hierarchy, gs_sweep_pair
+from ..hierarchy import Hierarchy, cycle_children, gs_sweep_pair
 from .Solver import IterativeSolver, on_device
 
 _SMOOTHERS = ("GaussSeidel", "Jacobi", "CG")          # Multigrid.py:149-155
@@ -97,26 +97,29 @@ class Multigrid(IterativeSolver):
     def solve(self, levels=2, smoother="Jacobi", smooth_steps=1, max_iterations=100, error=1e-08,
               initial_guess=None, cycle="V", first_call=False, *, omega=1.0,
               smoother_semantics="as_shipped", gs_mode="lexicographic", coarse_refine="auto",
-              use_graph=False, mutate_initial_guess=False, gs_sweep="forward"):
+              use_graph=False, mutate_initial_guess=False, gs_sweep="forward", cycle_shape="V"):
         """gs_sweep: direction of the Gauss-Seidel smoothing (also under as_shipped semantics, where Gauss-Seidel always
         runs) -- a pyamg sweep name ("forward" | "backward" | "symmetric") for pre- and post-smoothing, or a (pre, post)
         pair.  ("forward", "backward") gives a symmetric V-cycle at one pipelined launch per smoothing half; "symmetric"
-        costs a launch per direction and step."""
+        costs a launch per direction and step.
+        cycle_shape: "V" | "W" | "F", what pyamg's cycle= selects (Hierarchy.cycle).  `cycle` keeps the reference's
+        V-only switch (:55-57)."""
         if cycle != "V":
             raise ValueError("Cycle type unknown: %r" % (cycle,))            # :55-57
         if levels < 2:
             raise ValueError("levels must be >= 2 (levels counts grids)")
         eff = self._effective_smoother(smoother, smoother_semantics)
         pair = gs_sweep_pair(gs_sweep)
+        cycle_children(cycle_shape)
         H = self._setup(levels, first_call, coarse_refine)
         H.stream.wait_stream(torch.cuda.current_stream(self._device))
         with torch.cuda.stream(H.stream):
             self._solve_on_stream(H, eff, smooth_steps, max_iterations, error, initial_guess, omega,
-                                  gs_mode, use_graph, mutate_initial_guess, pair)
+                                  gs_mode, use_graph, mutate_initial_guess, pair, cycle_shape)
         torch.cuda.current_stream(self._device).wait_stream(H.stream)
 
     def _solve_on_stream(self, H, eff, smooth_steps, max_iterations, error, initial_guess, omega,
-                         gs_mode, use_graph, mutate_initial_guess, gs_sweep=("forward", "forward")):
+                         gs_mode, use_graph, mutate_initial_guess, gs_sweep=("forward", "forward"), shape="V"):
         fine = H.levels[0]
         if initial_guess is None:
             self._log("You should put an initial guess. Used zero vector")
@@ -132,7 +135,7 @@ class Multigrid(IterativeSolver):
                 if not state["done"]:
                     np.asarray(initial_guess).reshape(-1)[:] = x_dev.cpu().numpy()
                     state["done"] = True
-        graph = H.captured_cycle(eff, smooth_steps, omega, gs_mode, gs_sweep) if use_graph else None
+        graph = H.captured_cycle(eff, smooth_steps, omega, gs_mode, gs_sweep, shape) if use_graph else None
         track = []
         for _ in range(max_iterations):                                      # :59
             self.iterations += 1
@@ -148,7 +151,7 @@ class Multigrid(IterativeSolver):
             if graph is not None and hook is None:
                 graph.launch()
             else:
-                H.cycle(eff, smooth_steps, omega, gs_mode, after_presmooth=hook, gs_sweep=gs_sweep)   # :73
+                H.cycle(eff, smooth_steps, omega, gs_mode, after_presmooth=hook, gs_sweep=gs_sweep, shape=shape)   # :73
                 hook = None
         self.solution = self._column(fine.x)
         self.residual_vector = (np.ones(shape=(self.dim, 1)) if self.iterations <= 1
@@ -163,6 +166,27 @@ class Multigrid(IterativeSolver):
                 coarse_refine="auto", gs_sweep="forward"):
         """One V-cycle on (A, rhs) from u0; returns a fresh (n,1) array.  u0 receives the
         pre-smoothed iterate like in the reference (:88-89).  gs_sweep as in solve()."""
+        return self._one_cycle("V", A, u0, rhs, smoother, smooth_steps, levels, first_call, omega, smoother_semantics,
+                               gs_mode, coarse_refine, gs_sweep)
+
+    @on_device
+    def w_cycle(self, A, u0, rhs, smoother, smooth_steps, error, levels, first_call=False, *,
+                omega=1.0, smoother_semantics="as_shipped", gs_mode="lexicographic",
+                coarse_refine="auto", gs_sweep="forward"):
+        """One W-cycle (solve(cycle_shape="W")) with v_cycle's arguments and behaviour."""
+        return self._one_cycle("W", A, u0, rhs, smoother, smooth_steps, levels, first_call, omega, smoother_semantics,
+                               gs_mode, coarse_refine, gs_sweep)
+
+    @on_device
+    def f_cycle(self, A, u0, rhs, smoother, smooth_steps, error, levels, first_call=False, *,
+                omega=1.0, smoother_semantics="as_shipped", gs_mode="lexicographic",
+                coarse_refine="auto", gs_sweep="forward"):
+        """One F-cycle (solve(cycle_shape="F")) with v_cycle's arguments and behaviour."""
+        return self._one_cycle("F", A, u0, rhs, smoother, smooth_steps, levels, first_call, omega, smoother_semantics,
+                               gs_mode, coarse_refine, gs_sweep)
+
+    def _one_cycle(self, shape, A, u0, rhs, smoother, smooth_steps, levels, first_call, omega, smoother_semantics,
+                   gs_mode, coarse_refine, gs_sweep):
         if levels < 2:
             raise ValueError("levels must be >= 2")
         eff = self._effective_smoother(smoother, smoother_semantics)
@@ -188,7 +212,7 @@ class Multigrid(IterativeSolver):
                 u0a.reshape(-1)[:] = x_dev.cpu().numpy()
         H.stream.wait_stream(torch.cuda.current_stream(self._device))
         with torch.cuda.stream(H.stream):
-            H.cycle(eff, smooth_steps, omega, gs_mode, after_presmooth=hook, gs_sweep=pair)
+            H.cycle(eff, smooth_steps, omega, gs_mode, after_presmooth=hook, gs_sweep=pair, shape=shape)
             out = fine.x.cpu().numpy().reshape(n, 1).copy()
             if eff == "GaussSeidel":
                 H.check_smoothers()
