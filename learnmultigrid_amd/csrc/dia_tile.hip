@@ -22,19 +22,6 @@ namespace {
 constexpr int kCols = 64;                     // columns of a tile = lanes of a wave
 constexpr int kLS = kCols + 2;                // LDS line stride: one guard column on either side
 
-__device__ __forceinline__ double dpp_lower(double src)      // lane i <- lane i-1, lane 0 <- 0
-{
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(src), 0x138, 0xf, 0xf, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(src), 0x138, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double dpp_upper(double src)      // lane i <- lane i+1, lane 63 <- 0
-{
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(src), 0x130, 0xf, 0xf, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(src), 0x130, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-
 struct DArgs {
     int n, W, lines;
     int tiles_x, tiles_y;
@@ -57,7 +44,7 @@ __global__ void __launch_bounds__(RR / RB * LMG_WAVE) dia_tile_kernel(DArgs a)
     constexpr int H = S + (RESID ? 1 : 0) - (ZERO ? 1 : 0);
     constexpr int kWaves = RR / RB;
     constexpr int NS = Slots<UM>::count;
-    constexpr bool DIAG = (UM & 0x145u) != 0;
+    constexpr bool DIAG = (UM & kMaskCorners) != 0;
     static_assert(RR > 2 * H + 1 && kCols > 2 * H && RR % RB == 0 && (UM & 16u), "tile smaller than its halo / no diagonal slot");
     __shared__ double s_x[2][RR * kLS];
 
@@ -103,8 +90,8 @@ __global__ void __launch_bounds__(RR / RB * LMG_WAVE) dia_tile_kernel(DArgs a)
     auto line = [&](const double *src, int r, bool sides) -> Win {
         Win w;
         w.c = src[r * kLS + 1 + lane];
-        w.m = sides ? dpp_lower(w.c) : 0.0;
-        w.p = sides ? dpp_upper(w.c) : 0.0;
+        w.m = sides ? dpp_lower<true>(w.c) : 0.0;
+        w.p = sides ? dpp_upper<true>(w.c) : 0.0;
         return w;
     };
     // A x of the centre line of (u, c, d) for element k of this lane, slot order = column order
@@ -257,10 +244,6 @@ int launch1(DArgs a, int sweeps, bool resid, bool zero, hipStream_t st)
     }
 }
 
-constexpr unsigned kMask5 = 0x0BAu;           // {-W, -1, 0, +1, +W}
-constexpr unsigned kMask7a = 0x1BBu;          // + {-W-1, +W+1}: P1 on triangles cut along one diagonal
-constexpr unsigned kMask7b = 0x0FEu;          // + {-W+1, +W-1}: the other diagonal
-constexpr unsigned kMask9 = 0x1FFu;
 
 }  // namespace
 
@@ -289,7 +272,7 @@ int lmg_dia_smooth_supported(uint32_t union_mask)
 int lmg_dia_fill(int64_t n, int32_t line_stride, const int32_t *rowptr, const int32_t *colidx, const double *vals,
                  uint32_t union_mask, double *dia, int32_t *mismatch, uint32_t *mask_out, void *stream)
 {
-    if (n < 0 || line_stride < 3 || (union_mask & ~0x1FFu) || (n > 0 && (!rowptr || !colidx || !mismatch))) return LMG_ERR_ARG;
+    if (n < 0 || line_stride < 3 || (union_mask & ~kMask9) || (n > 0 && (!rowptr || !colidx || !mismatch))) return LMG_ERR_ARG;
     if (dia && !vals) return LMG_ERR_ARG;
     if (n == 0) return LMG_OK;
     int64_t grid = (n + 255) / 256;

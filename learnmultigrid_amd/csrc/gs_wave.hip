@@ -30,7 +30,6 @@
 
 namespace {
 
-constexpr int kMaxPat = 64;
 constexpr int kPF = 5;                      // iterations (of two steps) between issuing a load and using its value
 #ifndef LMG_GS_HYST
 #define LMG_GS_HYST 2          // (8: 8.12 ms per sweep at 4097^2, 4: 7.66, 2: 7.57; 513^2: 0.93 / 0.85 / 0.82)
@@ -41,7 +40,6 @@ constexpr int kPubDelay = 6;                // iterations between a result store
 constexpr int kVmOpsBase = 11;              // vector-memory instructions per iteration: 6 loads, 2 + 2 result stores, progress
                                             // (+ 1 load with several sweeps per launch)
 constexpr int kMaxSweeps = 4;               // sweeps pipelined behind each other in one launch
-constexpr unsigned kMask5 = 0x0BAu, kMask9 = 0x1FFu, kMask7 = 0x1BBu, kMask1D = 0x038u;
 constexpr unsigned kOOB = 0xFFFFFFF0u;      // buffer offset beyond any num_records: the access is dropped / reads 0
 constexpr int kSc1 = 16;                    // buffer cache policy: sc1 (write-through / L1 bypass, agent scope)
 
@@ -63,12 +61,6 @@ struct GArgs {
                                             // [3 + s * nbands + k] columns done on the last line of band k in sweep s
 };
 
-__device__ __forceinline__ double dpp_lower(double src)      // lane i <- lane i-1, lane 0 <- 0
-{
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(src), 0x138, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(src), 0x138, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
 __device__ __forceinline__ double lo2(const u4 &v) { return __hiloint2double((int)v.y, (int)v.x); }
 __device__ __forceinline__ double hi2(const u4 &v) { return __hiloint2double((int)v.w, (int)v.z); }
 
@@ -153,7 +145,7 @@ __global__ void __launch_bounds__(64) gs_wavefront_kernel(GArgs a)
     if constexpr (BWD) {
         load_patterns_mirrored(a, s_val, s_mask, lane);
     } else {
-        for (int i = lane; i < a.npat * 9; i += 64) s_val[i] = a.st_val[i];
+        for (int i = lane; i < a.npat * 9; i += 64) s_val[i] = a.st_val[i];      // (staged in place: see lmg_common.hpp)
         for (int i = lane; i < a.npat; i += 64) s_mask[i] = a.st_mask[i];
     }
     if (lane == 0) s_band = atomicAdd(&a.work[1], 1);
@@ -311,10 +303,10 @@ __global__ void __launch_bounds__(64) gs_wavefront_kernel(GArgs a)
             // ---- two steps -----------------------------------------------------------------------------
             // (the wave shifts run with all lanes enabled: a DPP read from a lane that a branch has switched off
             // returns the destination's old value, not the neighbour's)
-            const double inA = dpp_lower(R);
+            const double inA = dpp_lower<false>(R);
             const double upA = lane == 0 ? first(cur.up, i - W + (SK - 1)) : inA;
             const double xa = step(x, upA, first(cur.down, i + W + 1), first(cur.own, i + 1), first(cur.b, i), pa);
-            const double inB = dpp_lower(R);
+            const double inB = dpp_lower<false>(R);
             const double upB = lane == 0 ? second(cur.up, i - W + (SK - 1)) : inB;
             const double xb = step(x + 1, upB, second(cur.down, i + W + 1), second(cur.own, i + 1), second(cur.b, i), pb);
             // ---- results: one 16-byte and one 8-byte store, disabled ones out of range.  Only the band's LAST line is
@@ -403,7 +395,7 @@ __global__ void __launch_bounds__(64) gs_band_lds_kernel(GArgs a)
     if constexpr (BWD) {
         load_patterns_mirrored(a, s_val, s_mask, lane);
     } else {
-        for (int i = lane; i < a.npat * 9; i += 64) s_val[i] = a.st_val[i];
+        for (int i = lane; i < a.npat * 9; i += 64) s_val[i] = a.st_val[i];      // (staged in place: see lmg_common.hpp)
         for (int i = lane; i < a.npat; i += 64) s_mask[i] = a.st_mask[i];
     }
     if (lane == 0) s_band = atomicAdd(&a.work[1], 1);
@@ -657,7 +649,7 @@ __global__ void __launch_bounds__(64) gs_band_lds_kernel(GArgs a)
         const unsigned a_x1 = own_addr_prev;                           // tile address of (y, x + 1): what the call below reads b through
         nxt = read_inputs(x + 1);
         // ---- windows move one column to the right -----------------------------------------------------------------------
-        const double inU = dpp_lower(R);                               // lane l-1's result of the previous step = new (y-1, x)
+        const double inU = dpp_lower<false>(R);                               // lane l-1's result of the previous step = new (y-1, x)
         U0 = U1;
         if (SK == 2) {
             U1 = U2;
@@ -809,7 +801,7 @@ extern "C" {
 
 int lmg_stencil_gs_supported(uint32_t union_mask)
 {
-    return union_mask == kMask5 || union_mask == kMask9 || union_mask == kMask7 || union_mask == kMask1D;
+    return union_mask == kMask5 || union_mask == kMask9 || union_mask == kMask7a || union_mask == kMask1D;
 }
 
 int64_t lmg_stencil_gs_work_bytes(int64_t n, int32_t line_stride)
@@ -865,7 +857,7 @@ int gs_sweep(int64_t n, int32_t line_stride, const uint8_t *pid, int32_t npat, c
         int per_launch = n <= g_gs_multi_max_rows ? g_gs_max_sweeps : 1;
         // bands staged through LDS: 5- / 7- / 9-point operators, 16-byte aligned vectors (the piece that straddles the end of a
         // vector of odd length is then inside its last 16 bytes), at least one full chunk per line
-        const bool lds_ok = (union_mask == kMask5 || union_mask == kMask7 || (union_mask == kMask9 && g_gs_lds9)) && line_stride >= 64 &&
+        const bool lds_ok = (union_mask == kMask5 || union_mask == kMask7a || (union_mask == kMask9 && g_gs_lds9)) && line_stride >= 64 &&
                             lmg_aligned16(x) && lmg_aligned16(b) && (reinterpret_cast<uintptr_t>(pid) & 3u) == 0;
         // (one sweep: 513^2 0.47 ms with LDS bands, 0.83 with register bands; three sweeps pipelined in one launch, LDS bands vs
         // register bands: 513^2 0.63 vs 1.21 ms, 1025^2 1.08 vs 2.58, 2049^2 1.97 vs 7.7, 4097^2 3.9 vs 22.6 -- the LDS bands take
@@ -880,14 +872,14 @@ int gs_sweep(int64_t n, int32_t line_stride, const uint8_t *pid, int32_t npat, c
         int rc;
         if (use_lds) {
             rc = union_mask == kMask5 ? launch_lds<kMask5, BWD>(a, st)
-               : union_mask == kMask7 ? launch_lds<kMask7, BWD>(a, st) : launch_lds<kMask9, BWD>(a, st);
+               : union_mask == kMask7a ? launch_lds<kMask7a, BWD>(a, st) : launch_lds<kMask9, BWD>(a, st);
             if (rc != LMG_OK) return rc;
             continue;
         }
         switch (union_mask) {
         case kMask5: rc = launch<kMask5, BWD>(a, st); break;
         case kMask9: rc = launch<kMask9, BWD>(a, st); break;
-        case kMask7: rc = launch<kMask7, BWD>(a, st); break;
+        case kMask7a: rc = launch<kMask7a, BWD>(a, st); break;
         default: rc = launch<kMask1D, BWD>(a, st); break;
         }
         if (rc != LMG_OK) return rc;

@@ -25,7 +25,6 @@
 
 namespace {
 
-enum { MODE_RESIDUAL = 0, MODE_JACOBI = 1, MODE_SPMV = 2 };
 enum { COL16 = 0, COL32 = 1 };
 enum { VAL8 = 0, VAL16 = 1, VAL64 = 2 };
 
@@ -110,10 +109,8 @@ __global__ void __launch_bounds__(kBlock, LMG_PCSR_WAVES) pcsr_sweep_kernel(PArg
     const val_t *s_val = reinterpret_cast<const val_t *>(s_valb);
 
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int xcd = (int)(blockIdx.x & 7u), slot = (int)(blockIdx.x >> 3), nslots = (int)(gridDim.x >> 3);
-    const int t_begin = xcd * a.tiles_per_xcd;
-    const int t_end = min(a.tiles, t_begin + a.tiles_per_xcd);
-    if (t_begin + slot >= t_end) return;
+    const LmgXcdTiles own = lmg_xcd_tiles(a.tiles, a.tiles_per_xcd);
+    if (own.first >= own.end) return;
 
     if (VALMODE == VAL8) {
         for (int i = t; i < 256; i += kBlock) {
@@ -125,7 +122,7 @@ __global__ void __launch_bounds__(kBlock, LMG_PCSR_WAVES) pcsr_sweep_kernel(PArg
         }
     }
 
-    for (int tile = t_begin + slot; tile < t_end; tile += nslots) {
+    for (int tile = own.first; tile < own.end; tile += own.stride) {
         const int base = a.tile_base[tile];
         const int end = a.tile_base[tile + 1];
         const int cb0 = (COLMODE == COL16) ? a.tile_colbase[tile] : 0;
@@ -260,23 +257,6 @@ __global__ void __launch_bounds__(kBlock, LMG_PCSR_WAVES) pcsr_sweep_kernel(PArg
     }
 }
 
-__global__ void __launch_bounds__(1024) pcsr_reduce_partials_kernel(const double *partial, int64_t count,
-                                                                    double *out)
-{
-    __shared__ double s_red[1024 / LMG_WAVE];
-    double v0 = 0.0, v1 = 0.0, v2 = 0.0, v3 = 0.0;
-    int64_t i = threadIdx.x;
-    for (; i + 3 * 1024 < count; i += 4 * 1024) {
-        v0 += partial[i];
-        v1 += partial[i + 1024];
-        v2 += partial[i + 2048];
-        v3 += partial[i + 3072];
-    }
-    for (; i < count; i += 1024) v0 += partial[i];
-    const double tot = lmg_block_sum<1024>((v0 + v1) + (v2 + v3), s_red);
-    if (threadIdx.x == 0) out[0] = tot;
-}
-
 constexpr int kMaxLds = 64 * 1024;
 
 int lds_bytes(int cap, int colmode, int valmode)
@@ -344,16 +324,9 @@ int launch_geo(PArgs a, hipStream_t st)
     const int lds = lds_bytes(a.cap, COLMODE, VALMODE);
     if (lds > kMaxLds) return LMG_ERR_CAPACITY;
     // persistent grid: exactly as many workgroups per CU as registers + LDS admit
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
-            &per_cu, pcsr_sweep_kernel<MODE, COLMODE, VALMODE, JU, 0, kBlock, kRpt>, kBlock, (size_t)lds) != hipSuccess ||
-        per_cu < 1)
-        per_cu = 4;
-    if (per_cu > 32) per_cu = 32;
-    int64_t grid = 256 * (int64_t)per_cu;
-    if (grid > (int64_t)a.tiles_per_xcd * 8) grid = (int64_t)a.tiles_per_xcd * 8;
-    hipLaunchKernelGGL((pcsr_sweep_kernel<MODE, COLMODE, VALMODE, JU, 0, kBlock, kRpt>), dim3((unsigned)grid),
-                       dim3(kBlock), lds, st, a);
+    const auto kernel = pcsr_sweep_kernel<MODE, COLMODE, VALMODE, JU, 0, kBlock, kRpt>;
+    const unsigned grid = lmg_persistent_grid<kBlock>(kernel, (size_t)lds, 32, 0, a.tiles_per_xcd);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, st, a);
     LMG_CHECK_LAUNCH();
     return LMG_OK;
 }
@@ -401,15 +374,7 @@ int lmg_pcsr_sweep(int mode, int64_t n, int64_t nnz, int32_t tile_rows, int32_t 
     if (valmode != VAL64 && (!dict || ndict <= 0)) return LMG_ERR_ARG;
     if ((valmode == VAL8 && ndict > 256) || (valmode == VAL16 && ndict > 65536)) return LMG_ERR_ARG;
     if (!lmg_aligned16(col) || !lmg_aligned16(val)) return LMG_ERR_ALIGN;
-    if (mode == MODE_SPMV) {
-        if (!out || x == out) return LMG_ERR_ARG;
-    } else if (mode == MODE_JACOBI) {
-        if (!b || !out || x == out) return LMG_ERR_ARG;
-    } else if (mode == MODE_RESIDUAL) {
-        if (!b || (partials == nullptr) != (norm2 == nullptr) || (!out && !partials)) return LMG_ERR_ARG;
-    } else {
-        return LMG_ERR_ARG;
-    }
+    if (lmg_check_sweep_args(mode, x, b, out, partials, norm2) != LMG_OK) return LMG_ERR_ARG;
     PArgs a;
     a.n = (int)n;
     a.nnz = (int)nnz;
@@ -436,10 +401,7 @@ int lmg_pcsr_sweep(int mode, int64_t n, int64_t nnz, int32_t tile_rows, int32_t 
     else if (mode == MODE_JACOBI) rc = dispatch<MODE_JACOBI>(a, colmode, valmode, st);
     else rc = dispatch<MODE_SPMV>(a, colmode, valmode, st);
     if (rc != LMG_OK) return rc;
-    if (mode == MODE_RESIDUAL && partials) {
-        hipLaunchKernelGGL(pcsr_reduce_partials_kernel, dim3(1), dim3(1024), 0, st, partials, (int64_t)a.tiles, norm2);
-        LMG_CHECK_LAUNCH();
-    }
+    if (mode == MODE_RESIDUAL && partials) return lmg_reduce_partials(partials, a.tiles, norm2, st);
     return LMG_OK;
 }
 

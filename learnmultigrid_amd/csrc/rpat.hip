@@ -21,10 +21,8 @@
 
 namespace {
 
-enum { MODE_RESIDUAL = 0, MODE_JACOBI = 1, MODE_SPMV = 2 };
-
 constexpr int kBlock = 256;
-constexpr int kMaxPat = 256;      // pattern ids are uint8; id 255 is never used by the builder
+constexpr int kMaxRowPat = 256;   // pattern ids are uint8; id 255 is never used by the builder
 constexpr int kMaxEnt = 1024;     // total entries of all patterns (LDS: 12 KB)
 
 // Column base of a row for RECTANGULAR grid operators (transfers between nested grids): with
@@ -82,18 +80,17 @@ __global__ void __launch_bounds__(kBlock) rpat_sweep_kernel(RArgs a)
 {
     constexpr bool NTL = NT && (LMG_RPAT_NT_MODE & 1), NTS = NT && (LMG_RPAT_NT_MODE & 2);
     constexpr int kTileRows = kBlock * kRpt;
-    __shared__ int s_ptr[kMaxPat + 1];
+    __shared__ int s_ptr[kMaxRowPat + 1];
     __shared__ int s_off[kMaxEnt];
     __shared__ double s_val[kMaxEnt];
-    __shared__ double s_diag[MODE == MODE_JACOBI ? kMaxPat : 1];
-    __shared__ double s_rdiag[MODE == MODE_JACOBI ? kMaxPat : 1];
+    __shared__ double s_diag[MODE == MODE_JACOBI ? kMaxRowPat : 1];
+    __shared__ double s_rdiag[MODE == MODE_JACOBI ? kMaxRowPat : 1];
     __shared__ double s_red[kBlock / LMG_WAVE];
 
     const int t = threadIdx.x;
-    const int xcd = (int)(blockIdx.x & 7u), slot = (int)(blockIdx.x >> 3), nslots = (int)(gridDim.x >> 3);
-    const int t_begin = xcd * a.tiles_per_xcd;
-    const int t_end = min(a.tiles, t_begin + a.tiles_per_xcd);
-    if (t_begin + slot >= t_end) return;
+    const LmgXcdTiles own = lmg_xcd_tiles(a.tiles, a.tiles_per_xcd);
+    const int t_end = own.end, nslots = own.stride;
+    if (own.first >= t_end) return;
 
     // Pattern ids and right-hand sides travel through registers two tiles ahead, in two register
     // sets (A, B) used alternately.  The loop body is straight-line on purpose: the loads of set A
@@ -199,7 +196,7 @@ __global__ void __launch_bounds__(kBlock) rpat_sweep_kernel(RArgs a)
     };
     int patA[kRpt], patB[kRpt];
     double bA[kRpt], bB[kRpt];
-    int tile = t_begin + slot;
+    int tile = own.first;
     load_tile(tile, patA, bA);
     load_tile(tile + nslots, patB, bB);
     // the pattern tables are staged while the first two tiles' ids and right-hand sides are in flight: on the small
@@ -233,22 +230,6 @@ __global__ void __launch_bounds__(kBlock) rpat_sweep_kernel(RArgs a)
     if (tile < t_end) process(tile, patA, bA);
 }
 
-__global__ void __launch_bounds__(1024) rpat_reduce_partials_kernel(const double *partial, int64_t count, double *out)
-{
-    __shared__ double s_red[1024 / LMG_WAVE];
-    double v0 = 0.0, v1 = 0.0, v2 = 0.0, v3 = 0.0;
-    int64_t i = threadIdx.x;
-    for (; i + 3 * 1024 < count; i += 4 * 1024) {
-        v0 += partial[i];
-        v1 += partial[i + 1024];
-        v2 += partial[i + 2048];
-        v3 += partial[i + 3072];
-    }
-    for (; i < count; i += 1024) v0 += partial[i];
-    const double tot = lmg_block_sum<1024>((v0 + v1) + (v2 + v3), s_red);
-    if (threadIdx.x == 0) out[0] = tot;
-}
-
 int g_rpat_variant = 0;      // 0 = pick from the longest pattern; 1..4 = forced (tuning)
 
 template <int MODE, int JU, int kRpt, bool NT, bool MAP = false>
@@ -256,14 +237,9 @@ int launch_nt(RArgs a, hipStream_t st)
 {
     a.tiles = (a.n + kBlock * kRpt - 1) / (kBlock * kRpt);
     a.tiles_per_xcd = (a.tiles + 7) / 8;
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rpat_sweep_kernel<MODE, JU, kRpt, NT, MAP>, kBlock, 0) !=
-            hipSuccess || per_cu < 1)
-        per_cu = 4;
-    if (per_cu > 8) per_cu = 8;
-    int64_t grid = 256 * (int64_t)per_cu;
-    if (grid > (int64_t)a.tiles_per_xcd * 8) grid = (int64_t)a.tiles_per_xcd * 8;
-    hipLaunchKernelGGL((rpat_sweep_kernel<MODE, JU, kRpt, NT, MAP>), dim3((unsigned)grid), dim3(kBlock), 0, st, a);
+    const auto kernel = rpat_sweep_kernel<MODE, JU, kRpt, NT, MAP>;
+    const unsigned grid = lmg_persistent_grid<kBlock>(kernel, 0, 8, 0, a.tiles_per_xcd);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, st, a);
     LMG_CHECK_LAUNCH();
     return a.tiles;
 }
@@ -386,7 +362,7 @@ extern "C" {
 
 int lmg_rpat_limits(int32_t *max_patterns, int32_t *max_entries)
 {
-    if (max_patterns) *max_patterns = kMaxPat - 1;
+    if (max_patterns) *max_patterns = kMaxRowPat - 1;
     if (max_entries) *max_entries = kMaxEnt;
     return LMG_OK;
 }
@@ -426,18 +402,10 @@ int lmg_rpat_sweep_grid(int mode, int64_t n, const int32_t *h_grid_map, const ui
     GridMap gm;
     if (make_grid_map(h_grid_map, &gm) != LMG_OK) return LMG_ERR_ARG;
     if (gm.row_len > 0 && mode != MODE_SPMV) return LMG_ERR_ARG;         // rectangular operators: SpMV only
-    if (n < 0 || n >= INT32_MAX || npat < 1 || npat >= kMaxPat || nent < 0 || nent > kMaxEnt) return LMG_ERR_ARG;
+    if (n < 0 || n >= INT32_MAX || npat < 1 || npat >= kMaxRowPat || nent < 0 || nent > kMaxEnt) return LMG_ERR_ARG;
     if (n == 0) return LMG_OK;
     if (!pid || !pat_ptr || !x || (nent > 0 && (!pat_off || !pat_val))) return LMG_ERR_ARG;
-    if (mode == MODE_SPMV) {
-        if (!out || x == out) return LMG_ERR_ARG;
-    } else if (mode == MODE_JACOBI) {
-        if (!b || !out || x == out) return LMG_ERR_ARG;
-    } else if (mode == MODE_RESIDUAL) {
-        if (!b || (partials == nullptr) != (norm2 == nullptr) || (!out && !partials)) return LMG_ERR_ARG;
-    } else {
-        return LMG_ERR_ARG;
-    }
+    if (lmg_check_sweep_args(mode, x, b, out, partials, norm2) != LMG_OK) return LMG_ERR_ARG;
     RArgs a;
     a.map = gm;
     a.n = (int)n;
@@ -460,10 +428,7 @@ int lmg_rpat_sweep_grid(int mode, int64_t n, const int32_t *h_grid_map, const ui
     else if (mode == MODE_JACOBI) tiles = launch<MODE_JACOBI>(a, max_len, st);
     else tiles = launch<MODE_SPMV>(a, max_len, st);
     if (tiles < 0) return tiles;
-    if (mode == MODE_RESIDUAL && partials) {
-        hipLaunchKernelGGL(rpat_reduce_partials_kernel, dim3(1), dim3(1024), 0, st, partials, (int64_t)tiles, norm2);
-        LMG_CHECK_LAUNCH();
-    }
+    if (mode == MODE_RESIDUAL && partials) return lmg_reduce_partials(partials, tiles, norm2, st);
     return LMG_OK;
 }
 

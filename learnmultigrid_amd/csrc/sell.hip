@@ -20,7 +20,6 @@
 
 namespace {
 
-enum { MODE_RESIDUAL = 0, MODE_JACOBI = 1, MODE_SPMV = 2 };
 constexpr int kBlock = 256;
 constexpr int kSlicesPerBlock = kBlock / LMG_WAVE;
 
@@ -52,7 +51,7 @@ __global__ void __launch_bounds__(kBlock) sell_sweep_kernel(SArgs a)
     const col_t *col = static_cast<const col_t *>(a.col);
     const int lane = threadIdx.x & (LMG_WAVE - 1), wave = threadIdx.x / LMG_WAVE;
     // XCD-aware: XCD k (blockIdx mod 8) works on the k-th contiguous eighth of the slices
-    const int blk = (int)(blockIdx.x & 7u) * a.blocks_per_xcd + (int)(blockIdx.x >> 3);
+    const int blk = lmg_xcd_tile(a.blocks_per_xcd);
     const int slice = blk * kSlicesPerBlock + wave;
     double local = 0.0;
     if (blk < a.nblocks && slice < a.nslices) {
@@ -110,22 +109,6 @@ __global__ void __launch_bounds__(kBlock) sell_sweep_kernel(SArgs a)
         const double tot = lmg_block_sum<kBlock>(local, s_red);
         if (threadIdx.x == 0 && blk < a.nblocks) a.partial[blk] = tot;
     }
-}
-
-__global__ void __launch_bounds__(1024) sell_reduce_partials_kernel(const double *partial, int64_t count, double *out)
-{
-    __shared__ double s_red[1024 / LMG_WAVE];
-    double v0 = 0.0, v1 = 0.0, v2 = 0.0, v3 = 0.0;
-    int64_t i = threadIdx.x;
-    for (; i + 3 * 1024 < count; i += 4 * 1024) {
-        v0 += partial[i];
-        v1 += partial[i + 1024];
-        v2 += partial[i + 2048];
-        v3 += partial[i + 3072];
-    }
-    for (; i < count; i += 1024) v0 += partial[i];
-    const double tot = lmg_block_sum<1024>((v0 + v1) + (v2 + v3), s_red);
-    if (threadIdx.x == 0) out[0] = tot;
 }
 
 // ---- building the format (setup) -------------------------------------------------------------
@@ -260,15 +243,7 @@ int lmg_sell_sweep(int mode, int64_t n, const int64_t *slice_base, const int32_t
     if (n == 0) return LMG_OK;
     if (!slice_base || !slice_len || !rowlen || !col || !val || !x) return LMG_ERR_ARG;
     if (colmode == 0 && !slice_cmin) return LMG_ERR_ARG;
-    if (mode == MODE_SPMV) {
-        if (!out || x == out) return LMG_ERR_ARG;
-    } else if (mode == MODE_JACOBI) {
-        if (!b || !out || x == out) return LMG_ERR_ARG;
-    } else if (mode == MODE_RESIDUAL) {
-        if (!b || (partials == nullptr) != (norm2 == nullptr) || (!out && !partials)) return LMG_ERR_ARG;
-    } else {
-        return LMG_ERR_ARG;
-    }
+    if (lmg_check_sweep_args(mode, x, b, out, partials, norm2) != LMG_OK) return LMG_ERR_ARG;
     SArgs a;
     a.n = (int)n;
     a.nslices = (int)((n + LMG_WAVE - 1) / LMG_WAVE);
@@ -296,11 +271,8 @@ int lmg_sell_sweep(int mode, int64_t n, const int64_t *slice_base, const int32_t
            : mode == MODE_JACOBI ? launch<MODE_JACOBI, false>(a, max_len, st) : launch<MODE_SPMV, false>(a, max_len, st);
     }
     if (rc != LMG_OK) return rc;
-    if (mode == MODE_RESIDUAL && partials) {
-        // blocks beyond nblocks (grid rounded up to a multiple of 8) write nothing: only nblocks partials exist
-        hipLaunchKernelGGL(sell_reduce_partials_kernel, dim3(1), dim3(1024), 0, st, partials, (int64_t)a.nblocks, norm2);
-        LMG_CHECK_LAUNCH();
-    }
+    // blocks beyond nblocks (grid rounded up to a multiple of 8) write nothing: only nblocks partials exist
+    if (mode == MODE_RESIDUAL && partials) return lmg_reduce_partials(partials, a.nblocks, norm2, st);
     return LMG_OK;
 }
 

@@ -27,13 +27,7 @@
 
 namespace {
 
-enum { MODE_RESIDUAL = 0, MODE_JACOBI = 1, MODE_SPMV = 2 };
-
 constexpr int kBlock = 256;
-constexpr int kMaxPat = 64;       // stencil patterns held in LDS (9 values each)
-
-typedef double d2 __attribute__((ext_vector_type(2)));
-struct __attribute__((aligned(8))) d2u { double a, b; };      // 16 bytes at 8-byte alignment
 
 struct SArgs {
     int n;
@@ -51,21 +45,6 @@ struct SArgs {
     double alpha, beta;
     double *partial;
 };
-
-__device__ __forceinline__ double dpp_from_lower_lane(double src, double lane0)
-{
-    // lane i <- lane i-1 (wave_shr:1); lane 0 keeps `lane0`
-    const int lo = __builtin_amdgcn_update_dpp(__double2loint(lane0), __double2loint(src), 0x138, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(__double2hiint(lane0), __double2hiint(src), 0x138, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double dpp_from_upper_lane(double src, double lane63)
-{
-    // lane i <- lane i+1 (wave_shl:1); lane 63 keeps `lane63`
-    const int lo = __builtin_amdgcn_update_dpp(__double2loint(lane63), __double2loint(src), 0x130, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(__double2hiint(lane63), __double2hiint(src), 0x130, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
 
 // x[i], x[i+1] (0 where the index is outside [0, n)); ALIGNED16: i is even and the base 16-byte aligned
 template <bool ALIGNED16, bool NT>
@@ -115,17 +94,16 @@ __global__ void __launch_bounds__(kBlock, DIAG ? 4 : 8) stencil_sweep_kernel(SAr
 
     const int t = threadIdx.x;
     const int lane = t & (LMG_WAVE - 1);
-    const int xcd = (int)(blockIdx.x & 7u), slot = (int)(blockIdx.x >> 3), nslots = (int)(gridDim.x >> 3);
-    const int t_begin = xcd * a.tiles_per_xcd;
-    const int t_end = min(a.tiles, t_begin + a.tiles_per_xcd);
-    if (t_begin + slot >= t_end) {
+    const LmgXcdTiles own = lmg_xcd_tiles(a.tiles, a.tiles_per_xcd);
+    const int t_end = own.end, nslots = own.stride;
+    if (own.first >= t_end) {
         if (MODE == MODE_RESIDUAL && a.partial != nullptr && t == 0) a.partial[blockIdx.x] = 0.0;
         return;
     }
 
     const int n = a.n;
     const int64_t W = a.W;
-    const bool use_u = (a.umask & 0x007u) != 0, use_d = (a.umask & 0x1C0u) != 0;
+    const bool use_u = (a.umask & kMaskUpper) != 0, use_d = (a.umask & kMaskLower) != 0;
     const bool edge_lane = lane == 0 || lane == LMG_WAVE - 1;
 
     auto load_tile = [&](int tile, Pair<DIAG> (&P)[kP]) {
@@ -238,7 +216,7 @@ __global__ void __launch_bounds__(kBlock, DIAG ? 4 : 8) stencil_sweep_kernel(SAr
     // The first tile's rows are requested BEFORE the pattern table is staged: on the small levels of a cycle a
     // workgroup has one tile, and table-then-rows would be two dependent trips to memory in a 5 us kernel.
     Pair<DIAG> PA[kP];
-    int tile = t_begin + slot;
+    int tile = own.first;
     load_tile(tile, PA);
     for (int i = t; i < a.npat * 9; i += kBlock) s_val[i] = a.st_val[i];
     for (int i = t; i < a.npat; i += kBlock) {
@@ -265,22 +243,6 @@ __global__ void __launch_bounds__(kBlock, DIAG ? 4 : 8) stencil_sweep_kernel(SAr
     }
 }
 
-__global__ void __launch_bounds__(1024) stencil_reduce_partials_kernel(const double *partial, int64_t count, double *out)
-{
-    __shared__ double s_red[1024 / LMG_WAVE];
-    double v0 = 0.0, v1 = 0.0, v2 = 0.0, v3 = 0.0;
-    int64_t i = threadIdx.x;
-    for (; i + 3 * 1024 < count; i += 4 * 1024) {
-        v0 += partial[i];
-        v1 += partial[i + 1024];
-        v2 += partial[i + 2048];
-        v3 += partial[i + 3072];
-    }
-    for (; i < count; i += 1024) v0 += partial[i];
-    const double tot = lmg_block_sum<1024>((v0 + v1) + (v2 + v3), s_red);
-    if (threadIdx.x == 0) out[0] = tot;
-}
-
 int g_stencil_nt_rows = 1 << 23;      // rows from which the id / b / out streams bypass the caches
 int g_stencil_wgs_per_cu = 0;         // 0 = occupancy query
 
@@ -290,15 +252,9 @@ int launch_k(SArgs a, hipStream_t st)
     constexpr int kTileRows = 2 * kBlock;
     a.tiles = (a.n + kTileRows - 1) / kTileRows;
     a.tiles_per_xcd = (a.tiles + 7) / 8;
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, stencil_sweep_kernel<MODE, DIAG, NT>, kBlock, 0) !=
-            hipSuccess || per_cu < 1)
-        per_cu = 4;
-    if (per_cu > 8) per_cu = 8;
-    if (g_stencil_wgs_per_cu > 0 && g_stencil_wgs_per_cu < per_cu) per_cu = g_stencil_wgs_per_cu;
-    int64_t grid = 256 * (int64_t)per_cu;
-    if (grid > (int64_t)a.tiles_per_xcd * 8) grid = (int64_t)a.tiles_per_xcd * 8;
-    hipLaunchKernelGGL((stencil_sweep_kernel<MODE, DIAG, NT>), dim3((unsigned)grid), dim3(kBlock), 0, st, a);
+    const auto kernel = stencil_sweep_kernel<MODE, DIAG, NT>;
+    const unsigned grid = lmg_persistent_grid<kBlock>(kernel, 0, 8, g_stencil_wgs_per_cu, a.tiles_per_xcd);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, st, a);
     LMG_CHECK_LAUNCH();
     return (int)grid;
 }
@@ -306,7 +262,7 @@ int launch_k(SArgs a, hipStream_t st)
 template <int MODE>
 int launch(SArgs a, hipStream_t st)
 {
-    const bool diag = (a.umask & 0x145u) != 0;                 // slots 0, 2, 6, 8
+    const bool diag = (a.umask & kMaskCorners) != 0;
     const bool nt = a.n >= g_stencil_nt_rows;
     if (diag) return nt ? launch_k<MODE, true, true>(a, st) : launch_k<MODE, true, false>(a, st);
     return nt ? launch_k<MODE, false, true>(a, st) : launch_k<MODE, false, false>(a, st);
@@ -348,21 +304,13 @@ int lmg_stencil_sweep(int mode, int64_t n, int32_t line_stride, const uint8_t *p
                       const double *b, double *out, double alpha, double beta, double *partials, double *norm2,
                       void *stream)
 {
-    if (n < 0 || n >= INT32_MAX - 4096 || npat < 1 || npat > kMaxPat || (union_mask & ~0x1FFu)) return LMG_ERR_ARG;
+    if (n < 0 || n >= INT32_MAX - 4096 || npat < 1 || npat > kMaxPat || (union_mask & ~kMask9)) return LMG_ERR_ARG;
     if (n == 0) return LMG_OK;
     if (!pid || !st_val || !st_mask || !x) return LMG_ERR_ARG;
     // the line stride only matters when an upper / lower line is referenced at all
-    if ((union_mask & 0x1C7u) && (line_stride < 3 || line_stride >= n)) return LMG_ERR_ARG;
+    if ((union_mask & kMaskOffLine) && (line_stride < 3 || line_stride >= n)) return LMG_ERR_ARG;
     if (!lmg_aligned16(x) || (b && !lmg_aligned16(b)) || (out && !lmg_aligned16(out))) return LMG_ERR_ALIGN;
-    if (mode == MODE_SPMV) {
-        if (!out || x == out) return LMG_ERR_ARG;
-    } else if (mode == MODE_JACOBI) {
-        if (!b || !out || x == out) return LMG_ERR_ARG;
-    } else if (mode == MODE_RESIDUAL) {
-        if (!b || (partials == nullptr) != (norm2 == nullptr) || (!out && !partials)) return LMG_ERR_ARG;
-    } else {
-        return LMG_ERR_ARG;
-    }
+    if (lmg_check_sweep_args(mode, x, b, out, partials, norm2) != LMG_OK) return LMG_ERR_ARG;
     SArgs a;
     a.n = (int)n;
     a.W = line_stride;
@@ -384,10 +332,7 @@ int lmg_stencil_sweep(int mode, int64_t n, int32_t line_stride, const uint8_t *p
     else if (mode == MODE_JACOBI) nwg = launch<MODE_JACOBI>(a, st);
     else nwg = launch<MODE_SPMV>(a, st);
     if (nwg < 0) return nwg;
-    if (mode == MODE_RESIDUAL && partials) {
-        hipLaunchKernelGGL(stencil_reduce_partials_kernel, dim3(1), dim3(1024), 0, st, partials, (int64_t)nwg, norm2);
-        LMG_CHECK_LAUNCH();
-    }
+    if (mode == MODE_RESIDUAL && partials) return lmg_reduce_partials(partials, nwg, norm2, st);
     return LMG_OK;
 }
 

@@ -35,14 +35,7 @@ namespace {
 
 constexpr int kBlock = 256;
 constexpr int kWavesPerBlock = kBlock / LMG_WAVE;
-constexpr int kMaxPat = 64;
 constexpr int kStripCols = 2 * LMG_WAVE;      // linear indices per line and wave
-constexpr unsigned kMask5 = 0x0BAu;           // slots {-W, -1, 0, +1, +W}
-constexpr unsigned kMask9 = 0x1FFu;           // full 3x3
-constexpr unsigned kMask1D = 0x038u;          // {-1, 0, +1}
-
-typedef double d2 __attribute__((ext_vector_type(2)));
-struct __attribute__((aligned(8))) d2u { double a, b; };
 
 struct MArgs {
     int n;
@@ -99,34 +92,6 @@ template <int H, bool PROL, bool REST> struct StripGeom {
     static constexpr int U = EVEN ? ((kStripCols - ML - MRmin) & ~1) : kStripCols - ML - MRmin;
 };
 
-__device__ __forceinline__ double dpp_lower(double src)      // lane i <- lane i-1, lane 0 <- 0
-{
-    // (bound_ctrl: a lane without a source reads 0 -- no register has to be cleared for it first)
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(src), 0x138, 0xf, 0xf, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(src), 0x138, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double dpp_upper(double src)      // lane i <- lane i+1, lane 63 <- 0
-{
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(src), 0x130, 0xf, 0xf, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(src), 0x130, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-
-__device__ __forceinline__ d2 load2(const double *__restrict__ v, int64_t i, int n)
-{
-    d2 r;
-    if (i >= 0 && i + 1 < n) {
-        const d2u t = *reinterpret_cast<const d2u *>(v + i);
-        r.x = t.a;
-        r.y = t.b;
-    } else {
-        r.x = (i >= 0 && i < n) ? v[i] : 0.0;
-        r.y = (i + 1 >= 0 && i + 1 < n) ? v[i + 1] : 0.0;
-    }
-    return r;
-}
-
 // One line of input as it comes out of memory.  Every step issues EXACTLY the same vector-memory
 // instructions (three loads from clamped addresses, two -- with the residual four -- buffer stores whose
 // disabled lanes point out of range), none of them inside a branch, and nothing is computed from a load's
@@ -160,8 +125,8 @@ __device__ __forceinline__ void window(const d2 &c, double (&w)[4])
     w[1] = c.x;
     w[2] = c.y;
     if (SIDES) {
-        w[0] = dpp_lower(c.y);
-        w[3] = dpp_upper(c.x);
+        w[0] = dpp_lower<true>(c.y);
+        w[3] = dpp_upper<true>(c.x);
     } else {
         w[0] = w[3] = 0.0;
     }
@@ -172,7 +137,7 @@ template <unsigned UM>
 __device__ __forceinline__ void apply_rows(const double *s_val, int pA, int pB, int mA, int mB,
                                            const d2 &u, const d2 &c, const d2 &d, double &accA, double &accB)
 {
-    constexpr bool DIAG = (UM & 0x145u) != 0;
+    constexpr bool DIAG = (UM & kMaskCorners) != 0;
     double wu[4], wc[4], wd[4];
     window<true>(c, wc);
     window<DIAG>(u, wu);
@@ -198,7 +163,7 @@ template <unsigned UM>
 __device__ __forceinline__ void apply_rows_hot(const double (&hv)[9], const d2 &u, const d2 &c,
                                                const d2 &d, double &accA, double &accB)
 {
-    constexpr bool DIAG = (UM & 0x145u) != 0;
+    constexpr bool DIAG = (UM & kMaskCorners) != 0;
     double wu[4], wc[4], wd[4];
     window<true>(c, wc);
     window<DIAG>(u, wu);
@@ -534,7 +499,7 @@ __device__ __forceinline__ void fused_march(const MArgs &a, const Tables &T, con
                     }
                     const double en = L.e;
                     const double e0 = odd ? e_prev : en, e1 = en;
-                    const double e0r = dpp_upper(e0), e1r = dpp_upper(e1);
+                    const double e0r = dpp_upper<true>(e0), e1r = dpp_upper<true>(e1);
                     double accA, accB;
                     if (__all(q2 == (odd ? hotq_odd : hotq_even))) {          // wave-uniform
                         if (!odd) {
@@ -633,7 +598,7 @@ __device__ __forceinline__ void fused_march(const MArgs &a, const Tables &T, con
                     // line adds the middle of its own row.  Two running sums per lane, no ring of residual lines; the
                     // same products and sums in the same order as lmg_rpat_sweep_grid(SPMV, alpha = 1, beta = 0).
                     const double rA = Bq[q].x - accA, rB = Bq[q].y - accB;
-                    const double wl[3] = {dpp_lower(rB), rA, rB};              // columns 2X - 1, 2X, 2X + 1
+                    const double wl[3] = {dpp_lower<true>(rB), rA, rB};              // columns 2X - 1, 2X, 2X + 1
                     const bool y_odd = ((u - S - 1) & 1) != 0;                 // y_begin is even: compile time
                     unsigned off_bc = kOOB;
                     bool emit_line = false;                                    // FAST: the finished row's line is stored by this wave
@@ -720,7 +685,7 @@ __global__ void __launch_bounds__(kBlock, (REST && S >= 3) ? 2 : 3) stencil_fuse
     __shared__ int s_rm[REST ? kMaxPat : 1];
 
     const int t_ = threadIdx.x;
-    for (int i = t_; i < a.npat * 9; i += kBlock) s_val[i] = a.st_val[i];
+    for (int i = t_; i < a.npat * 9; i += kBlock) s_val[i] = a.st_val[i];      // (staged in place: see lmg_common.hpp)
     for (int i = t_; i < a.npat; i += kBlock) {
         const int m = a.st_mask[i];
         const double dg = (m & 16) ? a.st_val[i * 9 + 4] : 0.0;
@@ -956,7 +921,7 @@ static int fill_args(MArgs &a, int64_t n, int32_t line_stride, const uint8_t *pi
                      const int32_t *st_mask, uint32_t union_mask, int32_t hot_pattern, const double *h_hot_val, int sweeps,
                      const double *x_in, const double *b, double omega, double *x_out, double *r_out)
 {
-    if (n < 0 || n >= (1ll << 29) - 4096 || npat < 1 || npat > kMaxPat || (union_mask & ~0x1FFu)) return LMG_ERR_ARG;   // 32-bit byte offsets
+    if (n < 0 || n >= (1ll << 29) - 4096 || npat < 1 || npat > kMaxPat || (union_mask & ~kMask9)) return LMG_ERR_ARG;   // 32-bit byte offsets
     if (sweeps < 1 || sweeps > 3) return LMG_ERR_ARG;
     if (n == 0) return LMG_OK;
     if (n < 2) return LMG_ERR_CAPACITY;

@@ -20,26 +20,8 @@ namespace {
 
 constexpr int kRB = 2;                        // consecutive lines of a tile a wave owns: a tile of RR lines is RR / 2 waves
                                               // (4 lines per wave: cfg#2 cycle 0.131 instead of 0.122 ms, cfg#4 equal)
-constexpr int kMaxPat = 64;
 constexpr int kCols = 64;                     // columns of a tile = lanes of a wave
 constexpr int kLS = kCols + 2;                // LDS line stride: one guard column on either side
-constexpr unsigned kMask5 = 0x0BAu;
-constexpr unsigned kMask9 = 0x1FFu;
-
-__device__ __forceinline__ double dpp_lower(double src)      // lane i <- lane i-1, lane 0 <- 0
-{
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(src), 0x138, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(src), 0x138, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double dpp_upper(double src)      // lane i <- lane i+1, lane 63 <- 0
-{
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(src), 0x130, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(src), 0x130, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-
-struct __attribute__((aligned(8))) d2u { double a, b; };
 
 struct TArgs {
     int n, W, lines, npat;
@@ -118,7 +100,7 @@ stencil_tile_kernel(TArgs a)
     const int n = a.n;
     const int64_t W = a.W;
     constexpr int RB = RBV;                                      // consecutive lines of the tile a wave owns
-    constexpr bool DIAG = (UM & 0x145u) != 0;
+    constexpr bool DIAG = (UM & kMaskCorners) != 0;
     const int rb0 = wave * RB;
 
     // ---- the wave's lines are requested first, the pattern table is staged while they are in flight -------------
@@ -210,7 +192,7 @@ stencil_tile_kernel(TArgs a)
             lr[k] = crow ? ((int)a.rpid[jc < a.nc ? jc : 0] | 0x100) : 0;
         }
     }
-    for (int i = t; i < a.npat * 9; i += kBlock) s_val[i] = a.st_val[i];
+    for (int i = t; i < a.npat * 9; i += kBlock) s_val[i] = a.st_val[i];      // (staged in place: see lmg_common.hpp)
     for (int i = t; i < a.npat; i += kBlock) {
         const int m = a.st_mask[i];
         const double dg = (m & 16) ? a.st_val[i * 9 + 4] : 0.0;
@@ -268,8 +250,8 @@ stencil_tile_kernel(TArgs a)
     auto line = [&](const double *src, int r, bool sides) -> Win {
         Win w;
         w.c = src[r * kLS + 1 + lane];
-        w.m = sides ? dpp_lower(w.c) : 0.0;
-        w.p = sides ? dpp_upper(w.c) : 0.0;
+        w.m = sides ? dpp_lower<false>(w.c) : 0.0;
+        w.p = sides ? dpp_upper<false>(w.c) : 0.0;
         return w;
     };
     // A x of the centre line of (u, c, d) for this lane, slot order = column order
@@ -580,7 +562,7 @@ static int tile_args(TArgs &a, int64_t n, int32_t line_stride, const uint8_t *pi
                      const int32_t *st_mask, uint32_t union_mask, int32_t hot_pattern, const double *h_hot_val, int sweeps,
                      const double *x_in, const double *b, double omega, double *x_out, double *r_out)
 {
-    if (n < 0 || n >= (1ll << 31) - 4096 || npat < 1 || npat > kMaxPat || (union_mask & ~0x1FFu)) return LMG_ERR_ARG;
+    if (n < 0 || n >= (1ll << 31) - 4096 || npat < 1 || npat > kMaxPat || (union_mask & ~kMask9)) return LMG_ERR_ARG;
     if (sweeps < 1 || sweeps > 3) return LMG_ERR_ARG;
     if (n == 0) return LMG_OK;
     if (!pid || !st_val || !st_mask || !b || !x_out || x_in == x_out || r_out == x_out || (r_out && r_out == x_in))

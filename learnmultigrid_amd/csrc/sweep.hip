@@ -27,8 +27,6 @@
 
 namespace {
 
-enum { MODE_RESIDUAL = 0, MODE_JACOBI = 1, MODE_SPMV = 2 };
-
 struct SweepArgs {
     int n;
     int nnz;
@@ -56,7 +54,7 @@ __global__ void __launch_bounds__(BLOCK) csr_sweep_kernel(SweepArgs a)
     __shared__ double s_red[BLOCK / LMG_WAVE];
 
     const int t = threadIdx.x;
-    const int tile = (int)(blockIdx.x & 7u) * a.tiles_per_xcd + (int)(blockIdx.x >> 3);
+    const int tile = lmg_xcd_tile(a.tiles_per_xcd);
     if (tile >= a.tiles) return;
     const int r0 = tile * BLOCK;
     const int r1 = min(a.n, r0 + BLOCK);
@@ -138,8 +136,8 @@ __global__ void __launch_bounds__(BLOCK) csr_sweep_kernel(SweepArgs a)
     }
 }
 
-// Final deterministic reduction of the per-tile partials: one workgroup, fixed order,
-// four independent chains per thread so the loads pipeline.
+// Final deterministic reduction of the partial sums of a residual sweep of ANY format (lmg_reduce_partials): one
+// workgroup, fixed order, four independent chains per thread so the loads pipeline.
 __global__ void __launch_bounds__(1024) reduce_partials_kernel(const double *partial, int64_t count,
                                                                double *out)
 {
@@ -224,6 +222,13 @@ int check_csr(int64_t n, int64_t nnz, const void *rp, const void *ci, const void
 
 }  // namespace
 
+int lmg_reduce_partials(const double *partials, int64_t count, double *norm2, hipStream_t st)
+{
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(1024), 0, st, partials, count, norm2);
+    LMG_CHECK_LAUNCH();
+    return LMG_OK;
+}
+
 int lmg_sweep_tune_set(int v)
 {
     if (v < 0 || v >= kNumVariants) return LMG_ERR_ARG;
@@ -247,19 +252,14 @@ int lmg_csr_residual_norm2(int64_t n, int64_t nnz, const int32_t *rp, const int3
 {
     int st = check_csr(n, nnz, rp, ci, va);
     if (st != LMG_OK) return st;
-    if (!x || !b) return LMG_ERR_ARG;
-    if ((partials == nullptr) != (norm2 == nullptr)) return LMG_ERR_ARG;
-    if (!r && !partials) return LMG_ERR_ARG;
+    if (!x || lmg_check_sweep_args(MODE_RESIDUAL, x, b, r, partials, norm2) != LMG_OK) return LMG_ERR_ARG;
     const int variant = pick_variant(n, nnz);
     SweepArgs a{(int)n, (int)nnz, rp, ci, va, x, b, r, 0.0, 0.0, partials, 0, 0};
     st = launch_sweep<MODE_RESIDUAL>(a, variant, lmg_stream(stream));
     if (st != LMG_OK) return st;
     if (partials) {
         const int rows = kVariants[variant].block;
-        const int64_t tiles = (n + rows - 1) / rows;
-        hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(1024), 0, lmg_stream(stream),
-                           partials, tiles, norm2);
-        LMG_CHECK_LAUNCH();
+        return lmg_reduce_partials(partials, (n + rows - 1) / rows, norm2, lmg_stream(stream));
     }
     return LMG_OK;
 }
@@ -269,7 +269,7 @@ int lmg_csr_jacobi(int64_t n, int64_t nnz, const int32_t *rp, const int32_t *ci,
 {
     int st = check_csr(n, nnz, rp, ci, va);
     if (st != LMG_OK) return st;
-    if (!x_in || !b || !x_out || x_in == x_out) return LMG_ERR_ARG;
+    if (!x_in || lmg_check_sweep_args(MODE_JACOBI, x_in, b, x_out, nullptr, nullptr) != LMG_OK) return LMG_ERR_ARG;
     SweepArgs a{(int)n, (int)nnz, rp, ci, va, x_in, b, x_out, omega, 0.0, nullptr, 0, 0};
     return launch_sweep<MODE_JACOBI>(a, pick_variant(n, nnz), lmg_stream(stream));
 }
@@ -279,7 +279,7 @@ int lmg_csr_spmv(int64_t n, int64_t nnz, const int32_t *rp, const int32_t *ci, c
 {
     int st = check_csr(n, nnz, rp, ci, va);
     if (st != LMG_OK) return st;
-    if (!y || (nnz > 0 && !x) || x == y) return LMG_ERR_ARG;
+    if ((nnz > 0 && !x) || lmg_check_sweep_args(MODE_SPMV, x, nullptr, y, nullptr, nullptr) != LMG_OK) return LMG_ERR_ARG;
     SweepArgs a{(int)n, (int)nnz, rp, ci, va, x, nullptr, y, alpha, beta, nullptr, 0, 0};
     return launch_sweep<MODE_SPMV>(a, pick_variant(n, nnz), lmg_stream(stream));
 }

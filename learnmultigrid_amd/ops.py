@@ -594,6 +594,11 @@ class StencilTwin:
         self._gs_ok = None
         return self
 
+    def c_args(self):
+        """The nine leading arguments that describe this operator to lmg_stencil_smooth* / lmg_stencil_gs_sweep*."""
+        hv = None if self._hot_val is None else ctypes.addressof(self._hot_val)
+        return (self.n, self.W, _p(self.pid), self.npat, _p(self.st_val), _p(self.st_mask), self.umask, self.hot, hv)
+
     @property
     def gs_ok(self):
         """Whether the wavefront Gauss-Seidel kernel may run on this operator: a supported slot set and no coupling
@@ -678,6 +683,11 @@ class ProlongTwin:
         self._hot_pval = (ctypes.c_double * 9)(*pval)
         return self
 
+    def c_args(self, e):
+        """The arguments that describe the correction P e to the lmg_stencil_smooth*_prolong / _turnaround entry points."""
+        return (self.nc, self.Wc, _p(e), _p(self.pid), self.npat, _p(self.p_val), _p(self.p_mask),
+                ctypes.addressof(self._hot_pairs), ctypes.addressof(self._hot_pval))
+
 
 class RestrictTwin:
     """3x3-window view of the row-pattern twin of a RESTRICTION between nested grids for
@@ -731,6 +741,12 @@ class RestrictTwin:
             self.hot = int(cand[0] if counts is None else max(cand, key=lambda p: counts[p]))
             self._hot_val = (ctypes.c_double * 9)(*[float(v) for v in r_val[self.hot * 9: self.hot * 9 + 9]])
         return self
+
+    def c_args(self, bc):
+        """The arguments that describe b_coarse = R r to the lmg_stencil_smooth*_restrict entry points (the turnaround
+        pass takes them without the leading nc, Wc, which it has from the prolongation)."""
+        hr = None if self._hot_val is None else ctypes.addressof(self._hot_val)
+        return (self.nc, self.Wc, _p(bc), _p(self.pid), self.npat, _p(self.r_val), _p(self.r_mask), self.hot, hr)
 
 
 class DiaTwin:
@@ -904,52 +920,34 @@ def stencil_smooth(A, x_in, b, omega, sweeps, x_out, r_out=None, prolong=None, r
         return
     if S is None:
         raise LmgError("stencil_smooth needs a grid-stencil matrix")
-    hv = None if S._hot_val is None else ctypes.addressof(S._hot_val)
+    tiled = _fused_kind(A) == "tile"
+    vecs = (int(sweeps), _p(x_in), _p(b), float(omega), _p(x_out))
     if restrict is not None:
         R, bc = restrict
         T = R.restrict
         _vec_ok(bc)
         if T is None or r_out is not None or prolong is not None or T.n != S.n or T.W != S.W or bc.numel() != T.nc:
             raise LmgError("stencil_smooth: this restriction cannot be fused into the pass")
-        hr = None if T._hot_val is None else ctypes.addressof(T._hot_val)
-        if _fused_kind(A) == "tile" and not (S.n >= REG_RESTRICT_MIN_ROWS and _lib.lib().lmg_stencil_smooth_prolong_supported(S.umask)):
-            check(_lib.lib().lmg_stencil_smooth_tiled_restrict(S.n, S.W, _p(S.pid), S.npat, _p(S.st_val), _p(S.st_mask), S.umask,
-                                                               S.hot, hv, int(sweeps), _p(x_in), _p(b), float(omega), _p(x_out),
-                                                               T.nc, T.Wc, _p(bc), _p(T.pid), T.npat, _p(T.r_val), _p(T.r_mask),
-                                                               T.hot, hr, _s(S.pid)), "lmg_stencil_smooth_tiled_restrict")
-            return
-        check(_lib.lib().lmg_stencil_smooth_restrict(S.n, S.W, _p(S.pid), S.npat, _p(S.st_val), _p(S.st_mask), S.umask, S.hot,
-                                                     hv, int(sweeps), _p(x_in), _p(b), float(omega), _p(x_out), T.nc, T.Wc,
-                                                     _p(bc), _p(T.pid), T.npat, _p(T.r_val), _p(T.r_mask), T.hot, hr, _s(S.pid)),
-              "lmg_stencil_smooth_restrict")
-        return
-    if prolong is not None:
+        if tiled and not (S.n >= REG_RESTRICT_MIN_ROWS and _lib.lib().lmg_stencil_smooth_prolong_supported(S.umask)):
+            name = "lmg_stencil_smooth_tiled_restrict"
+        else:
+            name = "lmg_stencil_smooth_restrict"
+        tail = T.c_args(bc)
+    elif prolong is not None:
         P, e = prolong
         T = P.prolong
         _vec_ok(e)
         if T is None or r_out is not None or x_in is None or T.n != S.n or T.W != S.W or e.numel() != T.nc:
             raise LmgError("stencil_smooth: this prolongation cannot be fused into the pass")
-        if _fused_kind(A) == "tile" and not (S.n >= REG_PROLONG_MIN_ROWS and _lib.lib().lmg_stencil_smooth_prolong_supported(S.umask)):
-            check(_lib.lib().lmg_stencil_smooth_tiled_prolong(S.n, S.W, _p(S.pid), S.npat, _p(S.st_val), _p(S.st_mask), S.umask,
-                                                              S.hot, hv, int(sweeps), _p(x_in), _p(b), float(omega), _p(x_out),
-                                                              T.nc, T.Wc, _p(e), _p(T.pid), T.npat, _p(T.p_val), _p(T.p_mask),
-                                                              ctypes.addressof(T._hot_pairs), ctypes.addressof(T._hot_pval),
-                                                              _s(S.pid)), "lmg_stencil_smooth_tiled_prolong")
-            return
-        check(_lib.lib().lmg_stencil_smooth_prolong(S.n, S.W, _p(S.pid), S.npat, _p(S.st_val), _p(S.st_mask), S.umask, S.hot,
-                                                    hv, int(sweeps), _p(x_in), _p(b), float(omega), _p(x_out), T.nc, T.Wc,
-                                                    _p(e), _p(T.pid), T.npat, _p(T.p_val), _p(T.p_mask),
-                                                    ctypes.addressof(T._hot_pairs), ctypes.addressof(T._hot_pval), _s(S.pid)),
-              "lmg_stencil_smooth_prolong")
-        return
-    if _fused_kind(A) == "tile":
-        check(_lib.lib().lmg_stencil_smooth_tiled(S.n, S.W, _p(S.pid), S.npat, _p(S.st_val), _p(S.st_mask), S.umask, S.hot,
-                                                  hv, int(sweeps), _p(x_in), _p(b), float(omega), _p(x_out), _p(r_out), _s(S.pid)),
-              "lmg_stencil_smooth_tiled")
-        return
-    check(_lib.lib().lmg_stencil_smooth(S.n, S.W, _p(S.pid), S.npat, _p(S.st_val), _p(S.st_mask), S.umask, S.hot, hv,
-                                        int(sweeps), _p(x_in), _p(b), float(omega), _p(x_out), _p(r_out), _s(S.pid)),
-          "lmg_stencil_smooth")
+        if tiled and not (S.n >= REG_PROLONG_MIN_ROWS and _lib.lib().lmg_stencil_smooth_prolong_supported(S.umask)):
+            name = "lmg_stencil_smooth_tiled_prolong"
+        else:
+            name = "lmg_stencil_smooth_prolong"
+        tail = T.c_args(e)
+    else:
+        name = "lmg_stencil_smooth_tiled" if tiled else "lmg_stencil_smooth"
+        tail = (_p(r_out),)
+    check(getattr(_lib.lib(), name)(*S.c_args(), *vecs, *tail, _s(S.pid)), name)
 
 
 # The transfers are folded into the fused passes only on levels that do not fit the Infinity Cache: what is saved is
@@ -1062,13 +1060,9 @@ def stencil_smooth_turnaround(A, x_in, b, omega, sweeps_post, sweeps_pre, x_out,
     if (S is None or TP is None or TR is None or x_in is None or _fused_kind(A) != "tile" or TP.n != S.n or TP.W != S.W
             or TR.n != S.n or TR.W != S.W or e.numel() != TP.nc or bc.numel() != TR.nc):
         raise LmgError("stencil_smooth_turnaround: this level and its transfers cannot run the turnaround pass")
-    hv = None if S._hot_val is None else ctypes.addressof(S._hot_val)
-    hr = None if TR._hot_val is None else ctypes.addressof(TR._hot_val)
     check(_lib.lib().lmg_stencil_smooth_tiled_turnaround(
-        S.n, S.W, _p(S.pid), S.npat, _p(S.st_val), _p(S.st_mask), S.umask, S.hot, hv, int(sweeps_post), int(sweeps_pre),
-        _p(x_in), _p(b), float(omega), _p(x_out), TP.nc, TP.Wc, _p(e), _p(TP.pid), TP.npat, _p(TP.p_val), _p(TP.p_mask),
-        ctypes.addressof(TP._hot_pairs), ctypes.addressof(TP._hot_pval), _p(bc), _p(TR.pid), TR.npat, _p(TR.r_val),
-        _p(TR.r_mask), TR.hot, hr, _s(S.pid)), "lmg_stencil_smooth_tiled_turnaround")
+        *S.c_args(), int(sweeps_post), int(sweeps_pre), _p(x_in), _p(b), float(omega), _p(x_out), *TP.c_args(e),
+        *TR.c_args(bc)[2:], _s(S.pid)), "lmg_stencil_smooth_tiled_turnaround")
 
 
 def _use_stencil(A, *vecs):
@@ -1132,68 +1126,53 @@ def tune_get(key):
 
 
 # ---- sweeps ------------------------------------------------------------------------
+_MODE_NAMES = ("residual", "jacobi", "spmv")
+
+
+def _sweep(mode, A, x, b, out, alpha, beta, partials, norm2):
+    """One sweep (0 residual, 1 Jacobi, 2 SpMV) on the best twin A has: grid stencil -> row patterns -> sliced ELL ->
+    packed CSR -> plain CSR."""
+    what = "(%s)" % _MODE_NAMES[mode]
+    if _use_stencil(A, x, b, out):
+        check(_stencil(mode, A.stencil, x, b, out, alpha, beta, partials, norm2), "lmg_stencil_sweep" + what)
+        return
+    if _PACKED_ENABLED and A.patterns is not None:
+        check(_rpat(mode, A.patterns, x, b, out, alpha, beta, partials, norm2), "lmg_rpat_sweep" + what)
+        return
+    if _PACKED_ENABLED and A.sell is not None:
+        check(_sell(mode, A.sell, x, b, out, alpha, beta, partials, norm2), "lmg_sell_sweep" + what)
+        return
+    if _PACKED_ENABLED and A.packed is not None:
+        rc = _pcsr(mode, A.packed, x, b, out, alpha, beta, partials, norm2)
+        if rc != -4:                                   # LMG_ERR_CAPACITY: tile too large for LDS
+            check(rc, "lmg_pcsr_sweep" + what)
+            return
+    L, csr = _lib.lib(), (A.shape[0], A.nnz, _p(A.rowptr), _p(A.colidx), _p(A.vals))
+    if mode == 0:
+        check(L.lmg_csr_residual_norm2(*csr, _p(x), _p(b), _p(out), _p(partials), _p(norm2), _s(A.rowptr)),
+              "lmg_csr_residual_norm2")
+    elif mode == 1:
+        check(L.lmg_csr_jacobi(*csr, _p(x), _p(b), float(alpha), _p(out), _s(A.rowptr)), "lmg_csr_jacobi")
+    else:
+        check(L.lmg_csr_spmv(*csr, _p(x), _p(out), float(alpha), float(beta), _s(A.rowptr)), "lmg_csr_spmv")
+
+
 def csr_residual_norm2(A, x, b, r, partials, norm2):
     """r = b - A x (r may be None), norm2[0] = sum r_i^2 (partials/norm2 may both be None)."""
     _vec_ok(x, b, r, partials, norm2)
-    if _use_stencil(A, x, b, r):
-        check(_stencil(0, A.stencil, x, b, r, 0.0, 0.0, partials, norm2), "lmg_stencil_sweep(residual)")
-        return
-    if _PACKED_ENABLED and A.patterns is not None:
-        check(_rpat(0, A.patterns, x, b, r, 0.0, 0.0, partials, norm2), "lmg_rpat_sweep(residual)")
-        return
-    if _PACKED_ENABLED and A.sell is not None:
-        check(_sell(0, A.sell, x, b, r, 0.0, 0.0, partials, norm2), "lmg_sell_sweep(residual)")
-        return
-    if _PACKED_ENABLED and A.packed is not None:
-        rc = _pcsr(0, A.packed, x, b, r, 0.0, 0.0, partials, norm2)
-        if rc != -4:                                   # LMG_ERR_CAPACITY: tile too large for LDS
-            check(rc, "lmg_pcsr_sweep(residual)")
-            return
-    check(_lib.lib().lmg_csr_residual_norm2(A.shape[0], A.nnz, _p(A.rowptr), _p(A.colidx), _p(A.vals),
-                                            _p(x), _p(b), _p(r), _p(partials), _p(norm2), _s(A.rowptr)),
-          "lmg_csr_residual_norm2")
+    _sweep(0, A, x, b, r, 0.0, 0.0, partials, norm2)
 
 
 def csr_jacobi(A, x_in, b, omega, x_out):
     _vec_ok(x_in, b, x_out)
-    if _use_stencil(A, x_in, b, x_out):
-        check(_stencil(1, A.stencil, x_in, b, x_out, omega, 0.0, None, None), "lmg_stencil_sweep(jacobi)")
-        return
-    if _PACKED_ENABLED and A.patterns is not None:
-        check(_rpat(1, A.patterns, x_in, b, x_out, omega, 0.0, None, None), "lmg_rpat_sweep(jacobi)")
-        return
-    if _PACKED_ENABLED and A.sell is not None:
-        check(_sell(1, A.sell, x_in, b, x_out, omega, 0.0, None, None), "lmg_sell_sweep(jacobi)")
-        return
-    if _PACKED_ENABLED and A.packed is not None:
-        rc = _pcsr(1, A.packed, x_in, b, x_out, omega, 0.0, None, None)
-        if rc != -4:
-            check(rc, "lmg_pcsr_sweep(jacobi)")
-            return
-    check(_lib.lib().lmg_csr_jacobi(A.shape[0], A.nnz, _p(A.rowptr), _p(A.colidx), _p(A.vals),
-                                    _p(x_in), _p(b), float(omega), _p(x_out), _s(A.rowptr)), "lmg_csr_jacobi")
+    _sweep(1, A, x_in, b, x_out, omega, 0.0, None, None)
 
 
 def csr_spmv(A, x, y, alpha=1.0, beta=0.0):
     _vec_ok(x, y)
     if x.numel() != A.shape[1] or y.numel() != A.shape[0]:
         raise ValueError("spmv shape mismatch: A %s, x %d, y %d" % (A.shape, x.numel(), y.numel()))
-    if _use_stencil(A, x, y):
-        check(_stencil(2, A.stencil, x, None, y, alpha, beta, None, None), "lmg_stencil_sweep(spmv)")
-        return
-    if _PACKED_ENABLED and A.patterns is not None:
-        check(_rpat(2, A.patterns, x, None, y, alpha, beta, None, None), "lmg_rpat_sweep(spmv)")
-        return
-    if _PACKED_ENABLED and A.sell is not None:
-        check(_sell(2, A.sell, x, None, y, alpha, beta, None, None), "lmg_sell_sweep(spmv)")
-        return
-    if _PACKED_ENABLED and A.packed is not None:
-        rc = _pcsr(2, A.packed, x, None, y, alpha, beta, None, None)
-        if rc != -4:
-            check(rc, "lmg_pcsr_sweep(spmv)")
-            return
-    check(_lib.lib().lmg_csr_spmv(A.shape[0], A.nnz, _p(A.rowptr), _p(A.colidx), _p(A.vals),
-                                  _p(x), _p(y), float(alpha), float(beta), _s(A.rowptr)), "lmg_csr_spmv")
+    _sweep(2, A, x, None, y, alpha, beta, None, None)
 
 
 # ---- Gauss-Seidel ---------------------------------------------------------------------
@@ -1332,10 +1311,8 @@ def stencil_gs(A, x, b, sweeps=1, direction="forward"):
         S._gs_work = torch.zeros((nb + 7) // 8, dtype=torch.int64, device=x.device)
     if sweeps <= 0:
         return
-    hv = None if S._hot_val is None else ctypes.addressof(S._hot_val)
     name = "lmg_stencil_gs_sweep_backward" if bwd else "lmg_stencil_gs_sweep"
-    check(getattr(_lib.lib(), name)(S.n, S.W, _p(S.pid), S.npat, _p(S.st_val), _p(S.st_mask), S.umask, S.hot, hv,
-                                    _p(x), _p(b), _p(S._gs_work), int(sweeps), _s(S.pid)), name)
+    check(getattr(_lib.lib(), name)(*S.c_args(), _p(x), _p(b), _p(S._gs_work), int(sweeps), _s(S.pid)), name)
 
 
 def stencil_gs_check(A):
