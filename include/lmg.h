@@ -46,13 +46,47 @@ const char *lmg_status_string(int status);
 /* Number of visible HIP devices, or a negative lmg_status. */
 int lmg_device_count(void);
 
-/* Runtime tuning knobs (kernel variant selection; used by bench.py for A/B runs).
- *   key "pcsr_ju"       : row entries per step of the packed sweeps (0 = auto, 1, 3, 5).
- *   key "sweep_variant" : tile geometry of the plain-CSR sweep kernels, 0..6 (0 = default: chosen
- *                         per launch from the average row length).
- *   keys "rpat_variant", "rpat_nt_rows", "stencil_nt_rows", "stencil_wgs_per_cu", "fused_seg_lines",
- *        "fused_pf", "gs_single_max": geometry / cache-policy knobs of the twin kernels (parity tests force
- *        the instantiations a launcher would only pick on very large operators).       */
+/* Runtime tuning knobs: kernel variant selection and launch geometry, for A/B runs (bench.py, tools/) and for the
+ * parity tests, which force the instantiations a launcher would only pick on very large operators.  Both calls
+ * answer LMG_ERR_ARG to a key that is not listed here, lmg_tune_set also to a value it does not accept (and then
+ * changes nothing); lmg_tune_get returns the value.  [default]
+ *   key                        accepts        meaning
+ *   "sweep_variant"            0..6      [0]  tile geometry of the plain-CSR sweeps; 0 = from the average row length
+ *   "pcsr_ju"                  0 1 3 5 101 102  [0]  row entries per step of the packed sweeps; 0 = from the average
+ *                                             row length; 101, 102 = the one-/two-tile probes of the 16-bit/8-bit encoding
+ *   "rpat_variant"             0..4      [0]  geometry of the row-pattern sweeps; 0 = from the longest pattern
+ *                                             (a value >= 1000 sets "rpat_nt_rows" instead: bench.py's spelling)
+ *   "rpat_nt_rows"             >= 1      [8388608]  rows from which the row-pattern sweeps' streams bypass the caches
+ *   "stencil_nt_rows"          >= 1      [8388608]  the same for the stencil sweeps
+ *   "stencil_wgs_per_cu"       0..8      [0]  workgroups per CU of the stencil sweeps; 0 = occupancy query
+ *   "fused_seg_lines"          >= 0      [0]  lines per segment of the register-fused passes; 0 = chosen per launch
+ *   "fused_seg_min_lines"      >= 0      [0]  ... applied to grids of at least this many lines
+ *   "fused_seg_max_lines"      >= 0      [2147483647]  ... and at most this many
+ *   "fused_seg_lines_prol"     >= 0      [0]  lines per segment of the pass with the correction folded in; 0 = as the others
+ *   "fused_seg_lines_rest"     >= 0      [0]  ... with the restriction folded in
+ *   "fused_pf"                 0 2       [0]  kept for old scripts: stored, read by nothing
+ *   "fused_want_waves"         >= 1      [5120]  waves a register-fused launch aims at when it cuts segments
+ *   "fused_want_waves_rest3"   >= 1      [2700]  ... for three sweeps with a transfer folded in
+ *   "fused_floor_halos"        >= 1      [4]  shortest segment, in halos
+ *   "fused_balance"            0 1       [1]  shorter segments for the items that run the slower bodies
+ *   "fused_slow_pct"           10..100   [55] their steps, per cent of a normal item's
+ *   "fused_fast"               0 1       [1]  0: every wave runs the general body
+ *   "tile_rows"                0 16 32   [16] lines per tile of the tiled passes on grids below "tile_big_lines"; 0 = 32
+ *   "tile_rows_big"            0 16 32   [0]  ... on grids from "tile_big_lines" lines
+ *   "tile_big_lines"           >= 0      [600]
+ *   "tile_prol_wide_lines"     >= 0      [768]  lines from which the correcting tiled pass runs 8 waves of four lines
+ *   "tile_prol_wide_lines_hx"  >= 0      [1073741824]  the same for its hot-transfer kernels
+ *   "tile_turnaround_rows"     0 32 64   [0]  lines per tile of the turnaround pass; 0 = 64 from "tile_big_lines" lines, else 32
+ *   "tile_hot_transfers"       0 1       [1]  passes with a transfer folded in run the hot-transfer kernels
+ *   "dia_rows"                 0 32 64   [0]  lines per tile of lmg_dia_smooth; 0 = 32
+ *   "sell_nt"                  -1..1     [-1] nontemporal streams of the sliced-ELL sweeps: -1 by size, 0 never, 1 always
+ *   "sell_ju"                  0 5 7 8 10  [0]  row entries in flight there; 0 = from the longest row
+ *   "gsw_max_sweeps"           1..4      [4]  Gauss-Seidel sweeps pipelined in one launch
+ *   "gsw_multi_max_rows"       >= 0      [8000000]  ... on levels of at most this many rows (register bands)
+ *   "gsw_lds"                  -1..1     [-1] bands staged through LDS: -1 / 1 wherever possible, 0 never
+ *   "gsw_lds9"                 0 1       [1]  ... for 9-point operators too
+ *   "gsw_lds_multi"            0 1       [1]  ... with the sweeps of a step pipelined in one launch
+ *   "gs_single_max"            >= 1      [2048]  widest row set the one-workgroup Gauss-Seidel executor takes */
 int lmg_tune_set(const char *key, int value);
 int lmg_tune_get(const char *key);
 

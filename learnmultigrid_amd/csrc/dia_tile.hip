@@ -14,7 +14,6 @@
 // One pass over the level reads ~1.5 x (8 slots + 16) B/row instead of (S + 1) x 74 B/row of the packed-CSR sweeps.
 // The arithmetic per row and sweep is the sequence of the CSR kernels (entries in ascending column order = slot
 // order, separate multiply and add, omega * (rdiag * r)): bit-identical to them and to the CPU oracle.
-#include <string.h>
 #include "lmg_common.hpp"
 
 namespace {
@@ -247,20 +246,10 @@ int launch1(DArgs a, int sweeps, bool resid, bool zero, hipStream_t st)
 
 }  // namespace
 
-int lmg_dia_tune_set(const char *key, int v)
-{
-    if (strcmp(key, "dia_rows") == 0) {
-        if (v != 0 && v != 32 && v != 64) return LMG_ERR_ARG;
-        g_dia_rows = v;
-        return LMG_OK;
-    }
-    return LMG_ERR_ARG;
-}
-int lmg_dia_tune_get(const char *key)
-{
-    if (strcmp(key, "dia_rows") == 0) return g_dia_rows;
-    return LMG_ERR_ARG;
-}
+constexpr LmgTuneKey lmg_tune_dia[] = {
+    lmg_tune_list("dia_rows", &g_dia_rows, 0, 32, 64),
+    kLmgTuneEnd,
+};
 
 extern "C" {
 

@@ -233,13 +233,10 @@ void transpose_pattern(int64_t n, const int32_t *Ap, const int32_t *Aj, std::vec
 
 }  // namespace
 
-int lmg_gs_tune_set(int v)
-{
-    if (v < 1) return LMG_ERR_ARG;
-    g_gs_single_max = v;
-    return LMG_OK;
-}
-int lmg_gs_tune_get(void) { return g_gs_single_max; }
+constexpr LmgTuneKey lmg_tune_gs[] = {
+    lmg_tune_range("gs_single_max", &g_gs_single_max, 1),
+    kLmgTuneEnd,
+};
 
 extern "C" {
 

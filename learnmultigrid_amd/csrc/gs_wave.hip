@@ -25,7 +25,6 @@
 // the CPU oracle.  4097^2: one sweep ~1.5 ms instead of 43.7 ms (8191 launches); 513^2 ~0.25 ms instead of 2.5.
 // The BACKWARD sweep (pyamg's sweep='backward': rows n-1 .. 0) is the same kernels in mirrored coordinates (BWD, see pair_off_d).
 #include <math.h>
-#include <string.h>
 #include "lmg_common.hpp"
 
 namespace {
@@ -758,44 +757,14 @@ int g_gs_lds = -1;                          // bands staged through LDS (gs_band
 
 }  // namespace
 
-int lmg_gsw_tune_set(const char *key, int v)
-{
-    if (strcmp(key, "gsw_max_sweeps") == 0) {
-        if (v < 1 || v > kMaxSweeps) return LMG_ERR_ARG;
-        g_gs_max_sweeps = v;
-        return LMG_OK;
-    }
-    if (strcmp(key, "gsw_multi_max_rows") == 0) {
-        if (v < 0) return LMG_ERR_ARG;
-        g_gs_multi_max_rows = v;
-        return LMG_OK;
-    }
-    if (strcmp(key, "gsw_lds") == 0) {
-        if (v < -1 || v > 1) return LMG_ERR_ARG;
-        g_gs_lds = v;
-        return LMG_OK;
-    }
-    if (strcmp(key, "gsw_lds9") == 0) {
-        if (v < 0 || v > 1) return LMG_ERR_ARG;
-        g_gs_lds9 = v;
-        return LMG_OK;
-    }
-    if (strcmp(key, "gsw_lds_multi") == 0) {
-        if (v < 0 || v > 1) return LMG_ERR_ARG;
-        g_gs_lds_multi = v;
-        return LMG_OK;
-    }
-    return LMG_ERR_ARG;
-}
-int lmg_gsw_tune_get(const char *key)
-{
-    if (strcmp(key, "gsw_max_sweeps") == 0) return g_gs_max_sweeps;
-    if (strcmp(key, "gsw_multi_max_rows") == 0) return g_gs_multi_max_rows;
-    if (strcmp(key, "gsw_lds") == 0) return g_gs_lds;
-    if (strcmp(key, "gsw_lds_multi") == 0) return g_gs_lds_multi;
-    if (strcmp(key, "gsw_lds9") == 0) return g_gs_lds9;
-    return LMG_ERR_ARG;
-}
+constexpr LmgTuneKey lmg_tune_gsw[] = {
+    lmg_tune_range("gsw_max_sweeps", &g_gs_max_sweeps, 1, kMaxSweeps),
+    lmg_tune_range("gsw_multi_max_rows", &g_gs_multi_max_rows, 0),
+    lmg_tune_range("gsw_lds", &g_gs_lds, -1, 1),
+    lmg_tune_list("gsw_lds9", &g_gs_lds9, 0, 1),
+    lmg_tune_list("gsw_lds_multi", &g_gs_lds_multi, 0, 1),
+    kLmgTuneEnd,
+};
 
 extern "C" {
 
@@ -840,7 +809,7 @@ int gs_sweep(int64_t n, int32_t line_stride, const uint8_t *pid, int32_t npat, c
     a.hot = -1;
     for (int k = 0; k < 9; ++k) a.hot_val[k] = 0.0;
     a.hot_rcp = 0.0;
-    if (hot_pattern >= 0 && hot_pattern < npat && h_hot_val && h_hot_val[4] != 0.0) {
+    if (lmg_hot_usable(hot_pattern, npat, h_hot_val)) {
         a.hot = hot_pattern;
         for (int k = 0; k < 9; ++k) a.hot_val[k] = h_hot_val[BWD ? 8 - k : k];     // (BWD: mirrored slots, see load_patterns)
         int e = 0;

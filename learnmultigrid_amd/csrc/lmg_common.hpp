@@ -1,10 +1,14 @@
 // Shared helpers of the gfx950 kernels (wave64, 256 CUs in 8 XCDs): everything that more than one kernel file
 // needs has its single definition here -- the sweep modes and their argument rules, XCD-aware tile ownership and the
 // persistent grid that goes with it, the fixed-order sums, the DPP lane shifts, and the 3x3 stencil view (slot masks,
-// pattern-table limit).
+// pattern-table limit).  The host half at the end is what sits between the C ABI and hipLaunchKernelGGL in more than
+// one file: the rows of the tune-key tables, and the argument checks and sweep-count dispatch of the fused passes.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <stdint.h>
+#include <string.h>
+#include <type_traits>
 #include "lmg.h"
 
 #define LMG_WAVE 64
@@ -148,3 +152,198 @@ constexpr unsigned kMaskOffLine = kMaskUpper | kMaskLower;      // 0x1C7: any sl
 // The loops that stage a pattern table (st_val, st_mask) into LDS stay in the kernels: handed to a helper, the table
 // pointers are read from the kernel arguments at the call instead of inside the guarded loops, which reorders the
 // scalar loads of every kernel of gs_wave.hip, stencil_tile.hip and stencil_fused.hip.
+
+// =====================================================================================================================
+// Host half
+// =====================================================================================================================
+
+// ---- tune keys (lmg_tune_set / lmg_tune_get, vec.hip) ---------------------------------------------------------------
+// A file that owns knobs lists them once, next to the globals: the key, the int it sets, and the values it accepts --
+// an inclusive range, or a short list of the only ones.
+struct LmgTuneKey {
+    const char *key;
+    int *value;
+    int lo, hi;             // accepted: lo .. hi, both included ...
+    int nlist, list[6];     // ... or, with nlist > 0, exactly list[0 .. nlist)
+};
+constexpr LmgTuneKey lmg_tune_range(const char *key, int *value, int lo, int hi = INT_MAX)
+{
+    return {key, value, lo, hi, 0, {}};
+}
+template <typename... V>
+constexpr LmgTuneKey lmg_tune_list(const char *key, int *value, V... v)
+{
+    return {key, value, 0, 0, (int)sizeof...(V), {v...}};
+}
+constexpr LmgTuneKey kLmgTuneEnd = {nullptr, nullptr, 0, 0, 0, {}};      // closes a table
+// the tables, one per owning file (constant data: nothing registers itself when the library is loaded)
+extern const LmgTuneKey lmg_tune_sweep[], lmg_tune_pcsr[], lmg_tune_rpat[], lmg_tune_stencil[], lmg_tune_fused[],
+    lmg_tune_tile[], lmg_tune_dia[], lmg_tune_sell[], lmg_tune_gsw[], lmg_tune_gs[];
+
+static inline const LmgTuneKey *lmg_tune_find(const LmgTuneKey *table, const char *key)
+{
+    for (; table->key; ++table)
+        if (strcmp(table->key, key) == 0) return table;
+    return nullptr;
+}
+static inline bool lmg_tune_accepts(const LmgTuneKey &k, int v)
+{
+    if (k.nlist == 0) return v >= k.lo && v <= k.hi;
+    for (int i = 0; i < k.nlist; ++i)
+        if (k.list[i] == v) return true;
+    return false;
+}
+
+// ---- runtime sweep count / flag -> template argument ----------------------------------------------------------------
+// f(std::integral_constant<int, S>) for S = sweeps in LO .. HI; any other count takes HI, like the `default:` of the
+// switches this replaces (callers check the range first).  LMG_CT(s) reads the constant back inside the lambda.
+template <int LO, int HI, typename F>
+int lmg_with_sweeps(int sweeps, F &&f)
+{
+    if constexpr (LO < HI) {
+        if (sweeps == LO) return f(std::integral_constant<int, LO>{});
+        return lmg_with_sweeps<LO + 1, HI>(sweeps, f);
+    } else {
+        return f(std::integral_constant<int, HI>{});
+    }
+}
+template <typename F>
+int lmg_with_flag(bool flag, F &&f)
+{
+    return flag ? f(std::true_type{}) : f(std::false_type{});
+}
+#define LMG_CT(c) decltype(c)::value
+
+// ---- argument checks of the fused smoothing passes ------------------------------------------------------------------
+// stencil_fused.hip (iterates in registers, MArgs) and stencil_tile.hip (iterates in LDS, TArgs) take the same
+// arguments under the same rules; their argument structs name the shared fields alike, and each says in constexpr
+// members where its rules differ:
+//     kRowLimit            first row count refused
+//     kOneRowIsCapacity    a single row answers LMG_ERR_CAPACITY
+//     kProlMinCoarse, kProlStrideCovers, kProlChecksPairs      (prolongation, below)
+//     kRestCoarseLimit                                         (restriction, below)
+
+// a hot pattern the host can hand to a kernel in scalar registers: in the table, with values, and a diagonal to divide by
+static inline bool lmg_hot_usable(int32_t hot_pattern, int32_t npat, const double *h_hot_val)
+{
+    return hot_pattern >= 0 && hot_pattern < npat && h_hot_val && h_hot_val[4] != 0.0;
+}
+
+// The operator, the vectors and the sweep count.  Returns 1 with everything in `a` set but the fields only one of the
+// structs has (no transfer folded in), else the status to hand back: LMG_OK where there is nothing to do.
+template <typename A>
+int lmg_smooth_fill(A &a, int64_t n, int32_t line_stride, const uint8_t *pid, int32_t npat, const double *st_val,
+                    const int32_t *st_mask, uint32_t union_mask, int32_t hot_pattern, const double *h_hot_val, int sweeps,
+                    const double *x_in, const double *b, double omega, double *x_out, double *r_out)
+{
+    if (n < 0 || n >= A::kRowLimit || npat < 1 || npat > kMaxPat || (union_mask & ~kMask9)) return LMG_ERR_ARG;
+    if (sweeps < 1 || sweeps > 3) return LMG_ERR_ARG;
+    if (n == 0) return LMG_OK;
+    if (A::kOneRowIsCapacity && n < 2) return LMG_ERR_CAPACITY;
+    if (!pid || !st_val || !st_mask || !b || !x_out || x_in == x_out || r_out == x_out || (r_out && r_out == x_in))
+        return LMG_ERR_ARG;
+    if (line_stride < 3 || line_stride > n) return LMG_ERR_ARG;
+    a.n = (int)n;
+    a.W = line_stride;
+    a.lines = (int)((n + line_stride - 1) / line_stride);
+    a.npat = npat;
+    a.pid = pid;
+    a.st_val = st_val;
+    a.st_mask = st_mask;
+    a.x = x_in;
+    a.b = b;
+    a.out = x_out;
+    a.r = r_out;
+    a.omega = omega;
+    const bool hot = lmg_hot_usable(hot_pattern, npat, h_hot_val);
+    a.hot = hot ? hot_pattern : -1;
+    for (int k = 0; k < 9; ++k) a.hot_val[k] = hot ? h_hot_val[k] : 0.0;
+    a.hot_rdiag = hot ? 1.0 / h_hot_val[4] : 0.0;
+    a.ec = nullptr;
+    a.nc = a.Wc = 0;
+    a.ppid = nullptr;
+    a.pp_val = nullptr;
+    a.pp_mask = nullptr;
+    a.pp_npat = 0;
+    a.bc = nullptr;
+    a.rpid = nullptr;
+    a.rp_val = nullptr;
+    a.rp_mask = nullptr;
+    a.rp_npat = 0;
+    a.phot[0] = a.phot[1] = a.rhot = -1;
+    for (int k = 0; k < 9; ++k) a.phv[k] = a.rhv[k] = 0.0;
+    return 1;
+}
+
+// The prolongation folded into a pass (x_in + P e_coarse).  Checked before the operator; set after it.
+//     kProlMinCoarse       fewest coarse rows: 1 in the register pass, 2 in the tiled one (as found)
+//     kProlStrideCovers    the coarse line stride must cover half the fine one: the register pass finds the 2 x 2 window
+//                          of row (y, x) at ((y >> 1), (x >> 1)) from its lane number; not asked by the tiled pass (as found)
+//     kProlChecksPairs     hot pair ids outside P's table are dropped (-1): tiled pass only; both kernels just compare
+//                          the ids with the ones they load (as found)
+template <typename A>
+int lmg_prol_check(int32_t line_stride, const double *x_in, const double *x_out, int64_t n_coarse, int32_t coarse_stride,
+                   const double *e_coarse, const uint8_t *p_pid, int32_t p_npat, const double *p_val, const int32_t *p_mask)
+{
+    if (!x_in || !e_coarse || !p_pid || !p_val || !p_mask || p_npat < 1 || p_npat > kMaxPat) return LMG_ERR_ARG;
+    if (n_coarse < A::kProlMinCoarse || n_coarse >= (1ll << 31) || coarse_stride < 1 || coarse_stride > n_coarse)
+        return LMG_ERR_ARG;
+    if (e_coarse == x_out) return LMG_ERR_ARG;
+    if (A::kProlStrideCovers && (int64_t)coarse_stride < ((int64_t)line_stride + 1) / 2) return LMG_ERR_ARG;
+    return LMG_OK;
+}
+template <typename A>
+void lmg_prol_set(A &a, int64_t n_coarse, int32_t coarse_stride, const double *e_coarse, const uint8_t *p_pid, int32_t p_npat,
+                  const double *p_val, const int32_t *p_mask, const int32_t *h_hot_pairs, const double *h_hot_pval)
+{
+    a.ec = e_coarse;
+    a.nc = (int)n_coarse;
+    a.Wc = coarse_stride;
+    a.ppid = p_pid;
+    a.pp_val = p_val;
+    a.pp_mask = p_mask;
+    a.pp_npat = p_npat;
+    if (h_hot_pairs && h_hot_pval) {
+        for (int k = 0; k < 2; ++k) {
+            const int pair = h_hot_pairs[k];
+            const bool ok = !A::kProlChecksPairs || (pair >= 0 && (pair & 0xff) < p_npat && (pair >> 8) < p_npat);
+            a.phot[k] = ok ? pair : -1;
+        }
+        for (int k = 0; k < 9; ++k) a.phv[k] = h_hot_pval[k];
+    }
+}
+
+// The restriction folded into a pass (b_coarse = R (b - A x_out)).  Checked before the operator; set after it.
+//     kRestCoarseLimit     first coarse row count refused: 2^28 in the register pass, 2^31 in the tiled one (as found)
+template <typename A>
+int lmg_rest_check(int64_t n, int32_t line_stride, const double *x_in, const double *b, const double *x_out, int64_t n_coarse,
+                   int32_t coarse_stride, const double *b_coarse, const uint8_t *r_pid, int32_t r_npat, const double *r_val,
+                   const int32_t *r_mask)
+{
+    if (!b_coarse || !r_pid || !r_val || !r_mask || r_npat < 1 || r_npat > kMaxPat) return LMG_ERR_ARG;
+    if (n_coarse < 1 || n_coarse >= A::kRestCoarseLimit || coarse_stride < 1 || coarse_stride > n_coarse) return LMG_ERR_ARG;
+    if (b_coarse == x_in || b_coarse == x_out || b_coarse == b) return LMG_ERR_ARG;
+    // row (Y, X) of R sits on the fine node (2 Y, 2 X): every such node of the fine grid must have its coarse row
+    // -- and nothing else: the pass only writes b_coarse under those nodes, a larger coarse grid would keep stale rows
+    const int64_t lines = n > 0 ? (n + line_stride - 1) / line_stride : 0;
+    if ((int64_t)coarse_stride != ((int64_t)line_stride + 1) / 2 || (n % line_stride) != 0 ||
+        n_coarse != ((lines + 1) / 2) * coarse_stride)
+        return LMG_ERR_ARG;
+    return LMG_OK;
+}
+template <typename A>
+void lmg_rest_set(A &a, int64_t n_coarse, int32_t coarse_stride, double *b_coarse, const uint8_t *r_pid, int32_t r_npat,
+                  const double *r_val, const int32_t *r_mask, int32_t hot_r, const double *h_hot_rval)
+{
+    a.bc = b_coarse;
+    a.nc = (int)n_coarse;
+    a.Wc = coarse_stride;
+    a.rpid = r_pid;
+    a.rp_val = r_val;
+    a.rp_mask = r_mask;
+    a.rp_npat = r_npat;
+    if (hot_r >= 0 && hot_r < r_npat && h_hot_rval) {
+        a.rhot = hot_r;
+        for (int k = 0; k < 9; ++k) a.rhv[k] = h_hot_rval[k];
+    }
+}

@@ -348,13 +348,10 @@ int dispatch(PArgs a, int colmode, int valmode, hipStream_t st)
 
 }  // namespace
 
-int lmg_pcsr_tune_set(int ju)
-{
-    if (ju != 0 && ju != 1 && ju != 3 && ju != 5 && ju != 101 && ju != 102) return LMG_ERR_ARG;
-    g_pcsr_ju = ju;
-    return LMG_OK;
-}
-int lmg_pcsr_tune_get(void) { return g_pcsr_ju; }
+constexpr LmgTuneKey lmg_tune_pcsr[] = {
+    lmg_tune_list("pcsr_ju", &g_pcsr_ju, 0, 1, 3, 5, 101, 102),
+    kLmgTuneEnd,
+};
 
 extern "C" {
 

@@ -16,7 +16,6 @@
 // a few per cent for the near-uniform rows this format is used for.
 #include "lmg_common.hpp"
 #include <limits.h>
-#include <string.h>
 
 namespace {
 
@@ -211,26 +210,11 @@ int launch(SArgs a, int max_len, hipStream_t st)
 
 }  // namespace
 
-int lmg_sell_tune_set(const char *key, int v)
-{
-    if (strcmp(key, "sell_nt") == 0) {
-        if (v < -1 || v > 1) return LMG_ERR_ARG;
-        g_sell_nt = v;
-        return LMG_OK;
-    }
-    if (strcmp(key, "sell_ju") == 0) {
-        if (v != 0 && v != 5 && v != 7 && v != 8 && v != 10) return LMG_ERR_ARG;
-        g_sell_ju = v;
-        return LMG_OK;
-    }
-    return LMG_ERR_ARG;
-}
-int lmg_sell_tune_get(const char *key)
-{
-    if (strcmp(key, "sell_nt") == 0) return g_sell_nt;
-    if (strcmp(key, "sell_ju") == 0) return g_sell_ju;
-    return LMG_ERR_ARG;
-}
+constexpr LmgTuneKey lmg_tune_sell[] = {
+    lmg_tune_range("sell_nt", &g_sell_nt, -1, 1),
+    lmg_tune_list("sell_ju", &g_sell_ju, 0, 5, 7, 8, 10),
+    kLmgTuneEnd,
+};
 
 extern "C" {
 

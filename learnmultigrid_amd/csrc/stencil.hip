@@ -22,7 +22,6 @@
 // Arithmetic is unchanged: every row accumulates v*x over ITS pattern's entries in ascending column
 // order = slot order, products and sums rounded separately, so the results are bit-identical to
 // sweep.hip / pcsr.hip / rpat.hip and to the CPU oracle (tests assert array_equal).
-#include <string.h>
 #include "lmg_common.hpp"
 
 namespace {
@@ -270,26 +269,11 @@ int launch(SArgs a, hipStream_t st)
 
 }  // namespace
 
-int lmg_stencil_tune_set(const char *key, int v)
-{
-    if (strcmp(key, "stencil_nt_rows") == 0) {
-        if (v < 1) return LMG_ERR_ARG;
-        g_stencil_nt_rows = v;
-        return LMG_OK;
-    }
-    if (strcmp(key, "stencil_wgs_per_cu") == 0) {
-        if (v < 0 || v > 8) return LMG_ERR_ARG;
-        g_stencil_wgs_per_cu = v;
-        return LMG_OK;
-    }
-    return LMG_ERR_ARG;
-}
-int lmg_stencil_tune_get(const char *key)
-{
-    if (strcmp(key, "stencil_nt_rows") == 0) return g_stencil_nt_rows;
-    if (strcmp(key, "stencil_wgs_per_cu") == 0) return g_stencil_wgs_per_cu;
-    return LMG_ERR_ARG;
-}
+constexpr LmgTuneKey lmg_tune_stencil[] = {
+    lmg_tune_range("stencil_nt_rows", &g_stencil_nt_rows, 1),
+    lmg_tune_range("stencil_wgs_per_cu", &g_stencil_wgs_per_cu, 0, 8),
+    kLmgTuneEnd,
+};
 
 extern "C" {
 

@@ -18,7 +18,6 @@
 // lines (redundant loads and arithmetic, a few per cent).  Everything is expressed in linear indices
 // i = line * W + column, exactly like the format itself: a "column" outside [0, W) is just the linear
 // neighbour in the adjacent line, so no grid geometry is assumed beyond the pattern offsets c*W + d.
-#include <string.h>
 #include "lmg_common.hpp"
 
 #ifndef LMG_FUSED_NT_REST
@@ -38,6 +37,12 @@ constexpr int kWavesPerBlock = kBlock / LMG_WAVE;
 constexpr int kStripCols = 2 * LMG_WAVE;      // linear indices per line and wave
 
 struct MArgs {
+    // where this pass's argument rules differ from the tiled pass's (lmg_common.hpp)
+    static constexpr int64_t kRowLimit = (1ll << 29) - 4096;     // 32-bit byte offsets
+    static constexpr bool kOneRowIsCapacity = true;              // a lane loads two rows
+    static constexpr int64_t kProlMinCoarse = 1;
+    static constexpr bool kProlStrideCovers = true, kProlChecksPairs = false;
+    static constexpr int64_t kRestCoarseLimit = 1ll << 28;
     int n;
     int W;
     int lines;                // ceil(n / W)
@@ -67,8 +72,8 @@ struct MArgs {
     const double *pp_val;     // [pp_npat][4] values by slot
     const int *pp_mask;       // [pp_npat] slots present
     int pp_npat;
-    int hotp[2];              // even / odd lines: ids (A | B << 8) of the frequent pair of an (even, odd) column pair, or -1
-    double hp[9];             // their values: even line A s0 | B s0 s1 || odd line A s0 s2 | B s0 s1 s2 s3
+    int phot[2];              // even / odd lines: ids (A | B << 8) of the frequent pair of an (even, odd) column pair, or -1
+    double phv[9];            // their values: even line A s0 | B s0 s1 || odd line A s0 s2 | B s0 s1 s2 s3
     // REST: b_coarse = R r is formed on the fly instead of storing r (Multigrid.py:90 + :93 fused into the pre-smoothing
     // pass): row (Y, X) of R reads r at lines 2Y - 1 .. 2Y + 1, columns 2X - 1 .. 2X + 1 (slots 0..8 like the operator)
     double *bc;               // coarse right-hand side (output); nc, Wc as above
@@ -76,8 +81,8 @@ struct MArgs {
     const double *rp_val;     // [rp_npat][9]
     const int *rp_mask;       // [rp_npat]
     int rp_npat;
-    int hotr;                 // the frequent pattern with all nine slots, or -1
-    double hr[9];             // its values
+    int rhot;                 // the frequent pattern with all nine slots, or -1
+    double rhv[9];            // its values
 };
 
 // strip geometry: columns left of the stored part / stored columns of a 128-column window
@@ -293,10 +298,10 @@ __device__ __forceinline__ void fused_march(const MArgs &a, const Tables &T, con
     const double hrd = a.hot_rdiag;
     double hp[9];
 #pragma unroll
-    for (int s = 0; s < 9; ++s) hp[s] = PROL ? a.hp[s] : 0.0;
+    for (int s = 0; s < 9; ++s) hp[s] = PROL ? a.phv[s] : 0.0;
     const int okbits = FAST ? 0 : (3 << 16);
-    const int hotq_even = (PROL && a.hotp[0] >= 0) ? (a.hotp[0] | okbits) : -1;
-    const int hotq_odd = (PROL && a.hotp[1] >= 0) ? (a.hotp[1] | okbits) : -1;
+    const int hotq_even = (PROL && a.phot[0] >= 0) ? (a.phot[0] | okbits) : -1;
+    const int hotq_odd = (PROL && a.phot[1] >= 0) ? (a.phot[1] | okbits) : -1;
     double e_prev = 0.0;                                          // PROL: the coarse line the previous (even) line brought
 
     // FAST: byte offsets of the lane inside a line's window; lanes that never store point out of range
@@ -398,7 +403,7 @@ __device__ __forceinline__ void fused_march(const MArgs &a, const Tables &T, con
     const __amdgpu_buffer_rsrc_t rs_bc = __builtin_amdgcn_make_buffer_rsrc(REST ? a.bc : a.out, 0, (int)((unsigned)(REST ? a.nc : n) * 8u), 0x00020000);
     double hr[9];
 #pragma unroll
-    for (int s = 0; s < 9; ++s) hr[s] = REST ? a.hr[s] : 0.0;
+    for (int s = 0; s < 9; ++s) hr[s] = REST ? a.rhv[s] : 0.0;
     double acc_cur = 0.0;                                         // REST: running sum of the coarse row in progress,
     int rp_cur = 0, rp_now = 0;                                   //       its pattern id / the id that came with this line,
     bool st_cur = false, hot_cur = false;                         //       whether this lane stores it / all storing lanes are hot
@@ -635,7 +640,7 @@ __device__ __forceinline__ void fused_march(const MArgs &a, const Tables &T, con
                         rp_cur = rp_now;
                         sty_cur = y + 1 >= out_y0 && y + 1 < out_y1;
                         st_cur = sty_cur && colA;
-                        hot_cur = __all(!st_cur || rp_cur == a.hotr);
+                        hot_cur = __all(!st_cur || rp_cur == a.rhot);
                         acc_cur = 0.0;
                         if (hot_cur) {
 #pragma unroll
@@ -805,186 +810,77 @@ int launch4(MArgs a, hipStream_t st)
     return LMG_OK;
 }
 
-template <int S, unsigned UM>
-int launch2(MArgs a, bool resid, bool zero, hipStream_t st)
+// (sweeps, residual, zero iterate) -> template arguments: exactly the combinations each entry point offers
+template <unsigned UM>
+int launch_plain(MArgs a, int sweeps, bool resid, bool zero, hipStream_t st)
 {
-    if (resid) return zero ? launch4<S, UM, true, true>(a, st) : launch4<S, UM, true, false>(a, st);
-    return zero ? launch4<S, UM, false, true>(a, st) : launch4<S, UM, false, false>(a, st);
+    return lmg_with_sweeps<1, 3>(sweeps, [&](auto s) {
+        return lmg_with_flag(resid, [&](auto r) {
+            return lmg_with_flag(zero, [&](auto z) { return launch4<LMG_CT(s), UM, LMG_CT(r), LMG_CT(z)>(a, st); });
+        });
+    });
 }
 
 template <unsigned UM>
 int launch_prol(MArgs a, int sweeps, hipStream_t st)
 {
-    switch (sweeps) {
-    case 1: return launch4<1, UM, false, false, true>(a, st);
-    case 2: return launch4<2, UM, false, false, true>(a, st);
-    default: return launch4<3, UM, false, false, true>(a, st);
-    }
+    return lmg_with_sweeps<1, 3>(sweeps, [&](auto s) { return launch4<LMG_CT(s), UM, false, false, true>(a, st); });
 }
 
 template <unsigned UM>
 int launch_rest(MArgs a, int sweeps, bool zero, hipStream_t st)
 {
-    switch (sweeps) {
-    case 1: return zero ? launch4<1, UM, true, true, false, true>(a, st) : launch4<1, UM, true, false, false, true>(a, st);
-    case 2: return zero ? launch4<2, UM, true, true, false, true>(a, st) : launch4<2, UM, true, false, false, true>(a, st);
-    default: return zero ? launch4<3, UM, true, true, false, true>(a, st) : launch4<3, UM, true, false, false, true>(a, st);
-    }
+    return lmg_with_sweeps<1, 3>(sweeps, [&](auto s) {
+        return lmg_with_flag(zero, [&](auto z) { return launch4<LMG_CT(s), UM, true, LMG_CT(z), false, true>(a, st); });
+    });
 }
 
-template <unsigned UM>
-int launch1(MArgs a, int sweeps, bool resid, bool zero, hipStream_t st)
+// the fields only this pass has: the slot set, and the decomposition that launch4 decides
+MArgs own_fields(uint32_t union_mask)
 {
-    switch (sweeps) {
-    case 1: return launch2<1, UM>(a, resid, zero, st);
-    case 2: return launch2<2, UM>(a, resid, zero, st);
-    default: return launch2<3, UM>(a, resid, zero, st);
-    }
-}
-
-}  // namespace
-
-int lmg_fused_tune_set(const char *key, int v)
-{
-    if (strcmp(key, "fused_seg_lines") == 0) {
-        if (v < 0) return LMG_ERR_ARG;
-        g_fused_seg_lines = v;
-        return LMG_OK;
-    }
-    if (strcmp(key, "fused_pf") == 0) {
-        if (v != 0 && v != 2) return LMG_ERR_ARG;
-        g_fused_pf = v;
-        return LMG_OK;
-    }
-    if (strcmp(key, "fused_seg_min_lines") == 0) {
-        if (v < 0) return LMG_ERR_ARG;
-        g_fused_seg_min_lines = v;
-        return LMG_OK;
-    }
-    if (strcmp(key, "fused_seg_lines_prol") == 0 || strcmp(key, "fused_seg_lines_rest") == 0) {
-        if (v < 0) return LMG_ERR_ARG;
-        (key[16] == 'p' ? g_fused_seg_lines_prol : g_fused_seg_lines_rest) = v;
-        return LMG_OK;
-    }
-    if (strcmp(key, "fused_seg_max_lines") == 0) {
-        if (v < 0) return LMG_ERR_ARG;
-        g_fused_seg_max_lines = v;
-        return LMG_OK;
-    }
-    if (strcmp(key, "fused_want_waves_rest3") == 0) {
-        if (v < 1) return LMG_ERR_ARG;
-        g_fused_want_waves_rest3 = v;
-        return LMG_OK;
-    }
-    if (strcmp(key, "fused_want_waves") == 0) {
-        if (v < 1) return LMG_ERR_ARG;
-        g_fused_want_waves = v;
-        return LMG_OK;
-    }
-    if (strcmp(key, "fused_floor_halos") == 0) {
-        if (v < 1) return LMG_ERR_ARG;
-        g_fused_floor_halos = v;
-        return LMG_OK;
-    }
-    if (strcmp(key, "fused_balance") == 0 || strcmp(key, "fused_fast") == 0) {
-        if (v != 0 && v != 1) return LMG_ERR_ARG;
-        (key[6] == 'b' ? g_fused_balance : g_fused_fast) = v;
-        return LMG_OK;
-    }
-    if (strcmp(key, "fused_slow_pct") == 0) {
-        if (v < 10 || v > 100) return LMG_ERR_ARG;
-        g_fused_slow_pct = v;
-        return LMG_OK;
-    }
-    return LMG_ERR_ARG;
-}
-int lmg_fused_tune_get(const char *key)
-{
-    if (strcmp(key, "fused_seg_lines") == 0) return g_fused_seg_lines;
-    if (strcmp(key, "fused_pf") == 0) return g_fused_pf;
-    if (strcmp(key, "fused_seg_min_lines") == 0) return g_fused_seg_min_lines;
-    if (strcmp(key, "fused_seg_max_lines") == 0) return g_fused_seg_max_lines;
-    if (strcmp(key, "fused_seg_lines_prol") == 0) return g_fused_seg_lines_prol;
-    if (strcmp(key, "fused_seg_lines_rest") == 0) return g_fused_seg_lines_rest;
-    if (strcmp(key, "fused_want_waves") == 0) return g_fused_want_waves;
-    if (strcmp(key, "fused_want_waves_rest3") == 0) return g_fused_want_waves_rest3;
-    if (strcmp(key, "fused_floor_halos") == 0) return g_fused_floor_halos;
-    if (strcmp(key, "fused_balance") == 0) return g_fused_balance;
-    if (strcmp(key, "fused_fast") == 0) return g_fused_fast;
-    if (strcmp(key, "fused_slow_pct") == 0) return g_fused_slow_pct;
-    return LMG_ERR_ARG;
-}
-
-extern "C" {
-
-static int fill_args(MArgs &a, int64_t n, int32_t line_stride, const uint8_t *pid, int32_t npat, const double *st_val,
-                     const int32_t *st_mask, uint32_t union_mask, int32_t hot_pattern, const double *h_hot_val, int sweeps,
-                     const double *x_in, const double *b, double omega, double *x_out, double *r_out)
-{
-    if (n < 0 || n >= (1ll << 29) - 4096 || npat < 1 || npat > kMaxPat || (union_mask & ~kMask9)) return LMG_ERR_ARG;   // 32-bit byte offsets
-    if (sweeps < 1 || sweeps > 3) return LMG_ERR_ARG;
-    if (n == 0) return LMG_OK;
-    if (n < 2) return LMG_ERR_CAPACITY;
-    if (!pid || !st_val || !st_mask || !b || !x_out || x_in == x_out || r_out == x_out || (r_out && r_out == x_in))
-        return LMG_ERR_ARG;
-    if (line_stride < 3 || line_stride > n) return LMG_ERR_ARG;
-    a.n = (int)n;
-    a.W = line_stride;
-    a.lines = (int)((n + line_stride - 1) / line_stride);
-    a.npat = npat;
+    MArgs a;
     a.umask = union_mask;
     a.strips = a.segs = a.seg_lines = 0;
     a.items = a.nb_strips = a.edge_lines = a.allow_fast = 0;
     a.segs_b = a.seg_lines_b = 1;
-    a.pid = pid;
-    a.st_val = st_val;
-    a.st_mask = st_mask;
-    a.x = x_in;
-    a.b = b;
-    a.out = x_out;
-    a.r = r_out;
-    a.omega = omega;
-    a.hot = -1;
-    for (int k = 0; k < 9; ++k) a.hot_val[k] = 0.0;
-    a.hot_rdiag = 0.0;
-    if (hot_pattern >= 0 && hot_pattern < npat && h_hot_val && h_hot_val[4] != 0.0) {
-        a.hot = hot_pattern;
-        for (int k = 0; k < 9; ++k) a.hot_val[k] = h_hot_val[k];
-        a.hot_rdiag = 1.0 / h_hot_val[4];
-    }
-    a.ec = nullptr;
-    a.nc = a.Wc = 0;
-    a.ppid = nullptr;
-    a.pp_val = nullptr;
-    a.pp_mask = nullptr;
-    a.pp_npat = 0;
-    a.hotp[0] = a.hotp[1] = -1;
-    for (int k = 0; k < 9; ++k) a.hp[k] = 0.0;
-    a.bc = nullptr;
-    a.rpid = nullptr;
-    a.rp_val = nullptr;
-    a.rp_mask = nullptr;
-    a.rp_npat = 0;
-    a.hotr = -1;
-    for (int k = 0; k < 9; ++k) a.hr[k] = 0.0;
-    return 1;                                  // filled: launch
+    return a;
 }
+
+}  // namespace
+
+constexpr LmgTuneKey lmg_tune_fused[] = {
+    lmg_tune_range("fused_seg_lines", &g_fused_seg_lines, 0),
+    lmg_tune_range("fused_seg_min_lines", &g_fused_seg_min_lines, 0),
+    lmg_tune_range("fused_seg_max_lines", &g_fused_seg_max_lines, 0),
+    lmg_tune_list("fused_pf", &g_fused_pf, 0, 2),                          // nothing reads it (the kernels are built with PF = 2)
+    lmg_tune_range("fused_seg_lines_prol", &g_fused_seg_lines_prol, 0),
+    lmg_tune_range("fused_seg_lines_rest", &g_fused_seg_lines_rest, 0),
+    lmg_tune_range("fused_want_waves", &g_fused_want_waves, 1),
+    lmg_tune_range("fused_want_waves_rest3", &g_fused_want_waves_rest3, 1),
+    lmg_tune_range("fused_floor_halos", &g_fused_floor_halos, 1),
+    lmg_tune_list("fused_balance", &g_fused_balance, 0, 1),
+    lmg_tune_range("fused_slow_pct", &g_fused_slow_pct, 10, 100),
+    lmg_tune_list("fused_fast", &g_fused_fast, 0, 1),
+    kLmgTuneEnd,
+};
+
+extern "C" {
 
 int lmg_stencil_smooth(int64_t n, int32_t line_stride, const uint8_t *pid, int32_t npat, const double *st_val,
                        const int32_t *st_mask, uint32_t union_mask, int32_t hot_pattern, const double *h_hot_val,
                        int sweeps, const double *x_in, const double *b, double omega, double *x_out, double *r_out,
                        void *stream)
 {
-    MArgs a;
-    const int rc = fill_args(a, n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val, sweeps, x_in, b,
-                             omega, x_out, r_out);
+    MArgs a = own_fields(union_mask);
+    const int rc = lmg_smooth_fill(a, n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val, sweeps,
+                                   x_in, b, omega, x_out, r_out);
     if (rc != 1) return rc;
     hipStream_t st = lmg_stream(stream);
     const bool resid = r_out != nullptr, zero = x_in == nullptr;
     switch (union_mask) {
-    case kMask5: return launch1<kMask5>(a, sweeps, resid, zero, st);
-    case kMask9: return launch1<kMask9>(a, sweeps, resid, zero, st);
-    case kMask1D: return launch1<kMask1D>(a, sweeps, resid, zero, st);
+    case kMask5: return launch_plain<kMask5>(a, sweeps, resid, zero, st);
+    case kMask9: return launch_plain<kMask9>(a, sweeps, resid, zero, st);
+    case kMask1D: return launch_plain<kMask1D>(a, sweeps, resid, zero, st);
     default: return LMG_ERR_CAPACITY;        // other slot sets: run the separate sweeps
     }
 }
@@ -996,27 +892,14 @@ int lmg_stencil_smooth_prolong(int64_t n, int32_t line_stride, const uint8_t *pi
                                int32_t p_npat, const double *p_val, const int32_t *p_mask, const int32_t *h_hot_pairs,
                                const double *h_hot_pval, void *stream)
 {
-    if (!x_in || !e_coarse || !p_pid || !p_val || !p_mask || p_npat < 1 || p_npat > kMaxPat) return LMG_ERR_ARG;
-    if (n_coarse < 1 || n_coarse >= (1ll << 31) || coarse_stride < 1 || coarse_stride > n_coarse) return LMG_ERR_ARG;
-    if (e_coarse == x_out) return LMG_ERR_ARG;
-    // the 2 x 2 window of row (y, x) starts at ((y >> 1), (x >> 1)): the coarse line stride must cover the fine one
-    if ((int64_t)coarse_stride < ((int64_t)line_stride + 1) / 2) return LMG_ERR_ARG;
-    MArgs a;
-    const int rc = fill_args(a, n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val, sweeps, x_in, b,
-                             omega, x_out, nullptr);
+    const int bad = lmg_prol_check<MArgs>(line_stride, x_in, x_out, n_coarse, coarse_stride, e_coarse, p_pid, p_npat, p_val,
+                                          p_mask);
+    if (bad) return bad;
+    MArgs a = own_fields(union_mask);
+    const int rc = lmg_smooth_fill(a, n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val, sweeps,
+                                   x_in, b, omega, x_out, nullptr);
     if (rc != 1) return rc;
-    a.ec = e_coarse;
-    a.nc = (int)n_coarse;
-    a.Wc = coarse_stride;
-    a.ppid = p_pid;
-    a.pp_val = p_val;
-    a.pp_mask = p_mask;
-    a.pp_npat = p_npat;
-    if (h_hot_pairs && h_hot_pval) {
-        a.hotp[0] = h_hot_pairs[0];
-        a.hotp[1] = h_hot_pairs[1];
-        for (int k = 0; k < 9; ++k) a.hp[k] = h_hot_pval[k];
-    }
+    lmg_prol_set(a, n_coarse, coarse_stride, e_coarse, p_pid, p_npat, p_val, p_mask, h_hot_pairs, h_hot_pval);
     hipStream_t st = lmg_stream(stream);
     switch (union_mask) {
     case kMask5: return launch_prol<kMask5>(a, sweeps, st);
@@ -1032,29 +915,14 @@ int lmg_stencil_smooth_restrict(int64_t n, int32_t line_stride, const uint8_t *p
                                 int32_t r_npat, const double *r_val, const int32_t *r_mask, int32_t hot_r,
                                 const double *h_hot_rval, void *stream)
 {
-    if (!b_coarse || !r_pid || !r_val || !r_mask || r_npat < 1 || r_npat > kMaxPat) return LMG_ERR_ARG;
-    if (n_coarse < 1 || n_coarse >= (1ll << 28) || coarse_stride < 1 || coarse_stride > n_coarse) return LMG_ERR_ARG;
-    if ((const double *)b_coarse == x_in || b_coarse == x_out || (const double *)b_coarse == b) return LMG_ERR_ARG;
-    // row (Y, X) of R sits on the fine node (2 Y, 2 X): every such node of the fine grid must have its coarse row
-    const int64_t lines = n > 0 ? (n + line_stride - 1) / line_stride : 0;
-    // -- and nothing else: the pass only writes b_coarse under those nodes, a larger coarse grid would keep stale rows
-    if ((int64_t)coarse_stride != ((int64_t)line_stride + 1) / 2 || (n % line_stride) != 0 || n_coarse != ((lines + 1) / 2) * coarse_stride)
-        return LMG_ERR_ARG;
-    MArgs a;
-    const int rc = fill_args(a, n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val, sweeps, x_in, b,
-                             omega, x_out, nullptr);
+    const int bad = lmg_rest_check<MArgs>(n, line_stride, x_in, b, x_out, n_coarse, coarse_stride, b_coarse, r_pid, r_npat,
+                                          r_val, r_mask);
+    if (bad) return bad;
+    MArgs a = own_fields(union_mask);
+    const int rc = lmg_smooth_fill(a, n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val, sweeps,
+                                   x_in, b, omega, x_out, nullptr);
     if (rc != 1) return rc;
-    a.bc = b_coarse;
-    a.nc = (int)n_coarse;
-    a.Wc = coarse_stride;
-    a.rpid = r_pid;
-    a.rp_val = r_val;
-    a.rp_mask = r_mask;
-    a.rp_npat = r_npat;
-    if (hot_r >= 0 && hot_r < r_npat && h_hot_rval) {
-        a.hotr = hot_r;
-        for (int k = 0; k < 9; ++k) a.hr[k] = h_hot_rval[k];
-    }
+    lmg_rest_set(a, n_coarse, coarse_stride, b_coarse, r_pid, r_npat, r_val, r_mask, hot_r, h_hot_rval);
     hipStream_t st = lmg_stream(stream);
     const bool zero = x_in == nullptr;
     switch (union_mask) {

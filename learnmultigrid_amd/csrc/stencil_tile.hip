@@ -13,7 +13,6 @@
 // neighbour in the adjacent line.
 // (Tried: two columns per lane, 128-column tiles -- half the per-element overhead on paper, slower in practice: 9-point
 // 2049^2 61.5 / 48.0 us against 49.6 / 41.4 us for 3 sweeps + residual / 3 sweeps; twice the LDS per tile, half the waves.)
-#include <string.h>
 #include "lmg_common.hpp"
 
 namespace {
@@ -24,6 +23,12 @@ constexpr int kCols = 64;                     // columns of a tile = lanes of a 
 constexpr int kLS = kCols + 2;                // LDS line stride: one guard column on either side
 
 struct TArgs {
+    // where this pass's argument rules differ from the register pass's (lmg_common.hpp)
+    static constexpr int64_t kRowLimit = (1ll << 31) - 4096;     // rows are numbered in an int
+    static constexpr bool kOneRowIsCapacity = false;             // (one row is shorter than any line stride: LMG_ERR_ARG)
+    static constexpr int64_t kProlMinCoarse = 2;
+    static constexpr bool kProlStrideCovers = false, kProlChecksPairs = true;
+    static constexpr int64_t kRestCoarseLimit = 1ll << 31;
     int n, W, lines, npat;
     int tiles_x, tiles_y;
     const unsigned char *pid;
@@ -447,16 +452,6 @@ int launch4(TArgs a, hipStream_t st)
     return launch4x<S, UM, RESID, ZERO, PROL, REST, false>(a, st);
 }
 
-template <unsigned UM>
-int launch_prol(TArgs a, int sweeps, hipStream_t st)
-{
-    switch (sweeps) {
-    case 1: return launch4<1, UM, false, false, true>(a, st);
-    case 2: return launch4<2, UM, false, false, true>(a, st);
-    default: return launch4<3, UM, false, false, true>(a, st);
-    }
-}
-
 // The turnaround: x + P e, S = s_post + s_pre sweeps, b_coarse = R (b - A x) -- a halo of S + 2 lines and columns.  Its
 // 64-line tiles are 16 waves of four lines (a wave cannot hold more than 1024 threads' worth of 2-line blocks).
 template <int S, unsigned UM, bool HX>
@@ -467,159 +462,76 @@ int launch_turn3(TArgs a, hipStream_t st)
     return launch5<S, UM, true, false, 32, true, true, kRB, HX>(a, st);
 }
 
-template <int S, unsigned UM>
-int launch_turn2(TArgs a, hipStream_t st)
+// (sweeps, residual, zero iterate, hot transfers) -> template arguments: exactly the combinations each entry point offers
+template <unsigned UM>
+int launch_plain(TArgs a, int sweeps, bool resid, bool zero, hipStream_t st)
 {
-    if (g_tile_hot_transfers) return launch_turn3<S, UM, true>(a, st);
-    return launch_turn3<S, UM, false>(a, st);
+    return lmg_with_sweeps<1, 3>(sweeps, [&](auto s) {
+        return lmg_with_flag(resid, [&](auto r) {
+            return lmg_with_flag(zero, [&](auto z) { return launch4<LMG_CT(s), UM, LMG_CT(r), LMG_CT(z)>(a, st); });
+        });
+    });
 }
 
 template <unsigned UM>
-int launch_turn(TArgs a, int sweeps, hipStream_t st)
+int launch_prol(TArgs a, int sweeps, hipStream_t st)
 {
-    switch (sweeps) {
-    case 2: return launch_turn2<2, UM>(a, st);
-    case 3: return launch_turn2<3, UM>(a, st);
-    case 4: return launch_turn2<4, UM>(a, st);
-    case 5: return launch_turn2<5, UM>(a, st);
-    default: return launch_turn2<6, UM>(a, st);
-    }
+    return lmg_with_sweeps<1, 3>(sweeps, [&](auto s) { return launch4<LMG_CT(s), UM, false, false, true>(a, st); });
 }
 
 template <unsigned UM>
 int launch_rest(TArgs a, int sweeps, bool zero, hipStream_t st)
 {
-    switch (sweeps) {
-    case 1: return zero ? launch4<1, UM, true, true, false, true>(a, st) : launch4<1, UM, true, false, false, true>(a, st);
-    case 2: return zero ? launch4<2, UM, true, true, false, true>(a, st) : launch4<2, UM, true, false, false, true>(a, st);
-    default: return zero ? launch4<3, UM, true, true, false, true>(a, st) : launch4<3, UM, true, false, false, true>(a, st);
-    }
-}
-
-template <int S, unsigned UM>
-int launch2(TArgs a, bool resid, bool zero, hipStream_t st)
-{
-    if (resid) return zero ? launch4<S, UM, true, true>(a, st) : launch4<S, UM, true, false>(a, st);
-    return zero ? launch4<S, UM, false, true>(a, st) : launch4<S, UM, false, false>(a, st);
+    return lmg_with_sweeps<1, 3>(sweeps, [&](auto s) {
+        return lmg_with_flag(zero, [&](auto z) { return launch4<LMG_CT(s), UM, true, LMG_CT(z), false, true>(a, st); });
+    });
 }
 
 template <unsigned UM>
-int launch1(TArgs a, int sweeps, bool resid, bool zero, hipStream_t st)
+int launch_turn(TArgs a, int sweeps, hipStream_t st)
 {
-    switch (sweeps) {
-    case 1: return launch2<1, UM>(a, resid, zero, st);
-    case 2: return launch2<2, UM>(a, resid, zero, st);
-    default: return launch2<3, UM>(a, resid, zero, st);
-    }
+    return lmg_with_sweeps<2, 6>(sweeps, [&](auto s) {
+        return lmg_with_flag(g_tile_hot_transfers != 0, [&](auto hx) { return launch_turn3<LMG_CT(s), UM, LMG_CT(hx)>(a, st); });
+    });
+}
+
+// the fields only this pass has: the tiling that launch5 decides
+TArgs own_fields()
+{
+    TArgs a;
+    a.tiles_x = a.tiles_y = 0;
+    return a;
 }
 
 }  // namespace
 
-int lmg_tile_tune_set(const char *key, int v)
-{
-    if (strcmp(key, "tile_rows") == 0 || strcmp(key, "tile_rows_big") == 0) {
-        if (v != 0 && v != 16 && v != 32) return LMG_ERR_ARG;
-        (key[9] ? g_tile_rows_big : g_tile_rows) = v;
-        return LMG_OK;
-    }
-    if (strcmp(key, "tile_prol_wide_lines") == 0 || strcmp(key, "tile_prol_wide_lines_hx") == 0) {
-        if (v < 0) return LMG_ERR_ARG;
-        (key[20] ? g_tile_prol_wide_lines_hx : g_tile_prol_wide_lines) = v;
-        return LMG_OK;
-    }
-    if (strcmp(key, "tile_big_lines") == 0) {
-        if (v < 0) return LMG_ERR_ARG;
-        g_tile_big_lines = v;
-        return LMG_OK;
-    }
-    if (strcmp(key, "tile_turnaround_rows") == 0) {
-        if (v != 0 && v != 32 && v != 64) return LMG_ERR_ARG;
-        g_tile_turnaround_rows = v;
-        return LMG_OK;
-    }
-    if (strcmp(key, "tile_hot_transfers") == 0) {
-        if (v != 0 && v != 1) return LMG_ERR_ARG;
-        g_tile_hot_transfers = v;
-        return LMG_OK;
-    }
-    return LMG_ERR_ARG;
-}
-int lmg_tile_tune_get(const char *key)
-{
-    if (strcmp(key, "tile_rows") == 0) return g_tile_rows;
-    if (strcmp(key, "tile_rows_big") == 0) return g_tile_rows_big;
-    if (strcmp(key, "tile_big_lines") == 0) return g_tile_big_lines;
-    if (strcmp(key, "tile_prol_wide_lines") == 0) return g_tile_prol_wide_lines;
-    if (strcmp(key, "tile_hot_transfers") == 0) return g_tile_hot_transfers;
-    if (strcmp(key, "tile_prol_wide_lines_hx") == 0) return g_tile_prol_wide_lines_hx;
-    if (strcmp(key, "tile_turnaround_rows") == 0) return g_tile_turnaround_rows;
-    return LMG_ERR_ARG;
-}
+constexpr LmgTuneKey lmg_tune_tile[] = {
+    lmg_tune_list("tile_rows", &g_tile_rows, 0, 16, 32),
+    lmg_tune_list("tile_rows_big", &g_tile_rows_big, 0, 16, 32),
+    lmg_tune_range("tile_big_lines", &g_tile_big_lines, 0),
+    lmg_tune_range("tile_prol_wide_lines", &g_tile_prol_wide_lines, 0),
+    lmg_tune_range("tile_prol_wide_lines_hx", &g_tile_prol_wide_lines_hx, 0),
+    lmg_tune_list("tile_turnaround_rows", &g_tile_turnaround_rows, 0, 32, 64),
+    lmg_tune_list("tile_hot_transfers", &g_tile_hot_transfers, 0, 1),
+    kLmgTuneEnd,
+};
 
 extern "C" {
-
-static int tile_args(TArgs &a, int64_t n, int32_t line_stride, const uint8_t *pid, int32_t npat, const double *st_val,
-                     const int32_t *st_mask, uint32_t union_mask, int32_t hot_pattern, const double *h_hot_val, int sweeps,
-                     const double *x_in, const double *b, double omega, double *x_out, double *r_out)
-{
-    if (n < 0 || n >= (1ll << 31) - 4096 || npat < 1 || npat > kMaxPat || (union_mask & ~kMask9)) return LMG_ERR_ARG;
-    if (sweeps < 1 || sweeps > 3) return LMG_ERR_ARG;
-    if (n == 0) return LMG_OK;
-    if (!pid || !st_val || !st_mask || !b || !x_out || x_in == x_out || r_out == x_out || (r_out && r_out == x_in))
-        return LMG_ERR_ARG;
-    if (line_stride < 3 || line_stride > n) return LMG_ERR_ARG;
-    a.n = (int)n;
-    a.W = line_stride;
-    a.lines = (int)((n + line_stride - 1) / line_stride);
-    a.npat = npat;
-    a.tiles_x = a.tiles_y = 0;
-    a.pid = pid;
-    a.st_val = st_val;
-    a.st_mask = st_mask;
-    a.x = x_in;
-    a.b = b;
-    a.out = x_out;
-    a.r = r_out;
-    a.omega = omega;
-    a.hot = -1;
-    for (int k = 0; k < 9; ++k) a.hot_val[k] = 0.0;
-    a.hot_rdiag = 0.0;
-    if (hot_pattern >= 0 && hot_pattern < npat && h_hot_val && h_hot_val[4] != 0.0) {
-        a.hot = hot_pattern;
-        for (int k = 0; k < 9; ++k) a.hot_val[k] = h_hot_val[k];
-        a.hot_rdiag = 1.0 / h_hot_val[4];
-    }
-    a.ec = nullptr;
-    a.nc = a.Wc = 0;
-    a.ppid = nullptr;
-    a.pp_val = nullptr;
-    a.pp_mask = nullptr;
-    a.pp_npat = 0;
-    a.bc = nullptr;
-    a.rpid = nullptr;
-    a.rp_val = nullptr;
-    a.rp_mask = nullptr;
-    a.rp_npat = 0;
-    a.phot[0] = a.phot[1] = -1;
-    a.rhot = -1;
-    for (int k = 0; k < 9; ++k) a.phv[k] = a.rhv[k] = 0.0;
-    return 1;                                  // filled: launch
-}
 
 int lmg_stencil_smooth_tiled(int64_t n, int32_t line_stride, const uint8_t *pid, int32_t npat, const double *st_val,
                              const int32_t *st_mask, uint32_t union_mask, int32_t hot_pattern, const double *h_hot_val,
                              int sweeps, const double *x_in, const double *b, double omega, double *x_out, double *r_out,
                              void *stream)
 {
-    TArgs a;
-    const int rc = tile_args(a, n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val, sweeps, x_in, b,
-                             omega, x_out, r_out);
+    TArgs a = own_fields();
+    const int rc = lmg_smooth_fill(a, n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val, sweeps,
+                                   x_in, b, omega, x_out, r_out);
     if (rc != 1) return rc;
     hipStream_t st = lmg_stream(stream);
     const bool resid = r_out != nullptr, zero = x_in == nullptr;
     switch (union_mask) {
-    case kMask5: return launch1<kMask5>(a, sweeps, resid, zero, st);
-    case kMask9: return launch1<kMask9>(a, sweeps, resid, zero, st);
+    case kMask5: return launch_plain<kMask5>(a, sweeps, resid, zero, st);
+    case kMask9: return launch_plain<kMask9>(a, sweeps, resid, zero, st);
     default: return LMG_ERR_CAPACITY;        // other slot sets: run the separate sweeps
     }
 }
@@ -631,28 +543,14 @@ int lmg_stencil_smooth_tiled_prolong(int64_t n, int32_t line_stride, const uint8
                                      const uint8_t *p_pid, int32_t p_npat, const double *p_val, const int32_t *p_mask,
                                      const int32_t *h_hot_pairs, const double *h_hot_pval, void *stream)
 {
-    if (!x_in || !e_coarse || !p_pid || !p_val || !p_mask || p_npat < 1 || p_npat > kMaxPat) return LMG_ERR_ARG;
-    if (n_coarse < 2 || n_coarse >= (1ll << 31) || coarse_stride < 1 || coarse_stride > n_coarse) return LMG_ERR_ARG;
-    if (e_coarse == x_out) return LMG_ERR_ARG;
-    TArgs a;
-    const int rc = tile_args(a, n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val, sweeps, x_in, b,
-                             omega, x_out, nullptr);
+    const int bad = lmg_prol_check<TArgs>(line_stride, x_in, x_out, n_coarse, coarse_stride, e_coarse, p_pid, p_npat, p_val,
+                                          p_mask);
+    if (bad) return bad;
+    TArgs a = own_fields();
+    const int rc = lmg_smooth_fill(a, n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val, sweeps,
+                                   x_in, b, omega, x_out, nullptr);
     if (rc != 1) return rc;
-    a.ec = e_coarse;
-    a.nc = (int)n_coarse;
-    a.Wc = coarse_stride;
-    a.ppid = p_pid;
-    a.pp_val = p_val;
-    a.pp_mask = p_mask;
-    a.pp_npat = p_npat;
-    if (h_hot_pairs && h_hot_pval) {
-        for (int k = 0; k < 2; ++k) {
-            const int hp = h_hot_pairs[k];
-            const bool ok = hp >= 0 && (hp & 0xff) < p_npat && (hp >> 8) < p_npat;
-            a.phot[k] = ok ? hp : -1;
-        }
-        for (int k = 0; k < 9; ++k) a.phv[k] = h_hot_pval[k];
-    }
+    lmg_prol_set(a, n_coarse, coarse_stride, e_coarse, p_pid, p_npat, p_val, p_mask, h_hot_pairs, h_hot_pval);
     hipStream_t st = lmg_stream(stream);
     switch (union_mask) {
     case kMask5: return launch_prol<kMask5>(a, sweeps, st);
@@ -668,29 +566,14 @@ int lmg_stencil_smooth_tiled_restrict(int64_t n, int32_t line_stride, const uint
                                       const uint8_t *r_pid, int32_t r_npat, const double *r_val, const int32_t *r_mask,
                                       int32_t hot_r, const double *h_hot_rval, void *stream)
 {
-    if (!b_coarse || !r_pid || !r_val || !r_mask || r_npat < 1 || r_npat > kMaxPat) return LMG_ERR_ARG;
-    if (n_coarse < 1 || n_coarse >= (1ll << 31) || coarse_stride < 1 || coarse_stride > n_coarse) return LMG_ERR_ARG;
-    if ((const double *)b_coarse == x_in || b_coarse == x_out || (const double *)b_coarse == b) return LMG_ERR_ARG;
-    // every fine node (even line, even column) must have its coarse row
-    const int64_t lines = n > 0 ? (n + line_stride - 1) / line_stride : 0;
-    // -- and nothing else: the pass only writes b_coarse under those nodes, a larger coarse grid would keep stale rows
-    if ((int64_t)coarse_stride != ((int64_t)line_stride + 1) / 2 || (n % line_stride) != 0 || n_coarse != ((lines + 1) / 2) * coarse_stride)
-        return LMG_ERR_ARG;
-    TArgs a;
-    const int rc = tile_args(a, n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val, sweeps, x_in, b,
-                             omega, x_out, nullptr);
+    const int bad = lmg_rest_check<TArgs>(n, line_stride, x_in, b, x_out, n_coarse, coarse_stride, b_coarse, r_pid, r_npat,
+                                          r_val, r_mask);
+    if (bad) return bad;
+    TArgs a = own_fields();
+    const int rc = lmg_smooth_fill(a, n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val, sweeps,
+                                   x_in, b, omega, x_out, nullptr);
     if (rc != 1) return rc;
-    a.bc = b_coarse;
-    a.nc = (int)n_coarse;
-    a.Wc = coarse_stride;
-    a.rpid = r_pid;
-    a.rp_val = r_val;
-    a.rp_mask = r_mask;
-    a.rp_npat = r_npat;
-    if (hot_r >= 0 && hot_r < r_npat && h_hot_rval) {
-        a.rhot = hot_r;
-        for (int k = 0; k < 9; ++k) a.rhv[k] = h_hot_rval[k];
-    }
+    lmg_rest_set(a, n_coarse, coarse_stride, b_coarse, r_pid, r_npat, r_val, r_mask, hot_r, h_hot_rval);
     hipStream_t st = lmg_stream(stream);
     const bool zero = x_in == nullptr;
     switch (union_mask) {
@@ -710,44 +593,19 @@ int lmg_stencil_smooth_tiled_turnaround(int64_t n, int32_t line_stride, const ui
                                         const int32_t *r_mask, int32_t hot_r, const double *h_hot_rval, void *stream)
 {
     if (sweeps_post < 1 || sweeps_post > 3 || sweeps_pre < 1 || sweeps_pre > 3) return LMG_ERR_ARG;
-    // the argument checks of the correcting and of the restricting pass
-    if (!x_in || !e_coarse || !p_pid || !p_val || !p_mask || p_npat < 1 || p_npat > kMaxPat) return LMG_ERR_ARG;
-    if (!b_coarse || !r_pid || !r_val || !r_mask || r_npat < 1 || r_npat > kMaxPat) return LMG_ERR_ARG;
-    if (n_coarse < 2 || n_coarse >= (1ll << 31) || coarse_stride < 1 || coarse_stride > n_coarse) return LMG_ERR_ARG;
-    if (e_coarse == x_out || (const double *)b_coarse == e_coarse || (const double *)b_coarse == x_in || b_coarse == x_out ||
-        (const double *)b_coarse == b)
-        return LMG_ERR_ARG;
-    const int64_t lines = n > 0 ? (n + line_stride - 1) / line_stride : 0;
-    if ((int64_t)coarse_stride != ((int64_t)line_stride + 1) / 2 || (n % line_stride) != 0 || n_coarse != ((lines + 1) / 2) * coarse_stride)
-        return LMG_ERR_ARG;
-    TArgs a;
-    const int rc = tile_args(a, n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val, sweeps_post,
-                             x_in, b, omega, x_out, nullptr);
+    // the argument checks of the correcting and of the restricting pass, and the one pair only this pass can alias
+    int bad = lmg_prol_check<TArgs>(line_stride, x_in, x_out, n_coarse, coarse_stride, e_coarse, p_pid, p_npat, p_val, p_mask);
+    if (!bad)
+        bad = lmg_rest_check<TArgs>(n, line_stride, x_in, b, x_out, n_coarse, coarse_stride, b_coarse, r_pid, r_npat, r_val,
+                                    r_mask);
+    if (bad) return bad;
+    if ((const double *)b_coarse == e_coarse) return LMG_ERR_ARG;
+    TArgs a = own_fields();
+    const int rc = lmg_smooth_fill(a, n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val, sweeps_post,
+                                   x_in, b, omega, x_out, nullptr);
     if (rc != 1) return rc;
-    a.ec = e_coarse;
-    a.bc = b_coarse;
-    a.nc = (int)n_coarse;
-    a.Wc = coarse_stride;
-    a.ppid = p_pid;
-    a.pp_val = p_val;
-    a.pp_mask = p_mask;
-    a.pp_npat = p_npat;
-    if (h_hot_pairs && h_hot_pval) {
-        for (int k = 0; k < 2; ++k) {
-            const int hp = h_hot_pairs[k];
-            const bool ok = hp >= 0 && (hp & 0xff) < p_npat && (hp >> 8) < p_npat;
-            a.phot[k] = ok ? hp : -1;
-        }
-        for (int k = 0; k < 9; ++k) a.phv[k] = h_hot_pval[k];
-    }
-    a.rpid = r_pid;
-    a.rp_val = r_val;
-    a.rp_mask = r_mask;
-    a.rp_npat = r_npat;
-    if (hot_r >= 0 && hot_r < r_npat && h_hot_rval) {
-        a.rhot = hot_r;
-        for (int k = 0; k < 9; ++k) a.rhv[k] = h_hot_rval[k];
-    }
+    lmg_prol_set(a, n_coarse, coarse_stride, e_coarse, p_pid, p_npat, p_val, p_mask, h_hot_pairs, h_hot_pval);
+    lmg_rest_set(a, n_coarse, coarse_stride, b_coarse, r_pid, r_npat, r_val, r_mask, hot_r, h_hot_rval);
     hipStream_t st = lmg_stream(stream);
     switch (union_mask) {
     case kMask5: return launch_turn<kMask5>(a, sweeps_post + sweeps_pre, st);

@@ -229,13 +229,10 @@ int lmg_reduce_partials(const double *partials, int64_t count, double *norm2, hi
     return LMG_OK;
 }
 
-int lmg_sweep_tune_set(int v)
-{
-    if (v < 0 || v >= kNumVariants) return LMG_ERR_ARG;
-    g_sweep_variant = v;
-    return LMG_OK;
-}
-int lmg_sweep_tune_get(void) { return g_sweep_variant; }
+constexpr LmgTuneKey lmg_tune_sweep[] = {
+    lmg_tune_range("sweep_variant", &g_sweep_variant, 0, kNumVariants - 1),
+    kLmgTuneEnd,
+};
 
 extern "C" {
 
