@@ -261,6 +261,32 @@ int lmg_stencil_smooth_tiled_restrict(int64_t n, int32_t line_stride, const uint
  * lmg_stencil_smooth_tiled_restrict's (one coarse grid: n_coarse, coarse_stride as the restriction demands); b_coarse
  * must not alias e_coarse.  Same bits as the correcting pass followed by the restricting pass; the halo is
  * sweeps_post + sweeps_pre + 2 lines and columns, the tile 64 columns x 32 or 64 lines (tune key tile_turnaround_rows). */
+/* The tiled passes with ONE STEP OF THE CHEBYSHEV POLYNOMIAL SMOOTHER of degree 1..3 on D^-1 A in place of the Jacobi
+ * sweeps: sweep k = 0 .. degree - 1 of the pass is
+ *     d = a_k * d + c_k * (D^-1 (b - A x))   (k = 0: d = c_0 * (D^-1 (b - A x)), no add),     x = x + d,
+ * h_coef = HOST pointer to (a_0, c_0, a_1, c_1, ..) -- 2 * degree doubles, handed to the kernel in scalar registers; d
+ * lives in registers for the length of the pass and is never carried between launches.  Row sums in slot order, products
+ * and sums rounded separately: degree 1 is lmg_stencil_smooth_tiled with omega = c_0 bit for bit, and every degree has
+ * the bits of lmg_stencil_sweep(residual) + lmg_cheby_update per sweep.  Otherwise the arguments, rules and transfers of
+ * lmg_stencil_smooth_tiled / _tiled_prolong / _tiled_restrict (there is no Chebyshev turnaround pass). */
+int lmg_stencil_cheby_tiled(int64_t n, int32_t line_stride, const uint8_t *d_pid, int32_t npat,
+                            const double *d_st_val, const int32_t *d_st_mask, uint32_t union_mask,
+                            int32_t hot_pattern, const double *h_hot_val, int degree, const double *h_coef,
+                            const double *d_x_in, const double *d_b, double *d_x_out, double *d_r_out, void *stream);
+int lmg_stencil_cheby_tiled_prolong(int64_t n, int32_t line_stride, const uint8_t *d_pid, int32_t npat,
+                                    const double *d_st_val, const int32_t *d_st_mask, uint32_t union_mask,
+                                    int32_t hot_pattern, const double *h_hot_val, int degree, const double *h_coef,
+                                    const double *d_x_in, const double *d_b, double *d_x_out, int64_t n_coarse,
+                                    int32_t coarse_stride, const double *d_e_coarse, const uint8_t *d_p_pid,
+                                    int32_t p_npat, const double *d_p_val, const int32_t *d_p_mask,
+                                    const int32_t *h_hot_pairs, const double *h_hot_pval, void *stream);
+int lmg_stencil_cheby_tiled_restrict(int64_t n, int32_t line_stride, const uint8_t *d_pid, int32_t npat,
+                                     const double *d_st_val, const int32_t *d_st_mask, uint32_t union_mask,
+                                     int32_t hot_pattern, const double *h_hot_val, int degree, const double *h_coef,
+                                     const double *d_x_in, const double *d_b, double *d_x_out, int64_t n_coarse,
+                                     int32_t coarse_stride, double *d_b_coarse, const uint8_t *d_r_pid,
+                                     int32_t r_npat, const double *d_r_val, const int32_t *d_r_mask, int32_t hot_r,
+                                     const double *h_hot_rval, void *stream);
 int lmg_stencil_smooth_tiled_turnaround(int64_t n, int32_t line_stride, const uint8_t *d_pid, int32_t npat,
                                         const double *d_st_val, const int32_t *d_st_mask, uint32_t union_mask,
                                         int32_t hot_pattern, const double *h_hot_val, int sweeps_post, int sweeps_pre,
@@ -291,6 +317,11 @@ int lmg_dia_fill(int64_t n, int32_t line_stride, const int32_t *d_rowptr, const 
                  uint32_t union_mask, double *d_dia, int32_t *d_mismatch, uint32_t *d_mask_out, void *stream);
 int lmg_dia_smooth(int64_t n, int32_t line_stride, uint32_t union_mask, const double *d_dia, int sweeps,
                    const double *d_x_in, const double *d_b, double omega, double *d_x_out, double *d_r_out, void *stream);
+/* ... and with one Chebyshev step of degree 1..3 in place of the Jacobi sweeps (h_coef and arithmetic of
+ * lmg_stencil_cheby_tiled): same bits as lmg_csr_residual_norm2 + lmg_cheby_update per sweep. */
+int lmg_dia_cheby(int64_t n, int32_t line_stride, uint32_t union_mask, const double *d_dia, int degree,
+                  const double *h_coef, const double *d_x_in, const double *d_b, double *d_x_out, double *d_r_out,
+                  void *stream);
 
 /* The same pass with the coarse-grid correction folded in (Multigrid.py:115 + :121 in one pass):
  *     x_out = J^sweeps(x_in + P e_coarse)
@@ -381,6 +412,18 @@ int lmg_value_encode(int64_t count, const double *d_vals, const double *d_dict, 
                      void *d_out, int32_t *d_missing, void *stream);
 int lmg_csr_inverse_diagonal(int64_t n, const int32_t *d_rowptr, const int32_t *d_colidx, const double *d_vals,
                              double *d_dinv, void *stream);
+
+/* ---- Chebyshev polynomial smoother: the pieces outside the fused passes -------------------------------------------------
+ *   lmg_cheby_update    one step after a residual launch of ANY format, in one pass at 16 B per lane:
+ *                           d = a * d + c * (dinv * r)   (first != 0: d = c * (dinv * r), d is not read),   x = x + d
+ *                       dinv from lmg_csr_inverse_diagonal; the vectors must be distinct and 16-byte aligned.
+ *   lmg_csr_gershgorin  *d_lmax = max_i (sum_j |a_ij|) / |a_ii| over the rows with a non-zero diagonal (0 without any): the
+ *                       Gershgorin bound of the spectrum of D^-1 A, never below its largest eigenvalue.  Row sums in
+ *                       storage order, one maximum: bit-reproducible.  One memset and one launch (setup). */
+int lmg_cheby_update(int64_t n, double a, double c, int first, const double *d_dinv, const double *d_r, double *d_d,
+                     double *d_x, void *stream);
+int lmg_csr_gershgorin(int64_t n, const int32_t *d_rowptr, const int32_t *d_colidx, const double *d_vals, double *d_lmax,
+                       void *stream);
 
 /* CSR transpose by counting sort (setup: the restriction R = P^T as an explicit CSR, `i.T` of
  * Multigrid.py:93).  lmg_csr_transpose_count: d_counts[c] (zeroed by the caller, ncols entries) += number of

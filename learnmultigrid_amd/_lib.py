@@ -54,12 +54,18 @@ SIGNATURES = {
                                                     _i64, _i32, _p, _p, _i32, _p, _p, _p, _p, _p]),
     "lmg_stencil_smooth_tiled_restrict": (_c.c_int, [_i64, _i32, _p, _i32, _p, _p, _c.c_uint32, _i32, _p, _c.c_int, _p, _p, _f64, _p,
                                                      _i64, _i32, _p, _p, _i32, _p, _p, _i32, _p, _p]),
+    "lmg_stencil_cheby_tiled": (_c.c_int, [_i64, _i32, _p, _i32, _p, _p, _c.c_uint32, _i32, _p, _c.c_int, _p, _p, _p, _p, _p, _p]),
+    "lmg_stencil_cheby_tiled_prolong": (_c.c_int, [_i64, _i32, _p, _i32, _p, _p, _c.c_uint32, _i32, _p, _c.c_int, _p, _p, _p, _p,
+                                                   _i64, _i32, _p, _p, _i32, _p, _p, _p, _p, _p]),
+    "lmg_stencil_cheby_tiled_restrict": (_c.c_int, [_i64, _i32, _p, _i32, _p, _p, _c.c_uint32, _i32, _p, _c.c_int, _p, _p, _p, _p,
+                                                    _i64, _i32, _p, _p, _i32, _p, _p, _i32, _p, _p]),
     "lmg_stencil_smooth_tiled_turnaround": (_c.c_int, [_i64, _i32, _p, _i32, _p, _p, _c.c_uint32, _i32, _p, _c.c_int, _c.c_int, _p,
                                                        _p, _f64, _p, _i64, _i32, _p, _p, _i32, _p, _p, _p, _p,
                                                        _p, _p, _i32, _p, _p, _i32, _p, _p]),
     "lmg_dia_smooth_supported": (_c.c_int, [_c.c_uint32]),
     "lmg_dia_fill": (_c.c_int, [_i64, _i32, _p, _p, _p, _c.c_uint32, _p, _p, _p, _p]),
     "lmg_dia_smooth": (_c.c_int, [_i64, _i32, _c.c_uint32, _p, _c.c_int, _p, _p, _f64, _p, _p, _p]),
+    "lmg_dia_cheby": (_c.c_int, [_i64, _i32, _c.c_uint32, _p, _c.c_int, _p, _p, _p, _p, _p, _p]),
     "lmg_stencil_smooth_prolong_supported": (_c.c_int, [_c.c_uint32]),
     "lmg_stencil_smooth_prolong": (_c.c_int, [_i64, _i32, _p, _i32, _p, _p, _c.c_uint32, _i32, _p, _c.c_int, _p, _p, _f64, _p,
                                               _i64, _i32, _p, _p, _i32, _p, _p, _p, _p, _p]),
@@ -74,6 +80,8 @@ SIGNATURES = {
     "lmg_value_set_insert": (_c.c_int, [_i64, _p, _p, _i64, _i32, _p, _p]),
     "lmg_value_encode": (_c.c_int, [_i64, _p, _p, _i32, _c.c_int, _p, _p, _p]),
     "lmg_csr_inverse_diagonal": (_c.c_int, [_i64, _p, _p, _p, _p, _p]),
+    "lmg_cheby_update": (_c.c_int, [_i64, _f64, _f64, _c.c_int, _p, _p, _p, _p, _p]),
+    "lmg_csr_gershgorin": (_c.c_int, [_i64, _p, _p, _p, _p, _p]),
     "lmg_csr_transpose_max_row": (_c.c_int, []),
     "lmg_csr_transpose_count": (_c.c_int, [_i64, _i64, _p, _p, _p]),
     "lmg_csr_transpose_fill": (_c.c_int, [_i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p]),

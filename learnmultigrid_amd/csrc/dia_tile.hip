@@ -1,5 +1,6 @@
 // Fused smoothing passes for grid operators with VARIABLE coefficients (gfx950):
 //     x_out = J^S(x_in)   [r = b - A x_out]          S = 1..3 weighted-Jacobi sweeps, x_in == NULL: zero iterate
+// or, with CHEB, one Chebyshev smoothing step of degree S on D^-1 A in place of the S Jacobi sweeps (as in stencil_tile.hip)
 // on the DIA twin of a CSR matrix whose entries all sit at  column - row = c*W + d,  c, d in {-1, 0, 1}  (the 3x3
 // slots of stencil.hip) but whose VALUES differ from row to row: variable-coefficient stiffness matrices (cfg#5),
 // P1 matrices of jittered triangulations (cfg#3: 7 slots) -- the operators the reference's learned transfers are
@@ -30,6 +31,7 @@ struct DArgs {
     double *out;
     double *r;                // may be NULL without RESID
     double omega;
+    double cha[3], chc[3];    // CHEB: (a_k, c_k) of sweep k + 1 (last: every other field keeps its place)
 };
 
 template <unsigned UM> struct Slots {
@@ -37,7 +39,10 @@ template <unsigned UM> struct Slots {
     static constexpr int index(int s) { return __builtin_popcount(UM & ((1u << s) - 1u)); }
 };
 
-template <int S, unsigned UM, bool RESID, bool ZERO, int RR, int RB>
+// CHEB: sweep k = 0 .. S - 1 is  d = a_k * d + c_k * (rd * (b - A x))  (k = 0: no add),  x = x + d,  the coefficients in
+// scalar registers, d of the lane's RB elements in registers from sweep to sweep; degree 1 is the Jacobi sweep with
+// omega = c_0, bit for bit.
+template <int S, unsigned UM, bool RESID, bool ZERO, int RR, int RB, bool CHEB = false>
 __global__ void __launch_bounds__(RR / RB * LMG_WAVE) dia_tile_kernel(DArgs a)
 {
     constexpr int H = S + (RESID ? 1 : 0) - (ZERO ? 1 : 0);
@@ -85,6 +90,7 @@ __global__ void __launch_bounds__(RR / RB * LMG_WAVE) dia_tile_kernel(DArgs a)
     __syncthreads();
 
     const double omega = a.omega;
+    double dk[CHEB ? RB : 1];                                     // CHEB: d of the lane's elements
     struct Win { double m, c, p; };
     auto line = [&](const double *src, int r, bool sides) -> Win {
         Win w;
@@ -118,7 +124,25 @@ __global__ void __launch_bounds__(RR / RB * LMG_WAVE) dia_tile_kernel(DArgs a)
     for (int s = 1; s <= S; ++s) {
         const double *src = s_x[(s - 1) & 1];
         double *dst = s_x[s & 1];
-        if (ZERO && s == 1) {
+        if (CHEB && ZERO && s == 1) {
+            // first sweep from a zero iterate: x = d = c_0 * (D^-1 b)
+#pragma unroll
+            for (int k = 0; k < RB; ++k) {
+                dk[k] = a.chc[0] * (rd[k] * bk[k]);
+                dst[(rb0 + k) * kLS + 1 + lane] = ok[k] ? dk[k] : 0.0;
+            }
+        } else if (CHEB) {
+            const double ca = a.cha[s - 1], cc = a.chc[s - 1];
+            const bool first = s == 1;
+            block(src, [&](int k, double xc, double acc) {
+                const double res = bk[k] - acc;
+                const double z = rd[k] * res;
+                const double dn = first ? cc * z : ca * dk[k] + cc * z;
+                dk[k] = rd[k] == 0.0 ? 0.0 : dn;
+                const double nx = rd[k] == 0.0 ? xc : xc + dn;
+                dst[(rb0 + k) * kLS + 1 + lane] = ok[k] ? nx : 0.0;
+            });
+        } else if (ZERO && s == 1) {
             // first sweep from a zero iterate: x = omega * (D^-1 b) on every line (lmg_vmul's bits)
 #pragma unroll
             for (int k = 0; k < RB; ++k) dst[(rb0 + k) * kLS + 1 + lane] = ok[k] ? omega * (rd[k] * bk[k]) : 0.0;
@@ -205,7 +229,7 @@ __global__ void __launch_bounds__(256) dia_fill_kernel(int64_t n, int W, const i
 
 int g_dia_rows = 0;             // lines per tile: 0 = default, 32 or 64
 
-template <int S, unsigned UM, bool RESID, bool ZERO, int RR, int RB>
+template <int S, unsigned UM, bool RESID, bool ZERO, int RR, int RB, bool CHEB = false>
 int launch5(DArgs a, hipStream_t st)
 {
     constexpr int H = S + (RESID ? 1 : 0) - (ZERO ? 1 : 0);
@@ -213,34 +237,58 @@ int launch5(DArgs a, hipStream_t st)
     a.tiles_y = (a.lines + (RR - 2 * H) - 1) / (RR - 2 * H);
     const int64_t grid = (int64_t)a.tiles_x * a.tiles_y;
     if (grid > 0x7fffffff) return LMG_ERR_CAPACITY;
-    hipLaunchKernelGGL((dia_tile_kernel<S, UM, RESID, ZERO, RR, RB>), dim3((unsigned)grid), dim3(RR / RB * LMG_WAVE), 0, st, a);
+    hipLaunchKernelGGL((dia_tile_kernel<S, UM, RESID, ZERO, RR, RB, CHEB>), dim3((unsigned)grid), dim3(RR / RB * LMG_WAVE), 0, st, a);
     LMG_CHECK_LAUNCH();
     return LMG_OK;
 }
 
-template <int S, unsigned UM, bool RESID, bool ZERO>
+template <int S, unsigned UM, bool RESID, bool ZERO, bool CHEB = false>
 int launch4(DArgs a, hipStream_t st)
 {
     const int rr = g_dia_rows == 0 ? 32 : g_dia_rows;
-    if (rr == 64) return launch5<S, UM, RESID, ZERO, 64, 4>(a, st);
-    return launch5<S, UM, RESID, ZERO, 32, 2>(a, st);
+    if (rr == 64) return launch5<S, UM, RESID, ZERO, 64, 4, CHEB>(a, st);
+    return launch5<S, UM, RESID, ZERO, 32, 2, CHEB>(a, st);
 }
 
-template <int S, unsigned UM>
+template <int S, unsigned UM, bool CHEB = false>
 int launch2(DArgs a, bool resid, bool zero, hipStream_t st)
 {
-    if (resid) return zero ? launch4<S, UM, true, true>(a, st) : launch4<S, UM, true, false>(a, st);
-    return zero ? launch4<S, UM, false, true>(a, st) : launch4<S, UM, false, false>(a, st);
+    if (resid) return zero ? launch4<S, UM, true, true, CHEB>(a, st) : launch4<S, UM, true, false, CHEB>(a, st);
+    return zero ? launch4<S, UM, false, true, CHEB>(a, st) : launch4<S, UM, false, false, CHEB>(a, st);
 }
 
-template <unsigned UM>
+template <unsigned UM, bool CHEB = false>
 int launch1(DArgs a, int sweeps, bool resid, bool zero, hipStream_t st)
 {
     switch (sweeps) {
-    case 1: return launch2<1, UM>(a, resid, zero, st);
-    case 2: return launch2<2, UM>(a, resid, zero, st);
-    default: return launch2<3, UM>(a, resid, zero, st);
+    case 1: return launch2<1, UM, CHEB>(a, resid, zero, st);
+    case 2: return launch2<2, UM, CHEB>(a, resid, zero, st);
+    default: return launch2<3, UM, CHEB>(a, resid, zero, st);
     }
+}
+
+// the operator and the vectors of a pass: the argument rules lmg_dia_smooth and lmg_dia_cheby share.  Returns 1 with `a`
+// set, else the status to hand back (LMG_OK: nothing to do).
+int dia_fill_args(DArgs &a, int64_t n, int32_t line_stride, const double *dia, int sweeps, const double *x_in, const double *b,
+                  double omega, double *x_out, double *r_out)
+{
+    if (n < 0 || n >= (1ll << 31) - 4096) return LMG_ERR_ARG;
+    if (sweeps < 1 || sweeps > 3) return LMG_ERR_ARG;
+    if (n == 0) return LMG_OK;
+    if (!dia || !b || !x_out || x_in == x_out || r_out == x_out || (r_out && r_out == x_in)) return LMG_ERR_ARG;
+    if (line_stride < 3 || line_stride > n) return LMG_ERR_ARG;
+    a.n = (int)n;
+    a.W = line_stride;
+    a.lines = (int)((n + line_stride - 1) / line_stride);
+    a.tiles_x = a.tiles_y = 0;
+    a.dia = dia;
+    a.x = x_in;
+    a.b = b;
+    a.out = x_out;
+    a.r = r_out;
+    a.omega = omega;
+    for (int k = 0; k < 3; ++k) a.cha[k] = a.chc[k] = 0.0;
+    return 1;
 }
 
 
@@ -275,22 +323,9 @@ int lmg_dia_fill(int64_t n, int32_t line_stride, const int32_t *rowptr, const in
 int lmg_dia_smooth(int64_t n, int32_t line_stride, uint32_t union_mask, const double *dia, int sweeps, const double *x_in,
                    const double *b, double omega, double *x_out, double *r_out, void *stream)
 {
-    if (n < 0 || n >= (1ll << 31) - 4096) return LMG_ERR_ARG;
-    if (sweeps < 1 || sweeps > 3) return LMG_ERR_ARG;
-    if (n == 0) return LMG_OK;
-    if (!dia || !b || !x_out || x_in == x_out || r_out == x_out || (r_out && r_out == x_in)) return LMG_ERR_ARG;
-    if (line_stride < 3 || line_stride > n) return LMG_ERR_ARG;
     DArgs a;
-    a.n = (int)n;
-    a.W = line_stride;
-    a.lines = (int)((n + line_stride - 1) / line_stride);
-    a.tiles_x = a.tiles_y = 0;
-    a.dia = dia;
-    a.x = x_in;
-    a.b = b;
-    a.out = x_out;
-    a.r = r_out;
-    a.omega = omega;
+    const int rc = dia_fill_args(a, n, line_stride, dia, sweeps, x_in, b, omega, x_out, r_out);
+    if (rc != 1) return rc;
     hipStream_t st = lmg_stream(stream);
     const bool resid = r_out != nullptr, zero = x_in == nullptr;
     switch (union_mask) {
@@ -298,6 +333,28 @@ int lmg_dia_smooth(int64_t n, int32_t line_stride, uint32_t union_mask, const do
     case kMask7a: return launch1<kMask7a>(a, sweeps, resid, zero, st);
     case kMask7b: return launch1<kMask7b>(a, sweeps, resid, zero, st);
     case kMask9: return launch1<kMask9>(a, sweeps, resid, zero, st);
+    default: return LMG_ERR_CAPACITY;
+    }
+}
+
+int lmg_dia_cheby(int64_t n, int32_t line_stride, uint32_t union_mask, const double *dia, int degree, const double *h_coef,
+                  const double *x_in, const double *b, double *x_out, double *r_out, void *stream)
+{
+    if (degree < 1 || degree > 3 || !h_coef) return LMG_ERR_ARG;
+    DArgs a;
+    const int rc = dia_fill_args(a, n, line_stride, dia, degree, x_in, b, h_coef[1], x_out, r_out);
+    if (rc != 1) return rc;
+    for (int k = 0; k < degree; ++k) {
+        a.cha[k] = h_coef[2 * k];
+        a.chc[k] = h_coef[2 * k + 1];
+    }
+    hipStream_t st = lmg_stream(stream);
+    const bool resid = r_out != nullptr, zero = x_in == nullptr;
+    switch (union_mask) {
+    case kMask5: return launch1<kMask5, true>(a, degree, resid, zero, st);
+    case kMask7a: return launch1<kMask7a, true>(a, degree, resid, zero, st);
+    case kMask7b: return launch1<kMask7b, true>(a, degree, resid, zero, st);
+    case kMask9: return launch1<kMask9, true>(a, degree, resid, zero, st);
     default: return LMG_ERR_CAPACITY;
     }
 }

@@ -1,5 +1,6 @@
 // Fused smoothing passes for SMALL grid-stencil levels (format of stencil.hip) for gfx950:
 //     x_out = J^S(x_in)   [r = b - A x_out]          S = 1..3 weighted-Jacobi sweeps, x_in == NULL: zero iterate
+// or, with CHEB, one Chebyshev smoothing step of degree S on D^-1 A (below) in place of the S Jacobi sweeps
 // -- what stencil_fused.hip does for the multi-million-row levels, with the iterates in LDS instead of registers.
 // On a level of 10^4 .. 10^6 rows a sweep is a 2 - 7 us launch (tools/time_small.py) and the register kernel is no
 // help: a wave there walks 12 - 40 lines one after the other, 2 100 cycles each.  Here a WORKGROUP owns a tile of
@@ -65,6 +66,8 @@ struct TArgs {
     double phv[9];
     int rhot;
     double rhv[9];
+    // CHEB: the (a_k, c_k) of sweep k + 1 of the Chebyshev step (last, so that every other field keeps its place)
+    double cha[3], chc[3];
 };
 
 // HX (hot transfers, with PROL or REST): the correction x + P e is formed as each element arrives, from the usual pair
@@ -72,7 +75,13 @@ struct TArgs {
 // element stays live across the pattern staging and barrier; the restriction runs once per coarse node (a thread per
 // node of the tile's inner part, 32 per wave line) instead of being carried by every fine element, with the frequent
 // row of R in scalar registers where a whole wave has it.
-template <int S, unsigned UM, bool RESID, bool ZERO, int RR, bool PROL = false, bool REST = false, int RBV = kRB, bool HX = false>
+// CHEB (Chebyshev polynomial smoother of degree S on D^-1 A): sweep k = 0 .. S - 1 is
+//     d = a_k * d + c_k * (rdiag * (b - A x))   (k = 0: d = c_0 * (rdiag * (b - A x)), no add),   x = x + d
+// with the coefficients in scalar registers and d of the elements a lane owns in its registers from sweep to sweep (a
+// lane computes the same elements in every sweep, halo included, so d never travels).  The row sums, the transfers and
+// the residual are those of the Jacobi pass; degree 1 is the Jacobi sweep with omega = c_0, bit for bit.
+template <int S, unsigned UM, bool RESID, bool ZERO, int RR, bool PROL = false, bool REST = false, int RBV = kRB, bool HX = false,
+          bool CHEB = false>
 // (16-wave workgroups: at most 64 VGPRs, so that two of them share a CU -- the variants with the restriction had 65 - 67;
 // the 64-line turnaround, four lines per wave, needs 76 / 89 and spills under that bound)
 __global__ void __launch_bounds__(RR / RBV * LMG_WAVE, (RR / RBV == 16 && (!PROL || HX) && !(PROL && REST && RBV == 4)) ? 8 : 1)
@@ -243,6 +252,7 @@ stencil_tile_kernel(TArgs a)
     __syncthreads();
 
     const double omega = a.omega;
+    double dk[CHEB ? RB : 1];                                     // CHEB: d of the lane's elements
     double hv[9];
 #pragma unroll
     for (int s = 0; s < 9; ++s) hv[s] = a.hot_val[s];
@@ -309,7 +319,27 @@ stencil_tile_kernel(TArgs a)
     for (int s = 1; s <= S; ++s) {
         const double *src = s_x[(s - 1) & 1];
         double *dst = s_x[s & 1];
-        if (ZERO && s == 1) {
+        if (CHEB && ZERO && s == 1) {
+            // first sweep from a zero iterate: x = d = c_0 * (D^-1 b)
+#pragma unroll
+            for (int k = 0; k < RB; ++k) {
+                dk[k] = a.chc[0] * (s_rdiag[pk[k] & 0xff] * bk[k]);
+                dst[(rb0 + k) * kLS + 1 + lane] = (pk[k] >> 8) ? dk[k] : 0.0;
+            }
+        } else if (CHEB) {
+            const double ca = a.cha[s - 1], cc = a.chc[s - 1];
+            const bool first = s == 1;
+            block(src, 1, RR - 1, [&](int k, bool keep, bool hotp, double xc, double acc) {
+                const double res = bk[k] - acc;
+                const int q = pk[k] & 0xff;
+                const bool nodiag = !hotp && (s_mask[q] >> 16);
+                const double z = (hotp ? hrd : s_rdiag[q]) * res;
+                const double dn = first ? cc * z : ca * dk[k] + cc * z;
+                dk[k] = nodiag ? 0.0 : dn;
+                const double nx = nodiag ? xc : xc + dn;
+                if (keep) dst[(rb0 + k) * kLS + 1 + lane] = (pk[k] >> 8) ? nx : 0.0;
+            });
+        } else if (ZERO && s == 1) {
             // first sweep from a zero iterate: x = omega * (D^-1 b) on every line (lmg_vmul's bits)
 #pragma unroll
             for (int k = 0; k < RB; ++k)
@@ -410,7 +440,8 @@ int g_tile_prol_wide_lines_hx = 1 << 30;    // g_tile_prol_wide_lines of the HX 
                                             // runs 8 waves / SIMD (4 lines per wave: 87 VGPRs, 5); cfg#4 cycle 0.4698 ->
                                             // 0.4539 ms without the 4-line variant at 2049^2
 
-template <int S, unsigned UM, bool RESID, bool ZERO, int RR, bool PROL = false, bool REST = false, int RBV = kRB, bool HX = false>
+template <int S, unsigned UM, bool RESID, bool ZERO, int RR, bool PROL = false, bool REST = false, int RBV = kRB, bool HX = false,
+          bool CHEB = false>
 int launch5(TArgs a, hipStream_t st)
 {
     constexpr int H = S + (RESID ? 1 : 0) - (ZERO ? 1 : 0) + (REST ? 1 : 0);
@@ -418,7 +449,7 @@ int launch5(TArgs a, hipStream_t st)
     a.tiles_y = (a.lines + (RR - 2 * H) - 1) / (RR - 2 * H);
     const int64_t grid = (int64_t)a.tiles_x * a.tiles_y;
     if (grid > 0x7fffffff) return LMG_ERR_CAPACITY;
-    hipLaunchKernelGGL((stencil_tile_kernel<S, UM, RESID, ZERO, RR, PROL, REST, RBV, HX>), dim3((unsigned)grid),
+    hipLaunchKernelGGL((stencil_tile_kernel<S, UM, RESID, ZERO, RR, PROL, REST, RBV, HX, CHEB>), dim3((unsigned)grid),
                        dim3(RR / RBV * LMG_WAVE), 0, st, a);
     LMG_CHECK_LAUNCH();
     return LMG_OK;
@@ -430,26 +461,26 @@ static int tile_rows_for(const TArgs &a)
     return rr == 0 ? 32 : rr;     // measured in the cycle (cfg#4): 0.672 ms with 32-line tiles (16 waves), 0.688 with 16 (8 waves)
 }
 
-template <int S, unsigned UM, bool RESID, bool ZERO, bool PROL, bool REST, bool HX>
+template <int S, unsigned UM, bool RESID, bool ZERO, bool PROL, bool REST, bool HX, bool CHEB = false>
 int launch4x(TArgs a, hipStream_t st)
 {
-    if (tile_rows_for(a) == 16) return launch5<S, UM, RESID, ZERO, 16, PROL, REST, kRB, HX>(a, st);
+    if (tile_rows_for(a) == 16) return launch5<S, UM, RESID, ZERO, 16, PROL, REST, kRB, HX, CHEB>(a, st);
     // the pass with the correction needs 81 VGPRs: a 16-wave workgroup then fills a CU alone; on levels with many tiles
     // it runs 8 waves of four lines each (2049^2, 9-point: 69 instead of 81 us)
     if constexpr (PROL) {
         if (a.lines >= (HX ? g_tile_prol_wide_lines_hx : g_tile_prol_wide_lines))
-            return launch5<S, UM, RESID, ZERO, 32, PROL, REST, 4, HX>(a, st);
+            return launch5<S, UM, RESID, ZERO, 32, PROL, REST, 4, HX, CHEB>(a, st);
     }
-    return launch5<S, UM, RESID, ZERO, 32, PROL, REST, kRB, HX>(a, st);
+    return launch5<S, UM, RESID, ZERO, 32, PROL, REST, kRB, HX, CHEB>(a, st);
 }
 
-template <int S, unsigned UM, bool RESID, bool ZERO, bool PROL = false, bool REST = false>
+template <int S, unsigned UM, bool RESID, bool ZERO, bool PROL = false, bool REST = false, bool CHEB = false>
 int launch4(TArgs a, hipStream_t st)
 {
     if constexpr (PROL || REST) {
-        if (g_tile_hot_transfers) return launch4x<S, UM, RESID, ZERO, PROL, REST, true>(a, st);
+        if (g_tile_hot_transfers) return launch4x<S, UM, RESID, ZERO, PROL, REST, true, CHEB>(a, st);
     }
-    return launch4x<S, UM, RESID, ZERO, PROL, REST, false>(a, st);
+    return launch4x<S, UM, RESID, ZERO, PROL, REST, false, CHEB>(a, st);
 }
 
 // The turnaround: x + P e, S = s_post + s_pre sweeps, b_coarse = R (b - A x) -- a halo of S + 2 lines and columns.  Its
@@ -463,27 +494,29 @@ int launch_turn3(TArgs a, hipStream_t st)
 }
 
 // (sweeps, residual, zero iterate, hot transfers) -> template arguments: exactly the combinations each entry point offers
-template <unsigned UM>
+template <unsigned UM, bool CHEB = false>
 int launch_plain(TArgs a, int sweeps, bool resid, bool zero, hipStream_t st)
 {
     return lmg_with_sweeps<1, 3>(sweeps, [&](auto s) {
         return lmg_with_flag(resid, [&](auto r) {
-            return lmg_with_flag(zero, [&](auto z) { return launch4<LMG_CT(s), UM, LMG_CT(r), LMG_CT(z)>(a, st); });
+            return lmg_with_flag(zero, [&](auto z) {
+                return launch4<LMG_CT(s), UM, LMG_CT(r), LMG_CT(z), false, false, CHEB>(a, st);
+            });
         });
     });
 }
 
-template <unsigned UM>
+template <unsigned UM, bool CHEB = false>
 int launch_prol(TArgs a, int sweeps, hipStream_t st)
 {
-    return lmg_with_sweeps<1, 3>(sweeps, [&](auto s) { return launch4<LMG_CT(s), UM, false, false, true>(a, st); });
+    return lmg_with_sweeps<1, 3>(sweeps, [&](auto s) { return launch4<LMG_CT(s), UM, false, false, true, false, CHEB>(a, st); });
 }
 
-template <unsigned UM>
+template <unsigned UM, bool CHEB = false>
 int launch_rest(TArgs a, int sweeps, bool zero, hipStream_t st)
 {
     return lmg_with_sweeps<1, 3>(sweeps, [&](auto s) {
-        return lmg_with_flag(zero, [&](auto z) { return launch4<LMG_CT(s), UM, true, LMG_CT(z), false, true>(a, st); });
+        return lmg_with_flag(zero, [&](auto z) { return launch4<LMG_CT(s), UM, true, LMG_CT(z), false, true, CHEB>(a, st); });
     });
 }
 
@@ -500,7 +533,19 @@ TArgs own_fields()
 {
     TArgs a;
     a.tiles_x = a.tiles_y = 0;
+    for (int k = 0; k < 3; ++k) a.cha[k] = a.chc[k] = 0.0;
     return a;
+}
+
+// The coefficient table of a Chebyshev step: h_coef = HOST pointer to (a_0, c_0, .., a_(degree-1), c_(degree-1)).  c_0
+// stands in for omega in the shared argument rules.
+bool cheby_coef_ok(int degree, const double *h_coef) { return degree >= 1 && degree <= 3 && h_coef != nullptr; }
+void cheby_set(TArgs &a, int degree, const double *h_coef)
+{
+    for (int k = 0; k < degree; ++k) {
+        a.cha[k] = h_coef[2 * k];
+        a.chc[k] = h_coef[2 * k + 1];
+    }
 }
 
 }  // namespace
@@ -610,6 +655,77 @@ int lmg_stencil_smooth_tiled_turnaround(int64_t n, int32_t line_stride, const ui
     switch (union_mask) {
     case kMask5: return launch_turn<kMask5>(a, sweeps_post + sweeps_pre, st);
     case kMask9: return launch_turn<kMask9>(a, sweeps_post + sweeps_pre, st);
+    default: return LMG_ERR_CAPACITY;
+    }
+}
+
+int lmg_stencil_cheby_tiled(int64_t n, int32_t line_stride, const uint8_t *pid, int32_t npat, const double *st_val,
+                            const int32_t *st_mask, uint32_t union_mask, int32_t hot_pattern, const double *h_hot_val,
+                            int degree, const double *h_coef, const double *x_in, const double *b, double *x_out,
+                            double *r_out, void *stream)
+{
+    if (!cheby_coef_ok(degree, h_coef)) return LMG_ERR_ARG;
+    TArgs a = own_fields();
+    const int rc = lmg_smooth_fill(a, n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val, degree,
+                                   x_in, b, h_coef[1], x_out, r_out);
+    if (rc != 1) return rc;
+    cheby_set(a, degree, h_coef);
+    hipStream_t st = lmg_stream(stream);
+    const bool resid = r_out != nullptr, zero = x_in == nullptr;
+    switch (union_mask) {
+    case kMask5: return launch_plain<kMask5, true>(a, degree, resid, zero, st);
+    case kMask9: return launch_plain<kMask9, true>(a, degree, resid, zero, st);
+    default: return LMG_ERR_CAPACITY;        // other slot sets: residual launch + lmg_cheby_update
+    }
+}
+
+int lmg_stencil_cheby_tiled_prolong(int64_t n, int32_t line_stride, const uint8_t *pid, int32_t npat, const double *st_val,
+                                    const int32_t *st_mask, uint32_t union_mask, int32_t hot_pattern,
+                                    const double *h_hot_val, int degree, const double *h_coef, const double *x_in,
+                                    const double *b, double *x_out, int64_t n_coarse, int32_t coarse_stride,
+                                    const double *e_coarse, const uint8_t *p_pid, int32_t p_npat, const double *p_val,
+                                    const int32_t *p_mask, const int32_t *h_hot_pairs, const double *h_hot_pval, void *stream)
+{
+    if (!cheby_coef_ok(degree, h_coef)) return LMG_ERR_ARG;
+    const int bad = lmg_prol_check<TArgs>(line_stride, x_in, x_out, n_coarse, coarse_stride, e_coarse, p_pid, p_npat, p_val,
+                                          p_mask);
+    if (bad) return bad;
+    TArgs a = own_fields();
+    const int rc = lmg_smooth_fill(a, n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val, degree,
+                                   x_in, b, h_coef[1], x_out, nullptr);
+    if (rc != 1) return rc;
+    cheby_set(a, degree, h_coef);
+    lmg_prol_set(a, n_coarse, coarse_stride, e_coarse, p_pid, p_npat, p_val, p_mask, h_hot_pairs, h_hot_pval);
+    hipStream_t st = lmg_stream(stream);
+    switch (union_mask) {
+    case kMask5: return launch_prol<kMask5, true>(a, degree, st);
+    case kMask9: return launch_prol<kMask9, true>(a, degree, st);
+    default: return LMG_ERR_CAPACITY;
+    }
+}
+
+int lmg_stencil_cheby_tiled_restrict(int64_t n, int32_t line_stride, const uint8_t *pid, int32_t npat, const double *st_val,
+                                     const int32_t *st_mask, uint32_t union_mask, int32_t hot_pattern,
+                                     const double *h_hot_val, int degree, const double *h_coef, const double *x_in,
+                                     const double *b, double *x_out, int64_t n_coarse, int32_t coarse_stride,
+                                     double *b_coarse, const uint8_t *r_pid, int32_t r_npat, const double *r_val,
+                                     const int32_t *r_mask, int32_t hot_r, const double *h_hot_rval, void *stream)
+{
+    if (!cheby_coef_ok(degree, h_coef)) return LMG_ERR_ARG;
+    const int bad = lmg_rest_check<TArgs>(n, line_stride, x_in, b, x_out, n_coarse, coarse_stride, b_coarse, r_pid, r_npat,
+                                          r_val, r_mask);
+    if (bad) return bad;
+    TArgs a = own_fields();
+    const int rc = lmg_smooth_fill(a, n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val, degree,
+                                   x_in, b, h_coef[1], x_out, nullptr);
+    if (rc != 1) return rc;
+    cheby_set(a, degree, h_coef);
+    lmg_rest_set(a, n_coarse, coarse_stride, b_coarse, r_pid, r_npat, r_val, r_mask, hot_r, h_hot_rval);
+    hipStream_t st = lmg_stream(stream);
+    const bool zero = x_in == nullptr;
+    switch (union_mask) {
+    case kMask5: return launch_rest<kMask5, true>(a, degree, zero, st);
+    case kMask9: return launch_rest<kMask9, true>(a, degree, zero, st);
     default: return LMG_ERR_CAPACITY;
     }
 }

@@ -52,6 +52,71 @@ __global__ void __launch_bounds__(kBlock) vmul_kernel(int64_t n, double alpha, c
         out[i] = alpha * (x[i] * y[i]);
 }
 
+// One step of the Chebyshev polynomial smoother for the formats without a fused pass, after their residual launch:
+//     d = a * d + c * (dinv * r)   (FIRST: d = c * (dinv * r), d is not read),   x = x + d
+// two elements (16 bytes) per lane per step; products and sums round separately, the bits of the fused passes.
+template <bool FIRST>
+__global__ void __launch_bounds__(kBlock) cheby_update_kernel(int64_t n, double a, double c, const double *dinv,
+                                                              const double *r, double *d, double *x)
+{
+    const int64_t n2 = n >> 1;
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    const double2 *dinv2 = reinterpret_cast<const double2 *>(dinv), *r2 = reinterpret_cast<const double2 *>(r);
+    double2 *d2 = reinterpret_cast<double2 *>(d), *x2 = reinterpret_cast<double2 *>(x);
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n2; i += stride) {
+        const double2 iv = dinv2[i], rv = r2[i];
+        double2 xv = x2[i], dv;
+        if (FIRST) {
+            dv.x = c * (iv.x * rv.x);
+            dv.y = c * (iv.y * rv.y);
+        } else {
+            dv = d2[i];
+            dv.x = a * dv.x + c * (iv.x * rv.x);
+            dv.y = a * dv.y + c * (iv.y * rv.y);
+        }
+        xv.x = xv.x + dv.x;
+        xv.y = xv.y + dv.y;
+        d2[i] = dv;
+        x2[i] = xv;
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+        const int64_t i = n - 1;
+        const double z = c * (dinv[i] * r[i]);
+        const double dv = FIRST ? z : a * d[i] + z;
+        d[i] = dv;
+        x[i] = x[i] + dv;
+    }
+}
+
+// Gershgorin bound of D^-1 A: max over the rows with a non-zero diagonal of (sum_j |a_ij|) / |a_ii|, the row sums in
+// storage order (duplicate diagonal entries are summed like lmg_csr_inverse_diagonal does).  The ratios are >= 0, so
+// their order as doubles is the order of their bit patterns as unsigned integers: one integer maximum per wave into
+// *out (zeroed before the launch) -- a maximum does not depend on the order it is taken in.
+__global__ void __launch_bounds__(kBlock) csr_gershgorin_kernel(int64_t n, const int *rowptr, const int *colidx,
+                                                                const double *vals, unsigned long long *out)
+{
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    double m = 0.0;
+    for (int64_t row = (int64_t)blockIdx.x * kBlock + threadIdx.x; row < n; row += stride) {
+        double sum = 0.0, dg = 0.0;
+        for (int e = rowptr[row]; e < rowptr[row + 1]; ++e) {
+            const double v = vals[e];
+            sum += fabs(v);
+            if (colidx[e] == row) dg += v;
+        }
+        if (dg != 0.0) {
+            const double q = sum / fabs(dg);
+            m = q > m ? q : m;                       // (a NaN ratio never wins)
+        }
+    }
+#pragma unroll
+    for (int off = LMG_WAVE / 2; off > 0; off >>= 1) {
+        const double o = __shfl_down(m, off, LMG_WAVE);
+        m = o > m ? o : m;
+    }
+    if ((threadIdx.x & (LMG_WAVE - 1)) == 0 && m > 0.0) atomicMax(out, (unsigned long long)__double_as_longlong(m));
+}
+
 // fixed geometry (1024 partials) so the result does not depend on tuning knobs
 __global__ void __launch_bounds__(kBlock) dot_kernel(int64_t n, const double *x, const double *y,
                                                      double *partial)
@@ -686,6 +751,33 @@ int lmg_vmul(int64_t n, double alpha, const double *x, const double *y, double *
     if (n < 0 || (n > 0 && (!x || !y || !out))) return LMG_ERR_ARG;
     if (n == 0) return LMG_OK;
     hipLaunchKernelGGL(vmul_kernel, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, lmg_stream(stream), n, alpha, x, y, out);
+    LMG_CHECK_LAUNCH();
+    return LMG_OK;
+}
+
+int lmg_cheby_update(int64_t n, double a, double c, int first, const double *dinv, const double *r, double *d, double *x,
+                     void *stream)
+{
+    if (n < 0 || (n > 0 && (!dinv || !r || !d || !x))) return LMG_ERR_ARG;
+    if (n == 0) return LMG_OK;
+    if (d == x || d == r || d == dinv || x == r || x == dinv) return LMG_ERR_ARG;
+    if (!lmg_aligned16(dinv) || !lmg_aligned16(r) || !lmg_aligned16(d) || !lmg_aligned16(x)) return LMG_ERR_ALIGN;
+    const unsigned grid = grid_for(n, kBlock * 2);
+    if (first)
+        hipLaunchKernelGGL(cheby_update_kernel<true>, dim3(grid), dim3(kBlock), 0, lmg_stream(stream), n, a, c, dinv, r, d, x);
+    else
+        hipLaunchKernelGGL(cheby_update_kernel<false>, dim3(grid), dim3(kBlock), 0, lmg_stream(stream), n, a, c, dinv, r, d, x);
+    LMG_CHECK_LAUNCH();
+    return LMG_OK;
+}
+
+int lmg_csr_gershgorin(int64_t n, const int32_t *rowptr, const int32_t *colidx, const double *vals, double *lmax, void *stream)
+{
+    if (n < 0 || n >= INT32_MAX || !lmax || (n > 0 && (!rowptr || !colidx || !vals))) return LMG_ERR_ARG;
+    if (hipMemsetAsync(lmax, 0, sizeof(double), lmg_stream(stream)) != hipSuccess) return LMG_ERR_LAUNCH;
+    if (n == 0) return LMG_OK;
+    hipLaunchKernelGGL(csr_gershgorin_kernel, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, lmg_stream(stream), n, rowptr, colidx,
+                       vals, reinterpret_cast<unsigned long long *>(lmax));
     LMG_CHECK_LAUNCH();
     return LMG_OK;
 }

@@ -566,6 +566,9 @@ class DistributedVCycle:
     def cycle(self, smoother, steps, omega=1.0, l=0, x_is_zero=False):
         """One V-cycle from level l down.  Returns the number of ghost layers on which this level's
         iterate is exact afterwards (what the caller may prolongate from without a message)."""
+        if smoother == "Chebyshev":
+            raise ValueError("the distributed V-cycle does not run the Chebyshev smoother (single-GPU hierarchies only); "
+                             "use 'Jacobi' or 'GaussSeidel'")
         if smoother not in ("Jacobi", "GaussSeidel"):
             raise ValueError("the distributed V-cycle supports the smoothers 'Jacobi' and 'GaussSeidel' "
                              "(processor-block Gauss-Seidel), not %r" % (smoother,))
@@ -688,6 +691,10 @@ class DistributedVCycle:
         messages of the distributed levels are launched eagerly -- capturing each of them was measured at world size 1
         (2049^2: 0.592 ms with segment graphs vs 0.576 eager) and dropped, RCCL point-to-point inside a captured graph has
         not been tried on this pool."""
+        if smoother == "Chebyshev":                   # (now, not at the first step)
+            raise ValueError("the distributed V-cycle does not run the Chebyshev smoother (single-GPU hierarchies only); "
+                             "use 'Jacobi' or 'GaussSeidel'")
+
         def step():
             self.cycle(smoother, steps, omega)
         return step

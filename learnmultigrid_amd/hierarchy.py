@@ -47,6 +47,34 @@ def cycle_children(shape):
     return _CHILDREN[shape]
 
 
+def chebyshev_coefficients(lmax, ratio, degree):
+    """The (a_k, c_k), k = 0 .. degree - 1, of one Chebyshev smoothing step on [lmax / ratio, lmax] for D^-1 A:
+        d_k = a_k d_(k-1) + c_k D^-1 (b - A x_k),   x_(k+1) = x_k + d_k,
+    the three-term recurrence of the shifted and scaled Chebyshev polynomial (error polynomial of one step:
+    T_S((theta - lambda) / delta) / T_S(sigma)), in Python floats."""
+    lmax, ratio, degree = float(lmax), float(ratio), int(degree)
+    if not (ratio > 1.0 and math.isfinite(ratio)):
+        raise ValueError("cheby_ratio must be a finite number > 1 (lambda_min = lambda_max / cheby_ratio), got %r" % (ratio,))
+    if not (lmax > 0.0 and math.isfinite(lmax)):
+        raise ValueError("the Chebyshev smoother needs a finite bound lambda_max > 0 for D^-1 A, got %r" % (lmax,))
+    if degree < 1:
+        raise ValueError("the Chebyshev smoother needs a degree (smooth_steps) >= 1, got %r" % (degree,))
+    lmin = lmax / ratio
+    theta = (lmax + lmin) / 2
+    delta = (lmax - lmin) / 2
+    sigma = theta / delta
+    rho = 1 / sigma
+    coef = [(0.0, 1 / theta)]
+    for _ in range(1, degree):
+        rho_k = 1 / (2 * sigma - rho)
+        coef.append((rho_k * rho, 2 * rho_k / delta))
+        rho = rho_k
+    return coef
+
+
+CHEBY_RATIO = 4.0       # lambda_max / lambda_min: the oscillatory modes of D^-1 A under full coarsening in two dimensions
+
+
 def _directions(sweep):
     return ("forward", "backward") if sweep == "symmetric" else (sweep,)
 
@@ -63,7 +91,7 @@ def _to_csr_host(M):
 
 class Level:
     __slots__ = ("n", "A", "P", "R", "x", "b", "r", "tmp", "plan_RA", "plan_RAP", "RA",
-                 "gs_sched", "host_pattern", "dinv", "M", "plan_RM", "plan_RMP", "RM")
+                 "gs_sched", "host_pattern", "dinv", "M", "plan_RM", "plan_RMP", "RM", "d")
 
     def __init__(self, A):
         self.n = A.shape[0]
@@ -78,6 +106,7 @@ class Level:
         self.gs_sched = {}
         self.host_pattern = None
         self.dinv = None
+        self.d = None                  # Chebyshev smoother: the step vector of the two-launch path (prepare_smoother)
         self.M = None                  # mass matrix of the level (optional, see Hierarchy(mass=...))
         self.plan_RM = self.plan_RMP = self.RM = None
 
@@ -146,6 +175,7 @@ class Hierarchy:
         self.norm2 = torch.zeros(1, dtype=F64, device=self.device)
         self._factor_coarsest()
         self._graphs = {}
+        self._cheby = None             # Chebyshev smoother: bounds and coefficient tables (prepare_smoother)
 
     # ------------------------------------------------------------------ setup ----------
     @property
@@ -220,8 +250,59 @@ class Hierarchy:
             for lev in self.levels:
                 lev.A.repack_values()            # same pattern: only the value streams change
         self._inverse_diagonals()
+        if self.levels[0].dinv is not None:          # (made on first use by a smoother that needs it: follows the values too)
+            self.levels[0].dinv = self.ops.csr_inverse_diagonal(self.levels[0].A)
         self._factor_coarsest()
         self._graphs = {}
+        if self._cheby is not None:                  # new values: new bounds, new tables
+            lmax_arg, ratio = self._cheby["args"]
+            self._cheby = None
+            self._prepare_chebyshev(lmax_arg, ratio)
+
+    # ------------------------------------------------------------------ Chebyshev ------
+    def _prepare_chebyshev(self, cheby_lmax=None, cheby_ratio=None):
+        """Bounds [lmax / ratio, lmax] of D^-1 A on every smoothed level, the inverse diagonals and the step vectors of
+        the two-launch path.  cheby_lmax: None = the Gershgorin bound of each level (one small launch and one 8-byte
+        read per level), a float for all levels, or one value per smoothed level.  Both None: keep what is prepared."""
+        if self._cheby is not None and cheby_lmax is None and cheby_ratio is None:
+            return
+        ratio = CHEBY_RATIO if cheby_ratio is None else float(cheby_ratio)
+        chebyshev_coefficients(1.0, ratio, 1)                     # (checks the ratio)
+        nl = len(self.levels) - 1
+        if cheby_lmax is None or isinstance(cheby_lmax, (int, float)):
+            given = [cheby_lmax] * nl
+        else:
+            given = list(cheby_lmax)
+            if len(given) != nl:
+                raise ValueError("cheby_lmax needs one value per smoothed level (%d), got %d" % (nl, len(given)))
+        args = (None if cheby_lmax is None else tuple(float(v) for v in given), ratio)
+        if self._cheby is not None and self._cheby["args"] == args:
+            return
+        lmax = []
+        for lev, g in zip(self.levels[:-1], given):
+            if g is None:
+                self.ops.csr_gershgorin(lev.A, self.norm2)
+                g = float(self.norm2.item())
+            chebyshev_coefficients(g, ratio, 1)                   # (checks the bound)
+            lmax.append(float(g))
+            if lev.dinv is None:
+                lev.dinv = self.ops.csr_inverse_diagonal(lev.A)
+            if lev.d is None:
+                lev.d = torch.zeros(lev.n, dtype=F64, device=self.device)
+        self._cheby = {"args": args, "lmax": lmax, "ratio": ratio, "coef": {}}
+
+    def cheby_key(self):
+        """What a captured Chebyshev cycle depends on besides the cycle's own arguments: the bounds in use."""
+        return None if self._cheby is None else (tuple(self._cheby["lmax"]), self._cheby["ratio"])
+
+    def _cheby_coef(self, l, degree):
+        ch = self._cheby
+        if ch is None:
+            raise RuntimeError("Chebyshev smoother used before prepare_smoother")
+        key = (l, degree)
+        if key not in ch["coef"]:
+            ch["coef"][key] = chebyshev_coefficients(ch["lmax"][l], ch["ratio"], degree)
+        return ch["coef"][key]
 
     def rebuild_mass_numeric(self, new_vals):
         """New values of the fine mass matrix on the same pattern: numeric SpGEMM passes only."""
@@ -295,6 +376,15 @@ class Hierarchy:
             for _ in range(steps):
                 self.ops.csr_jacobi(lev.A, lev.x, lev.b, omega, lev.tmp)
                 lev.x, lev.tmp = lev.tmp, lev.x
+        elif smoother == "Chebyshev":
+            # one step of degree `steps`, two launches per sweep: r = b - A x, then d = a d + c D^-1 r, x += d (in place)
+            for k, (a, c) in enumerate(self._cheby_coef(l, steps)):
+                if k == 0 and x_is_zero:
+                    self.ops.zero(lev.x)
+                    self.ops.cheby_update(a, c, lev.dinv, lev.b, lev.d, lev.x, first=True)     # b - A 0 = b
+                else:
+                    self.ops.csr_residual_norm2(lev.A, lev.x, lev.b, lev.r, None, None)
+                    self.ops.cheby_update(a, c, lev.dinv, lev.r, lev.d, lev.x, first=(k == 0))
         else:
             raise ValueError("unknown smoother %r" % (smoother,))
 
@@ -318,15 +408,35 @@ class Hierarchy:
         return avail(self.levels[l].A) if direction == "forward" else avail(self.levels[l].A, direction)
 
     def _fusable(self, l, smoother, steps):
+        if smoother == "Chebyshev":
+            # one step is one pass: d is never carried between launches
+            avail = getattr(self.ops, "stencil_cheby_available", None)
+            return (avail is not None and 1 <= steps <= self.ops.FUSED_MAX_SWEEPS and avail(self.levels[l].A))
         avail = getattr(self.ops, "stencil_smooth_available", None)
         return (smoother == "Jacobi" and steps >= 1 and avail is not None and avail(self.levels[l].A))
 
-    def smooth_fused(self, l, steps, omega, x_is_zero=False, want_residual=False, correction=None, restrict_to=None):
+    def _transfer_avail(self, smoother, which):
+        """The ops predicate that says whether `which` ("prolong" | "restrict") folds into the fused pass of `smoother`."""
+        return getattr(self.ops, "stencil_%s_%s_available" % ("cheby" if smoother == "Chebyshev" else "smooth", which), None)
+
+    def smooth_fused(self, l, steps, omega, x_is_zero=False, want_residual=False, correction=None, restrict_to=None,
+                     smoother="Jacobi"):
         """`steps` Jacobi sweeps on level l (and r = b - A x afterwards) as fused passes of at most
         FUSED_MAX_SWEEPS sweeps each (lmg_stencil_smooth): same bits as smooth() + the residual launch,
         a third of the passes over the level's vectors.  correction = (P, e): the first pass starts from
         x + P e (Multigrid.py:115 folded in; the caller has checked stencil_smooth_prolong_available)."""
         lev = self.levels[l]
+        if smoother == "Chebyshev":
+            # one step of degree `steps` (<= FUSED_MAX_SWEEPS, see _fusable) as one tiled pass
+            kw = {}
+            if correction is not None:
+                kw["prolong"] = correction
+            elif restrict_to is not None:
+                kw["restrict"] = restrict_to
+            self.ops.stencil_cheby(lev.A, None if x_is_zero else lev.x, lev.b, self._cheby_coef(l, steps), lev.tmp,
+                                   lev.r if (want_residual and restrict_to is None) else None, **kw)
+            lev.x, lev.tmp = lev.tmp, lev.x
+            return
         left = steps
         mx = self.ops.FUSED_MAX_SWEEPS
         while left > 0:
@@ -357,7 +467,8 @@ class Hierarchy:
                 self.ops.axpby(1.0, lev.tmp, 1.0, lev.x)
 
     def cycle(self, smoother, steps, omega=1.0, gs_mode="lexicographic", l=0, depth=None,
-              after_presmooth=None, x_is_zero=False, gs_sweep=("forward", "forward"), shape="V"):
+              after_presmooth=None, x_is_zero=False, gs_sweep=("forward", "forward"), shape="V", *,
+              cheby_lmax=None, cheby_ratio=None):
         """One V(steps, steps) cycle on level l: levels[l].x is the iterate, levels[l].b the
         right-hand side (Multigrid.py:77-124).  depth = number of grids used.
         gs_sweep: directions of the Gauss-Seidel pre- and post-smoothing, a pyamg sweep name for both or a (pre, post)
@@ -368,8 +479,15 @@ class Hierarchy:
         second-coarsest -- one V-cycle, two W-cycles, or an F-cycle then a V-cycle on the next level, the second visit
         starting from the first one's iterate with the same right-hand side; the coarsest level is solved once per
         visit of the level above it.  Where a level runs the tiled Jacobi passes, the post-smoothing of one visit and
-        the pre-smoothing of the next run as one turnaround pass (ops.stencil_smooth_turnaround)."""
+        the pre-smoothing of the next run as one turnaround pass (ops.stencil_smooth_turnaround).
+        smoother "Chebyshev": `steps` is the DEGREE of the one polynomial smoothing step run before and after the coarse
+        correction, on [lmax / cheby_ratio, lmax] of D^-1 A per level (omega is not used).  cheby_lmax / cheby_ratio as in
+        prepare_smoother; left None they are what was prepared (the Gershgorin bounds and CHEBY_RATIO by default)."""
         children = cycle_children(shape)
+        if smoother == "Chebyshev":
+            if steps < 1:
+                raise ValueError("the Chebyshev smoother needs smooth_steps >= 1 (the degree), got %r" % (steps,))
+            self._prepare_chebyshev(cheby_lmax, cheby_ratio)
         self._visit(smoother, steps, omega, gs_mode, l, (len(self.levels) if depth is None else depth) - 1, children,
                     gs_sweep_pair(gs_sweep), x_is_zero, after_presmooth)
 
@@ -400,15 +518,15 @@ class Hierarchy:
         """Pre-smoothing of level l, residual, b_(l+1) = R r (Multigrid.py:88-93)."""
         lev, nxt = self.levels[l], self.levels[l + 1]
         fused = self._fusable(l, smoother, steps)
-        ravail = getattr(self.ops, "stencil_smooth_restrict_available", None)
+        ravail = self._transfer_avail(smoother, "restrict")
         restricted = False
         if fused and ravail is not None and ravail(lev.A, lev.R):
-            self.smooth_fused(l, steps, omega, x_is_zero, restrict_to=(lev.R, nxt.b))   # :88 + :90 + :93 in one pass
+            self.smooth_fused(l, steps, omega, x_is_zero, restrict_to=(lev.R, nxt.b), smoother=smoother)   # :88 + :90 + :93 in one pass
             restricted = True
             if after_presmooth is not None:
                 after_presmooth(lev.x)
         elif fused:
-            self.smooth_fused(l, steps, omega, x_is_zero, want_residual=True)  # :88 + :90 in one pass
+            self.smooth_fused(l, steps, omega, x_is_zero, want_residual=True, smoother=smoother)  # :88 + :90 in one pass
             if after_presmooth is not None:
                 after_presmooth(lev.x)
         else:
@@ -423,20 +541,21 @@ class Hierarchy:
         """x += P x_(l+1), post-smoothing of level l (Multigrid.py:115-121)."""
         lev, nxt = self.levels[l], self.levels[l + 1]
         fused = self._fusable(l, smoother, steps)
-        pavail = getattr(self.ops, "stencil_smooth_prolong_available", None)
+        pavail = self._transfer_avail(smoother, "prolong")
         if fused and pavail is not None and pavail(lev.A, lev.P):
-            self.smooth_fused(l, steps, omega, correction=(lev.P, nxt.x))     # :115 + :121 in one pass
+            self.smooth_fused(l, steps, omega, correction=(lev.P, nxt.x), smoother=smoother)     # :115 + :121 in one pass
             return
         self.ops.csr_spmv(lev.P, nxt.x, lev.x, 1.0, 1.0)                           # :115
         if fused:
-            self.smooth_fused(l, steps, omega)                                # :121
+            self.smooth_fused(l, steps, omega, smoother=smoother)             # :121
         else:
             self.smooth(l, smoother, steps, omega, gs_mode, direction=post)       # :121
 
     def _turnaround_ok(self, l, smoother, steps):
         avail = getattr(self.ops, "stencil_smooth_turnaround_selected", None)
         lev = self.levels[l]
-        return (avail is not None and steps <= self.ops.FUSED_MAX_SWEEPS and self._fusable(l, smoother, steps)
+        # (Jacobi only: the Chebyshev step has no turnaround pass -- its post- and pre-passes stay separate)
+        return (avail is not None and smoother == "Jacobi" and steps <= self.ops.FUSED_MAX_SWEEPS and self._fusable(l, smoother, steps)
                 and avail(lev.A, lev.P, lev.R))
 
     def _turnaround(self, l, steps, omega):
@@ -464,10 +583,18 @@ class Hierarchy:
         for lev in self.levels[:-1]:
             chk(lev.A)
 
-    def prepare_smoother(self, smoother, gs_mode="lexicographic", l_from=0, gs_sweep=("forward", "forward")):
+    def prepare_smoother(self, smoother, gs_mode="lexicographic", l_from=0, gs_sweep=("forward", "forward"), *,
+                         cheby_lmax=None, cheby_ratio=None):
         """Everything a Gauss-Seidel cycle would otherwise do lazily on its first sweep -- the wavefront kernel's eligibility
         test (a device -> host read) and work buffer, the level schedules -- from level l_from down, for every direction
-        gs_sweep uses: nothing of it may happen while a hipGraph is being captured."""
+        gs_sweep uses: nothing of it may happen while a hipGraph is being captured.
+        Chebyshev: the bound lmax of D^-1 A per level -- cheby_lmax: None = its Gershgorin bound max_i sum_j |a_ij| / |a_ii|
+        (never below the true lambda_max: no safety factor, the step cannot diverge), a float, or one value per smoothed
+        level -- and lambda_min = lmax / cheby_ratio (default CHEBY_RATIO); the coefficient tables follow from them on the
+        host.  rebuild_numeric() renews both."""
+        if smoother == "Chebyshev":
+            self._prepare_chebyshev(cheby_lmax, cheby_ratio)
+            return
         if smoother != "GaussSeidel":
             return
         dirs = []
@@ -480,12 +607,15 @@ class Hierarchy:
                 else:
                     self.gs_schedule(l, gs_mode, d)
 
-    def captured_cycle(self, smoother, steps, omega, gs_mode, gs_sweep=("forward", "forward"), shape="V"):
+    def captured_cycle(self, smoother, steps, omega, gs_mode, gs_sweep=("forward", "forward"), shape="V", *,
+                       cheby_lmax=None, cheby_ratio=None):
         """The same launch sequence as cycle(), captured once into a hipGraph and replayed (one graph per sweep pair and
         cycle shape)."""
         pair = gs_sweep_pair(gs_sweep)
         cycle_children(shape)
-        key = (smoother, steps, omega, gs_mode, pair, shape)
+        if smoother == "Chebyshev":                 # (before the key: the bounds in use are part of it)
+            self.prepare_smoother(smoother, cheby_lmax=cheby_lmax, cheby_ratio=cheby_ratio)
+        key = (smoother, steps, omega, gs_mode, pair, shape) + ((self.cheby_key(),) if smoother == "Chebyshev" else ())
         g = self._graphs.get(key)
         if g is None:
             self.prepare_smoother(smoother, gs_mode, gs_sweep=pair)
@@ -507,7 +637,7 @@ class Hierarchy:
     def memory_bytes(self):
         tot = 0
         for lev in self.levels:
-            tot += lev.A.bytes() + 4 * 8 * lev.n
+            tot += lev.A.bytes() + (4 + (lev.d is not None)) * 8 * lev.n
             for M in (lev.P, lev.R, lev.RA):
                 if M is not None:
                     tot += M.bytes()

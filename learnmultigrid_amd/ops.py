@@ -1065,6 +1065,111 @@ def stencil_smooth_turnaround(A, x_in, b, omega, sweeps_post, sweeps_pre, x_out,
         *TR.c_args(bc)[2:], _s(S.pid)), "lmg_stencil_smooth_tiled_turnaround")
 
 
+# ---- Chebyshev polynomial smoother (hierarchy.py: smoother="Chebyshev") -------------------------------------------------
+# One smoothing step of degree S is S sweeps d = a_k d + c_k D^-1 (b - A x), x += d; `coef` = [(a_0, c_0), ...] is the
+# host's table (hierarchy.chebyshev_coefficients).  Levels with a stencil or DIA twin run a step of degree <= 3 as ONE tiled
+# pass (lmg_stencil_cheby_tiled*, lmg_dia_cheby), every other format -- and every degree above 3 -- as the residual launch
+# plus cheby_update per sweep.  The register-marching pass has no Chebyshev variant: levels from FUSED_MIN_ROWS rows on
+# run the tiled pass too, up to CHEBY_TILED_MAX_ROWS rows (the two-launch path beyond; see DESIGN.md for the 4097^2 times).
+CHEBY_TILED_MAX_ROWS = (1 << 31) - 4096 - 1
+
+
+def _cheby_kind(A):
+    """'tile' (stencil_tile.hip), 'dia' (dia_tile.hip) or None: how stencil_cheby would run on A."""
+    S = getattr(A, "stencil", None)
+    D = getattr(A, "dia", None)
+    if S is None and D is not None and _PACKED_ENABLED and _DIA_ENABLED and _FUSED_ENABLED:
+        return "dia"
+    if not (_PACKED_ENABLED and _STENCIL_ENABLED and _FUSED_ENABLED and _TILED_ENABLED and S is not None):
+        return None
+    if (TILED_MIN_ROWS <= S.n <= CHEBY_TILED_MAX_ROWS and S.W >= 3
+            and _lib.lib().lmg_stencil_smooth_tiled_supported(S.umask)):
+        return "tile"
+    return None
+
+
+def stencil_cheby_available(A):
+    """True when `A` has a stencil or DIA twin on which stencil_cheby runs a Chebyshev step as one pass."""
+    return _cheby_kind(A) is not None
+
+
+def stencil_cheby_prolong_available(A, P):
+    """True when stencil_cheby can take `prolong=(P, e)` (the rule of the tiled Jacobi pass: always where it can)."""
+    T = getattr(P, "prolong", None)
+    S = getattr(A, "stencil", None)
+    return bool(_FUSED_PROLONG_ENABLED and T is not None and _cheby_kind(A) == "tile" and T.n == S.n and T.W == S.W)
+
+
+def stencil_cheby_restrict_available(A, R):
+    """True when stencil_cheby can take `restrict=(R, b_coarse)` (the rule of the tiled Jacobi pass)."""
+    T = getattr(R, "restrict", None)
+    S = getattr(A, "stencil", None)
+    if not (_FUSED_RESTRICT_ENABLED and T is not None and _cheby_kind(A) == "tile" and T.n == S.n and T.W == S.W):
+        return False
+    if S.n > TILED_RESTRICT_MAX_ROWS:
+        return False
+    lines = (S.n + S.W - 1) // S.W
+    return T.nc >= ((lines + 1) // 2 - 1) * T.Wc + (S.W + 1) // 2
+
+
+def _cheby_coef(coef):
+    flat = [float(v) for pair in coef for v in pair]
+    if not 1 <= len(coef) <= FUSED_MAX_SWEEPS or len(flat) != 2 * len(coef):
+        raise LmgError("stencil_cheby takes 1..%d (a_k, c_k) pairs, got %r" % (FUSED_MAX_SWEEPS, coef))
+    return (ctypes.c_double * len(flat))(*flat)
+
+
+def stencil_cheby(A, x_in, b, coef, x_out, r_out=None, prolong=None, restrict=None):
+    """x_out = one Chebyshev step of degree len(coef) (1..3) from x_in (None = zero iterate), r_out = b - A x_out
+    (optional), in one tiled pass; same bits as csr_residual_norm2 + cheby_update per sweep.  prolong = (P, e) and
+    restrict = (R, b_coarse) as in stencil_smooth (stencil twins only; see stencil_cheby_*_available)."""
+    _vec_ok(x_in, b, x_out, r_out)
+    kind = _cheby_kind(A)
+    hc = _cheby_coef(coef)
+    head = (len(coef), ctypes.addressof(hc), _p(x_in), _p(b), _p(x_out))
+    if kind == "dia":
+        D = A.dia
+        if prolong is not None or restrict is not None:
+            raise LmgError("stencil_cheby: transfers cannot be fused into the pass of a variable-coefficient operator")
+        check(_lib.lib().lmg_dia_cheby(D.n, D.W, D.umask, _p(D.dia), *head, _p(r_out), _s(D.dia)), "lmg_dia_cheby")
+        return
+    if kind != "tile":
+        raise LmgError("stencil_cheby needs a level that runs the tiled passes (stencil_cheby_available)")
+    S = A.stencil
+    if restrict is not None:
+        R, bc = restrict
+        T = R.restrict
+        _vec_ok(bc)
+        if T is None or r_out is not None or prolong is not None or T.n != S.n or T.W != S.W or bc.numel() != T.nc:
+            raise LmgError("stencil_cheby: this restriction cannot be fused into the pass")
+        name, tail = "lmg_stencil_cheby_tiled_restrict", T.c_args(bc)
+    elif prolong is not None:
+        P, e = prolong
+        T = P.prolong
+        _vec_ok(e)
+        if T is None or r_out is not None or x_in is None or T.n != S.n or T.W != S.W or e.numel() != T.nc:
+            raise LmgError("stencil_cheby: this prolongation cannot be fused into the pass")
+        name, tail = "lmg_stencil_cheby_tiled_prolong", T.c_args(e)
+    else:
+        name, tail = "lmg_stencil_cheby_tiled", (_p(r_out),)
+    check(getattr(_lib.lib(), name)(*S.c_args(), *head, *tail, _s(S.pid)), name)
+
+
+def cheby_update(a, c, dinv, r, d, x, first=False):
+    """d = a * d + c * (dinv * r) (first: d = c * (dinv * r), d is not read); x += d -- the Chebyshev sweep after a
+    residual launch (lmg_cheby_update)."""
+    _vec_ok(dinv, r, d, x)
+    check(_lib.lib().lmg_cheby_update(x.numel(), float(a), float(c), int(bool(first)), _p(dinv), _p(r), _p(d), _p(x), _s(x)),
+          "lmg_cheby_update")
+
+
+def csr_gershgorin(A, out):
+    """out[0] = max_i (sum_j |a_ij|) / |a_ii|, the Gershgorin bound of the spectrum of D^-1 A (lmg_csr_gershgorin)."""
+    _vec_ok(out)
+    check(_lib.lib().lmg_csr_gershgorin(A.shape[0], _p(A.rowptr), _p(A.colidx), _p(A.vals), _p(out), _s(A.rowptr)),
+          "lmg_csr_gershgorin")
+
+
 def _use_stencil(A, *vecs):
     if not (_PACKED_ENABLED and _STENCIL_ENABLED and A.stencil is not None):
         return False
@@ -1735,6 +1840,10 @@ def register_torch_ops():
     lib.define("operator_spmv(int handle, Tensor x) -> Tensor")
     lib.define("operator_residual(int handle, Tensor x, Tensor b) -> (Tensor, Tensor)")
     lib.define("operator_jacobi(int handle, Tensor x, Tensor b, float omega, int sweeps) -> Tensor")
+    lib.define("operator_chebyshev(int handle, Tensor x, Tensor b, int degree, float lmax, float ratio) -> Tensor")
+    lib.define("operator_gershgorin(int handle) -> Tensor")
+    lib.define("cheby_update_(float a, float c, bool first, Tensor dinv, Tensor r, Tensor(a!) d, Tensor(b!) x) -> ()")
+    lib.define("csr_gershgorin(Tensor rowptr, Tensor colidx, Tensor vals) -> Tensor")
     lib.define("operator_gauss_seidel_(int handle, Tensor(a!) x, Tensor b, int sweeps) -> ()")
     lib.define("operator_gauss_seidel_backward_(int handle, Tensor(a!) x, Tensor b, int sweeps) -> ()")
 
@@ -1808,6 +1917,38 @@ def register_torch_ops():
                 cur = out
         return cur if sweeps > 0 else x.clone()
 
+    def op_gershgorin(rowptr, colidx, vals):
+        out = torch.empty(1, dtype=F64, device=vals.device)
+        csr_gershgorin(_csr(rowptr, colidx, vals, rowptr.numel() - 1), out)
+        return out
+
+    def op_h_gershgorin(h):
+        A = _get(h)["A"]
+        return op_gershgorin(A.rowptr, A.colidx, A.vals)
+
+    def op_cheby_update_(a, c, first, dinv, r, d, x):
+        cheby_update(a, c, dinv, r, d, x, first)
+
+    def op_h_chebyshev(h, x, b, degree, lmax, ratio):
+        """One Chebyshev step of `degree` on [lmax / ratio, lmax] (lmax <= 0: the Gershgorin bound)."""
+        from .hierarchy import chebyshev_coefficients
+        ent = _get(h)
+        A = ent["A"]
+        if lmax <= 0.0:
+            lmax = float(op_h_gershgorin(h).item())
+        coef = chebyshev_coefficients(lmax, ratio, int(degree))
+        if stencil_cheby_available(A) and len(coef) <= FUSED_MAX_SWEEPS:
+            out = torch.empty_like(x)
+            stencil_cheby(A, x, b, coef, out)
+            return out
+        if ent.get("dinv") is None:
+            ent["dinv"] = csr_inverse_diagonal(A)
+        out, r, d = x.clone(), torch.empty_like(x), torch.empty_like(x)
+        for k, (a, c) in enumerate(coef):
+            csr_residual_norm2(A, out, b, r, None, None)
+            cheby_update(a, c, ent["dinv"], r, d, out, first=(k == 0))
+        return out
+
     def op_h_gs_(h, x, b, sweeps):
         ent = _get(h)
         A = ent["A"]
@@ -1846,6 +1987,10 @@ def register_torch_ops():
     lib.impl("operator_spmv", op_h_spmv, "CUDA")
     lib.impl("operator_residual", op_h_residual, "CUDA")
     lib.impl("operator_jacobi", op_h_jacobi, "CUDA")
+    lib.impl("operator_chebyshev", op_h_chebyshev, "CUDA")
+    lib.impl("operator_gershgorin", op_h_gershgorin, "CompositeExplicitAutograd")
+    lib.impl("cheby_update_", op_cheby_update_, "CUDA")
+    lib.impl("csr_gershgorin", op_gershgorin, "CUDA")
     lib.impl("operator_gauss_seidel_", op_h_gs_, "CUDA")
     lib.impl("operator_gauss_seidel_backward_", op_h_gs_backward_, "CUDA")
     register_torch_ops._lib = lib        # keep alive

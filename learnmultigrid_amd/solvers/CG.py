@@ -11,7 +11,10 @@ nu forward Gauss-Seidel sweeps before and nu backward sweeps after the coarse co
 with R = P^T, Galerkin coarse operators and the direct coarse solve that cycle is a symmetric
 operator, the standard MG-PCG setup (each half is one pipelined launch of the wavefront kernel).
 precond_cycle_shape="W" applies one W-cycle instead (Hierarchy.cycle); it is as symmetric as the V-cycle.  An F-cycle
-is not (its second visits are V-cycles: the F-cycle's adjoint would run them first) and is rejected."""
+is not (its second visits are V-cycles: the F-cycle's adjoint would run them first) and is rejected.
+precond_smoother="Chebyshev" smooths with one Chebyshev polynomial step of degree precond_steps on either side: a polynomial
+in D^-1 A applied to D^-1 is a symmetric operator, so the cycle is one too -- as parallel as the Jacobi cycle, no damping
+parameter (precond_omega is not used; bounds as prepared on the hierarchy, Hierarchy.prepare_smoother)."""
 import math
 
 import numpy as np
@@ -32,8 +35,8 @@ class CG(IterativeSolver):
     @on_device
     def solve(self, max_iterations=1000, error=1e-08, initial_guess=None, *, preconditioner=None,
               precond_steps=2, precond_omega=0.8, precond_smoother="Jacobi", precond_cycle_shape="V"):
-        if precond_smoother not in ("Jacobi", "GaussSeidel"):
-            raise ValueError("precond_smoother must be 'Jacobi' or 'GaussSeidel', got %r" % (precond_smoother,))
+        if precond_smoother not in ("Jacobi", "GaussSeidel", "Chebyshev"):
+            raise ValueError("precond_smoother must be 'Jacobi', 'GaussSeidel' or 'Chebyshev', got %r" % (precond_smoother,))
         if precond_cycle_shape not in ("V", "W"):
             raise ValueError("precond_cycle_shape must be 'V' or 'W' (CG needs a symmetric preconditioner), got %r"
                              % (precond_cycle_shape,))
@@ -51,6 +54,8 @@ class CG(IterativeSolver):
         self.residual = math.sqrt(s.item())
         track = [self.residual]
         H = preconditioner
+        if H is not None and precond_smoother == "Chebyshev":
+            H.prepare_smoother("Chebyshev")        # bounds and work vectors before the first application
 
         def apply_M(src, dst):
             if H is None:
@@ -61,6 +66,8 @@ class CG(IterativeSolver):
             if precond_smoother == "GaussSeidel":
                 H.cycle("GaussSeidel", precond_steps, 1.0, x_is_zero=True, gs_sweep=("forward", "backward"),
                         shape=precond_cycle_shape)
+            elif precond_smoother == "Chebyshev":
+                H.cycle("Chebyshev", precond_steps, 1.0, x_is_zero=True, shape=precond_cycle_shape)
             else:
                 H.cycle("Jacobi", precond_steps, precond_omega, x_is_zero=True, shape=precond_cycle_shape)
             ops.copy(fine.x, dst)

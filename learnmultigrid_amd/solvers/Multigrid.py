@@ -32,6 +32,7 @@ from ..hierarchy import Hierarchy, cycle_children, gs_sweep_pair
 from .Solver import IterativeSolver, on_device
 
 _SMOOTHERS = ("GaussSeidel", "Jacobi", "CG")          # Multigrid.py:149-155
+_EXTRA_SMOOTHERS = ("Chebyshev",)                     # not in the reference: honoured under smoother_semantics="as_named"
 
 
 class Multigrid(IterativeSolver):
@@ -82,8 +83,9 @@ class Multigrid(IterativeSolver):
 
     @staticmethod
     def _effective_smoother(smoother, semantics):
-        if smoother not in _SMOOTHERS:
-            raise ValueError("unknown smoother %r (reference: 'Jacobi', 'GaussSeidel', 'CG')" % (smoother,))
+        if smoother not in _SMOOTHERS + _EXTRA_SMOOTHERS:
+            raise ValueError("unknown smoother %r (reference: 'Jacobi', 'GaussSeidel', 'CG'; this build also: 'Chebyshev')"
+                             % (smoother,))
         if semantics == "as_shipped":
             return "GaussSeidel"
         if semantics != "as_named":
@@ -92,13 +94,28 @@ class Multigrid(IterativeSolver):
             raise ValueError("CG is not a V-cycle smoother in this build (unused by the reference too)")
         return smoother
 
+    @staticmethod
+    def _check_cheby(eff, smooth_steps, cheby_ratio):
+        """The keyword checks of the Chebyshev smoother that need no hierarchy (before any setup work)."""
+        if eff != "Chebyshev":
+            return
+        if smooth_steps < 1:
+            raise ValueError("the Chebyshev smoother needs smooth_steps >= 1 (the degree), got %r" % (smooth_steps,))
+        if cheby_ratio is not None and not float(cheby_ratio) > 1.0:
+            raise ValueError("cheby_ratio must be > 1 (lambda_min = lambda_max / cheby_ratio), got %r" % (cheby_ratio,))
+
     # -- Multigrid.solve (Multigrid.py:36-75) ---------------------------------------------------
     @on_device
     def solve(self, levels=2, smoother="Jacobi", smooth_steps=1, max_iterations=100, error=1e-08,
               initial_guess=None, cycle="V", first_call=False, *, omega=1.0,
               smoother_semantics="as_shipped", gs_mode="lexicographic", coarse_refine="auto",
-              use_graph=False, mutate_initial_guess=False, gs_sweep="forward", cycle_shape="V"):
-        """gs_sweep: direction of the Gauss-Seidel smoothing (also under as_shipped semantics, where Gauss-Seidel always
+              use_graph=False, mutate_initial_guess=False, gs_sweep="forward", cycle_shape="V",
+              cheby_lmax=None, cheby_ratio=None):
+        """smoother="Chebyshev" (under smoother_semantics="as_named"; as shipped the name is ignored like every other): one
+        Chebyshev polynomial smoothing step of degree smooth_steps on D^-1 A before and after the coarse correction, on
+        [lmax / cheby_ratio, lmax] per level.  cheby_lmax: None = each level's Gershgorin bound, a float, or one value per
+        smoothed level; cheby_ratio: None = 4.0 (Hierarchy.prepare_smoother).  omega is not used.
+        gs_sweep: direction of the Gauss-Seidel smoothing (also under as_shipped semantics, where Gauss-Seidel always
         runs) -- a pyamg sweep name ("forward" | "backward" | "symmetric") for pre- and post-smoothing, or a (pre, post)
         pair.  ("forward", "backward") gives a symmetric V-cycle at one pipelined launch per smoothing half; "symmetric"
         costs a launch per direction and step.
@@ -111,9 +128,12 @@ class Multigrid(IterativeSolver):
         eff = self._effective_smoother(smoother, smoother_semantics)
         pair = gs_sweep_pair(gs_sweep)
         cycle_children(cycle_shape)
+        self._check_cheby(eff, smooth_steps, cheby_ratio)
         H = self._setup(levels, first_call, coarse_refine)
         H.stream.wait_stream(torch.cuda.current_stream(self._device))
         with torch.cuda.stream(H.stream):
+            if eff == "Chebyshev":
+                H.prepare_smoother(eff, cheby_lmax=cheby_lmax, cheby_ratio=cheby_ratio)
             self._solve_on_stream(H, eff, smooth_steps, max_iterations, error, initial_guess, omega,
                                   gs_mode, use_graph, mutate_initial_guess, pair, cycle_shape)
         torch.cuda.current_stream(self._device).wait_stream(H.stream)
@@ -163,34 +183,35 @@ class Multigrid(IterativeSolver):
     @on_device
     def v_cycle(self, A, u0, rhs, smoother, smooth_steps, error, levels, first_call=False, *,
                 omega=1.0, smoother_semantics="as_shipped", gs_mode="lexicographic",
-                coarse_refine="auto", gs_sweep="forward"):
+                coarse_refine="auto", gs_sweep="forward", cheby_lmax=None, cheby_ratio=None):
         """One V-cycle on (A, rhs) from u0; returns a fresh (n,1) array.  u0 receives the
-        pre-smoothed iterate like in the reference (:88-89).  gs_sweep as in solve()."""
+        pre-smoothed iterate like in the reference (:88-89).  gs_sweep, cheby_lmax, cheby_ratio as in solve()."""
         return self._one_cycle("V", A, u0, rhs, smoother, smooth_steps, levels, first_call, omega, smoother_semantics,
-                               gs_mode, coarse_refine, gs_sweep)
+                               gs_mode, coarse_refine, gs_sweep, cheby_lmax, cheby_ratio)
 
     @on_device
     def w_cycle(self, A, u0, rhs, smoother, smooth_steps, error, levels, first_call=False, *,
                 omega=1.0, smoother_semantics="as_shipped", gs_mode="lexicographic",
-                coarse_refine="auto", gs_sweep="forward"):
+                coarse_refine="auto", gs_sweep="forward", cheby_lmax=None, cheby_ratio=None):
         """One W-cycle (solve(cycle_shape="W")) with v_cycle's arguments and behaviour."""
         return self._one_cycle("W", A, u0, rhs, smoother, smooth_steps, levels, first_call, omega, smoother_semantics,
-                               gs_mode, coarse_refine, gs_sweep)
+                               gs_mode, coarse_refine, gs_sweep, cheby_lmax, cheby_ratio)
 
     @on_device
     def f_cycle(self, A, u0, rhs, smoother, smooth_steps, error, levels, first_call=False, *,
                 omega=1.0, smoother_semantics="as_shipped", gs_mode="lexicographic",
-                coarse_refine="auto", gs_sweep="forward"):
+                coarse_refine="auto", gs_sweep="forward", cheby_lmax=None, cheby_ratio=None):
         """One F-cycle (solve(cycle_shape="F")) with v_cycle's arguments and behaviour."""
         return self._one_cycle("F", A, u0, rhs, smoother, smooth_steps, levels, first_call, omega, smoother_semantics,
-                               gs_mode, coarse_refine, gs_sweep)
+                               gs_mode, coarse_refine, gs_sweep, cheby_lmax, cheby_ratio)
 
     def _one_cycle(self, shape, A, u0, rhs, smoother, smooth_steps, levels, first_call, omega, smoother_semantics,
-                   gs_mode, coarse_refine, gs_sweep):
+                   gs_mode, coarse_refine, gs_sweep, cheby_lmax=None, cheby_ratio=None):
         if levels < 2:
             raise ValueError("levels must be >= 2")
         eff = self._effective_smoother(smoother, smoother_semantics)
         pair = gs_sweep_pair(gs_sweep)
+        self._check_cheby(eff, smooth_steps, cheby_ratio)
         if A is self.matrix:
             H = self._setup(levels, first_call, coarse_refine)
         else:
@@ -212,6 +233,8 @@ class Multigrid(IterativeSolver):
                 u0a.reshape(-1)[:] = x_dev.cpu().numpy()
         H.stream.wait_stream(torch.cuda.current_stream(self._device))
         with torch.cuda.stream(H.stream):
+            if eff == "Chebyshev":
+                H.prepare_smoother(eff, cheby_lmax=cheby_lmax, cheby_ratio=cheby_ratio)
             H.cycle(eff, smooth_steps, omega, gs_mode, after_presmooth=hook, gs_sweep=pair, shape=shape)
             out = fine.x.cpu().numpy().reshape(n, 1).copy()
             if eff == "GaussSeidel":

@@ -1,0 +1,326 @@
+"""The Chebyshev polynomial smoother without a GPU: the coefficient table against numpy's Chebyshev polynomials, the CPU twin
+(tests/chebyshev_ref.py) against the oracle's Jacobi sweep and dense eigenvalues, Hierarchy.cycle("Chebyshev", ...) on
+the ops shim against the twin's cycles bit for bit, convergence against damped Jacobi, and the solvers' keyword checks."""
+import numpy as np
+import pytest
+import scipy.sparse as sp
+import torch
+from numpy.polynomial import chebyshev as npcheb
+
+import cheby_ops_shim as cshim
+import chebyshev_ref as C
+from conftest import coo_from, load_golden
+from cycle_shapes_ref import ShapeCycle
+from learnmultigrid_amd import problems as P
+from learnmultigrid_amd.hierarchy import CHEBY_RATIO, Hierarchy, chebyshev_coefficients
+from oracle import kernels as K
+
+
+def _np(t):
+    return t.numpy()
+
+
+def _sp(A):
+    return sp.csr_matrix((_np(A.vals), _np(A.colidx), _np(A.rowptr)), shape=A.shape)
+
+
+# ---- coefficient table ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("lmax,ratio", [(2.0, 4.0), (1.0, 4.0), (1.7, 10.0), (2.0, 30.0), (3.5, 1.5), (0.9, 2.0)])
+@pytest.mark.parametrize("degree", [1, 2, 3, 4, 5, 6])
+def test_one_step_is_the_scaled_chebyshev_polynomial(lmax, ratio, degree):
+    """A = diag(lambda_i), b = 0, x = 1: the step leaves T_S((theta - lambda_i) / delta) / T_S(sigma).  (D = I is handed
+    to the twin explicitly: diag(lambda) scaled by its own diagonal would be the identity.)"""
+    lmin = lmax / ratio
+    lam = np.concatenate([np.linspace(lmin, lmax, 41), np.linspace(0.02 * lmax, lmin, 9)])
+    A = sp.diags(lam).tocsr()
+    coef = chebyshev_coefficients(lmax, ratio, degree)
+    assert coef == C.coefficients(lmax, ratio, degree)            # product and twin: the same table, bit for bit
+    got = C.cheby_step(A, np.ones(lam.size), np.zeros(lam.size), coef, dinv=np.ones(lam.size))
+    theta, delta = (lmax + lmin) / 2, (lmax - lmin) / 2
+    T = npcheb.Chebyshev.basis(degree)
+    want = T((theta - lam) / delta) / T(theta / delta)
+    print("degree %d lmax %g ratio %g: max |got - want| = %.3e" % (degree, lmax, ratio, np.abs(got - want).max()))
+    np.testing.assert_allclose(got, want, rtol=0, atol=1e-13)
+    # the min-max property on the target interval
+    assert np.abs(got[:41]).max() <= 1 / T(theta / delta) + 1e-13
+
+
+def test_three_step_factor_of_the_issue():
+    """[lmax / 4, lmax]: degree 3 reaches 1 / T_3(5 / 3) ~ 0.074, three Jacobi sweeps at 0.8 reach 0.6^3 = 0.216."""
+    T3 = npcheb.Chebyshev.basis(3)
+    assert abs(1 / T3(5 / 3) - 0.0740) < 5e-4
+    lam = np.linspace(0.5, 2.0, 301)
+    got = C.cheby_step(sp.diags(lam).tocsr(), np.ones(301), np.zeros(301), chebyshev_coefficients(2.0, 4.0, 3), dinv=np.ones(301))
+    assert abs(np.abs(got).max() - 1 / T3(5 / 3)) < 1e-12
+    assert np.abs((1 - 0.8 * lam) ** 3).max() == pytest.approx(0.216)
+
+
+@pytest.mark.parametrize("bad", [1.0, 0.5, 0.0, -3.0, float("nan"), float("inf")])
+def test_coefficients_reject_bad_ratios(bad):
+    with pytest.raises(ValueError):
+        chebyshev_coefficients(2.0, bad, 3)
+
+
+def test_coefficients_reject_bad_bounds_and_degrees():
+    for lmax in (0.0, -1.0, float("nan"), float("inf")):
+        with pytest.raises(ValueError):
+            chebyshev_coefficients(lmax, 4.0, 3)
+    with pytest.raises(ValueError):
+        chebyshev_coefficients(2.0, 4.0, 0)
+
+
+# ---- twin against the oracle ------------------------------------------------------------------------------------------------
+def _matrices():
+    out = {}
+    A, rhs = P.poisson_2d_structured(16)
+    out["poisson2d"] = (K.as_csr(A), rhs.ravel())
+    A, rhs = P.variable_coeff_poisson_2d_structured(12)
+    out["varcoef"] = (K.as_csr(A), np.asarray(rhs).ravel())
+    A, rhs = P.jittered_poisson_2d(12)
+    out["jittered"] = (K.as_csr(A), np.asarray(rhs).ravel())
+    A, rhs = P.poisson_1d_fd(40)
+    out["poisson1d"] = (K.as_csr(A), np.asarray(rhs).ravel())
+    return out
+
+
+@pytest.mark.parametrize("name", ["poisson2d", "varcoef", "jittered", "poisson1d"])
+def test_degree_one_is_weighted_jacobi_bit_for_bit(name):
+    A, b = _matrices()[name]
+    rng = np.random.default_rng(5)
+    x = rng.standard_normal(A.shape[0])
+    for lmax, ratio in ((2.0, 4.0), (1.9, 7.0), (C.gershgorin(A), 4.0)):
+        (a0, c0), = C.coefficients(lmax, ratio, 1)
+        theta = (lmax + lmax / ratio) / 2
+        assert a0 == 0.0 and c0 == 1 / theta
+        assert np.array_equal(C.cheby_step(A, x, b, [(a0, c0)]), K.jacobi(A, x, b, 1 / theta))
+
+
+def _golden_matrices():
+    out = []
+    for ne in (16, 64, 1024):
+        out.append(("g2_ne%d" % ne, coo_from(load_golden("g2_poisson1d_ne%d" % ne), "A")))
+    for k in (4, 16):
+        g = load_golden("g4_structured2d_k%d" % k)
+        out.append(("g4_k%d" % k, coo_from(g, "A")))
+        out.append(("g4_k%d_free" % k, coo_from(g, "A_free")))
+    g = load_golden("g5_saved_A")
+    shape = tuple(int(s) for s in g["shape"])
+    out.append(("g5", sp.coo_matrix((g["data"], (g["row"], g["col"])), shape=shape).tocsr()))
+    return out
+
+
+@pytest.mark.parametrize("name,A", _golden_matrices(), ids=[n for n, _ in _golden_matrices()])
+def test_gershgorin_twin_bounds_the_spectrum(name, A):
+    A = K.as_csr(A)
+    g = C.gershgorin(A)
+    # the definition, row by row
+    rows = [(np.abs(A[i].data).sum(), A[i, i]) for i in range(min(A.shape[0], 200))]
+    assert g >= max(s / abs(d) for s, d in rows if d != 0) - 1e-15
+    if A.shape[0] <= 400:                                   # small enough for a dense eigen-solve
+        d = A.diagonal()
+        keep = d != 0
+        M = A.toarray()[keep][:, keep] / d[keep][:, None]
+        lam = np.linalg.eigvals(M)
+        print("%s: Gershgorin %.6f, lambda_max(D^-1 A) %.6f" % (name, g, lam.real.max()))
+        # the dense eigen-solve carries its own backward error, O(n eps ||M||): where the bound is attained (the pure
+        # Neumann operator, lambda_max = 2 exactly) it may return 2 + a few ulp
+        slack = A.shape[0] * np.finfo(float).eps * g
+        assert g >= lam.real.max() - slack and g >= np.abs(lam).max() - slack
+
+
+@pytest.mark.parametrize("m", [8, 16, 33, 64])
+def test_gershgorin_of_the_five_point_operator_is_two(m):
+    A, _ = P.poisson_2d_structured(m)
+    assert C.gershgorin(A) == 2.0
+    assert np.array_equal(C.inverse_diagonal(A), _np(cshim.shim.csr_inverse_diagonal(_dev(A))))
+
+
+def _dev(A):
+    from learnmultigrid_amd.ops import DeviceCSR
+    return DeviceCSR.from_scipy(K.as_csr(A), "cpu")
+
+
+# ---- Hierarchy logic on the shim ------------------------------------------------------------------------------------------------
+def _problem(m=32, levels=4):
+    A, rhs = P.poisson_2d_structured(m)
+    return A, rhs, P.geometric_hierarchy_2d(m + 1, levels)
+
+
+def _twin_of(H, **kw):
+    """The twin on H's own level operators and its coarsest-level solver (Hierarchy.coarse_solve's steps)."""
+    last = H.levels[-1]
+
+    def coarse(rc):
+        last.b.copy_(torch.from_numpy(rc.copy()))
+        H.coarse_solve()
+        return last.x.numpy().copy()
+
+    return C.ChebyCycle([_sp(l.A) for l in H.levels], [_sp(l.P) for l in H.levels[:-1]],
+                        [_sp(l.R) for l in H.levels[:-1]], coarse, **kw)
+
+
+def _run(H, rhs, cycles, degree, shape, **kw):
+    H.levels[0].b.copy_(torch.from_numpy(rhs.ravel().copy()))
+    H.ops.zero(H.levels[0].x)
+    norms = []
+    for _ in range(cycles):
+        norms.append(H.residual_norm())
+        H.cycle("Chebyshev", degree, shape=shape, **kw)
+    return np.array(norms), H.levels[0].x.numpy().copy()
+
+
+@pytest.mark.parametrize("shape", ["V", "W", "F"])
+@pytest.mark.parametrize("degree", [1, 3, 5])
+def test_hierarchy_cycle_equals_the_twin(shape, degree):
+    A, rhs, hier = _problem()
+    H = Hierarchy(A, hier, "cpu", ops_mod=cshim.base())
+    got, x = _run(H, rhs, 3, degree, shape)
+    assert H.cheby_key() == ((2.0,) + tuple(C.gershgorin(_sp(l.A)) for l in H.levels[1:-1]), CHEBY_RATIO)
+    want, xw = C.history(_twin_of(H), _sp(H.levels[0].A), rhs, 3, degree=degree, shape=shape)
+    assert np.array_equal(x, xw)
+    np.testing.assert_allclose(got, want, rtol=1e-13, atol=0)
+    assert got[-1] < 0.2 * got[0]
+
+
+@pytest.mark.parametrize("shape", ["V", "W", "F"])
+@pytest.mark.parametrize("degree,max_rows", [(1, None), (3, None), (3, 300), (5, None)])
+def test_fused_passes_keep_the_bits_and_fold_the_transfers(shape, degree, max_rows):
+    A, rhs, hier = _problem()
+    plain, fz = cshim.base(), cshim.fused(max_rows)
+    h0, x0 = _run(Hierarchy(A, hier, "cpu", ops_mod=plain), rhs, 2, degree, shape)
+    h1, x1 = _run(Hierarchy(A, hier, "cpu", ops_mod=fz), rhs, 2, degree, shape)
+    assert np.array_equal(h0, h1) and np.array_equal(x0, x1)
+    if degree > 3:
+        assert not fz.calls                                   # beyond three sweeps: the two-launch path
+        return
+    assert fz.calls and {c[0] for c in fz.calls} == {"prolong", "restrict"}      # every pass carries its transfer
+    assert all(c[2] == degree for c in fz.calls)                                 # one whole step per pass
+    assert any(c[3] for c in fz.calls) and not any(c[3] for c in fz.calls if c[1] == A.shape[0])   # zero iterate: coarse visits
+    if max_rows is not None:
+        assert all(c[1] <= max_rows for c in fz.calls)
+
+
+def test_zero_initial_iterate_visit():
+    A, rhs, hier = _problem()
+    for ops_mod in (cshim.base(), cshim.fused()):
+        H = Hierarchy(A, hier, "cpu", ops_mod=ops_mod)
+        H.levels[0].b.copy_(torch.from_numpy(rhs.ravel().copy()))
+        H.levels[0].x.copy_(torch.full((A.shape[0],), 7.0, dtype=torch.float64))       # must not be read
+        H.cycle("Chebyshev", 3, x_is_zero=True)
+        want = _twin_of(H).cycle(np.zeros(A.shape[0]), rhs.ravel(), degree=3)
+        assert np.array_equal(H.levels[0].x.numpy(), want)
+
+
+def test_overrides_and_rebuild():
+    A, rhs, hier = _problem(16, 3)
+    H = Hierarchy(A, hier, "cpu", ops_mod=cshim.base())
+    H.prepare_smoother("Chebyshev", cheby_lmax=1.9, cheby_ratio=8.0)
+    assert H.cheby_key() == ((1.9, 1.9), 8.0)
+    _, x = _run(H, rhs, 2, 3, "V")                             # None, None: what was prepared
+    _, xw = C.history(_twin_of(H, lmax=[1.9, 1.9], ratio=8.0), _sp(H.levels[0].A), rhs, 2, degree=3)
+    assert np.array_equal(x, xw)
+    _run(H, rhs, 1, 2, "V", cheby_lmax=[2.0, 1.5])
+    assert H.cheby_key() == ((2.0, 1.5), CHEBY_RATIO)      # a keyword that is given resets the other to its default
+    with pytest.raises(ValueError):
+        H.prepare_smoother("Chebyshev", cheby_lmax=[2.0])      # one value per smoothed level
+    with pytest.raises(ValueError):
+        H.prepare_smoother("Chebyshev", cheby_ratio=1.0)
+    with pytest.raises(ValueError):
+        H.cycle("Chebyshev", 0)
+    # new matrix values: the Gershgorin bounds follow.  (Both sets of values are generic: SciPy's product, which stands in
+    # for the SpGEMM here, drops the sums that cancel exactly, so the constant-coefficient pattern would not be kept.)
+    rng = np.random.default_rng(3)
+    base = K.as_csr(A)
+
+    def perturbed():
+        v = base.data.copy()
+        off = v < 0
+        v[off] *= 1.0 + 0.3 * rng.random(int(off.sum()))
+        return v
+
+    A1 = sp.csr_matrix((perturbed(), base.indices.copy(), base.indptr.copy()), shape=base.shape)
+    H = Hierarchy(A1, hier, "cpu", ops_mod=cshim.base())
+    H.prepare_smoother("Chebyshev")
+    before = H.cheby_key()
+    vals = perturbed()
+    H.rebuild_numeric(torch.from_numpy(vals))
+    after = H.cheby_key()
+    assert after != before and after[0] == tuple(C.gershgorin(_sp(l.A)) for l in H.levels[:-1])
+    assert np.array_equal(_np(H.levels[0].dinv), C.inverse_diagonal(_sp(H.levels[0].A)))
+
+
+def test_unknown_smoother_still_raises():
+    A, rhs, hier = _problem(16, 3)
+    H = Hierarchy(A, hier, "cpu", ops_mod=cshim.base())
+    with pytest.raises(ValueError):
+        H.cycle("Tschebyscheff", 3)
+
+
+# ---- convergence ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("m,levels", [(64, 4), (128, 5)])
+def test_chebyshev_needs_no_more_cycles_than_damped_jacobi(m, levels):
+    A, rhs, hier = _problem(m, levels)
+    b = rhs.ravel()
+
+    def count(step):
+        x = np.zeros(A.shape[0])
+        for it in range(1, 101):
+            x = step(x)
+            if np.sqrt(K.residual(A, x, b)[1]) <= 1e-10:
+                return it
+        return 101
+
+    cheb = C.ChebyCycle.galerkin(A, hier)
+    jac = ShapeCycle(A, hier, "V")
+    n_cheb = count(lambda x: cheb.cycle(x, b, degree=3))
+    n_jac = count(lambda x: jac.cycle(x, b, smoother="Jacobi", steps=3, omega=0.8))
+    print("%d^2, %d levels, V(3,3) to 1e-10: Chebyshev %d cycles, Jacobi(0.8) %d cycles" % (m + 1, levels, n_cheb, n_jac))
+    assert n_cheb <= n_jac <= 100
+
+
+# ---- solver keywords -------------------------------------------------------------------------------------------------------------
+def test_solver_keywords():
+    from learnmultigrid_amd.solvers.Multigrid import Multigrid
+    eff = Multigrid._effective_smoother
+    assert eff("Chebyshev", "as_shipped") == "GaussSeidel"        # as shipped, the name is ignored: Gauss-Seidel runs
+    assert eff("Chebyshev", "as_named") == "Chebyshev"
+    with pytest.raises(ValueError):
+        eff("Tschebyscheff", "as_named")
+    for bad in (1.0, 0.3, -2.0):
+        with pytest.raises(ValueError):
+            Multigrid._check_cheby("Chebyshev", 3, bad)
+    with pytest.raises(ValueError):
+        Multigrid._check_cheby("Chebyshev", 0, None)
+    Multigrid._check_cheby("Chebyshev", 3, 4.0)
+    Multigrid._check_cheby("GaussSeidel", 3, 0.5)                 # not the Chebyshev smoother: the keyword is not looked at
+    import inspect
+    for name in ("solve", "v_cycle", "w_cycle", "f_cycle"):
+        sig = inspect.signature(getattr(Multigrid, name))
+        for kw in ("cheby_lmax", "cheby_ratio"):
+            assert sig.parameters[kw].kind is inspect.Parameter.KEYWORD_ONLY and sig.parameters[kw].default is None
+
+
+def test_solve_rejects_bad_ratio_before_any_gpu_work():
+    """solve() checks the keywords first: no device is touched on the way to the error."""
+    from learnmultigrid_amd.solvers import GeometricMG
+    A, rhs = P.poisson_1d_fd(16)
+    mg = GeometricMG.__new__(GeometricMG)
+    with pytest.raises(ValueError, match="cheby_ratio"):
+        GeometricMG.solve.__wrapped__(mg, levels=2, smoother="Chebyshev", smooth_steps=3, smoother_semantics="as_named",
+                                      cheby_ratio=1.0)
+
+
+def test_distributed_cycle_rejects_chebyshev():
+    from learnmultigrid_amd.dist import DistributedVCycle
+    D = DistributedVCycle.__new__(DistributedVCycle)
+    with pytest.raises(ValueError, match="Chebyshev"):
+        D.cycle("Chebyshev", 3)
+    with pytest.raises(ValueError, match="Chebyshev"):
+        D.make_step("Chebyshev", 3, 1.0)
+
+
+def test_cg_accepts_the_name():
+    import inspect
+    from learnmultigrid_amd.solvers.CG import CG
+    src = inspect.getsource(CG.solve)
+    assert '"Chebyshev"' in src
