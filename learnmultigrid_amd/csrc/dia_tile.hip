@@ -250,47 +250,52 @@ int launch4(DArgs a, hipStream_t st)
     return launch5<S, UM, RESID, ZERO, 32, 2, CHEB>(a, st);
 }
 
-template <int S, unsigned UM, bool CHEB = false>
-int launch2(DArgs a, bool resid, bool zero, hipStream_t st)
-{
-    if (resid) return zero ? launch4<S, UM, true, true, CHEB>(a, st) : launch4<S, UM, true, false, CHEB>(a, st);
-    return zero ? launch4<S, UM, false, true, CHEB>(a, st) : launch4<S, UM, false, false, CHEB>(a, st);
-}
-
-template <unsigned UM, bool CHEB = false>
-int launch1(DArgs a, int sweeps, bool resid, bool zero, hipStream_t st)
-{
-    switch (sweeps) {
-    case 1: return launch2<1, UM, CHEB>(a, resid, zero, st);
-    case 2: return launch2<2, UM, CHEB>(a, resid, zero, st);
-    default: return launch2<3, UM, CHEB>(a, resid, zero, st);
-    }
-}
-
-// the operator and the vectors of a pass: the argument rules lmg_dia_smooth and lmg_dia_cheby share.  Returns 1 with `a`
-// set, else the status to hand back (LMG_OK: nothing to do).
-int dia_fill_args(DArgs &a, int64_t n, int32_t line_stride, const double *dia, int sweeps, const double *x_in, const double *b,
-                  double omega, double *x_out, double *r_out)
+// The operator and the vectors of a pass, and the coefficient table of a Chebyshev step (h_coef: as in stencil_tile.hip;
+// null: weighted Jacobi): the argument rules of lmg_dia_smooth and lmg_dia_cheby.  Returns 1 with `a` set, else the
+// status to hand back (LMG_OK: nothing to do).
+int dia_fill_args(DArgs &a, int64_t n, int32_t line_stride, const double *dia, const LmgSolve &v, const double *h_coef)
 {
     if (n < 0 || n >= (1ll << 31) - 4096) return LMG_ERR_ARG;
-    if (sweeps < 1 || sweeps > 3) return LMG_ERR_ARG;
+    if (v.sweeps < 1 || v.sweeps > 3) return LMG_ERR_ARG;
     if (n == 0) return LMG_OK;
-    if (!dia || !b || !x_out || x_in == x_out || r_out == x_out || (r_out && r_out == x_in)) return LMG_ERR_ARG;
+    if (!dia || !v.b || !v.x_out || v.x_in == v.x_out || v.r_out == v.x_out || (v.r_out && v.r_out == v.x_in)) return LMG_ERR_ARG;
     if (line_stride < 3 || line_stride > n) return LMG_ERR_ARG;
     a.n = (int)n;
     a.W = line_stride;
     a.lines = (int)((n + line_stride - 1) / line_stride);
     a.tiles_x = a.tiles_y = 0;
     a.dia = dia;
-    a.x = x_in;
-    a.b = b;
-    a.out = x_out;
-    a.r = r_out;
-    a.omega = omega;
-    for (int k = 0; k < 3; ++k) a.cha[k] = a.chc[k] = 0.0;
+    a.x = v.x_in;
+    a.b = v.b;
+    a.out = v.x_out;
+    a.r = v.r_out;
+    a.omega = v.omega;
+    for (int k = 0; k < 3; ++k) {
+        a.cha[k] = h_coef && k < v.sweeps ? h_coef[2 * k] : 0.0;
+        a.chc[k] = h_coef && k < v.sweeps ? h_coef[2 * k + 1] : 0.0;
+    }
     return 1;
 }
 
+// (slot set, smoother, sweeps, residual, zero iterate) -> template arguments
+int dia_pass(int64_t n, int32_t line_stride, uint32_t union_mask, const double *dia, const LmgSolve &v, const double *h_coef,
+             void *stream)
+{
+    DArgs a;
+    const int rc = dia_fill_args(a, n, line_stride, dia, v, h_coef);
+    if (rc != 1) return rc;
+    return lmg_with_mask<kMask5, kMask7a, kMask7b, kMask9>(union_mask, [&](auto m) {
+        return lmg_with_flag(h_coef != nullptr, [&](auto ch) {
+            return lmg_with_sweeps<1, 3>(v.sweeps, [&](auto s) {
+                return lmg_with_flag(v.r_out != nullptr, [&](auto r) {
+                    return lmg_with_flag(v.x_in == nullptr, [&](auto z) {
+                        return launch4<LMG_CT(s), LMG_CT(m), LMG_CT(r), LMG_CT(z), LMG_CT(ch)>(a, lmg_stream(stream));
+                    });
+                });
+            });
+        });
+    });
+}
 
 }  // namespace
 
@@ -323,40 +328,14 @@ int lmg_dia_fill(int64_t n, int32_t line_stride, const int32_t *rowptr, const in
 int lmg_dia_smooth(int64_t n, int32_t line_stride, uint32_t union_mask, const double *dia, int sweeps, const double *x_in,
                    const double *b, double omega, double *x_out, double *r_out, void *stream)
 {
-    DArgs a;
-    const int rc = dia_fill_args(a, n, line_stride, dia, sweeps, x_in, b, omega, x_out, r_out);
-    if (rc != 1) return rc;
-    hipStream_t st = lmg_stream(stream);
-    const bool resid = r_out != nullptr, zero = x_in == nullptr;
-    switch (union_mask) {
-    case kMask5: return launch1<kMask5>(a, sweeps, resid, zero, st);
-    case kMask7a: return launch1<kMask7a>(a, sweeps, resid, zero, st);
-    case kMask7b: return launch1<kMask7b>(a, sweeps, resid, zero, st);
-    case kMask9: return launch1<kMask9>(a, sweeps, resid, zero, st);
-    default: return LMG_ERR_CAPACITY;
-    }
+    return dia_pass(n, line_stride, union_mask, dia, {sweeps, x_in, b, omega, x_out, r_out}, nullptr, stream);
 }
 
 int lmg_dia_cheby(int64_t n, int32_t line_stride, uint32_t union_mask, const double *dia, int degree, const double *h_coef,
                   const double *x_in, const double *b, double *x_out, double *r_out, void *stream)
 {
     if (degree < 1 || degree > 3 || !h_coef) return LMG_ERR_ARG;
-    DArgs a;
-    const int rc = dia_fill_args(a, n, line_stride, dia, degree, x_in, b, h_coef[1], x_out, r_out);
-    if (rc != 1) return rc;
-    for (int k = 0; k < degree; ++k) {
-        a.cha[k] = h_coef[2 * k];
-        a.chc[k] = h_coef[2 * k + 1];
-    }
-    hipStream_t st = lmg_stream(stream);
-    const bool resid = r_out != nullptr, zero = x_in == nullptr;
-    switch (union_mask) {
-    case kMask5: return launch1<kMask5, true>(a, degree, resid, zero, st);
-    case kMask7a: return launch1<kMask7a, true>(a, degree, resid, zero, st);
-    case kMask7b: return launch1<kMask7b, true>(a, degree, resid, zero, st);
-    case kMask9: return launch1<kMask9, true>(a, degree, resid, zero, st);
-    default: return LMG_ERR_CAPACITY;
-    }
+    return dia_pass(n, line_stride, union_mask, dia, {degree, x_in, b, h_coef[1], x_out, r_out}, h_coef, stream);
 }
 
 }  // extern "C"

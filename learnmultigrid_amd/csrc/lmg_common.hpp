@@ -2,7 +2,7 @@
 // needs has its single definition here -- the sweep modes and their argument rules, XCD-aware tile ownership and the
 // persistent grid that goes with it, the fixed-order sums, the DPP lane shifts, and the 3x3 stencil view (slot masks,
 // pattern-table limit).  The host half at the end is what sits between the C ABI and hipLaunchKernelGGL in more than
-// one file: the rows of the tune-key tables, and the argument checks and sweep-count dispatch of the fused passes.
+// one file: the rows of the tune-key tables, and the one body of a fused-pass entry point (argument groups, checks, dispatch).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <limits.h>
@@ -212,9 +212,18 @@ int lmg_with_flag(bool flag, F &&f)
 {
     return flag ? f(std::true_type{}) : f(std::false_type{});
 }
+// f(std::integral_constant<unsigned, M>) for the M of the list that union_mask equals; LMG_ERR_CAPACITY for a slot set
+// outside the list: nothing is built for it, the caller runs the separate sweeps
+template <unsigned... M, typename F>
+int lmg_with_mask(uint32_t union_mask, F &&f)
+{
+    int rc = LMG_ERR_CAPACITY;
+    (void)((union_mask == M && (rc = f(std::integral_constant<unsigned, M>{}), true)) || ...);
+    return rc;
+}
 #define LMG_CT(c) decltype(c)::value
 
-// ---- argument checks of the fused smoothing passes ------------------------------------------------------------------
+// ---- the fused smoothing passes: argument groups, their checks, and the one body of an entry point ------------------
 // stencil_fused.hip (iterates in registers, MArgs) and stencil_tile.hip (iterates in LDS, TArgs) take the same
 // arguments under the same rules; their argument structs name the shared fields alike, and each says in constexpr
 // members where its rules differ:
@@ -222,6 +231,47 @@ int lmg_with_flag(bool flag, F &&f)
 //     kOneRowIsCapacity    a single row answers LMG_ERR_CAPACITY
 //     kProlMinCoarse, kProlStrideCovers, kProlChecksPairs      (prolongation, below)
 //     kRestCoarseLimit                                         (restriction, below)
+// The groups list their members in the order of the C ABI (include/lmg.h), so an entry point hands its own arguments
+// on in braces.
+struct LmgOperator {
+    int64_t n;
+    int32_t line_stride;
+    const uint8_t *pid;
+    int32_t npat;
+    const double *st_val;
+    const int32_t *st_mask;
+    uint32_t union_mask;
+    int32_t hot_pattern;
+    const double *h_hot_val;
+};
+struct LmgSolve {           // a Chebyshev step: sweeps = its degree, omega = c_0
+    int sweeps;
+    const double *x_in, *b;
+    double omega;
+    double *x_out, *r_out;
+};
+struct LmgProl {
+    int64_t n_coarse;
+    int32_t coarse_stride;
+    const double *e_coarse;
+    const uint8_t *p_pid;
+    int32_t p_npat;
+    const double *p_val;
+    const int32_t *p_mask;
+    const int32_t *h_hot_pairs;
+    const double *h_hot_pval;
+};
+struct LmgRest {
+    int64_t n_coarse;
+    int32_t coarse_stride;
+    double *b_coarse;
+    const uint8_t *r_pid;
+    int32_t r_npat;
+    const double *r_val;
+    const int32_t *r_mask;
+    int32_t hot_r;
+    const double *h_hot_rval;
+};
 
 // a hot pattern the host can hand to a kernel in scalar registers: in the table, with values, and a diagonal to divide by
 static inline bool lmg_hot_usable(int32_t hot_pattern, int32_t npat, const double *h_hot_val)
@@ -232,33 +282,33 @@ static inline bool lmg_hot_usable(int32_t hot_pattern, int32_t npat, const doubl
 // The operator, the vectors and the sweep count.  Returns 1 with everything in `a` set but the fields only one of the
 // structs has (no transfer folded in), else the status to hand back: LMG_OK where there is nothing to do.
 template <typename A>
-int lmg_smooth_fill(A &a, int64_t n, int32_t line_stride, const uint8_t *pid, int32_t npat, const double *st_val,
-                    const int32_t *st_mask, uint32_t union_mask, int32_t hot_pattern, const double *h_hot_val, int sweeps,
-                    const double *x_in, const double *b, double omega, double *x_out, double *r_out)
+int lmg_smooth_fill(A &a, const LmgOperator &op, const LmgSolve &v)
 {
-    if (n < 0 || n >= A::kRowLimit || npat < 1 || npat > kMaxPat || (union_mask & ~kMask9)) return LMG_ERR_ARG;
-    if (sweeps < 1 || sweeps > 3) return LMG_ERR_ARG;
+    const int64_t n = op.n;
+    if (n < 0 || n >= A::kRowLimit || op.npat < 1 || op.npat > kMaxPat || (op.union_mask & ~kMask9)) return LMG_ERR_ARG;
+    if (v.sweeps < 1 || v.sweeps > 3) return LMG_ERR_ARG;
     if (n == 0) return LMG_OK;
     if (A::kOneRowIsCapacity && n < 2) return LMG_ERR_CAPACITY;
-    if (!pid || !st_val || !st_mask || !b || !x_out || x_in == x_out || r_out == x_out || (r_out && r_out == x_in))
+    if (!op.pid || !op.st_val || !op.st_mask || !v.b || !v.x_out || v.x_in == v.x_out || v.r_out == v.x_out ||
+        (v.r_out && v.r_out == v.x_in))
         return LMG_ERR_ARG;
-    if (line_stride < 3 || line_stride > n) return LMG_ERR_ARG;
+    if (op.line_stride < 3 || op.line_stride > n) return LMG_ERR_ARG;
     a.n = (int)n;
-    a.W = line_stride;
-    a.lines = (int)((n + line_stride - 1) / line_stride);
-    a.npat = npat;
-    a.pid = pid;
-    a.st_val = st_val;
-    a.st_mask = st_mask;
-    a.x = x_in;
-    a.b = b;
-    a.out = x_out;
-    a.r = r_out;
-    a.omega = omega;
-    const bool hot = lmg_hot_usable(hot_pattern, npat, h_hot_val);
-    a.hot = hot ? hot_pattern : -1;
-    for (int k = 0; k < 9; ++k) a.hot_val[k] = hot ? h_hot_val[k] : 0.0;
-    a.hot_rdiag = hot ? 1.0 / h_hot_val[4] : 0.0;
+    a.W = op.line_stride;
+    a.lines = (int)((n + op.line_stride - 1) / op.line_stride);
+    a.npat = op.npat;
+    a.pid = op.pid;
+    a.st_val = op.st_val;
+    a.st_mask = op.st_mask;
+    a.x = v.x_in;
+    a.b = v.b;
+    a.out = v.x_out;
+    a.r = v.r_out;
+    a.omega = v.omega;
+    const bool hot = lmg_hot_usable(op.hot_pattern, op.npat, op.h_hot_val);
+    a.hot = hot ? op.hot_pattern : -1;
+    for (int k = 0; k < 9; ++k) a.hot_val[k] = hot ? op.h_hot_val[k] : 0.0;
+    a.hot_rdiag = hot ? 1.0 / op.h_hot_val[4] : 0.0;
     a.ec = nullptr;
     a.nc = a.Wc = 0;
     a.ppid = nullptr;
@@ -282,68 +332,82 @@ int lmg_smooth_fill(A &a, int64_t n, int32_t line_stride, const uint8_t *pid, in
 //     kProlChecksPairs     hot pair ids outside P's table are dropped (-1): tiled pass only; both kernels just compare
 //                          the ids with the ones they load (as found)
 template <typename A>
-int lmg_prol_check(int32_t line_stride, const double *x_in, const double *x_out, int64_t n_coarse, int32_t coarse_stride,
-                   const double *e_coarse, const uint8_t *p_pid, int32_t p_npat, const double *p_val, const int32_t *p_mask)
+int lmg_prol_check(const LmgOperator &op, const LmgSolve &v, const LmgProl &p)
 {
-    if (!x_in || !e_coarse || !p_pid || !p_val || !p_mask || p_npat < 1 || p_npat > kMaxPat) return LMG_ERR_ARG;
-    if (n_coarse < A::kProlMinCoarse || n_coarse >= (1ll << 31) || coarse_stride < 1 || coarse_stride > n_coarse)
+    if (!v.x_in || !p.e_coarse || !p.p_pid || !p.p_val || !p.p_mask || p.p_npat < 1 || p.p_npat > kMaxPat) return LMG_ERR_ARG;
+    if (p.n_coarse < A::kProlMinCoarse || p.n_coarse >= (1ll << 31) || p.coarse_stride < 1 || p.coarse_stride > p.n_coarse)
         return LMG_ERR_ARG;
-    if (e_coarse == x_out) return LMG_ERR_ARG;
-    if (A::kProlStrideCovers && (int64_t)coarse_stride < ((int64_t)line_stride + 1) / 2) return LMG_ERR_ARG;
+    if (p.e_coarse == v.x_out) return LMG_ERR_ARG;
+    if (A::kProlStrideCovers && (int64_t)p.coarse_stride < ((int64_t)op.line_stride + 1) / 2) return LMG_ERR_ARG;
     return LMG_OK;
 }
 template <typename A>
-void lmg_prol_set(A &a, int64_t n_coarse, int32_t coarse_stride, const double *e_coarse, const uint8_t *p_pid, int32_t p_npat,
-                  const double *p_val, const int32_t *p_mask, const int32_t *h_hot_pairs, const double *h_hot_pval)
+void lmg_prol_set(A &a, const LmgProl &p)
 {
-    a.ec = e_coarse;
-    a.nc = (int)n_coarse;
-    a.Wc = coarse_stride;
-    a.ppid = p_pid;
-    a.pp_val = p_val;
-    a.pp_mask = p_mask;
-    a.pp_npat = p_npat;
-    if (h_hot_pairs && h_hot_pval) {
+    a.ec = p.e_coarse;
+    a.nc = (int)p.n_coarse;
+    a.Wc = p.coarse_stride;
+    a.ppid = p.p_pid;
+    a.pp_val = p.p_val;
+    a.pp_mask = p.p_mask;
+    a.pp_npat = p.p_npat;
+    if (p.h_hot_pairs && p.h_hot_pval) {
         for (int k = 0; k < 2; ++k) {
-            const int pair = h_hot_pairs[k];
-            const bool ok = !A::kProlChecksPairs || (pair >= 0 && (pair & 0xff) < p_npat && (pair >> 8) < p_npat);
+            const int pair = p.h_hot_pairs[k];
+            const bool ok = !A::kProlChecksPairs || (pair >= 0 && (pair & 0xff) < p.p_npat && (pair >> 8) < p.p_npat);
             a.phot[k] = ok ? pair : -1;
         }
-        for (int k = 0; k < 9; ++k) a.phv[k] = h_hot_pval[k];
+        for (int k = 0; k < 9; ++k) a.phv[k] = p.h_hot_pval[k];
     }
 }
 
 // The restriction folded into a pass (b_coarse = R (b - A x_out)).  Checked before the operator; set after it.
 //     kRestCoarseLimit     first coarse row count refused: 2^28 in the register pass, 2^31 in the tiled one (as found)
 template <typename A>
-int lmg_rest_check(int64_t n, int32_t line_stride, const double *x_in, const double *b, const double *x_out, int64_t n_coarse,
-                   int32_t coarse_stride, const double *b_coarse, const uint8_t *r_pid, int32_t r_npat, const double *r_val,
-                   const int32_t *r_mask)
+int lmg_rest_check(const LmgOperator &op, const LmgSolve &v, const LmgRest &r)
 {
-    if (!b_coarse || !r_pid || !r_val || !r_mask || r_npat < 1 || r_npat > kMaxPat) return LMG_ERR_ARG;
-    if (n_coarse < 1 || n_coarse >= A::kRestCoarseLimit || coarse_stride < 1 || coarse_stride > n_coarse) return LMG_ERR_ARG;
-    if (b_coarse == x_in || b_coarse == x_out || b_coarse == b) return LMG_ERR_ARG;
+    if (!r.b_coarse || !r.r_pid || !r.r_val || !r.r_mask || r.r_npat < 1 || r.r_npat > kMaxPat) return LMG_ERR_ARG;
+    if (r.n_coarse < 1 || r.n_coarse >= A::kRestCoarseLimit || r.coarse_stride < 1 || r.coarse_stride > r.n_coarse)
+        return LMG_ERR_ARG;
+    if (r.b_coarse == v.x_in || r.b_coarse == v.x_out || r.b_coarse == v.b) return LMG_ERR_ARG;
     // row (Y, X) of R sits on the fine node (2 Y, 2 X): every such node of the fine grid must have its coarse row
     // -- and nothing else: the pass only writes b_coarse under those nodes, a larger coarse grid would keep stale rows
-    const int64_t lines = n > 0 ? (n + line_stride - 1) / line_stride : 0;
-    if ((int64_t)coarse_stride != ((int64_t)line_stride + 1) / 2 || (n % line_stride) != 0 ||
-        n_coarse != ((lines + 1) / 2) * coarse_stride)
+    const int64_t lines = op.n > 0 ? (op.n + op.line_stride - 1) / op.line_stride : 0;
+    if ((int64_t)r.coarse_stride != ((int64_t)op.line_stride + 1) / 2 || (op.n % op.line_stride) != 0 ||
+        r.n_coarse != ((lines + 1) / 2) * r.coarse_stride)
         return LMG_ERR_ARG;
     return LMG_OK;
 }
 template <typename A>
-void lmg_rest_set(A &a, int64_t n_coarse, int32_t coarse_stride, double *b_coarse, const uint8_t *r_pid, int32_t r_npat,
-                  const double *r_val, const int32_t *r_mask, int32_t hot_r, const double *h_hot_rval)
+void lmg_rest_set(A &a, const LmgRest &r)
 {
-    a.bc = b_coarse;
-    a.nc = (int)n_coarse;
-    a.Wc = coarse_stride;
-    a.rpid = r_pid;
-    a.rp_val = r_val;
-    a.rp_mask = r_mask;
-    a.rp_npat = r_npat;
-    if (hot_r >= 0 && hot_r < r_npat && h_hot_rval) {
-        a.rhot = hot_r;
-        for (int k = 0; k < 9; ++k) a.rhv[k] = h_hot_rval[k];
+    a.bc = r.b_coarse;
+    a.nc = (int)r.n_coarse;
+    a.Wc = r.coarse_stride;
+    a.rpid = r.r_pid;
+    a.rp_val = r.r_val;
+    a.rp_mask = r.r_mask;
+    a.rp_npat = r.r_npat;
+    if (r.hot_r >= 0 && r.hot_r < r.r_npat && r.h_hot_rval) {
+        a.rhot = r.hot_r;
+        for (int k = 0; k < 9; ++k) a.rhv[k] = r.h_hot_rval[k];
     }
+}
+
+// The body of every fused-pass entry point.  `a` arrives with the fields only its struct has; p / r: the transfer folded
+// in, or null.  The transfers are checked first (prolongation, then restriction: a pass with both can also alias their
+// coarse vectors), then the operator, where "nothing to do" answers; launch(a, m) runs with the slot set as
+// std::integral_constant m, for the sets M.. the pass is built for.
+template <unsigned... M, typename A, typename Launch>
+int lmg_fused_pass(A a, const LmgOperator &op, const LmgSolve &v, const LmgProl *p, const LmgRest *r, Launch &&launch)
+{
+    int bad = p ? lmg_prol_check<A>(op, v, *p) : LMG_OK;
+    if (!bad && r) bad = lmg_rest_check<A>(op, v, *r);
+    if (bad) return bad;
+    if (p && r && (const double *)r->b_coarse == p->e_coarse) return LMG_ERR_ARG;
+    const int rc = lmg_smooth_fill(a, op, v);
+    if (rc != 1) return rc;
+    if (p) lmg_prol_set(a, *p);
+    if (r) lmg_rest_set(a, *r);
+    return lmg_with_mask<M...>(op.union_mask, [&](auto m) { return launch(a, m); });
 }

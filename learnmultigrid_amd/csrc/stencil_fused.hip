@@ -871,18 +871,11 @@ int lmg_stencil_smooth(int64_t n, int32_t line_stride, const uint8_t *pid, int32
                        int sweeps, const double *x_in, const double *b, double omega, double *x_out, double *r_out,
                        void *stream)
 {
-    MArgs a = own_fields(union_mask);
-    const int rc = lmg_smooth_fill(a, n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val, sweeps,
-                                   x_in, b, omega, x_out, r_out);
-    if (rc != 1) return rc;
-    hipStream_t st = lmg_stream(stream);
-    const bool resid = r_out != nullptr, zero = x_in == nullptr;
-    switch (union_mask) {
-    case kMask5: return launch_plain<kMask5>(a, sweeps, resid, zero, st);
-    case kMask9: return launch_plain<kMask9>(a, sweeps, resid, zero, st);
-    case kMask1D: return launch_plain<kMask1D>(a, sweeps, resid, zero, st);
-    default: return LMG_ERR_CAPACITY;        // other slot sets: run the separate sweeps
-    }
+    return lmg_fused_pass<kMask5, kMask9, kMask1D>(      // other slot sets: run the separate sweeps
+        own_fields(union_mask), {n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val},
+        {sweeps, x_in, b, omega, x_out, r_out}, nullptr, nullptr, [&](const MArgs &a, auto m) {
+            return launch_plain<LMG_CT(m)>(a, sweeps, r_out != nullptr, x_in == nullptr, lmg_stream(stream));
+        });
 }
 
 int lmg_stencil_smooth_prolong(int64_t n, int32_t line_stride, const uint8_t *pid, int32_t npat, const double *st_val,
@@ -892,20 +885,11 @@ int lmg_stencil_smooth_prolong(int64_t n, int32_t line_stride, const uint8_t *pi
                                int32_t p_npat, const double *p_val, const int32_t *p_mask, const int32_t *h_hot_pairs,
                                const double *h_hot_pval, void *stream)
 {
-    const int bad = lmg_prol_check<MArgs>(line_stride, x_in, x_out, n_coarse, coarse_stride, e_coarse, p_pid, p_npat, p_val,
-                                          p_mask);
-    if (bad) return bad;
-    MArgs a = own_fields(union_mask);
-    const int rc = lmg_smooth_fill(a, n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val, sweeps,
-                                   x_in, b, omega, x_out, nullptr);
-    if (rc != 1) return rc;
-    lmg_prol_set(a, n_coarse, coarse_stride, e_coarse, p_pid, p_npat, p_val, p_mask, h_hot_pairs, h_hot_pval);
-    hipStream_t st = lmg_stream(stream);
-    switch (union_mask) {
-    case kMask5: return launch_prol<kMask5>(a, sweeps, st);
-    case kMask9: return launch_prol<kMask9>(a, sweeps, st);
-    default: return LMG_ERR_CAPACITY;
-    }
+    const LmgProl p = {n_coarse, coarse_stride, e_coarse, p_pid, p_npat, p_val, p_mask, h_hot_pairs, h_hot_pval};
+    return lmg_fused_pass<kMask5, kMask9>(
+        own_fields(union_mask), {n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val},
+        {sweeps, x_in, b, omega, x_out, nullptr}, &p, nullptr,
+        [&](const MArgs &a, auto m) { return launch_prol<LMG_CT(m)>(a, sweeps, lmg_stream(stream)); });
 }
 
 int lmg_stencil_smooth_restrict(int64_t n, int32_t line_stride, const uint8_t *pid, int32_t npat, const double *st_val,
@@ -915,21 +899,11 @@ int lmg_stencil_smooth_restrict(int64_t n, int32_t line_stride, const uint8_t *p
                                 int32_t r_npat, const double *r_val, const int32_t *r_mask, int32_t hot_r,
                                 const double *h_hot_rval, void *stream)
 {
-    const int bad = lmg_rest_check<MArgs>(n, line_stride, x_in, b, x_out, n_coarse, coarse_stride, b_coarse, r_pid, r_npat,
-                                          r_val, r_mask);
-    if (bad) return bad;
-    MArgs a = own_fields(union_mask);
-    const int rc = lmg_smooth_fill(a, n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val, sweeps,
-                                   x_in, b, omega, x_out, nullptr);
-    if (rc != 1) return rc;
-    lmg_rest_set(a, n_coarse, coarse_stride, b_coarse, r_pid, r_npat, r_val, r_mask, hot_r, h_hot_rval);
-    hipStream_t st = lmg_stream(stream);
-    const bool zero = x_in == nullptr;
-    switch (union_mask) {
-    case kMask5: return launch_rest<kMask5>(a, sweeps, zero, st);
-    case kMask9: return launch_rest<kMask9>(a, sweeps, zero, st);
-    default: return LMG_ERR_CAPACITY;
-    }
+    const LmgRest r = {n_coarse, coarse_stride, b_coarse, r_pid, r_npat, r_val, r_mask, hot_r, h_hot_rval};
+    return lmg_fused_pass<kMask5, kMask9>(
+        own_fields(union_mask), {n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val},
+        {sweeps, x_in, b, omega, x_out, nullptr}, nullptr, &r,
+        [&](const MArgs &a, auto m) { return launch_rest<LMG_CT(m)>(a, sweeps, x_in == nullptr, lmg_stream(stream)); });
 }
 
 int lmg_stencil_smooth_supported(uint32_t union_mask)

@@ -528,24 +528,49 @@ int launch_turn(TArgs a, int sweeps, hipStream_t st)
     });
 }
 
-// the fields only this pass has: the tiling that launch5 decides
-TArgs own_fields()
-{
-    TArgs a;
-    a.tiles_x = a.tiles_y = 0;
-    for (int k = 0; k < 3; ++k) a.cha[k] = a.chc[k] = 0.0;
-    return a;
-}
-
 // The coefficient table of a Chebyshev step: h_coef = HOST pointer to (a_0, c_0, .., a_(degree-1), c_(degree-1)).  c_0
 // stands in for omega in the shared argument rules.
 bool cheby_coef_ok(int degree, const double *h_coef) { return degree >= 1 && degree <= 3 && h_coef != nullptr; }
-void cheby_set(TArgs &a, int degree, const double *h_coef)
+
+// the fields only this pass has: the tiling that launch5 decides, and the table of a Chebyshev step (cheby_coef_ok)
+TArgs own_fields(int degree, const double *h_coef)
 {
-    for (int k = 0; k < degree; ++k) {
-        a.cha[k] = h_coef[2 * k];
-        a.chc[k] = h_coef[2 * k + 1];
+    TArgs a;
+    a.tiles_x = a.tiles_y = 0;
+    for (int k = 0; k < 3; ++k) {
+        a.cha[k] = h_coef && k < degree ? h_coef[2 * k] : 0.0;
+        a.chc[k] = h_coef && k < degree ? h_coef[2 * k + 1] : 0.0;
     }
+    return a;
+}
+
+// The plain, the correcting and the restricting pass, for both smoothers: h_coef == nullptr is weighted Jacobi, else a
+// Chebyshev step of degree v.sweeps (the entry point has asked cheby_coef_ok).
+int tiled_plain(const LmgOperator &op, const LmgSolve &v, const double *h_coef, void *stream)
+{
+    return lmg_fused_pass<kMask5, kMask9>(own_fields(v.sweeps, h_coef), op, v, nullptr, nullptr, [&](const TArgs &a, auto m) {
+        return lmg_with_flag(h_coef != nullptr, [&](auto ch) {
+            return launch_plain<LMG_CT(m), LMG_CT(ch)>(a, v.sweeps, v.r_out != nullptr, v.x_in == nullptr, lmg_stream(stream));
+        });
+    });
+}
+
+int tiled_prolong(const LmgOperator &op, const LmgSolve &v, const double *h_coef, const LmgProl &p, void *stream)
+{
+    return lmg_fused_pass<kMask5, kMask9>(own_fields(v.sweeps, h_coef), op, v, &p, nullptr, [&](const TArgs &a, auto m) {
+        return lmg_with_flag(h_coef != nullptr, [&](auto ch) {
+            return launch_prol<LMG_CT(m), LMG_CT(ch)>(a, v.sweeps, lmg_stream(stream));
+        });
+    });
+}
+
+int tiled_restrict(const LmgOperator &op, const LmgSolve &v, const double *h_coef, const LmgRest &r, void *stream)
+{
+    return lmg_fused_pass<kMask5, kMask9>(own_fields(v.sweeps, h_coef), op, v, nullptr, &r, [&](const TArgs &a, auto m) {
+        return lmg_with_flag(h_coef != nullptr, [&](auto ch) {
+            return launch_rest<LMG_CT(m), LMG_CT(ch)>(a, v.sweeps, v.x_in == nullptr, lmg_stream(stream));
+        });
+    });
 }
 
 }  // namespace
@@ -568,17 +593,8 @@ int lmg_stencil_smooth_tiled(int64_t n, int32_t line_stride, const uint8_t *pid,
                              int sweeps, const double *x_in, const double *b, double omega, double *x_out, double *r_out,
                              void *stream)
 {
-    TArgs a = own_fields();
-    const int rc = lmg_smooth_fill(a, n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val, sweeps,
-                                   x_in, b, omega, x_out, r_out);
-    if (rc != 1) return rc;
-    hipStream_t st = lmg_stream(stream);
-    const bool resid = r_out != nullptr, zero = x_in == nullptr;
-    switch (union_mask) {
-    case kMask5: return launch_plain<kMask5>(a, sweeps, resid, zero, st);
-    case kMask9: return launch_plain<kMask9>(a, sweeps, resid, zero, st);
-    default: return LMG_ERR_CAPACITY;        // other slot sets: run the separate sweeps
-    }
+    return tiled_plain({n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val},
+                       {sweeps, x_in, b, omega, x_out, r_out}, nullptr, stream);
 }
 
 int lmg_stencil_smooth_tiled_prolong(int64_t n, int32_t line_stride, const uint8_t *pid, int32_t npat, const double *st_val,
@@ -588,20 +604,9 @@ int lmg_stencil_smooth_tiled_prolong(int64_t n, int32_t line_stride, const uint8
                                      const uint8_t *p_pid, int32_t p_npat, const double *p_val, const int32_t *p_mask,
                                      const int32_t *h_hot_pairs, const double *h_hot_pval, void *stream)
 {
-    const int bad = lmg_prol_check<TArgs>(line_stride, x_in, x_out, n_coarse, coarse_stride, e_coarse, p_pid, p_npat, p_val,
-                                          p_mask);
-    if (bad) return bad;
-    TArgs a = own_fields();
-    const int rc = lmg_smooth_fill(a, n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val, sweeps,
-                                   x_in, b, omega, x_out, nullptr);
-    if (rc != 1) return rc;
-    lmg_prol_set(a, n_coarse, coarse_stride, e_coarse, p_pid, p_npat, p_val, p_mask, h_hot_pairs, h_hot_pval);
-    hipStream_t st = lmg_stream(stream);
-    switch (union_mask) {
-    case kMask5: return launch_prol<kMask5>(a, sweeps, st);
-    case kMask9: return launch_prol<kMask9>(a, sweeps, st);
-    default: return LMG_ERR_CAPACITY;
-    }
+    return tiled_prolong({n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val},
+                         {sweeps, x_in, b, omega, x_out, nullptr}, nullptr,
+                         {n_coarse, coarse_stride, e_coarse, p_pid, p_npat, p_val, p_mask, h_hot_pairs, h_hot_pval}, stream);
 }
 
 int lmg_stencil_smooth_tiled_restrict(int64_t n, int32_t line_stride, const uint8_t *pid, int32_t npat, const double *st_val,
@@ -611,21 +616,9 @@ int lmg_stencil_smooth_tiled_restrict(int64_t n, int32_t line_stride, const uint
                                       const uint8_t *r_pid, int32_t r_npat, const double *r_val, const int32_t *r_mask,
                                       int32_t hot_r, const double *h_hot_rval, void *stream)
 {
-    const int bad = lmg_rest_check<TArgs>(n, line_stride, x_in, b, x_out, n_coarse, coarse_stride, b_coarse, r_pid, r_npat,
-                                          r_val, r_mask);
-    if (bad) return bad;
-    TArgs a = own_fields();
-    const int rc = lmg_smooth_fill(a, n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val, sweeps,
-                                   x_in, b, omega, x_out, nullptr);
-    if (rc != 1) return rc;
-    lmg_rest_set(a, n_coarse, coarse_stride, b_coarse, r_pid, r_npat, r_val, r_mask, hot_r, h_hot_rval);
-    hipStream_t st = lmg_stream(stream);
-    const bool zero = x_in == nullptr;
-    switch (union_mask) {
-    case kMask5: return launch_rest<kMask5>(a, sweeps, zero, st);
-    case kMask9: return launch_rest<kMask9>(a, sweeps, zero, st);
-    default: return LMG_ERR_CAPACITY;
-    }
+    return tiled_restrict({n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val},
+                          {sweeps, x_in, b, omega, x_out, nullptr}, nullptr,
+                          {n_coarse, coarse_stride, b_coarse, r_pid, r_npat, r_val, r_mask, hot_r, h_hot_rval}, stream);
 }
 
 int lmg_stencil_smooth_tiled_turnaround(int64_t n, int32_t line_stride, const uint8_t *pid, int32_t npat, const double *st_val,
@@ -637,26 +630,15 @@ int lmg_stencil_smooth_tiled_turnaround(int64_t n, int32_t line_stride, const ui
                                         double *b_coarse, const uint8_t *r_pid, int32_t r_npat, const double *r_val,
                                         const int32_t *r_mask, int32_t hot_r, const double *h_hot_rval, void *stream)
 {
+    // its own rule: two sweep counts, in front of the checks of the correcting and of the restricting pass
     if (sweeps_post < 1 || sweeps_post > 3 || sweeps_pre < 1 || sweeps_pre > 3) return LMG_ERR_ARG;
-    // the argument checks of the correcting and of the restricting pass, and the one pair only this pass can alias
-    int bad = lmg_prol_check<TArgs>(line_stride, x_in, x_out, n_coarse, coarse_stride, e_coarse, p_pid, p_npat, p_val, p_mask);
-    if (!bad)
-        bad = lmg_rest_check<TArgs>(n, line_stride, x_in, b, x_out, n_coarse, coarse_stride, b_coarse, r_pid, r_npat, r_val,
-                                    r_mask);
-    if (bad) return bad;
-    if ((const double *)b_coarse == e_coarse) return LMG_ERR_ARG;
-    TArgs a = own_fields();
-    const int rc = lmg_smooth_fill(a, n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val, sweeps_post,
-                                   x_in, b, omega, x_out, nullptr);
-    if (rc != 1) return rc;
-    lmg_prol_set(a, n_coarse, coarse_stride, e_coarse, p_pid, p_npat, p_val, p_mask, h_hot_pairs, h_hot_pval);
-    lmg_rest_set(a, n_coarse, coarse_stride, b_coarse, r_pid, r_npat, r_val, r_mask, hot_r, h_hot_rval);
-    hipStream_t st = lmg_stream(stream);
-    switch (union_mask) {
-    case kMask5: return launch_turn<kMask5>(a, sweeps_post + sweeps_pre, st);
-    case kMask9: return launch_turn<kMask9>(a, sweeps_post + sweeps_pre, st);
-    default: return LMG_ERR_CAPACITY;
-    }
+    const LmgProl p = {n_coarse, coarse_stride, e_coarse, p_pid, p_npat, p_val, p_mask, h_hot_pairs, h_hot_pval};
+    const LmgRest r = {n_coarse, coarse_stride, b_coarse, r_pid, r_npat, r_val, r_mask, hot_r, h_hot_rval};
+    return lmg_fused_pass<kMask5, kMask9>(own_fields(0, nullptr),
+                                          {n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val},
+                                          {sweeps_post, x_in, b, omega, x_out, nullptr}, &p, &r, [&](const TArgs &a, auto m) {
+                                              return launch_turn<LMG_CT(m)>(a, sweeps_post + sweeps_pre, lmg_stream(stream));
+                                          });
 }
 
 int lmg_stencil_cheby_tiled(int64_t n, int32_t line_stride, const uint8_t *pid, int32_t npat, const double *st_val,
@@ -665,18 +647,8 @@ int lmg_stencil_cheby_tiled(int64_t n, int32_t line_stride, const uint8_t *pid, 
                             double *r_out, void *stream)
 {
     if (!cheby_coef_ok(degree, h_coef)) return LMG_ERR_ARG;
-    TArgs a = own_fields();
-    const int rc = lmg_smooth_fill(a, n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val, degree,
-                                   x_in, b, h_coef[1], x_out, r_out);
-    if (rc != 1) return rc;
-    cheby_set(a, degree, h_coef);
-    hipStream_t st = lmg_stream(stream);
-    const bool resid = r_out != nullptr, zero = x_in == nullptr;
-    switch (union_mask) {
-    case kMask5: return launch_plain<kMask5, true>(a, degree, resid, zero, st);
-    case kMask9: return launch_plain<kMask9, true>(a, degree, resid, zero, st);
-    default: return LMG_ERR_CAPACITY;        // other slot sets: residual launch + lmg_cheby_update
-    }
+    return tiled_plain({n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val},
+                       {degree, x_in, b, h_coef[1], x_out, r_out}, h_coef, stream);
 }
 
 int lmg_stencil_cheby_tiled_prolong(int64_t n, int32_t line_stride, const uint8_t *pid, int32_t npat, const double *st_val,
@@ -687,21 +659,9 @@ int lmg_stencil_cheby_tiled_prolong(int64_t n, int32_t line_stride, const uint8_
                                     const int32_t *p_mask, const int32_t *h_hot_pairs, const double *h_hot_pval, void *stream)
 {
     if (!cheby_coef_ok(degree, h_coef)) return LMG_ERR_ARG;
-    const int bad = lmg_prol_check<TArgs>(line_stride, x_in, x_out, n_coarse, coarse_stride, e_coarse, p_pid, p_npat, p_val,
-                                          p_mask);
-    if (bad) return bad;
-    TArgs a = own_fields();
-    const int rc = lmg_smooth_fill(a, n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val, degree,
-                                   x_in, b, h_coef[1], x_out, nullptr);
-    if (rc != 1) return rc;
-    cheby_set(a, degree, h_coef);
-    lmg_prol_set(a, n_coarse, coarse_stride, e_coarse, p_pid, p_npat, p_val, p_mask, h_hot_pairs, h_hot_pval);
-    hipStream_t st = lmg_stream(stream);
-    switch (union_mask) {
-    case kMask5: return launch_prol<kMask5, true>(a, degree, st);
-    case kMask9: return launch_prol<kMask9, true>(a, degree, st);
-    default: return LMG_ERR_CAPACITY;
-    }
+    return tiled_prolong({n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val},
+                         {degree, x_in, b, h_coef[1], x_out, nullptr}, h_coef,
+                         {n_coarse, coarse_stride, e_coarse, p_pid, p_npat, p_val, p_mask, h_hot_pairs, h_hot_pval}, stream);
 }
 
 int lmg_stencil_cheby_tiled_restrict(int64_t n, int32_t line_stride, const uint8_t *pid, int32_t npat, const double *st_val,
@@ -712,22 +672,9 @@ int lmg_stencil_cheby_tiled_restrict(int64_t n, int32_t line_stride, const uint8
                                      const int32_t *r_mask, int32_t hot_r, const double *h_hot_rval, void *stream)
 {
     if (!cheby_coef_ok(degree, h_coef)) return LMG_ERR_ARG;
-    const int bad = lmg_rest_check<TArgs>(n, line_stride, x_in, b, x_out, n_coarse, coarse_stride, b_coarse, r_pid, r_npat,
-                                          r_val, r_mask);
-    if (bad) return bad;
-    TArgs a = own_fields();
-    const int rc = lmg_smooth_fill(a, n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val, degree,
-                                   x_in, b, h_coef[1], x_out, nullptr);
-    if (rc != 1) return rc;
-    cheby_set(a, degree, h_coef);
-    lmg_rest_set(a, n_coarse, coarse_stride, b_coarse, r_pid, r_npat, r_val, r_mask, hot_r, h_hot_rval);
-    hipStream_t st = lmg_stream(stream);
-    const bool zero = x_in == nullptr;
-    switch (union_mask) {
-    case kMask5: return launch_rest<kMask5, true>(a, degree, zero, st);
-    case kMask9: return launch_rest<kMask9, true>(a, degree, zero, st);
-    default: return LMG_ERR_CAPACITY;
-    }
+    return tiled_restrict({n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val},
+                          {degree, x_in, b, h_coef[1], x_out, nullptr}, h_coef,
+                          {n_coarse, coarse_stride, b_coarse, r_pid, r_npat, r_val, r_mask, hot_r, h_hot_rval}, stream);
 }
 
 int lmg_stencil_smooth_tiled_supported(uint32_t union_mask)

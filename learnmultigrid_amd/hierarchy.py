@@ -72,6 +72,10 @@ def chebyshev_coefficients(lmax, ratio, degree):
     return coef
 
 
+# the ops predicates of the fused Chebyshev passes, by the Jacobi predicate each stands in for (Hierarchy._ask)
+CHEBY_TWIN = {"stencil_smooth_available": "stencil_cheby_available",
+              "stencil_smooth_prolong_available": "stencil_cheby_prolong_available",
+              "stencil_smooth_restrict_available": "stencil_cheby_restrict_available"}
 CHEBY_RATIO = 4.0       # lambda_max / lambda_min: the oscillatory modes of D^-1 A under full coarsening in two dimensions
 
 
@@ -325,9 +329,7 @@ class Hierarchy:
                 if direction != "backward":
                     raise ValueError("unknown Gauss-Seidel sweep direction %r" % (direction,))
                 sched = self.gs_schedule(l, kind).reversed()
-                prep = getattr(self.ops, "gs_prepare", None)
-                if prep is not None:
-                    prep(lev.A, sched)
+                self._ask("gs_prepare", lev.A, sched)
                 lev.gs_sched[key] = sched
             return lev.gs_sched[key]
         if kind not in lev.gs_sched:
@@ -339,9 +341,7 @@ class Hierarchy:
             # the schedule-ordered pattern copy of the one-workgroup executor is built HERE, eagerly:
             # it allocates and reads sizes back to the host, which must never happen while a
             # hipGraph is being captured (captured_cycle only calls gs_schedule before the capture)
-            prep = getattr(self.ops, "gs_prepare", None)
-            if prep is not None:
-                prep(lev.A, sched)
+            self._ask("gs_prepare", lev.A, sched)
             lev.gs_sched[kind] = sched
         return lev.gs_sched[kind]
 
@@ -401,57 +401,53 @@ class Hierarchy:
         else:
             self.ops.csr_gs_schedule(lev.A, lev.x, lev.b, self.gs_schedule(l, gs_mode, direction), steps)
 
+    def _ask(self, name, *args, smoother=None):
+        """self.ops.<name>(*args), or False where the ops module has no such name (an ops module leaves out what it does
+        not offer).  With smoother "Chebyshev", the Chebyshev twin of a Jacobi predicate is asked in its place."""
+        if smoother == "Chebyshev":
+            name = CHEBY_TWIN[name]
+        fn = getattr(self.ops, name, None)
+        return fn(*args) if fn is not None else False
+
     def _wavefront_gs(self, l, gs_mode, direction="forward"):
-        avail = getattr(self.ops, "stencil_gs_available", None)
-        if gs_mode != "lexicographic" or avail is None:
+        if gs_mode != "lexicographic":
             return False
-        return avail(self.levels[l].A) if direction == "forward" else avail(self.levels[l].A, direction)
+        A = self.levels[l].A
+        return self._ask("stencil_gs_available", A) if direction == "forward" else self._ask("stencil_gs_available", A, direction)
 
     def _fusable(self, l, smoother, steps):
-        if smoother == "Chebyshev":
-            # one step is one pass: d is never carried between launches
-            avail = getattr(self.ops, "stencil_cheby_available", None)
-            return (avail is not None and 1 <= steps <= self.ops.FUSED_MAX_SWEEPS and avail(self.levels[l].A))
-        avail = getattr(self.ops, "stencil_smooth_available", None)
-        return (smoother == "Jacobi" and steps >= 1 and avail is not None and avail(self.levels[l].A))
-
-    def _transfer_avail(self, smoother, which):
-        """The ops predicate that says whether `which` ("prolong" | "restrict") folds into the fused pass of `smoother`."""
-        return getattr(self.ops, "stencil_%s_%s_available" % ("cheby" if smoother == "Chebyshev" else "smooth", which), None)
+        if smoother not in ("Jacobi", "Chebyshev") or steps < 1:
+            return False
+        if not self._ask("stencil_smooth_available", self.levels[l].A, smoother=smoother):
+            return False
+        # a Chebyshev step is one pass: d is never carried between launches
+        return smoother == "Jacobi" or steps <= self.ops.FUSED_MAX_SWEEPS
 
     def smooth_fused(self, l, steps, omega, x_is_zero=False, want_residual=False, correction=None, restrict_to=None,
                      smoother="Jacobi"):
         """`steps` Jacobi sweeps on level l (and r = b - A x afterwards) as fused passes of at most
         FUSED_MAX_SWEEPS sweeps each (lmg_stencil_smooth): same bits as smooth() + the residual launch,
         a third of the passes over the level's vectors.  correction = (P, e): the first pass starts from
-        x + P e (Multigrid.py:115 folded in; the caller has checked stencil_smooth_prolong_available)."""
+        x + P e (Multigrid.py:115 folded in; the caller has checked stencil_smooth_prolong_available).
+        smoother "Chebyshev": one step of degree `steps` (<= FUSED_MAX_SWEEPS, see _fusable) as the one pass, with its
+        coefficient table in place of (omega, sweeps)."""
         lev = self.levels[l]
-        if smoother == "Chebyshev":
-            # one step of degree `steps` (<= FUSED_MAX_SWEEPS, see _fusable) as one tiled pass
-            kw = {}
-            if correction is not None:
-                kw["prolong"] = correction
-            elif restrict_to is not None:
-                kw["restrict"] = restrict_to
-            self.ops.stencil_cheby(lev.A, None if x_is_zero else lev.x, lev.b, self._cheby_coef(l, steps), lev.tmp,
-                                   lev.r if (want_residual and restrict_to is None) else None, **kw)
-            lev.x, lev.tmp = lev.tmp, lev.x
-            return
+        cheby = smoother == "Chebyshev"
+        run = self.ops.stencil_cheby if cheby else self.ops.stencil_smooth
         left = steps
-        mx = self.ops.FUSED_MAX_SWEEPS
         while left > 0:
-            k = min(left, mx)
+            k = left if cheby else min(left, self.ops.FUSED_MAX_SWEEPS)
             left -= k
+            how = (self._cheby_coef(l, k),) if cheby else (omega, k)
+            x_in = None if x_is_zero else lev.x
             if correction is not None:
-                self.ops.stencil_smooth(lev.A, lev.x, lev.b, omega, k, lev.tmp, None, prolong=correction)
+                run(lev.A, lev.x, lev.b, *how, lev.tmp, None, prolong=correction)
                 correction = None
             elif restrict_to is not None and left == 0:
                 # b_coarse = R (b - A x) formed in the pass, the residual itself is not written
-                self.ops.stencil_smooth(lev.A, None if x_is_zero else lev.x, lev.b, omega, k, lev.tmp, None,
-                                        restrict=restrict_to)
+                run(lev.A, x_in, lev.b, *how, lev.tmp, None, restrict=restrict_to)
             else:
-                self.ops.stencil_smooth(lev.A, None if x_is_zero else lev.x, lev.b, omega, k, lev.tmp,
-                                        lev.r if (want_residual and left == 0) else None)
+                run(lev.A, x_in, lev.b, *how, lev.tmp, lev.r if (want_residual and left == 0) else None)
             lev.x, lev.tmp = lev.tmp, lev.x
             x_is_zero = False
 
@@ -518,9 +514,8 @@ class Hierarchy:
         """Pre-smoothing of level l, residual, b_(l+1) = R r (Multigrid.py:88-93)."""
         lev, nxt = self.levels[l], self.levels[l + 1]
         fused = self._fusable(l, smoother, steps)
-        ravail = self._transfer_avail(smoother, "restrict")
         restricted = False
-        if fused and ravail is not None and ravail(lev.A, lev.R):
+        if fused and self._ask("stencil_smooth_restrict_available", lev.A, lev.R, smoother=smoother):
             self.smooth_fused(l, steps, omega, x_is_zero, restrict_to=(lev.R, nxt.b), smoother=smoother)   # :88 + :90 + :93 in one pass
             restricted = True
             if after_presmooth is not None:
@@ -541,8 +536,7 @@ class Hierarchy:
         """x += P x_(l+1), post-smoothing of level l (Multigrid.py:115-121)."""
         lev, nxt = self.levels[l], self.levels[l + 1]
         fused = self._fusable(l, smoother, steps)
-        pavail = self._transfer_avail(smoother, "prolong")
-        if fused and pavail is not None and pavail(lev.A, lev.P):
+        if fused and self._ask("stencil_smooth_prolong_available", lev.A, lev.P, smoother=smoother):
             self.smooth_fused(l, steps, omega, correction=(lev.P, nxt.x), smoother=smoother)     # :115 + :121 in one pass
             return
         self.ops.csr_spmv(lev.P, nxt.x, lev.x, 1.0, 1.0)                           # :115
@@ -552,11 +546,10 @@ class Hierarchy:
             self.smooth(l, smoother, steps, omega, gs_mode, direction=post)       # :121
 
     def _turnaround_ok(self, l, smoother, steps):
-        avail = getattr(self.ops, "stencil_smooth_turnaround_selected", None)
         lev = self.levels[l]
         # (Jacobi only: the Chebyshev step has no turnaround pass -- its post- and pre-passes stay separate)
-        return (avail is not None and smoother == "Jacobi" and steps <= self.ops.FUSED_MAX_SWEEPS and self._fusable(l, smoother, steps)
-                and avail(lev.A, lev.P, lev.R))
+        return bool(smoother == "Jacobi" and self._fusable(l, smoother, steps)
+                    and self._ask("stencil_smooth_turnaround_selected", lev.A, lev.P, lev.R) and steps <= self.ops.FUSED_MAX_SWEEPS)
 
     def _turnaround(self, l, steps, omega):
         """Post-smoothing of one visit of level l and pre-smoothing of the next, with the restriction, in one pass."""
@@ -577,11 +570,8 @@ class Hierarchy:
         (gs_wave.hip then leaves a wrong iterate behind and sets a flag).  One 4-byte D2H read per level that
         has run the wavefront kernel: call it where the host synchronises anyway (after the residual norm of an
         outer iteration, after a graph replay)."""
-        chk = getattr(self.ops, "stencil_gs_check", None)
-        if chk is None:
-            return
         for lev in self.levels[:-1]:
-            chk(lev.A)
+            self._ask("stencil_gs_check", lev.A)
 
     def prepare_smoother(self, smoother, gs_mode="lexicographic", l_from=0, gs_sweep=("forward", "forward"), *,
                          cheby_lmax=None, cheby_ratio=None):

@@ -870,21 +870,28 @@ def set_tiled_enabled(flag):
     _TILED_ENABLED = bool(flag)
 
 
-def _fused_kind(A):
-    """'reg' (stencil_fused.hip), 'tile' (stencil_tile.hip), 'dia' (dia_tile.hip: per-row values) or None: how
-    stencil_smooth would run on A."""
+def _pass_kind(A, cheby):
+    """'reg' (stencil_fused.hip), 'tile' (stencil_tile.hip), 'dia' (dia_tile.hip: per-row values) or None: how a
+    smoothing step -- Jacobi sweeps, or with `cheby` a Chebyshev step -- would run on A as one pass."""
     S = getattr(A, "stencil", None)
     D = getattr(A, "dia", None)
     if S is None and D is not None and _PACKED_ENABLED and _DIA_ENABLED and _FUSED_ENABLED:
         return "dia"
     if not (_PACKED_ENABLED and _STENCIL_ENABLED and _FUSED_ENABLED and S is not None):
         return None
-    if S.n >= FUSED_MIN_ROWS:
+    if S.n >= FUSED_MIN_ROWS and not cheby:
         # (the register pass addresses with 32-bit byte offsets: beyond REG_MAX_ROWS the separate sweeps run)
         return "reg" if (S.n < REG_MAX_ROWS and _lib.lib().lmg_stencil_smooth_supported(S.umask)) else None
-    if _TILED_ENABLED and S.n >= TILED_MIN_ROWS and S.W >= 3 and _lib.lib().lmg_stencil_smooth_tiled_supported(S.umask):
+    # the register pass has no Chebyshev form: a Chebyshev step stays on the tiled pass, up to CHEBY_TILED_MAX_ROWS rows
+    if (_TILED_ENABLED and S.n >= TILED_MIN_ROWS and not (cheby and S.n > CHEBY_TILED_MAX_ROWS) and S.W >= 3
+            and _lib.lib().lmg_stencil_smooth_tiled_supported(S.umask)):
         return "tile"
     return None
+
+
+def _fused_kind(A):
+    """How stencil_smooth would run on A (_pass_kind)."""
+    return _pass_kind(A, False)
 
 
 def stencil_smooth_available(A):
@@ -910,44 +917,48 @@ def stencil_smooth(A, x_in, b, omega, sweeps, x_out, r_out=None, prolong=None, r
     restrict = (R, b_coarse): b_coarse = R (b - A x_out) instead of r_out (Multigrid.py:90 + :93, the residual is
     never written: lmg_stencil_smooth_restrict; see stencil_smooth_restrict_available)."""
     _vec_ok(x_in, b, x_out, r_out)
-    S = A.stencil
-    if S is None and getattr(A, "dia", None) is not None:
+    if A.stencil is not None:
+        kind = "tile" if _fused_kind(A) == "tile" else "reg"
+    elif getattr(A, "dia", None) is not None:
+        kind = "dia"
+    else:
+        raise LmgError("stencil_smooth needs a grid-stencil matrix")
+    _run_pass("smooth", kind, A, (int(sweeps), _p(x_in), _p(b), float(omega), _p(x_out)), x_in, r_out, prolong, restrict)
+
+
+def _run_pass(stem, kind, A, head, x_in, r_out, prolong, restrict):
+    """The call of stencil_smooth (stem "smooth") and stencil_cheby ("cheby") on a level that runs the pass `kind`:
+    lmg_dia_<stem> or lmg_stencil_<stem>[_tiled][_prolong | _restrict].  head: the C arguments from the sweep count to
+    x_out."""
+    who = "stencil_" + stem
+    if kind == "dia":
         D = A.dia
         if prolong is not None or restrict is not None:
-            raise LmgError("stencil_smooth: transfers cannot be fused into the pass of a variable-coefficient operator")
-        check(_lib.lib().lmg_dia_smooth(D.n, D.W, D.umask, _p(D.dia), int(sweeps), _p(x_in), _p(b), float(omega), _p(x_out),
-                                        _p(r_out), _s(D.dia)), "lmg_dia_smooth")
+            raise LmgError("%s: transfers cannot be fused into the pass of a variable-coefficient operator" % who)
+        name = "lmg_dia_" + stem
+        check(getattr(_lib.lib(), name)(D.n, D.W, D.umask, _p(D.dia), *head, _p(r_out), _s(D.dia)), name)
         return
-    if S is None:
-        raise LmgError("stencil_smooth needs a grid-stencil matrix")
-    tiled = _fused_kind(A) == "tile"
-    vecs = (int(sweeps), _p(x_in), _p(b), float(omega), _p(x_out))
-    if restrict is not None:
-        R, bc = restrict
-        T = R.restrict
-        _vec_ok(bc)
-        if T is None or r_out is not None or prolong is not None or T.n != S.n or T.W != S.W or bc.numel() != T.nc:
-            raise LmgError("stencil_smooth: this restriction cannot be fused into the pass")
-        if tiled and not (S.n >= REG_RESTRICT_MIN_ROWS and _lib.lib().lmg_stencil_smooth_prolong_supported(S.umask)):
-            name = "lmg_stencil_smooth_tiled_restrict"
-        else:
-            name = "lmg_stencil_smooth_restrict"
-        tail = T.c_args(bc)
-    elif prolong is not None:
-        P, e = prolong
-        T = P.prolong
-        _vec_ok(e)
-        if T is None or r_out is not None or x_in is None or T.n != S.n or T.W != S.W or e.numel() != T.nc:
-            raise LmgError("stencil_smooth: this prolongation cannot be fused into the pass")
-        if tiled and not (S.n >= REG_PROLONG_MIN_ROWS and _lib.lib().lmg_stencil_smooth_prolong_supported(S.umask)):
-            name = "lmg_stencil_smooth_tiled_prolong"
-        else:
-            name = "lmg_stencil_smooth_prolong"
-        tail = T.c_args(e)
-    else:
-        name = "lmg_stencil_smooth_tiled" if tiled else "lmg_stencil_smooth"
+    S = A.stencil
+    tiled = kind == "tile"
+    form = "restrict" if restrict is not None else "prolong" if prolong is not None else None
+    if form is None:
         tail = (_p(r_out),)
-    check(getattr(_lib.lib(), name)(*S.c_args(), *vecs, *tail, _s(S.pid)), name)
+    else:
+        M, vec = restrict if form == "restrict" else prolong
+        T = getattr(M, form)
+        _vec_ok(vec)
+        # the restricting pass takes no correction, the correcting pass no zero iterate
+        other = prolong is not None if form == "restrict" else x_in is None
+        if T is None or r_out is not None or other or T.n != S.n or T.W != S.W or vec.numel() != T.nc:
+            what = "restriction" if form == "restrict" else "prolongation"
+            raise LmgError("%s: this %s cannot be fused into the pass" % (who, what))
+        # Jacobi only: a level on the tiled passes may take the register pass for this launch (A/B knobs)
+        reg_min = REG_RESTRICT_MIN_ROWS if form == "restrict" else REG_PROLONG_MIN_ROWS
+        if stem == "smooth" and S.n >= reg_min and _lib.lib().lmg_stencil_smooth_prolong_supported(S.umask):
+            tiled = False
+        tail = T.c_args(vec)
+    name = "lmg_stencil_%s%s%s" % (stem, "_tiled" if tiled else "", "_" + form if form else "")
+    check(getattr(_lib.lib(), name)(*S.c_args(), *head, *tail, _s(S.pid)), name)
 
 
 # The transfers are folded into the fused passes only on levels that do not fit the Infinity Cache: what is saved is
@@ -969,17 +980,26 @@ def set_fused_prolong_enabled(flag):
     _FUSED_PROLONG_ENABLED = bool(flag)
 
 
-def stencil_smooth_prolong_available(A, P):
-    """True when stencil_smooth can take `prolong=(P, e)`: A runs fused passes and P is a 2x2-window grid
-    prolongation onto A's grid."""
-    T = getattr(P, "prolong", None)
+def _twin_on_grid(A, M, form):
+    """The grid twin of transfer M (form "prolong" or "restrict") where it sits on the grid of A's stencil twin, else None."""
+    T = getattr(M, form, None)
     S = getattr(A, "stencil", None)
-    kind = _fused_kind(A)
-    if not (_FUSED_PROLONG_ENABLED and T is not None and kind in ("reg", "tile") and T.n == S.n and T.W == S.W):
+    return T if (T is not None and S is not None and T.n == S.n and T.W == S.W) else None
+
+
+def _prolong_available(A, P, kind):
+    if not (_FUSED_PROLONG_ENABLED and kind in ("reg", "tile") and _twin_on_grid(A, P, "prolong") is not None):
         return False
     if kind == "tile":                   # the tile is loaded as x + P e: always cheaper than the P launch it replaces
         return True
+    S = A.stencil
     return bool(S.n >= FUSED_TRANSFER_MIN_ROWS and _lib.lib().lmg_stencil_smooth_prolong_supported(S.umask))
+
+
+def stencil_smooth_prolong_available(A, P):
+    """True when stencil_smooth can take `prolong=(P, e)`: A runs fused passes and P is a 2x2-window grid
+    prolongation onto A's grid."""
+    return _prolong_available(A, P, _fused_kind(A))
 
 
 _FUSED_RESTRICT_ENABLED = True
@@ -996,20 +1016,23 @@ def set_fused_restrict_enabled(flag):
     _FUSED_RESTRICT_ENABLED = bool(flag)
 
 
-def stencil_smooth_restrict_available(A, R):
-    """True when stencil_smooth can take `restrict=(R, b_coarse)`: A runs fused passes and R is the 3x3-window
-    restriction from A's grid with a coarse row under every (even line, even column) node."""
-    T = getattr(R, "restrict", None)
-    S = getattr(A, "stencil", None)
-    kind = _fused_kind(A)
-    if not (_FUSED_RESTRICT_ENABLED and T is not None and kind in ("reg", "tile") and T.n == S.n and T.W == S.W):
+def _restrict_available(A, R, kind):
+    T = _twin_on_grid(A, R, "restrict")
+    if not (_FUSED_RESTRICT_ENABLED and kind in ("reg", "tile") and T is not None):
         return False
+    S = A.stencil
     if kind == "reg" and not (S.n >= FUSED_TRANSFER_MIN_ROWS and _lib.lib().lmg_stencil_smooth_prolong_supported(S.umask)):
         return False
     if kind == "tile" and S.n > TILED_RESTRICT_MAX_ROWS:
         return False
     lines = (S.n + S.W - 1) // S.W
     return T.nc >= ((lines + 1) // 2 - 1) * T.Wc + (S.W + 1) // 2
+
+
+def stencil_smooth_restrict_available(A, R):
+    """True when stencil_smooth can take `restrict=(R, b_coarse)`: A runs fused passes and R is the 3x3-window
+    restriction from A's grid with a coarse row under every (even line, even column) node."""
+    return _restrict_available(A, R, _fused_kind(A))
 
 
 _FUSED_TURNAROUND_ENABLED = True
@@ -1075,17 +1098,8 @@ CHEBY_TILED_MAX_ROWS = (1 << 31) - 4096 - 1
 
 
 def _cheby_kind(A):
-    """'tile' (stencil_tile.hip), 'dia' (dia_tile.hip) or None: how stencil_cheby would run on A."""
-    S = getattr(A, "stencil", None)
-    D = getattr(A, "dia", None)
-    if S is None and D is not None and _PACKED_ENABLED and _DIA_ENABLED and _FUSED_ENABLED:
-        return "dia"
-    if not (_PACKED_ENABLED and _STENCIL_ENABLED and _FUSED_ENABLED and _TILED_ENABLED and S is not None):
-        return None
-    if (TILED_MIN_ROWS <= S.n <= CHEBY_TILED_MAX_ROWS and S.W >= 3
-            and _lib.lib().lmg_stencil_smooth_tiled_supported(S.umask)):
-        return "tile"
-    return None
+    """'tile' (stencil_tile.hip), 'dia' (dia_tile.hip) or None: how stencil_cheby would run on A (_pass_kind)."""
+    return _pass_kind(A, True)
 
 
 def stencil_cheby_available(A):
@@ -1095,21 +1109,12 @@ def stencil_cheby_available(A):
 
 def stencil_cheby_prolong_available(A, P):
     """True when stencil_cheby can take `prolong=(P, e)` (the rule of the tiled Jacobi pass: always where it can)."""
-    T = getattr(P, "prolong", None)
-    S = getattr(A, "stencil", None)
-    return bool(_FUSED_PROLONG_ENABLED and T is not None and _cheby_kind(A) == "tile" and T.n == S.n and T.W == S.W)
+    return _prolong_available(A, P, _cheby_kind(A))
 
 
 def stencil_cheby_restrict_available(A, R):
     """True when stencil_cheby can take `restrict=(R, b_coarse)` (the rule of the tiled Jacobi pass)."""
-    T = getattr(R, "restrict", None)
-    S = getattr(A, "stencil", None)
-    if not (_FUSED_RESTRICT_ENABLED and T is not None and _cheby_kind(A) == "tile" and T.n == S.n and T.W == S.W):
-        return False
-    if S.n > TILED_RESTRICT_MAX_ROWS:
-        return False
-    lines = (S.n + S.W - 1) // S.W
-    return T.nc >= ((lines + 1) // 2 - 1) * T.Wc + (S.W + 1) // 2
+    return _restrict_available(A, R, _cheby_kind(A))
 
 
 def _cheby_coef(coef):
@@ -1126,33 +1131,9 @@ def stencil_cheby(A, x_in, b, coef, x_out, r_out=None, prolong=None, restrict=No
     _vec_ok(x_in, b, x_out, r_out)
     kind = _cheby_kind(A)
     hc = _cheby_coef(coef)
-    head = (len(coef), ctypes.addressof(hc), _p(x_in), _p(b), _p(x_out))
-    if kind == "dia":
-        D = A.dia
-        if prolong is not None or restrict is not None:
-            raise LmgError("stencil_cheby: transfers cannot be fused into the pass of a variable-coefficient operator")
-        check(_lib.lib().lmg_dia_cheby(D.n, D.W, D.umask, _p(D.dia), *head, _p(r_out), _s(D.dia)), "lmg_dia_cheby")
-        return
-    if kind != "tile":
+    if kind is None:
         raise LmgError("stencil_cheby needs a level that runs the tiled passes (stencil_cheby_available)")
-    S = A.stencil
-    if restrict is not None:
-        R, bc = restrict
-        T = R.restrict
-        _vec_ok(bc)
-        if T is None or r_out is not None or prolong is not None or T.n != S.n or T.W != S.W or bc.numel() != T.nc:
-            raise LmgError("stencil_cheby: this restriction cannot be fused into the pass")
-        name, tail = "lmg_stencil_cheby_tiled_restrict", T.c_args(bc)
-    elif prolong is not None:
-        P, e = prolong
-        T = P.prolong
-        _vec_ok(e)
-        if T is None or r_out is not None or x_in is None or T.n != S.n or T.W != S.W or e.numel() != T.nc:
-            raise LmgError("stencil_cheby: this prolongation cannot be fused into the pass")
-        name, tail = "lmg_stencil_cheby_tiled_prolong", T.c_args(e)
-    else:
-        name, tail = "lmg_stencil_cheby_tiled", (_p(r_out),)
-    check(getattr(_lib.lib(), name)(*S.c_args(), *head, *tail, _s(S.pid)), name)
+    _run_pass("cheby", kind, A, (len(coef), ctypes.addressof(hc), _p(x_in), _p(b), _p(x_out)), x_in, r_out, prolong, restrict)
 
 
 def cheby_update(a, c, dinv, r, d, x, first=False):
@@ -1174,6 +1155,8 @@ def _use_stencil(A, *vecs):
     if not (_PACKED_ENABLED and _STENCIL_ENABLED and A.stencil is not None):
         return False
     return all(v is None or v.data_ptr() % 16 == 0 for v in vecs)
+
+
 _SELL_ENABLED = True
 SELL_MIN_AVG = 12.0          # average row length from which the sliced-ELL twin replaces the packed CSR
 

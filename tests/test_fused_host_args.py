@@ -1,9 +1,13 @@
-"""CPU-only contract of the argument checks of the seven lmg_stencil_smooth* entry points: which arguments are refused,
-with which status, and which rule answers first when two are broken.
+"""CPU-only contract of the argument checks of the fused-pass entry points -- the seven lmg_stencil_smooth*, the three
+lmg_stencil_cheby_tiled*, lmg_dia_smooth and lmg_dia_cheby: which arguments are refused, with which status, and which
+rule answers first when two are broken.
 
 Every call here is refused or has n == 0, so it returns before any HIP call: the pointers are made-up host addresses
 that nothing reads (the hot-pattern tables, which the host does read once the checks have passed, are always NULL).
-A call that the library would accept with n > 0 must never be added: it would launch."""
+The one exception is the coefficient table of a Chebyshev step, which the host reads in front of the other checks: a
+real array.  A call that the library would accept with n > 0 must never be added: it would launch."""
+import ctypes
+
 import pytest
 
 from learnmultigrid_amd import _lib
@@ -13,7 +17,8 @@ M5, M9, M1D, M7A = 0x0BA, 0x1FF, 0x038, 0x1BB       # M7A: a legal slot set that
 REG_ROWS = 2**29 - 4096                             # first row count the register pass refuses
 TILE_ROWS = 2**31 - 4096                            # ... and the tiled pass
 # made-up, distinct, 16-byte aligned addresses
-PID, VAL, MASK, X, B, OUT, R, EC, PPID, PVAL, PMASK, BC, RPID, RVAL, RMASK = (0x100000 * (k + 1) for k in range(15))
+PID, VAL, MASK, X, B, OUT, R, EC, PPID, PVAL, PMASK, BC, RPID, RVAL, RMASK, DIA = (0x100000 * (k + 1) for k in range(16))
+COEF = (ctypes.c_double * 6)(0.0, 0.8, 0.25, 0.7, 0.2, 0.6)      # (a_k, c_k), k = 0 .. 2: host memory the library reads
 
 OPERATOR = ["n", "line_stride", "pid", "npat", "st_val", "st_mask", "union_mask", "hot_pattern", "h_hot_val"]
 SOLVE = ["x_in", "b", "omega", "x_out"]
@@ -23,6 +28,7 @@ REST = ["b_coarse", "r_pid", "r_npat", "r_val", "r_mask", "hot_r", "h_hot_rval"]
 PLAIN_ARGS = OPERATOR + ["sweeps"] + SOLVE + ["r_out", "stream"]
 PROL_ARGS = OPERATOR + ["sweeps"] + SOLVE + COARSE + PROL + ["stream"]
 REST_ARGS = OPERATOR + ["sweeps"] + SOLVE + COARSE + REST + ["stream"]
+CHEB = ["degree", "h_coef", "x_in", "b", "x_out"]               # in place of sweeps and omega
 ENTRY = {
     "lmg_stencil_smooth": PLAIN_ARGS,
     "lmg_stencil_smooth_prolong": PROL_ARGS,
@@ -31,7 +37,11 @@ ENTRY = {
     "lmg_stencil_smooth_tiled_prolong": PROL_ARGS,
     "lmg_stencil_smooth_tiled_restrict": REST_ARGS,
     "lmg_stencil_smooth_tiled_turnaround": OPERATOR + ["sweeps_post", "sweeps_pre"] + SOLVE + COARSE + PROL + REST + ["stream"],
+    "lmg_stencil_cheby_tiled": OPERATOR + CHEB + ["r_out", "stream"],
+    "lmg_stencil_cheby_tiled_prolong": OPERATOR + CHEB + COARSE + PROL + ["stream"],
+    "lmg_stencil_cheby_tiled_restrict": OPERATOR + CHEB + COARSE + REST + ["stream"],
 }
+CHEBY = [e for e in ENTRY if "cheby" in e]
 REGISTER = [e for e in ENTRY if "tiled" not in e]
 TILED = [e for e in ENTRY if "tiled" in e]
 WITH_PROL = [e for e in ENTRY if "p_pid" in ENTRY[e]]
@@ -50,9 +60,10 @@ def complete(**changes):
     a = dict(pid=PID, npat=3, st_val=VAL, st_mask=MASK, union_mask=M7A, hot_pattern=-1, h_hot_val=None, sweeps=2,
              sweeps_post=2, sweeps_pre=2, x_in=X, b=B, omega=0.8, x_out=OUT, r_out=R, stream=None, e_coarse=EC, p_pid=PPID,
              p_npat=4, p_val=PVAL, p_mask=PMASK, h_hot_pairs=None, h_hot_pval=None, b_coarse=BC, r_pid=RPID, r_npat=4,
-             r_val=RVAL, r_mask=RMASK, hot_r=-1, h_hot_rval=None)
+             r_val=RVAL, r_mask=RMASK, hot_r=-1, h_hot_rval=None, h_coef=COEF, dia=DIA)
     a.update(shape(9, 9))
     a.update(changes)
+    a.setdefault("degree", a["sweeps"])      # a Chebyshev step reads the sweep count of a case as its degree
     return a
 
 
@@ -106,7 +117,7 @@ def test_row_limit(L, entry):
         assert call(L, entry, n=TILE_ROWS - 1) == ARG
 
 
-@pytest.mark.parametrize("entry", ["lmg_stencil_smooth", "lmg_stencil_smooth_tiled"])
+@pytest.mark.parametrize("entry", ["lmg_stencil_smooth", "lmg_stencil_smooth_tiled", "lmg_stencil_cheby_tiled"])
 def test_plain_pass(L, entry):
     assert call(L, entry, r_out=None) == CAPACITY
     assert call(L, entry, x_in=None) == CAPACITY                # the zero iterate
@@ -141,6 +152,10 @@ def test_one_row(L):
     assert call(L, "lmg_stencil_smooth_tiled", n=1, line_stride=1) == ARG
     assert call(L, "lmg_stencil_smooth_tiled_prolong", n=1, line_stride=1) == ARG
     assert call(L, "lmg_stencil_smooth_tiled_restrict", n=1, line_stride=1, coarse_stride=1, n_coarse=1) == ARG
+    assert call(L, "lmg_stencil_cheby_tiled", n=1) == ARG
+    assert call(L, "lmg_stencil_cheby_tiled", n=1, line_stride=1) == ARG
+    assert call(L, "lmg_stencil_cheby_tiled_prolong", n=1, line_stride=1) == ARG
+    assert call(L, "lmg_stencil_cheby_tiled_restrict", n=1, line_stride=1, coarse_stride=1, n_coarse=1) == ARG
 
 
 @pytest.mark.parametrize("entry", sorted(set(WITH_PROL + WITH_REST)))
@@ -195,6 +210,22 @@ def test_prolongation_differences(L):
     assert call(L, reg, n=0, pid=None, b=None, x_out=None) == OK
     assert call(L, tiled, n=0, pid=None, b=None, x_out=None) == OK
     assert call(L, reg, n=0, x_in=None) == ARG
+
+
+def test_cheby_prolongation_is_the_tiled_one(L):
+    """What test_prolongation_differences pins for lmg_stencil_smooth_tiled_prolong holds for its Chebyshev twin."""
+    tiled = "lmg_stencil_cheby_tiled_prolong"
+    assert call(L, tiled, n=0, line_stride=1, n_coarse=1, coarse_stride=1) == ARG       # the two-row coarse minimum
+    assert call(L, tiled, n=0, line_stride=1, n_coarse=2, coarse_stride=1) == OK
+    assert call(L, tiled, n=0, line_stride=1, n_coarse=2, coarse_stride=2) == OK
+    assert call(L, tiled, coarse_stride=4) == CAPACITY
+    assert call(L, tiled, n=0, coarse_stride=4) == OK
+    assert call(L, tiled, n_coarse=1000) == CAPACITY
+    assert call(L, tiled, n_coarse=2**31 - 1) == CAPACITY
+    assert call(L, tiled, n=0, sweeps=4) == ARG
+    assert call(L, tiled, n=0, union_mask=0x200) == ARG
+    assert call(L, tiled, n=0, pid=None, b=None, x_out=None) == OK
+    assert call(L, tiled, n=0, x_in=None) == ARG
 
 
 @pytest.mark.parametrize("entry", WITH_REST)
@@ -255,3 +286,75 @@ def test_order_of_checks(L):
     assert call(L, "lmg_stencil_smooth_tiled_prolong", n=0, e_coarse=OUT) == ARG
     assert call(L, "lmg_stencil_smooth_prolong", n=0, e_coarse=OUT) == ARG
     assert call(L, "lmg_stencil_smooth_prolong", n=1, line_stride=1, e_coarse=OUT) == ARG
+    assert call(L, "lmg_stencil_cheby_tiled_prolong", n=0, e_coarse=OUT) == ARG
+
+
+@pytest.mark.parametrize("entry", CHEBY)
+def test_cheby_degree_and_coefficients(L, entry):
+    """The degree (1 .. 3) and the coefficient table are looked at in front of everything else, "nothing to do" included."""
+    for degree in (1, 2, 3):
+        assert call(L, entry, degree=degree) == CAPACITY
+    for degree in (0, 4, -1):
+        assert call(L, entry, degree=degree) == ARG
+    assert call(L, entry, h_coef=None) == ARG
+    nothing = dict(n=0, line_stride=0, pid=None, st_val=None, st_mask=None, b=None, x_out=None, r_out=None)
+    if "restrict" in entry:
+        assert call(L, entry, **nothing) == ARG                 # an empty fine grid has no coarse grid under it
+    else:
+        assert call(L, entry, **nothing) == OK
+    assert call(L, entry, h_coef=None, **nothing) == ARG
+    assert call(L, entry, degree=4, **nothing) == ARG
+
+
+# ---- the DIA passes: no pattern table, a row limit of their own, and no rule against stray bits of the slot set -------------
+DIA_ENTRY = {
+    "lmg_dia_smooth": ["n", "line_stride", "union_mask", "dia", "sweeps", "x_in", "b", "omega", "x_out", "r_out", "stream"],
+    "lmg_dia_cheby": ["n", "line_stride", "union_mask", "dia", "degree", "h_coef", "x_in", "b", "x_out", "r_out", "stream"],
+}
+DIA_BUILT = (M5, M7A, 0x0FE, M9)                    # the slot sets lmg_dia_smooth_supported answers for
+
+
+def dia_call(L, entry, **changes):
+    """complete() with the 1-D slot set, which the DIA pass is not built for: with no change, CAPACITY."""
+    a = complete(**dict(dict(union_mask=M1D), **changes))
+    assert a["n"] == 0 or a["union_mask"] not in DIA_BUILT, "this could launch"
+    return getattr(L, entry)(*[a[k] for k in DIA_ENTRY[entry]])
+
+
+@pytest.mark.parametrize("entry", sorted(DIA_ENTRY))
+def test_dia_pass(L, entry):
+    assert not L.lmg_dia_smooth_supported(M1D) and all(L.lmg_dia_smooth_supported(m) for m in DIA_BUILT)
+    assert dia_call(L, entry) == CAPACITY
+    for s in (1, 3):
+        assert dia_call(L, entry, sweeps=s) == CAPACITY
+    for s in (0, 4):
+        assert dia_call(L, entry, sweeps=s) == ARG
+    assert dia_call(L, entry, r_out=None) == CAPACITY
+    assert dia_call(L, entry, x_in=None) == CAPACITY             # the zero iterate
+    assert dia_call(L, entry, union_mask=0x200) == CAPACITY      # stray bits: just a slot set without a kernel
+    assert dia_call(L, entry, union_mask=0) == CAPACITY
+    for name in ("dia", "b", "x_out"):
+        assert dia_call(L, entry, **{name: None}) == ARG, name
+    assert dia_call(L, entry, x_in=OUT) == ARG
+    assert dia_call(L, entry, r_out=X) == ARG
+    assert dia_call(L, entry, r_out=OUT) == ARG
+    assert dia_call(L, entry, line_stride=2) == ARG
+    assert dia_call(L, entry, line_stride=82) == ARG             # longer than the vector
+    assert dia_call(L, entry, n=TILE_ROWS - 1, line_stride=3) == CAPACITY
+    assert dia_call(L, entry, n=TILE_ROWS) == ARG
+    assert dia_call(L, entry, n=-1) == ARG
+    # nothing to do: after the sizes and the sweep count, before the pointers and the line stride
+    nothing = dict(n=0, line_stride=0, dia=None, x_in=None, b=None, x_out=None, r_out=None)
+    assert dia_call(L, entry, **nothing) == OK
+    assert dia_call(L, entry, union_mask=M9, **nothing) == OK
+    assert dia_call(L, entry, sweeps=4, **nothing) == ARG
+    # a fault and a slot set without a kernel: the fault
+    assert dia_call(L, entry, union_mask=0x200, dia=None) == ARG
+
+
+def test_dia_cheby_coefficients(L):
+    """In front of everything else, like the tiled Chebyshev passes."""
+    entry = "lmg_dia_cheby"
+    assert dia_call(L, entry, degree=-1) == ARG
+    assert dia_call(L, entry, h_coef=None) == ARG
+    assert dia_call(L, entry, h_coef=None, n=0, line_stride=0, dia=None, x_in=None, b=None, x_out=None, r_out=None) == ARG
