@@ -61,6 +61,8 @@ import torch.distributed as dist
 
 from .ops import DeviceCSR, F64, I32
 
+_UNREACHED = 1 << 20           # _layer_of: "in none of the layers" (deeper than any halo)
+
 
 def block_bounds(n_units, world):
     """Contiguous split of n_units into `world` blocks, sizes differing by at most 1."""
@@ -102,6 +104,55 @@ def _take(vals, sources):
     return torch.cat([vals[src[1]:src[2]] if src[0] == "slice" else vals[src[1]] for src in sources])
 
 
+def _member(sorted_set, values):
+    """Mask of the `values` (int64) that occur in `sorted_set` (sorted int64, may be empty)."""
+    if sorted_set.numel() == 0:
+        return torch.zeros(values.shape, dtype=torch.bool, device=values.device)
+    pos = torch.searchsorted(sorted_set, values).clamp(max=sorted_set.numel() - 1)
+    return sorted_set[pos] == values
+
+
+def _layer_of(layers, cols):
+    """1-based index of the ghost layer (sorted int64 sets, layer 1 first) that holds each of `cols`;
+    _UNREACHED for a column in none of them."""
+    lay = torch.full((cols.numel(),), _UNREACHED, dtype=torch.long, device=cols.device)
+    for k, layer in enumerate(layers, 1):
+        lay = torch.where(_member(layer, cols), torch.full_like(lay, k), lay)
+    return lay
+
+
+def _local_operator(M, d, owned, real):
+    """Rows of the replicated matrix M in the layout of level d, [ghost rows below | owned rows | ghost rows above]:
+    `owned` is _rows(M, d.lo, d.hi); the ghost rows in the sorted set `real` carry their rows of M, the others are empty.
+    Returns (rowptr over d.n_tot rows, GLOBAL colidx, vals, sources); the entries and the sources (see _take) come in the
+    order [below, owned, above], which rebuild_numeric relies on."""
+    def ghost_rows(gset):
+        is_real = _member(real, gset)
+        cnt, ci, va, src = _gather_rows(M, gset[is_real], with_source=True)
+        counts = torch.zeros(gset.numel(), dtype=torch.long, device=gset.device)
+        counts[is_real] = cnt
+        return counts, ci, va, src
+
+    rp, ci, va, src = owned
+    parts = [ghost_rows(d.ghost_lo), ((rp[1:] - rp[:-1]).long(), ci, va, src), ghost_rows(d.ghost_hi)]
+    counts, cols, vals, sources = zip(*parts)
+    rowptr = torch.zeros(d.n_tot + 1, dtype=I32, device=va.device)
+    rowptr[1:] = torch.cumsum(torch.cat(counts), 0).to(I32)
+    return rowptr, torch.cat(cols), torch.cat(vals).contiguous(), list(sources)
+
+
+class _LevelSetup:
+    """What the setup steps of one distributed level hand to each other (this rank's view of the level)."""
+
+    def __init__(self, A, P, R):
+        self.A, self.P, self.R = A, P, R      # _rows() of the owned rows of A_l and P_l, and of the owned rows of level l+1 of R_l
+        self.layers = None                    # layers[k - 1]: the rows reached from the owned block in k hops through A_l (sorted)
+        self.real = None                      # sorted ghost rows that carry real rows: BOTH A and P take their real ghost rows from it
+        self.r_need = None                    # deepest ghost layer the restriction reads (_UNREACHED: beyond the halo)
+        self.ghosts = None                    # the level's sorted ghost set: what A_l, R_l and the ghost-carrying P_{l-1} reference
+        self.p_need = None                    # p_need[k]: deepest layer of level l+1 read by the P rows of the ghost layers <= k
+
+
 class _DLevel:
     """One distributed level on this rank.  Vector layout (length n_tot):
         [ghosts below lo | owned rows lo..hi | ghosts above hi]      (all in global order)
@@ -109,6 +160,23 @@ class _DLevel:
     on the diagonal (the kernels find the diagonal that way), every kernel takes whole
     vectors, and local column indices grow with the global ones (tile column spans stay small:
     the packed 16-bit column encoding keeps working)."""
+
+    def __init__(self, lo, hi, ghosts, device):
+        """Rows [lo, hi) of the level with the sorted ghost set `ghosts` (global row indices)."""
+        self.lo, self.hi, self.n_own = lo, hi, hi - lo
+        self.ghost_lo, self.ghost_hi = ghosts[ghosts < lo].contiguous(), ghosts[ghosts >= hi].contiguous()
+        self.n_lo, self.n_hi = int(self.ghost_lo.numel()), int(self.ghost_hi.numel())
+        self.n_tot = self.n_lo + self.n_own + self.n_hi
+        self.own = slice(self.n_lo, self.n_lo + self.n_own)
+        self.x, self.b, self.r, self.tmp = (torch.zeros(self.n_tot, dtype=F64, device=device) for _ in range(4))
+        # filled in by the later setup steps
+        self.recv = None                      # exchange plan: (source rank, first ghost slot, count) per message
+        self.send = None                      # ... and (peer, (first, end) slots or an index tensor, pack buffer or None)
+        self.A = self.P = self.R = None       # local operators (DeviceCSR); R: rows of level l+1, P: columns of level l+1
+        self.A_src = self.P_src = self.R_src = None   # where their values lie in the replicated operators (_take)
+        self.dinv = None                      # inverse diagonal of A
+        self.rows_global = None               # global row index of every layout slot
+        self.gs_sched = None                  # level schedule of the owned rows, built at the first Gauss-Seidel sweep
 
     def to_local(self, c):
         c = c.long()
@@ -122,6 +190,16 @@ class _DLevel:
         nnz = rp_owned[-1:]
         return torch.cat([torch.zeros(self.n_lo, dtype=I32, device=rp_owned.device), rp_owned,
                           nnz.expand(self.n_hi)]).contiguous()
+
+
+def _check_smoother(smoother):
+    """Refuse what the distributed cycle does not run (reads no instance state: callers check before any setup)."""
+    if smoother == "Chebyshev":
+        raise ValueError("the distributed V-cycle does not run the Chebyshev smoother (single-GPU hierarchies only); "
+                         "use 'Jacobi' or 'GaussSeidel'")
+    if smoother not in ("Jacobi", "GaussSeidel"):
+        raise ValueError("the distributed V-cycle supports the smoothers 'Jacobi' and 'GaussSeidel' "
+                         "(processor-block Gauss-Seidel), not %r" % (smoother,))
 
 
 class DistributedVCycle:
@@ -145,284 +223,70 @@ class DistributedVCycle:
         # per level, others before every sweep.  1 = the classic one-layer halo.
         self.halo_depth = max(1, int(halo_depth))
         self.n_exchanges = 0                      # halo exchanges issued so far (tests, bench)
-        nlev = len(full.levels)
-        sizes = [lev.n for lev in full.levels]
-        # ---- which levels are distributed -------------------------------------------------
-        self.n_dist = 0
-        for l in range(nlev - 1):                   # the coarsest level is always replicated
-            if sizes[l] >= replicate_below and sizes[l] >= 4 * self.world:
-                self.n_dist = l + 1
-            else:
-                break
-        if self.n_dist == 0:
-            raise ValueError("problem too small to distribute (fine level has %d rows)" % sizes[0])
-        # ---- row ranges per level ------------------------------------------------------------
-        self.bounds = []
-        side = grid_side
-        for l in range(self.n_dist + 1):
-            n = sizes[l]
-            if l == 0:
-                if side is not None and side * side == n:
-                    cuts = [c * side for c in block_bounds(side, self.world)]
-                else:
-                    side = None
-                    cuts = block_bounds(n, self.world)
-            else:
-                # coarse row c lives with the rank that owns its anchor fine row (the row of
-                # the largest entry of column c of P): coarse line j stays with fine line 2j
-                R = full.levels[l - 1].R
-                anchor = self._anchors(R)
-                prev = torch.tensor(self.bounds[l - 1], device=anchor.device, dtype=anchor.dtype)
-                cm = torch.cummax(anchor, 0).values
-                cuts = torch.searchsorted(cm, prev[:-1].contiguous()).tolist() + [n]
-                cuts[0] = 0
-            self.bounds.append([int(c) for c in cuts])
-        # ---- local slices + ghost sets ---------------------------------------------------------
-        raw = []
+        self.n_dist = self._choose_distributed_levels(replicate_below)
+        self.bounds, self.grid_side = self._row_bounds(grid_side)
+        setup = []
         for l in range(self.n_dist):
-            lo, hi = self.bounds[l][self.rank], self.bounds[l][self.rank + 1]
-            clo, chi = self.bounds[l + 1][self.rank], self.bounds[l + 1][self.rank + 1]
-            lev = full.levels[l]
-            raw.append({"A": _rows(lev.A, lo, hi), "P": _rows(lev.P, lo, hi), "R": _rows(lev.R, clo, chi)})
-        # The prolongation is applied on every ghost layer that carries real rows too, so that the
-        # corrected iterate needs no exchange before post-smoothing (see cycle()).
-        ghosts, real_ghosts, r_need, p_ghost_rows, layers_all = [], [], [], [], []
-        for l in range(self.n_dist):
-            lo, hi = self.bounds[l][self.rank], self.bounds[l][self.rank + 1]
-            A_l = full.levels[l].A
-
-            def outside(c, known):
-                c = c.long()
-                c = torch.unique(c[(c < lo) | (c >= hi)])
-                if known.numel():
-                    pos = torch.searchsorted(known, c).clamp(max=known.numel() - 1)
-                    c = c[known[pos] != c]
-                return c
-
-            # layer k = rows reached from the owned block in k hops through A_l; the rows of all
-            # layers but the last are kept as REAL rows of the local operator
-            known = torch.zeros(0, dtype=torch.long, device=A_l.vals.device)
-            frontier = outside(raw[l]["A"][1], known)
-            real = known
-            layers = []
-            for k in range(self.halo_depth):
-                layers.append(frontier)
-                known = torch.unique(torch.cat([known, frontier]))
-                if k + 1 == self.halo_depth or frontier.numel() == 0:
-                    break
-                real = known
-                frontier = outside(_gather_rows(A_l, frontier)[1], known)
-            # deepest ghost layer the restriction reads (a residual is exact on layer k only if x
-            # is exact on layer k + 1); columns that A does not reach within halo_depth hops at all
-            # rule the few-exchanges scheme out on this level
-            rc = outside(raw[l]["R"][1], known[:0])
-            need = 0
-            if rc.numel():
-                lay = torch.full((rc.numel(),), 1 << 20, dtype=torch.long, device=rc.device)
-                for k, fr in enumerate(layers, 1):
-                    if fr.numel():
-                        pos = torch.searchsorted(fr, rc).clamp(max=fr.numel() - 1)
-                        lay = torch.where(fr[pos] == rc, torch.full_like(lay, k), lay)
-                need = int(lay.max())
-            r_need.append(need)
-            p_ghost_rows.append(real)                  # ghost rows of this level that carry real P rows
-            layers_all.append(layers)
-            extra = [raw[l]["R"][1]]
-            if l > 0:
-                extra.append(raw[l - 1]["P"][1])
-                # ... and what the P rows of the finer level's inner ghost layers reference
-                extra.append(_gather_rows(full.levels[l - 1].P, p_ghost_rows[l - 1])[1])
-            known = torch.unique(torch.cat([known, outside(torch.cat(extra), known)]))
-            ghosts.append(known)                       # sorted
-            real_ghosts.append(real)
-        # p_need[l][k]: deepest ghost layer of level l+1 that the P rows of the level-l ghost layers
-        # <= k read (0: owned coarse rows only; the replicated level below the last distributed one
-        # is complete on every rank)
-        p_need = []
-        for l in range(self.n_dist):
-            need_k = [0] * (self.halo_depth + 1)
-            if l + 1 < self.n_dist:
-                clo, chi = self.bounds[l + 1][self.rank], self.bounds[l + 1][self.rank + 1]
-                worst = 0
-                for k in range(0, self.halo_depth):
-                    rows_k = None if k == 0 else (layers_all[l][k - 1] if k - 1 < len(layers_all[l]) else None)
-                    cols = raw[l]["P"][1] if k == 0 else (
-                        _gather_rows(full.levels[l].P, rows_k)[1] if rows_k is not None and rows_k.numel() else None)
-                    if cols is not None and cols.numel():
-                        c = torch.unique(cols.long())
-                        c = c[(c < clo) | (c >= chi)]
-                        if c.numel():
-                            lay = torch.full((c.numel(),), 1 << 20, dtype=torch.long, device=c.device)
-                            for kk, fr in enumerate(layers_all[l + 1], 1):
-                                if fr.numel():
-                                    pos = torch.searchsorted(fr, c).clamp(max=fr.numel() - 1)
-                                    lay = torch.where(fr[pos] == c, torch.full_like(lay, kk), lay)
-                            worst = max(worst, int(lay.max()))
-                    need_k[k] = worst
-                need_k[self.halo_depth] = worst
-            p_need.append(need_k)
-        gathered = [None] * self.world
-        dist.all_gather_object(gathered, [g.cpu().numpy() for g in ghosts] + [r_need, p_need], group=group)
-        # every rank must take the same branch of the cycle (the exchanges are collective)
-        self.r_need = [max(g[-2][l] for g in gathered) for l in range(self.n_dist)]
-        self.p_need = [[max(g[-1][l][k] for g in gathered) for k in range(self.halo_depth + 1)]
-                       for l in range(self.n_dist)]
-        self.dl = []
-        for l in range(self.n_dist):
-            d = _DLevel()
-            lo, hi = self.bounds[l][self.rank], self.bounds[l][self.rank + 1]
-            d.lo, d.hi, d.n_own = lo, hi, hi - lo
-            g = ghosts[l]
-            d.ghost_lo, d.ghost_hi = g[g < lo].contiguous(), g[g >= hi].contiguous()
-            d.n_lo, d.n_hi = int(d.ghost_lo.numel()), int(d.ghost_hi.numel())
-            d.n_tot = d.n_lo + d.n_own + d.n_hi
-            d.own = slice(d.n_lo, d.n_lo + d.n_own)
-            # exchange plan: per source rank one contiguous ghost segment (ghosts are sorted and
-            # ownership is contiguous)
-            gb = torch.tensor(self.bounds[l], device=g.device)
-            d.recv = []
-            for part, base in ((d.ghost_lo, 0), (d.ghost_hi, d.n_lo + d.n_own)):
-                if part.numel() == 0:
-                    continue
-                owner = torch.searchsorted(gb, part, right=True) - 1
-                for q in torch.unique(owner).tolist():
-                    idx = torch.nonzero(owner == q).flatten()
-                    d.recv.append((int(q), base + int(idx[0]), int(idx.numel())))
-            d.send = []
-            for q in range(self.world):
-                if q == self.rank:
-                    continue
-                want = gathered[q][l]
-                mine = want[(want >= lo) & (want < hi)] - lo + d.n_lo
-                if mine.size:
-                    if mine.size == int(mine[-1]) - int(mine[0]) + 1:
-                        # structured row blocks: the boundary grid line is one contiguous run,
-                        # sent straight out of the vector (no pack kernel, no staging buffer)
-                        d.send.append((q, (int(mine[0]), int(mine[-1]) + 1), None))
-                    else:
-                        d.send.append((q, torch.from_numpy(mine.astype(np.int32)).to(self.device),
-                                       torch.empty(mine.size, dtype=F64, device=self.device)))
-            for name in ("x", "b", "r", "tmp"):
-                setattr(d, name, torch.zeros(d.n_tot, dtype=F64, device=self.device))
-            self.dl.append(d)
-        # ---- the exchange plans of all ranks must pair up: a send without its receive would hang in RCCL, so
-        # check it here, once, where a mismatch can still raise ---------------------------------------------
-        plan = [([(q, (idx[1] - idx[0]) if isinstance(idx, tuple) else int(idx.numel())) for q, idx, _b in d.send],
-                 [(q, cnt) for q, _off, cnt in d.recv]) for d in self.dl]
-        plans = [None] * self.world
-        dist.all_gather_object(plans, plan, group=group)
-        for l in range(self.n_dist):
-            for p in range(self.world):
-                for q, cnt in plans[p][l][0]:
-                    if (p, cnt) not in plans[q][l][1]:
-                        raise RuntimeError("halo plan of level %d: rank %d sends %d values to rank %d, which does not "
-                                           "expect them" % (l, p, cnt, q))
-                for q, cnt in plans[p][l][1]:
-                    if (p, cnt) not in plans[q][l][0]:
-                        raise RuntimeError("halo plan of level %d: rank %d expects %d values from rank %d, which does "
-                                           "not send them" % (l, p, cnt, q))
-        # ---- local operators in the level layouts -------------------------------------------------
-        for l in range(self.n_dist):
-            d = self.dl[l]
-            rp, ci, va, src_own = raw[l]["A"]
-            A_l = full.levels[l].A
-            rg = real_ghosts[l]
-            parts_rp, parts_ci, parts_va, d.A_src = [], [], [], []
-            for gset in (d.ghost_lo, None, d.ghost_hi):
-                if gset is None:
-                    parts_rp.append((rp[1:] - rp[:-1]).long())
-                    parts_ci.append(ci)
-                    parts_va.append(va)
-                    d.A_src.append(src_own)
-                    continue
-                if gset.numel() and rg.numel():
-                    pos = torch.searchsorted(rg, gset).clamp(max=rg.numel() - 1)
-                    is_real = rg[pos] == gset
-                else:
-                    is_real = torch.zeros(gset.numel(), dtype=torch.bool, device=gset.device)
-                cnt, gci, gva, gsrc = _gather_rows(A_l, gset[is_real], with_source=True)
-                full_cnt = torch.zeros(gset.numel(), dtype=torch.long, device=gset.device)
-                full_cnt[is_real] = cnt
-                parts_rp.append(full_cnt)
-                parts_ci.append(gci)
-                parts_va.append(gva)
-                d.A_src.append(gsrc)
-            counts = torch.cat(parts_rp)
-            rp_loc = torch.zeros(d.n_tot + 1, dtype=I32, device=va.device)
-            rp_loc[1:] = torch.cumsum(counts, 0).to(I32)
-            d.A = DeviceCSR(rp_loc, d.to_local(torch.cat(parts_ci)).to(I32).contiguous(),
-                            torch.cat(parts_va).contiguous(), (d.n_tot, d.n_tot))
-            d.rows_global = torch.cat([d.ghost_lo, torch.arange(d.lo, d.hi, device=va.device), d.ghost_hi])
-            d.dinv = self.ops.csr_inverse_diagonal(d.A)
-            rp, ci, va, src_r = raw[l]["R"]               # rows: level l+1, columns: level l
-            rp_p, ci_p, va_p, src_p = raw[l]["P"]         # rows: level l,   columns: level l+1
-            d.R_src = [src_r]
-            # P rows: owned rows + the inner ghost layers (real), other ghost rows empty
-            P_l = full.levels[l].P
-            pg = p_ghost_rows[l]
-            pp_rp, pp_ci, pp_va, d.P_src = [], [], [], []
-            for gset in (d.ghost_lo, None, d.ghost_hi):
-                if gset is None:
-                    pp_rp.append((rp_p[1:] - rp_p[:-1]).long())
-                    pp_ci.append(ci_p)
-                    pp_va.append(va_p)
-                    d.P_src.append(src_p)
-                    continue
-                if gset.numel() and pg.numel():
-                    pos = torch.searchsorted(pg, gset).clamp(max=pg.numel() - 1)
-                    is_real = pg[pos] == gset
-                else:
-                    is_real = torch.zeros(gset.numel(), dtype=torch.bool, device=gset.device)
-                cnt, gci, gva, gsrc = _gather_rows(P_l, gset[is_real], with_source=True)
-                full_cnt = torch.zeros(gset.numel(), dtype=torch.long, device=gset.device)
-                full_cnt[is_real] = cnt
-                pp_rp.append(full_cnt)
-                pp_ci.append(gci)
-                pp_va.append(gva)
-                d.P_src.append(gsrc)
-            rp_ploc = torch.zeros(d.n_tot + 1, dtype=I32, device=va.device)
-            rp_ploc[1:] = torch.cumsum(torch.cat(pp_rp), 0).to(I32)
-            ci_ploc, va_ploc = torch.cat(pp_ci), torch.cat(pp_va).contiguous()
-            if l + 1 < self.n_dist:
-                nxt = self.dl[l + 1]
-                d.R = DeviceCSR(nxt.embed_rows(rp), d.to_local(ci).to(I32).contiguous(), va.contiguous(),
-                                (nxt.n_tot, d.n_tot))
-                d.P = DeviceCSR(rp_ploc, nxt.to_local(ci_ploc).to(I32).contiguous(), va_ploc, (d.n_tot, nxt.n_tot))
-            else:                                         # next level is replicated on every rank
-                nrows = self.bounds[l + 1][self.rank + 1] - self.bounds[l + 1][self.rank]
-                d.R = DeviceCSR(rp.contiguous(), d.to_local(ci).to(I32).contiguous(), va.contiguous(),
-                                (nrows, d.n_tot))
-                d.P = DeviceCSR(rp_ploc, ci_ploc.contiguous(), va_ploc, (d.n_tot, full.levels[l + 1].n))
+            setup.append(self._ghost_layers(l, setup[l - 1] if l else None))
+        for l, s in enumerate(setup):
+            s.p_need = self._prolongation_needs(l, s, setup[l + 1] if l + 1 < self.n_dist else None)
+        wanted = self._agree_on_needs(setup)                     # collective
+        self.dl = [self._make_level(l, s.ghosts, [w[l] for w in wanted]) for l, s in enumerate(setup)]
+        self._check_plans_pair_up()                              # collective
+        for l, s in enumerate(setup):
+            self._cut_local_operators(l, s)
         if getattr(full, "use_packed", False):
-            for l, d in enumerate(self.dl):
-                d.A.pack()
-                # local blocks are whole grid lines: their transfers are grid transfers with these line lengths
-                # (row patterns relative to a column-base map instead of a packed CSR stream)
-                wf, wc = math.isqrt(sizes[l]), math.isqrt(sizes[l + 1])
-                hint = (wf, wc) if (side is not None and wf * wf == sizes[l] and wc * wc == sizes[l + 1]) else None
-                for M in (d.R, d.P):
-                    # (DeviceCSR.pack is the same method whatever ops module drives the kernels: always takes the hint)
-                    M.pack(line_strides=hint)
-        # ---- all-gather plumbing for the first replicated level ----------------------------------
-        L = self.n_dist
-        cb = self.bounds[L]
-        self.ag_max = max(cb[p + 1] - cb[p] for p in range(self.world))
-        self.ag_send = torch.zeros(self.ag_max, dtype=F64, device=self.device)
-        self.ag_recv = torch.zeros(self.ag_max * self.world, dtype=F64, device=self.device)
-        idx = np.concatenate([np.arange(cb[p + 1] - cb[p]) + p * self.ag_max for p in range(self.world)])
-        self.ag_index = torch.from_numpy(idx.astype(np.int32)).to(self.device)
-        self.ag_rows = cb[self.rank + 1] - cb[self.rank]
+            self._pack_twins()
+        self._setup_all_gather()
         self.use_tail_graph = True
         self._tail_graphs = {}
         self.partials = torch.empty(max(1024, self.ops.partials_count(self.dl[0].n_tot)), dtype=F64,
                                     device=self.device)
         self.norm2 = torch.zeros(1, dtype=F64, device=self.device)
 
-    # ------------------------------------------------------------------------------------------
     @classmethod
     def from_problem(cls, A, transfers, device, ops_mod=None, **kw):
         from .hierarchy import Hierarchy
         return cls(Hierarchy(A, transfers, device, ops_mod=ops_mod), device, ops_mod=ops_mod, **kw)
+
+    # ---- setup, in the order __init__ runs it ----------------------------------------------------------
+    def _own(self, l):
+        """This rank's row range [lo, hi) of level l."""
+        return self.bounds[l][self.rank], self.bounds[l][self.rank + 1]
+
+    def _choose_distributed_levels(self, replicate_below):
+        """Level sizes, world size -> number of distributed levels: the leading levels with at least `replicate_below`
+        rows (and 4 per rank); the coarsest level is always replicated."""
+        n_dist = 0
+        for lev in self.full.levels[:-1]:
+            if lev.n < replicate_below or lev.n < 4 * self.world:
+                break
+            n_dist += 1
+        if n_dist == 0:
+            raise ValueError("problem too small to distribute (fine level has %d rows)" % self.full.levels[0].n)
+        return n_dist
+
+    def _row_bounds(self, grid_side):
+        """The caller's grid side, R of the distributed levels -> (bounds, effective grid side): bounds[l] holds the
+        world + 1 row cuts of level l, for l = 0 .. n_dist (the first replicated level is cut too: the all-gather); the
+        effective side is `grid_side` when the fine level is that square grid -- its cuts then fall on grid lines --
+        and None otherwise."""
+        n = self.full.levels[0].n
+        if grid_side is not None and grid_side * grid_side == n:
+            bounds = [[c * grid_side for c in block_bounds(grid_side, self.world)]]
+        else:
+            grid_side = None
+            bounds = [block_bounds(n, self.world)]
+        for l in range(1, self.n_dist + 1):
+            # coarse row c lives with the rank that owns its anchor fine row (the row of
+            # the largest entry of column c of P): coarse line j stays with fine line 2j
+            anchor = self._anchors(self.full.levels[l - 1].R)
+            prev = torch.tensor(bounds[l - 1], device=anchor.device, dtype=anchor.dtype)
+            cm = torch.cummax(anchor, 0).values
+            cuts = torch.searchsorted(cm, prev[:-1].contiguous()).tolist() + [self.full.levels[l].n]
+            cuts[0] = 0
+            bounds.append([int(c) for c in cuts])
+        return bounds, grid_side
 
     @staticmethod
     def _anchors(R):
@@ -438,6 +302,170 @@ class DistributedVCycle:
         anchor = anchor.scatter_reduce(0, rows, cand, reduce="amin", include_self=True)
         anchor = torch.where(anchor == 2 ** 62, torch.zeros_like(anchor), anchor)   # empty rows
         return anchor
+
+    def _ghost_layers(self, l, finer):
+        """Bounds, the replicated operators of level l and the finer level's record (None on the fine level) -> the
+        record of level l with its owned slices, ghost `layers`, the `real` row set, `r_need` and the sorted `ghosts`."""
+        lo, hi = self._own(l)
+        lev = self.full.levels[l]
+        s = _LevelSetup(_rows(lev.A, lo, hi), _rows(lev.P, lo, hi), _rows(lev.R, *self._own(l + 1)))
+
+        def outside(c, known=None):
+            """The distinct columns outside the owned block (and not in `known`), sorted."""
+            c = c.long()
+            c = torch.unique(c[(c < lo) | (c >= hi)])
+            return c if known is None else c[~_member(known, c)]
+
+        # layer k = rows reached from the owned block in k hops through A_l; the rows of all
+        # layers but the last are kept as REAL rows of the local operator
+        frontier = outside(s.A[1])
+        known = s.real = frontier.new_zeros(0)
+        s.layers = []
+        for k in range(self.halo_depth):
+            s.layers.append(frontier)
+            known = torch.unique(torch.cat([known, frontier]))
+            if k + 1 == self.halo_depth or frontier.numel() == 0:
+                break
+            s.real = known
+            frontier = outside(_gather_rows(lev.A, frontier)[1], known)
+        # deepest ghost layer the restriction reads (a residual is exact on layer k only if x
+        # is exact on layer k + 1); columns that A does not reach within halo_depth hops at all
+        # rule the few-exchanges scheme out on this level
+        rc = outside(s.R[1])
+        s.r_need = int(_layer_of(s.layers, rc).max()) if rc.numel() else 0
+        # The prolongation is applied on every ghost layer that carries real rows too, so that the
+        # corrected iterate needs no exchange before post-smoothing (see cycle()): the ghost set also
+        # covers what the finer level's P rows reference, owned ones and those of its inner ghost layers
+        extra = [s.R[1]]
+        if finer is not None:
+            extra += [finer.P[1], _gather_rows(self.full.levels[l - 1].P, finer.real)[1]]
+        s.ghosts = torch.unique(torch.cat([known, outside(torch.cat(extra), known)]))
+        return s
+
+    def _prolongation_needs(self, l, s, coarser):
+        """The records of level l and of level l+1 (None when that one is replicated) -> p_need of level l: p_need[k] is
+        the deepest ghost layer of level l+1 that the P rows of the level-l ghost layers <= k read (0: owned coarse
+        rows only; a replicated level is complete on every rank)."""
+        D = self.halo_depth
+        if coarser is None:
+            return [0] * (D + 1)
+        clo, chi = self._own(l + 1)
+        need, worst = [], 0
+        for rows in [None] + s.layers[:D - 1]:                    # owned rows, then layer 1, 2, ...
+            c = torch.unique((s.P[1] if rows is None else _gather_rows(self.full.levels[l].P, rows)[1]).long())
+            c = c[(c < clo) | (c >= chi)]
+            if c.numel():
+                worst = max(worst, int(_layer_of(coarser.layers, c).max()))
+            need.append(worst)
+        return need + [worst] * (D + 1 - len(need))
+
+    def _agree_on_needs(self, setup):
+        """The ranks' records -> self.r_need, self.p_need (the maximum over the ranks: every rank must take the same
+        branch of the cycle, the exchanges are collective); returns, per rank, the ghost sets of its levels as host arrays.
+        The first of the two setup collectives."""
+        mine = [s.ghosts.cpu().numpy() for s in setup] + [[s.r_need for s in setup], [s.p_need for s in setup]]
+        gathered = [None] * self.world
+        dist.all_gather_object(gathered, mine, group=self.group)
+        self.r_need = [max(g[-2][l] for g in gathered) for l in range(self.n_dist)]
+        self.p_need = [[max(g[-1][l][k] for g in gathered) for k in range(self.halo_depth + 1)]
+                       for l in range(self.n_dist)]
+        return [g[:-2] for g in gathered]
+
+    def _make_level(self, l, ghosts, wanted):
+        """This rank's sorted ghost set of level l and every rank's (`wanted[q]`, host arrays) -> the _DLevel with its
+        exchange plan: what to receive into which ghost slots, which owned slots to send to whom."""
+        lo, hi = self._own(l)
+        d = _DLevel(lo, hi, ghosts, self.device)
+        # per source rank one contiguous ghost segment (ghosts are sorted and ownership is contiguous)
+        gb = torch.tensor(self.bounds[l], device=ghosts.device)
+        d.recv = []
+        for part, base in ((d.ghost_lo, 0), (d.ghost_hi, d.n_lo + d.n_own)):
+            if part.numel() == 0:
+                continue
+            owner = torch.searchsorted(gb, part, right=True) - 1
+            for q in torch.unique(owner).tolist():
+                idx = torch.nonzero(owner == q).flatten()
+                d.recv.append((int(q), base + int(idx[0]), int(idx.numel())))
+        d.send = []
+        for q in range(self.world):
+            if q == self.rank:
+                continue
+            want = wanted[q]
+            mine = want[(want >= lo) & (want < hi)] - lo + d.n_lo
+            if mine.size:
+                if mine.size == int(mine[-1]) - int(mine[0]) + 1:
+                    # structured row blocks: the boundary grid line is one contiguous run,
+                    # sent straight out of the vector (no pack kernel, no staging buffer)
+                    d.send.append((q, (int(mine[0]), int(mine[-1]) + 1), None))
+                else:
+                    d.send.append((q, torch.from_numpy(mine.astype(np.int32)).to(self.device),
+                                   torch.empty(mine.size, dtype=F64, device=self.device)))
+        return d
+
+    def _check_plans_pair_up(self):
+        """The exchange plans of self.dl -> nothing, or an error: a send without its receive would hang in RCCL, so the
+        plans of all ranks are compared here, once, where a mismatch can still raise.  The second setup collective."""
+        plan = [([(q, (idx[1] - idx[0]) if isinstance(idx, tuple) else int(idx.numel())) for q, idx, _b in d.send],
+                 [(q, cnt) for q, _off, cnt in d.recv]) for d in self.dl]
+        plans = [None] * self.world
+        dist.all_gather_object(plans, plan, group=self.group)
+        for l in range(self.n_dist):
+            for p in range(self.world):
+                for q, cnt in plans[p][l][0]:
+                    if (p, cnt) not in plans[q][l][1]:
+                        raise RuntimeError("halo plan of level %d: rank %d sends %d values to rank %d, which does not "
+                                           "expect them" % (l, p, cnt, q))
+                for q, cnt in plans[p][l][1]:
+                    if (p, cnt) not in plans[q][l][0]:
+                        raise RuntimeError("halo plan of level %d: rank %d expects %d values from rank %d, which does "
+                                           "not send them" % (l, p, cnt, q))
+
+    def _cut_local_operators(self, l, s):
+        """The record of level l, self.dl[l] and (for the column layout of P and the row layout of R) self.dl[l + 1] ->
+        the local A, P, R of self.dl[l] with their value sources, its inverse diagonal and rows_global."""
+        d, lev = self.dl[l], self.full.levels[l]
+        rp, ci, va, d.A_src = _local_operator(lev.A, d, s.A, s.real)
+        d.A = DeviceCSR(rp, d.to_local(ci).to(I32).contiguous(), va, (d.n_tot, d.n_tot))
+        d.rows_global = torch.cat([d.ghost_lo, torch.arange(d.lo, d.hi, device=va.device), d.ghost_hi])
+        d.dinv = self.ops.csr_inverse_diagonal(d.A)
+        # P rows: owned rows + the inner ghost layers (real), other ghost rows empty
+        rp_p, ci_p, va_p, d.P_src = _local_operator(lev.P, d, s.P, s.real)      # rows: level l,   columns: level l+1
+        rp, ci, va, src_r = s.R                                                 # rows: level l+1, columns: level l
+        d.R_src = [src_r]
+        if l + 1 < self.n_dist:
+            nxt = self.dl[l + 1]
+            d.R = DeviceCSR(nxt.embed_rows(rp), d.to_local(ci).to(I32).contiguous(), va.contiguous(),
+                            (nxt.n_tot, d.n_tot))
+            d.P = DeviceCSR(rp_p, nxt.to_local(ci_p).to(I32).contiguous(), va_p, (d.n_tot, nxt.n_tot))
+        else:                                         # next level is replicated on every rank
+            clo, chi = self._own(l + 1)
+            d.R = DeviceCSR(rp.contiguous(), d.to_local(ci).to(I32).contiguous(), va.contiguous(),
+                            (chi - clo, d.n_tot))
+            d.P = DeviceCSR(rp_p, ci_p.contiguous(), va_p, (d.n_tot, self.full.levels[l + 1].n))
+
+    def _pack_twins(self):
+        """The local operators, the level sizes and the effective grid side -> their lossless twins (in place)."""
+        for l, d in enumerate(self.dl):
+            d.A.pack()
+            # local blocks are whole grid lines: their transfers are grid transfers with these line lengths
+            # (row patterns relative to a column-base map instead of a packed CSR stream)
+            nf, nc = self.full.levels[l].n, self.full.levels[l + 1].n
+            wf, wc = math.isqrt(nf), math.isqrt(nc)
+            hint = (wf, wc) if (self.grid_side is not None and wf * wf == nf and wc * wc == nc) else None
+            for M in (d.R, d.P):
+                # (DeviceCSR.pack is the same method whatever ops module drives the kernels: always takes the hint)
+                M.pack(line_strides=hint)
+
+    def _setup_all_gather(self):
+        """The bounds of the first replicated level -> the all-gather plumbing: every rank sends ag_max values (its
+        ag_rows owned rows first), ag_index picks the owned rows of all ranks out of the gathered buffer in global order."""
+        cb = self.bounds[self.n_dist]
+        self.ag_max = max(cb[p + 1] - cb[p] for p in range(self.world))
+        self.ag_send = torch.zeros(self.ag_max, dtype=F64, device=self.device)
+        self.ag_recv = torch.zeros(self.ag_max * self.world, dtype=F64, device=self.device)
+        idx = np.concatenate([np.arange(cb[p + 1] - cb[p]) + p * self.ag_max for p in range(self.world)])
+        self.ag_index = torch.from_numpy(idx.astype(np.int32)).to(self.device)
+        self.ag_rows = cb[self.rank + 1] - cb[self.rank]
 
     # ---- communication -----------------------------------------------------------------------------
     def exchange(self, d, vec):
@@ -465,6 +493,21 @@ class DistributedVCycle:
             req.wait()
         for dst, host in landing:
             dst.copy_(host)
+
+    def _all_gather(self, send, recv):
+        """`send` of every rank, in rank order, into `recv` (through the host when gloo drives GPU ranks)."""
+        if self.host_staged:
+            host = torch.empty(recv.numel(), dtype=F64)
+            dist.all_gather_into_tensor(host, send.cpu(), group=self.group)
+            recv.copy_(host)
+        else:
+            dist.all_gather_into_tensor(recv, send, group=self.group)
+
+    def _all_reduce_norm(self):
+        """Square root of self.norm2 summed over the ranks (through the host when gloo drives GPU ranks)."""
+        total = self.norm2.cpu() if self.host_staged else self.norm2
+        dist.all_reduce(total, op=dist.ReduceOp.SUM, group=self.group)
+        return math.sqrt(total.item())
 
     def set_rhs(self, rhs):
         d = self.dl[0]
@@ -527,7 +570,7 @@ class DistributedVCycle:
     def _owned_gs_schedule(self, d):
         """Level schedule of the exact forward sweep over the OWNED rows of a local block (dependencies among owned rows
         only: ghost columns are constants of the sweep), as local row indices; built once per level."""
-        if getattr(d, "gs_sched", None) is None:
+        if d.gs_sched is None:
             import scipy.sparse as sp
             rp = d.A.rowptr.cpu().numpy().astype(np.int64)
             ci = d.A.colidx.cpu().numpy().astype(np.int64)
@@ -566,12 +609,7 @@ class DistributedVCycle:
     def cycle(self, smoother, steps, omega=1.0, l=0, x_is_zero=False):
         """One V-cycle from level l down.  Returns the number of ghost layers on which this level's
         iterate is exact afterwards (what the caller may prolongate from without a message)."""
-        if smoother == "Chebyshev":
-            raise ValueError("the distributed V-cycle does not run the Chebyshev smoother (single-GPU hierarchies only); "
-                             "use 'Jacobi' or 'GaussSeidel'")
-        if smoother not in ("Jacobi", "GaussSeidel"):
-            raise ValueError("the distributed V-cycle supports the smoothers 'Jacobi' and 'GaussSeidel' "
-                             "(processor-block Gauss-Seidel), not %r" % (smoother,))
+        _check_smoother(smoother)
         gs = smoother == "GaussSeidel"
         o = self.ops
         d = self.dl[l]
@@ -610,12 +648,7 @@ class DistributedVCycle:
         else:
             fl = self.full.levels[l + 1]
             o.csr_spmv(d.R, d.r, self.ag_send[:self.ag_rows], 1.0, 0.0)
-            if self.host_staged:
-                recv = torch.empty(self.ag_recv.numel(), dtype=F64)
-                dist.all_gather_into_tensor(recv, self.ag_send.cpu(), group=self.group)
-                self.ag_recv.copy_(recv)
-            else:
-                dist.all_gather_into_tensor(self.ag_recv, self.ag_send, group=self.group)
+            self._all_gather(self.ag_send, self.ag_recv)
             o.gather(self.ag_index, self.ag_recv, fl.b)
             self._replicated_tail(smoother, steps, omega, l + 1)
             o.csr_spmv(d.P, fl.x, d.x, 1.0, 1.0)      # the replicated correction is complete on every rank
@@ -678,12 +711,7 @@ class DistributedVCycle:
         self.ops.csr_residual_norm2(d.A, d.x, d.b, d.r, None, None)
         r_own = d.r[d.own]                              # ghost rows are real rows: count the owned ones only
         self.ops.dot(r_own, r_own, self.partials, self.norm2)
-        if self.host_staged:
-            h = self.norm2.cpu()
-            dist.all_reduce(h, op=dist.ReduceOp.SUM, group=self.group)
-            return math.sqrt(h.item())
-        dist.all_reduce(self.norm2, op=dist.ReduceOp.SUM, group=self.group)
-        return math.sqrt(self.norm2.item())
+        return self._all_reduce_norm()
 
     def make_step(self, smoother, steps, omega, graph=False):
         """One V-cycle as a callable.  `graph` is accepted for symmetry with Hierarchy.captured_cycle: the replicated tail
@@ -691,9 +719,7 @@ class DistributedVCycle:
         messages of the distributed levels are launched eagerly -- capturing each of them was measured at world size 1
         (2049^2: 0.592 ms with segment graphs vs 0.576 eager) and dropped, RCCL point-to-point inside a captured graph has
         not been tried on this pool."""
-        if smoother == "Chebyshev":                   # (now, not at the first step)
-            raise ValueError("the distributed V-cycle does not run the Chebyshev smoother (single-GPU hierarchies only); "
-                             "use 'Jacobi' or 'GaussSeidel'")
+        _check_smoother(smoother)                     # (now, not at the first step)
 
         def step():
             self.cycle(smoother, steps, omega)
