@@ -4,36 +4,21 @@ PyTorch custom ops (`torch.ops.lmg.*`).
 PyTorch is plumbing here: it owns device memory and the current HIP stream; every
 arithmetic step is a hand-written gfx950 kernel reached through ctypes.  The same
 Python callables back the `torch.ops.lmg.*` ops and the solver's internal calls.
+
+What lives here: DeviceCSR and its pack() policy -- which of the storage twins of twins.py an operator gets --, every
+enable switch and size threshold that picks a kernel, and one wrapper per entry point: sweeps, fused smoothing passes,
+Gauss-Seidel, vectors, dense blocks, SpGEMM, hipGraph capture.  The twins themselves -- their formats, their construction
+and the C arguments that describe them -- are in twins.py and re-exported here under their old names.
 """
 import ctypes
-import math
 
 import numpy as np
 import torch
 
 from . import _lib
 from ._lib import LmgError, check
-
-F64 = torch.float64
-I32 = torch.int32
-
-
-def _s(*ts):
-    """The HIP stream the launch goes to: the current stream of the device that holds the tensors (the first
-    device tensor among `ts`), or of the current device when none is given."""
-    for t in ts:
-        if t is not None and getattr(t, "is_cuda", False):
-            if t.device.index != torch.cuda.current_device():
-                # a HIP launch goes to the CURRENT device: refuse loudly instead of launching there with another
-                # device's pointers (the solver classes switch devices themselves: solvers.Solver.on_device)
-                raise LmgError("operands live on %s but the current device is cuda:%d: wrap the call in "
-                               "torch.cuda.device(...)" % (t.device, torch.cuda.current_device()))
-            return torch.cuda.current_stream(t.device).cuda_stream
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
+from .twins import (F64, I32, DiaTwin, PackedCSR, ProlongTwin, RestrictTwin, RowPatterns, SellCSR,  # noqa: F401
+                    StencilTwin, _p, _s)
 
 
 def _vec_ok(*ts):
@@ -85,9 +70,7 @@ class DeviceCSR:
                     self.patterns = RowPatterns.from_csr(self, gm)
                     if self.patterns is not None:
                         break
-            self.stencil = StencilTwin.from_patterns(self.patterns, self.shape) if _STENCIL_ENABLED else None
-            self.prolong = ProlongTwin.from_patterns(self.patterns, self.shape) if _STENCIL_ENABLED else None
-            self.restrict = RestrictTwin.from_patterns(self.patterns, self.shape) if _STENCIL_ENABLED else None
+            self._derive_grid_twins()
         if patterns and self.patterns is not None:
             return self.patterns
         if self.sell is not None:
@@ -110,22 +93,20 @@ class DeviceCSR:
                     return self.sell
         return self.packed
 
+    def _derive_grid_twins(self):
+        """stencil, prolong, restrict: the window views of `patterns` the fused passes read (None where it has none)."""
+        self.stencil, self.prolong, self.restrict = (
+            T.from_patterns(self.patterns, self.shape) if _STENCIL_ENABLED else None
+            for T in (StencilTwin, ProlongTwin, RestrictTwin))
+
     def invalidate_packed(self):
-        self.packed = None
-        self.patterns = None
-        self.sell = None
-        self.stencil = None
-        self.prolong = None
-        self.restrict = None
-        self.dia = None
+        self.packed = self.patterns = self.sell = self.stencil = self.prolong = self.restrict = self.dia = None
 
     def repack_values(self):
         """After the values changed in place: refresh the twins (cheaply if possible)."""
         if self.patterns is not None:
             self.patterns = RowPatterns.from_csr(self, self.patterns.grid_map)
-            self.stencil = StencilTwin.from_patterns(self.patterns, self.shape) if _STENCIL_ENABLED else None
-            self.prolong = ProlongTwin.from_patterns(self.patterns, self.shape) if _STENCIL_ENABLED else None
-            self.restrict = RestrictTwin.from_patterns(self.patterns, self.shape) if _STENCIL_ENABLED else None
+            self._derive_grid_twins()
             if self.patterns is None:
                 self.pack()
         if self.sell is not None:
@@ -195,625 +176,6 @@ class DeviceCSR:
         return 12 * self.nnz + 4 * (self.shape[0] + 1)
 
 
-class PackedCSR:
-    """Lossless packed twin of a DeviceCSR for lmg_pcsr_sweep (see include/lmg.h):
-    uint8 row lengths, uint16 tile-relative columns when every 512-row tile spans < 65536
-    columns, and a value dictionary (uint8 / uint16 indices) when the matrix has few
-    distinct values -- compared BITWISE, so -0.0 / NaN payloads survive.  Built at setup by the
-    kernels of csrc/pack.hip (format conversion, like SciPy's csc -> csr)."""
-
-    __slots__ = ("n", "nnz", "shape", "tile_rows", "tile_cap", "tile_base", "tile_colbase", "rowlen", "col",
-                 "colmode", "val", "valmode", "dict", "ndict", "bytes_")
-
-    @staticmethod
-    def _padded(t):
-        raw = t.contiguous().view(torch.uint8)
-        out = torch.zeros(((raw.numel() + 15) // 16) * 16 + 16, dtype=torch.uint8, device=t.device)
-        out[: raw.numel()] = raw
-        return out
-
-    _VSET_SLOTS = 1 << 20          # uint64 slots of the distinct-value table (8 MB)
-    _VSET_LIMIT = 65536            # more distinct values than this: raw fp64 stream
-
-    @staticmethod
-    def _padded_empty(nbytes, device):
-        return torch.zeros(((nbytes + 15) // 16) * 16 + 16, dtype=torch.uint8, device=device)
-
-    @classmethod
-    def _distinct_values(cls, vals, limit=None):
-        """Sorted (as signed 64-bit patterns) distinct values of `vals`, or None when there are
-        more than `limit` (default _VSET_LIMIT) of them.  Hash-set kernel + a sort of the few
-        survivors instead of sorting all nnz values."""
-        L = _lib.lib()
-        dev = vals.device
-        limit = cls._VSET_LIMIT if limit is None else int(limit)
-        table = torch.full((cls._VSET_SLOTS,), -1, dtype=torch.int64, device=dev)
-        state = torch.zeros(4, dtype=I32, device=dev)
-        check(L.lmg_value_set_insert(vals.numel(), _p(vals), _p(table), cls._VSET_SLOTS, limit,
-                                     _p(state), _s(vals)), "lmg_value_set_insert")
-        st = state.cpu()
-        if int(st[1]):
-            return None
-        # the few survivors: collected by an own kernel, sorted on the host (a library sort / mask / cat each cost
-        # 50 - 75 ms of code-object loading in a fresh process)
-        cap = limit + 8
-        out = torch.empty(cap, dtype=torch.int64, device=dev)
-        cnt = torch.zeros(1, dtype=I32, device=dev)
-        check(L.lmg_value_set_collect(_p(table), cls._VSET_SLOTS, _p(out), cap, _p(cnt), _s(vals)), "lmg_value_set_collect")
-        k = int(cnt.cpu()[0])
-        if k > cap:
-            return None
-        keys = out[:k].cpu().numpy()
-        if int(st[2]):
-            keys = np.concatenate([keys, np.array([-1], dtype=np.int64)])
-        if keys.size > limit:
-            return None
-        return torch.from_numpy(np.sort(keys)).to(dev)
-
-    @staticmethod
-    def _encode_values(vals, uniq, width, out):
-        missing = torch.zeros(1, dtype=I32, device=vals.device)
-        check(_lib.lib().lmg_value_encode(vals.numel(), _p(vals), _p(uniq), int(uniq.numel()), width, _p(out),
-                                          _p(missing), _s(vals)), "lmg_value_encode")
-        if int(missing):
-            raise LmgError("value dictionary does not cover the matrix values")
-
-    @classmethod
-    def from_csr(cls, A):
-        n, nnz = A.shape[0], A.nnz
-        if n == 0 or nnz == 0:
-            return None
-        L = _lib.lib()
-        dev = A.vals.device
-        rowlen = (A.rowptr[1:] - A.rowptr[:-1])
-        if int(rowlen.max()) > 255 or int(rowlen.min()) < 0:
-            return None
-        # value encoding first: it decides how many bytes an entry occupies in LDS
-        uniq = cls._distinct_values(A.vals)
-        ndict = int(uniq.numel()) if uniq is not None else 1 << 30
-        # tile height: 512 rows unless the rows are so long that a tile would not leave room for
-        # several workgroups per CU (budget ~20 KB of LDS per tile); long-row tiles only exist
-        # for the VAL8 / VAL64 encodings
-        avg = nnz / n
-        T = int(L.lmg_pcsr_tile_rows())
-        bpe = 2 + (1 if ndict <= 256 else (2 if ndict <= 65536 else 8))
-        if T * avg * bpe > 20480:
-            T = 128 if 128 * avg * (2 + (1 if ndict <= 256 else 8)) <= 20480 else 64
-            if 256 < ndict <= 65536:
-                ndict = 1 << 30                    # force raw values
-        ntile = (n + T - 1) // T
-        tb = A.rowptr[0:n:T]
-        tile_base = torch.cat([tb, A.rowptr[n:n + 1]]).contiguous()
-        tile_nnz = tile_base[1:] - tile_base[:-1]
-        self = cls()
-        self.n, self.nnz, self.shape = n, nnz, A.shape
-        self.tile_rows = T
-        self.tile_cap = int(tile_nnz.max())
-        self.tile_base = tile_base
-        self.rowlen = rowlen.to(torch.uint8).contiguous()
-        cmin = torch.empty(ntile, dtype=I32, device=dev)
-        cmax = torch.empty(ntile, dtype=I32, device=dev)
-        check(L.lmg_pcsr_tile_colrange(n, T, _p(A.rowptr), _p(A.colidx), _p(cmin), _p(cmax), _s(A.rowptr)),
-              "lmg_pcsr_tile_colrange")
-        self.tile_colbase = cmin
-        if int((cmax - cmin).max()) < 65536:
-            self.colmode = 0
-            self.col = cls._padded_empty(2 * nnz, dev)
-            check(L.lmg_pcsr_encode_cols16(n, T, _p(A.rowptr), _p(A.colidx), _p(cmin), _p(self.col), _s(A.rowptr)),
-                  "lmg_pcsr_encode_cols16")
-        else:
-            self.colmode = 1
-            self.col = cls._padded(A.colidx)
-        self.ndict = ndict
-        if self.ndict <= 256:
-            self.valmode = 0
-            self.val = cls._padded_empty(nnz, dev)
-            cls._encode_values(A.vals, uniq, 1, self.val)
-            self.dict = uniq.view(F64)
-        elif self.ndict <= 65536:
-            self.valmode = 1
-            self.val = cls._padded_empty(2 * nnz, dev)
-            cls._encode_values(A.vals, uniq, 2, self.val)
-            self.dict = uniq.view(F64)
-        else:
-            self.valmode = 2
-            self.val = cls._padded(A.vals)
-            self.dict = None
-            self.ndict = 0
-        self.bytes_ = (self.rowlen.numel() + 8 * ntile + nnz * ((2, 4)[self.colmode] + (1, 2, 8)[self.valmode]))
-        return self
-
-    def bytes(self):
-        return int(self.bytes_)
-
-    def update_values(self, A):
-        """New values, same sparsity pattern (Galerkin rebuild): only the value stream (and the
-        dictionary) is re-encoded; returns False when the value encoding no longer fits and the
-        caller has to repack from scratch."""
-        if A.nnz != self.nnz:
-            return False
-        if self.valmode == 2:
-            self.val[: self.nnz * 8].view(F64).copy_(A.vals)
-            return True
-        uniq = self._distinct_values(A.vals)
-        nd = int(uniq.numel()) if uniq is not None else 1 << 30
-        if (self.valmode == 0 and nd > 256) or (self.valmode == 1 and nd > 65536):
-            return False
-        self._encode_values(A.vals, uniq, 1 if self.valmode == 0 else 2, self.val)
-        self.dict = uniq.view(F64)
-        self.ndict = nd
-        return True
-
-
-class SellCSR:
-    """Sliced-ELL (SELL-64) twin of a DeviceCSR for lmg_sell_sweep (see include/lmg.h): slices of 64
-    rows padded to their longest row, entries stored column-major inside a slice.  For long rows
-    with all-distinct values (Galerkin operators of learned / L2-type transfers); refused when the
-    padding would cost more than 20 % extra entries."""
-
-    __slots__ = ("n", "nnz", "shape", "slice_base", "slice_len", "slice_cmin", "rowlen", "col", "colmode", "val",
-                 "max_len", "padded", "bytes_")
-
-    MAX_PADDING = 1.2
-
-    @classmethod
-    def from_csr(cls, A):
-        n, nnz = A.shape[0], A.nnz
-        if n == 0 or nnz == 0 or not A.vals.is_cuda:
-            return None
-        L = _lib.lib()
-        dev = A.vals.device
-        nsl = (n + 63) // 64
-        slice_len = torch.empty(nsl, dtype=I32, device=dev)
-        cmin = torch.empty(nsl, dtype=I32, device=dev)
-        cmax = torch.empty(nsl, dtype=I32, device=dev)
-        check(L.lmg_sell_slice_info(n, _p(A.rowptr), _p(A.colidx), _p(slice_len), _p(cmin), _p(cmax), _s(A.rowptr)),
-              "lmg_sell_slice_info")
-        padded = 64 * int(slice_len.long().sum())
-        if padded > cls.MAX_PADDING * nnz or padded >= 2 ** 31 - 64:
-            return None
-        self = cls()
-        self.n, self.nnz, self.shape, self.padded = n, nnz, A.shape, padded
-        sl = slice_len.long() * 64
-        self.slice_base = (torch.cumsum(sl, 0) - sl).contiguous()
-        self.slice_len = slice_len
-        self.slice_cmin = cmin
-        self.rowlen = (A.rowptr[1:] - A.rowptr[:-1]).contiguous()
-        self.max_len = int(slice_len.max())
-        self.colmode = 0 if int((cmax - cmin).max()) < 65536 else 1
-        self.col = torch.zeros(padded + 64, dtype=torch.int16 if self.colmode == 0 else I32, device=dev)
-        self.val = torch.zeros(padded + 64, dtype=F64, device=dev)
-        check(L.lmg_sell_fill(n, _p(A.rowptr), _p(A.colidx), _p(A.vals), _p(self.slice_base), _p(cmin), self.colmode,
-                              _p(self.col), _p(self.val), _s(A.rowptr)), "lmg_sell_fill")
-        self.bytes_ = padded * ((2, 4)[self.colmode] + 8) + 16 * nsl + 4 * n
-        return self
-
-    def bytes(self):
-        return int(self.bytes_)
-
-    def update_values(self, A):
-        """New values, same pattern (Galerkin rebuild): only the value stream is rewritten."""
-        check(_lib.lib().lmg_sell_fill(self.n, _p(A.rowptr), None, _p(A.vals), _p(self.slice_base), _p(self.slice_cmin),
-                                       self.colmode, None, _p(self.val), _s(A.rowptr)), "lmg_sell_fill(values)")
-        return True
-
-
-def _pid_counts(R):
-    """How often every pattern id of a RowPatterns twin occurs (own histogram kernel: a library one costs 0.4 s of
-    code-object loading in a fresh process)."""
-    cnt = torch.zeros(4 * 256, dtype=I32, device=R.pid.device)
-    check(_lib.lib().lmg_pattern_parity_counts(int(R.n), 1, _p(R.pid), _p(cnt), _s(R.pid)), "lmg_pattern_parity_counts")
-    return cnt.cpu().numpy().reshape(4, 256).sum(axis=0)[:R.npat].astype(np.int64)
-
-
-class RowPatterns:
-    """Lossless row-pattern twin of a DeviceCSR for lmg_rpat_sweep (see include/lmg.h): every
-    distinct row -- (length; column - row and value bits of each entry, in storage order) -- is
-    stored once, each row carries a uint8 pattern id.  Only matrices with at most 255 distinct
-    rows and 1024 pattern entries qualify (assembled constant-coefficient grid operators and
-    their Galerkin coarsenings); from_csr returns None for everything else."""
-
-    __slots__ = ("n", "nnz", "shape", "pid", "npat", "nent", "max_len", "pat_ptr", "pat_off", "pat_val", "bytes_",
-                 "grid_map", "_gm")
-
-    @staticmethod
-    def grid_map_candidates(shape, line_strides=None):
-        """Column-base maps worth trying for a RECTANGULAR operator (see lmg_rpat_sweep_grid): the
-        tensor-product transfer between two square grids when both dimensions are perfect squares, and
-        the 1-D transfer.  line_strides = (fine, coarse) line lengths of a transfer between blocks of whole grid
-        lines that are not square (the local blocks of a distributed level): tried first.  Nothing is assumed: a
-        map is only used if every entry verifies."""
-        nr, nc = int(shape[0]), int(shape[1])
-        if nr == nc or nr < 2 or nc < 2:
-            return []
-        out = []
-        if line_strides is not None:
-            wf, wcs = int(line_strides[0]), int(line_strides[1])
-            if wf >= 2 and wcs >= 2:
-                out.append((wf, wcs, 1, 1, 0) if nr > nc else (wcs, 2 * wf, 0, 0, 1))
-        wr, wc = math.isqrt(nr), math.isqrt(nc)
-        if wr * wr == nr and wc * wc == nc and min(wr, wc) >= 2:
-            out.append((wr, wc, 1, 1, 0) if nr > nc else (wr, 2 * wc, 0, 0, 1))
-        out.append((nr + 1, 0, 0, 1, 0) if nr > nc else (nr + 1, 0, 0, 0, 1))
-        return out
-
-    @staticmethod
-    def grid_base(grid_map, rows):
-        """base(row) of lmg_rpat_sweep_grid for an int64 numpy array of rows."""
-        if grid_map is None:
-            return rows
-        rl, cs, ysh, xsh, xshl = grid_map
-        y, x = rows // rl, rows % rl
-        return (y >> ysh) * cs + ((x >> xsh) << xshl)
-
-    @classmethod
-    def from_csr(cls, A, grid_map=None):
-        n, nnz = A.shape[0], A.nnz
-        if n == 0 or nnz == 0 or not A.vals.is_cuda:
-            return None
-        L = _lib.lib()
-        dev = A.vals.device
-        gm = None if grid_map is None else (ctypes.c_int32 * 5)(*[int(v) for v in grid_map])
-        gmp = None if gm is None else ctypes.addressof(gm)
-        mp, me = ctypes.c_int32(0), ctypes.c_int32(0)
-        check(L.lmg_rpat_limits(ctypes.addressof(mp), ctypes.addressof(me)), "lmg_rpat_limits")
-        max_pat, max_ent = int(mp.value), int(me.value)
-        hashes = torch.empty(n, dtype=torch.int64, device=dev)
-        check(L.lmg_rpat_row_hash_grid(n, gmp, _p(A.rowptr), _p(A.colidx), _p(A.vals), _p(hashes), _s(A.rowptr)),
-              "lmg_rpat_row_hash_grid")
-        uniq = PackedCSR._distinct_values(hashes.view(F64), limit=max_pat)
-        if uniq is None:
-            return None
-        npat = int(uniq.numel())
-        # (32 spare bytes behind the ids: the LDS-staged Gauss-Seidel bands fetch them in aligned dwords, up to 19 bytes past n)
-        pid = torch.zeros(n + 32, dtype=torch.uint8, device=dev)[:n]
-        PackedCSR._encode_values(hashes.view(F64), uniq, 1, pid)
-        del hashes
-        rep = torch.full((256,), -1, dtype=I32, device=dev)
-        check(L.lmg_rpat_claim(n, _p(pid), _p(rep), _s(pid)), "lmg_rpat_claim")
-        # (the pattern table is a few hundred numbers: index gathers on the device, the arithmetic on the host -- every
-        # library elementwise kernel used for the first time costs 50 - 75 ms of code-object loading)
-        rep_h = rep[:npat].cpu().numpy().astype(np.int64)
-        if npat == 0 or rep_h.min() < 0:
-            return None
-        rep = torch.from_numpy(rep_h).to(dev)
-        starts, ends = A.rowptr[rep].cpu().numpy().astype(np.int64), A.rowptr[torch.from_numpy(rep_h + 1).to(dev)].cpu().numpy().astype(np.int64)
-        lens = ends - starts
-        nent = int(lens.sum())
-        if nent > max_ent:
-            return None
-        idx = np.concatenate([np.arange(s_, e_) for s_, e_ in zip(starts, ends)]) if nent else np.zeros(0, np.int64)
-        d_idx = torch.from_numpy(idx).to(dev)
-        self = cls()
-        self.n, self.nnz, self.shape = n, nnz, A.shape
-        self.pid = pid
-        self.npat, self.nent = npat, nent
-        self.max_len = int(lens.max())
-        ptr = np.zeros(npat + 1, dtype=np.int32)
-        np.cumsum(lens, out=ptr[1:])
-        self.pat_ptr = torch.from_numpy(ptr).to(dev)
-        base_of = cls.grid_base(grid_map, np.repeat(rep_h, lens).astype(np.int64))
-        if nent:
-            off_h = A.colidx[d_idx].cpu().numpy().astype(np.int64) - base_of
-            if np.abs(off_h).max() >= 2 ** 31:
-                return None
-            self.pat_off = torch.from_numpy(off_h.astype(np.int32)).to(dev)
-        else:
-            self.pat_off = torch.zeros(1, dtype=I32, device=dev)
-        self.pat_val = A.vals[d_idx].contiguous() if nent else torch.zeros(1, dtype=F64, device=dev)
-        mismatch = torch.zeros(1, dtype=I32, device=dev)
-        check(L.lmg_rpat_verify_grid(n, A.shape[1], gmp, _p(A.rowptr), _p(A.colidx), _p(A.vals), _p(pid), npat,
-                                     _p(self.pat_ptr), _p(self.pat_off), _p(self.pat_val), _p(mismatch), _s(A.rowptr)),
-              "lmg_rpat_verify_grid")
-        if int(mismatch):
-            return None                                # a hash collision: not worth a second try
-        self.bytes_ = n + 4 * (npat + 1) + 12 * nent
-        self.grid_map = None if grid_map is None else tuple(int(v) for v in grid_map)
-        self._gm = gm                                  # keeps the host array of the map alive
-        return self
-
-    def bytes(self):
-        return int(self.bytes_)
-
-
-class StencilTwin:
-    """3x3-stencil view of a RowPatterns twin for lmg_stencil_sweep (see include/lmg.h): every entry
-    of every pattern at  column - row = c * W + d,  c, d in {-1, 0, 1},  for ONE line stride W, every
-    pattern in ascending column order.  Derived from the (already verified) pattern table on the host
-    -- a few hundred numbers --; the per-row pattern ids are shared with the RowPatterns twin.
-    from_patterns returns None for everything that does not fit (the RPAT kernel then runs)."""
-
-    __slots__ = ("n", "W", "npat", "pid", "st_val", "st_mask", "umask", "bytes_", "patterns", "hot", "_hot_val",
-                 "_gs_ok", "_gs_work")
-
-    @staticmethod
-    def _decompose(off, W):
-        """(c, d) of a linear offset for line stride W, or None."""
-        for c in (-1, 0, 1):
-            d = off - c * W
-            if -1 <= d <= 1:
-                return c, d
-        return None
-
-    @classmethod
-    def from_patterns(cls, R, shape):
-        if R is None or shape[0] != shape[1] or R.n < 2:
-            return None
-        mp = ctypes.c_int32(0)
-        check(_lib.lib().lmg_stencil_limits(ctypes.addressof(mp)), "lmg_stencil_limits")
-        if R.npat > int(mp.value):
-            return None
-        ptr = R.pat_ptr.cpu().numpy()
-        off = R.pat_off.cpu().numpy().astype(np.int64)[: R.nent]
-        val = R.pat_val.cpu().numpy()[: R.nent]
-        for p in range(R.npat):
-            o = off[ptr[p]:ptr[p + 1]]
-            if o.size > 9 or np.any(np.diff(o) <= 0):            # slot order must be storage order
-                return None
-        mx = int(np.abs(off).max()) if off.size else 0
-        if mx <= 1:
-            cands = [int(R.n)]                                    # 1-D: one line, only the centre slots are used
-            if R.n < 3:
-                return None
-        else:
-            cands = [w for w in (mx, mx - 1, mx + 1) if 3 <= w < R.n]
-        # several strides can fit (a 7-point operator {-W-1, -W, -1, 0, 1, W, W+1} also reads as a sheared
-        # stencil of stride W + 1): prefer the one that cuts the rows into whole lines
-        fits = [w for w in cands if all(cls._decompose(int(o), w) is not None for o in off)]
-        if not fits:
-            return None
-        W = next((w for w in fits if R.n % w == 0), fits[0])
-        slots = [cls._decompose(int(o), W) for o in off]
-        st_val = np.zeros(R.npat * 9)
-        st_mask = np.zeros(R.npat, dtype=np.int32)
-        for p in range(R.npat):
-            for j in range(ptr[p], ptr[p + 1]):
-                c, d = slots[j]
-                sidx = (c + 1) * 3 + (d + 1)
-                if st_mask[p] & (1 << sidx):
-                    return None
-                st_mask[p] |= 1 << sidx
-                st_val[p * 9 + sidx] = val[j]
-        dev = R.pid.device
-        self = cls()
-        self.n, self.W, self.npat, self.pid, self.patterns = int(R.n), int(W), int(R.npat), R.pid, R
-        self.st_val = torch.from_numpy(st_val).to(dev)
-        self.st_mask = torch.from_numpy(st_mask).to(dev)
-        self.umask = int(np.bitwise_or.reduce(st_mask)) if R.npat else 0
-        self.bytes_ = R.n + 76 * R.npat
-        # hot pattern for the fused smoothing pass: the most frequent one among those that have every
-        # union slot and a non-zero diagonal (the interior row of a grid operator)
-        self.hot, self._hot_val = -1, None
-        cand = [p for p in range(R.npat) if st_mask[p] == self.umask and (st_mask[p] & 16) and st_val[p * 9 + 4] != 0.0]
-        if cand:
-            counts = _pid_counts(R) if len(cand) > 1 else None
-            self.hot = int(cand[0] if counts is None else max(cand, key=lambda p: counts[p]))
-            self._hot_val = (ctypes.c_double * 9)(*[float(v) for v in st_val[self.hot * 9: self.hot * 9 + 9]])
-        # wavefront Gauss-Seidel (lmg_stencil_gs_sweep): see gs_ok below (decided on first use)
-        self._gs_work = None
-        self._gs_ok = None
-        return self
-
-    def c_args(self):
-        """The nine leading arguments that describe this operator to lmg_stencil_smooth* / lmg_stencil_gs_sweep*."""
-        hv = None if self._hot_val is None else ctypes.addressof(self._hot_val)
-        return (self.n, self.W, _p(self.pid), self.npat, _p(self.st_val), _p(self.st_mask), self.umask, self.hot, hv)
-
-    @property
-    def gs_ok(self):
-        """Whether the wavefront Gauss-Seidel kernel may run on this operator: a supported slot set and no coupling
-        across the ends of a line -- rows in column 0 must not reach column - 1, rows in column W - 1 not column + 1.
-        Decided on first use (a few library elementwise kernels on the ids of two grid columns: their code objects
-        cost 0.13 s to load in a fresh process, which a Jacobi-only run never needs).
-        (1-D chains are one lane of the wavefront kernel; the one-wave chain executor of gs.hip, x in LDS, is
-        faster there: 0.29 vs 0.5 us per row)"""
-        if self._gs_ok is None:
-            ok = bool(_lib.lib().lmg_stencil_gs_supported(self.umask)) and self.n >= 2 and bool(self.umask & 0x1C7)
-            if ok:
-                mk = self.st_mask.cpu().numpy()
-                W = self.W
-                first = mk[self.pid[0::W].cpu().numpy()]
-                last = mk[self.pid[W - 1::W].cpu().numpy()]
-                ok = not bool(((first & 0x49) != 0).any()) and not bool(((last & 0x124) != 0).any())
-            self._gs_ok = ok
-        return self._gs_ok
-
-    def bytes(self):
-        return int(self.bytes_)
-
-
-class ProlongTwin:
-    """2x2-window view of the row-pattern twin of a PROLONGATION between nested grids for
-    lmg_stencil_smooth_prolong (see include/lmg.h): row (y, x) of the fine grid (line stride W) reads the coarse
-    vector only at ((y >> 1) * Wc + (x >> 1)) + {0, 1, Wc, Wc + 1} -- the tensor-product interpolation of
-    Multigrid.interpolator applied along both axes.  Derived on the host from the (already verified) pattern
-    table of a RowPatterns twin with the column-base map (W, Wc, 1, 1, 0); from_patterns returns None for
-    everything else (the correction then runs as its own lmg_rpat_sweep_grid launch)."""
-
-    __slots__ = ("n", "W", "nc", "Wc", "npat", "pid", "p_val", "p_mask", "_hot_pairs", "_hot_pval", "patterns")
-
-    @classmethod
-    def from_patterns(cls, R, shape):
-        if R is None or R.grid_map is None or R.npat > 64 or R.n < 2:
-            return None
-        W, Wc, ysh, xsh, xshl = R.grid_map
-        if (ysh, xsh, xshl) != (1, 1, 0) or Wc < 2 or W < 3 or 2 * Wc < W + 1 or shape[1] >= 2 ** 31:
-            return None
-        ptr = R.pat_ptr.cpu().numpy()
-        off = R.pat_off.cpu().numpy().astype(np.int64)[: R.nent]
-        val = R.pat_val.cpu().numpy()[: R.nent]
-        slot_of = {0: 0, 1: 1, Wc: 2, Wc + 1: 3}
-        p_val = np.zeros(R.npat * 4)
-        p_mask = np.zeros(R.npat, dtype=np.int32)
-        for p in range(R.npat):
-            o = off[ptr[p]:ptr[p + 1]]
-            if o.size > 4 or np.any(np.diff(o) <= 0) or any(int(v) not in slot_of for v in o):
-                return None
-            for j in range(ptr[p], ptr[p + 1]):
-                k = slot_of[int(off[j])]
-                p_mask[p] |= 1 << k
-                p_val[p * 4 + k] = val[j]
-        dev = R.pid.device
-        # which patterns occur where: counts by (line parity, column parity)
-        n = int(R.n)
-        cnt = torch.zeros(4 * 256, dtype=I32, device=dev)
-        check(_lib.lib().lmg_pattern_parity_counts(n, int(W), _p(R.pid), _p(cnt), _s(R.pid)), "lmg_pattern_parity_counts")
-        counts = cnt.cpu().numpy().reshape(2, 2, 256)[:, :, :R.npat].astype(np.int64)
-        if np.any((counts[0].sum(axis=0) > 0) & ((p_mask & 0xC) != 0)):
-            return None                        # a row on an even line reaching the coarse line below: not this shape
-        self = cls()
-        self.n, self.W, self.nc, self.Wc, self.npat = n, int(W), int(shape[1]), int(Wc), int(R.npat)
-        self.pid, self.patterns = R.pid, R
-        self.p_val = torch.from_numpy(p_val).to(dev)
-        self.p_mask = torch.from_numpy(p_mask).to(dev)
-        # the usual pattern pair of an (even, odd) column pair on even / odd lines, with exactly the slots of the
-        # tensor-product interpolation: their values travel in scalar registers
-        want = (((0x1, 0x3)), ((0x5, 0xF)))
-        pairs, pval = [], []
-        for yl in range(2):
-            ids = []
-            for xl in range(2):
-                cand = [p for p in range(R.npat) if p_mask[p] == want[yl][xl] and counts[yl][xl][p] > 0]
-                ids.append(max(cand, key=lambda p: counts[yl][xl][p]) if cand else -1)
-            pairs.append(-1 if min(ids) < 0 else ids[0] | (ids[1] << 8))
-            for xl in range(2):
-                m = want[yl][xl]
-                pval += [float(p_val[ids[xl] * 4 + k]) if ids[xl] >= 0 else 0.0 for k in range(4) if (m >> k) & 1]
-        self._hot_pairs = (ctypes.c_int32 * 2)(*pairs)
-        self._hot_pval = (ctypes.c_double * 9)(*pval)
-        return self
-
-    def c_args(self, e):
-        """The arguments that describe the correction P e to the lmg_stencil_smooth*_prolong / _turnaround entry points."""
-        return (self.nc, self.Wc, _p(e), _p(self.pid), self.npat, _p(self.p_val), _p(self.p_mask),
-                ctypes.addressof(self._hot_pairs), ctypes.addressof(self._hot_pval))
-
-
-class RestrictTwin:
-    """3x3-window view of the row-pattern twin of a RESTRICTION between nested grids for
-    lmg_stencil_smooth_restrict (see include/lmg.h): row (Y, X) of the coarse grid (line stride Wc) reads the
-    fine vector (line stride W) only at (2 Y * W + 2 X) + c * W + d, c, d in {-1, 0, 1} -- the transpose of the
-    tensor-product interpolation.  Derived on the host from the pattern table of a RowPatterns twin with the
-    column-base map (Wc, 2 W, 0, 0, 1); None for everything else (the restriction then is its own launch)."""
-
-    __slots__ = ("nc", "Wc", "n", "W", "npat", "pid", "r_val", "r_mask", "hot", "_hot_val", "patterns")
-
-    @classmethod
-    def from_patterns(cls, R, shape):
-        if R is None or R.grid_map is None or R.npat > 64:
-            return None
-        Wc, cs, ysh, xsh, xshl = R.grid_map
-        if (ysh, xsh, xshl) != (0, 0, 1) or cs % 2 or Wc < 2 or shape[0] >= 2 ** 28:
-            return None
-        W = cs // 2
-        # the fused passes write b_coarse only under fine nodes (even line, even column < W): the coarse grid must be
-        # exactly that set, or rows beyond it would keep the previous cycle's right-hand side
-        if W < 3 or Wc != (W + 1) // 2 or shape[1] % W or int(R.n) != ((shape[1] // W + 1) // 2) * Wc:
-            return None
-        ptr = R.pat_ptr.cpu().numpy()
-        off = R.pat_off.cpu().numpy().astype(np.int64)[: R.nent]
-        val = R.pat_val.cpu().numpy()[: R.nent]
-        r_val = np.zeros(R.npat * 9)
-        r_mask = np.zeros(R.npat, dtype=np.int32)
-        for p in range(R.npat):
-            o = off[ptr[p]:ptr[p + 1]]
-            if o.size > 9 or np.any(np.diff(o) <= 0):
-                return None
-            for j in range(ptr[p], ptr[p + 1]):
-                cd = StencilTwin._decompose(int(off[j]), W)
-                if cd is None:
-                    return None
-                k = (cd[0] + 1) * 3 + (cd[1] + 1)
-                if r_mask[p] & (1 << k):
-                    return None
-                r_mask[p] |= 1 << k
-                r_val[p * 9 + k] = val[j]
-        dev = R.pid.device
-        self = cls()
-        self.nc, self.Wc, self.n, self.W, self.npat = int(R.n), int(Wc), int(shape[1]), int(W), int(R.npat)
-        self.pid, self.patterns = R.pid, R
-        self.r_val = torch.from_numpy(r_val).to(dev)
-        self.r_mask = torch.from_numpy(r_mask).to(dev)
-        self.hot, self._hot_val = -1, None
-        cand = [p for p in range(R.npat) if r_mask[p] == 0x1FF]
-        if cand:
-            counts = _pid_counts(R) if len(cand) > 1 else None
-            self.hot = int(cand[0] if counts is None else max(cand, key=lambda p: counts[p]))
-            self._hot_val = (ctypes.c_double * 9)(*[float(v) for v in r_val[self.hot * 9: self.hot * 9 + 9]])
-        return self
-
-    def c_args(self, bc):
-        """The arguments that describe b_coarse = R r to the lmg_stencil_smooth*_restrict entry points (the turnaround
-        pass takes them without the leading nc, Wc, which it has from the prolongation)."""
-        hr = None if self._hot_val is None else ctypes.addressof(self._hot_val)
-        return (self.nc, self.Wc, _p(bc), _p(self.pid), self.npat, _p(self.r_val), _p(self.r_mask), self.hot, hr)
-
-
-class DiaTwin:
-    """Slot arrays of a grid operator with per-row values for lmg_dia_smooth (see include/lmg.h): every entry at
-    column - row = c * W + d, c, d in {-1, 0, 1}, for ONE line stride W; dia[q * n + row] = the entry of `row` in slot
-    number q of the union mask (+0.0 where the row has none).  Built and verified on the device: W is guessed from a
-    few rows in the middle of the matrix, a probe pass collects the slots of ALL entries for that W and refuses the
-    matrix if any entry is not a slot; from_csr returns None for everything that does not fit (the packed-CSR sweeps
-    then run one launch per sweep)."""
-
-    __slots__ = ("n", "W", "umask", "nslots", "dia", "bytes_")
-    MIN_ROWS = 4096
-
-    @staticmethod
-    def _probe(A, W, umask, dia):
-        dev = A.vals.device
-        flags = torch.zeros(2, dtype=I32, device=dev)
-        check(_lib.lib().lmg_dia_fill(A.shape[0], int(W), _p(A.rowptr), _p(A.colidx), _p(A.vals), int(umask), _p(dia),
-                                      flags.data_ptr(), flags.data_ptr() + 4, _s(A.rowptr)), "lmg_dia_fill")
-        f = flags.cpu().numpy()
-        return int(f[0]), int(f[1]) & 0x1FF
-
-    @classmethod
-    def from_csr(cls, A):
-        n = A.shape[0]
-        if n < cls.MIN_ROWS or A.nnz == 0 or A.nnz > 9 * n or not A.vals.is_cuda or n >= 2 ** 31 - 4096:
-            return None
-        # candidate strides from the longest of a few rows in the middle: its largest |column - row| is W - 1, W or W + 1
-        mid = n // 2
-        rp = A.rowptr[mid:mid + 9].cpu().numpy().astype(np.int64)
-        ci = A.colidx[rp[0]:rp[-1]].cpu().numpy().astype(np.int64)
-        rows = np.repeat(np.arange(mid, mid + 8), np.diff(rp))
-        off = np.abs(ci - rows)
-        mx = int(off.max()) if off.size else 0
-        if mx < 4:
-            return None
-        # (several strides can fit -- a 7-point operator also reads as the other 7-point orientation of stride W + 1;
-        # everything is a linear index, so any of them is correct: prefer the one that cuts the rows into whole lines)
-        for W in sorted((mx, mx - 1, mx + 1), key=lambda w: (n % w != 0 if w > 0 else True)):
-            if not (3 <= W < n):
-                continue
-            bad, seen = cls._probe(A, W, 0x1FF, None)
-            if bad or not (seen & 16):
-                continue
-            umask = next((m for m in (0x0BA, 0x1BB, 0x0FE, 0x1FF) if not (seen & ~m)), None)
-            if umask is None or not _lib.lib().lmg_dia_smooth_supported(umask):
-                return None
-            self = cls()
-            self.n, self.W, self.umask = int(n), int(W), int(umask)
-            self.nslots = bin(umask).count("1")
-            self.dia = torch.empty(self.nslots * n, dtype=F64, device=A.vals.device)
-            bad, _seen = cls._probe(A, W, umask, self.dia)
-            if bad:
-                return None
-            self.bytes_ = 8 * self.nslots * n
-            return self
-        return None
-
-    def update_values(self, A):
-        """New values on the same pattern (Galerkin rebuild of a variable-coefficient level)."""
-        bad, _seen = self._probe(A, self.W, self.umask, self.dia)
-        return not bad
-
-    def bytes(self):
-        return int(self.bytes_)
-
-
 _PACKED_ENABLED = True
 _PATTERNS_ENABLED = True
 _STENCIL_ENABLED = True
@@ -838,12 +200,6 @@ def set_stencil_enabled(flag):
     """Whether 3x3-stencil row-pattern matrices run lmg_stencil_sweep (default) or lmg_rpat_sweep."""
     global _STENCIL_ENABLED
     _STENCIL_ENABLED = bool(flag)
-
-
-def _stencil(mode, S, x, b, out, alpha, beta, partials, norm2):
-    return _lib.lib().lmg_stencil_sweep(mode, S.n, S.W, _p(S.pid), S.npat, _p(S.st_val), _p(S.st_mask), S.umask,
-                                        _p(x), _p(b), _p(out), float(alpha), float(beta), _p(partials), _p(norm2),
-                                        _s(S.pid))
 
 
 FUSED_MAX_SWEEPS = 3
@@ -1167,12 +523,6 @@ def set_sell_enabled(flag):
     _SELL_ENABLED = bool(flag)
 
 
-def _sell(mode, S, x, b, out, alpha, beta, partials, norm2):
-    return _lib.lib().lmg_sell_sweep(mode, S.n, _p(S.slice_base), _p(S.slice_len), _p(S.slice_cmin), _p(S.rowlen),
-                                     _p(S.col), S.colmode, _p(S.val), S.max_len, _p(x), _p(b), _p(out), float(alpha),
-                                     float(beta), _p(partials), _p(norm2), _s(S.slice_base))
-
-
 def set_packed_enabled(flag):
     """Route csr_jacobi / csr_residual_norm2 / csr_spmv through the lossless twins when they
     exist (default) or always through the plain CSR kernels (A/B and parity tests)."""
@@ -1184,21 +534,6 @@ def set_patterns_enabled(flag):
     """Whether pack() may pick the row-pattern twin (default) or always builds the packed CSR."""
     global _PATTERNS_ENABLED
     _PATTERNS_ENABLED = bool(flag)
-
-
-def _rpat(mode, R, x, b, out, alpha, beta, partials, norm2):
-    gmp = None if R._gm is None else ctypes.addressof(R._gm)
-    return _lib.lib().lmg_rpat_sweep_grid(mode, R.n, gmp, _p(R.pid), R.npat, R.nent, R.max_len, _p(R.pat_ptr),
-                                          _p(R.pat_off), _p(R.pat_val), _p(x), _p(b), _p(out), float(alpha),
-                                          float(beta), _p(partials), _p(norm2), _s(R.pid))
-
-
-def _pcsr(mode, P, x, b, out, alpha, beta, partials, norm2):
-    rc = _lib.lib().lmg_pcsr_sweep(mode, P.n, P.nnz, P.tile_rows, P.tile_cap, _p(P.tile_base), _p(P.tile_colbase),
-                                   _p(P.rowlen), _p(P.col), P.colmode, _p(P.val), P.valmode,
-                                   _p(P.dict), P.ndict, _p(x), _p(b), _p(out), float(alpha), float(beta),
-                                   _p(partials), _p(norm2), _s(P.tile_base))
-    return rc
 
 
 def partials_count(n):
@@ -1217,25 +552,33 @@ def tune_get(key):
 _MODE_NAMES = ("residual", "jacobi", "spmv")
 
 
+def _twin_sweep(entry, mode, twin, tail):
+    """entry = the lmg_*_sweep function of the twin's format; tail: the vectors and scalars every one of them ends with."""
+    head, t = twin.sweep_args()
+    return entry(mode, *head, *tail, _s(t))
+
+
 def _sweep(mode, A, x, b, out, alpha, beta, partials, norm2):
     """One sweep (0 residual, 1 Jacobi, 2 SpMV) on the best twin A has: grid stencil -> row patterns -> sliced ELL ->
     packed CSR -> plain CSR."""
     what = "(%s)" % _MODE_NAMES[mode]
+    L = _lib.lib()
+    tail = (_p(x), _p(b), _p(out), float(alpha), float(beta), _p(partials), _p(norm2))
     if _use_stencil(A, x, b, out):
-        check(_stencil(mode, A.stencil, x, b, out, alpha, beta, partials, norm2), "lmg_stencil_sweep" + what)
+        check(_twin_sweep(L.lmg_stencil_sweep, mode, A.stencil, tail), "lmg_stencil_sweep" + what)
         return
     if _PACKED_ENABLED and A.patterns is not None:
-        check(_rpat(mode, A.patterns, x, b, out, alpha, beta, partials, norm2), "lmg_rpat_sweep" + what)
+        check(_twin_sweep(L.lmg_rpat_sweep_grid, mode, A.patterns, tail), "lmg_rpat_sweep" + what)
         return
     if _PACKED_ENABLED and A.sell is not None:
-        check(_sell(mode, A.sell, x, b, out, alpha, beta, partials, norm2), "lmg_sell_sweep" + what)
+        check(_twin_sweep(L.lmg_sell_sweep, mode, A.sell, tail), "lmg_sell_sweep" + what)
         return
     if _PACKED_ENABLED and A.packed is not None:
-        rc = _pcsr(mode, A.packed, x, b, out, alpha, beta, partials, norm2)
+        rc = _twin_sweep(L.lmg_pcsr_sweep, mode, A.packed, tail)
         if rc != -4:                                   # LMG_ERR_CAPACITY: tile too large for LDS
             check(rc, "lmg_pcsr_sweep" + what)
             return
-    L, csr = _lib.lib(), (A.shape[0], A.nnz, _p(A.rowptr), _p(A.colidx), _p(A.vals))
+    csr = (A.shape[0], A.nnz, _p(A.rowptr), _p(A.colidx), _p(A.vals))
     if mode == 0:
         check(L.lmg_csr_residual_norm2(*csr, _p(x), _p(b), _p(out), _p(partials), _p(norm2), _s(A.rowptr)),
               "lmg_csr_residual_norm2")
