@@ -890,7 +890,8 @@ int lmg_dense_gemv_windows_off(int64_t nblocks, int64_t rows, int64_t cols, cons
 int lmg_coarse_front(int64_t nblocks, int64_t bs, const double *M, const double *b, const int32_t *perm, double *y,
                      int64_t ntail, double *tail_out, void *stream)
 {
-    if (nblocks < 0 || bs < 0 || ntail < 0 || (nblocks * bs > 0 && (!M || !b || !perm || !y)) || (ntail > 0 && !tail_out) || b == y)
+    if (nblocks < 0 || bs < 0 || ntail < 0 || (nblocks * bs > 0 && (!M || !b || !perm || !y)) ||
+        (ntail > 0 && (!tail_out || !b || !perm)) || b == y)
         return LMG_ERR_ARG;
     if (nblocks * bs == 0 && ntail == 0) return LMG_OK;
     if (!lmg_aligned16(M) || (bs % 2)) return LMG_ERR_ALIGN;
@@ -961,7 +962,7 @@ int lmg_csr_to_dense(int64_t n, int64_t m, const int32_t *rowptr, const int32_t 
 {
     if (n < 0 || m < 0) return LMG_ERR_ARG;
     if (n == 0) return LMG_OK;
-    if (!rowptr || !dense) return LMG_ERR_ARG;
+    if (!rowptr || !colidx || !vals || !dense) return LMG_ERR_ARG;      // (rowptr[n] > 0 cannot be excluded on the host)
     hipLaunchKernelGGL(csr_to_dense_kernel, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, lmg_stream(stream), n, m, rowptr,
                        colidx, vals, dense);
     LMG_CHECK_LAUNCH();

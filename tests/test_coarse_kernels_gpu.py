@@ -1,0 +1,943 @@
+"""The dense kernels behind the coarsest-level solve (coarse.py), one by one (-m gpu): every entry point against the
+formula include/lmg.h documents for it, evaluated on the host in a wider type.
+
+Two classes of data:
+
+  exact   entries, alpha, beta, z: non-zero integers in [-8, 8].  Every product and partial sum is an integer far below
+          2^53 in any summation order and with or without FMA contraction, so the kernel must reproduce the int64
+          evaluation exactly (np.array_equal): a dropped, doubled or misplaced element cannot hide.
+  real    magnitudes uniform in [0.5, 2), random signs (no term small enough to hide under the bound); reference in
+          np.longdouble (fractions.Fraction where longdouble is no wider than 64 bits).  Bound, elementwise: the
+          worst-case forward error of a length-K inner product summed in ANY order, one rounding each for the product
+          with alpha, the addition of z and -- with accumulate -- the addition of the previous value,
+
+              |got - want| <= (K + 3) * 2^-53 * (|alpha| * (|M| @ |x|) + |z| (+ |previous out|))
+
+          (GEMM: |alpha| * (|A| @ |B|) + |beta| * |C|).  Derived, not measured.
+
+Every output buffer starts as NaN (as data where the kernel accumulates); whatever the formula does not write -- gaps
+between strided blocks, rows with a negative index, guard cells around a view -- must keep its bits.
+"""
+import fractions
+import os
+import re
+
+import numpy as np
+import pytest
+import scipy.sparse as sp
+import scipy.sparse.linalg as spla
+
+torch = pytest.importorskip("torch")
+pytestmark = pytest.mark.gpu
+
+import cpu_ops_shim as shim                                             # noqa: E402
+from conftest import ROOT                                               # noqa: E402
+from learnmultigrid_amd import _lib, coarse, ops, problems as P         # noqa: E402
+from learnmultigrid_amd.ops import DeviceCSR                            # noqa: E402
+
+DEV = "cuda:0"
+KINDS = ["exact", "real"]
+U = fractions.Fraction(1, 2 ** 53)
+WIDE = np.finfo(np.longdouble).eps <= 2.0 ** -63
+
+# what the shapes below were derived from (csrc/vec.hip, csrc/gemm.hip); test_shapes_follow_the_kernel_constants
+# fails when one of them changes, and the shapes have to be derived again
+WAVES_CAP = 256 * 8 * 4          # kMaxGrid workgroups of kBlock / LMG_WAVE waves: one row per wave beyond -> stride loop
+THREADS_CAP = 256 * 8 * 256      # kMaxGrid * kBlock threads: one element per thread beyond -> stride loop
+COARSE_ROWS = 36                 # kCoarseRows
+LDS_CAP_BYTES = 60000            # operand segment of the gather kernels
+
+
+# ---- helpers ----------------------------------------------------------------------------------------------------------------
+def dev(a, dtype=None):
+    t = torch.from_numpy(np.ascontiguousarray(a))
+    if dtype is not None:
+        t = t.to(dtype)
+    return t.to(DEV)
+
+
+def cpu(a, dtype=None):
+    t = torch.from_numpy(np.array(a, copy=True))
+    return t if dtype is None else t.to(dtype)
+
+
+def host(t):
+    return t.cpu().numpy()
+
+
+def i32(a):
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def nan(*shape):
+    return np.full(shape, np.nan)
+
+
+def data(kind, rng, *shape):
+    sign = rng.choice([-1.0, 1.0], size=shape)
+    if kind == "exact":
+        return sign * rng.integers(1, 9, size=shape)
+    return sign * rng.uniform(0.5, 2.0, size=shape)
+
+
+def scalar(kind, rng):
+    return float(data(kind, rng, 1)[0])
+
+
+def wide(kind, a):
+    """`a` in the type the reference is evaluated in."""
+    a = np.asarray(a, dtype=np.float64)
+    if kind == "exact":
+        assert np.array_equal(a, np.rint(a))
+        return a.astype(np.int64)
+    if WIDE:
+        assert np.finfo(np.longdouble).eps <= 2.0 ** -63
+        return a.astype(np.longdouble)
+    return np.vectorize(fractions.Fraction, otypes=[object])(a)
+
+
+def products(kind, M, segs, alpha=1.0, z=None):
+    """(value, magnitude) of z + alpha * M_k @ segs_k for the stack M (nb, rows, cols) and operand segments (nb, cols):
+    both (nb, rows), in the reference type; magnitude = |z| + |alpha| |M_k| @ |segs_k| (what the bound scales with)."""
+    Mw, sw, a = wide(kind, M), wide(kind, segs), wide(kind, alpha)[()]
+    val = a * (Mw @ sw[:, :, None])[:, :, 0]
+    mag = abs(a) * (np.abs(Mw) @ np.abs(sw)[:, :, None])[:, :, 0]
+    if z is not None:
+        val = wide(kind, z) + val
+        mag = np.abs(wide(kind, z)) + mag
+    return val, mag
+
+
+class Expect:
+    """What one output buffer must hold: `before` (its content at the launch, float64) everywhere except where put()
+    places a value with its magnitude."""
+
+    def __init__(self, kind, before):
+        self.kind, self.before = kind, np.array(before, dtype=np.float64)
+        zero = wide(kind, np.zeros(1)).dtype
+        self.want = np.zeros(self.before.shape, dtype=zero)
+        self.mag = np.zeros(self.before.shape, dtype=zero)
+        self.written = np.zeros(self.before.shape, dtype=bool)
+
+    def put(self, pos, val, mag, accumulate=False):
+        if accumulate:
+            prev = wide(self.kind, self.before[pos])
+            val, mag = val + prev, mag + np.abs(prev)
+        self.want[pos], self.mag[pos], self.written[pos] = val, mag, True
+
+    def put_bits(self, pos, values):
+        """float64 values that must arrive bit for bit (copies; sums of two float64 numbers)."""
+        self.put(pos, wide(self.kind, values), 0)
+
+    def check(self, got, K, what=""):
+        got = np.ascontiguousarray(got, dtype=np.float64)
+        assert got.shape == self.before.shape
+        keep = ~self.written
+        same = got.view(np.int64)[keep] == self.before.view(np.int64)[keep]
+        assert same.all(), "%s: %d cells outside the formula were written" % (what, int((~same).sum()))
+        w = self.written
+        if self.kind == "exact":
+            ok = got[w] == self.want[w].astype(np.float64)
+            assert ok.all(), "%s: %d of %d values differ from the int64 evaluation" % (what, int((~ok).sum()), ok.size)
+            return
+        fin = np.isfinite(got[w])
+        assert fin.all(), "%s: %d values are not finite" % (what, int((~fin).sum()))
+        gw = got[w].astype(np.longdouble) if WIDE else np.vectorize(fractions.Fraction, otypes=[object])(got[w])
+        err = np.abs(gw - self.want[w])
+        bound = self.mag[w] * ((K + 3) * (np.longdouble(2.0) ** -53 if WIDE else U))
+        ok = np.asarray(err <= bound, dtype=bool)
+        worst = max([float(e / b) if b else float("inf") for e, b in zip(err[~ok], bound[~ok])], default=0.0)
+        assert ok.all(), "%s: %d of %d values beyond the bound, worst %.3g x bound" % (what, int((~ok).sum()), ok.size, worst)
+
+
+def source_constant(fname, name):
+    txt = open(os.path.join(ROOT, "learnmultigrid_amd", "csrc", fname)).read()
+    m = re.search(r"constexpr int (?:\w+ = \d+, )*%s = ([0-9 *]+)[;,]" % name, txt)
+    assert m, name
+    return int(np.prod([int(f) for f in m.group(1).split("*")]))
+
+
+def test_shapes_follow_the_kernel_constants():
+    kblock, kmax = source_constant("vec.hip", "kBlock"), source_constant("vec.hip", "kMaxGrid")
+    assert (kblock, kmax, kmax * kblock // 64, kmax * kblock) == (256, 2048, WAVES_CAP, THREADS_CAP)
+    assert source_constant("vec.hip", "kCoarseRows") == COARSE_ROWS
+    assert [source_constant("gemm.hip", k) for k in ("kTM", "kTN", "kTK")] == [64, 64, 16]
+    vec = open(os.path.join(ROOT, "learnmultigrid_amd", "csrc", "vec.hip")).read()
+    assert vec.count("* 8 > %d" % LDS_CAP_BYTES) == 2                    # both gather entry points
+    gemm = open(os.path.join(ROOT, "learnmultigrid_amd", "csrc", "gemm.hip")).read()
+    assert "if (g > 4096) g = 4096;" in gemm                             # copy2d's grid cap (x 256 threads)
+
+
+# ---- dense_gemv_blockdiag ---------------------------------------------------------------------------------------------------
+def blockdiag_case(kind, nb, bs):
+    rng = np.random.default_rng([1, nb, bs])
+    return data(kind, rng, nb, bs, bs), data(kind, rng, nb * bs)
+
+
+def run_blockdiag(mod, put, M, x):
+    nb, bs, _ = M.shape
+    ybuf = put(nan(nb * bs + 2))
+    xbuf = put(np.concatenate([nan(2), x]))                 # (a 16-byte aligned start behind two guard cells)
+    mod.dense_gemv_blockdiag(put(M), xbuf[2:], ybuf[1:-1])
+    return host(ybuf)
+
+
+def expect_blockdiag(kind, M, x):
+    nb, bs, _ = M.shape
+    e = Expect(kind, nan(nb * bs + 2))
+    val, mag = products(kind, M, x.reshape(nb, bs))
+    e.put(slice(1, -1), val.ravel(), mag.ravel())
+    return e
+
+
+BLOCKDIAG = [(nb, bs) for bs in (2, 126, 128, 130, 258) for nb in (1, 3)] + [(WAVES_CAP // 2 + 4, 2)]
+
+
+@pytest.mark.parametrize("nb,bs", BLOCKDIAG)
+@pytest.mark.parametrize("kind", KINDS)
+def test_dense_gemv_blockdiag(kind, nb, bs):
+    M, x = blockdiag_case(kind, nb, bs)
+    expect_blockdiag(kind, M, x).check(run_blockdiag(ops, dev, M, x), bs)
+
+
+# ---- dense_gemv_windows / dense_gemv_windows_off ----------------------------------------------------------------------------
+def windows_layouts():
+    out = {}
+    for cols in (2, 128, 130):
+        for rows in (1, 5):                                 # windows side by side, gaps in y
+            out["c%dr%d" % (cols, rows)] = dict(nb=3, rows=rows, cols=cols, xs=cols, ys=rows + 3, zs=None, alpha=None)
+            out["c%dr%dz" % (cols, rows)] = dict(nb=3, rows=rows, cols=cols, xs=cols, ys=rows, zs=rows + 1, alpha=-1.0)
+    for b in (2, 66):                                       # the calls of BlockCyclicReduction.apply, block size b
+        out["bcr_c_b%d" % b] = dict(nb=3, rows=b, cols=b, xs=2 * b, ys=b, zs=None, alpha=1.0)
+        out["bcr_rhs_b%d" % b] = dict(nb=3, rows=b, cols=2 * b, xs=b, ys=b, zs=2 * b, alpha=-1.0)
+        out["bcr_odd_b%d" % b] = dict(nb=3, rows=b, cols=2 * b, xs=b, ys=2 * b, zs=b, alpha=-1.0)
+        out["bcr_wide_b%d" % b] = dict(nb=3, rows=b, cols=b, xs=2 * b, ys=2 * b, zs=b, alpha=-1.0)
+    out["grid_stride"] = dict(nb=WAVES_CAP // 2 + 4, rows=2, cols=2, xs=2, ys=2, zs=3, alpha=-1.0)
+    return out
+
+
+WINDOWS = windows_layouts()
+
+
+def windows_case(kind, name, starts=None):
+    L = WINDOWS[name] if isinstance(name, str) else name
+    nb, rows, cols = L["nb"], L["rows"], L["cols"]
+    rng = np.random.default_rng([2, nb, rows, cols, L["ys"]])
+    c = dict(L)
+    c["M"] = data(kind, rng, nb, rows, cols)
+    c["starts"] = np.arange(nb) * L["xs"] if starts is None else np.asarray(starts)
+    c["x"] = data(kind, rng, int(c["starts"].max()) + cols)
+    c["z"] = None if L["zs"] is None else data(kind, rng, (nb - 1) * L["zs"] + rows)
+    c["alpha"] = scalar(kind, rng) if L["alpha"] is None else L["alpha"]
+    return c
+
+
+def run_windows(mod, put, c, off=False):
+    nb, rows = c["nb"], c["rows"]
+    ybuf = put(nan((nb - 1) * c["ys"] + rows + 2))
+    z = None if c["z"] is None else put(c["z"])
+    if off:
+        xo = put(i32(c["starts"]))
+        mod.dense_gemv_windows_off(put(c["M"]), put(c["x"]), xo, ybuf[1:-1], c["ys"], z=z, z_stride=c["zs"] or 0, alpha=c["alpha"])
+    else:
+        mod.dense_gemv_windows(put(c["M"]), put(c["x"]), c["xs"], ybuf[1:-1], c["ys"], z=z, z_stride=c["zs"] or 0, alpha=c["alpha"])
+    return host(ybuf)
+
+
+def expect_windows(kind, c):
+    nb, rows, cols = c["nb"], c["rows"], c["cols"]
+    segs = np.stack([c["x"][s:s + cols] for s in c["starts"]])
+    z = None if c["z"] is None else np.stack([c["z"][k * c["zs"]:k * c["zs"] + rows] for k in range(nb)])
+    val, mag = products(kind, c["M"], segs, c["alpha"], z)
+    e = Expect(kind, nan((nb - 1) * c["ys"] + rows + 2))
+    for k in range(nb):
+        e.put(slice(1 + k * c["ys"], 1 + k * c["ys"] + rows), val[k], mag[k])
+    return e
+
+
+@pytest.mark.parametrize("name", list(WINDOWS))
+@pytest.mark.parametrize("kind", KINDS)
+def test_dense_gemv_windows(kind, name):
+    c = windows_case(kind, name)
+    expect_windows(kind, c).check(run_windows(ops, dev, c), c["cols"], name)
+
+
+def windows_off_case(kind, cols, rows, with_z):
+    """Window starts that are odd (8-byte aligned only), equal, and overlapping."""
+    L = dict(nb=4, rows=rows, cols=cols, xs=None, ys=rows + 2, zs=rows + 1 if with_z else None, alpha=None)
+    return windows_case(kind, L, starts=[1, 1, 1 + cols // 2, 5])
+
+
+@pytest.mark.parametrize("with_z", [False, True], ids=["noz", "z"])
+@pytest.mark.parametrize("rows", [1, 5])
+@pytest.mark.parametrize("cols", [2, 128, 130])
+@pytest.mark.parametrize("kind", KINDS)
+def test_dense_gemv_windows_off(kind, cols, rows, with_z):
+    c = windows_off_case(kind, cols, rows, with_z)
+    expect_windows(kind, c).check(run_windows(ops, dev, c, off=True), cols)
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_dense_gemv_windows_off_grid_stride(kind):
+    nb = WAVES_CAP // 2 + 4
+    L = dict(nb=nb, rows=2, cols=2, xs=None, ys=2, zs=2, alpha=-1.0)
+    c = windows_case(kind, L, starts=(np.arange(nb) * 7) % 11)
+    expect_windows(kind, c).check(run_windows(ops, dev, c, off=True), 2)
+
+
+# ---- coarse_front / coarse_back (strips of consecutive unknowns) ------------------------------------------------------------
+def front_case(kind, nb, bs, ntail):
+    """perm = strips at scattered starts (odd ones too), consecutive inside a strip, then a tail of scattered unknowns."""
+    rng = np.random.default_rng([3, nb, bs, ntail])
+    L = nb * (bs + 3) + ntail + 7
+    starts, pos = np.zeros(nb, dtype=np.int64), 3
+    for k in reversed(range(nb)):
+        starts[k], pos = pos, pos + bs + 3
+    strips = (starts[:, None] + np.arange(bs)[None, :]).ravel()
+    rest = np.setdiff1d(np.arange(L), strips)
+    perm = np.concatenate([strips, rng.permutation(rest)[:ntail]])
+    return dict(M=data(kind, rng, nb, bs, bs), b=data(kind, rng, L), perm=i32(perm), nb=nb, bs=bs, ntail=ntail)
+
+
+def run_front(c):
+    nI = c["nb"] * c["bs"]
+    ybuf, tbuf = dev(nan(nI + 2)), dev(nan(c["ntail"] + 2))
+    ops.coarse_front(dev(c["M"]), dev(c["b"]), dev(c["perm"]), ybuf[1:-1], tbuf[1:1 + c["ntail"]])
+    return host(ybuf), host(tbuf)
+
+
+@pytest.mark.parametrize("nb", [1, 2])
+@pytest.mark.parametrize("bs", [2, 130, 1022, 1026])
+@pytest.mark.parametrize("kind", KINDS)
+def test_coarse_front(kind, bs, nb):
+    for ntail in (0, 1, 300):
+        c = front_case(kind, nb, bs, ntail)
+        nI = nb * bs
+        gy, gt = run_front(c)
+        val, mag = products(kind, c["M"], c["b"][c["perm"][:nI]].reshape(nb, bs))
+        ey = Expect(kind, nan(nI + 2))
+        ey.put(slice(1, -1), val.ravel(), mag.ravel())
+        ey.check(gy, bs, "y, ntail %d" % ntail)
+        et = Expect(kind, nan(ntail + 2))
+        et.put_bits(slice(1, 1 + ntail), c["b"][c["perm"][nI:]])
+        et.check(gt, 0, "tail, ntail %d" % ntail)
+
+
+def back_case(kind, nb, rows, cols, ntail, accumulate, full=False):
+    rng = np.random.default_rng([4, nb, rows, cols, ntail, int(accumulate)])
+    nI = nb * rows
+    starts = np.array([1, 1, 1 + cols // 2, 5])[:nb]
+    nout = nI + ntail + (0 if full else 5)
+    return dict(M=data(kind, rng, nb, rows, cols), starts=starts, x=data(kind, rng, max(int(starts.max()) + cols, ntail) + 1),
+                z=data(kind, rng, nI), alpha=scalar(kind, rng), perm=i32(rng.permutation(nout)[:nI + ntail]),
+                before=data(kind, rng, nout) if accumulate else nan(nout), nb=nb, rows=rows, cols=cols, ntail=ntail,
+                accumulate=accumulate)
+
+
+def run_back(c):
+    out = dev(c["before"])
+    ops.coarse_back(dev(c["M"]), dev(c["x"]), dev(i32(c["starts"])), dev(c["z"]), c["alpha"], dev(c["perm"]), out,
+                    c["accumulate"], c["ntail"])
+    return host(out)
+
+
+def expect_back(kind, c, xidx=None, oidx=None, tail_idx=None):
+    """out[oidx[k*rows + r]] (+)= z + alpha * M_k[r] . x[window k] (oidx < 0: skipped), out[tail_idx[i]] (+)= x[i]."""
+    nb, rows, cols = c["M"].shape
+    segs = np.stack([c["x"][s:s + cols] for s in c["starts"]]) if xidx is None else c["x"][xidx].reshape(nb, cols)
+    val, mag = products(kind, c["M"], segs, c["alpha"], c["z"].reshape(nb, rows))
+    e = Expect(kind, c["before"])
+    ok = oidx >= 0
+    e.put(oidx[ok], val.ravel()[ok], mag.ravel()[ok], c["accumulate"])
+    xt = c["x"][:tail_idx.size]
+    e.put_bits(tail_idx, xt + c["before"][tail_idx] if c["accumulate"] else xt)      # (one float64 addition: exact bits)
+    return e
+
+
+@pytest.mark.parametrize("accumulate", [False, True], ids=["set", "acc"])
+@pytest.mark.parametrize("rows", [1, 7])
+@pytest.mark.parametrize("cols", [2, 510, 514])
+@pytest.mark.parametrize("kind", KINDS)
+def test_coarse_back(kind, cols, rows, accumulate):
+    for ntail in (0, 1, 300):
+        c = back_case(kind, 3, rows, cols, ntail, accumulate)
+        nI = 3 * rows
+        e = expect_back(kind, c, oidx=c["perm"][:nI].astype(np.int64), tail_idx=c["perm"][nI:].astype(np.int64))
+        e.check(run_back(c), cols, "ntail %d" % ntail)
+
+
+# ---- coarse_front_gather / coarse_back_gather (every operand index from a table) -------------------------------------------
+def front_gather_case(kind, nb, bs, ntail):
+    """idx: a random permutation with a share of -1 padding; with more than one block the last one is padding only."""
+    rng = np.random.default_rng([5, nb, bs, ntail])
+    L = nb * bs + 9
+    idx = rng.permutation(L)[:nb * bs].astype(np.int64)
+    idx[rng.random(nb * bs) < 0.2] = -1
+    if nb > 1:
+        idx[(nb - 1) * bs:] = -1
+    return dict(M=data(kind, rng, nb, bs, bs), b=data(kind, rng, max(L, ntail)), idx=i32(idx),
+                tail_idx=i32(rng.permutation(max(L, ntail))[:ntail]))
+
+
+def run_front_gather(mod, put, c):
+    nb, bs, _ = c["M"].shape
+    ntail = c["tail_idx"].size
+    ybuf, tbuf = put(nan(nb * bs + 2)), put(nan(ntail + 2))
+    mod.coarse_front_gather(put(c["M"]), put(c["b"]), put(c["idx"]), ybuf[1:-1], put(c["tail_idx"]), tbuf[1:1 + ntail])
+    return host(ybuf), host(tbuf)
+
+
+def expect_front_gather(kind, c):
+    nb, bs, _ = c["M"].shape
+    ntail = c["tail_idx"].size
+    idx = c["idx"].astype(np.int64)
+    seg = np.where(idx >= 0, c["b"][np.maximum(idx, 0)], 0.0).reshape(nb, bs)
+    val, mag = products(kind, c["M"], seg)
+    ey = Expect(kind, nan(nb * bs + 2))
+    ey.put(slice(1, -1), val.ravel(), mag.ravel())
+    et = Expect(kind, nan(ntail + 2))
+    et.put_bits(slice(1, 1 + ntail), c["b"][c["tail_idx"]])
+    return ey, et
+
+
+GATHER_SHAPES = [(nb, ntail) for nb in (1, 3) for ntail in (0, 1, 1000)]      # 1000 > 1 block x 256 threads: tail stride loop
+
+
+@pytest.mark.parametrize("bs", [2, 36, 38, 74, 128, 130, 300])
+@pytest.mark.parametrize("kind", KINDS)
+def test_coarse_front_gather(kind, bs):
+    for nb, ntail in GATHER_SHAPES:
+        c = front_gather_case(kind, nb, bs, ntail)
+        ey, et = expect_front_gather(kind, c)
+        gy, gt = run_front_gather(ops, dev, c)
+        ey.check(gy, bs, "y, %d blocks, ntail %d" % (nb, ntail))
+        et.check(gt, 0, "tail, %d blocks, ntail %d" % (nb, ntail))
+
+
+def back_gather_case(kind, nb, rows, cols, ntail, accumulate):
+    rng = np.random.default_rng([6, nb, rows, cols, ntail, int(accumulate)])
+    nI = nb * rows
+    nx = max(cols + 3, ntail)
+    nout = nI + ntail + 5
+    where = rng.permutation(nout)
+    oidx = where[:nI].astype(np.int64)
+    oidx[rng.random(nI) < 0.2] = -1
+    if nb > 1:
+        oidx[(nb - 1) * rows:] = -1
+    return dict(M=data(kind, rng, nb, rows, cols), x=data(kind, rng, nx), xidx=i32(rng.integers(0, nx, nb * cols)),
+                z=data(kind, rng, nI), alpha=scalar(kind, rng), oidx=i32(oidx), tail_idx=i32(where[nI:nI + ntail]),
+                before=data(kind, rng, nout) if accumulate else nan(nout), accumulate=accumulate)
+
+
+def run_back_gather(mod, put, c):
+    out = put(c["before"])
+    mod.coarse_back_gather(put(c["M"]), put(c["x"]), put(c["xidx"]), put(c["z"]), c["alpha"], put(c["oidx"]),
+                           put(c["tail_idx"]), out, c["accumulate"])
+    return host(out)
+
+
+def expect_back_gather(kind, c):
+    return expect_back(kind, c, xidx=c["xidx"].astype(np.int64), oidx=c["oidx"].astype(np.int64),
+                       tail_idx=c["tail_idx"].astype(np.int64))
+
+
+@pytest.mark.parametrize("cols", [2, 128, 130, 300])
+@pytest.mark.parametrize("rows", [2, 36, 38, 74])
+@pytest.mark.parametrize("kind", KINDS)
+def test_coarse_back_gather(kind, rows, cols):
+    for nb, ntail in GATHER_SHAPES:
+        for accumulate in (False, True):
+            c = back_gather_case(kind, nb, rows, cols, ntail, accumulate)
+            expect_back_gather(kind, c).check(run_back_gather(ops, dev, c), cols,
+                                              "%d blocks, ntail %d, accumulate %d" % (nb, ntail, accumulate))
+
+
+# ---- gemm / copy2d on strided views ------------------------------------------------------------------------------------------
+def sub(t, r0, rows, c0, cols):
+    return t[..., r0:r0 + rows, c0:c0 + cols]
+
+
+def gemm_check(kind, batch, M, N, K, alpha, beta, broadcast=None, seed=0):
+    """Operands and result as sub-blocks of larger matrices (lda > K, ldb > N, ldc > N, guard cells all round)."""
+    rng = np.random.default_rng([7, batch, M, N, K, seed])
+    Ab = nan(*((batch,) if broadcast != "A" else ()), M + 2, K + 3)     # (NaN around the operands: a read outside shows)
+    Bb = nan(*((batch,) if broadcast != "B" else ()), K + 3, N + 2)
+    sub(Ab, 1, M, 2, K)[...] = data(kind, rng, *Ab.shape[:-2], M, K)
+    sub(Bb, 2, K, 1, N)[...] = data(kind, rng, *Bb.shape[:-2], K, N)
+    Cb = nan(batch, M + 2, N + 3) if beta == 0.0 else data(kind, rng, batch, M + 2, N + 3)
+    dA, dB, dC = dev(Ab), dev(Bb), dev(Cb)
+    ops.gemm(sub(dA, 1, M, 2, K), sub(dB, 2, K, 1, N), sub(dC, 1, M, 1, N), alpha=alpha, beta=beta)
+    Aw, Bw = wide(kind, sub(Ab, 1, M, 2, K)), wide(kind, sub(Bb, 2, K, 1, N))
+    a = wide(kind, alpha)[()]
+    val = a * (Aw @ Bw) + np.zeros((batch, 1, 1), dtype=Aw.dtype)
+    mag = abs(a) * (np.abs(Aw) @ np.abs(Bw)) + np.zeros((batch, 1, 1), dtype=Aw.dtype)
+    if beta != 0.0:                                                     # (beta == 0: C is not read -- it holds NaN)
+        Cw, bw = wide(kind, sub(Cb, 1, M, 1, N)), wide(kind, beta)[()]
+        val, mag = val + bw * Cw, mag + abs(bw) * np.abs(Cw)
+    e = Expect(kind, Cb)
+    e.put((slice(None), slice(1, 1 + M), slice(1, 1 + N)), val, mag)
+    e.check(host(dC), K, "batch %d, alpha %g, beta %g, broadcast %s" % (batch, alpha, beta, broadcast))
+
+
+@pytest.mark.parametrize("MNK", [(1, 1, 1), (63, 65, 15), (64, 64, 16), (65, 63, 17), (130, 70, 33), (5, 5, 0)],
+                         ids=lambda s: "x".join(map(str, s)))
+@pytest.mark.parametrize("kind", KINDS)
+def test_gemm_on_views(kind, MNK):
+    rng = np.random.default_rng(70)
+    for batch in (1, 3):
+        gemm_check(kind, batch, *MNK, alpha=scalar(kind, rng), beta=0.0)
+        gemm_check(kind, batch, *MNK, alpha=-1.0, beta=1.0)
+        gemm_check(kind, batch, *MNK, alpha=scalar(kind, rng), beta=scalar(kind, rng))
+    gemm_check(kind, 3, *MNK, alpha=scalar(kind, rng), beta=0.0, broadcast="A")
+    gemm_check(kind, 3, *MNK, alpha=-1.0, beta=1.0, broadcast="B")
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_gemm_into_the_lower_left_block_of_the_inverse(kind):
+    """The destination _inv_schur_dev writes -W to: out[:, h:, :h] of a fresh (b, n, n) batch, alpha = -1."""
+    rng = np.random.default_rng(71)
+    b, n = 3, 37
+    h = n // 2
+    IS, V = data(kind, rng, b, n - h, n - h), data(kind, rng, b, n - h, h)
+    out = dev(nan(b, n, n))
+    ops.gemm(dev(IS), dev(V), out[:, h:, :h], alpha=-1.0)
+    e = Expect(kind, nan(b, n, n))
+    Iw, Vw = wide(kind, IS), wide(kind, V)
+    e.put((slice(None), slice(h, n), slice(0, h)), -(Iw @ Vw), np.abs(Iw) @ np.abs(Vw))
+    e.check(host(out), n - h)
+
+
+def copy2d_check(kind, src_view, dst_view, src_np, dst_before, dst_pos, dst_buf, alpha, accumulate, what):
+    ops.copy2d(src_view, dst_view, alpha=alpha, accumulate=accumulate)
+    a = wide(kind, alpha)[()]
+    val = a * wide(kind, src_np)
+    e = Expect(kind, dst_before)
+    e.put(dst_pos, val, np.abs(val), accumulate)
+    e.check(host(dst_buf), 0, what)
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_copy2d(kind):
+    rng = np.random.default_rng(72)
+    # the diagonal as a strided column (_defect_dev): cols = 1, ld = n + 1, batch stride n * n
+    b, n = 2, 7
+    src = data(kind, rng, b, n, 1)
+    D = dev(nan(b, n, n))
+    diag = (np.arange(b)[:, None], np.arange(n)[None, :], np.arange(n)[None, :])
+    copy2d_check(kind, dev(src), torch.as_strided(D, (b, n, 1), (n * n, n + 1, 1)), src[:, :, 0], nan(b, n, n), diag, D, 1.0,
+                 False, "diagonal")
+    # a sub-block into a sub-block, alpha = -2; then accumulated onto data
+    r, c = 5, 9
+    Sb = data(kind, rng, 3, r + 3, c + 4)
+    for accumulate in (False, True):
+        before = data(kind, rng, 3, r + 4, c + 2) if accumulate else nan(3, r + 4, c + 2)
+        Db = dev(before)
+        copy2d_check(kind, sub(dev(Sb), 1, r, 2, c), sub(Db, 2, r, 1, c), sub(Sb, 1, r, 2, c), before,
+                     (slice(None), slice(2, 2 + r), slice(1, 1 + c)), Db, -2.0, accumulate, "sub-block, accumulate %d" % accumulate)
+    # more elements than 4096 workgroups x 256 threads: the stride loop
+    rows, cols = 1025, 1024
+    assert rows * cols > 4096 * 256
+    Sb = data(kind, rng, 1, rows, cols + 1)
+    Db = dev(nan(1, rows, cols + 2))
+    copy2d_check(kind, sub(dev(Sb), 0, rows, 0, cols), sub(Db, 0, rows, 1, cols), sub(Sb, 0, rows, 0, cols),
+                 nan(1, rows, cols + 2), (slice(None), slice(None), slice(1, 1 + cols)), Db, scalar(kind, rng), False, "stride loop")
+
+
+# ---- block_copy, csr_to_dense, pattern_parity_counts -------------------------------------------------------------------------
+def run_block_copy(mod, put, src, nb, bs, ss, ds):
+    dbuf = put(nan((nb - 1) * ds + bs + 2))
+    mod.block_copy(nb, bs, put(src), ss, dbuf[1:-1], ds)
+    return host(dbuf)
+
+
+def expect_block_copy(src, nb, bs, ss, ds):
+    e = Expect("real", nan((nb - 1) * ds + bs + 2))
+    for k in range(nb):
+        e.put_bits(slice(1 + k * ds, 1 + k * ds + bs), src[k * ss:k * ss + bs])
+    return e
+
+
+@pytest.mark.parametrize("nb,bs,ss,ds", [(3, 1, 1, 2), (3, 2, 2, 4), (3, 130, 130, 260), (3, 5, 7, 6),
+                                         (THREADS_CAP // 130 + 40, 130, 130, 260)])
+def test_block_copy(nb, bs, ss, ds):
+    """(3, b, b, 2b): the call of BlockCyclicReduction.apply; the last case is beyond one element per thread."""
+    assert nb == 3 or nb * bs > THREADS_CAP
+    src = data("real", np.random.default_rng([8, nb, bs]), (nb - 1) * ss + bs)
+    expect_block_copy(src, nb, bs, ss, ds).check(run_block_copy(ops, dev, src, nb, bs, ss, ds), 0)
+
+
+def test_csr_to_dense_sums_duplicates():
+    """A rectangular matrix with empty rows and duplicate entries, added onto what `dense` holds (exact data)."""
+    rng = np.random.default_rng(9)
+    n, m = 301, 47                                                      # (more than one workgroup of rows)
+    counts = rng.integers(0, 9, n)
+    counts[::5] = 0
+    rows = np.repeat(np.arange(n), counts)
+    cols = rng.integers(0, m, rows.size)                                # repeats inside a row: duplicates, unsorted
+    vals = data("exact", rng, rows.size)
+    assert np.unique(rows * m + cols).size < rows.size
+    rowptr = np.concatenate([[0], np.cumsum(counts)])
+    dA = DeviceCSR(dev(i32(rowptr)), dev(i32(cols)), dev(vals), (n, m))
+    before = np.concatenate([nan(3), data("exact", rng, n * m), nan(3)])
+    buf = dev(before)
+    ops.csr_to_dense(dA, buf[3:-3].view(n, m))
+    e = Expect("exact", before)
+    want = sp.coo_matrix((vals, (rows, cols)), shape=(n, m)).toarray()
+    e.put(slice(3, -3), wide("exact", want.ravel()), 0, accumulate=True)
+    e.check(host(buf), 0)
+    # and what coarse.csr_to_dense makes of it
+    assert np.array_equal(host(coarse.csr_to_dense(dA)), want)
+
+
+def parity_counts(pid, W):
+    i = np.arange(pid.size, dtype=np.int64)
+    key = (((i // W) & 1) * 2 + ((i % W) & 1)) * 256 + pid
+    return np.bincount(key, minlength=1024).astype(np.int64)
+
+
+@pytest.mark.parametrize("n,W", [(1, 1), (1000, 1), (1003, 5), (64 * 40 + 17, 64), (129 * 31 + 77, 129),
+                                 (THREADS_CAP * 16 + 4099, 129)])
+def test_pattern_parity_counts(n, W):
+    """Against the NumPy histogram; counts are added onto what the table holds.  The last n is beyond 16 rows per thread."""
+    assert W == 1 or n % W
+    rng = np.random.default_rng([10, n, W])
+    pid = rng.integers(0, 256, n).astype(np.uint8)
+    pid[:2] = (0, 255)[:min(n, 2)]
+    before = rng.integers(0, 5, 1024).astype(np.int32)
+    d_pid, cnt = dev(pid), dev(before)
+    _lib.check(_lib.lib().lmg_pattern_parity_counts(n, W, d_pid.data_ptr(), cnt.data_ptr(), ops._s(d_pid)))
+    assert np.array_equal(host(cnt).astype(np.int64), before + parity_counts(pid, W))
+
+
+# ---- the bit-identities include/lmg.h states -------------------------------------------------------------------------------
+def bits(t):
+    return t.view(torch.int64)
+
+
+@pytest.mark.parametrize("bs", [130, 1026])
+def test_coarse_front_is_gather_then_blockdiag(bs):
+    c = front_case("real", 2, bs, 300)
+    nI, n = 2 * bs, 2 * bs + 300
+    M, b, perm = dev(c["M"]), dev(c["b"]), dev(c["perm"])
+    y1, t1 = dev(nan(nI)), dev(nan(300))
+    ops.coarse_front(M, b, perm, y1, t1)
+    bp, y2 = dev(nan(n)), dev(nan(nI))
+    ops.gather(perm, b, bp)
+    ops.dense_gemv_blockdiag(M, bp[:nI], y2)
+    assert torch.equal(bits(y1), bits(y2)) and torch.equal(bits(t1), bits(bp[nI:]))
+    assert not torch.isnan(y1).any()
+
+
+@pytest.mark.parametrize("cols", [130, 514])
+def test_coarse_back_is_windows_off_then_scatter_then_axpby(cols):
+    nb, rows, ntail = 3, 7, 300
+    nI = nb * rows
+    c = back_case("real", nb, rows, cols, ntail, True, full=True)
+    M, x, xo, z, perm = dev(c["M"]), dev(c["x"]), dev(i32(c["starts"])), dev(c["z"]), dev(c["perm"])
+    out1 = dev(nan(nI + ntail))
+    ops.coarse_back(M, x, xo, z, c["alpha"], perm, out1, False, ntail)
+    xp, out2 = dev(nan(nI + ntail)), dev(nan(nI + ntail))
+    ops.dense_gemv_windows_off(M, x, xo, xp[:nI], rows, z=z, z_stride=rows, alpha=c["alpha"])
+    ops.copy(x[:ntail], xp[nI:])
+    ops.scatter(perm, xp, out2)
+    assert torch.equal(bits(out1), bits(out2)) and not torch.isnan(out1).any()
+    acc1, acc2 = dev(c["before"]), dev(c["before"])
+    ops.coarse_back(M, x, xo, z, c["alpha"], perm, acc1, True, ntail)
+    ops.axpby(1.0, out2, 1.0, acc2)
+    assert torch.equal(bits(acc1), bits(acc2))
+    assert not torch.equal(acc1, dev(c["before"]))
+
+
+# ---- the CPU stand-ins of tests/cpu_ops_shim.py against the kernels they stand for ----------------------------------------
+def test_shim_dense_gemv_blockdiag():
+    for nb, bs in ((3, 2), (3, 130)):
+        M, x = blockdiag_case("real", nb, bs)
+        e = expect_blockdiag("real", M, x)
+        got, stand_in = run_blockdiag(ops, dev, M, x), run_blockdiag(shim, cpu, M, x)
+        e.check(stand_in, bs, "shim")
+        between(e, got, stand_in, bs)
+
+
+def between(e, got, stand_in, K):
+    """The same bound between kernel and stand-in: the stand-in's values take the place of the reference."""
+    w = e.written
+    assert np.array_equal(np.isnan(got), np.isnan(stand_in))
+    pair = Expect("real", e.before)
+    pair.put(np.nonzero(w), wide("real", stand_in[w]), e.mag[w])
+    pair.check(got, K, "kernel against shim")
+
+
+@pytest.mark.parametrize("name", ["c130r5", "c128r1z", "bcr_rhs_b66", "bcr_odd_b66", "bcr_c_b2", "bcr_wide_b2"])
+def test_shim_dense_gemv_windows(name):
+    c = windows_case("real", name)
+    e = expect_windows("real", c)
+    got, stand_in = run_windows(ops, dev, c), run_windows(shim, cpu, c)
+    e.check(stand_in, c["cols"], "shim")
+    between(e, got, stand_in, c["cols"])
+
+
+@pytest.mark.parametrize("with_z", [False, True], ids=["noz", "z"])
+def test_shim_dense_gemv_windows_off(with_z):
+    c = windows_off_case("real", 130, 5, with_z)
+    e = expect_windows("real", c)
+    got, stand_in = run_windows(ops, dev, c, off=True), run_windows(shim, cpu, c, off=True)
+    e.check(stand_in, 130, "shim")
+    between(e, got, stand_in, 130)
+
+
+def test_shim_coarse_front_gather():
+    for nb, ntail in ((1, 1000), (3, 1)):
+        c = front_gather_case("real", nb, 74, ntail)
+        ey, et = expect_front_gather("real", c)
+        (gy, gt), (sy, st) = run_front_gather(ops, dev, c), run_front_gather(shim, cpu, c)
+        ey.check(sy, 74, "shim y")
+        et.check(st, 0, "shim tail")
+        between(ey, gy, sy, 74)
+        assert np.array_equal(gt.view(np.int64), st.view(np.int64))
+
+
+@pytest.mark.parametrize("accumulate", [False, True], ids=["set", "acc"])
+def test_shim_coarse_back_gather(accumulate):
+    for nb, ntail in ((1, 1000), (3, 1)):
+        c = back_gather_case("real", nb, 38, 130, ntail, accumulate)
+        e = expect_back_gather("real", c)
+        got, stand_in = run_back_gather(ops, dev, c), run_back_gather(shim, cpu, c)
+        e.check(stand_in, 130, "shim")
+        between(e, got, stand_in, 130)
+
+
+def test_shim_block_copy():
+    nb, bs, ss, ds = 3, 130, 130, 260
+    src = data("real", np.random.default_rng(11), (nb - 1) * ss + bs)
+    got, stand_in = run_block_copy(ops, dev, src, nb, bs, ss, ds), run_block_copy(shim, cpu, src, nb, bs, ss, ds)
+    expect_block_copy(src, nb, bs, ss, ds).check(stand_in, 0, "shim")
+    assert np.array_equal(got.view(np.int64), stand_in.view(np.int64))
+
+
+# ---- solver paths that no other device test takes ---------------------------------------------------------------------------
+def galerkin_operator(m):
+    A, _ = P.poisson_2d_structured(2 * m)
+    Pm = P.tensor_interpolator_2d(2 * m + 1)
+    Ac = sp.csr_matrix(Pm.T @ A @ Pm)
+    Ac.sort_indices()
+    return Ac
+
+
+def scrambled_operator():
+    """The operator of test_block_cyclic_reduction_reorders_scrambled_operators (test_coarse_cpu.py)."""
+    Ac = galerkin_operator(40)
+    rng = np.random.default_rng(3)
+    p = rng.permutation(Ac.shape[0])
+    As = sp.csr_matrix(Ac[p][:, p])
+    As.sort_indices()
+    return As
+
+
+OPERATORS = {"9pt_33": lambda: galerkin_operator(32), "9pt_65": lambda: galerkin_operator(64), "scrambled_41": scrambled_operator}
+
+
+def solve_case(name):
+    Ac = OPERATORS[name]()
+    b = np.random.default_rng(12).standard_normal(Ac.shape[0])
+    return Ac, b, spla.spsolve(sp.csc_matrix(Ac), b)
+
+
+def rel_err(x, want):
+    return np.linalg.norm(host(x) - want) / np.linalg.norm(want)
+
+
+@pytest.mark.parametrize("name", list(OPERATORS))
+def test_block_cyclic_reduction_on_the_device_matches_superlu(name):
+    """lmg_dense_gemv_windows and lmg_block_copy are all BlockCyclicReduction.apply runs; 1e-10 is what test_coarse_cpu.py
+    asserts for this solver (on the stand-ins) for the 9-point and the scrambled operator."""
+    Ac, b, want = solve_case(name)
+    solver = coarse.make_coarse_solver(DeviceCSR.from_scipy(Ac, DEV), ops, "bcr")
+    assert solver.kind == "block-cyclic-reduction" and (solver.perm is not None) == (name == "scrambled_41")
+    x = dev(nan(Ac.shape[0]))
+    solver.apply(dev(b), x)
+    err = rel_err(x, want)
+    print("bcr %s: relative error %.3g" % (name, err))
+    assert err < 1e-10
+
+
+@pytest.mark.parametrize("name", ["9pt_33", "9pt_65"])
+def test_banded_solver_without_the_folded_permutation_is_bit_equal(name, monkeypatch):
+    Ac, b, want = solve_case(name)
+    n = Ac.shape[0]
+    solver = coarse.make_coarse_solver(DeviceCSR.from_scipy(Ac, DEV), ops, "banded")
+    assert solver.kind == "banded-block" and solver.W is not None
+    prev = np.random.default_rng(13).standard_normal(n)
+    folded, folded_acc = dev(nan(n)), dev(prev)
+    solver.apply(dev(b), folded)
+    solver.apply(dev(b), folded_acc, accumulate=True)
+    monkeypatch.setattr(coarse, "FOLD_PERMUTATION", False)
+    plain, plain_acc = dev(nan(n)), dev(prev)
+    solver.apply(dev(b), plain)                              # gather, blockdiag, spmv, gemv, windows_off, scatter
+    solver.apply(dev(b), plain_acc, accumulate=True)         # ... into a temporary, then axpby
+    assert torch.equal(bits(plain), bits(folded)) and not torch.isnan(plain).any()
+    assert torch.equal(bits(plain_acc), bits(folded_acc))
+    assert torch.equal(bits(plain_acc), bits(dev(prev) + plain))      # (axpby(1, ., 1, .): one rounding per entry)
+    err = rel_err(plain, want)
+    print("banded unfolded %s: relative error %.3g" % (name, err))
+    assert err < 1e-11                                       # (test_coarse_cpu.py's bound for this solver on the stand-ins)
+
+
+@pytest.mark.parametrize("name", ["9pt_33", "9pt_65"])
+def test_banded_solver_with_the_two_launch_back_substitution(name, monkeypatch):
+    """x_I = A_II^-1 (b_I - A_IS x_S): lmg_dense_gemv_blockdiag a second time instead of lmg_dense_gemv_windows_off;
+    another order of sums, so against SuperLU at the tolerance test_coarse_gpu.py asserts."""
+    Ac, b, want = solve_case(name)
+    n = Ac.shape[0]
+    monkeypatch.setattr(coarse, "BACKSUB_ONE_LAUNCH", False)
+    solver = coarse.make_coarse_solver(DeviceCSR.from_scipy(Ac, DEV), ops, "banded")
+    assert solver.kind == "banded-block" and solver.W is None
+    x = dev(nan(n))
+    solver.apply(dev(b), x)
+    err = rel_err(x, want)
+    print("banded two-launch %s: relative error %.3g" % (name, err))
+    assert err < 1e-12
+    acc = x.clone()
+    solver.apply(dev(b), acc, accumulate=True)
+    assert torch.equal(bits(acc), bits(x + x))
+
+
+def dominant(rng, *shape):
+    """Diagonally dominant by rows (the diagonal is twice the sum of the others' magnitudes)."""
+    A = rng.uniform(-1.0, 1.0, shape)
+    n = shape[-1]
+    eye = np.eye(n, dtype=bool)
+    A[..., eye] = 0.0
+    A[..., eye] = 2.0 * np.abs(A).sum(-1) + 1.0
+    return A
+
+
+@pytest.mark.parametrize("shape", [(1, 1), (129, 129), (200, 200), (3, 150, 150), (2, 257, 257)], ids=lambda s: "x".join(map(str, s)))
+def test_dense_inverse_on_the_device_needs_no_fallback(shape, monkeypatch):
+    """The Schur recursion on lmg_batched_gemm / lmg_copy2d / lmg_batched_inverse alone: torch.linalg.inv, the first step of
+    the fallback, raises."""
+    A = dominant(np.random.default_rng([14, *shape]), *shape)
+    cond = float(np.max(np.linalg.cond(A)))
+    assert cond <= 100.0
+
+    def no_fallback(*a, **k):
+        raise AssertionError("dense_inverse fell back to torch.linalg.inv")
+
+    monkeypatch.setattr(torch.linalg, "inv", no_fallback)
+    dA = dev(A)
+    M = coarse.dense_inverse(dA)
+    defect = coarse._defect_dev(dA, M)
+    got, ref = host(M), np.linalg.inv(A)
+    eye = np.eye(shape[-1])
+    print("dense_inverse %s: cond %.3g, defect (Frobenius, own kernels) %.3g, max |I - A M| %.3g, NumPy's max |I - A inv(A)| %.3g, "
+          "max |M - inv(A)| / max |inv(A)| %.3g" % (shape, cond, defect, np.abs(eye - A @ got).max(), np.abs(eye - A @ ref).max(),
+                                                    np.abs(got - ref).max() / np.abs(ref).max()))
+    assert got.shape == A.shape and defect < 1e-9
+    assert np.abs(eye - A @ got).max() < 1e-9
+    assert np.abs(got - ref).max() <= 1e-9 * cond * np.abs(ref).max()
+
+
+# ---- argument checks (real, adequately sized device tensors only: a check that wrongly passes still reads inside them) -------
+OK, ERR_ARG, ERR_ALIGN, ERR_CAPACITY = 0, -1, -2, -4
+
+
+def test_entry_points_check_their_arguments():
+    L = _lib.lib()
+    f = dev(np.ones(4096))                                   # every double operand below fits into 4096 entries
+    g, y = dev(np.ones(4096)), dev(nan(4096))
+    ix = dev(np.zeros(4096, dtype=np.int32))
+    p = lambda t: t.data_ptr()
+    s = ops._s(f)
+    untouched = lambda: bool(torch.isnan(y).all())
+    # odd block size / columns / window stride; a matrix 8 bytes off
+    assert L.lmg_dense_gemv_blockdiag(2, 3, p(f), p(g), p(y), s) == ERR_ALIGN
+    assert L.lmg_dense_gemv_blockdiag(2, 4, p(f[1:]), p(g), p(y), s) == ERR_ALIGN
+    assert L.lmg_dense_gemv_blockdiag(2, 4, p(f), p(g[1:]), p(y), s) == ERR_ALIGN
+    assert L.lmg_dense_gemv_windows(2, 2, 3, p(f), p(g), 4, None, 0, 1.0, p(y), 2, s) == ERR_ALIGN
+    assert L.lmg_dense_gemv_windows(2, 2, 4, p(f), p(g), 3, None, 0, 1.0, p(y), 2, s) == ERR_ALIGN
+    assert L.lmg_dense_gemv_windows(2, 2, 4, p(f[1:]), p(g), 4, None, 0, 1.0, p(y), 2, s) == ERR_ALIGN
+    assert L.lmg_dense_gemv_windows_off(2, 2, 3, p(f), p(g), p(ix), None, 0, 1.0, p(y), 2, s) == ERR_ALIGN
+    assert L.lmg_dense_gemv_windows_off(2, 2, 4, p(f[1:]), p(g), p(ix), None, 0, 1.0, p(y), 2, s) == ERR_ALIGN
+    assert L.lmg_coarse_front(2, 3, p(f), p(g), p(ix), p(y), 2, p(y[8:]), s) == ERR_ALIGN
+    assert L.lmg_coarse_front(2, 4, p(f[1:]), p(g), p(ix), p(y), 2, p(y[8:]), s) == ERR_ALIGN
+    assert L.lmg_coarse_back(2, 2, 3, p(f), p(g), p(ix), p(g), 2, 1.0, p(ix), p(y), 0, 2, s) == ERR_ALIGN
+    assert L.lmg_coarse_back(2, 2, 4, p(f[1:]), p(g), p(ix), p(g), 2, 1.0, p(ix), p(y), 0, 2, s) == ERR_ALIGN
+    assert L.lmg_coarse_front_gather(2, 3, p(f), p(g), p(ix), p(y), 2, p(ix), p(y[8:]), s) == ERR_ALIGN
+    assert L.lmg_coarse_front_gather(2, 4, p(f[1:]), p(g), p(ix), p(y), 2, p(ix), p(y[8:]), s) == ERR_ALIGN
+    assert L.lmg_coarse_front_gather(2, 4, p(f), p(g), p(ix[1:]), p(y), 2, p(ix), p(y[8:]), s) == ERR_ALIGN
+    assert L.lmg_coarse_back_gather(2, 2, 3, p(f), p(g), p(ix), p(g), 2, 1.0, p(ix), p(y), 0, 2, p(ix), s) == ERR_ALIGN
+    assert L.lmg_coarse_back_gather(2, 2, 4, p(f[1:]), p(g), p(ix), p(g), 2, 1.0, p(ix), p(y), 0, 2, p(ix), s) == ERR_ALIGN
+    assert L.lmg_coarse_back_gather(2, 2, 4, p(f), p(g), p(ix[1:]), p(g), 2, 1.0, p(ix), p(y), 0, 2, p(ix), s) == ERR_ALIGN
+    # blocks that overlap in y; aliased operands
+    assert L.lmg_dense_gemv_windows(2, 4, 2, p(f), p(g), 2, None, 0, 1.0, p(y), 3, s) == ERR_ARG
+    assert L.lmg_dense_gemv_windows_off(2, 4, 2, p(f), p(g), p(ix), None, 0, 1.0, p(y), 3, s) == ERR_ARG
+    assert L.lmg_block_copy(2, 4, p(f), 4, p(y), 3, s) == ERR_ARG
+    assert L.lmg_dense_gemv_blockdiag(2, 4, p(f), p(y), p(y), s) == ERR_ARG
+    assert L.lmg_dense_gemv_windows(2, 2, 4, p(f), p(y), 4, None, 0, 1.0, p(y), 2, s) == ERR_ARG
+    assert L.lmg_dense_gemv_windows(2, 2, 4, p(f), p(g), 4, p(y), 2, 1.0, p(y), 2, s) == ERR_ARG
+    assert L.lmg_dense_gemv_windows_off(2, 2, 4, p(f), p(y), p(ix), None, 0, 1.0, p(y), 2, s) == ERR_ARG
+    assert L.lmg_coarse_front(2, 4, p(f), p(y), p(ix), p(y), 0, None, s) == ERR_ARG
+    assert L.lmg_coarse_front_gather(2, 4, p(f), p(y), p(ix), p(y), 0, None, None, s) == ERR_ARG
+    assert L.lmg_coarse_back(2, 2, 4, p(f), p(y), p(ix), p(g), 2, 1.0, p(ix), p(y), 0, 2, s) == ERR_ARG
+    assert L.lmg_coarse_back(2, 2, 4, p(f), p(g), p(ix), p(y), 2, 1.0, p(ix), p(y), 0, 2, s) == ERR_ARG
+    assert L.lmg_coarse_back_gather(2, 2, 4, p(f), p(y), p(ix), p(g), 2, 1.0, p(ix), p(y), 0, 2, p(ix), s) == ERR_ARG
+    assert L.lmg_coarse_back_gather(2, 2, 4, p(f), p(g), p(ix), p(y), 2, 1.0, p(ix), p(y), 0, 2, p(ix), s) == ERR_ARG
+    # GEMM: a leading dimension below the row length, more batches than a grid has z-blocks
+    assert L.lmg_batched_gemm(1, 4, 4, 4, 1.0, p(f), 3, 0, p(g), 4, 0, 0.0, p(y), 4, 0, s) == ERR_ARG
+    assert L.lmg_batched_gemm(1, 4, 4, 4, 1.0, p(f), 4, 0, p(g), 3, 0, 0.0, p(y), 4, 0, s) == ERR_ARG
+    assert L.lmg_batched_gemm(1, 4, 4, 4, 1.0, p(f), 4, 0, p(g), 4, 0, 0.0, p(y), 3, 0, s) == ERR_ARG
+    assert L.lmg_copy2d(1, 4, 4, 1.0, p(f), 3, 0, p(y), 4, 0, 0, s) == ERR_ARG
+    assert untouched()
+    many = 65536
+    a1, b1, c1 = dev(np.ones(many)), dev(np.ones(many)), dev(nan(many))
+    assert L.lmg_batched_gemm(many, 1, 1, 1, 1.0, p(a1), 1, 1, p(b1), 1, 1, 0.0, p(c1), 1, 1, s) == ERR_ARG
+    assert L.lmg_copy2d(many, 1, 1, 1.0, p(a1), 1, 1, p(c1), 1, 1, 0, s) == ERR_ARG
+    assert bool(torch.isnan(c1).all())
+    # empty sizes: nothing to do, nothing written
+    assert L.lmg_dense_gemv_blockdiag(0, 4, p(f), p(g), p(y), s) == OK
+    assert L.lmg_dense_gemv_blockdiag(3, 0, p(f), p(g), p(y), s) == OK
+    assert L.lmg_dense_gemv_windows(0, 2, 4, p(f), p(g), 4, None, 0, 1.0, p(y), 2, s) == OK
+    assert L.lmg_dense_gemv_windows(3, 0, 4, p(f), p(g), 4, None, 0, 1.0, p(y), 2, s) == OK
+    assert L.lmg_dense_gemv_windows_off(0, 2, 4, p(f), p(g), p(ix), None, 0, 1.0, p(y), 2, s) == OK
+    assert L.lmg_coarse_front(0, 4, p(f), p(g), p(ix), p(y), 0, p(y[8:]), s) == OK
+    assert L.lmg_coarse_back(0, 2, 4, p(f), p(g), p(ix), p(g), 2, 1.0, p(ix), p(y), 0, 0, s) == OK
+    assert L.lmg_coarse_front_gather(0, 4, p(f), p(g), p(ix), p(y), 0, p(ix), p(y[8:]), s) == OK
+    assert L.lmg_coarse_back_gather(0, 2, 4, p(f), p(g), p(ix), p(g), 2, 1.0, p(ix), p(y), 0, 0, p(ix), s) == OK
+    assert L.lmg_batched_gemm(0, 4, 4, 4, 1.0, p(f), 4, 16, p(g), 4, 16, 0.0, p(y), 4, 16, s) == OK
+    assert L.lmg_batched_gemm(1, 0, 4, 4, 1.0, p(f), 4, 0, p(g), 4, 0, 0.0, p(y), 4, 0, s) == OK
+    assert L.lmg_batched_gemm(1, 4, 0, 4, 1.0, p(f), 4, 0, p(g), 4, 0, 0.0, p(y), 4, 0, s) == OK
+    assert L.lmg_copy2d(1, 0, 4, 1.0, p(f), 4, 0, p(y), 4, 0, 0, s) == OK
+    assert L.lmg_copy2d(1, 4, 0, 1.0, p(f), 4, 0, p(y), 4, 0, 0, s) == OK
+    assert L.lmg_block_copy(0, 4, p(f), 4, p(y), 4, s) == OK
+    assert L.lmg_block_copy(3, 0, p(f), 4, p(y), 4, s) == OK
+    cnt = dev(np.zeros(1024, dtype=np.int32))
+    assert L.lmg_pattern_parity_counts(0, 5, p(ix), p(cnt), s) == OK
+    assert L.lmg_csr_to_dense(0, 4, p(ix), p(ix), p(f), p(y), s) == OK
+    torch.cuda.synchronize()
+    assert untouched() and not bool(cnt.any())
+
+
+def test_gather_kernels_refuse_segments_beyond_their_lds():
+    """An operand segment of more than 60000 bytes does not fit: 7500 doubles are accepted, 7502 are not."""
+    L = _lib.lib()
+    fits, over = LDS_CAP_BYTES // 8, LDS_CAP_BYTES // 8 + 2
+    assert fits % 2 == 0 and fits * 8 <= LDS_CAP_BYTES < over * 8
+    p = lambda t: t.data_ptr()
+    rng = np.random.default_rng(15)
+    # back: 2 rows of `over` columns are small
+    c = back_gather_case("exact", 1, 2, over, 1, False)
+    t = {k: dev(v) for k, v in c.items() if isinstance(v, np.ndarray)}
+    s = ops._s(t["M"])
+    assert L.lmg_coarse_back_gather(1, 2, over, p(t["M"]), p(t["x"]), p(t["xidx"]), p(t["z"]), 2, c["alpha"], p(t["oidx"]),
+                                    p(t["before"]), 0, 1, p(t["tail_idx"]), s) == ERR_CAPACITY
+    assert bool(torch.isnan(t["before"]).all())
+    c = back_gather_case("exact", 1, 2, fits, 1, False)
+    expect_back_gather("exact", c).check(run_back_gather(ops, dev, c), fits)
+    # front: the block is square, 450 MB at this size -- allocated, never filled; the accepted call reads all of it
+    M = torch.empty(over * over, dtype=torch.float64, device=DEV)
+    b, y, tail = dev(data("exact", rng, over)), dev(nan(over)), dev(nan(2))
+    idx = dev(i32(rng.permutation(over)))
+    assert L.lmg_coarse_front_gather(1, over, p(M), p(b), p(idx), p(y), 2, p(idx), p(tail), s) == ERR_CAPACITY
+    assert bool(torch.isnan(y).all()) and bool(torch.isnan(tail).all())
+    assert L.lmg_coarse_front_gather(1, fits, p(M), p(b), p(idx[:fits]), p(y), 2, p(idx), p(tail), s) == OK
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(y[fits:]).all()) and torch.equal(tail, b[idx[:2].long()])
