@@ -334,7 +334,12 @@ int lmg_dia_cheby(int64_t n, int32_t line_stride, uint32_t union_mask, const dou
  * in the same order, so x_out has the bits of prolongation + separate sweeps.  h_hot_pairs (HOST, 2 ints,
  * may be NULL): for even / odd lines the ids (even column | odd column << 8) of the usual pattern pair,
  * with masks {0}, {0,1} / {0,2}, {0,1,2,3}, or -1; h_hot_pval (HOST, 9 doubles): their values in that
- * order.  5- and 9-point union masks (lmg_stencil_smooth_prolong_supported). */
+ * order.  5- and 9-point union masks (lmg_stencil_smooth_prolong_supported).
+ * PRECONDITION (this entry point and lmg_stencil_smooth_restrict, not their _tiled forms): no entry of the operator
+ * crosses the end of a line -- no pattern used in column 0 of a line has a slot of column - 1, none used in column
+ * line_stride - 1 a slot of column + 1 (x-periodic operators, a 7-point operator read with the stride of its other
+ * orientation).  A lane owns a coarse column here, so the elements beyond a line end, which only such an entry reads,
+ * get the correction of the wrong coarse nodes.  The caller checks (ops.py: StencilTwin.line_end_coupling). */
 int lmg_stencil_smooth_prolong_supported(uint32_t union_mask);
 int lmg_stencil_smooth_prolong(int64_t n, int32_t line_stride, const uint8_t *d_pid, int32_t npat,
                                const double *d_st_val, const int32_t *d_st_mask, uint32_t union_mask,
@@ -353,7 +358,8 @@ int lmg_stencil_smooth_prolong(int64_t n, int32_t line_stride, const uint8_t *d_
  * three lines stay in registers, and every coarse row is summed like lmg_rpat_sweep_grid(SPMV, alpha = 1,
  * beta = 0) would, so b_coarse has the bits of residual + restriction launches.  Every fine node (even line,
  * even column) must have its coarse row (LMG_ERR_ARG otherwise).  hot_r / h_hot_rval (HOST, 9 doubles): a
- * pattern with all nine slots, or -1 / NULL.  d_x_in == NULL: zero initial iterate, as in lmg_stencil_smooth. */
+ * pattern with all nine slots, or -1 / NULL.  d_x_in == NULL: zero initial iterate, as in lmg_stencil_smooth.
+ * Precondition: no entry of the operator across the end of a line (see lmg_stencil_smooth_prolong). */
 int lmg_stencil_smooth_restrict(int64_t n, int32_t line_stride, const uint8_t *d_pid, int32_t npat,
                                 const double *d_st_val, const int32_t *d_st_mask, uint32_t union_mask,
                                 int32_t hot_pattern, const double *h_hot_val, int sweeps, const double *d_x_in,

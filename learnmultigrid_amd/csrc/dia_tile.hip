@@ -67,7 +67,9 @@ __global__ void __launch_bounds__(RR / RB * LMG_WAVE) dia_tile_kernel(DArgs a)
     for (int k = 0; k < RB; ++k) {
         const int y = y0 + rb0 + k;
         const int64_t i = (int64_t)y * W + c0 + lane;
-        ok[k] = y >= 0 && y < a.lines && i >= 0 && i < n;
+        // validity is LINEAR, like the twin: (line -1, column W) is row 0 and (line `lines`, column -1) row n - 1, which an
+        // operator with an entry across a line end (x-periodic, sheared 7-point) reads from rows W - 1 and n - W
+        ok[k] = i >= 0 && i < n;
         const int64_t j = ok[k] ? i : 0;
         lx[k] = (!ZERO && ok[k]) ? a.x[j] : 0.0;
         bk[k] = ok[k] ? a.b[j] : 0.0;

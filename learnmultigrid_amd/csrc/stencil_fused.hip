@@ -358,9 +358,12 @@ __device__ __forceinline__ void fused_march(const MArgs &a, const Tables &T, con
             }
             return;
         }
-        const bool line_ok = y >= 0 && y < a.lines && y < y_end;             // wave-uniform, no branch on it
+        // An element is a row of the matrix where its LINEAR index is one, whatever its line: (line -1, column W) is row 0
+        // and (line `lines`, column -1) row n - 1, which an operator with an entry across a line end reads from rows W - 1
+        // and n - W.  (The coarse vectors of PROL / REST below are found by line and lane: they keep the clamped line.)
+        const bool line_ok = y < y_end;                                      // wave-uniform, no branch on it
         const int yc = min(max(y, 0), a.lines - 1);
-        const int64_t i = (int64_t)yc * W + c0 + cidx;
+        const int64_t i = (int64_t)y * W + c0 + cidx;
         const bool okA = line_ok && i >= 0 && i < n, okB = line_ok && i + 1 >= 0 && i + 1 < n;
         const int64_t j = min(max(i, (int64_t)0), (int64_t)n - 2);           // always a valid pair (n >= 2)
         L.ok = (okA ? 1 : 0) | (okB ? 2 : 0) | (i == -1 ? 4 : 0) | (i == (int64_t)n - 1 ? 8 : 0);

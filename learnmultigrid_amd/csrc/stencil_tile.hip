@@ -139,7 +139,9 @@ stencil_tile_kernel(TArgs a)
     for (int k = 0; k < RB; ++k) {
         const int y = y0 + rb0 + k;
         const int64_t i = (int64_t)y * W + c0 + lane;
-        const bool ok = y >= 0 && y < a.lines && i >= 0 && i < n;
+        // (linear validity: an element outside the lines 0 .. lines - 1 whose index is a row -- (-1, W) is row 0, (lines, -1)
+        // row n - 1 -- is that row, which operators with an entry across a line end read)
+        const bool ok = i >= 0 && i < n;
         const int64_t j = ok ? i : 0;
         lx[k] = (!ZERO && ok) ? a.x[j] : 0.0;
         bk[k] = ok ? a.b[j] : 0.0;

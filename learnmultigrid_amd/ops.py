@@ -98,6 +98,11 @@ class DeviceCSR:
         self.stencil, self.prolong, self.restrict = (
             T.from_patterns(self.patterns, self.shape) if _STENCIL_ENABLED else None
             for T in (StencilTwin, ProlongTwin, RestrictTwin))
+        S = self.stencil
+        if S is not None and S.n >= min(FUSED_TRANSFER_MIN_ROWS, REG_PROLONG_MIN_ROWS, REG_RESTRICT_MIN_ROWS):
+            # a level that may fold its transfers into the register pass: whether it has entries across a line end (two
+            # device -> host reads) is asked in every cycle -- decided now, never while a hipGraph is being captured
+            S.line_end_coupling
 
     def invalidate_packed(self):
         self.packed = self.patterns = self.sell = self.stencil = self.prolong = self.restrict = self.dia = None
@@ -310,8 +315,13 @@ def _run_pass(stem, kind, A, head, x_in, r_out, prolong, restrict):
             raise LmgError("%s: this %s cannot be fused into the pass" % (who, what))
         # Jacobi only: a level on the tiled passes may take the register pass for this launch (A/B knobs)
         reg_min = REG_RESTRICT_MIN_ROWS if form == "restrict" else REG_PROLONG_MIN_ROWS
-        if stem == "smooth" and S.n >= reg_min and _lib.lib().lmg_stencil_smooth_prolong_supported(S.umask):
+        if (stem == "smooth" and S.n >= reg_min and _lib.lib().lmg_stencil_smooth_prolong_supported(S.umask)
+                and not S.line_end_coupling):
             tiled = False
+        if not tiled and S.line_end_coupling:
+            # (the register pass finds the coarse window of an element by its lane: wrong for the elements beyond a line end,
+            # which only such an operator reads -- include/lmg.h; the tiled pass finds it by the element's own line and column)
+            raise LmgError("%s: the register pass folds no transfer into an operator with entries across a line end" % who)
         tail = T.c_args(vec)
     name = "lmg_stencil_%s%s%s" % (stem, "_tiled" if tiled else "", "_" + form if form else "")
     check(getattr(_lib.lib(), name)(*S.c_args(), *head, *tail, _s(S.pid)), name)
@@ -349,7 +359,8 @@ def _prolong_available(A, P, kind):
     if kind == "tile":                   # the tile is loaded as x + P e: always cheaper than the P launch it replaces
         return True
     S = A.stencil
-    return bool(S.n >= FUSED_TRANSFER_MIN_ROWS and _lib.lib().lmg_stencil_smooth_prolong_supported(S.umask))
+    return bool(S.n >= FUSED_TRANSFER_MIN_ROWS and _lib.lib().lmg_stencil_smooth_prolong_supported(S.umask)
+                and not S.line_end_coupling)
 
 
 def stencil_smooth_prolong_available(A, P):
@@ -377,7 +388,8 @@ def _restrict_available(A, R, kind):
     if not (_FUSED_RESTRICT_ENABLED and kind in ("reg", "tile") and T is not None):
         return False
     S = A.stencil
-    if kind == "reg" and not (S.n >= FUSED_TRANSFER_MIN_ROWS and _lib.lib().lmg_stencil_smooth_prolong_supported(S.umask)):
+    if kind == "reg" and not (S.n >= FUSED_TRANSFER_MIN_ROWS and _lib.lib().lmg_stencil_smooth_prolong_supported(S.umask)
+                              and not S.line_end_coupling):
         return False
     if kind == "tile" and S.n > TILED_RESTRICT_MAX_ROWS:
         return False

@@ -479,7 +479,7 @@ class StencilTwin:
     from_patterns returns None for everything that does not fit (the RPAT kernel then runs)."""
 
     __slots__ = ("n", "W", "npat", "pid", "st_val", "st_mask", "umask", "bytes_", "patterns", "hot", "_hot_val",
-                 "_gs_ok", "_gs_work")
+                 "_gs_ok", "_gs_work", "_line_end")
     _decompose = staticmethod(_decompose)
 
     @classmethod
@@ -511,6 +511,7 @@ class StencilTwin:
         # wavefront Gauss-Seidel (lmg_stencil_gs_sweep): see gs_ok below (decided on first use)
         self._gs_work = None
         self._gs_ok = None
+        self._line_end = None
         return self
 
     def sweep_args(self):
@@ -532,14 +533,23 @@ class StencilTwin:
         faster there: 0.29 vs 0.5 us per row)"""
         if self._gs_ok is None:
             ok = bool(_lib.lib().lmg_stencil_gs_supported(self.umask)) and self.n >= 2 and bool(self.umask & 0x1C7)
-            if ok:
-                mk = self.st_mask.cpu().numpy()
-                W = self.W
-                first = mk[self.pid[0::W].cpu().numpy()]
-                last = mk[self.pid[W - 1::W].cpu().numpy()]
-                ok = not bool(((first & 0x49) != 0).any()) and not bool(((last & 0x124) != 0).any())
-            self._gs_ok = ok
+            self._gs_ok = ok and not self.line_end_coupling
         return self._gs_ok
+
+    @property
+    def line_end_coupling(self):
+        """Whether an entry crosses the end of a line: a row in column 0 with a slot of column - 1 (0, 3, 6), or a row in
+        column W - 1 with a slot of column + 1 (2, 5, 8) -- x-periodic operators, 7-point operators read with the stride of
+        their other orientation.  The sweeps and the plain fused passes are linear in the row index and take such an
+        operator; what finds a neighbour by grid line does not (gs_ok; the transfers folded into the register pass, whose
+        lanes own coarse columns).  Decided on first use, for the reason given at gs_ok."""
+        if self._line_end is None:
+            mk = self.st_mask.cpu().numpy()
+            W = self.W
+            first = mk[self.pid[0::W].cpu().numpy()]
+            last = mk[self.pid[W - 1::W].cpu().numpy()]
+            self._line_end = bool(((first & 0x49) != 0).any()) or bool(((last & 0x124) != 0).any())
+        return self._line_end
 
     def bytes(self):
         return int(self.bytes_)

@@ -92,7 +92,10 @@ def stencil_by_twin(A):
     assert S.st_val.dtype == torch.float64 and S.st_mask.dtype == torch.int32
     mask = S.st_mask.numpy()
     assert S.umask == np.bitwise_or.reduce(mask)
-    assert list(S._hot_val) == list(S.st_val.numpy()[S.hot * 9: S.hot * 9 + 9])
+    if S.hot < 0:                          # no pattern has every union slot (x-periodic 5-point: interior and wrap-around rows)
+        assert S.hot == -1 and S._hot_val is None
+    else:
+        assert list(S._hot_val) == list(S.st_val.numpy()[S.hot * 9: S.hot * 9 + 9])
     assert S.c_args()[:2] + S.c_args()[6:8] == (S.n, S.W, S.umask, S.hot)
     return S.W, S.st_val.numpy(), mask, R.pid.numpy(), S.hot
 
@@ -154,6 +157,59 @@ def test_stencil_refusals(name, stencil_of):
 
 def test_shortest_line(stencil_of):
     assert stencil_of(banded(3, [-1, 0, 1], [-1.0, 2.0, -1.0]))[0] == 3
+
+
+# ---- operators with live boundary rows (tests/grid_ops.py): entries across the end of a line ----------------------------
+def line_end_cases():
+    """name -> (A, W, union mask, crosses a line end): small versions of the operators of test_grid_shapes_gpu.py."""
+    import grid_ops as G
+    return {
+        # x-periodic 5-point: the wrap-around links are the slots 2 and 6 of the grid's own stride
+        "periodic5": (G.grid_op(7, 6, 0x0BA, "const", periodic_x=True), 7, 0x0FE, True),
+        "periodic9": (G.grid_op(7, 6, 0x1FF, "const", periodic_x=True), 7, 0x1FF, True),
+        # 7-point on 4 x 5: 5 is looked at first and divides the 20 rows -- the sheared stride, the other orientation
+        "sheared7_4x5": (G.grid_op(4, 5, 0x1BB, "const"), 5, 0x0FE, True),
+        # the mirror, 5 x 4: 6 does not divide 20, the grid's own stride does
+        "plain7_5x4": (G.grid_op(5, 4, 0x1BB, "const"), 5, 0x1BB, False),
+        # the other orientation never shears on a whole rectangle: its own stride is looked at first and divides
+        "plain7b_7x6": (G.grid_op(7, 6, 0x0FE, "const"), 7, 0x0FE, False),
+        # live boundary rows alone cross nothing
+        "plain9_7x6": (G.grid_op(7, 6, 0x1FF, "const"), 7, 0x1FF, False),
+        "ragged5": (G.grid_op(7, 6, 0x0BA, "const", rows=37), 7, 0x0BA, False),
+    }
+
+
+@pytest.mark.parametrize("name", sorted(line_end_cases()))
+def test_operators_with_live_boundary_rows_are_linear(name, stencil_of):
+    """The twins read an operator by linear offsets only: an x-periodic or sheared one decodes like any other and the
+    decoded table IS the matrix; whether an entry then crosses a line end is a property the twin reports, not a refusal."""
+    import grid_ops as G
+    A, W, umask, crosses = line_end_cases()[name]
+    got_W, values, mask, pid, _hot = stencil_of(A)
+    assert got_W == W and np.bitwise_or.reduce(mask) == umask
+    assert_rebuilds(A, pid, values, mask, window_3x3(W))
+    assert (G.line_end_coupling(A, W).size > 0) == crosses
+    if stencil_of is stencil_by_twin:
+        S = ops.StencilTwin.from_patterns(record(A), A.shape)
+        assert S.line_end_coupling is crosses
+        if crosses:
+            assert not S.gs_ok
+
+
+def test_generated_operators_keep_their_boundary_couplings():
+    import grid_ops as G
+    for slots, per_row in ((0x0BA, 5), (0x1BB, 7), (0x0FE, 7), (0x1FF, 9)):
+        for values in ("const", "row"):
+            A = G.grid_op(9, 8, slots, values)
+            assert A.has_sorted_indices and A.indices.dtype == np.int32 and A.shape == (72, 72)
+            lens = np.diff(A.indptr)
+            assert lens.max() == per_row and lens.min() >= 3 and lens[4 * 9 + 4] == per_row     # no identity rows
+            d = A.diagonal()
+            assert np.all(d > abs(A).sum(axis=1).A1 - d) and np.all(np.abs(A.data) >= 0.5)
+            B = G.grid_op(9, 8, slots, values, rows=60)
+            assert B.shape == (60, 60) and (B != A[:60, :60]).nnz == 0
+    A = G.grid_op(9, 8, 0x0BA, "const", periodic_x=True)
+    assert A[8, 0] != 0 and A[0, 8] != 0 and A[71, 63] != 0 and np.diff(A.indptr).min() == 4
 
 
 def test_decoder_refusals():
