@@ -431,6 +431,27 @@ int lmg_cheby_update(int64_t n, double a, double c, int first, const double *d_d
 int lmg_csr_gershgorin(int64_t n, const int32_t *d_rowptr, const int32_t *d_colidx, const double *d_vals, double *d_lmax,
                        void *stream);
 
+/* ---- line relaxation: the tridiagonal systems of the grid lines (csrc/line.hip) -----------------------------------------
+ * A level of n rows with line stride W (n % line_stride == 0, LMG_ERR_ARG otherwise) has H = n / W lines.  dir 0 ("x"):
+ * one system per storage line, rows k W .. k W + W - 1, its matrix T the entries of A at column - row in {-1, 0, +1};
+ * dir 1 ("y"): one system per grid column k, rows k, k + W, k + 2 W, ..., the entries at column - row in {-W, 0, +W}.  A
+ * missing entry is 0.  Lane <-> system in both kernels; products and sums round separately.
+ *   lmg_line_factor  reads the tridiagonal part from the sorted, duplicate-free CSR and factors every system once: along
+ *                    a system j = 0 .. L - 1 with sub-, main and super-diagonal lo_j, a_j, up_j,
+ *                        den_0 = a_0,  den_j = a_j - lo_j * cp_(j-1),  minv_j = 1.0 / den_j,  cp_j = up_j * minv_j;
+ *                    writes the three n-vectors d_lo, d_minv, d_cp (indexed by row; distinct), and ORs into *d_flags
+ *                    (zeroed by the caller): bit 0 if, for dir 0, a stored non-zero entry couples two lines -- (i, i + 1)
+ *                    with (i + 1) % W == 0, or (i + 1, i) --, bit 1 if a pivot den_j is zero or not finite.
+ *   lmg_line_solve   x <- x + omega * T^-1 r on the systems first, first + step, ... (zebra: (0, 2) then (1, 2); all:
+ *                    (0, 1)); every other row of d_x and d_r keeps its bits.  Forward  d_0 = r_0 * minv_0,
+ *                    d_j = (r_j - lo_j * d_(j-1)) * minv_j  overwrites d_r; backward  e_(L-1) = d_(L-1),
+ *                    e_j = d_j - cp_j * e_(j+1),  x_i = x_i + omega * e_j  updates d_x in place (the residual is formed
+ *                    before the launch: no hazard).  No division, no scratch.  first < 0 or step < 1: LMG_ERR_ARG. */
+int lmg_line_factor(int64_t n, int32_t line_stride, int dir, const int32_t *d_rowptr, const int32_t *d_colidx,
+                    const double *d_vals, double *d_lo, double *d_minv, double *d_cp, int32_t *d_flags, void *stream);
+int lmg_line_solve(int64_t n, int32_t line_stride, int dir, int64_t first, int64_t step, const double *d_lo,
+                   const double *d_minv, const double *d_cp, double *d_r, double omega, double *d_x, void *stream);
+
 /* CSR transpose by counting sort (setup: the restriction R = P^T as an explicit CSR, `i.T` of
  * Multigrid.py:93).  lmg_csr_transpose_count: d_counts[c] (zeroed by the caller, ncols entries) += number of
  * entries in column c; the caller scans d_counts into d_t_rowptr with lmg_exclusive_scan_i32;

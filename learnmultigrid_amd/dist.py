@@ -197,6 +197,9 @@ def _check_smoother(smoother):
     if smoother == "Chebyshev":
         raise ValueError("the distributed V-cycle does not run the Chebyshev smoother (single-GPU hierarchies only); "
                          "use 'Jacobi' or 'GaussSeidel'")
+    if smoother == "Line":
+        raise ValueError("the distributed V-cycle does not run the Line smoother (single-GPU hierarchies only: a grid line "
+                         "would cross the row blocks); use 'Jacobi' or 'GaussSeidel'")
     if smoother not in ("Jacobi", "GaussSeidel"):
         raise ValueError("the distributed V-cycle supports the smoothers 'Jacobi' and 'GaussSeidel' "
                          "(processor-block Gauss-Seidel), not %r" % (smoother,))

@@ -23,6 +23,7 @@ import torch
 from . import ops
 from .coarse import make_coarse_solver
 from .ops import DeviceCSR, F64
+from .twins import DiaTwin, line_stride
 
 
 GS_SWEEPS = ("forward", "backward", "symmetric")       # pyamg's gauss_seidel(sweep=...)
@@ -79,6 +80,32 @@ CHEBY_TWIN = {"stencil_smooth_available": "stencil_cheby_available",
 CHEBY_RATIO = 4.0       # lambda_max / lambda_min: the oscillatory modes of D^-1 A under full coarsening in two dimensions
 
 
+LINE_DIRS = ("x", "y", "xy")          # the line_dir of the "Line" smoother: the systems one step solves, in this order
+LINE_ORDERS = ("zebra", "jacobi")     # its line_order: even systems then odd ones with a fresh residual, or all from one
+
+
+def line_config(line_dir=None, line_order=None):
+    """(line_dir, line_order) with the defaults ("xy", "zebra") filled in, or a ValueError (reads no state: the solver
+    classes check their keywords with it before any setup)."""
+    line_dir = "xy" if line_dir is None else line_dir
+    line_order = "zebra" if line_order is None else line_order
+    if line_dir not in LINE_DIRS:
+        raise ValueError("line_dir must be one of %s, got %r" % (LINE_DIRS, line_dir))
+    if line_order not in LINE_ORDERS:
+        raise ValueError("line_order must be one of %s, got %r" % (LINE_ORDERS, line_order))
+    return line_dir, line_order
+
+
+def line_half_steps(line_dir, line_order, reverse=False):
+    """The launches of one "Line" smoothing step as (direction, first, step) of ops.line_solve, each after a fresh residual:
+    per direction of line_dir the even systems then the odd ones (zebra) or all systems (jacobi).  reverse: the
+    post-smoothing half -- directions and colours in the opposite order, which makes the cycle's smoothing halves adjoint
+    to each other whenever A is symmetric."""
+    colours = ((0, 2), (1, 2)) if line_order == "zebra" else ((0, 1),)
+    out = [(d, first, step) for d in line_dir for (first, step) in colours]
+    return out[::-1] if reverse else out
+
+
 def _directions(sweep):
     return ("forward", "backward") if sweep == "symmetric" else (sweep,)
 
@@ -95,7 +122,7 @@ def _to_csr_host(M):
 
 class Level:
     __slots__ = ("n", "A", "P", "R", "x", "b", "r", "tmp", "plan_RA", "plan_RAP", "RA",
-                 "gs_sched", "host_pattern", "dinv", "M", "plan_RM", "plan_RMP", "RM", "d")
+                 "gs_sched", "host_pattern", "dinv", "M", "plan_RM", "plan_RMP", "RM", "d", "line")
 
     def __init__(self, A):
         self.n = A.shape[0]
@@ -111,6 +138,7 @@ class Level:
         self.host_pattern = None
         self.dinv = None
         self.d = None                  # Chebyshev smoother: the step vector of the two-launch path (prepare_smoother)
+        self.line = None               # "Line" smoother: {"W": line stride, "x" / "y": factor triple} (prepare_smoother)
         self.M = None                  # mass matrix of the level (optional, see Hierarchy(mass=...))
         self.plan_RM = self.plan_RMP = self.RM = None
 
@@ -180,6 +208,7 @@ class Hierarchy:
         self._factor_coarsest()
         self._graphs = {}
         self._cheby = None             # Chebyshev smoother: bounds and coefficient tables (prepare_smoother)
+        self._line = None              # "Line" smoother: the (line_dir, line_order) in use (prepare_smoother)
 
     # ------------------------------------------------------------------ setup ----------
     @property
@@ -262,6 +291,63 @@ class Hierarchy:
             lmax_arg, ratio = self._cheby["args"]
             self._cheby = None
             self._prepare_chebyshev(lmax_arg, ratio)
+        if self._line is not None:                   # new values: new factors, for every direction that had them
+            had = [sorted(k for k in (lev.line or ()) if k != "W") for lev in self.levels[:-1]]
+            for lev in self.levels[:-1]:
+                lev.line = None
+            for dirs in sorted({d for h in had for d in h}):
+                self._factor_lines(dirs)
+
+    # ------------------------------------------------------------------ line relaxation --
+    def _line_stride(self, l):
+        """The line stride of level l: that of its grid twin, or -- small levels only, whose twins are never built -- the one
+        its offsets fit on the host (twins.line_stride).  None: no 3x3 grid geometry."""
+        lev = self.levels[l]
+        for twin in (getattr(lev.A, "stencil", None), getattr(lev.A, "dia", None)):
+            if twin is not None:
+                return int(twin.W)
+        if lev.n >= DiaTwin.MIN_ROWS:
+            return None
+        if lev.host_pattern is None:
+            lev.host_pattern = (lev.A.rowptr.cpu().numpy(), lev.A.colidx.cpu().numpy())
+        rp, ci = lev.host_pattern
+        rows = np.repeat(np.arange(lev.n, dtype=np.int64), np.diff(rp))
+        W = line_stride(np.unique(ci.astype(np.int64) - rows), lev.n)
+        return None if W is None else int(W)
+
+    def _factor_lines(self, dirs):
+        """The factors of every smoothed level for the directions `dirs` that it does not have yet (one flag read each)."""
+        for l, lev in enumerate(self.levels[:-1]):
+            if lev.line is None:
+                W = self._line_stride(l)
+                if W is None:
+                    raise ValueError("the Line smoother cannot run on level %d (%d rows): no 3x3 grid geometry" % (l, lev.n))
+                if lev.n % W != 0:
+                    raise ValueError("the Line smoother cannot run on level %d: its %d rows are no whole lines of %d "
+                                     "(n %% W != 0)" % (l, lev.n, W))
+                if W == lev.n:
+                    raise ValueError("the Line smoother cannot run on level %d: one line of %d rows (W == n, a 1-D operator)"
+                                     % (l, lev.n))
+                lev.line = {"W": W}
+            for d in dirs:
+                if d not in lev.line:
+                    try:
+                        lev.line[d] = self.ops.line_factor(lev.A, lev.line["W"], d)
+                    except ValueError as e:
+                        raise ValueError("the Line smoother cannot run on level %d (%d rows, line stride %d): %s"
+                                         % (l, lev.n, lev.line["W"], e)) from None
+
+    def _prepare_line(self, line_dir=None, line_order=None):
+        """Both None: keep what is prepared (the defaults when nothing is)."""
+        if self._line is not None and line_dir is None and line_order is None:
+            return
+        cfg = line_config(line_dir, line_order)
+        self._factor_lines(cfg[0])
+        self._line = cfg
+
+    def line_key(self):
+        """What a captured Line cycle depends on besides the cycle's own arguments: (line_dir, line_order) in use."""
+        return self._line
 
     # ------------------------------------------------------------------ Chebyshev ------
     def _prepare_chebyshev(self, cheby_lmax=None, cheby_ratio=None):
@@ -385,6 +471,24 @@ class Hierarchy:
                 else:
                     self.ops.csr_residual_norm2(lev.A, lev.x, lev.b, lev.r, None, None)
                     self.ops.cheby_update(a, c, lev.dinv, lev.r, lev.d, lev.x, first=(k == 0))
+        elif smoother == "Line":
+            # per half-step: r = b - A x, then x += omega T^-1 r on its systems, in place (direction "backward": the
+            # post-smoothing half, directions and colours reversed)
+            if self._line is None or lev.line is None:
+                raise RuntimeError("Line smoother used before prepare_smoother")
+            if direction not in ("forward", "backward"):
+                raise ValueError("the Line smoother runs 'forward' (pre-smoothing) or 'backward' (post-smoothing), got %r"
+                                 % (direction,))
+            if x_is_zero:
+                self.ops.zero(lev.x)
+            for _ in range(steps):
+                for d, first, step in line_half_steps(*self._line, reverse=(direction == "backward")):
+                    if x_is_zero:
+                        self.ops.copy(lev.b, lev.r)                                  # b - A 0 = b
+                        x_is_zero = False
+                    else:
+                        self.ops.csr_residual_norm2(lev.A, lev.x, lev.b, lev.r, None, None)
+                    self.ops.line_solve(lev.line["W"], d, first, step, lev.line[d], lev.r, omega, lev.x)
         else:
             raise ValueError("unknown smoother %r" % (smoother,))
 
@@ -464,7 +568,7 @@ class Hierarchy:
 
     def cycle(self, smoother, steps, omega=1.0, gs_mode="lexicographic", l=0, depth=None,
               after_presmooth=None, x_is_zero=False, gs_sweep=("forward", "forward"), shape="V", *,
-              cheby_lmax=None, cheby_ratio=None):
+              cheby_lmax=None, cheby_ratio=None, line_dir=None, line_order=None):
         """One V(steps, steps) cycle on level l: levels[l].x is the iterate, levels[l].b the
         right-hand side (Multigrid.py:77-124).  depth = number of grids used.
         gs_sweep: directions of the Gauss-Seidel pre- and post-smoothing, a pyamg sweep name for both or a (pre, post)
@@ -478,14 +582,21 @@ class Hierarchy:
         the pre-smoothing of the next run as one turnaround pass (ops.stencil_smooth_turnaround).
         smoother "Chebyshev": `steps` is the DEGREE of the one polynomial smoothing step run before and after the coarse
         correction, on [lmax / cheby_ratio, lmax] of D^-1 A per level (omega is not used).  cheby_lmax / cheby_ratio as in
-        prepare_smoother; left None they are what was prepared (the Gershgorin bounds and CHEBY_RATIO by default)."""
+        prepare_smoother; left None they are what was prepared (the Gershgorin bounds and CHEBY_RATIO by default).
+        smoother "Line": `steps` line relaxation steps with damping omega on either side -- line_dir "x" | "y" | "xy",
+        line_order "zebra" | "jacobi" as in prepare_smoother, left None what was prepared ("xy", "zebra" by default); the
+        post-smoothing half runs the directions and colours in reverse (gs_sweep is not used)."""
         children = cycle_children(shape)
         if smoother == "Chebyshev":
             if steps < 1:
                 raise ValueError("the Chebyshev smoother needs smooth_steps >= 1 (the degree), got %r" % (steps,))
             self._prepare_chebyshev(cheby_lmax, cheby_ratio)
+        pair = gs_sweep_pair(gs_sweep)
+        if smoother == "Line":
+            self._prepare_line(line_dir, line_order)
+            pair = ("forward", "backward")
         self._visit(smoother, steps, omega, gs_mode, l, (len(self.levels) if depth is None else depth) - 1, children,
-                    gs_sweep_pair(gs_sweep), x_is_zero, after_presmooth)
+                    pair, x_is_zero, after_presmooth)
 
     def _visit(self, smoother, steps, omega, gs_mode, l, last, children, pair, x_is_zero=False, after_presmooth=None,
                entered=False, leave_open=False):
@@ -574,16 +685,24 @@ class Hierarchy:
             self._ask("stencil_gs_check", lev.A)
 
     def prepare_smoother(self, smoother, gs_mode="lexicographic", l_from=0, gs_sweep=("forward", "forward"), *,
-                         cheby_lmax=None, cheby_ratio=None):
+                         cheby_lmax=None, cheby_ratio=None, line_dir=None, line_order=None):
         """Everything a Gauss-Seidel cycle would otherwise do lazily on its first sweep -- the wavefront kernel's eligibility
         test (a device -> host read) and work buffer, the level schedules -- from level l_from down, for every direction
         gs_sweep uses: nothing of it may happen while a hipGraph is being captured.
         Chebyshev: the bound lmax of D^-1 A per level -- cheby_lmax: None = its Gershgorin bound max_i sum_j |a_ij| / |a_ii|
         (never below the true lambda_max: no safety factor, the step cannot diverge), a float, or one value per smoothed
         level -- and lambda_min = lmax / cheby_ratio (default CHEBY_RATIO); the coefficient tables follow from them on the
-        host.  rebuild_numeric() renews both."""
+        host.  rebuild_numeric() renews both.
+        Line: the factored tridiagonal systems of every smoothed level for the directions of line_dir ("x" | "y" | "xy",
+        default "xy") -- per level and direction two launches and one flag read --, and line_order ("zebra" | "jacobi",
+        default "zebra").  A level that cannot run it raises a ValueError that names the level and the reason: no 3x3 grid
+        geometry, rows that are no whole lines, a single line, an entry that couples two x-lines, a zero pivot.
+        rebuild_numeric() renews the factors."""
         if smoother == "Chebyshev":
             self._prepare_chebyshev(cheby_lmax, cheby_ratio)
+            return
+        if smoother == "Line":
+            self._prepare_line(line_dir, line_order)
             return
         if smoother != "GaussSeidel":
             return
@@ -598,14 +717,17 @@ class Hierarchy:
                     self.gs_schedule(l, gs_mode, d)
 
     def captured_cycle(self, smoother, steps, omega, gs_mode, gs_sweep=("forward", "forward"), shape="V", *,
-                       cheby_lmax=None, cheby_ratio=None):
+                       cheby_lmax=None, cheby_ratio=None, line_dir=None, line_order=None):
         """The same launch sequence as cycle(), captured once into a hipGraph and replayed (one graph per sweep pair and
         cycle shape)."""
         pair = gs_sweep_pair(gs_sweep)
         cycle_children(shape)
         if smoother == "Chebyshev":                 # (before the key: the bounds in use are part of it)
             self.prepare_smoother(smoother, cheby_lmax=cheby_lmax, cheby_ratio=cheby_ratio)
+        if smoother == "Line":                      # (the factors: flag reads, never inside the capture)
+            self.prepare_smoother(smoother, line_dir=line_dir, line_order=line_order)
         key = (smoother, steps, omega, gs_mode, pair, shape) + ((self.cheby_key(),) if smoother == "Chebyshev" else ())
+        key += (self.line_key(),) if smoother == "Line" else ()
         g = self._graphs.get(key)
         if g is None:
             self.prepare_smoother(smoother, gs_mode, gs_sweep=pair)
@@ -628,6 +750,7 @@ class Hierarchy:
         tot = 0
         for lev in self.levels:
             tot += lev.A.bytes() + (4 + (lev.d is not None)) * 8 * lev.n
+            tot += 0 if lev.line is None else 24 * lev.n * (len(lev.line) - 1)
             for M in (lev.P, lev.R, lev.RA):
                 if M is not None:
                     tot += M.bytes()

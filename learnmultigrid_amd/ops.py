@@ -519,6 +519,52 @@ def csr_gershgorin(A, out):
           "lmg_csr_gershgorin")
 
 
+# ---- line relaxation (csrc/line.hip) -------------------------------------------------------------------------------------
+LINE_DIRS = {"x": 0, "y": 1}        # the `dir` of lmg_line_factor / lmg_line_solve
+LINE_COUPLED, LINE_PIVOT = 1, 2     # the bits of their flag word
+
+
+def line_factor_flags(A, W, dir):
+    """((lo, minv, cp), flags): the factored tridiagonal systems of the grid lines of A in direction "x" | "y" for line
+    stride W (lmg_line_factor: two launches, setup) and its flag word -- LINE_COUPLED: a non-zero entry couples two x-lines,
+    LINE_PIVOT: a zero or non-finite pivot.  One 4-byte device -> host read: never while a hipGraph is being captured."""
+    if dir not in LINE_DIRS:
+        raise ValueError("line direction must be 'x' or 'y', got %r" % (dir,))
+    n = A.shape[0]
+    if A.shape[0] != A.shape[1] or int(W) < 1 or n % int(W) != 0:
+        raise ValueError("line relaxation needs a square operator whose %d rows are whole lines of %r" % (n, W))
+    dev = A.vals.device
+    lo, minv, cp = (torch.empty(n, dtype=F64, device=dev) for _ in range(3))
+    flags = torch.zeros(1, dtype=I32, device=dev)
+    check(_lib.lib().lmg_line_factor(n, int(W), LINE_DIRS[dir], _p(A.rowptr), _p(A.colidx), _p(A.vals), _p(lo), _p(minv),
+                                     _p(cp), _p(flags), _s(A.rowptr)), "lmg_line_factor")
+    return (lo, minv, cp), int(flags.item())
+
+
+def line_factor(A, W, dir):
+    """The factor triple (lo, minv, cp) of line_factor_flags, or a ValueError that says which flag was set."""
+    fac, flags = line_factor_flags(A, W, dir)
+    if flags & LINE_COUPLED:
+        raise ValueError("a non-zero entry couples two x-lines (an entry across the end of a line)")
+    if flags & LINE_PIVOT:
+        raise ValueError("a zero or non-finite pivot in the %s-line systems" % dir)
+    return fac
+
+
+def line_solve(W, dir, first, step, fac, r, omega, x):
+    """x += omega * T^-1 r on the systems first, first + step, ... of direction dir; r (the residual, formed before the
+    call) is overwritten on those systems, every other row of x and r keeps its bits (lmg_line_solve)."""
+    lo, minv, cp = fac
+    _vec_ok(lo, minv, cp, r, x)
+    n = x.numel()
+    if any(t.numel() != n for t in (lo, minv, cp, r)):
+        raise ValueError("line_solve: the factors, r and x must have one entry per row")
+    if dir not in LINE_DIRS:
+        raise ValueError("line direction must be 'x' or 'y', got %r" % (dir,))
+    check(_lib.lib().lmg_line_solve(n, int(W), LINE_DIRS[dir], int(first), int(step), _p(lo), _p(minv), _p(cp), _p(r),
+                                    float(omega), _p(x), _s(x)), "lmg_line_solve")
+
+
 def _use_stencil(A, *vecs):
     if not (_PACKED_ENABLED and _STENCIL_ENABLED and A.stencil is not None):
         return False
@@ -1185,6 +1231,17 @@ def register_torch_ops():
     lib.define("operator_gauss_seidel_(int handle, Tensor(a!) x, Tensor b, int sweeps) -> ()")
     lib.define("operator_gauss_seidel_backward_(int handle, Tensor(a!) x, Tensor b, int sweeps) -> ()")
 
+    lib.define("line_factor(Tensor rowptr, Tensor colidx, Tensor vals, int line_stride, str dir) -> (Tensor, Tensor, Tensor, int)")
+    lib.define("line_solve(int line_stride, str dir, int first, int step, Tensor lo, Tensor minv, Tensor cp, Tensor(a!) r, "
+               "float omega, Tensor(b!) x) -> ()")
+
+    def op_line_factor(rowptr, colidx, vals, line_stride, dir):
+        (lo, minv, cp), flags = line_factor_flags(_csr(rowptr, colidx, vals, rowptr.numel() - 1), line_stride, dir)
+        return lo, minv, cp, flags
+
+    def op_line_solve(line_stride, dir, first, step, lo, minv, cp, r, omega, x):
+        line_solve(line_stride, dir, first, step, (lo, minv, cp), r, omega, x)
+
     def op_spgemm(arp, aci, ava, acols, brp, bci, bva, bcols):
         C = spgemm(_csr(arp, aci, ava, acols), _csr(brp, bci, bva, bcols))
         return C.rowptr, C.colidx, C.vals
@@ -1329,6 +1386,8 @@ def register_torch_ops():
     lib.impl("operator_gershgorin", op_h_gershgorin, "CompositeExplicitAutograd")
     lib.impl("cheby_update_", op_cheby_update_, "CUDA")
     lib.impl("csr_gershgorin", op_gershgorin, "CUDA")
+    lib.impl("line_factor", op_line_factor, "CUDA")
+    lib.impl("line_solve", op_line_solve, "CUDA")
     lib.impl("operator_gauss_seidel_", op_h_gs_, "CUDA")
     lib.impl("operator_gauss_seidel_backward_", op_h_gs_backward_, "CUDA")
     register_torch_ops._lib = lib        # keep alive

@@ -108,6 +108,23 @@ def poisson_2d_structured(m, dirichlet=True):
     return A, rhs
 
 
+def anisotropic_poisson_2d_structured(m, ax, ay):
+    """The 5-point operator of -(ax u_xx + ay u_yy) on the (m+1)^2 grid, scaled by h^2, in the layout of
+    poisson_2d_structured: interior rows [-ay, -ax, 2 ax + 2 ay, -ax, -ay] at columns k-(m+1), k-1, k, k+1, k+(m+1),
+    identity boundary rows (columns untouched), rhs 1/m^2 inside and 0 on the boundary.  ax << ay (or the reverse) is the
+    model problem of line relaxation: point smoothers leave the error along the weak direction."""
+    A, _ = poisson_2d_structured(m)
+    s = m + 1
+    ax, ay = float(ax), float(ay)
+    interior = np.flatnonzero(np.diff(A.indptr) == 5)
+    p = A.indptr[interior].astype(np.int64)
+    for off, v in enumerate((-ay, -ax, 2 * ax + 2 * ay, -ax, -ay)):
+        A.data[p + off] = v
+    rhs = np.zeros((s * s, 1))
+    rhs[interior, 0] = 1.0 / (m * m)
+    return A, rhs
+
+
 def tensor_interpolator_2d(s):
     """Build-defined 2-D geometric transfer: tensor product of the reference's 1-D
     interpolator with itself on an s x s row-major grid -> ((s*s), (sc*sc)) CSR."""

@@ -14,13 +14,18 @@ precond_cycle_shape="W" applies one W-cycle instead (Hierarchy.cycle); it is as 
 is not (its second visits are V-cycles: the F-cycle's adjoint would run them first) and is rejected.
 precond_smoother="Chebyshev" smooths with one Chebyshev polynomial step of degree precond_steps on either side: a polynomial
 in D^-1 A applied to D^-1 is a symmetric operator, so the cycle is one too -- as parallel as the Jacobi cycle, no damping
-parameter (precond_omega is not used; bounds as prepared on the hierarchy, Hierarchy.prepare_smoother)."""
+parameter (precond_omega is not used; bounds as prepared on the hierarchy, Hierarchy.prepare_smoother).
+precond_smoother="Line" smooths with precond_steps line relaxation steps (precond_line_dir "x" | "y" | "xy",
+precond_line_order "zebra" | "jacobi", damping precond_omega: pass 1.0 for zebra) on either side; the post-smoothing half
+runs the directions and colours in reverse, the adjoint of the pre-smoothing half, so the cycle is a symmetric operator --
+the preconditioner for operators with a strong direction."""
 import math
 
 import numpy as np
 import torch
 
 from .. import ops
+from ..hierarchy import line_config
 from ..ops import F64
 from .Solver import IterativeSolver, on_device
 
@@ -34,9 +39,13 @@ class CG(IterativeSolver):
 
     @on_device
     def solve(self, max_iterations=1000, error=1e-08, initial_guess=None, *, preconditioner=None,
-              precond_steps=2, precond_omega=0.8, precond_smoother="Jacobi", precond_cycle_shape="V"):
-        if precond_smoother not in ("Jacobi", "GaussSeidel", "Chebyshev"):
-            raise ValueError("precond_smoother must be 'Jacobi', 'GaussSeidel' or 'Chebyshev', got %r" % (precond_smoother,))
+              precond_steps=2, precond_omega=0.8, precond_smoother="Jacobi", precond_cycle_shape="V",
+              precond_line_dir="xy", precond_line_order="zebra"):
+        if precond_smoother not in ("Jacobi", "GaussSeidel", "Chebyshev", "Line"):
+            raise ValueError("precond_smoother must be 'Jacobi', 'GaussSeidel', 'Chebyshev' or 'Line', got %r"
+                             % (precond_smoother,))
+        if precond_smoother == "Line":
+            line_config(precond_line_dir, precond_line_order)
         if precond_cycle_shape not in ("V", "W"):
             raise ValueError("precond_cycle_shape must be 'V' or 'W' (CG needs a symmetric preconditioner), got %r"
                              % (precond_cycle_shape,))
@@ -56,6 +65,8 @@ class CG(IterativeSolver):
         H = preconditioner
         if H is not None and precond_smoother == "Chebyshev":
             H.prepare_smoother("Chebyshev")        # bounds and work vectors before the first application
+        if H is not None and precond_smoother == "Line":
+            H.prepare_smoother("Line", line_dir=precond_line_dir, line_order=precond_line_order)
 
         def apply_M(src, dst):
             if H is None:
@@ -68,6 +79,8 @@ class CG(IterativeSolver):
                         shape=precond_cycle_shape)
             elif precond_smoother == "Chebyshev":
                 H.cycle("Chebyshev", precond_steps, 1.0, x_is_zero=True, shape=precond_cycle_shape)
+            elif precond_smoother == "Line":
+                H.cycle("Line", precond_steps, precond_omega, x_is_zero=True, shape=precond_cycle_shape)
             else:
                 H.cycle("Jacobi", precond_steps, precond_omega, x_is_zero=True, shape=precond_cycle_shape)
             ops.copy(fine.x, dst)

@@ -28,11 +28,11 @@ import scipy.sparse as sp
 import torch
 
 from .. import ops, problems
-from ..hierarchy import Hierarchy, cycle_children, gs_sweep_pair
+from ..hierarchy import Hierarchy, cycle_children, gs_sweep_pair, line_config
 from .Solver import IterativeSolver, on_device
 
 _SMOOTHERS = ("GaussSeidel", "Jacobi", "CG")          # Multigrid.py:149-155
-_EXTRA_SMOOTHERS = ("Chebyshev",)                     # not in the reference: honoured under smoother_semantics="as_named"
+_EXTRA_SMOOTHERS = ("Chebyshev", "Line")                    # not in the reference: honoured under smoother_semantics="as_named"
 
 
 class Multigrid(IterativeSolver):
@@ -84,7 +84,7 @@ class Multigrid(IterativeSolver):
     @staticmethod
     def _effective_smoother(smoother, semantics):
         if smoother not in _SMOOTHERS + _EXTRA_SMOOTHERS:
-            raise ValueError("unknown smoother %r (reference: 'Jacobi', 'GaussSeidel', 'CG'; this build also: 'Chebyshev')"
+            raise ValueError("unknown smoother %r (reference: 'Jacobi', 'GaussSeidel', 'CG'; this build also: 'Chebyshev', 'Line')"
                              % (smoother,))
         if semantics == "as_shipped":
             return "GaussSeidel"
@@ -104,14 +104,26 @@ class Multigrid(IterativeSolver):
         if cheby_ratio is not None and not float(cheby_ratio) > 1.0:
             raise ValueError("cheby_ratio must be > 1 (lambda_min = lambda_max / cheby_ratio), got %r" % (cheby_ratio,))
 
+    @staticmethod
+    def _check_line(eff, line_dir, line_order):
+        """The keyword checks of the Line smoother (before any setup work); not looked at for any other smoother."""
+        if eff == "Line":
+            line_config(line_dir, line_order)
+
     # -- Multigrid.solve (Multigrid.py:36-75) ---------------------------------------------------
     @on_device
     def solve(self, levels=2, smoother="Jacobi", smooth_steps=1, max_iterations=100, error=1e-08,
               initial_guess=None, cycle="V", first_call=False, *, omega=1.0,
               smoother_semantics="as_shipped", gs_mode="lexicographic", coarse_refine="auto",
               use_graph=False, mutate_initial_guess=False, gs_sweep="forward", cycle_shape="V",
-              cheby_lmax=None, cheby_ratio=None):
-        """smoother="Chebyshev" (under smoother_semantics="as_named"; as shipped the name is ignored like every other): one
+              cheby_lmax=None, cheby_ratio=None, line_dir="xy", line_order="zebra"):
+        """smoother="Line" (under smoother_semantics="as_named"; as shipped the name is ignored like every other): line
+        relaxation -- smooth_steps steps with damping omega before and after the coarse correction, each solving the
+        tridiagonal systems of the grid lines in direction line_dir ("x": storage lines, "y": grid columns, "xy": x then y;
+        the post-smoothing half runs the reverse order), even systems then odd ones (line_order="zebra", omega = 1.0 suits)
+        or all from one residual (line_order="jacobi", omega ~ 0.8).  The smoother for operators with a strong direction;
+        grid levels with a 3x3 stencil only (Hierarchy.prepare_smoother says which level cannot run it, and why).
+        smoother="Chebyshev" (under smoother_semantics="as_named"; as shipped the name is ignored like every other): one
         Chebyshev polynomial smoothing step of degree smooth_steps on D^-1 A before and after the coarse correction, on
         [lmax / cheby_ratio, lmax] per level.  cheby_lmax: None = each level's Gershgorin bound, a float, or one value per
         smoothed level; cheby_ratio: None = 4.0 (Hierarchy.prepare_smoother).  omega is not used.
@@ -129,11 +141,14 @@ class Multigrid(IterativeSolver):
         pair = gs_sweep_pair(gs_sweep)
         cycle_children(cycle_shape)
         self._check_cheby(eff, smooth_steps, cheby_ratio)
+        self._check_line(eff, line_dir, line_order)
         H = self._setup(levels, first_call, coarse_refine)
         H.stream.wait_stream(torch.cuda.current_stream(self._device))
         with torch.cuda.stream(H.stream):
             if eff == "Chebyshev":
                 H.prepare_smoother(eff, cheby_lmax=cheby_lmax, cheby_ratio=cheby_ratio)
+            elif eff == "Line":
+                H.prepare_smoother(eff, line_dir=line_dir, line_order=line_order)
             self._solve_on_stream(H, eff, smooth_steps, max_iterations, error, initial_guess, omega,
                                   gs_mode, use_graph, mutate_initial_guess, pair, cycle_shape)
         torch.cuda.current_stream(self._device).wait_stream(H.stream)
@@ -183,35 +198,40 @@ class Multigrid(IterativeSolver):
     @on_device
     def v_cycle(self, A, u0, rhs, smoother, smooth_steps, error, levels, first_call=False, *,
                 omega=1.0, smoother_semantics="as_shipped", gs_mode="lexicographic",
-                coarse_refine="auto", gs_sweep="forward", cheby_lmax=None, cheby_ratio=None):
+                coarse_refine="auto", gs_sweep="forward", cheby_lmax=None, cheby_ratio=None, line_dir="xy",
+                line_order="zebra"):
         """One V-cycle on (A, rhs) from u0; returns a fresh (n,1) array.  u0 receives the
-        pre-smoothed iterate like in the reference (:88-89).  gs_sweep, cheby_lmax, cheby_ratio as in solve()."""
+        pre-smoothed iterate like in the reference (:88-89).  gs_sweep, cheby_lmax, cheby_ratio, line_dir, line_order as in
+        solve()."""
         return self._one_cycle("V", A, u0, rhs, smoother, smooth_steps, levels, first_call, omega, smoother_semantics,
-                               gs_mode, coarse_refine, gs_sweep, cheby_lmax, cheby_ratio)
+                               gs_mode, coarse_refine, gs_sweep, cheby_lmax, cheby_ratio, line_dir, line_order)
 
     @on_device
     def w_cycle(self, A, u0, rhs, smoother, smooth_steps, error, levels, first_call=False, *,
                 omega=1.0, smoother_semantics="as_shipped", gs_mode="lexicographic",
-                coarse_refine="auto", gs_sweep="forward", cheby_lmax=None, cheby_ratio=None):
+                coarse_refine="auto", gs_sweep="forward", cheby_lmax=None, cheby_ratio=None, line_dir="xy",
+                line_order="zebra"):
         """One W-cycle (solve(cycle_shape="W")) with v_cycle's arguments and behaviour."""
         return self._one_cycle("W", A, u0, rhs, smoother, smooth_steps, levels, first_call, omega, smoother_semantics,
-                               gs_mode, coarse_refine, gs_sweep, cheby_lmax, cheby_ratio)
+                               gs_mode, coarse_refine, gs_sweep, cheby_lmax, cheby_ratio, line_dir, line_order)
 
     @on_device
     def f_cycle(self, A, u0, rhs, smoother, smooth_steps, error, levels, first_call=False, *,
                 omega=1.0, smoother_semantics="as_shipped", gs_mode="lexicographic",
-                coarse_refine="auto", gs_sweep="forward", cheby_lmax=None, cheby_ratio=None):
+                coarse_refine="auto", gs_sweep="forward", cheby_lmax=None, cheby_ratio=None, line_dir="xy",
+                line_order="zebra"):
         """One F-cycle (solve(cycle_shape="F")) with v_cycle's arguments and behaviour."""
         return self._one_cycle("F", A, u0, rhs, smoother, smooth_steps, levels, first_call, omega, smoother_semantics,
-                               gs_mode, coarse_refine, gs_sweep, cheby_lmax, cheby_ratio)
+                               gs_mode, coarse_refine, gs_sweep, cheby_lmax, cheby_ratio, line_dir, line_order)
 
     def _one_cycle(self, shape, A, u0, rhs, smoother, smooth_steps, levels, first_call, omega, smoother_semantics,
-                   gs_mode, coarse_refine, gs_sweep, cheby_lmax=None, cheby_ratio=None):
+                   gs_mode, coarse_refine, gs_sweep, cheby_lmax=None, cheby_ratio=None, line_dir="xy", line_order="zebra"):
         if levels < 2:
             raise ValueError("levels must be >= 2")
         eff = self._effective_smoother(smoother, smoother_semantics)
         pair = gs_sweep_pair(gs_sweep)
         self._check_cheby(eff, smooth_steps, cheby_ratio)
+        self._check_line(eff, line_dir, line_order)
         if A is self.matrix:
             H = self._setup(levels, first_call, coarse_refine)
         else:
@@ -235,6 +255,8 @@ class Multigrid(IterativeSolver):
         with torch.cuda.stream(H.stream):
             if eff == "Chebyshev":
                 H.prepare_smoother(eff, cheby_lmax=cheby_lmax, cheby_ratio=cheby_ratio)
+            elif eff == "Line":
+                H.prepare_smoother(eff, line_dir=line_dir, line_order=line_order)
             H.cycle(eff, smooth_steps, omega, gs_mode, after_presmooth=hook, gs_sweep=pair, shape=shape)
             out = fine.x.cpu().numpy().reshape(n, 1).copy()
             if eff == "GaussSeidel":
