@@ -53,7 +53,12 @@ int lmg_device_count(void);
  *   key                        accepts        meaning
  *   "sweep_variant"            0..6      [0]  tile geometry of the plain-CSR sweeps; 0 = from the average row length
  *   "pcsr_ju"                  0 1 3 5 101 102  [0]  row entries per step of the packed sweeps; 0 = from the average
- *                                             row length; 101, 102 = the one-/two-tile probes of the 16-bit/8-bit encoding
+ *                                             row length.  101, 102 = TIMING PROBES, not sweeps: the kernel of 1 with
+ *                                             the gathers of x left out (101: the column index stands in for x[column])
+ *                                             and with the staging of the tile left out as well (102: whatever LDS
+ *                                             holds).  The output vectors are written but are NOT the sweep's result.
+ *                                             Only for the uint16-column / uint8-value encoding on 512-row tiles;
+ *                                             lmg_pcsr_sweep answers LMG_ERR_ARG for every other twin while one is set.
  *   "rpat_variant"             0..4      [0]  geometry of the row-pattern sweeps; 0 = from the longest pattern
  *                                             (a value >= 1000 sets "rpat_nt_rows" instead: bench.py's spelling)
  *   "rpat_nt_rows"             >= 1      [8388608]  rows from which the row-pattern sweeps' streams bypass the caches

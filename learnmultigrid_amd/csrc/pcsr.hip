@@ -81,7 +81,8 @@ __device__ __forceinline__ void stage_bytes(const unsigned char *g, long lo16, l
 }
 
 // JU = entries of each row handled per step (JU x 4 independent gathers in flight per thread)
-// EXP (timing experiments only, wrong results): 1 = no x gathers, 2 = no gathers and no staging
+// EXP (timing experiments only, WRONG RESULTS -- reached through pcsr_ju = 101 / 102, see g_pcsr_ju):
+//   1 = no x gathers: (double)column stands in for x[column];  2 = neither gathers nor staging: LDS is read as it is
 #ifndef LMG_PCSR_WAVES
 #define LMG_PCSR_WAVES 1
 #endif
@@ -266,7 +267,11 @@ int lds_bytes(int cap, int colmode, int valmode)
     return (valmode == VAL8 ? 4096 : 0) + ((cap * cs + 15) & ~15) + 16 + ((cap * vs + 15) & ~15) + 16 + 32 + 16;
 }
 
-int g_pcsr_ju = 0;      // 0 = pick from the average row length; 1, 2, 3, 5 = forced (tuning)
+// 0 = pick from the average row length; 1, 3, 5 = forced (tuning, parity tests; short tiles run 1 as 3).
+// 101 / 102 = the EXP 1 / EXP 2 instantiations of the JU 1 kernel: timing probes that tell the cost of the gathers and of
+// the staging apart.  What they write to the output vectors is NOT the sweep's result (no x is read), so nothing but
+// a timing loop may set them; they exist for COL16 / VAL8 on 512-row tiles only, every other twin gets LMG_ERR_ARG.
+int g_pcsr_ju = 0;
 
 template <int MODE, int COLMODE, int VALMODE, int JU>
 int launch_ju(PArgs a, hipStream_t st);

@@ -198,10 +198,18 @@ class PackedCSR:
             raise LmgError("value dictionary does not cover the matrix values")
 
     @classmethod
-    def from_csr(cls, A):
+    def from_csr(cls, A, tile_rows=None, colmode=None):
+        """tile_rows (512, 128 or 64) and colmode (0: uint16 tile-relative columns, 1: int32) override the choices made
+        below -- the format allows any tile height and int32 columns for any matrix; None keeps the builder's own rule.
+        The value encoding always follows from the number of distinct values.  (pack() passes neither: the parity tests
+        reach the short tiles and the int32 columns on small matrices this way.)"""
         n, nnz = A.shape[0], A.nnz
         if n == 0 or nnz == 0:
             return None
+        if tile_rows is not None and int(tile_rows) not in (512, 128, 64):
+            raise ValueError("tile_rows must be 512, 128 or 64, got %r" % (tile_rows,))
+        if colmode is not None and int(colmode) not in (0, 1):
+            raise ValueError("colmode must be 0 or 1, got %r" % (colmode,))
         L = _lib.lib()
         dev = A.vals.device
         rowlen = (A.rowptr[1:] - A.rowptr[:-1])
@@ -216,7 +224,9 @@ class PackedCSR:
         avg = nnz / n
         T = int(L.lmg_pcsr_tile_rows())
         bpe = 2 + (1 if ndict <= 256 else (2 if ndict <= 65536 else 8))
-        if T * avg * bpe > 20480:
+        if tile_rows is not None:
+            T = int(tile_rows)
+        elif T * avg * bpe > 20480:
             T = 128 if 128 * avg * (2 + (1 if ndict <= 256 else 8)) <= 20480 else 64
             if 256 < ndict <= 65536:
                 ndict = 1 << 30                    # force raw values
@@ -235,7 +245,10 @@ class PackedCSR:
         check(L.lmg_pcsr_tile_colrange(n, T, _p(A.rowptr), _p(A.colidx), _p(cmin), _p(cmax), _s(A.rowptr)),
               "lmg_pcsr_tile_colrange")
         self.tile_colbase = cmin
-        if int((cmax - cmin).max()) < 65536:
+        fits16 = int((cmax - cmin).max()) < 65536
+        if colmode == 0 and not fits16:
+            raise ValueError("colmode 0: a tile spans 65536 columns or more")
+        if (fits16 if colmode is None else int(colmode) == 0):
             self.colmode = 0
             self.col = cls._padded_empty(2 * nnz, dev)
             check(L.lmg_pcsr_encode_cols16(n, T, _p(A.rowptr), _p(A.colidx), _p(cmin), _p(self.col), _s(A.rowptr)),
@@ -301,10 +314,16 @@ class SellCSR:
     MAX_PADDING = 1.2
 
     @classmethod
-    def from_csr(cls, A):
+    def from_csr(cls, A, colmode=None, max_padding=None):
+        """colmode (0: uint16 slice-relative columns, 1: int32) and max_padding (padded entries per entry of the matrix
+        from which the twin is refused; default MAX_PADDING) override the choices made below -- the format allows int32
+        columns and any padding for any matrix; None keeps the builder's own rule.  (pack() passes neither: the parity
+        tests reach the int32 columns and ragged slices on small matrices this way.)"""
         n, nnz = A.shape[0], A.nnz
         if n == 0 or nnz == 0 or not A.vals.is_cuda:
             return None
+        if colmode is not None and int(colmode) not in (0, 1):
+            raise ValueError("colmode must be 0 or 1, got %r" % (colmode,))
         L = _lib.lib()
         dev = A.vals.device
         nsl = (n + 63) // 64
@@ -314,7 +333,7 @@ class SellCSR:
         check(L.lmg_sell_slice_info(n, _p(A.rowptr), _p(A.colidx), _p(slice_len), _p(cmin), _p(cmax), _s(A.rowptr)),
               "lmg_sell_slice_info")
         padded = 64 * int(slice_len.long().sum())
-        if padded > cls.MAX_PADDING * nnz or padded >= 2 ** 31 - 64:
+        if padded > (cls.MAX_PADDING if max_padding is None else max_padding) * nnz or padded >= 2 ** 31 - 64:
             return None
         self = cls()
         self.n, self.nnz, self.shape, self.padded = n, nnz, A.shape, padded
@@ -324,7 +343,10 @@ class SellCSR:
         self.slice_cmin = cmin
         self.rowlen = (A.rowptr[1:] - A.rowptr[:-1]).contiguous()
         self.max_len = int(slice_len.max())
-        self.colmode = 0 if int((cmax - cmin).max()) < 65536 else 1
+        fits16 = int((cmax - cmin).max()) < 65536
+        if colmode == 0 and not fits16:
+            raise ValueError("colmode 0: a slice spans 65536 columns or more")
+        self.colmode = (0 if fits16 else 1) if colmode is None else int(colmode)
         self.col = torch.zeros(padded + 64, dtype=torch.int16 if self.colmode == 0 else I32, device=dev)
         self.val = torch.zeros(padded + 64, dtype=F64, device=dev)
         check(L.lmg_sell_fill(n, _p(A.rowptr), _p(A.colidx), _p(A.vals), _p(self.slice_base), _p(cmin), self.colmode,

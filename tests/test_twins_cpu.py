@@ -337,3 +337,16 @@ def test_restriction(s, via):
     counts = np.bincount(pid)
     full = [p for p in range(len(r_mask)) if r_mask[p] == 0x1FF]
     assert hot in full and counts[hot] == max(counts[p] for p in full) and hot == pid[Wc + 1]
+
+
+def test_builder_overrides_refuse_what_the_formats_do_not_have():
+    """tile_rows / colmode of PackedCSR.from_csr and colmode of SellCSR.from_csr are checked before anything is built."""
+    A = SimpleNamespace(shape=(4, 4), nnz=4, vals=torch.zeros(4, dtype=torch.float64))
+    for bad in (0, 256, 1024):
+        with pytest.raises(ValueError):
+            ops.PackedCSR.from_csr(A, tile_rows=bad)
+    for bad in (-1, 2):
+        with pytest.raises(ValueError):
+            ops.PackedCSR.from_csr(A, colmode=bad)
+    # (a host matrix gets no sliced-ELL twin at all, whatever is asked for)
+    assert ops.SellCSR.from_csr(A, colmode=2) is None
