@@ -578,7 +578,8 @@ int lmg_dense_gemv_windows(int64_t nblocks, int64_t rows, int64_t cols, const do
 
 /* The same with a table of window starts: the x window of block k is d_x[d_x_offsets[k] .. + cols) (any 8-byte
  * aligned start; the caller keeps every window inside the allocation).  Back-substitution of the banded coarse
- * solver: x_I = y_I - (A_II^-1 A_IS) x_S in one launch (coarse.py BandedBlockSolver.apply). */
+ * solver: x_I = y_I - (A_II^-1 A_IS) x_S in one launch (coarse.py BandedBlockSolver.apply).  With
+ * d_x_offsets[k] = k * x_stride the bits of lmg_dense_gemv_windows (one routine sums the rows of both). */
 int lmg_dense_gemv_windows_off(int64_t nblocks, int64_t rows, int64_t cols, const double *d_M, const double *d_x,
                                const int32_t *d_x_offsets, const double *d_z, int64_t z_stride, double alpha,
                                double *d_y, int64_t y_stride, void *stream);
@@ -590,7 +591,8 @@ int lmg_dense_gemv_windows_off(int64_t nblocks, int64_t rows, int64_t cols, cons
  *                     out[perm[nblocks*rows + i]] (+)= x[i], i < ntail   (accumulate != 0: += , the refinement step).
  * Every block of d_perm[0 .. nblocks*bs) is a run of consecutive indices (perm[k bs + c] = perm[k bs] + c: a strip of the
  * banded solver), which lmg_coarse_front relies on.
- * Same sums as lmg_dense_gemv_blockdiag / lmg_dense_gemv_windows_off followed by lmg_gather / lmg_scatter / lmg_axpby. */
+ * Same sums as lmg_dense_gemv_blockdiag / lmg_dense_gemv_windows_off followed by lmg_gather / lmg_scatter / lmg_axpby:
+ * all of them sum a row through one routine (csrc/dense.hip). */
 int lmg_coarse_front(int64_t nblocks, int64_t bs, const double *d_M, const double *d_b, const int32_t *d_perm, double *d_y,
                      int64_t ntail, double *d_tail_out, void *stream);
 int lmg_coarse_back(int64_t nblocks, int64_t rows, int64_t cols, const double *d_M, const double *d_x,

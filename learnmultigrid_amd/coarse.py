@@ -203,7 +203,61 @@ def half_bandwidth(A_host):
     return int(np.abs(coo.row - coo.col).max()) if coo.nnz else 0
 
 
-class BandedBlockSolver:
+class _SchurBlockSolver:
+    """The numeric phase BandedBlockSolver and GridBlockSolver share: the exact block elimination
+
+        [ A_II  A_IS ] [x_I]   [b_I]        A_II = blockdiag(k blocks, s x s)
+        [ A_SI  A_SS ] [x_S] = [b_S]        S    = A_SS - A_SI A_II^-1 A_IS
+
+    on the entry maps a subclass's _symbolic built once per sparsity pattern: _src_XX / _dst_XX (entry of A -> flat
+    position in the dense II / IS / SI / SS storage, IS and SI on windows of _wcols separator unknowns per block), _upd
+    (the passes that subtract the k local updates from S), _offdiag (the sparse off-diagonal blocks apply() multiplies
+    by, with the entries of A their values come from) and _nnz.  A subclass supplies the product step (_products) and,
+    where its blocks are padded, _pad_blocks."""
+    supports_accumulate = True
+
+    def _place(self, v, src, dst, size):
+        """zeros(size) with out[dst[k]] = v[src[k]] (destinations are distinct: sorted, duplicate-free CSR) --
+        own gather / scatter kernels: torch's index_put_ costs 0.4 s to load in a fresh process."""
+        out = torch.zeros(size, dtype=F64, device=v.device)
+        if src.numel():
+            tmp = torch.empty(src.numel(), dtype=F64, device=v.device)
+            self.ops.gather(src, v, tmp)
+            self.ops.scatter(dst, tmp, out)
+        return out
+
+    def _pad_blocks(self, dense):
+        pass
+
+    def factor(self, A):
+        """Block inverses, Schur complement S = A_SS - A_SI A_II^-1 A_IS and S^-1 from the
+        current values of A (same pattern as at construction).  Device only: repeated for every Galerkin rebuild."""
+        if A.nnz != self._nnz:
+            raise ValueError("coarse operator changed its sparsity pattern")
+        k, s, c, nS = self.k, self.s, self._wcols, self.nS
+        v = A.vals
+        dense = self._place(v, self._src_II, self._dst_II, k * s * s)
+        self._pad_blocks(dense)
+        self.blocks = dense_inverse(dense.view(k, s, s))       # all blocks as one batch
+        ais = self._place(v, self._src_IS, self._dst_IS, k * s * c)
+        asi = self._place(v, self._src_SI, self._dst_SI, k * c * s)
+        upd = self._products(ais.view(k, s, c), asi.view(k, c, s)).reshape(-1)       # k x c x c: A_SI A_II^-1 A_IS per block
+        Sc = self._place(v, self._src_SS, self._dst_SS, nS * nS)
+        for sel, dst in self._upd:                       # S[dst] -= upd[sel], every destination once per pass
+            if sel.numel():
+                tmp = torch.empty(sel.numel(), dtype=F64, device=v.device)
+                cur = torch.empty(sel.numel(), dtype=F64, device=v.device)
+                self.ops.gather(sel, upd, tmp)
+                self.ops.gather(dst, Sc, cur)
+                self.ops.axpby(-1.0, tmp, 1.0, cur)
+                self.ops.scatter(dst, cur, Sc)
+        self.Sinv = dense_inverse(Sc.view(nS, nS))
+        for csr, src in self._offdiag:                   # values of the sparse blocks; their packed twins are stale
+            self.ops.gather(src, v, csr.vals)
+            csr.invalidate_packed()
+
+
+class BandedBlockSolver(_SchurBlockSolver):
     kind = "banded-block"
 
     @staticmethod
@@ -312,11 +366,12 @@ class BandedBlockSolver:
             sel[np.arange(k) % 2 != parity] = False
             self._upd.append((t32(flat[sel]), t32(dst[sel])))
         # sparse off-diagonal blocks for apply(): CSR patterns once, values refreshed by factor()
-        self._IS_src = t32(np.rint(IS_pat.data).astype(np.int64) - 1)
-        self._SI_src = t32(np.rint(SI_pat.data).astype(np.int64) - 1)
         z64 = lambda m_: torch.zeros(m_, dtype=F64, device=dev)
         self.A_IS = DeviceCSR(t(IS_pat.indptr, torch.int32), t(IS_pat.indices, torch.int32), z64(IS_pat.nnz), (nI, nS))
         self.A_SI = DeviceCSR(t(SI_pat.indptr, torch.int32), t(SI_pat.indices, torch.int32), z64(SI_pat.nnz), (nS, nI))
+        self._offdiag = [(self.A_IS, t32(np.rint(IS_pat.data).astype(np.int64) - 1)),
+                         (self.A_SI, t32(np.rint(SI_pat.data).astype(np.int64) - 1))]
+        self._wcols = cw
         self.perm = t(perm, torch.int32)
         # back-substitution in one launch: x_I = y_I - W x_S with W = A_II^-1 A_IS per strip (s x cw, cw padded to even;
         # window starts ws[i] in x_S; x_S is followed by zeros so that the last window stays inside)
@@ -329,54 +384,14 @@ class BandedBlockSolver:
         self.Sinv = None
         self._nnz = int(cols.size)
 
-    # ---- numeric: device only (repeated for every Galerkin rebuild) -----------------------
-    def _place(self, v, src, dst, size):
-        """zeros(size) with out[dst[k]] = v[src[k]] (destinations are distinct: sorted, duplicate-free CSR) --
-        own gather / scatter kernels: torch's index_put_ costs 0.4 s to load in a fresh process."""
-        out = torch.zeros(size, dtype=F64, device=v.device)
-        if src.numel():
-            tmp = torch.empty(src.numel(), dtype=F64, device=v.device)
-            self.ops.gather(src, v, tmp)
-            self.ops.scatter(dst, tmp, out)
-        return out
-
-    def factor(self, A):
-        """Strip inverses, Schur complement S = A_SS - A_SI A_II^-1 A_IS and S^-1 from the
-        current values of A (same pattern as at construction)."""
-        if A.nnz != self._nnz:
-            raise ValueError("coarse operator changed its sparsity pattern")
-        k, s, cw, nS = self.k, self.s, self.cw, self.nS
-        dev = A.vals.device
-        v = A.vals
-        dense = self._place(v, self._src_II, self._dst_II, k * s * s).view(k, s, s)
-        self.blocks = dense_inverse(dense)            # all strips as one batch
-        ais = self._place(v, self._src_IS, self._dst_IS, k * s * cw)
-        asi = self._place(v, self._src_SI, self._dst_SI, k * cw * s)
-        w_ = torch.bmm(self.blocks, ais.view(k, s, cw))                                      # k x s x cw: A_II^-1 A_IS
-        upd = torch.bmm(asi.view(k, cw, s), w_)                                              # k x cw x cw
+    def _products(self, ais, asi):
+        w_ = torch.bmm(self.blocks, ais)                                                     # k x s x cw: A_II^-1 A_IS
         if BACKSUB_ONE_LAUNCH and hasattr(self.ops, "dense_gemv_windows_off"):
-            self.W = torch.zeros((k, s, self.cwp), dtype=F64, device=dev)
-            self.W[:, :, :cw] = w_
+            self.W = torch.zeros((self.k, self.s, self.cwp), dtype=F64, device=w_.device)
+            self.W[:, :, :self.cw] = w_
         else:
             self.W = None
-        del w_
-        Sc = self._place(v, self._src_SS, self._dst_SS, nS * nS)
-        upd = upd.reshape(-1)
-        for sel, dst in self._upd:                       # S[dst] -= upd[sel], every destination once per pass
-            if sel.numel():
-                tmp = torch.empty(sel.numel(), dtype=F64, device=dev)
-                cur = torch.empty(sel.numel(), dtype=F64, device=dev)
-                self.ops.gather(sel, upd, tmp)
-                self.ops.gather(dst, Sc, cur)
-                self.ops.axpby(-1.0, tmp, 1.0, cur)
-                self.ops.scatter(dst, cur, Sc)
-        self.Sinv = dense_inverse(Sc.view(nS, nS))
-        self.ops.gather(self._IS_src, v, self.A_IS.vals)
-        self.ops.gather(self._SI_src, v, self.A_SI.vals)
-        self.A_IS.invalidate_packed()
-        self.A_SI.invalidate_packed()
-
-    supports_accumulate = True
+        return torch.bmm(asi, w_)
 
     def apply(self, b, x, accumulate=False):
         """x = A^-1 b; accumulate: x += A^-1 b (the refinement step of Hierarchy.coarse_solve without a temporary)."""
@@ -414,7 +429,7 @@ class BandedBlockSolver:
 
 
 
-class GridBlockSolver:
+class GridBlockSolver(_SchurBlockSolver):
     """One-level nested dissection in TWO directions for operators of a row-major grid (n = lines x W unknowns,
     every coupling within r lines and r columns: the 9-point Galerkin operators of the geometric transfers, r = 1;
     the 25-point ones of L2-type / learned transfers, r = 2).  Separator lines AND columns, r unknowns thick, cut
@@ -429,7 +444,6 @@ class GridBlockSolver:
     2 241 separator unknowns) against 159 MB for 21 strips.  Four launches per application, the permutation folded
     into the first and the last one (lmg_coarse_front_gather / lmg_coarse_back_gather)."""
     kind = "grid-block"
-    supports_accumulate = True
 
     @staticmethod
     def detect_grid(n, A_host):
@@ -586,9 +600,10 @@ class GridBlockSolver:
                 if np.unique(d_).size != d_.size:
                     raise ValueError("blocks of one parity class share separator unknowns")
                 self._upd.append((t32(flat[sel]), t32(d_)))
-        self._SI_src = t32(np.rint(SI_pat.data).astype(np.int64) - 1)
         z64 = lambda m_: torch.zeros(m_, dtype=F64, device=dev)
         self.A_SI = DeviceCSR(t(SI_pat.indptr, torch.int32), t(SI_pat.indices, torch.int32), z64(SI_pat.nnz), (nS, k * s))
+        self._offdiag = [(self.A_SI, t32(np.rint(SI_pat.data).astype(np.int64) - 1))]
+        self._wcols = cwp
         gI = np.full(k * s, -1, dtype=np.int64)
         gI[slot[order]] = order
         self._gI = t32(gI)                                           # padded interior slot -> unknown (-1: padding)
@@ -603,37 +618,17 @@ class GridBlockSolver:
         self.Sinv = None
         self._nnz = int(cols.size)
 
-    _place = BandedBlockSolver._place
-
-    def factor(self, A):
-        if A.nnz != self._nnz:
-            raise ValueError("coarse operator changed its sparsity pattern")
-        k, s, cwp, nS = self.k, self.s, self.cwp, self.nS
-        dev = A.vals.device
-        v = A.vals
-        dense = self._place(v, self._src_II, self._dst_II, k * s * s)
+    def _pad_blocks(self, dense):
         if self._pad_dst.numel():
-            self.ops.scatter(self._pad_dst, torch.ones(self._pad_dst.numel(), dtype=F64, device=dev), dense)
-        self.blocks = dense_inverse(dense.view(k, s, s))
-        ais = self._place(v, self._src_IS, self._dst_IS, k * s * cwp)
-        asi = self._place(v, self._src_SI, self._dst_SI, k * cwp * s)
-        if v.is_cuda and hasattr(self.ops, "gemm"):
-            self.Wm = self.ops.gemm(self.blocks, ais.view(k, s, cwp), torch.empty((k, s, cwp), dtype=F64, device=dev))
-            upd = self.ops.gemm(asi.view(k, cwp, s), self.Wm, torch.empty((k, cwp, cwp), dtype=F64, device=dev)).reshape(-1)
-        else:
-            self.Wm = torch.bmm(self.blocks, ais.view(k, s, cwp)).contiguous()           # k x s x cwp: A_II^-1 A_IS
-            upd = torch.bmm(asi.view(k, cwp, s), self.Wm).reshape(-1)                    # k x cwp x cwp
-        Sc = self._place(v, self._src_SS, self._dst_SS, nS * nS)
-        for sel, dst in self._upd:                       # S[dst] -= upd[sel], every destination once per pass
-            tmp = torch.empty(sel.numel(), dtype=F64, device=dev)
-            cur = torch.empty(sel.numel(), dtype=F64, device=dev)
-            self.ops.gather(sel, upd, tmp)
-            self.ops.gather(dst, Sc, cur)
-            self.ops.axpby(-1.0, tmp, 1.0, cur)
-            self.ops.scatter(dst, cur, Sc)
-        self.Sinv = dense_inverse(Sc.view(nS, nS))
-        self.ops.gather(self._SI_src, v, self.A_SI.vals)
-        self.A_SI.invalidate_packed()
+            self.ops.scatter(self._pad_dst, torch.ones(self._pad_dst.numel(), dtype=F64, device=dense.device), dense)
+
+    def _products(self, ais, asi):
+        k, s, cwp = ais.shape
+        if ais.is_cuda and hasattr(self.ops, "gemm"):
+            self.Wm = self.ops.gemm(self.blocks, ais, torch.empty((k, s, cwp), dtype=F64, device=ais.device))
+            return self.ops.gemm(asi, self.Wm, torch.empty((k, cwp, cwp), dtype=F64, device=ais.device))
+        self.Wm = torch.bmm(self.blocks, ais).contiguous()                           # k x s x cwp: A_II^-1 A_IS
+        return torch.bmm(asi, self.Wm)
 
     def apply(self, b, x, accumulate=False):
         """x = A^-1 b; accumulate: x += A^-1 b."""

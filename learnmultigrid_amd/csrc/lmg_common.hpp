@@ -1,5 +1,5 @@
 // Shared helpers of the gfx950 kernels (wave64, 256 CUs in 8 XCDs): everything that more than one kernel file
-// needs has its single definition here -- the sweep modes and their argument rules, XCD-aware tile ownership and the
+// needs has its single definition here -- the grid of a grid-stride launch, the sweep modes and their argument rules, XCD-aware tile ownership and the
 // persistent grid that goes with it, the fixed-order sums, the DPP lane shifts, and the 3x3 stencil view (slot masks,
 // pattern-table limit).  The host half at the end is what sits between the C ABI and hipLaunchKernelGGL in more than
 // one file: the rows of the tune-key tables, and the one body of a fused-pass entry point (argument groups, checks, dispatch).
@@ -21,6 +21,18 @@
 
 static inline hipStream_t lmg_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 static inline bool lmg_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// ---- launch geometry of the grid-stride kernels (vec.hip, dense.hip) -------------------------------------------------
+constexpr int kLmgBlock = 256;
+constexpr int kLmgMaxGrid = 256 * 8;   // 256 CUs x 8 resident workgroups: grid-stride beyond
+
+static inline unsigned lmg_grid_for(int64_t n, int per_block)
+{
+    int64_t g = (n + per_block - 1) / per_block;
+    if (g > kLmgMaxGrid) g = kLmgMaxGrid;
+    if (g < 1) g = 1;
+    return (unsigned)g;
+}
 
 // ---- the three sweeps every storage format offers (the `mode` of the lmg_*_sweep entry points) ---------------------
 enum { MODE_RESIDUAL = 0, MODE_JACOBI = 1, MODE_SPMV = 2 };

@@ -40,10 +40,10 @@ KINDS = ["exact", "real"]
 U = fractions.Fraction(1, 2 ** 53)
 WIDE = np.finfo(np.longdouble).eps <= 2.0 ** -63
 
-# what the shapes below were derived from (csrc/vec.hip, csrc/gemm.hip); test_shapes_follow_the_kernel_constants
-# fails when one of them changes, and the shapes have to be derived again
-WAVES_CAP = 256 * 8 * 4          # kMaxGrid workgroups of kBlock / LMG_WAVE waves: one row per wave beyond -> stride loop
-THREADS_CAP = 256 * 8 * 256      # kMaxGrid * kBlock threads: one element per thread beyond -> stride loop
+# what the shapes below were derived from (the launch geometry in csrc/lmg_common.hpp, csrc/dense.hip, csrc/gemm.hip);
+# test_shapes_follow_the_kernel_constants fails when one of them changes, and the shapes have to be derived again
+WAVES_CAP = 256 * 8 * 4          # kLmgMaxGrid workgroups of kLmgBlock / LMG_WAVE waves: one row per wave beyond -> stride loop
+THREADS_CAP = 256 * 8 * 256      # kLmgMaxGrid * kLmgBlock threads: one element per thread beyond -> stride loop
 COARSE_ROWS = 36                 # kCoarseRows
 LDS_CAP_BYTES = 60000            # operand segment of the gather kernels
 
@@ -158,12 +158,12 @@ def source_constant(fname, name):
 
 
 def test_shapes_follow_the_kernel_constants():
-    kblock, kmax = source_constant("vec.hip", "kBlock"), source_constant("vec.hip", "kMaxGrid")
+    kblock, kmax = source_constant("lmg_common.hpp", "kLmgBlock"), source_constant("lmg_common.hpp", "kLmgMaxGrid")
     assert (kblock, kmax, kmax * kblock // 64, kmax * kblock) == (256, 2048, WAVES_CAP, THREADS_CAP)
-    assert source_constant("vec.hip", "kCoarseRows") == COARSE_ROWS
+    assert source_constant("dense.hip", "kCoarseRows") == COARSE_ROWS
     assert [source_constant("gemm.hip", k) for k in ("kTM", "kTN", "kTK")] == [64, 64, 16]
-    vec = open(os.path.join(ROOT, "learnmultigrid_amd", "csrc", "vec.hip")).read()
-    assert vec.count("* 8 > %d" % LDS_CAP_BYTES) == 2                    # both gather entry points
+    dense = open(os.path.join(ROOT, "learnmultigrid_amd", "csrc", "dense.hip")).read()
+    assert dense.count("* 8 > %d" % LDS_CAP_BYTES) == 2                  # both gather entry points
     gemm = open(os.path.join(ROOT, "learnmultigrid_amd", "csrc", "gemm.hip")).read()
     assert "if (g > 4096) g = 4096;" in gemm                             # copy2d's grid cap (x 256 threads)
 
@@ -646,6 +646,20 @@ def test_coarse_back_is_windows_off_then_scatter_then_axpby(cols):
     ops.axpby(1.0, out2, 1.0, acc2)
     assert torch.equal(bits(acc1), bits(acc2))
     assert not torch.equal(acc1, dev(c["before"]))
+
+
+@pytest.mark.parametrize("cols,xs", [(130, 64), (514, 256)])
+def test_windows_is_windows_off_at_the_strided_starts(cols, xs):
+    """65 pairs: a second trip for lane 0 only; 257 pairs: five trips.  xs even and below cols: the windows overlap."""
+    nb, rows = 3, 7
+    c = windows_case("real", dict(nb=nb, rows=rows, cols=cols, xs=xs, ys=rows + 3, zs=rows + 1, alpha=None))
+    assert np.array_equal(c["starts"], np.arange(nb) * xs) and c["z"] is not None and c["alpha"] not in (0.0, 1.0)
+    strided, by_table = run_windows(ops, dev, c), run_windows(ops, dev, c, off=True)      # (NaN outputs, guard cells)
+    assert np.array_equal(strided.view(np.int64), by_table.view(np.int64))
+    written = np.zeros(strided.size, dtype=bool)
+    for k in range(nb):
+        written[1 + k * c["ys"]:1 + k * c["ys"] + rows] = True
+    assert np.array_equal(np.isnan(strided), ~written)
 
 
 # ---- the CPU stand-ins of tests/cpu_ops_shim.py against the kernels they stand for ----------------------------------------
