@@ -554,6 +554,33 @@ int lmg_dot(int64_t n, const double *d_x, const double *d_y, double *d_partials,
 int lmg_gather(int64_t n, const int32_t *d_idx, const double *d_x, double *d_buf, void *stream);
 int lmg_scatter(int64_t n, const int32_t *d_idx, const double *d_buf, double *d_x, void *stream);
 
+/* ---- fused Gram-Schmidt passes of the Krylov solvers (csrc/krylov.hip) ----------------------------------------------------
+ * A basis is a row-major block d_V[k][ldv] of doubles, ldv >= n and even, so that every row is 16-byte aligned like the
+ * base (LMG_ERR_ARG for an odd ldv or ldv < n, LMG_ERR_ALIGN for a base of d_V or d_w off 16 bytes).  Elements n .. ldv-1
+ * of a row, and rows >= k, are never read or written.  k <= lmg_krylov_max_vectors() (65: restart <= 64), LMG_ERR_ARG for
+ * k < 0 or beyond.  d_partials: lmg_multi_partials_count(n, k) doubles of scratch for either call.
+ *
+ *   lmg_multi_dot    d_out[j] = V_j . w, j < k.  w is read once per 16 columns, every V_j once.
+ *   lmg_multi_axpy   every element:  w = w - coef[0] * v_0,  then  - coef[1] * v_1, ... j ascending (subtract == 0: +); each
+ *                    product and each sum rounds on its own, the bits of the loop `for j: w = w - coef[j] * V[j]`.
+ *                    d_coef is a DEVICE array, typically the d_out of the lmg_multi_dot before it on the same stream.
+ *                    d_norm2 != NULL receives |w_new|^2 (d_partials needed); NULL: no reduction, d_partials may be NULL
+ *                    and is not written.  w is read and written once, every V_j read once.  w must not overlap d_V.
+ *
+ * Summation order, the same for every column and for |w|^2, independent of k, of the other columns and of every tune key:
+ * 1024 workgroups of 256 lanes; lane t of workgroup g owns the element pairs (2 i, 2 i + 1), i = 256 g + t + 262144 m,
+ * m = 0, 1, ..., and adds their products to one accumulator in ascending i, first element of the pair first; the last
+ * element of an odd n is added by lane 0 of workgroup 0 after its pairs.  A workgroup's sum: 64-lane butterfly
+ * (offsets 32, 16, ... 1), then its four waves in ascending order.  The 1024 partials: a second launch, one partial per
+ * lane, butterfly, then the 16 waves in ascending order.  (Not the element <-> lane map of lmg_dot, which loads 8 bytes.)
+ * k == 0 is LMG_OK (lmg_multi_axpy with d_norm2 then still sums |w|^2); n == 0 is LMG_OK, d_out[j] = 0 resp. *d_norm2 = 0. */
+int lmg_krylov_max_vectors(void);
+int64_t lmg_multi_partials_count(int64_t n, int k);
+int lmg_multi_dot(int64_t n, int k, const double *d_V, int64_t ldv, const double *d_w, double *d_partials, double *d_out,
+                  void *stream);
+int lmg_multi_axpy(int64_t n, int k, int subtract, const double *d_V, int64_t ldv, const double *d_coef, double *d_w,
+                   double *d_partials, double *d_norm2, void *stream);
+
 /* ---- coarsest level --------------------------------------------------------------
  * y = M x for a dense row-major n x m matrix: applies a pre-factored coarse operator
  * (M = A_L^-1 computed once at setup) in place of the per-cycle SuperLU

@@ -870,6 +870,40 @@ def dot(x, y, partials, out):
     check(_lib.lib().lmg_dot(x.numel(), _p(x), _p(y), _p(partials), _p(out), _s(x)), "lmg_dot")
 
 
+def krylov_max_vectors():
+    """Most basis rows one multi_dot / multi_axpy call takes."""
+    return int(_lib.lib().lmg_krylov_max_vectors())
+
+
+def multi_partials_count(n, k):
+    return int(_lib.lib().lmg_multi_partials_count(int(n), int(k)))
+
+
+def _basis_ok(V, k, w):
+    _vec_ok(V, w)
+    if V.dim() != 2 or not 0 <= int(k) <= V.shape[0] or w.dim() != 1 or w.numel() > V.shape[1]:
+        raise ValueError("basis %s does not hold %d rows of %d elements" % (tuple(V.shape), k, w.numel()))
+
+
+def multi_dot(V, k, w, partials, out):
+    """out[j] = V[j, :n] . w for j < k in one pass over w (n = w.numel(); V is 2-D contiguous, its row stride is ldv)."""
+    _basis_ok(V, k, w)
+    _vec_ok(partials, out)
+    if out.numel() < int(k) or partials.numel() < multi_partials_count(w.numel(), k):
+        raise ValueError("multi_dot: out or partials too short for %d columns" % k)
+    check(_lib.lib().lmg_multi_dot(w.numel(), int(k), _p(V), V.shape[1], _p(w), _p(partials), _p(out), _s(w)), "lmg_multi_dot")
+
+
+def multi_axpy(V, k, coef, w, partials=None, norm2=None, subtract=True):
+    """w -= sum_j coef[j] V[j, :n] (subtract=False: +=), j ascending, coef a DEVICE tensor; norm2[0] = |w_new|^2 if given."""
+    _basis_ok(V, k, w)
+    _vec_ok(coef, partials, norm2)
+    if coef.numel() < int(k) or (norm2 is not None and (partials is None or partials.numel() < multi_partials_count(w.numel(), k))):
+        raise ValueError("multi_axpy: coef or partials too short for %d columns" % k)
+    check(_lib.lib().lmg_multi_axpy(w.numel(), int(k), 1 if subtract else 0, _p(V), V.shape[1], _p(coef), _p(w), _p(partials),
+                                    _p(norm2), _s(w)), "lmg_multi_axpy")
+
+
 def gather(idx, x, buf):
     check(_lib.lib().lmg_gather(idx.numel(), _p(idx), _p(x), _p(buf), _s(idx)), "lmg_gather")
 
@@ -1390,5 +1424,24 @@ def register_torch_ops():
     lib.impl("line_solve", op_line_solve, "CUDA")
     lib.impl("operator_gauss_seidel_", op_h_gs_, "CUDA")
     lib.impl("operator_gauss_seidel_backward_", op_h_gs_backward_, "CUDA")
+
+    # ---- the fused Gram-Schmidt passes of the Krylov solvers: V is a 2-D contiguous basis, k its rows in use ----------
+    lib.define("multi_dot(Tensor V, int k, Tensor w) -> Tensor")
+    lib.define("multi_axpy_(Tensor V, int k, Tensor coef, Tensor(a!) w, bool subtract) -> Tensor")
+
+    def op_multi_dot(V, k, w):
+        part = torch.empty(multi_partials_count(w.numel(), k), dtype=F64, device=w.device)
+        out = torch.zeros(int(k), dtype=F64, device=w.device)
+        multi_dot(V, k, w, part, out)
+        return out
+
+    def op_multi_axpy_(V, k, coef, w, subtract):
+        part = torch.empty(multi_partials_count(w.numel(), k), dtype=F64, device=w.device)
+        n2 = torch.zeros(1, dtype=F64, device=w.device)
+        multi_axpy(V, k, coef, w, part, n2, subtract=bool(subtract))
+        return n2
+
+    lib.impl("multi_dot", op_multi_dot, "CUDA")
+    lib.impl("multi_axpy_", op_multi_axpy_, "CUDA")
     register_torch_ops._lib = lib        # keep alive
     _registered = True

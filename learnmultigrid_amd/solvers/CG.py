@@ -27,6 +27,7 @@ import torch
 from .. import ops
 from ..hierarchy import line_config
 from ..ops import F64
+from ._precond import make_apply
 from .Solver import IterativeSolver, on_device
 
 
@@ -63,28 +64,9 @@ class CG(IterativeSolver):
         self.residual = math.sqrt(s.item())
         track = [self.residual]
         H = preconditioner
-        if H is not None and precond_smoother == "Chebyshev":
-            H.prepare_smoother("Chebyshev")        # bounds and work vectors before the first application
-        if H is not None and precond_smoother == "Line":
-            H.prepare_smoother("Line", line_dir=precond_line_dir, line_order=precond_line_order)
-
-        def apply_M(src, dst):
-            if H is None:
-                ops.copy(src, dst)
-                return
-            fine = H.levels[0]
-            ops.copy(src, fine.b)
-            if precond_smoother == "GaussSeidel":
-                H.cycle("GaussSeidel", precond_steps, 1.0, x_is_zero=True, gs_sweep=("forward", "backward"),
-                        shape=precond_cycle_shape)
-            elif precond_smoother == "Chebyshev":
-                H.cycle("Chebyshev", precond_steps, 1.0, x_is_zero=True, shape=precond_cycle_shape)
-            elif precond_smoother == "Line":
-                H.cycle("Line", precond_steps, precond_omega, x_is_zero=True, shape=precond_cycle_shape)
-            else:
-                H.cycle("Jacobi", precond_steps, precond_omega, x_is_zero=True, shape=precond_cycle_shape)
-            ops.copy(fine.x, dst)
-
+        # forward sweeps before, backward sweeps after the coarse correction: the symmetric Gauss-Seidel cycle
+        apply_M = make_apply(H, precond_smoother, precond_steps, precond_omega, precond_cycle_shape, ("forward", "backward"),
+                             precond_line_dir, precond_line_order)
         z = torch.empty_like(x)
         apply_M(r, z)
         p = z.clone()

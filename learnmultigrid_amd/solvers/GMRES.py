@@ -1,0 +1,71 @@
+"""Restarted flexible GMRES -- the Krylov solver for what CG cannot take: operators that are not symmetric (the grid
+problems of problems.py keep their Dirichlet rows as identity rows and leave the columns alone) and preconditioners that
+are not symmetric operators (forward Gauss-Seidel on both sides of the coarse correction, the cycle the reference ships;
+F-cycles).  The reference has no such class; the conventions are those of CG: the initial residual is track_res[0], one
+entry per iteration after it, stop on ||r|| <= error.
+
+`preconditioner=Hierarchy` preconditions from the right with one cycle from a zero guess per iteration, with CG's
+keywords; `precond_cycle_shape` also takes "F", and `precond_gs_sweep` any sweep name or (pre, post) pair of
+Hierarchy.cycle (default forward / forward).  The iteration is krylov.fgmres: classical Gram-Schmidt applied twice in four
+fused launches and one device-to-host read per iteration; its residual estimate is the true residual norm in exact
+arithmetic, and the true norm is recomputed at the end of every cycle of `restart` iterations.  Memory: 2 restart + 1
+vectors for the bases, (2 restart + 4) 8 n bytes with x, b and the scratch."""
+import numpy as np
+import torch
+
+from .. import krylov, ops
+from ..hierarchy import cycle_children, gs_sweep_pair
+from ..ops import F64
+from ._precond import check_smoother, make_apply
+from .Solver import IterativeSolver, on_device
+
+
+def check_keywords(restart, max_vectors, precond_smoother, precond_cycle_shape, precond_gs_sweep, precond_line_dir,
+                   precond_line_order):
+    """The keyword checks of GMRES.solve (ValueError); returns the (pre, post) Gauss-Seidel directions.  max_vectors:
+    the most basis rows a Gram-Schmidt launch takes (ops.krylov_max_vectors()): a cycle holds restart + 1."""
+    if int(restart) != restart or restart < 1:
+        raise ValueError("restart must be an integer >= 1, got %r" % (restart,))
+    if restart >= max_vectors:
+        raise ValueError("restart must be < %d (the Gram-Schmidt kernels take %d basis vectors), got %r"
+                         % (max_vectors, max_vectors, restart))
+    check_smoother(precond_smoother, precond_line_dir, precond_line_order)
+    cycle_children(precond_cycle_shape)
+    return gs_sweep_pair(precond_gs_sweep)
+
+
+class GMRES(IterativeSolver):
+
+    def __init__(self, matrix, rhs, **kw):
+        super().__init__(matrix, rhs, **kw)
+        self._log("Selected GMRES")
+        self.label = "GMRES"
+
+    @on_device
+    def solve(self, max_iterations=1000, error=1e-08, initial_guess=None, *, restart=30, preconditioner=None,
+              precond_steps=2, precond_omega=0.8, precond_smoother="Jacobi", precond_cycle_shape="V",
+              precond_gs_sweep="forward", precond_line_dir="xy", precond_line_order="zebra"):
+        pair = check_keywords(restart, ops.krylov_max_vectors(), precond_smoother, precond_cycle_shape, precond_gs_sweep,
+                              precond_line_dir, precond_line_order)
+        A = self._device_matrix()
+        A.pack()
+        n = self.dim
+        dev = self._device
+        b = self._to_device(self.rhs)
+        x = torch.zeros(n, dtype=F64, device=dev) if initial_guess is None else self._to_device(initial_guess)
+        r = torch.empty_like(x)
+        H = preconditioner
+        apply_M = None
+        if H is not None:
+            apply_M = make_apply(H, precond_smoother, precond_steps, precond_omega, precond_cycle_shape, pair,
+                                 precond_line_dir, precond_line_order)
+        track, self.iterations = krylov.fgmres(ops, A, b, x, apply_M, restart=int(restart), max_iterations=max_iterations,
+                                               error=error, residual_out=r)
+        if track[-1] <= error:
+            self._log("Reached convergence")
+        if H is not None and precond_smoother == "GaussSeidel":
+            H.check_smoothers()            # a timed-out wavefront band raises instead of leaving a wrong solution
+        self.residual = track[-1]
+        self.solution = self._column(x)
+        self.residual_vector = self._column(r)
+        self.track_res = np.array(track, dtype=float).reshape(-1, 1)

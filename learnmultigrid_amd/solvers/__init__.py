@@ -3,7 +3,8 @@ from .Solver import Solver, DirectSolver, IterativeSolver
 from .Jacobi import Jacobi
 from .GaussSeidel import GaussSeidel
 from .CG import CG
+from .GMRES import GMRES
 from .Multigrid import Multigrid, GeometricMG, SemiGeometricMG, HierarchyMG, NeuralMG
 
-__all__ = ["Solver", "DirectSolver", "IterativeSolver", "Jacobi", "GaussSeidel", "CG", "Multigrid",
+__all__ = ["Solver", "DirectSolver", "IterativeSolver", "Jacobi", "GaussSeidel", "CG", "GMRES", "Multigrid",
            "GeometricMG", "SemiGeometricMG", "HierarchyMG", "NeuralMG"]
