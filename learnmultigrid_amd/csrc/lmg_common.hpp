@@ -123,8 +123,9 @@ __device__ __forceinline__ double lmg_block_sum(double v, double *s_red)
 // CTRL 0x138 (wave_shr:1): lane i <- lane i-1; 0x130 (wave_shl:1): lane i <- lane i+1.  The lane without a source
 // (0 resp. 63) keeps `old`.  BOUND_CTRL is the caller's choice and stays visible at every call site: true makes the
 // instruction itself write 0 to that lane, so no register has to be cleared for it first (stencil_fused.hip,
-// dia_tile.hip); false is the plain old-value form that stencil_tile.hip and gs_wave.hip were built and measured
-// with -- changing it there changes their generated code -- and the only correct one with a fill value other than 0.
+// stencil_tile.hip, dia_tile.hip: two v_mov less per shift of a double); false is the plain old-value form that
+// gs_wave.hip was built and measured with -- changing it there changes its generated code -- and the only correct one
+// with a fill value other than 0.
 template <int CTRL, bool BOUND_CTRL>
 __device__ __forceinline__ double lmg_dpp_shift(double old, double src)
 {

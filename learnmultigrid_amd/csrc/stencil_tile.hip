@@ -12,6 +12,17 @@
 // multiply and add, omega * (rdiag * r)), so every value is bit-identical to the separate launches; as in
 // stencil_fused.hip everything is a LINEAR index i = line * W + column, a column outside [0, W) being the linear
 // neighbour in the adjacent line.
+// The prologue REQUESTS, THEN CONSUMES: every global load a thread makes before the first barrier -- its lines of x, b and
+// pattern ids, with a transfer the ids of P / R and the coarse windows, and its element of every table the workgroup
+// stages -- is issued first, outside any branch, from an address that is valid whatever the element turns out to be
+// (clamped indices; the diagonal of pattern i at i * 9 + 4 whatever its mask says); only behind the last of them does
+// anything look at a result (the `ok` selects, the reciprocals, the hot-pattern tests, the LDS writes).  gfx950 counts
+// loads in ONE in-order counter (vmcnt): written as `ok ? a.b[j] : 0.0` and as load-then-store staging loops, the
+// prologue was a chain of seven dependent round trips per workgroup -- a wait per line, one per table loop, two in the
+// reciprocal loop -- which a level of one or two workgroups per CU cannot hide; now it is one.  The same rule, for the
+// same reason, governs the lines of stencil_fused.hip (see `struct Line` there).  What remains behind the wait: the row of
+// P of an element without the usual pair (waves of the usual pair skip it), the tail of a table of more than
+// kBlock / 9 patterns, and the further lines of the kernels that cannot hold all their lines' windows in 64 registers.
 // (Tried: two columns per lane, 128-column tiles -- half the per-element overhead on paper, slower in practice: 9-point
 // 2049^2 61.5 / 48.0 us against 49.6 / 41.4 us for 3 sweeps + residual / 3 sweeps; twice the LDS per tile, half the waves.)
 #include "lmg_common.hpp"
@@ -80,11 +91,21 @@ struct TArgs {
 // with the coefficients in scalar registers and d of the elements a lane owns in its registers from sweep to sweep (a
 // lane computes the same elements in every sweep, halo included, so d never travels).  The row sums, the transfers and
 // the residual are those of the Jacobi pass; degree 1 is the Jacobi sweep with omega = c_0, bit for bit.
+// Waves per SIMD a kernel is held to; 8 means at most 64 VGPRs.
+//  - 16-wave workgroups, so that two of them share a CU -- the variants with the restriction had 65 - 67; the 64-line
+//    turnaround, four lines per wave, needs 76 / 89 and spills under that bound.
+//  - The 16-line restricting pass with hot transfers from a non-zero iterate: it had 57 registers while its prologue was a
+//    chain of branches; with the straight-line prologue the scheduler, left to itself, spends 67 - 71 on its sweeps.
+constexpr int tile_min_waves(int RR, int RBV, bool ZERO, bool PROL, bool REST, bool HX, bool CHEB)
+{
+    if (RR / RBV == 16 && (!PROL || HX) && !(PROL && REST && RBV == 4)) return 8;
+    if (RR == 16 && REST && HX && !PROL && !ZERO && !CHEB) return 8;
+    return 1;
+}
+
 template <int S, unsigned UM, bool RESID, bool ZERO, int RR, bool PROL = false, bool REST = false, int RBV = kRB, bool HX = false,
           bool CHEB = false>
-// (16-wave workgroups: at most 64 VGPRs, so that two of them share a CU -- the variants with the restriction had 65 - 67;
-// the 64-line turnaround, four lines per wave, needs 76 / 89 and spills under that bound)
-__global__ void __launch_bounds__(RR / RBV * LMG_WAVE, (RR / RBV == 16 && (!PROL || HX) && !(PROL && REST && RBV == 4)) ? 8 : 1)
+__global__ void __launch_bounds__(RR / RBV * LMG_WAVE, tile_min_waves(RR, RBV, ZERO, PROL, REST, HX, CHEB))
 stencil_tile_kernel(TArgs a)
 {
     // PROL && REST: the turnaround of a repeated level visit -- the post-smoothing pass of visit k (correction, then
@@ -117,35 +138,58 @@ stencil_tile_kernel(TArgs a)
     constexpr bool DIAG = (UM & kMaskCorners) != 0;
     const int rb0 = wave * RB;
 
-    // ---- the wave's lines are requested first, the pattern table is staged while they are in flight -------------
-    double lx[RB], bk[RB];
-    int pk[RB];                                                   // pattern id | 0x100 where the element is a row of the matrix
-    double le[(PROL && !HX) ? RB : 1][4];                         // PROL: the 2 x 2 coarse window of every element
-    int lq[PROL ? RB : 1];                                        //       and its pattern id in P
-    int lr[(REST && !HX) ? RB : 1];                               // REST: the id of R's row | 0x100 where the element has one
+    // ---- request: every global load of the prologue, from addresses that are valid whatever the element is ----------
+    // (the rule and its reason: head of this file)
+    struct Raw {                                                  // one element of a wave line as it comes out of memory
+        double x, b;
+        int pid, ppid, rpid;
+        d2u e01, e23;                                             // PROL: the 2 x 2 coarse window, two 16-byte loads
+    };
+    Raw raw[RB];
+    bool ok[RB];
+    // PROL: bit 0 / 1: the first / second load of the window starts where the window does, bit 2 / 3: parity of the
+    // element's own line / column -- one register per line instead of the 64-bit indices they come from
+    int wf[PROL ? RB : 1];
+    bool crow[(REST && !HX) ? RB : 1];                            // REST: the element carries a row of R
     // REST with HX: this thread's coarse node -- line t >> 5, column t & 31 of the even nodes of the inner part
     int rq = 0, rrow = H, rcol = H;
-    bool rown = false;
+    bool rown = false, rhas = false;
     if (REST && HX) {
         const int ye0 = (y0 + H + 1) & ~1, xe0 = (c0 + H + 1) & ~1;   // (y0 + H, c0 + H >= 0)
         const int yf = ye0 + 2 * (t >> 5), xf = xe0 + 2 * (t & 31);
         rown = yf < y0 + RR - H && yf < a.lines && xf < c0 + kCols - H && xf < W;
         const int64_t jc = (int64_t)(yf >> 1) * a.Wc + (xf >> 1);
-        rq = (rown && jc < a.nc) ? (int)a.rpid[jc] : 0;
+        rhas = rown && jc < a.nc;
+        rq = (int)a.rpid[rhas ? jc : 0];
         rrow = rown ? yf - y0 : H;
         rcol = rown ? xf - c0 : H;
     }
+    // PROL with HX: the usual pair of P as values in scalar registers (a select between two kernel arguments that the
+    // compiler can still see as such becomes a load from the argument block, indexed by the lane: a round trip)
+    int phot[2] = {-1, -1};
+    double phv[9] = {};
+    if (PROL && HX) {
 #pragma unroll
-    for (int k = 0; k < RB; ++k) {
+        for (int s = 0; s < 2; ++s) {
+            phot[s] = a.phot[s];
+            asm volatile("" : "+s"(phot[s]));
+        }
+#pragma unroll
+        for (int s = 0; s < 9; ++s) {
+            phv[s] = a.phv[s];
+            asm volatile("" : "+s"(phv[s]));
+        }
+    }
+    auto request = [&](int k) {
         const int y = y0 + rb0 + k;
         const int64_t i = (int64_t)y * W + c0 + lane;
         // (linear validity: an element outside the lines 0 .. lines - 1 whose index is a row -- (-1, W) is row 0, (lines, -1)
         // row n - 1 -- is that row, which operators with an entry across a line end read)
-        const bool ok = i >= 0 && i < n;
-        const int64_t j = ok ? i : 0;
-        lx[k] = (!ZERO && ok) ? a.x[j] : 0.0;
-        bk[k] = ok ? a.b[j] : 0.0;
-        pk[k] = ok ? ((int)a.pid[j] | 0x100) : 0;
+        ok[k] = i >= 0 && i < n;
+        const int64_t j = ok[k] ? i : 0;
+        raw[k].x = ZERO ? 0.0 : a.x[j];
+        raw[k].b = a.b[j];
+        raw[k].pid = (int)a.pid[j];
         if (PROL) {
             // the element is row j of P whatever its place in the tile (a column outside [0, W) is an element of the
             // adjacent line): its own line and column decide the window.  On grids at least two tiles wide one step to
@@ -160,13 +204,95 @@ stencil_tile_kernel(TArgs a)
                 xx = (int)((unsigned)j - (unsigned)yy * (unsigned)a.W);
             }
             const int64_t base = (int64_t)(yy >> 1) * a.Wc + (xx >> 1);
-            lq[k] = ok ? (int)a.ppid[j] : 0;
+            raw[k].ppid = (int)a.ppid[j];
             // slots 0, 1 and 2, 3 are neighbours in memory: two 16-byte loads (8-byte aligned is enough); slots a
             // pattern does not have may point anywhere inside the vector
-            const int64_t b0 = ok ? min(base, (int64_t)a.nc - 2) : 0, b1 = ok ? min(base + a.Wc, (int64_t)a.nc - 2) : 0;
-            const d2u e01 = *reinterpret_cast<const d2u *>(a.ec + b0), e23 = *reinterpret_cast<const d2u *>(a.ec + b1);
+            const int64_t b0 = ok[k] ? min(base, (int64_t)a.nc - 2) : 0, b1 = ok[k] ? min(base + a.Wc, (int64_t)a.nc - 2) : 0;
+            raw[k].e01 = *reinterpret_cast<const d2u *>(a.ec + b0);
+            raw[k].e23 = *reinterpret_cast<const d2u *>(a.ec + b1);
+            wf[k] = (b0 == base ? 1 : 0) | (b1 == base + a.Wc ? 2 : 0) | ((yy & 1) << 2) | ((xx & 1) << 3);
+        }
+        if (REST && !HX) {
+            // elements on (even line, even column) of the grid carry a row of R
+            const int c = c0 + lane;
+            crow[k] = ok[k] && !(y & 1) && !(c & 1) && c >= 0 && c < W;
+            const int64_t jc = (int64_t)(y >> 1) * a.Wc + (c >> 1);
+            raw[k].rpid = (int)a.rpid[(crow[k] && jc < a.nc) ? jc : 0];
+        }
+    };
+    // The loaded values pass through empty asm statements: a load cannot sink into a branch behind one, and no use can
+    // rise above it.  The last request comes first, so that the one wait stands in front of it.
+    auto arrived = [&](int k) {
+        if (PROL)
+            asm volatile("" : "+v"(raw[k].ppid), "+v"(raw[k].e01.a), "+v"(raw[k].e01.b), "+v"(raw[k].e23.a), "+v"(raw[k].e23.b),
+                              "+v"(wf[k]));
+        if (REST && !HX) asm volatile("" : "+v"(raw[k].rpid));
+        if (!ZERO) asm volatile("" : "+v"(raw[k].x));
+        asm volatile("" : "+v"(raw[k].b), "+v"(raw[k].pid));
+    };
+    // four lines with their windows in flight are 56 registers: those kernels ask for their lines one at a time
+    constexpr int RG = (PROL && (RB > 2 || REST)) ? 1 : RB;
+    static_assert(RB % RG == 0, "whole groups of lines");
+#pragma unroll
+    for (int k = 0; k < RG; ++k) request(k);
+    // this thread's element of every table the workgroup stages (a block is at least as long as any table but the two
+    // with nine values per pattern: their tail, if there is one, follows the consume step)
+    static_assert(kBlock >= kMaxPat * 4, "one element of the short tables per thread");
+    const int tv_n = a.npat * 9, tr_n = REST ? a.rp_npat * 9 : 1, tp_n = (PROL && !HX) ? a.pp_npat * 4 : 1;
+    const int tm_i = min(t, a.npat - 1);
+    double raw_sv = a.st_val[min(t, tv_n - 1)];                   // (staged in place: see lmg_common.hpp)
+    int raw_sm = a.st_mask[tm_i];
+    double raw_sd = a.st_val[tm_i * 9 + 4];                       // the diagonal: inside the table whatever the mask says
+    double raw_rv = 0.0, raw_pv = 0.0;
+    int raw_rm = 0, raw_pm = 0;
+    if (REST) {
+        raw_rv = a.rp_val[min(t, tr_n - 1)];
+        raw_rm = a.rp_mask[min(t, a.rp_npat - 1)];
+    }
+    if (PROL && !HX) {
+        raw_pv = a.pp_val[min(t, tp_n - 1)];
+        raw_pm = a.pp_mask[min(t, a.pp_npat - 1)];
+    }
+    // (what needs no load goes here, behind the requests)
+    for (int i = t; i < 2 * RR; i += kBlock) {                    // guard columns of both iterate buffers
+        const int r = i >> 1, g = (i & 1) ? kLS - 1 : 0;
+        s_x[0][r * kLS + g] = 0.0;
+        s_x[1][r * kLS + g] = 0.0;
+    }
+
+    // ---- consume: nothing above this line uses a loaded value --------------------------------------------------------
+    if (PROL && !HX) asm volatile("" : "+v"(raw_pv), "+v"(raw_pm));
+    if (REST) asm volatile("" : "+v"(raw_rv), "+v"(raw_rm));
+    asm volatile("" : "+v"(raw_sv), "+v"(raw_sm), "+v"(raw_sd));
+#pragma unroll
+    for (int k = RG - 1; k >= 0; --k) arrived(k);
+    if (REST && HX) asm volatile("" : "+v"(rq));
+    // (the tables' copies first: their registers are free before the lines need theirs; the reciprocals last, when the
+    // lines' are free)
+    if (t < tv_n) s_val[t] = raw_sv;
+    if (REST) {
+        if (t < tr_n) s_rv[t] = raw_rv;
+        if (t < a.rp_npat) s_rm[t] = raw_rm;
+    }
+    if (PROL && !HX) {
+        if (t < tp_n) s_pv[t] = raw_pv;
+        if (t < a.pp_npat) s_pm[t] = raw_pm;
+    }
+    double lx[RB], bk[RB];
+    int pk[RB];                                                   // pattern id | 0x100 where the element is a row of the matrix
+    double le[(PROL && !HX) ? RB : 1][4];                         // PROL: the 2 x 2 coarse window of every element
+    int lq[PROL ? RB : 1];                                        //       and its pattern id in P
+    int lr[(REST && !HX) ? RB : 1];                               // REST: the id of R's row | 0x100 where the element has one
+    if (REST && HX) rq = rhas ? (rq & 0xff) : 0;
+    auto consume = [&](int k) {
+        lx[k] = (!ZERO && ok[k]) ? raw[k].x : 0.0;
+        bk[k] = ok[k] ? raw[k].b : 0.0;
+        pk[k] = ok[k] ? ((raw[k].pid & 0xff) | 0x100) : 0;  // (& 0xff: behind the asm statement a byte is any int)
+        if (PROL) {
+            lq[k] = ok[k] ? (raw[k].ppid & 0xff) : 0;
+            const d2u e01 = raw[k].e01, e23 = raw[k].e23;
             // (a window clamped at the end of the vector starts one element early: its first slot is the second value)
-            const double w0 = b0 == base ? e01.a : e01.b, w1 = e01.b, w2 = b1 == base + a.Wc ? e23.a : e23.b, w3 = e23.b;
+            const double w0 = (wf[k] & 1) ? e01.a : e01.b, w1 = e01.b, w2 = (wf[k] & 2) ? e23.a : e23.b, w3 = e23.b;
             if (!HX) {
                 le[k][0] = w0;
                 le[k][1] = w1;
@@ -174,21 +300,26 @@ stencil_tile_kernel(TArgs a)
                 le[k][3] = w3;
             } else {
                 // x + P e now: the sums of lmg_rpat_sweep_grid(SPMV, alpha = 1, beta = 1) in the same order
-                const int yl = yy & 1, xl = xx & 1;
-                const int hp = a.phot[yl];
-                const bool hotk = !ok || (hp >= 0 && lq[k] == ((xl ? hp >> 8 : hp) & 0xff));
+                const int yl = (wf[k] >> 2) & 1, xl = (wf[k] >> 3) & 1;
+                // (read first, selected after: a select between two reads turns into one indexed read)
+                const int h0 = phot[0], h1 = phot[1];
+                const double p0 = phv[0], p1 = phv[1], p2 = phv[2], p3 = phv[3], p4 = phv[4], p5 = phv[5], p6 = phv[6], p7 = phv[7],
+                             p8 = phv[8];
+                const int hp = yl ? h1 : h0;
+                const bool hotk = !ok[k] || (hp >= 0 && lq[k] == ((xl ? hp >> 8 : hp) & 0xff));
                 double acc = 0.0;
                 if (__all(hotk)) {                                // wave-uniform: the usual pair, slots 0 (1) (2) (3)
-                    const double v0 = yl ? (xl ? a.phv[5] : a.phv[3]) : (xl ? a.phv[1] : a.phv[0]);
-                    const double v1 = yl ? a.phv[6] : a.phv[2], v2 = xl ? a.phv[7] : a.phv[4];
+                    const double v0 = yl ? (xl ? p5 : p3) : (xl ? p1 : p0);
+                    const double v1 = yl ? p6 : p2, v2 = xl ? p7 : p4;
                     acc = acc + v0 * w0;
                     double tv = acc + v1 * w1;
                     acc = xl ? tv : acc;
                     tv = acc + v2 * w2;
                     acc = yl ? tv : acc;
-                    tv = acc + a.phv[8] * w3;
+                    tv = acc + p8 * w3;
                     acc = (xl & yl) ? tv : acc;
                 } else {
+                    // (the one round trip left behind the wait: P's own row, which waves of the usual pair never ask for)
                     const int q = lq[k], m = a.pp_mask[q];
                     const double w[4] = {w0, w1, w2, w3};
 #pragma unroll
@@ -200,29 +331,31 @@ stencil_tile_kernel(TArgs a)
                 lx[k] = (pk[k] >> 8) ? lx[k] + acc : 0.0;
             }
         }
-        if (REST && !HX) {
-            // elements on (even line, even column) of the grid carry a row of R
-            const int c = c0 + lane;
-            const bool crow = ok && !(y & 1) && !(c & 1) && c >= 0 && c < W;
-            const int64_t jc = (int64_t)(y >> 1) * a.Wc + (c >> 1);
-            lr[k] = crow ? ((int)a.rpid[jc < a.nc ? jc : 0] | 0x100) : 0;
-        }
+        if (REST && !HX) lr[k] = crow[k] ? ((raw[k].rpid & 0xff) | 0x100) : 0;
+    };
+#pragma unroll
+    for (int k = 0; k < RG; ++k) consume(k);
+#pragma unroll
+    for (int g = RG; g < RB; g += RG) {                           // (the remaining groups: a round trip each)
+#pragma unroll
+        for (int k = g; k < g + RG; ++k) request(k);
+#pragma unroll
+        for (int k = g + RG - 1; k >= g; --k) arrived(k);
+#pragma unroll
+        for (int k = g; k < g + RG; ++k) consume(k);
     }
-    for (int i = t; i < a.npat * 9; i += kBlock) s_val[i] = a.st_val[i];      // (staged in place: see lmg_common.hpp)
-    for (int i = t; i < a.npat; i += kBlock) {
-        const int m = a.st_mask[i];
-        const double dg = (m & 16) ? a.st_val[i * 9 + 4] : 0.0;
-        s_rdiag[i] = dg != 0.0 ? 1.0 / dg : 0.0;
-        s_mask[i] = dg == 0.0 ? (m | (1 << 16)) : m;             // bit 16: no usable diagonal -> copy x
+    if (t < a.npat) {
+        const int m = raw_sm;
+        const double dg = (m & 16) ? raw_sd : 0.0;
+        s_rdiag[t] = dg != 0.0 ? 1.0 / dg : 0.0;
+        s_mask[t] = dg == 0.0 ? (m | (1 << 16)) : m;             // bit 16: no usable diagonal -> copy x
     }
-    for (int i = t; i < 2 * RR; i += kBlock) {                    // guard columns of both iterate buffers
-        const int r = i >> 1, g = (i & 1) ? kLS - 1 : 0;
-        s_x[0][r * kLS + g] = 0.0;
-        s_x[1][r * kLS + g] = 0.0;
+    if constexpr (kBlock < kMaxPat * 9) {                         // more than kBlock / 9 patterns: the tails
+        for (int i = t + kBlock; i < tv_n; i += kBlock) s_val[i] = a.st_val[i];
+        if (REST)
+            for (int i = t + kBlock; i < tr_n; i += kBlock) s_rv[i] = a.rp_val[i];
     }
     if (PROL && !HX) {
-        for (int i = t; i < a.pp_npat * 4; i += kBlock) s_pv[i] = a.pp_val[i];
-        for (int i = t; i < a.pp_npat; i += kBlock) s_pm[i] = a.pp_mask[i];
         __syncthreads();
         // x + P e: the sums of lmg_rpat_sweep_grid(SPMV, alpha = 1, beta = 1) in the same order
 #pragma unroll
@@ -236,10 +369,6 @@ stencil_tile_kernel(TArgs a)
             }
             lx[k] = (pk[k] >> 8) ? lx[k] + acc : 0.0;
         }
-    }
-    if (REST) {
-        for (int i = t; i < a.rp_npat * 9; i += kBlock) s_rv[i] = a.rp_val[i];
-        for (int i = t; i < a.rp_npat; i += kBlock) s_rm[i] = a.rp_mask[i];
     }
     const int hot = a.hot >= 0 ? (a.hot | 0x100) : -1;
     bool mine = true;
@@ -267,8 +396,8 @@ stencil_tile_kernel(TArgs a)
     auto line = [&](const double *src, int r, bool sides) -> Win {
         Win w;
         w.c = src[r * kLS + 1 + lane];
-        w.m = sides ? dpp_lower<false>(w.c) : 0.0;
-        w.p = sides ? dpp_upper<false>(w.c) : 0.0;
+        w.m = sides ? dpp_lower<true>(w.c) : 0.0;
+        w.p = sides ? dpp_upper<true>(w.c) : 0.0;
         return w;
     };
     // A x of the centre line of (u, c, d) for this lane, slot order = column order
