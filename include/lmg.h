@@ -327,6 +327,20 @@ int lmg_dia_smooth(int64_t n, int32_t line_stride, uint32_t union_mask, const do
 int lmg_dia_cheby(int64_t n, int32_t line_stride, uint32_t union_mask, const double *d_dia, int degree,
                   const double *h_coef, const double *d_x_in, const double *d_b, double *d_x_out, double *d_r_out,
                   void *stream);
+/* The same three with fp32 slot arrays (a cycle used as a preconditioner: 4 B per slot and row).  The twin then IS the
+ * matrix A32 = double(float(A)), value by value: a value is widened when it is loaded and everything after that -- products,
+ * summation order, the diagonal -- is the fp64 pass, so the outputs have the bits of the fp64 entry points on a twin of A32.
+ * Vectors and accumulation stay fp64.  lmg_dia_fill_f32 also raises bit 1 of *d_mismatch (|= 2) when a stored value other
+ * than 0 is not finite or rounds to +-inf, a subnormal or zero: rounding must not change what an entry is, the caller then
+ * keeps the fp64 twin.  Same argument checks and status codes as the fp64 forms. */
+int lmg_dia_fill_f32(int64_t n, int32_t line_stride, const int32_t *d_rowptr, const int32_t *d_colidx, const double *d_vals,
+                     uint32_t union_mask, float *d_dia, int32_t *d_mismatch, uint32_t *d_mask_out, void *stream);
+int lmg_dia_smooth_f32(int64_t n, int32_t line_stride, uint32_t union_mask, const float *d_dia, int sweeps,
+                       const double *d_x_in, const double *d_b, double omega, double *d_x_out, double *d_r_out,
+                       void *stream);
+int lmg_dia_cheby_f32(int64_t n, int32_t line_stride, uint32_t union_mask, const float *d_dia, int degree,
+                      const double *h_coef, const double *d_x_in, const double *d_b, double *d_x_out, double *d_r_out,
+                      void *stream);
 
 /* The same pass with the coarse-grid correction folded in (Multigrid.py:115 + :121 in one pass):
  *     x_out = J^sweeps(x_in + P e_coarse)
@@ -392,6 +406,17 @@ int lmg_sell_slice_info(int64_t n, const int32_t *d_rowptr, const int32_t *d_col
 int lmg_sell_fill(int64_t n, const int32_t *d_rowptr, const int32_t *d_colidx, const double *d_vals,
                   const int64_t *d_slice_base, const int32_t *d_slice_cmin, int colmode, void *d_col_out,
                   double *d_val_out, void *stream);
+/* ... and with an fp32 value stream (6 B per entry with uint16 columns): the twin is A32 = double(float(A)), a value is
+ * widened when loaded, the rest is the fp64 sweep -- same bits as lmg_sell_sweep on a twin of A32.  lmg_sell_fill_f32 rounds
+ * the values and sets *d_flag |= 1 (required, zeroed by the caller) when a stored value other than 0 is not finite or
+ * rounds to +-inf, a subnormal or zero; the caller then keeps fp64 values.  Same checks and status codes otherwise. */
+int lmg_sell_sweep_f32(int mode, int64_t n, const int64_t *d_slice_base, const int32_t *d_slice_len,
+                       const int32_t *d_slice_cmin, const int32_t *d_rowlen, const void *d_col, int colmode,
+                       const float *d_val, int32_t max_len, const double *d_x, const double *d_b, double *d_out,
+                       double alpha, double beta, double *d_partials, double *d_norm2, void *stream);
+int lmg_sell_fill_f32(int64_t n, const int32_t *d_rowptr, const int32_t *d_colidx, const double *d_vals,
+                      const int64_t *d_slice_base, const int32_t *d_slice_cmin, int colmode, void *d_col_out,
+                      float *d_val_out, int32_t *d_flag, void *stream);
 
 /* ---- building the packed twin (setup) ----------------------------------------------
  * One streaming pass each; learnmultigrid_amd/ops.py PackedCSR.from_csr is the calling sequence.

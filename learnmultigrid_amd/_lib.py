@@ -66,6 +66,9 @@ SIGNATURES = {
     "lmg_dia_fill": (_c.c_int, [_i64, _i32, _p, _p, _p, _c.c_uint32, _p, _p, _p, _p]),
     "lmg_dia_smooth": (_c.c_int, [_i64, _i32, _c.c_uint32, _p, _c.c_int, _p, _p, _f64, _p, _p, _p]),
     "lmg_dia_cheby": (_c.c_int, [_i64, _i32, _c.c_uint32, _p, _c.c_int, _p, _p, _p, _p, _p, _p]),
+    "lmg_dia_fill_f32": (_c.c_int, [_i64, _i32, _p, _p, _p, _c.c_uint32, _p, _p, _p, _p]),
+    "lmg_dia_smooth_f32": (_c.c_int, [_i64, _i32, _c.c_uint32, _p, _c.c_int, _p, _p, _f64, _p, _p, _p]),
+    "lmg_dia_cheby_f32": (_c.c_int, [_i64, _i32, _c.c_uint32, _p, _c.c_int, _p, _p, _p, _p, _p, _p]),
     "lmg_stencil_smooth_prolong_supported": (_c.c_int, [_c.c_uint32]),
     "lmg_stencil_smooth_prolong": (_c.c_int, [_i64, _i32, _p, _i32, _p, _p, _c.c_uint32, _i32, _p, _c.c_int, _p, _p, _f64, _p,
                                               _i64, _i32, _p, _p, _i32, _p, _p, _p, _p, _p]),
@@ -74,7 +77,9 @@ SIGNATURES = {
     "lmg_sell_sweep": (_c.c_int, [_c.c_int, _i64, _p, _p, _p, _p, _p, _c.c_int, _p, _i32, _p, _p, _p, _f64, _f64, _p, _p, _p]),
     "lmg_sell_slice_info": (_c.c_int, [_i64, _p, _p, _p, _p, _p, _p]),
     "lmg_sell_fill": (_c.c_int, [_i64, _p, _p, _p, _p, _p, _c.c_int, _p, _p, _p]),
-    "lmg_pcsr_tile_colrange": (_c.c_int, [_i64, _i32, _p, _p, _p, _p, _p]),
+    "lmg_sell_sweep_f32": (_c.c_int, [_c.c_int, _i64, _p, _p, _p, _p, _p, _c.c_int, _p, _i32, _p, _p, _p, _f64, _f64, _p, _p, _p]),
+    "lmg_sell_fill_f32": (_c.c_int, [_i64, _p, _p, _p, _p, _p, _c.c_int, _p, _p, _p, _p]),
+    "lmg_pcsr_tile_colrange":(_c.c_int, [_i64, _i32, _p, _p, _p, _p, _p]),
     "lmg_pcsr_encode_cols16": (_c.c_int, [_i64, _i32, _p, _p, _p, _p, _p]),
     "lmg_value_set_collect": (_c.c_int, [_p, _i64, _p, _i32, _p, _p]),
     "lmg_value_set_insert": (_c.c_int, [_i64, _p, _p, _i64, _i32, _p, _p]),

@@ -16,6 +16,7 @@
 // The arithmetic per row and sweep is the sequence of the CSR kernels (entries in ascending column order = slot
 // order, separate multiply and add, omega * (rdiag * r)): bit-identical to them and to the CPU oracle.
 #include "lmg_common.hpp"
+#include <float.h>
 
 namespace {
 
@@ -25,7 +26,7 @@ constexpr int kLS = kCols + 2;                // LDS line stride: one guard colu
 struct DArgs {
     int n, W, lines;
     int tiles_x, tiles_y;
-    const double *dia;        // [nslots][n]
+    const void *dia;          // [nslots][n] of the kernel's VT: double, or float (widened when loaded)
     const double *x;          // may be NULL with ZERO
     const double *b;
     double *out;
@@ -42,9 +43,12 @@ template <unsigned UM> struct Slots {
 // CHEB: sweep k = 0 .. S - 1 is  d = a_k * d + c_k * (rd * (b - A x))  (k = 0: no add),  x = x + d,  the coefficients in
 // scalar registers, d of the lane's RB elements in registers from sweep to sweep; degree 1 is the Jacobi sweep with
 // omega = c_0, bit for bit.
-template <int S, unsigned UM, bool RESID, bool ZERO, int RR, int RB, bool CHEB = false>
+// VT float: the twin represents double(float(A)) value by value; everything after the load -- the diagonal included -- is
+// the fp64 pass on those values.
+template <int S, unsigned UM, bool RESID, bool ZERO, int RR, int RB, bool CHEB = false, typename VT = double>
 __global__ void __launch_bounds__(RR / RB * LMG_WAVE) dia_tile_kernel(DArgs a)
 {
+    const VT *dia = static_cast<const VT *>(a.dia);
     constexpr int H = S + (RESID ? 1 : 0) - (ZERO ? 1 : 0);
     constexpr int kWaves = RR / RB;
     constexpr int NS = Slots<UM>::count;
@@ -74,7 +78,7 @@ __global__ void __launch_bounds__(RR / RB * LMG_WAVE) dia_tile_kernel(DArgs a)
         lx[k] = (!ZERO && ok[k]) ? a.x[j] : 0.0;
         bk[k] = ok[k] ? a.b[j] : 0.0;
 #pragma unroll
-        for (int q = 0; q < NS; ++q) av[k][q] = ok[k] ? a.dia[(int64_t)q * n + j] : 0.0;
+        for (int q = 0; q < NS; ++q) av[k][q] = ok[k] ? (double)dia[(int64_t)q * n + j] : 0.0;
     }
     for (int i = t; i < 2 * RR; i += kWaves * LMG_WAVE) {         // guard columns of both iterate buffers
         const int r = i >> 1, g = (i & 1) ? kLS - 1 : 0;
@@ -183,12 +187,15 @@ __global__ void __launch_bounds__(RR / RB * LMG_WAVE) dia_tile_kernel(DArgs a)
 // DIA twin of a CSR matrix: dia[q][row] = value of the entry in slot number q of the union mask (ascending slots), 0.0
 // where the row has none.  One thread per row; an entry that is no 3x3 slot of stride W, or not in the union mask,
 // raises the mismatch flag (the caller then keeps the packed CSR).  probe != 0: only OR the slots into mask_out.
+// VT float: the values are rounded to fp32; bit 1 of the flag word is raised when a stored value other than 0 is not finite
+// or rounds to +-inf, a subnormal or zero (the caller then keeps fp64 values).
+template <typename VT>
 __global__ void __launch_bounds__(256) dia_fill_kernel(int64_t n, int W, const int *rowptr, const int *colidx, const double *vals,
-                                                       unsigned umask, double *dia, int *mismatch, unsigned *mask_out)
+                                                       unsigned umask, VT *dia, int *mismatch, unsigned *mask_out)
 {
     const int64_t stride = (int64_t)gridDim.x * 256;
     unsigned seen_all = 0;
-    bool bad = false;
+    bool bad = false, range = false;
     for (int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x; row < n; row += stride) {
         double v9[9];
 #pragma unroll
@@ -208,6 +215,10 @@ __global__ void __launch_bounds__(256) dia_fill_kernel(int64_t n, int W, const i
             }
             seen |= 1u << slot;
             const double v = vals ? vals[e] : 0.0;
+            if (sizeof(VT) == 4 && dia) {
+                const float m = fabsf((float)v);
+                range = range || (v != 0.0 && !(m >= FLT_MIN && m <= FLT_MAX));     // (NaN fails both comparisons)
+            }
 #pragma unroll
             for (int s = 0; s < 9; ++s)
                 if (s == slot) v9[s] = v;
@@ -219,19 +230,20 @@ __global__ void __launch_bounds__(256) dia_fill_kernel(int64_t n, int W, const i
 #pragma unroll
             for (int s = 0; s < 9; ++s) {
                 if ((umask >> s) & 1u) {
-                    dia[(int64_t)q * n + row] = v9[s];
+                    dia[(int64_t)q * n + row] = (VT)v9[s];
                     ++q;
                 }
             }
         }
     }
     if (bad) atomicOr(mismatch, 1);
+    if (range) atomicOr(mismatch, 2);
     if (mask_out && seen_all) atomicOr(mask_out, seen_all);
 }
 
 int g_dia_rows = 0;             // lines per tile: 0 = default, 32 or 64
 
-template <int S, unsigned UM, bool RESID, bool ZERO, int RR, int RB, bool CHEB = false>
+template <int S, unsigned UM, bool RESID, bool ZERO, int RR, int RB, bool CHEB, typename VT>
 int launch5(DArgs a, hipStream_t st)
 {
     constexpr int H = S + (RESID ? 1 : 0) - (ZERO ? 1 : 0);
@@ -239,23 +251,23 @@ int launch5(DArgs a, hipStream_t st)
     a.tiles_y = (a.lines + (RR - 2 * H) - 1) / (RR - 2 * H);
     const int64_t grid = (int64_t)a.tiles_x * a.tiles_y;
     if (grid > 0x7fffffff) return LMG_ERR_CAPACITY;
-    hipLaunchKernelGGL((dia_tile_kernel<S, UM, RESID, ZERO, RR, RB, CHEB>), dim3((unsigned)grid), dim3(RR / RB * LMG_WAVE), 0, st, a);
+    hipLaunchKernelGGL((dia_tile_kernel<S, UM, RESID, ZERO, RR, RB, CHEB, VT>), dim3((unsigned)grid), dim3(RR / RB * LMG_WAVE), 0, st, a);
     LMG_CHECK_LAUNCH();
     return LMG_OK;
 }
 
-template <int S, unsigned UM, bool RESID, bool ZERO, bool CHEB = false>
+template <int S, unsigned UM, bool RESID, bool ZERO, bool CHEB, typename VT>
 int launch4(DArgs a, hipStream_t st)
 {
     const int rr = g_dia_rows == 0 ? 32 : g_dia_rows;
-    if (rr == 64) return launch5<S, UM, RESID, ZERO, 64, 4, CHEB>(a, st);
-    return launch5<S, UM, RESID, ZERO, 32, 2, CHEB>(a, st);
+    if (rr == 64) return launch5<S, UM, RESID, ZERO, 64, 4, CHEB, VT>(a, st);
+    return launch5<S, UM, RESID, ZERO, 32, 2, CHEB, VT>(a, st);
 }
 
 // The operator and the vectors of a pass, and the coefficient table of a Chebyshev step (h_coef: as in stencil_tile.hip;
 // null: weighted Jacobi): the argument rules of lmg_dia_smooth and lmg_dia_cheby.  Returns 1 with `a` set, else the
 // status to hand back (LMG_OK: nothing to do).
-int dia_fill_args(DArgs &a, int64_t n, int32_t line_stride, const double *dia, const LmgSolve &v, const double *h_coef)
+int dia_fill_args(DArgs &a, int64_t n, int32_t line_stride, const void *dia, const LmgSolve &v, const double *h_coef)
 {
     if (n < 0 || n >= (1ll << 31) - 4096) return LMG_ERR_ARG;
     if (v.sweeps < 1 || v.sweeps > 3) return LMG_ERR_ARG;
@@ -279,8 +291,9 @@ int dia_fill_args(DArgs &a, int64_t n, int32_t line_stride, const double *dia, c
     return 1;
 }
 
-// (slot set, smoother, sweeps, residual, zero iterate) -> template arguments
-int dia_pass(int64_t n, int32_t line_stride, uint32_t union_mask, const double *dia, const LmgSolve &v, const double *h_coef,
+// (slot set, smoother, sweeps, residual, zero iterate) -> template arguments; VT: the type of the slot arrays
+template <typename VT>
+int dia_pass(int64_t n, int32_t line_stride, uint32_t union_mask, const VT *dia, const LmgSolve &v, const double *h_coef,
              void *stream)
 {
     DArgs a;
@@ -291,12 +304,27 @@ int dia_pass(int64_t n, int32_t line_stride, uint32_t union_mask, const double *
             return lmg_with_sweeps<1, 3>(v.sweeps, [&](auto s) {
                 return lmg_with_flag(v.r_out != nullptr, [&](auto r) {
                     return lmg_with_flag(v.x_in == nullptr, [&](auto z) {
-                        return launch4<LMG_CT(s), LMG_CT(m), LMG_CT(r), LMG_CT(z), LMG_CT(ch)>(a, lmg_stream(stream));
+                        return launch4<LMG_CT(s), LMG_CT(m), LMG_CT(r), LMG_CT(z), LMG_CT(ch), VT>(a, lmg_stream(stream));
                     });
                 });
             });
         });
     });
+}
+
+template <typename VT>
+int dia_fill(int64_t n, int32_t line_stride, const int32_t *rowptr, const int32_t *colidx, const double *vals,
+             uint32_t union_mask, VT *dia, int32_t *mismatch, uint32_t *mask_out, void *stream)
+{
+    if (n < 0 || line_stride < 3 || (union_mask & ~kMask9) || (n > 0 && (!rowptr || !colidx || !mismatch))) return LMG_ERR_ARG;
+    if (dia && !vals) return LMG_ERR_ARG;
+    if (n == 0) return LMG_OK;
+    int64_t grid = (n + 255) / 256;
+    if (grid > 256 * 32) grid = 256 * 32;
+    hipLaunchKernelGGL(dia_fill_kernel<VT>, dim3((unsigned)grid), dim3(256), 0, lmg_stream(stream), n, (int)line_stride, rowptr,
+                       colidx, vals, union_mask, dia, mismatch, mask_out);
+    LMG_CHECK_LAUNCH();
+    return LMG_OK;
 }
 
 }  // namespace
@@ -316,28 +344,39 @@ int lmg_dia_smooth_supported(uint32_t union_mask)
 int lmg_dia_fill(int64_t n, int32_t line_stride, const int32_t *rowptr, const int32_t *colidx, const double *vals,
                  uint32_t union_mask, double *dia, int32_t *mismatch, uint32_t *mask_out, void *stream)
 {
-    if (n < 0 || line_stride < 3 || (union_mask & ~kMask9) || (n > 0 && (!rowptr || !colidx || !mismatch))) return LMG_ERR_ARG;
-    if (dia && !vals) return LMG_ERR_ARG;
-    if (n == 0) return LMG_OK;
-    int64_t grid = (n + 255) / 256;
-    if (grid > 256 * 32) grid = 256 * 32;
-    hipLaunchKernelGGL(dia_fill_kernel, dim3((unsigned)grid), dim3(256), 0, lmg_stream(stream), n, (int)line_stride, rowptr, colidx,
-                       vals, union_mask, dia, mismatch, mask_out);
-    LMG_CHECK_LAUNCH();
-    return LMG_OK;
+    return dia_fill<double>(n, line_stride, rowptr, colidx, vals, union_mask, dia, mismatch, mask_out, stream);
+}
+
+int lmg_dia_fill_f32(int64_t n, int32_t line_stride, const int32_t *rowptr, const int32_t *colidx, const double *vals,
+                     uint32_t union_mask, float *dia, int32_t *mismatch, uint32_t *mask_out, void *stream)
+{
+    return dia_fill<float>(n, line_stride, rowptr, colidx, vals, union_mask, dia, mismatch, mask_out, stream);
 }
 
 int lmg_dia_smooth(int64_t n, int32_t line_stride, uint32_t union_mask, const double *dia, int sweeps, const double *x_in,
                    const double *b, double omega, double *x_out, double *r_out, void *stream)
 {
-    return dia_pass(n, line_stride, union_mask, dia, {sweeps, x_in, b, omega, x_out, r_out}, nullptr, stream);
+    return dia_pass<double>(n, line_stride, union_mask, dia, {sweeps, x_in, b, omega, x_out, r_out}, nullptr, stream);
+}
+
+int lmg_dia_smooth_f32(int64_t n, int32_t line_stride, uint32_t union_mask, const float *dia, int sweeps, const double *x_in,
+                       const double *b, double omega, double *x_out, double *r_out, void *stream)
+{
+    return dia_pass<float>(n, line_stride, union_mask, dia, {sweeps, x_in, b, omega, x_out, r_out}, nullptr, stream);
 }
 
 int lmg_dia_cheby(int64_t n, int32_t line_stride, uint32_t union_mask, const double *dia, int degree, const double *h_coef,
                   const double *x_in, const double *b, double *x_out, double *r_out, void *stream)
 {
     if (degree < 1 || degree > 3 || !h_coef) return LMG_ERR_ARG;
-    return dia_pass(n, line_stride, union_mask, dia, {degree, x_in, b, h_coef[1], x_out, r_out}, h_coef, stream);
+    return dia_pass<double>(n, line_stride, union_mask, dia, {degree, x_in, b, h_coef[1], x_out, r_out}, h_coef, stream);
+}
+
+int lmg_dia_cheby_f32(int64_t n, int32_t line_stride, uint32_t union_mask, const float *dia, int degree, const double *h_coef,
+                      const double *x_in, const double *b, double *x_out, double *r_out, void *stream)
+{
+    if (degree < 1 || degree > 3 || !h_coef) return LMG_ERR_ARG;
+    return dia_pass<float>(n, line_stride, union_mask, dia, {degree, x_in, b, h_coef[1], x_out, r_out}, h_coef, stream);
 }
 
 }  // extern "C"

@@ -10,11 +10,12 @@
 //   entry j of row r is stored at  slice_base[s] + 64 j + (r mod 64)
 // so the wave that owns a slice reads entry j of all its 64 rows with ONE coalesced load per
 // stream (columns: uint16 relative to the slice's smallest column when every slice spans
-// < 65536 columns, else int32; values: raw fp64), straight into registers: no LDS, no barrier,
-// full occupancy.  Lane t still accumulates row t in storage order with separately rounded
+// < 65536 columns, else int32; values: raw fp64, or -- the _f32 entry points -- fp32 widened to fp64
+// when loaded), straight into registers: no LDS, no barrier, full occupancy.  Lane t still accumulates row t in storage order with separately rounded
 // products => bit-identical to the CSR kernels.  Padding costs (L_s - len) entries per row:
 // a few per cent for the near-uniform rows this format is used for.
 #include "lmg_common.hpp"
+#include <float.h>
 #include <limits.h>
 
 namespace {
@@ -32,7 +33,7 @@ struct SArgs {
     const int *slice_cmin;         // nslices: column base (COL16)
     const int *rowlen;             // n
     const void *col;
-    const double *val;
+    const void *val;               // VT of the kernel: double, or float (widened when loaded)
     const double *x;
     const double *b;
     double *out;
@@ -42,12 +43,14 @@ struct SArgs {
 
 // NT: the entry streams (columns, values) are read once per sweep: nontemporal loads keep them from evicting the
 // vector lines the gathers of x live on (L2)
-template <int MODE, bool COL16, int JU, bool NT = false>
+// VT float: the twin represents double(float(A)) value by value -- same products, same order, same diagonal
+template <int MODE, bool COL16, int JU, bool NT = false, typename VT = double>
 __global__ void __launch_bounds__(kBlock) sell_sweep_kernel(SArgs a)
 {
     __shared__ double s_red[kBlock / LMG_WAVE];
     typedef typename std::conditional<COL16, unsigned short, int>::type col_t;
     const col_t *col = static_cast<const col_t *>(a.col);
+    const VT *val = static_cast<const VT *>(a.val);
     const int lane = threadIdx.x & (LMG_WAVE - 1), wave = threadIdx.x / LMG_WAVE;
     // XCD-aware: XCD k (blockIdx mod 8) works on the k-th contiguous eighth of the slices
     const int blk = lmg_xcd_tile(a.blocks_per_xcd);
@@ -70,7 +73,7 @@ __global__ void __launch_bounds__(kBlock) sell_sweep_kernel(SArgs a)
                 const int j = (j0 + jj < slen) ? j0 + jj : slen - 1;      // padded storage: always readable
                 const long long e = base + (long long)j * LMG_WAVE;
                 c[jj] = cb + (int)(NT ? __builtin_nontemporal_load(col + e) : col[e]);
-                v[jj] = NT ? __builtin_nontemporal_load(a.val + e) : a.val[e];
+                v[jj] = (double)(NT ? __builtin_nontemporal_load(val + e) : val[e]);
             }
 #pragma unroll
             for (int jj = 0; jj < JU; ++jj) xv[jj] = a.x[(j0 + jj < len) ? c[jj] : 0];
@@ -144,12 +147,14 @@ __global__ void __launch_bounds__(kBlock) sell_slice_info_kernel(int64_t n, int6
     }
 }
 
-// lane = row: copies its entries to their padded positions (col_out may be null: values only)
-template <bool COL16>
+// lane = row: copies its entries to their padded positions (col_out may be null: values only).  VT float: the values are
+// rounded to fp32; *flag |= 1 when a stored value other than 0 is not finite or rounds to +-inf, a subnormal or zero
+// (rounding must not change what an entry is: the caller then keeps fp64 values)
+template <bool COL16, typename VT>
 __global__ void __launch_bounds__(kBlock) sell_fill_kernel(int64_t n, int64_t nslices, const int *__restrict__ rowptr,
                                                            const int *__restrict__ colidx, const double *__restrict__ vals,
                                                            const long long *__restrict__ slice_base,
-                                                           const int *__restrict__ cmin, void *col_out, double *val_out)
+                                                           const int *__restrict__ cmin, void *col_out, VT *val_out, int *flag)
 {
     typedef typename std::conditional<COL16, unsigned short, int>::type col_t;
     col_t *co = static_cast<col_t *>(col_out);
@@ -161,11 +166,19 @@ __global__ void __launch_bounds__(kBlock) sell_fill_kernel(int64_t n, int64_t ns
     const int s = rowptr[row], e = rowptr[row + 1];
     const long long base = slice_base[slice] + lane;
     const int cb = COL16 ? cmin[slice] : 0;
+    bool bad = false;
     for (int k = s; k < e; ++k) {
         const long long p = base + (long long)(k - s) * LMG_WAVE;
         if (co) co[p] = (col_t)(colidx[k] - cb);
-        val_out[p] = vals[k];
+        const double v = vals[k];
+        const VT w = (VT)v;
+        if (sizeof(VT) == 4) {
+            const float m = fabsf((float)w);
+            bad = bad || (v != 0.0 && !(m >= FLT_MIN && m <= FLT_MAX));     // (NaN fails both comparisons)
+        }
+        val_out[p] = w;
     }
+    if (bad) atomicOr(flag, 1);
 }
 
 // measured (tools/time_sell.py, Jacobi sweep): 2049^2 x 25 entries (1.05 GB) 0.264 -> 0.250 ms, 1025^2 x 49 (0.51 GB)
@@ -174,10 +187,11 @@ int g_sell_ju = 0;                        // entries of a row in flight: 0 = by 
 int g_sell_nt = -1;                       // -1: by size, 0: never, 1: always
 int64_t g_sell_nt_entries = 30000000;     // padded entries from which the streams no longer fit the 256 MB Infinity Cache
 
-template <int MODE, bool COL16>
+template <int MODE, bool COL16, typename VT>
 int launch(SArgs a, int max_len, hipStream_t st)
 {
-    // measured on MI355X (tools/tune_sweep.py --matrix L1|L2): see DESIGN.md
+    // measured on MI355X (tools/tune_sweep.py --matrix L1|L2): see DESIGN.md.  The choices below were measured on fp64 values
+    // and are kept as they are for fp32 values (sell_nt_entries counts entries, not bytes)
     const dim3 grid((unsigned)(a.blocks_per_xcd * 8)), block(kBlock);
     const bool nt = g_sell_nt == 1 || (g_sell_nt < 0 && (int64_t)a.n * max_len >= g_sell_nt_entries);
     // entries of a row in flight: the factor that leaves the fewest idle slots in the last trip over the longest row (25-entry
@@ -195,33 +209,23 @@ int launch(SArgs a, int max_len, hipStream_t st)
             }
         }
     }
-    if (max_len <= 12) hipLaunchKernelGGL((sell_sweep_kernel<MODE, COL16, 4>), grid, block, 0, st, a);
-    else if (ju == 5 && nt) hipLaunchKernelGGL((sell_sweep_kernel<MODE, COL16, 5, true>), grid, block, 0, st, a);
-    else if (ju == 5) hipLaunchKernelGGL((sell_sweep_kernel<MODE, COL16, 5>), grid, block, 0, st, a);
-    else if (ju == 7 && nt) hipLaunchKernelGGL((sell_sweep_kernel<MODE, COL16, 7, true>), grid, block, 0, st, a);
-    else if (ju == 7) hipLaunchKernelGGL((sell_sweep_kernel<MODE, COL16, 7>), grid, block, 0, st, a);
-    else if (ju == 10 && nt) hipLaunchKernelGGL((sell_sweep_kernel<MODE, COL16, 10, true>), grid, block, 0, st, a);
-    else if (ju == 10) hipLaunchKernelGGL((sell_sweep_kernel<MODE, COL16, 10>), grid, block, 0, st, a);
-    else if (nt) hipLaunchKernelGGL((sell_sweep_kernel<MODE, COL16, 8, true>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((sell_sweep_kernel<MODE, COL16, 8>), grid, block, 0, st, a);
+    if (max_len <= 12) hipLaunchKernelGGL((sell_sweep_kernel<MODE, COL16, 4, false, VT>), grid, block, 0, st, a);
+    else if (ju == 5 && nt) hipLaunchKernelGGL((sell_sweep_kernel<MODE, COL16, 5, true, VT>), grid, block, 0, st, a);
+    else if (ju == 5) hipLaunchKernelGGL((sell_sweep_kernel<MODE, COL16, 5, false, VT>), grid, block, 0, st, a);
+    else if (ju == 7 && nt) hipLaunchKernelGGL((sell_sweep_kernel<MODE, COL16, 7, true, VT>), grid, block, 0, st, a);
+    else if (ju == 7) hipLaunchKernelGGL((sell_sweep_kernel<MODE, COL16, 7, false, VT>), grid, block, 0, st, a);
+    else if (ju == 10 && nt) hipLaunchKernelGGL((sell_sweep_kernel<MODE, COL16, 10, true, VT>), grid, block, 0, st, a);
+    else if (ju == 10) hipLaunchKernelGGL((sell_sweep_kernel<MODE, COL16, 10, false, VT>), grid, block, 0, st, a);
+    else if (nt) hipLaunchKernelGGL((sell_sweep_kernel<MODE, COL16, 8, true, VT>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((sell_sweep_kernel<MODE, COL16, 8, false, VT>), grid, block, 0, st, a);
     LMG_CHECK_LAUNCH();
     return LMG_OK;
 }
 
-}  // namespace
-
-constexpr LmgTuneKey lmg_tune_sell[] = {
-    lmg_tune_range("sell_nt", &g_sell_nt, -1, 1),
-    lmg_tune_list("sell_ju", &g_sell_ju, 0, 5, 7, 8, 10),
-    kLmgTuneEnd,
-};
-
-extern "C" {
-
-int lmg_sell_sweep(int mode, int64_t n, const int64_t *slice_base, const int32_t *slice_len, const int32_t *slice_cmin,
-                   const int32_t *rowlen, const void *col, int colmode, const double *val, int32_t max_len,
-                   const double *x, const double *b, double *out, double alpha, double beta, double *partials,
-                   double *norm2, void *stream)
+template <typename VT>
+int sell_sweep(int mode, int64_t n, const int64_t *slice_base, const int32_t *slice_len, const int32_t *slice_cmin,
+               const int32_t *rowlen, const void *col, int colmode, const VT *val, int32_t max_len, const double *x,
+               const double *b, double *out, double alpha, double beta, double *partials, double *norm2, void *stream)
 {
     if (n < 0 || n >= INT32_MAX - 64 || (colmode != 0 && colmode != 1) || max_len < 0) return LMG_ERR_ARG;
     if (n == 0) return LMG_OK;
@@ -248,16 +252,67 @@ int lmg_sell_sweep(int mode, int64_t n, const int64_t *slice_base, const int32_t
     hipStream_t st = lmg_stream(stream);
     int rc;
     if (colmode == 0) {
-        rc = mode == MODE_RESIDUAL ? launch<MODE_RESIDUAL, true>(a, max_len, st)
-           : mode == MODE_JACOBI ? launch<MODE_JACOBI, true>(a, max_len, st) : launch<MODE_SPMV, true>(a, max_len, st);
+        rc = mode == MODE_RESIDUAL ? launch<MODE_RESIDUAL, true, VT>(a, max_len, st)
+           : mode == MODE_JACOBI ? launch<MODE_JACOBI, true, VT>(a, max_len, st) : launch<MODE_SPMV, true, VT>(a, max_len, st);
     } else {
-        rc = mode == MODE_RESIDUAL ? launch<MODE_RESIDUAL, false>(a, max_len, st)
-           : mode == MODE_JACOBI ? launch<MODE_JACOBI, false>(a, max_len, st) : launch<MODE_SPMV, false>(a, max_len, st);
+        rc = mode == MODE_RESIDUAL ? launch<MODE_RESIDUAL, false, VT>(a, max_len, st)
+           : mode == MODE_JACOBI ? launch<MODE_JACOBI, false, VT>(a, max_len, st) : launch<MODE_SPMV, false, VT>(a, max_len, st);
     }
     if (rc != LMG_OK) return rc;
     // blocks beyond nblocks (grid rounded up to a multiple of 8) write nothing: only nblocks partials exist
     if (mode == MODE_RESIDUAL && partials) return lmg_reduce_partials(partials, a.nblocks, norm2, st);
     return LMG_OK;
+}
+
+// flag: the range flag of the fp32 form (null for fp64 values, which the kernel then never touches)
+template <typename VT>
+int sell_fill(int64_t n, const int32_t *rowptr, const int32_t *colidx, const double *vals, const int64_t *slice_base,
+              const int32_t *slice_cmin, int colmode, void *col_out, VT *val_out, int32_t *flag, void *stream)
+{
+    if (n < 0 || (colmode != 0 && colmode != 1)) return LMG_ERR_ARG;
+    if (n == 0) return LMG_OK;
+    if (!rowptr || !vals || !slice_base || !val_out || (col_out && !colidx) || (colmode == 0 && !slice_cmin))
+        return LMG_ERR_ARG;
+    if (sizeof(VT) == 4 && !flag) return LMG_ERR_ARG;
+    const int64_t nslices = (n + LMG_WAVE - 1) / LMG_WAVE;
+    const unsigned grid = (unsigned)((nslices + kSlicesPerBlock - 1) / kSlicesPerBlock);
+    const long long *sb = reinterpret_cast<const long long *>(slice_base);
+    if (colmode == 0)
+        hipLaunchKernelGGL((sell_fill_kernel<true, VT>), dim3(grid), dim3(kBlock), 0, lmg_stream(stream), n, nslices, rowptr,
+                           colidx, vals, sb, slice_cmin, col_out, val_out, flag);
+    else
+        hipLaunchKernelGGL((sell_fill_kernel<false, VT>), dim3(grid), dim3(kBlock), 0, lmg_stream(stream), n, nslices, rowptr,
+                           colidx, vals, sb, slice_cmin, col_out, val_out, flag);
+    LMG_CHECK_LAUNCH();
+    return LMG_OK;
+}
+
+}  // namespace
+
+constexpr LmgTuneKey lmg_tune_sell[] = {
+    lmg_tune_range("sell_nt", &g_sell_nt, -1, 1),
+    lmg_tune_list("sell_ju", &g_sell_ju, 0, 5, 7, 8, 10),
+    kLmgTuneEnd,
+};
+
+extern "C" {
+
+int lmg_sell_sweep(int mode, int64_t n, const int64_t *slice_base, const int32_t *slice_len, const int32_t *slice_cmin,
+                   const int32_t *rowlen, const void *col, int colmode, const double *val, int32_t max_len,
+                   const double *x, const double *b, double *out, double alpha, double beta, double *partials,
+                   double *norm2, void *stream)
+{
+    return sell_sweep<double>(mode, n, slice_base, slice_len, slice_cmin, rowlen, col, colmode, val, max_len, x, b, out, alpha,
+                              beta, partials, norm2, stream);
+}
+
+int lmg_sell_sweep_f32(int mode, int64_t n, const int64_t *slice_base, const int32_t *slice_len, const int32_t *slice_cmin,
+                       const int32_t *rowlen, const void *col, int colmode, const float *val, int32_t max_len,
+                       const double *x, const double *b, double *out, double alpha, double beta, double *partials,
+                       double *norm2, void *stream)
+{
+    return sell_sweep<float>(mode, n, slice_base, slice_len, slice_cmin, rowlen, col, colmode, val, max_len, x, b, out, alpha,
+                             beta, partials, norm2, stream);
 }
 
 int lmg_sell_slice_info(int64_t n, const int32_t *rowptr, const int32_t *colidx, int32_t *slice_len, int32_t *cmin,
@@ -278,21 +333,14 @@ int lmg_sell_fill(int64_t n, const int32_t *rowptr, const int32_t *colidx, const
                   const int64_t *slice_base, const int32_t *slice_cmin, int colmode, void *col_out, double *val_out,
                   void *stream)
 {
-    if (n < 0 || (colmode != 0 && colmode != 1)) return LMG_ERR_ARG;
-    if (n == 0) return LMG_OK;
-    if (!rowptr || !vals || !slice_base || !val_out || (col_out && !colidx) || (colmode == 0 && !slice_cmin))
-        return LMG_ERR_ARG;
-    const int64_t nslices = (n + LMG_WAVE - 1) / LMG_WAVE;
-    const unsigned grid = (unsigned)((nslices + kSlicesPerBlock - 1) / kSlicesPerBlock);
-    const long long *sb = reinterpret_cast<const long long *>(slice_base);
-    if (colmode == 0)
-        hipLaunchKernelGGL(sell_fill_kernel<true>, dim3(grid), dim3(kBlock), 0, lmg_stream(stream), n, nslices, rowptr,
-                           colidx, vals, sb, slice_cmin, col_out, val_out);
-    else
-        hipLaunchKernelGGL(sell_fill_kernel<false>, dim3(grid), dim3(kBlock), 0, lmg_stream(stream), n, nslices, rowptr,
-                           colidx, vals, sb, slice_cmin, col_out, val_out);
-    LMG_CHECK_LAUNCH();
-    return LMG_OK;
+    return sell_fill<double>(n, rowptr, colidx, vals, slice_base, slice_cmin, colmode, col_out, val_out, nullptr, stream);
+}
+
+int lmg_sell_fill_f32(int64_t n, const int32_t *rowptr, const int32_t *colidx, const double *vals,
+                      const int64_t *slice_base, const int32_t *slice_cmin, int colmode, void *col_out, float *val_out,
+                      int32_t *flag, void *stream)
+{
+    return sell_fill<float>(n, rowptr, colidx, vals, slice_base, slice_cmin, colmode, col_out, val_out, flag, stream);
 }
 
 }  // extern "C"

@@ -23,7 +23,7 @@ import torch
 from . import ops
 from .coarse import make_coarse_solver
 from .ops import DeviceCSR, F64
-from .twins import DiaTwin, line_stride
+from .twins import DiaTwin, check_values, line_stride
 
 
 GS_SWEEPS = ("forward", "backward", "symmetric")       # pyamg's gauss_seidel(sweep=...)
@@ -147,14 +147,21 @@ class Hierarchy:
     """levels[0] is the fine grid; transfers[l] (n_l x n_{l+1}) prolongates level l+1 -> l."""
 
     def __init__(self, A, transfers, device, coarse_refine="auto", verbose=False, ops_mod=None,
-                 use_packed=True, coarse_solver="auto", spgemm_record="lazy", mass=None):
+                 use_packed=True, coarse_solver="auto", spgemm_record="lazy", mass=None, cycle_values="f64"):
         """coarse_refine: steps of iterative refinement around every coarsest-level solve; "auto" (default) measures
         the solver once at setup -- ||b - A x|| / ||b|| of one application -- and refines only when that is not at
         rounding level (the explicit block inverses of coarse.py reach 1e-14 on the Galerkin operators of grid
         problems: no refinement, half the launches and bytes of the coarsest solve).
         mass: optional fine-level mass matrix; every level then also gets M_(l+1) = Q_l^T M_l Q_l by the
         same device SpGEMM (`M_coarse = i.T @ M @ i`, Multigrid.py:273-275, and `mass = Q.T @ mass @ Q` of
-        NeuralMG_2D.define_hierarchy, :763): levels[l].M, refreshed by rebuild_mass_numeric()."""
+        NeuralMG_2D.define_hierarchy, :763): levels[l].M, refreshed by rebuild_mass_numeric().
+        cycle_values: "f64" | "f32", how the twins of every level's A, P and R store their values (H.cycle_values).  "f32":
+        the cycle applies A32 = double(float(A)), P32 and R32 -- fp32 value streams in the SELL and DIA twins, vectors and
+        arithmetic in fp64 -- and is a PRECONDITIONER (CG.solve / GMRES.solve(preconditioner=H)): a fixed linear operator
+        close to A^-1, not a solver for A x = b (residual_norm() raises).  The Galerkin products and the coarsest
+        factorisation read the fp64 CSR arrays either way.  Matrices without twins (use_packed=False, the CPU test shims)
+        are not affected."""
+        self.cycle_values = check_values(cycle_values, "cycle_values")
         # `ops_mod` exists for the CPU-only host-logic tests (a test shim stands in for the
         # HIP kernels); the product always runs with learnmultigrid_amd.ops.
         self.ops = ops if ops_mod is None else ops_mod
@@ -222,13 +229,21 @@ class Hierarchy:
         for lev in self.levels:
             for M in (lev.A, lev.P, lev.R):
                 if M is not None and hasattr(M, "pack"):
-                    M.pack()
+                    M.pack(values=self.cycle_values)
+
+    def _cycle_source(self, A):
+        """The matrix the sweeps on A apply, as plain CSR: A itself, or -- twins that hold fp32 values -- its rounded view
+        (DeviceCSR.cycle_source), so that what the host derives for a smoother agrees with what the kernels load."""
+        return A.cycle_source() if getattr(A, "twin_values", "f64") == "f32" else A
+
+    def _inverse_diagonal(self, lev):
+        return self.ops.csr_inverse_diagonal(self._cycle_source(lev.A))
 
     def _inverse_diagonals(self):
         # for the zero-initial-guess first sweep on coarse levels (allocated at setup so that
         # nothing has to be allocated while a hipGraph is being captured)
         for lev in self.levels[1:-1]:
-            lev.dinv = self.ops.csr_inverse_diagonal(lev.A)
+            lev.dinv = self._inverse_diagonal(lev)
 
     def _factor_coarsest(self):
         """Direct solver of the coarsest operator (setup): dense inverse, or the banded block
@@ -260,7 +275,10 @@ class Hierarchy:
         b = bh.to(self.device)
         x = torch.zeros(n, dtype=F64, device=self.device)
         self.coarse.apply(b, x)
-        self.ops.csr_residual_norm2(lev.A, x, b, None, self.partials, self.norm2)       # own kernels only (no library load)
+        # (own kernels only: no library load.  What is measured is the factorisation, which reads the fp64 values: with
+        # fp32 twins the residual is taken on the plain CSR arrays, not on A32)
+        A = lev.A.plain() if getattr(lev.A, "twin_values", "f64") == "f32" else lev.A
+        self.ops.csr_residual_norm2(A, x, b, None, self.partials, self.norm2)
         rel = math.sqrt(max(float(self.norm2.item()), 0.0)) / nb
         self.coarse_residual = rel
         self.coarse_refine = 0 if rel <= self.COARSE_AUTO_TOL else 1
@@ -284,7 +302,7 @@ class Hierarchy:
                 lev.A.repack_values()            # same pattern: only the value streams change
         self._inverse_diagonals()
         if self.levels[0].dinv is not None:          # (made on first use by a smoother that needs it: follows the values too)
-            self.levels[0].dinv = self.ops.csr_inverse_diagonal(self.levels[0].A)
+            self.levels[0].dinv = self._inverse_diagonal(self.levels[0])
         self._factor_coarsest()
         self._graphs = {}
         if self._cheby is not None:                  # new values: new bounds, new tables
@@ -371,12 +389,12 @@ class Hierarchy:
         lmax = []
         for lev, g in zip(self.levels[:-1], given):
             if g is None:
-                self.ops.csr_gershgorin(lev.A, self.norm2)
+                self.ops.csr_gershgorin(self._cycle_source(lev.A), self.norm2)
                 g = float(self.norm2.item())
             chebyshev_coefficients(g, ratio, 1)                   # (checks the bound)
             lmax.append(float(g))
             if lev.dinv is None:
-                lev.dinv = self.ops.csr_inverse_diagonal(lev.A)
+                lev.dinv = self._inverse_diagonal(lev)
             if lev.d is None:
                 lev.d = torch.zeros(lev.n, dtype=F64, device=self.device)
         self._cheby = {"args": args, "lmax": lmax, "ratio": ratio, "coef": {}}
@@ -455,7 +473,7 @@ class Hierarchy:
         elif smoother == "Jacobi":
             if x_is_zero:
                 if lev.dinv is None:
-                    lev.dinv = self.ops.csr_inverse_diagonal(lev.A)
+                    lev.dinv = self._inverse_diagonal(lev)
                 self.ops.vmul(omega, lev.dinv, lev.b, lev.tmp)
                 lev.x, lev.tmp = lev.tmp, lev.x
                 steps -= 1
@@ -671,6 +689,11 @@ class Hierarchy:
 
     def residual_norm(self, want_vector=True):
         """||b - A x||_2 on the fine level (Multigrid.py:62-63); one 8-byte D2H copy."""
+        if self.cycle_values != "f64":
+            raise ValueError("a hierarchy with cycle_values=%r is a preconditioner, not the operator of the outer iteration: "
+                             "its sweeps read rounded values, so this would be the residual of A32 x = b.  Use it through "
+                             "CG.solve / GMRES.solve(preconditioner=H), which take the residual with their own fp64 "
+                             "operator" % (self.cycle_values,))
         lev = self.levels[0]
         self.ops.csr_residual_norm2(lev.A, lev.x, lev.b, self.outer_r if want_vector else None,
                                self.partials, self.norm2)
@@ -746,6 +769,26 @@ class Hierarchy:
             self._graphs[key] = g
         return g
 
+    def twin_bytes(self):
+        """Bytes of the storage twins of every level's A, P and R at the width they have (fp32 value streams count 4 B a
+        value): what the cycle's launches stream, next to the CSR arrays memory_bytes() counts -- those stay fp64 whatever
+        cycle_values is, the Galerkin products and rebuild_numeric read them."""
+        tot = 0
+        for lev in self.levels:
+            for M in (lev.A, lev.P, lev.R):
+                for name in ("patterns", "sell", "packed", "dia"):
+                    T = getattr(M, name, None) if M is not None else None
+                    tot += 0 if T is None else T.bytes()
+        return tot
+
+    @staticmethod
+    def _csr_model_bytes(M):
+        """One pass over M in the byte model of cycle_bytes: 4 B column and 8 B value per entry -- 4 B where the twin the
+        sweeps read stores fp32 values -- and the row pointers."""
+        S = getattr(M, "sell", None)
+        narrow = S is not None and getattr(S, "values", "f64") == "f32"
+        return (8 if narrow else 12) * M.nnz + 4 * (M.shape[0] + 1)
+
     def memory_bytes(self):
         tot = 0
         for lev in self.levels:
@@ -758,13 +801,16 @@ class Hierarchy:
 
     def cycle_bytes(self, steps):
         """Algorithmic HBM bytes of one V(steps,steps) cycle: per level
-        (2*steps+1) sweeps + restriction + prolongation; coarsest dense apply separately."""
+        (2*steps+1) sweeps + restriction + prolongation; coarsest dense apply separately.  An operator whose SELL or DIA
+        twin stores fp32 values (cycle_values="f32") counts 4 B a value."""
         tot = 0
         for lev in self.levels[:-1]:
             n, nnz = lev.n, lev.A.nnz
             nc = lev.P.shape[1]
-            tot += (2 * steps + 1) * (12 * nnz + 4 * (n + 1) + 24 * n)
-            tot += 12 * lev.R.nnz + 4 * (nc + 1) + 8 * n + 8 * nc
-            tot += 12 * lev.P.nnz + 4 * (n + 1) + 8 * nc + 16 * n
+            D = getattr(lev.A, "dia", None)
+            a_bytes = self._csr_model_bytes(lev.A) - (4 * nnz if D is not None and getattr(D, "values", "f64") == "f32" else 0)
+            tot += (2 * steps + 1) * (a_bytes + 24 * n)
+            tot += self._csr_model_bytes(lev.R) + 8 * n + 8 * nc
+            tot += self._csr_model_bytes(lev.P) + 8 * nc + 16 * n
         coarse = (1 + self.coarse_refine) * self.coarse.bytes_per_apply()
         return tot, coarse

@@ -17,8 +17,8 @@ import torch
 
 from . import _lib
 from ._lib import LmgError, check
-from .twins import (F64, I32, DiaTwin, PackedCSR, ProlongTwin, RestrictTwin, RowPatterns, SellCSR,  # noqa: F401
-                    StencilTwin, _p, _s)
+from .twins import (F32, F64, I32, DiaTwin, PackedCSR, ProlongTwin, RestrictTwin, RowPatterns, SellCSR,  # noqa: F401
+                    StencilTwin, _p, _s, check_values)
 
 
 def _vec_ok(*ts):
@@ -34,7 +34,7 @@ class DeviceCSR:
     """CSR matrix resident in HBM: int32 rowptr[n+1], int32 colidx[nnz], fp64 vals[nnz]."""
 
     __slots__ = ("rowptr", "colidx", "vals", "shape", "nnz", "packed", "patterns", "sell", "stencil", "prolong", "restrict",
-                 "dia")
+                 "dia", "values", "twin_values")
 
     def __init__(self, rowptr, colidx, vals, shape):
         if rowptr.dtype != I32 or colidx.dtype != I32 or vals.dtype != F64:
@@ -51,23 +51,42 @@ class DeviceCSR:
         self.prolong = None          # ProlongTwin view of `patterns` (2x2-window grid prolongations)
         self.restrict = None         # RestrictTwin view of `patterns` (their transposes)
         self.dia = None              # DiaTwin (grid operators with per-row values): fused smoothing passes only
+        self.values = "f64"          # what pack() was last asked for: "f64" | "f32" (repack_values honours it)
+        self.twin_values = "f64"     # what the twins hold: "f32" = A32 = double(float(A)), value by value
 
-    def pack(self, patterns=None, line_strides=None):
+    def pack(self, patterns=None, line_strides=None, values=None):
         """Build (once) the lossless twin the sweep kernels prefer; keeps the CSR arrays.
         Row patterns (RowPatterns) when the rows repeat -- assembled grid operators --, else the
         packed CSR (PackedCSR).  patterns=False forces the packed CSR, None = module default.
-        line_strides: see RowPatterns.grid_map_candidates (transfers between non-square blocks of grid lines)."""
+        line_strides: see RowPatterns.grid_map_candidates (transfers between non-square blocks of grid lines).
+        values: "f64" | "f32", None = what the matrix remembers from an earlier pack() ("f64" at first).  "f32" (a cycle
+        used as a preconditioner): every twin of the matrix represents A32 = double(float(A)), value by value -- the SELL
+        and DIA twins store fp32 values, which the kernels widen when they load them; the row-pattern and packed twins
+        keep their formats and widths (one byte per row, dictionary-coded or raw fp64 values) and are built from the
+        rounded values, so that every launch on the matrix applies the same operator.  The CSR arrays keep the fp64 values
+        (the Galerkin products and the coarse factorisation read them).  A matrix with a value that fails the range rule
+        (SellCSR) gets fp64 twins as a whole: twin_values says what the twins hold."""
+        if values is not None:
+            check_values(values)
         if not self.vals.is_cuda:
             return None
+        src = self
+        if values is not None and values != self.values:
+            self.values = values
+            src = self._retarget()
+        elif self.twin_values == "f32":
+            src = self.cycle_source()
+        # src: what the formats that do not narrow are built from
+        vkw = {} if self.twin_values == "f64" else {"values": "f32"}
         if patterns is None:
             patterns = _PATTERNS_ENABLED
         if patterns and self.patterns is None and self.packed is None and self.sell is None:
             if self.shape[0] == self.shape[1]:
-                self.patterns = RowPatterns.from_csr(self)
+                self.patterns = RowPatterns.from_csr(src)
             else:
                 # rectangular grid operators (transfers): row patterns relative to a column-base map
                 for gm in (RowPatterns.grid_map_candidates(self.shape, line_strides) if _GRID_MAPS_ENABLED else []):
-                    self.patterns = RowPatterns.from_csr(self, gm)
+                    self.patterns = RowPatterns.from_csr(src, gm)
                     if self.patterns is not None:
                         break
             self._derive_grid_twins()
@@ -79,15 +98,15 @@ class DeviceCSR:
             if self.dia is None and _DIA_ENABLED and self.shape[0] == self.shape[1]:
                 # variable-coefficient grid operators: slot arrays for the fused smoothing passes, next to the
                 # packed CSR that serves the single sweeps / SpMV
-                self.dia = DiaTwin.from_csr(self)
-            self.packed = PackedCSR.from_csr(self)
+                self.dia = DiaTwin.from_csr(self, **vkw)
+            self.packed = PackedCSR.from_csr(src)
             # long rows whose values do not fit a dictionary: the sliced-ELL twin reads them without
             # LDS staging (the packed kernel's row-strided LDS walk is bank-conflict-bound there)
             pk = self.packed
             long_raw = pk is not None and pk.valmode == 2 and pk.tile_rows < 512
             unpackable = pk is None and self.nnz > 0           # rows longer than 255 entries (dense-ish operators)
             if _SELL_ENABLED and (long_raw or unpackable) and self.nnz >= SELL_MIN_AVG * self.shape[0]:
-                self.sell = SellCSR.from_csr(self)
+                self.sell = SellCSR.from_csr(self, **vkw)
                 if self.sell is not None:
                     self.packed = None
                     return self.sell
@@ -107,18 +126,62 @@ class DeviceCSR:
     def invalidate_packed(self):
         self.packed = self.patterns = self.sell = self.stencil = self.prolong = self.restrict = self.dia = None
 
+    def _rounded(self):
+        """The values rounded to fp32 and widened again (a new tensor), or None when one of them fails the range rule of
+        the fp32 twins: other than 0 and not finite, or rounded to +-inf, a subnormal or zero.  (Library elementwise kernels:
+        only a matrix packed with values="f32" ever comes here, at setup.)"""
+        v = self.vals
+        r = v.to(F32).to(F64)
+        m = r.abs()
+        bad = (v != 0) & ~((m >= float(np.finfo(np.float32).tiny)) & (m <= float(np.finfo(np.float32).max)))
+        return None if bool(bad.any()) else r
+
+    def _retarget(self):
+        """Decide what the twins hold from what pack() was asked for and the values as they are now -- "f32" where every
+        value passes the range rule --, drop twins of the other kind, and return the matrix the formats that do not narrow
+        are built from (cycle_source, made once)."""
+        r = self._rounded() if self.values == "f32" else None
+        want = "f64" if r is None else "f32"
+        if want != self.twin_values:
+            self.invalidate_packed()
+            self.twin_values = want
+        return self if r is None else DeviceCSR(self.rowptr, self.colidx, r, self.shape)
+
+    def cycle_source(self):
+        """The matrix the twins stand for, as plain CSR: self, or -- twins that hold A32 -- a twinless view of A32 that
+        shares the index arrays (built on demand: the inverse diagonals and the formats that do not narrow are taken from
+        it, so that they agree with what the sweeps read)."""
+        if self.twin_values == "f64":
+            return self
+        r = self._rounded()
+        if r is None:
+            raise LmgError("the values no longer fit fp32: call repack_values() after changing the values of a matrix")
+        return DeviceCSR(self.rowptr, self.colidx, r, self.shape)
+
+    def plain(self):
+        """A twinless view of the same arrays: the sweeps on it run the plain CSR kernels on the fp64 values."""
+        return DeviceCSR(self.rowptr, self.colidx, self.vals, self.shape)
+
     def repack_values(self):
-        """After the values changed in place: refresh the twins (cheaply if possible)."""
+        """After the values changed in place: refresh the twins (cheaply if possible) at the width pack() was asked for.
+        Where the new values fail the range rule of the fp32 twins the matrix gets fp64 twins, and fp32 twins again once
+        later values pass it."""
+        had = any(t is not None for t in (self.patterns, self.sell, self.dia, self.packed))
+        src = self._retarget() if self.values == "f32" else self
+        if had and not any(t is not None for t in (self.patterns, self.sell, self.dia, self.packed)):
+            self.pack()                                    # the twins changed kind: from scratch
+            return
         if self.patterns is not None:
-            self.patterns = RowPatterns.from_csr(self, self.patterns.grid_map)
+            self.patterns = RowPatterns.from_csr(src, self.patterns.grid_map)
             self._derive_grid_twins()
             if self.patterns is None:
                 self.pack()
-        if self.sell is not None:
-            self.sell.update_values(self)
+        if self.sell is not None and not self.sell.update_values(self):
+            # update_values refused (fp32 values out of range): that twin again -- its columns, its padding -- in fp64
+            self.sell = SellCSR.from_csr(self, colmode=self.sell.colmode, max_padding=float("inf"))
         if self.dia is not None and not self.dia.update_values(self):
             self.dia = None
-        if self.packed is not None and not self.packed.update_values(self):
+        if self.packed is not None and not self.packed.update_values(src):
             self.packed = None
             self.pack(patterns=False)
 
@@ -296,7 +359,7 @@ def _run_pass(stem, kind, A, head, x_in, r_out, prolong, restrict):
         D = A.dia
         if prolong is not None or restrict is not None:
             raise LmgError("%s: transfers cannot be fused into the pass of a variable-coefficient operator" % who)
-        name = "lmg_dia_" + stem
+        name = "lmg_dia_" + stem + ("_f32" if D.values == "f32" else "")
         check(getattr(_lib.lib(), name)(D.n, D.W, D.umask, _p(D.dia), *head, _p(r_out), _s(D.dia)), name)
         return
     S = A.stencil
@@ -629,7 +692,8 @@ def _sweep(mode, A, x, b, out, alpha, beta, partials, norm2):
         check(_twin_sweep(L.lmg_rpat_sweep_grid, mode, A.patterns, tail), "lmg_rpat_sweep" + what)
         return
     if _PACKED_ENABLED and A.sell is not None:
-        check(_twin_sweep(L.lmg_sell_sweep, mode, A.sell, tail), "lmg_sell_sweep" + what)
+        name = "lmg_sell_sweep_f32" if A.sell.values == "f32" else "lmg_sell_sweep"
+        check(_twin_sweep(getattr(L, name), mode, A.sell, tail), name + what)
         return
     if _PACKED_ENABLED and A.packed is not None:
         rc = _twin_sweep(L.lmg_pcsr_sweep, mode, A.packed, tail)

@@ -21,7 +21,16 @@ from . import _lib
 from ._lib import LmgError, check
 
 F64 = torch.float64
+F32 = torch.float32
 I32 = torch.int32
+VALUES = ("f64", "f32")        # how a SELL / DIA twin stores its values (the vectors and the arithmetic are fp64 either way)
+
+
+def check_values(values, what="values"):
+    """`values` if it is one of VALUES, else a ValueError (reads no state: callers check before they build anything)."""
+    if values not in VALUES:
+        raise ValueError("%s must be one of %s, got %r" % (what, VALUES, values))
+    return values
 
 
 def _s(*ts):
@@ -306,19 +315,23 @@ class SellCSR:
     """Sliced-ELL (SELL-64) twin of a DeviceCSR for lmg_sell_sweep (see include/lmg.h): slices of 64
     rows padded to their longest row, entries stored column-major inside a slice.  For long rows
     with all-distinct values (Galerkin operators of learned / L2-type transfers); refused when the
-    padding would cost more than 20 % extra entries."""
+    padding would cost more than 20 % extra entries.
+    values "f32": the value stream is fp32 and the twin represents A32 = double(float(A)) value by value
+    (lmg_sell_sweep_f32: a cycle used as a preconditioner); refused -- None -- when a stored value other than 0 is not
+    finite or rounds to +-inf, a subnormal or zero."""
 
     __slots__ = ("n", "nnz", "shape", "slice_base", "slice_len", "slice_cmin", "rowlen", "col", "colmode", "val",
-                 "max_len", "padded", "bytes_")
+                 "max_len", "padded", "bytes_", "values")
 
     MAX_PADDING = 1.2
 
     @classmethod
-    def from_csr(cls, A, colmode=None, max_padding=None):
+    def from_csr(cls, A, colmode=None, max_padding=None, values="f64"):
         """colmode (0: uint16 slice-relative columns, 1: int32) and max_padding (padded entries per entry of the matrix
         from which the twin is refused; default MAX_PADDING) override the choices made below -- the format allows int32
         columns and any padding for any matrix; None keeps the builder's own rule.  (pack() passes neither: the parity
         tests reach the int32 columns and ragged slices on small matrices this way.)"""
+        check_values(values)
         n, nnz = A.shape[0], A.nnz
         if n == 0 or nnz == 0 or not A.vals.is_cuda:
             return None
@@ -348,11 +361,24 @@ class SellCSR:
             raise ValueError("colmode 0: a slice spans 65536 columns or more")
         self.colmode = (0 if fits16 else 1) if colmode is None else int(colmode)
         self.col = torch.zeros(padded + 64, dtype=torch.int16 if self.colmode == 0 else I32, device=dev)
-        self.val = torch.zeros(padded + 64, dtype=F64, device=dev)
-        check(L.lmg_sell_fill(n, _p(A.rowptr), _p(A.colidx), _p(A.vals), _p(self.slice_base), _p(cmin), self.colmode,
-                              _p(self.col), _p(self.val), _s(A.rowptr)), "lmg_sell_fill")
-        self.bytes_ = padded * ((2, 4)[self.colmode] + 8) + 16 * nsl + 4 * n
+        self.values = values
+        self.val = torch.zeros(padded + 64, dtype=F64 if values == "f64" else F32, device=dev)
+        if not self._fill(A, self.col):
+            return None
+        self.bytes_ = padded * ((2, 4)[self.colmode] + self.val.element_size()) + 16 * nsl + 4 * n
         return self
+
+    def _fill(self, A, col):
+        """The value stream (and with `col` the columns) from A; False when fp32 values fail the range rule."""
+        L = _lib.lib()
+        head = (self.n, _p(A.rowptr), None if col is None else _p(A.colidx), _p(A.vals), _p(self.slice_base),
+                _p(self.slice_cmin), self.colmode, _p(col), _p(self.val))
+        if self.values == "f64":
+            check(L.lmg_sell_fill(*head, _s(A.rowptr)), "lmg_sell_fill")
+            return True
+        flag = torch.zeros(1, dtype=I32, device=self.val.device)
+        check(L.lmg_sell_fill_f32(*head, _p(flag), _s(A.rowptr)), "lmg_sell_fill_f32")
+        return not int(flag.cpu()[0])
 
     def bytes(self):
         return int(self.bytes_)
@@ -363,10 +389,9 @@ class SellCSR:
                 self.colmode, _p(self.val), self.max_len), self.slice_base
 
     def update_values(self, A):
-        """New values, same pattern (Galerkin rebuild): only the value stream is rewritten."""
-        check(_lib.lib().lmg_sell_fill(self.n, _p(A.rowptr), None, _p(A.vals), _p(self.slice_base), _p(self.slice_cmin),
-                                       self.colmode, None, _p(self.val), _s(A.rowptr)), "lmg_sell_fill(values)")
-        return True
+        """New values, same pattern (Galerkin rebuild): only the value stream is rewritten, at the width it has.  False
+        when fp32 values fail the range rule (the caller rebuilds the twin in fp64)."""
+        return self._fill(A, None)
 
 
 def _pid_counts(R):
@@ -672,22 +697,28 @@ class DiaTwin:
     number q of the union mask (+0.0 where the row has none).  Built and verified on the device: W is guessed from a
     few rows in the middle of the matrix, a probe pass collects the slots of ALL entries for that W and refuses the
     matrix if any entry is not a slot; from_csr returns None for everything that does not fit (the packed-CSR sweeps
-    then run one launch per sweep)."""
+    then run one launch per sweep).
+    values "f32": fp32 slot arrays, the twin represents A32 = double(float(A)) value by value (lmg_dia_smooth_f32);
+    refused -- None -- when a stored value other than 0 is not finite or rounds to +-inf, a subnormal or zero."""
 
-    __slots__ = ("n", "W", "umask", "nslots", "dia", "bytes_")
+    __slots__ = ("n", "W", "umask", "nslots", "dia", "bytes_", "values")
     MIN_ROWS = 4096
 
     @staticmethod
     def _probe(A, W, umask, dia):
+        """(flag word, slots seen) of a fill (dia: fp64 or fp32 slot arrays) or probe (dia None) pass; flag bit 0: an entry
+        is no slot of the mask, bit 1 (fp32 arrays): a value fails the range rule."""
         dev = A.vals.device
         flags = torch.zeros(2, dtype=I32, device=dev)
-        check(_lib.lib().lmg_dia_fill(A.shape[0], int(W), _p(A.rowptr), _p(A.colidx), _p(A.vals), int(umask), _p(dia),
-                                      flags.data_ptr(), flags.data_ptr() + 4, _s(A.rowptr)), "lmg_dia_fill")
+        name = "lmg_dia_fill_f32" if dia is not None and dia.dtype == F32 else "lmg_dia_fill"
+        check(getattr(_lib.lib(), name)(A.shape[0], int(W), _p(A.rowptr), _p(A.colidx), _p(A.vals), int(umask), _p(dia),
+                                        flags.data_ptr(), flags.data_ptr() + 4, _s(A.rowptr)), name)
         f = flags.cpu().numpy()
         return int(f[0]), int(f[1]) & 0x1FF
 
     @classmethod
-    def from_csr(cls, A):
+    def from_csr(cls, A, values="f64"):
+        check_values(values)
         n = A.shape[0]
         if n < cls.MIN_ROWS or A.nnz == 0 or A.nnz > 9 * n or not A.vals.is_cuda or n >= 2 ** 31 - 4096:
             return None
@@ -714,16 +745,18 @@ class DiaTwin:
             self = cls()
             self.n, self.W, self.umask = int(n), int(W), int(umask)
             self.nslots = bin(umask).count("1")
-            self.dia = torch.empty(self.nslots * n, dtype=F64, device=A.vals.device)
+            self.values = values
+            self.dia = torch.empty(self.nslots * n, dtype=F64 if values == "f64" else F32, device=A.vals.device)
             bad, _seen = cls._probe(A, W, umask, self.dia)
             if bad:
                 return None
-            self.bytes_ = 8 * self.nslots * n
+            self.bytes_ = self.dia.element_size() * self.nslots * n
             return self
         return None
 
     def update_values(self, A):
-        """New values on the same pattern (Galerkin rebuild of a variable-coefficient level)."""
+        """New values on the same pattern (Galerkin rebuild of a variable-coefficient level), at the width the twin has.
+        False: an entry left the pattern or -- fp32 -- a value fails the range rule."""
         bad, _seen = self._probe(A, self.W, self.umask, self.dia)
         return not bad
 
