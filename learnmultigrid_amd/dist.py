@@ -59,6 +59,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from . import smoothing
 from .ops import DeviceCSR, F64, I32
 
 _UNREACHED = 1 << 20           # _layer_of: "in none of the layers" (deeper than any halo)
@@ -537,20 +538,12 @@ class DistributedVCycle:
         the next sweep needs.  Otherwise one exchange per sweep.
         Returns True when d.r = b - A x was produced along the way (fused pass, want_residual)."""
         o = self.ops
-        fused = getattr(o, "stencil_smooth_available", None)
-        if deep and steps > 0 and fused is not None and fused(d.A):
+        if deep and steps > 0 and smoothing.ask(o, "stencil_smooth_available", d.A):
             # no message between the sweeps: they (and the residual) run as fused passes over the local
             # block -- the same bits as one launch per sweep (lmg_stencil_smooth)
             if not exchanged:
                 self.exchange(d, d.b if x_is_zero else d.x)
-            left, zero = steps, x_is_zero
-            while left > 0:
-                k = min(left, o.FUSED_MAX_SWEEPS)
-                left -= k
-                o.stencil_smooth(d.A, None if zero else d.x, d.b, omega, k, d.tmp,
-                                 d.r if (want_residual and left == 0) else None)
-                d.x, d.tmp = d.tmp, d.x
-                zero = False
+            smoothing.fused_passes(o, d.A, d, steps, omega, x_is_zero, want_residual)
             return want_residual
         if x_is_zero and steps > 0:
             if deep and not exchanged:
@@ -583,12 +576,9 @@ class DistributedVCycle:
             pat = sp.csr_matrix((np.ones(int(keep.sum()), dtype=np.int8), (rows[keep] - lo, ci[keep] - lo)),
                                 shape=(d.n_own, d.n_own))
             pat.sort_indices()
-            sched = self.ops.build_gs_schedule(pat, "lexicographic", self.device)
-            sched.d_rows += lo                                   # local row numbering of the block ([ghosts | owned | ghosts])
-            prep = getattr(self.ops, "gs_prepare", None)
-            if prep is not None:
-                prep(d.A, sched)
-            d.gs_sched = sched
+            # row_offset: the local row numbering of the block ([ghosts | owned | ghosts])
+            d.gs_sched = smoothing.gs_schedule(self.ops, d.A, pat.indptr, pat.indices, "lexicographic", self.device,
+                                               row_offset=lo)
         return d.gs_sched
 
     def _smooth_gs(self, d, steps, x_is_zero):
@@ -597,17 +587,13 @@ class DistributedVCycle:
         o = self.ops
         if x_is_zero:
             o.zero(d.x)
-        wave = getattr(o, "stencil_gs_available", None)
         # the wavefront kernel relaxes EVERY row of the matrix it is given: only with the classic one-layer halo are the
         # ghost rows of the local operator empty (and therefore left alone)
-        use_wave = wave is not None and self.halo_depth == 1 and wave(d.A)
+        use_wave = self.halo_depth == 1 and smoothing.wavefront_gs(o, d.A)
         for k in range(steps):
             if not (x_is_zero and k == 0):
                 self.exchange(d, d.x)                           # (a zero iterate has zero ghosts)
-            if use_wave:
-                o.stencil_gs(d.A, d.x, d.b, 1)
-            else:
-                o.csr_gs_schedule(d.A, d.x, d.b, self._owned_gs_schedule(d), 1)
+            smoothing.gauss_seidel(o, d.A, d, use_wave, lambda: self._owned_gs_schedule(d), 1)
 
     def cycle(self, smoother, steps, omega=1.0, l=0, x_is_zero=False):
         """One V-cycle from level l down.  Returns the number of ghost layers on which this level's

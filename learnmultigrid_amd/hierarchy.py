@@ -20,21 +20,12 @@ import numpy as np
 import scipy.sparse as sp
 import torch
 
-from . import ops
+from . import ops, smoothing
 from .coarse import make_coarse_solver
 from .ops import DeviceCSR, F64
+from .smoothing import (CHEBY_RATIO, GS_SWEEPS, LINE_DIRS, LINE_ORDERS, _directions, chebyshev_coefficients,  # noqa: F401
+                        gs_sweep_pair, line_config, line_half_steps)
 from .twins import DiaTwin, check_values, line_stride
-
-
-GS_SWEEPS = ("forward", "backward", "symmetric")       # pyamg's gauss_seidel(sweep=...)
-
-
-def gs_sweep_pair(gs_sweep):
-    """(pre, post) smoothing directions of a Gauss-Seidel cycle from a pyamg sweep name (used for both) or a pair."""
-    pair = (gs_sweep, gs_sweep) if isinstance(gs_sweep, str) else tuple(gs_sweep)
-    if len(pair) != 2 or any(d not in GS_SWEEPS for d in pair):
-        raise ValueError("gs_sweep must be one of %s or a (pre, post) pair of them, got %r" % (GS_SWEEPS, gs_sweep))
-    return pair
 
 
 CYCLE_SHAPES = ("V", "W", "F")                         # pyamg's multilevel_solver.solve(cycle=...)
@@ -48,66 +39,10 @@ def cycle_children(shape):
     return _CHILDREN[shape]
 
 
-def chebyshev_coefficients(lmax, ratio, degree):
-    """The (a_k, c_k), k = 0 .. degree - 1, of one Chebyshev smoothing step on [lmax / ratio, lmax] for D^-1 A:
-        d_k = a_k d_(k-1) + c_k D^-1 (b - A x_k),   x_(k+1) = x_k + d_k,
-    the three-term recurrence of the shifted and scaled Chebyshev polynomial (error polynomial of one step:
-    T_S((theta - lambda) / delta) / T_S(sigma)), in Python floats."""
-    lmax, ratio, degree = float(lmax), float(ratio), int(degree)
-    if not (ratio > 1.0 and math.isfinite(ratio)):
-        raise ValueError("cheby_ratio must be a finite number > 1 (lambda_min = lambda_max / cheby_ratio), got %r" % (ratio,))
-    if not (lmax > 0.0 and math.isfinite(lmax)):
-        raise ValueError("the Chebyshev smoother needs a finite bound lambda_max > 0 for D^-1 A, got %r" % (lmax,))
-    if degree < 1:
-        raise ValueError("the Chebyshev smoother needs a degree (smooth_steps) >= 1, got %r" % (degree,))
-    lmin = lmax / ratio
-    theta = (lmax + lmin) / 2
-    delta = (lmax - lmin) / 2
-    sigma = theta / delta
-    rho = 1 / sigma
-    coef = [(0.0, 1 / theta)]
-    for _ in range(1, degree):
-        rho_k = 1 / (2 * sigma - rho)
-        coef.append((rho_k * rho, 2 * rho_k / delta))
-        rho = rho_k
-    return coef
-
-
 # the ops predicates of the fused Chebyshev passes, by the Jacobi predicate each stands in for (Hierarchy._ask)
 CHEBY_TWIN = {"stencil_smooth_available": "stencil_cheby_available",
               "stencil_smooth_prolong_available": "stencil_cheby_prolong_available",
               "stencil_smooth_restrict_available": "stencil_cheby_restrict_available"}
-CHEBY_RATIO = 4.0       # lambda_max / lambda_min: the oscillatory modes of D^-1 A under full coarsening in two dimensions
-
-
-LINE_DIRS = ("x", "y", "xy")          # the line_dir of the "Line" smoother: the systems one step solves, in this order
-LINE_ORDERS = ("zebra", "jacobi")     # its line_order: even systems then odd ones with a fresh residual, or all from one
-
-
-def line_config(line_dir=None, line_order=None):
-    """(line_dir, line_order) with the defaults ("xy", "zebra") filled in, or a ValueError (reads no state: the solver
-    classes check their keywords with it before any setup)."""
-    line_dir = "xy" if line_dir is None else line_dir
-    line_order = "zebra" if line_order is None else line_order
-    if line_dir not in LINE_DIRS:
-        raise ValueError("line_dir must be one of %s, got %r" % (LINE_DIRS, line_dir))
-    if line_order not in LINE_ORDERS:
-        raise ValueError("line_order must be one of %s, got %r" % (LINE_ORDERS, line_order))
-    return line_dir, line_order
-
-
-def line_half_steps(line_dir, line_order, reverse=False):
-    """The launches of one "Line" smoothing step as (direction, first, step) of ops.line_solve, each after a fresh residual:
-    per direction of line_dir the even systems then the odd ones (zebra) or all systems (jacobi).  reverse: the
-    post-smoothing half -- directions and colours in the opposite order, which makes the cycle's smoothing halves adjoint
-    to each other whenever A is symmetric."""
-    colours = ((0, 2), (1, 2)) if line_order == "zebra" else ((0, 1),)
-    out = [(d, first, step) for d in line_dir for (first, step) in colours]
-    return out[::-1] if reverse else out
-
-
-def _directions(sweep):
-    return ("forward", "backward") if sweep == "symmetric" else (sweep,)
 
 
 def _to_csr_host(M):
@@ -427,27 +362,19 @@ class Hierarchy:
         """Schedule of the Gauss-Seidel sweep on level l, cached per (kind, direction): a backward sweep runs the sets of
         the forward schedule in reverse order (GSSchedule.reversed), with its own schedule-ordered pattern copy."""
         lev = self.levels[l]
-        if direction != "forward":
-            key = (kind, direction)
-            if key not in lev.gs_sched:
-                if direction != "backward":
-                    raise ValueError("unknown Gauss-Seidel sweep direction %r" % (direction,))
-                sched = self.gs_schedule(l, kind).reversed()
-                self._ask("gs_prepare", lev.A, sched)
-                lev.gs_sched[key] = sched
-            return lev.gs_sched[key]
-        if kind not in lev.gs_sched:
-            if lev.host_pattern is None:
-                lev.host_pattern = (lev.A.rowptr.cpu().numpy(), lev.A.colidx.cpu().numpy())
-            rp, ci = lev.host_pattern
-            pat = sp.csr_matrix((np.ones(ci.size, dtype=np.int8), ci, rp), shape=lev.A.shape)
-            sched = self.ops.build_gs_schedule(pat, kind, self.device)
-            # the schedule-ordered pattern copy of the one-workgroup executor is built HERE, eagerly:
-            # it allocates and reads sizes back to the host, which must never happen while a
-            # hipGraph is being captured (captured_cycle only calls gs_schedule before the capture)
-            self._ask("gs_prepare", lev.A, sched)
-            lev.gs_sched[kind] = sched
-        return lev.gs_sched[kind]
+        key = kind if direction == "forward" else (kind, direction)
+        if key not in lev.gs_sched:
+            # built and prepared HERE, eagerly (captured_cycle only calls gs_schedule before the capture)
+            if direction == "backward":
+                lev.gs_sched[key] = self.gs_schedule(l, kind).reversed()
+                self._ask("gs_prepare", lev.A, lev.gs_sched[key])
+            elif direction != "forward":
+                raise ValueError("unknown Gauss-Seidel sweep direction %r" % (direction,))
+            else:
+                if lev.host_pattern is None:
+                    lev.host_pattern = (lev.A.rowptr.cpu().numpy(), lev.A.colidx.cpu().numpy())
+                lev.gs_sched[key] = smoothing.gs_schedule(self.ops, lev.A, *lev.host_pattern, kind, self.device)
+        return lev.gs_sched[key]
 
     # ------------------------------------------------------------------ solve ----------
     def smooth(self, l, smoother, steps, omega, gs_mode, x_is_zero=False, direction="forward"):
@@ -481,14 +408,7 @@ class Hierarchy:
                 self.ops.csr_jacobi(lev.A, lev.x, lev.b, omega, lev.tmp)
                 lev.x, lev.tmp = lev.tmp, lev.x
         elif smoother == "Chebyshev":
-            # one step of degree `steps`, two launches per sweep: r = b - A x, then d = a d + c D^-1 r, x += d (in place)
-            for k, (a, c) in enumerate(self._cheby_coef(l, steps)):
-                if k == 0 and x_is_zero:
-                    self.ops.zero(lev.x)
-                    self.ops.cheby_update(a, c, lev.dinv, lev.b, lev.d, lev.x, first=True)     # b - A 0 = b
-                else:
-                    self.ops.csr_residual_norm2(lev.A, lev.x, lev.b, lev.r, None, None)
-                    self.ops.cheby_update(a, c, lev.dinv, lev.r, lev.d, lev.x, first=(k == 0))
+            smoothing.chebyshev_step(self.ops, lev.A, lev, self._cheby_coef(l, steps), x_is_zero)
         elif smoother == "Line":
             # per half-step: r = b - A x, then x += omega T^-1 r on its systems, in place (direction "backward": the
             # post-smoothing half, directions and colours reversed)
@@ -512,30 +432,18 @@ class Hierarchy:
 
     def _gs(self, l, gs_mode, steps, direction):
         lev = self.levels[l]
-        if direction not in ("forward", "backward"):
-            raise ValueError("unknown Gauss-Seidel sweep direction %r" % (direction,))
-        if self._wavefront_gs(l, gs_mode, direction):
-            # grid-stencil level: exact sweep as a pipelined wavefront, no schedule needed
-            if direction == "forward":
-                self.ops.stencil_gs(lev.A, lev.x, lev.b, steps)
-            else:
-                self.ops.stencil_gs(lev.A, lev.x, lev.b, steps, direction)
-        else:
-            self.ops.csr_gs_schedule(lev.A, lev.x, lev.b, self.gs_schedule(l, gs_mode, direction), steps)
+        smoothing.gauss_seidel(self.ops, lev.A, lev, self._wavefront_gs(l, gs_mode, direction),
+                               lambda: self.gs_schedule(l, gs_mode, direction), steps, direction)
 
     def _ask(self, name, *args, smoother=None):
         """self.ops.<name>(*args), or False where the ops module has no such name (an ops module leaves out what it does
         not offer).  With smoother "Chebyshev", the Chebyshev twin of a Jacobi predicate is asked in its place."""
         if smoother == "Chebyshev":
             name = CHEBY_TWIN[name]
-        fn = getattr(self.ops, name, None)
-        return fn(*args) if fn is not None else False
+        return smoothing.ask(self.ops, name, *args)
 
     def _wavefront_gs(self, l, gs_mode, direction="forward"):
-        if gs_mode != "lexicographic":
-            return False
-        A = self.levels[l].A
-        return self._ask("stencil_gs_available", A) if direction == "forward" else self._ask("stencil_gs_available", A, direction)
+        return gs_mode == "lexicographic" and smoothing.wavefront_gs(self.ops, self.levels[l].A, direction)
 
     def _fusable(self, l, smoother, steps):
         if smoother not in ("Jacobi", "Chebyshev") or steps < 1:
@@ -553,25 +461,9 @@ class Hierarchy:
         x + P e (Multigrid.py:115 folded in; the caller has checked stencil_smooth_prolong_available).
         smoother "Chebyshev": one step of degree `steps` (<= FUSED_MAX_SWEEPS, see _fusable) as the one pass, with its
         coefficient table in place of (omega, sweeps)."""
-        lev = self.levels[l]
-        cheby = smoother == "Chebyshev"
-        run = self.ops.stencil_cheby if cheby else self.ops.stencil_smooth
-        left = steps
-        while left > 0:
-            k = left if cheby else min(left, self.ops.FUSED_MAX_SWEEPS)
-            left -= k
-            how = (self._cheby_coef(l, k),) if cheby else (omega, k)
-            x_in = None if x_is_zero else lev.x
-            if correction is not None:
-                run(lev.A, lev.x, lev.b, *how, lev.tmp, None, prolong=correction)
-                correction = None
-            elif restrict_to is not None and left == 0:
-                # b_coarse = R (b - A x) formed in the pass, the residual itself is not written
-                run(lev.A, x_in, lev.b, *how, lev.tmp, None, restrict=restrict_to)
-            else:
-                run(lev.A, x_in, lev.b, *how, lev.tmp, lev.r if (want_residual and left == 0) else None)
-            lev.x, lev.tmp = lev.tmp, lev.x
-            x_is_zero = False
+        coef = self._cheby_coef(l, steps) if smoother == "Chebyshev" and steps > 0 else None
+        smoothing.fused_passes(self.ops, self.levels[l].A, self.levels[l], steps, omega, x_is_zero, want_residual,
+                               correction, restrict_to, coef)
 
     def coarse_solve(self):
         lev = self.levels[-1]
@@ -643,20 +535,16 @@ class Hierarchy:
         """Pre-smoothing of level l, residual, b_(l+1) = R r (Multigrid.py:88-93)."""
         lev, nxt = self.levels[l], self.levels[l + 1]
         fused = self._fusable(l, smoother, steps)
-        restricted = False
-        if fused and self._ask("stencil_smooth_restrict_available", lev.A, lev.R, smoother=smoother):
+        restricted = fused and self._ask("stencil_smooth_restrict_available", lev.A, lev.R, smoother=smoother)
+        if restricted:
             self.smooth_fused(l, steps, omega, x_is_zero, restrict_to=(lev.R, nxt.b), smoother=smoother)   # :88 + :90 + :93 in one pass
-            restricted = True
-            if after_presmooth is not None:
-                after_presmooth(lev.x)
         elif fused:
             self.smooth_fused(l, steps, omega, x_is_zero, want_residual=True, smoother=smoother)  # :88 + :90 in one pass
-            if after_presmooth is not None:
-                after_presmooth(lev.x)
         else:
             self.smooth(l, smoother, steps, omega, gs_mode, x_is_zero, pre)       # :88
-            if after_presmooth is not None:
-                after_presmooth(lev.x)
+        if after_presmooth is not None:
+            after_presmooth(lev.x)
+        if not fused:
             self.ops.csr_residual_norm2(lev.A, lev.x, lev.b, lev.r, None, None)        # :90
         if not restricted:
             self.ops.csr_spmv(lev.R, lev.r, nxt.b, 1.0, 0.0)                       # :93

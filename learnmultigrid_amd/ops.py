@@ -1,9 +1,9 @@
-"""Torch-facing wrappers of the C ABI (include/lmg.h) and their registration as
-PyTorch custom ops (`torch.ops.lmg.*`).
+"""Torch-facing wrappers of the C ABI (include/lmg.h).
 
 PyTorch is plumbing here: it owns device memory and the current HIP stream; every
 arithmetic step is a hand-written gfx950 kernel reached through ctypes.  The same
-Python callables back the `torch.ops.lmg.*` ops and the solver's internal calls.
+Python callables back the `torch.ops.lmg.*` ops (torch_ops.py; register_torch_ops() here
+registers them) and the solver's internal calls.
 
 What lives here: DeviceCSR and its pack() policy -- which of the storage twins of twins.py an operator gets --, every
 enable switch and size threshold that picks a kernel, and one wrapper per entry point: sweeps, fused smoothing passes,
@@ -1264,248 +1264,7 @@ class CapturedGraph:
 
 
 # ---- torch.ops.lmg.* registration ------------------------------------------------------------
-_registered = False
-
-
 def register_torch_ops():
-    """Expose the kernels as PyTorch custom ops taking ROCm tensors, e.g.
-    torch.ops.lmg.csr_jacobi(rowptr, colidx, vals, x, b, omega) -> x_new."""
-    global _registered
-    if _registered:
-        return
-    lib = torch.library.Library("lmg", "DEF")
-    lib.define("csr_residual(Tensor rowptr, Tensor colidx, Tensor vals, Tensor x, Tensor b) -> (Tensor, Tensor)")
-    lib.define("csr_jacobi(Tensor rowptr, Tensor colidx, Tensor vals, Tensor x, Tensor b, float omega) -> Tensor")
-    lib.define("csr_spmv(Tensor rowptr, Tensor colidx, Tensor vals, int ncols, Tensor x) -> Tensor")
-    lib.define("csr_gs_rows_(Tensor rowptr, Tensor colidx, Tensor vals, Tensor(a!) x, Tensor b, Tensor rows) -> ()")
-
-    def _csr(rowptr, colidx, vals, ncols):
-        return DeviceCSR(rowptr, colidx, vals, (rowptr.numel() - 1, ncols))
-
-    def op_residual(rowptr, colidx, vals, x, b):
-        A = _csr(rowptr, colidx, vals, x.numel())
-        r = torch.empty_like(x)
-        part = torch.empty(partials_count(A.shape[0]), dtype=F64, device=x.device)
-        n2 = torch.empty(1, dtype=F64, device=x.device)
-        csr_residual_norm2(A, x, b, r, part, n2)
-        return r, n2
-
-    def op_jacobi(rowptr, colidx, vals, x, b, omega):
-        A = _csr(rowptr, colidx, vals, x.numel())
-        out = torch.empty_like(x)
-        csr_jacobi(A, x, b, omega, out)
-        return out
-
-    def op_spmv(rowptr, colidx, vals, ncols, x):
-        A = _csr(rowptr, colidx, vals, ncols)
-        y = torch.empty(A.shape[0], dtype=F64, device=x.device)
-        csr_spmv(A, x, y, 1.0, 0.0)
-        return y
-
-    def op_gs_rows_(rowptr, colidx, vals, x, b, rows):
-        csr_gs_rows(_csr(rowptr, colidx, vals, x.numel()), x, b, rows)
-
-    lib.impl("csr_residual", op_residual, "CUDA")
-    lib.impl("csr_jacobi", op_jacobi, "CUDA")
-    lib.impl("csr_spmv", op_spmv, "CUDA")
-    lib.impl("csr_gs_rows_", op_gs_rows_, "CUDA")
-
-    # ---- the rest of the C ABI: Galerkin SpGEMM, coarse GEMV, and operators with their lossless twins --------
-    lib.define("spgemm(Tensor a_rowptr, Tensor a_colidx, Tensor a_vals, int a_cols, Tensor b_rowptr, Tensor b_colidx, "
-               "Tensor b_vals, int b_cols) -> (Tensor, Tensor, Tensor)")
-    lib.define("csr_transpose(Tensor rowptr, Tensor colidx, Tensor vals, int ncols) -> (Tensor, Tensor, Tensor)")
-    lib.define("dense_gemv(Tensor M, Tensor x) -> Tensor")
-    # an operator handle owns the packed / row-pattern / stencil / sliced-ELL twin built once by pack()
-    lib.define("operator_create(Tensor rowptr, Tensor colidx, Tensor vals, int ncols) -> int")
-    lib.define("operator_format(int handle) -> str")
-    lib.define("operator_free(int handle) -> ()")
-    lib.define("operator_spmv(int handle, Tensor x) -> Tensor")
-    lib.define("operator_residual(int handle, Tensor x, Tensor b) -> (Tensor, Tensor)")
-    lib.define("operator_jacobi(int handle, Tensor x, Tensor b, float omega, int sweeps) -> Tensor")
-    lib.define("operator_chebyshev(int handle, Tensor x, Tensor b, int degree, float lmax, float ratio) -> Tensor")
-    lib.define("operator_gershgorin(int handle) -> Tensor")
-    lib.define("cheby_update_(float a, float c, bool first, Tensor dinv, Tensor r, Tensor(a!) d, Tensor(b!) x) -> ()")
-    lib.define("csr_gershgorin(Tensor rowptr, Tensor colidx, Tensor vals) -> Tensor")
-    lib.define("operator_gauss_seidel_(int handle, Tensor(a!) x, Tensor b, int sweeps) -> ()")
-    lib.define("operator_gauss_seidel_backward_(int handle, Tensor(a!) x, Tensor b, int sweeps) -> ()")
-
-    lib.define("line_factor(Tensor rowptr, Tensor colidx, Tensor vals, int line_stride, str dir) -> (Tensor, Tensor, Tensor, int)")
-    lib.define("line_solve(int line_stride, str dir, int first, int step, Tensor lo, Tensor minv, Tensor cp, Tensor(a!) r, "
-               "float omega, Tensor(b!) x) -> ()")
-
-    def op_line_factor(rowptr, colidx, vals, line_stride, dir):
-        (lo, minv, cp), flags = line_factor_flags(_csr(rowptr, colidx, vals, rowptr.numel() - 1), line_stride, dir)
-        return lo, minv, cp, flags
-
-    def op_line_solve(line_stride, dir, first, step, lo, minv, cp, r, omega, x):
-        line_solve(line_stride, dir, first, step, (lo, minv, cp), r, omega, x)
-
-    def op_spgemm(arp, aci, ava, acols, brp, bci, bva, bcols):
-        C = spgemm(_csr(arp, aci, ava, acols), _csr(brp, bci, bva, bcols))
-        return C.rowptr, C.colidx, C.vals
-
-    def op_transpose(rowptr, colidx, vals, ncols):
-        T = _csr(rowptr, colidx, vals, ncols).transpose()
-        return T.rowptr, T.colidx, T.vals
-
-    def op_dense_gemv(M, x):
-        y = torch.empty(M.shape[0], dtype=F64, device=x.device)
-        dense_gemv(M.contiguous(), x, y)
-        return y
-
-    handles = register_torch_ops._handles = {}
-
-    def op_create(rowptr, colidx, vals, ncols):
-        A = _csr(rowptr, colidx, vals, ncols)
-        A.pack()
-        h = 1 + max(handles, default=0)
-        handles[h] = {"A": A, "gs": None, "gs_backward": None}
-        return h
-
-    def _get(h):
-        if h not in handles:
-            raise LmgError("unknown operator handle %d" % h)
-        return handles[h]
-
-    def op_format(h):
-        A = _get(h)["A"]
-        return ("stencil" if A.stencil is not None else "rpat" if A.patterns is not None else
-                "sell" if A.sell is not None else "pcsr" if A.packed is not None else "csr")
-
-    def op_free(h):
-        handles.pop(h, None)
-
-    def op_h_spmv(h, x):
-        A = _get(h)["A"]
-        y = torch.empty(A.shape[0], dtype=F64, device=x.device)
-        csr_spmv(A, x, y, 1.0, 0.0)
-        return y
-
-    def op_h_residual(h, x, b):
-        A = _get(h)["A"]
-        r = torch.empty_like(b)
-        part = torch.empty(partials_count(A.shape[0]), dtype=F64, device=x.device)
-        n2 = torch.empty(1, dtype=F64, device=x.device)
-        csr_residual_norm2(A, x, b, r, part, n2)
-        return r, n2
-
-    def op_h_jacobi(h, x, b, omega, sweeps):
-        A = _get(h)["A"]
-        cur, out = x, torch.empty_like(x)
-        spare = None
-        left = int(sweeps)
-        while left > 0:
-            if A.stencil is not None and stencil_smooth_available(A):
-                k = min(left, FUSED_MAX_SWEEPS)
-                stencil_smooth(A, cur, b, omega, k, out)
-            else:
-                k = 1
-                csr_jacobi(A, cur, b, omega, out)
-            left -= k
-            if left > 0:
-                nxt = spare if spare is not None else torch.empty_like(x)
-                spare = cur if cur is not x else None
-                cur, out = out, nxt
-            else:
-                cur = out
-        return cur if sweeps > 0 else x.clone()
-
-    def op_gershgorin(rowptr, colidx, vals):
-        out = torch.empty(1, dtype=F64, device=vals.device)
-        csr_gershgorin(_csr(rowptr, colidx, vals, rowptr.numel() - 1), out)
-        return out
-
-    def op_h_gershgorin(h):
-        A = _get(h)["A"]
-        return op_gershgorin(A.rowptr, A.colidx, A.vals)
-
-    def op_cheby_update_(a, c, first, dinv, r, d, x):
-        cheby_update(a, c, dinv, r, d, x, first)
-
-    def op_h_chebyshev(h, x, b, degree, lmax, ratio):
-        """One Chebyshev step of `degree` on [lmax / ratio, lmax] (lmax <= 0: the Gershgorin bound)."""
-        from .hierarchy import chebyshev_coefficients
-        ent = _get(h)
-        A = ent["A"]
-        if lmax <= 0.0:
-            lmax = float(op_h_gershgorin(h).item())
-        coef = chebyshev_coefficients(lmax, ratio, int(degree))
-        if stencil_cheby_available(A) and len(coef) <= FUSED_MAX_SWEEPS:
-            out = torch.empty_like(x)
-            stencil_cheby(A, x, b, coef, out)
-            return out
-        if ent.get("dinv") is None:
-            ent["dinv"] = csr_inverse_diagonal(A)
-        out, r, d = x.clone(), torch.empty_like(x), torch.empty_like(x)
-        for k, (a, c) in enumerate(coef):
-            csr_residual_norm2(A, out, b, r, None, None)
-            cheby_update(a, c, ent["dinv"], r, d, out, first=(k == 0))
-        return out
-
-    def op_h_gs_(h, x, b, sweeps):
-        ent = _get(h)
-        A = ent["A"]
-        if stencil_gs_available(A):
-            stencil_gs(A, x, b, int(sweeps))
-            stencil_gs_check(A)          # one 4-byte read: a timed-out band must not return a wrong iterate silently
-            return
-        if ent["gs"] is None:
-            import scipy.sparse as sp
-            pat = sp.csr_matrix((np.ones(A.nnz, dtype=np.int8), A.colidx.cpu().numpy(), A.rowptr.cpu().numpy()), shape=A.shape)
-            ent["gs"] = build_gs_schedule(pat, "lexicographic", A.device)
-        csr_gs_schedule(A, x, b, ent["gs"], int(sweeps))
-
-    def op_h_gs_backward_(h, x, b, sweeps):
-        ent = _get(h)
-        A = ent["A"]
-        if stencil_gs_available(A, "backward"):
-            stencil_gs(A, x, b, int(sweeps), "backward")
-            stencil_gs_check(A)
-            return
-        if ent["gs_backward"] is None:
-            if ent["gs"] is None:
-                import scipy.sparse as sp
-                pat = sp.csr_matrix((np.ones(A.nnz, dtype=np.int8), A.colidx.cpu().numpy(), A.rowptr.cpu().numpy()),
-                                    shape=A.shape)
-                ent["gs"] = build_gs_schedule(pat, "lexicographic", A.device)
-            ent["gs_backward"] = ent["gs"].reversed()
-        csr_gs_schedule(A, x, b, ent["gs_backward"], int(sweeps))
-
-    lib.impl("spgemm", op_spgemm, "CUDA")
-    lib.impl("csr_transpose", op_transpose, "CUDA")
-    lib.impl("dense_gemv", op_dense_gemv, "CUDA")
-    lib.impl("operator_create", op_create, "CUDA")
-    lib.impl("operator_format", op_format, "CompositeExplicitAutograd")
-    lib.impl("operator_free", op_free, "CompositeExplicitAutograd")
-    lib.impl("operator_spmv", op_h_spmv, "CUDA")
-    lib.impl("operator_residual", op_h_residual, "CUDA")
-    lib.impl("operator_jacobi", op_h_jacobi, "CUDA")
-    lib.impl("operator_chebyshev", op_h_chebyshev, "CUDA")
-    lib.impl("operator_gershgorin", op_h_gershgorin, "CompositeExplicitAutograd")
-    lib.impl("cheby_update_", op_cheby_update_, "CUDA")
-    lib.impl("csr_gershgorin", op_gershgorin, "CUDA")
-    lib.impl("line_factor", op_line_factor, "CUDA")
-    lib.impl("line_solve", op_line_solve, "CUDA")
-    lib.impl("operator_gauss_seidel_", op_h_gs_, "CUDA")
-    lib.impl("operator_gauss_seidel_backward_", op_h_gs_backward_, "CUDA")
-
-    # ---- the fused Gram-Schmidt passes of the Krylov solvers: V is a 2-D contiguous basis, k its rows in use ----------
-    lib.define("multi_dot(Tensor V, int k, Tensor w) -> Tensor")
-    lib.define("multi_axpy_(Tensor V, int k, Tensor coef, Tensor(a!) w, bool subtract) -> Tensor")
-
-    def op_multi_dot(V, k, w):
-        part = torch.empty(multi_partials_count(w.numel(), k), dtype=F64, device=w.device)
-        out = torch.zeros(int(k), dtype=F64, device=w.device)
-        multi_dot(V, k, w, part, out)
-        return out
-
-    def op_multi_axpy_(V, k, coef, w, subtract):
-        part = torch.empty(multi_partials_count(w.numel(), k), dtype=F64, device=w.device)
-        n2 = torch.zeros(1, dtype=F64, device=w.device)
-        multi_axpy(V, k, coef, w, part, n2, subtract=bool(subtract))
-        return n2
-
-    lib.impl("multi_dot", op_multi_dot, "CUDA")
-    lib.impl("multi_axpy_", op_multi_axpy_, "CUDA")
-    register_torch_ops._lib = lib        # keep alive
-    _registered = True
+    """Expose the kernels as PyTorch custom ops taking ROCm tensors, torch.ops.lmg.* (torch_ops.py)."""
+    from . import torch_ops          # (imports this module)
+    torch_ops.register()

@@ -25,9 +25,8 @@ import numpy as np
 import torch
 
 from .. import ops
-from ..hierarchy import line_config
 from ..ops import F64
-from ._precond import make_apply
+from ._precond import check_smoother, make_apply
 from .Solver import IterativeSolver, on_device
 
 
@@ -42,11 +41,7 @@ class CG(IterativeSolver):
     def solve(self, max_iterations=1000, error=1e-08, initial_guess=None, *, preconditioner=None,
               precond_steps=2, precond_omega=0.8, precond_smoother="Jacobi", precond_cycle_shape="V",
               precond_line_dir="xy", precond_line_order="zebra"):
-        if precond_smoother not in ("Jacobi", "GaussSeidel", "Chebyshev", "Line"):
-            raise ValueError("precond_smoother must be 'Jacobi', 'GaussSeidel', 'Chebyshev' or 'Line', got %r"
-                             % (precond_smoother,))
-        if precond_smoother == "Line":
-            line_config(precond_line_dir, precond_line_order)
+        check_smoother(precond_smoother, precond_line_dir, precond_line_order)
         if precond_cycle_shape not in ("V", "W"):
             raise ValueError("precond_cycle_shape must be 'V' or 'W' (CG needs a symmetric preconditioner), got %r"
                              % (precond_cycle_shape,))

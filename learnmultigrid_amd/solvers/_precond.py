@@ -7,7 +7,7 @@ SMOOTHERS = ("Jacobi", "GaussSeidel", "Chebyshev", "Line")
 
 
 def check_smoother(smoother, line_dir, line_order):
-    """The smoother checks CG.solve makes (it keeps its own copy, word for word as before), for the other Krylov solvers."""
+    """The smoother name and, for "Line", its keywords: what CG.solve and GMRES.solve check before any device work."""
     if smoother not in SMOOTHERS:
         raise ValueError("precond_smoother must be 'Jacobi', 'GaussSeidel', 'Chebyshev' or 'Line', got %r" % (smoother,))
     if smoother == "Line":

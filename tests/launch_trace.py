@@ -1,0 +1,366 @@
+"""TEST-ONLY: a recording wrapper around an ops namespace, and the launch traces of the smoothing paths on CPU tensors.
+
+Tracer(ops_mod).ops is a namespace with every function of `ops_mod` wrapped: each call is logged as one line
+    name param=value ...
+with the arguments bound to the parameter names of the wrapped function (defaults filled in, so a flag left out and a
+flag passed at its default read the same).  A matrix reads as ROWSxCOLS, a vector the test has named (Tracer.name: the
+buffers of a level, "L1.X" / "L1.T" for the two iterate buffers by the slot they start in) as that name, any other
+vector as "prev" when the previous call wrote it and "t" otherwise, a coefficient table as coef[degree], None, numbers
+and strings as themselves.  Predicates (*_available, *_selected) and partials_count only answer questions and are not
+logged.  all_traces() is what tests/golden/launch_traces.json holds (tools/launch_traces.py writes it).
+"""
+import inspect
+import json
+import os
+import socket
+import sys
+import types
+
+import numpy as np
+import torch
+
+# the parameter each op writes its result to (only used to tell "prev" from "t" among unnamed vectors)
+WRITES = {"csr_jacobi": "x_out", "vmul": "out", "stencil_smooth": "x_out", "stencil_cheby": "x_out",
+          "stencil_smooth_turnaround": "x_out", "stencil_gs": "x", "csr_gs_schedule": "x", "cheby_update": "x",
+          "line_solve": "x", "zero": "x", "csr_spmv": "y", "axpby": "y", "copy": "dst", "csr_residual_norm2": "r",
+          "gather": "buf", "scatter": "x"}
+QUIET = ("_available", "_selected")
+
+
+def _key(t):
+    return (t.data_ptr(), t.numel())
+
+
+class Tracer:
+    def __init__(self, ops_mod, **extra):
+        self.log = []
+        self.names = {}
+        self._last = None
+        self.ops = types.SimpleNamespace()
+        members = {k: getattr(ops_mod, k) for k in dir(ops_mod) if not k.startswith("__")}
+        members.update(extra)
+        for k, v in members.items():
+            logged = inspect.isfunction(v) and not k.startswith("_") and not k.endswith(QUIET) and k != "partials_count"
+            setattr(self.ops, k, self._wrap(k, v) if logged else v)
+
+    def name(self, t, label):
+        self.names[_key(t)] = label
+
+    def name_level(self, lev, prefix):
+        for attr, label in (("x", "X"), ("tmp", "T"), ("b", "b"), ("r", "r"), ("d", "d"), ("dinv", "dinv")):
+            t = getattr(lev, attr, None)
+            if t is not None:
+                self.name(t, "%s.%s" % (prefix, label))
+
+    def clear(self):
+        del self.log[:]
+        self._last = None
+
+    def mark(self, text):
+        self.log.append("-- " + text)
+
+    def _show(self, v):
+        if v is None or isinstance(v, (bool, int, str)):
+            return str(v)
+        if isinstance(v, float):
+            return repr(v)
+        if isinstance(v, torch.Tensor):
+            k = _key(v)
+            return self.names.get(k, "prev" if k == self._last else "t")
+        if hasattr(v, "shape") and (hasattr(v, "rowptr") or hasattr(v, "indptr")):
+            return "%dx%d" % tuple(v.shape)
+        if isinstance(v, (list, tuple)):
+            if v and all(isinstance(e, tuple) and all(isinstance(f, float) for f in e) for e in v):
+                return "coef[%d]" % len(v)
+            return "(" + ",".join(self._show(e) for e in v) + ")"
+        return type(v).__name__
+
+    def _wrap(self, name, fn):
+        sig = inspect.signature(fn)
+
+        def traced(*a, **k):
+            bound = sig.bind(*a, **k)
+            bound.apply_defaults()
+            self.log.append(" ".join([name] + ["%s=%s" % (p, self._show(v)) for p, v in bound.arguments.items()]))
+            out = bound.arguments.get(WRITES.get(name))
+            self._last = _key(out) if isinstance(out, torch.Tensor) else None
+            return fn(*a, **k)
+        return traced
+
+
+# ---- the ops namespaces the traces run on ------------------------------------------------------------------------------
+def trace_shim(fused_max_rows=0):
+    """cpu_ops_shim with the Chebyshev and Line ops, multicolour schedules, and -- on matrices of at most fused_max_rows
+    rows (None: all, 0: none; then the names are absent) -- stand-ins of the fused Jacobi and Chebyshev passes, the
+    turnaround pass and the wavefront Gauss-Seidel kernel."""
+    import cheby_ops_shim
+    import line_ops_shim
+    from learnmultigrid_amd import ops
+    from oracle import kernels as K
+    from test_cycle_shapes_cpu import _sp, fused_shim
+    ns = cheby_ops_shim.base() if fused_max_rows == 0 else cheby_ops_shim.fused(fused_max_rows)
+    ln = line_ops_shim.base()
+    ns.line_factor, ns.line_solve = ln.line_factor, ln.line_solve
+
+    def build_gs_schedule(A_scipy_csr, kind, device):
+        # (the product's host-side builder: colour classes and reversed() exist; the shim sweeps the rows of a schedule
+        # in ascending order whatever its sets are, which is all a trace needs)
+        return ops.build_gs_schedule(A_scipy_csr, kind, device)
+
+    ns.build_gs_schedule = build_gs_schedule
+    if fused_max_rows == 0:
+        return ns
+    ok = (lambda A: True) if fused_max_rows is None else (lambda A: A.shape[0] <= fused_max_rows)
+    fs = fused_shim(True)
+    ns.stencil_smooth, ns.stencil_smooth_turnaround = fs.stencil_smooth, fs.stencil_smooth_turnaround
+    ns.stencil_smooth_available = ok
+    ns.stencil_smooth_prolong_available = ns.stencil_smooth_restrict_available = lambda A, M: ok(A)
+    ns.stencil_smooth_turnaround_selected = lambda A, P_, R: ok(A)
+    ns.stencil_gs_available = lambda A, direction="forward": ok(A)
+
+    def stencil_gs(A, x, b, sweeps=1, direction="forward"):
+        rows = np.flatnonzero(np.diff(A.rowptr.numpy())).astype(np.int32)          # (ghost rows of a local block are empty)
+        rows = rows if direction == "forward" else rows[::-1].copy()
+        xx = x.numpy()
+        for _ in range(int(sweeps)):
+            K.gs_rows(_sp(A), xx, b.numpy(), rows)
+
+    ns.stencil_gs = stencil_gs
+    ns.stencil_gs_check = lambda A: None
+    return ns
+
+
+FUSED = {"none": 0, "small": 289, "all": None}        # trace_shim(fused_max_rows): no level, the 17 x 17 level, every level
+
+
+def _problem():
+    from learnmultigrid_amd import problems as P
+    A, rhs = P.poisson_2d_structured(32)
+    return A, rhs, P.geometric_hierarchy_2d(33, 3)
+
+
+SMOOTHERS = ([("Jacobi", s, {}) for s in (1, 3, 4, 7)]
+             + [("GaussSeidel", 2, {"gs_mode": mode, "gs_sweep": sweep})
+                for mode in ("lexicographic", "multicolor")
+                for sweep in (("forward", "forward"), ("forward", "backward"), "symmetric")]
+             + [("Chebyshev", d, {}) for d in (2, 4)]
+             + [("Line", 1, {"line_dir": "xy", "line_order": "zebra"})])
+
+
+def hierarchy_traces():
+    """prepare_smoother, then one cycle, of a 3-level hierarchy on the 33 x 33 5-point problem."""
+    from learnmultigrid_amd.hierarchy import Hierarchy
+    A, rhs, hier = _problem()
+    out = {}
+    for fname, max_rows in FUSED.items():
+        for smoother, steps, kw in SMOOTHERS:
+            for shape in ("V", "W"):
+                for zero in (False, True):
+                    tr = Tracer(trace_shim(max_rows))
+                    H = Hierarchy(A.copy(), hier, "cpu", ops_mod=tr.ops)
+                    H.levels[0].b.copy_(torch.from_numpy(rhs.ravel().copy()))
+                    for l, lev in enumerate(H.levels):
+                        tr.name_level(lev, "L%d" % l)
+                    tr.clear()
+                    prep = {k: v for k, v in kw.items() if k != "gs_mode"}
+                    H.prepare_smoother(smoother, kw.get("gs_mode", "lexicographic"), **prep)
+                    for l, lev in enumerate(H.levels):               # (the Chebyshev step vectors exist now)
+                        tr.name_level(lev, "L%d" % l)
+                    tr.mark("cycle")
+                    H.cycle(smoother, steps, 0.8, shape=shape, x_is_zero=zero, **kw)
+                    tag = "/".join(str(v) for v in kw.values())
+                    out["hierarchy %s %s%d%s %s zero=%d" % (fname, smoother, steps, " " + tag if tag else "", shape, zero)] = tr.log
+    return out
+
+
+# ---- the distributed cycle: the configurations of tests/test_dist_cpu.py -------------------------------------------------
+DIST_JACOBI = [(2, 32, 4, 200, 2, 6, "geometric", 0), (2, 48, 3, 1, 2, 6, "geometric", 0), (3, 40, 4, 300, 2, 6, "geometric", 0),
+               (2, 48, 3, 1, 3, 8, "geometric", 0), (2, 48, 3, 1, 3, 6, "geometric", 0), (2, 48, 3, 1, 3, 5, "geometric", 0),
+               (2, 48, 3, 1, 4, 5, "geometric", 0), (3, 40, 4, 300, 2, 1, "geometric", 0), (4, 64, 4, 500, 3, 8, "geometric", 0),
+               (8, 128, 4, 2000, 3, 8, "geometric", 0),
+               (2, 48, 3, 1, 2, 8, "learned", 0), (2, 48, 3, 1, 2, 12, "learned", 0), (2, 48, 3, 1, 2, 4, "learned", 0),
+               (2, 48, 3, 1, 3, 8, "geometric", None), (2, 48, 3, 1, 4, 8, "geometric", None)]    # ... and on the fused stand-ins
+DIST_GS = [(2, 32, 3, 200, 1, 0), (3, 40, 3, 300, 1, 0), (2, 48, 3, 1, 6, 0),
+           (2, 32, 3, 200, 1, None), (2, 48, 3, 1, 6, None)]                                       # ... and on the wavefront stand-in
+
+
+def _free_port():
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    p = s.getsockname()[1]
+    s.close()
+    return p
+
+
+def _dist_key(job, rank):
+    (world, m, levels, rb, steps, hd, transfer, fused), gs = job
+    return ("dist %s world=%d m=%d levels=%d below=%d steps=%d halo=%d %s fused=%s rank=%d"
+            % ("GaussSeidel" if gs else "Jacobi", world, m, levels, rb, steps, hd, transfer, "none" if fused == 0 else "all", rank))
+
+
+def _dist_worker(rank, world, port, jobs, out_dir):
+    """Every job of one world size in one process group (a spawn costs more than the cycles)."""
+    import json
+    import scipy.sparse as sp
+    import torch.distributed as dist
+    from learnmultigrid_amd import problems as P
+    from learnmultigrid_amd.dist import DistributedVCycle
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    out = {}
+    try:
+        for job in jobs:
+            (_, m, levels, replicate_below, steps, halo_depth, transfer, fused), gs = job
+            A, rhs = P.poisson_2d_structured(m)
+            if transfer == "geometric":
+                hier = P.geometric_hierarchy_2d(m + 1, levels)
+            else:
+                hier = []
+                for li, sz in enumerate(P.level_sizes(m + 1, levels)[:-1]):
+                    l2 = P.pseudo_l2_interpolator_1d(sz)
+                    hier.append(P.learned_like(sp.kron(l2, l2).tocsr(), 43 + li))
+            tr = Tracer(trace_shim(fused))
+            D = DistributedVCycle.from_problem(A, hier, "cpu", ops_mod=tr.ops, grid_side=m + 1,
+                                               replicate_below=replicate_below, halo_depth=halo_depth)
+            for l, d in enumerate(D.dl):
+                tr.name_level(d, "D%d" % l)
+            for l, lev in enumerate(D.full.levels):
+                tr.name_level(lev, "L%d" % l)
+            tr.name(D.ag_send, "ag_send")
+            tr.name(D.ag_recv, "ag_recv")
+
+            def traced_exchange(d, vec, D=D, tr=tr, exchange=D.exchange):
+                tr.log.append("exchange level=%d vec=%s" % (D.dl.index(d), tr._show(vec)))
+                exchange(d, vec)
+
+            D.exchange = traced_exchange
+            D.set_rhs(rhs)
+            tr.clear()
+            if gs:
+                D._smooth_gs(D.dl[0], 3, False)
+                tr.mark("cycle")
+                D.cycle("GaussSeidel", 2)
+            else:
+                D.cycle("Jacobi", steps, 0.8)
+            out[_dist_key(job, rank)] = tr.log
+        with open(os.path.join(out_dir, "trace_%d.json" % rank), "w") as f:
+            json.dump(out, f)
+    finally:
+        dist.destroy_process_group()
+
+
+def dist_traces():
+    import json
+    import tempfile
+    import torch.multiprocessing as mp
+    out = {}
+    jobs = [(c, False) for c in DIST_JACOBI] + [((w, m, lv, rb, 2, hd, "geometric", fz), True) for w, m, lv, rb, hd, fz in DIST_GS]
+    for world in sorted({j[0][0] for j in jobs}):
+        with tempfile.TemporaryDirectory() as tmp:
+            mp.spawn(_dist_worker, args=(world, _free_port(), [j for j in jobs if j[0][0] == world], tmp), nprocs=world, join=True)
+            for r in range(world):
+                with open(os.path.join(tmp, "trace_%d.json" % r)) as f:
+                    out.update(json.load(f))
+    return out
+
+
+# ---- the operator handles of torch.ops.lmg ---------------------------------------------------------------------------------
+def _parent_operator(ns):
+    """The smoothing closures of register_torch_ops as they stood in ops.py before torch_ops.py existed, run on an ops
+    namespace in place of the module's globals: jacobi / chebyshev / gauss_seidel_ with the signatures of
+    torch_ops.Operator.  Only used to write the golden file from a checkout without torch_ops.py."""
+    import ast
+    import learnmultigrid_amd.ops as real
+    tree = ast.parse(open(real.__file__).read())
+    reg = next(n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == "register_torch_ops")
+    want = ("_csr", "op_gershgorin", "op_h_gershgorin", "op_h_jacobi", "op_h_chebyshev", "op_h_gs_", "op_h_gs_backward_")
+    mod = ast.Module(body=[n for n in reg.body if isinstance(n, ast.FunctionDef) and n.name in want], type_ignores=[])
+    g = {"stencil_cheby_available": lambda A: False, "stencil_gs_available": lambda A, direction="forward": False}
+    g.update(vars(ns))
+    g.update(torch=torch, np=np, F64=real.F64, DeviceCSR=real.DeviceCSR, __package__="learnmultigrid_amd", __name__="parent")
+
+    def make(A):
+        ent = {"A": A, "gs": None, "gs_backward": None}
+        env = dict(g, _get=lambda h: ent)
+        exec(compile(mod, "ops.py:register_torch_ops", "exec"), env)
+        return types.SimpleNamespace(
+            jacobi=lambda o, x, b, omega, sweeps: env["op_h_jacobi"](0, x, b, omega, sweeps),
+            chebyshev=lambda o, x, b, degree, lmax, ratio: env["op_h_chebyshev"](0, x, b, degree, lmax, ratio),
+            gauss_seidel_=lambda o, x, b, sweeps, direction="forward":
+                env["op_h_gs_" if direction == "forward" else "op_h_gs_backward_"](0, x, b, sweeps))
+    return make
+
+
+def operator_traces():
+    from learnmultigrid_amd.ops import DeviceCSR
+    A, rhs, _ = _problem()
+    out = {}
+    for fname, max_rows in (("none", 0), ("all", None)):
+        tr = Tracer(trace_shim(max_rows))
+        try:
+            from learnmultigrid_amd.torch_ops import Operator
+        except ImportError:
+            Operator = _parent_operator(tr.ops)
+        b = torch.from_numpy(rhs.ravel().copy())
+        x = torch.from_numpy(np.random.default_rng(7).standard_normal(A.shape[0]))
+        tr.name(x, "x")
+        tr.name(b, "b")
+
+        def fresh():
+            M = DeviceCSR.from_scipy(A.copy(), "cpu")
+            if max_rows is None:
+                M.stencil = object()             # (the ops only take the fused passes on an operator with a grid-stencil twin)
+            return Operator(M)
+
+        def record(name, run):
+            tr.clear()
+            x0 = x.clone()
+            run()
+            assert torch.equal(x, x0) or "gauss_seidel" in name
+            out["operator %s %s" % (fname, name)] = list(tr.log)
+
+        for sweeps in (0, 1, 3, 4, 7):
+            record("jacobi sweeps=%d" % sweeps, lambda: fresh().jacobi(tr.ops, x, b, 0.8, sweeps))
+        for degree in (1, 2, 3, 4):
+            record("chebyshev degree=%d" % degree, lambda: fresh().chebyshev(tr.ops, x, b, degree, 1.9, 4.0))
+        record("chebyshev degree=2 lmax=gershgorin", lambda: fresh().chebyshev(tr.ops, x, b, 2, 0.0, 4.0))
+        for direction in ("forward", "backward"):
+            for sweeps in (1, 3):
+                op = fresh()                     # (two calls on one handle: the second reuses the schedule)
+
+                def twice():
+                    op.gauss_seidel_(tr.ops, x, b, sweeps, direction)
+                    tr.mark("again")
+                    op.gauss_seidel_(tr.ops, x, b, sweeps, direction)
+                record("gauss_seidel %s sweeps=%d" % (direction, sweeps), twice)
+    return out
+
+
+def all_traces():
+    here = os.path.dirname(os.path.abspath(__file__))
+    for p in (here, os.path.dirname(here)):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    out = {}
+    out.update(hierarchy_traces())
+    out.update(dist_traces())
+    out.update(operator_traces())
+    return out
+
+
+def dump(traces, f):
+    """{case: [line, ...]} as the golden file: every distinct line once, every distinct trace once as indices into them,
+    with the cases that produce it (many cases -- ranks, shapes that do not matter to a path -- share a trace)."""
+    lines = sorted({line for t in traces.values() for line in t})
+    at = {line: i for i, line in enumerate(lines)}
+    groups = {}
+    for case in sorted(traces):
+        groups.setdefault(tuple(at[line] for line in traces[case]), []).append(case)
+    f.write('{"lines": [\n' + ",\n".join(json.dumps(line) for line in lines) + '],\n"traces": [\n')
+    f.write(",\n".join(json.dumps([cases, list(idx)]) for idx, cases in groups.items()) + "]}\n")
+
+
+def load(f):
+    doc = json.load(f)
+    return {case: [doc["lines"][i] for i in idx] for cases, idx in doc["traces"] for case in cases}
