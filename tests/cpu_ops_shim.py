@@ -2,23 +2,38 @@
 
 It lets the -m "not gpu" suite exercise the HOST logic that sits above the kernels
 (hierarchy recursion, row-block partitioning, ghost layouts, halo plans, collectives over
-gloo) by routing every kernel call to the CPU oracle.  It lives under tests/ on purpose:
+gloo, the Krylov loop) by routing every kernel call to the CPU oracle and the CPU twins of
+the smoothers (tests/chebyshev_ref.py, tests/line_ref.py).  It lives under tests/ on purpose:
 the product package never imports it and has no CPU path.
+
+The rule of this module.  Every public function and class at module level stands for the op of
+the same name in learnmultigrid_amd.ops and takes a prefix of its parameters
+(tests/test_shim_signatures_cpu.py); none of them records its calls.  The module is usable as it
+is (ops_mod=shim).  The package reads a name that is ABSENT as "not offered", so what the plain
+stand-in does not offer must stay absent here: every stencil_* name, gs_prepare,
+FUSED_MAX_SWEEPS, CapturedGraph, gemm, coarse_front and coarse_back.  Those, and everything that
+records, exist only on the namespaces the three factories below return (FACTORIES; they are the
+module's own tools and not part of any namespace):
+
+    namespace(**replace)   a fresh copy of the module with an empty `calls` list
+    recording_line()       ... whose line_factor / line_solve / csr_residual_norm2 / copy record
+    fused(passes, ...)     ... with stand-ins of the fused passes, which record
 """
+import sys as _sys
+import types as _types
+
 import numpy as np
 import scipy.sparse as sp
 import torch
 
+import chebyshev_ref as _CR
+import line_ref as _LR
 from learnmultigrid_amd.ops import DeviceCSR, F64, I32   # pure-torch container, device agnostic
 from oracle import kernels as K
+from support import to_numpy as _np, to_scipy as _sp
 
-
-def _np(t):
-    return t.numpy()
-
-
-def _sp(A):
-    return sp.csr_matrix((_np(A.vals), _np(A.colidx), _np(A.rowptr)), shape=A.shape)
+FACTORIES = ("namespace", "recording_line", "fused")
+_MAX_VECTORS = 65
 
 
 def partials_count(n):
@@ -139,11 +154,11 @@ def coarse_front_gather(M, b, idx, y, tail_idx, tail_out):
     _np(tail_out)[:] = bn[_np(tail_idx)]
 
 
-def coarse_back_gather(Wm, x_tail, xidx, z, alpha, oidx, tail_idx, out, accumulate):
-    k, s, cwp = Wm.shape
+def coarse_back_gather(W, x_tail, xidx, z, alpha, oidx, tail_idx, out, accumulate):
+    k, s, cwp = W.shape
     xn, wi, zn, gi, on = _np(x_tail), _np(xidx).reshape(k, cwp), _np(z), _np(oidx), _np(out)
     for i in range(k):
-        v = zn[i * s:(i + 1) * s] + alpha * K.dense_gemv(np.ascontiguousarray(_np(Wm[i])), np.ascontiguousarray(xn[wi[i]]))
+        v = zn[i * s:(i + 1) * s] + alpha * K.dense_gemv(np.ascontiguousarray(_np(W[i])), np.ascontiguousarray(xn[wi[i]]))
         g = gi[i * s:(i + 1) * s]
         ok = g >= 0
         on[g[ok]] = v[ok] + on[g[ok]] if accumulate else v[ok]
@@ -190,3 +205,190 @@ def csr_gs_schedule(A, x, b, sched, sweeps=1):
     for _ in range(int(sweeps)):
         K.lib().orc_csr_gs_rows(rp, ci, va, xx, np.ascontiguousarray(_np(b)), rows, rows.size)
     _np(x)[:] = xx
+
+
+def cheby_update(a, c, dinv, r, d, x, first=False):
+    z = _np(dinv) * _np(r)
+    dn = c * z if first else a * _np(d) + c * z
+    _np(d)[:] = dn
+    _np(x)[:] = _np(x) + dn
+
+
+def csr_gershgorin(A, out):
+    _np(out)[0] = _CR.gershgorin(_sp(A))
+
+
+def line_factor(A, W, dir):
+    fac, flags = _LR.factor(_sp(A), int(W), dir)
+    if flags & _LR.COUPLED:
+        raise ValueError("a non-zero entry couples two x-lines (an entry across the end of a line)")
+    if flags & _LR.PIVOT:
+        raise ValueError("a zero or non-finite pivot in the %s-line systems" % dir)
+    return tuple(torch.from_numpy(v) for v in fac)
+
+
+def line_solve(W, dir, first, step, fac, r, omega, x):
+    xn, rn = _LR.solve(tuple(_np(v) for v in fac), int(W), dir, int(first), int(step), _np(r), float(omega), _np(x))
+    _np(x)[:] = xn
+    _np(r)[:] = rn
+
+
+def krylov_max_vectors():
+    return _MAX_VECTORS
+
+
+def multi_partials_count(n, k):
+    return 1024 * max(int(k), 1)
+
+
+def multi_dot(V, k, w, partials, out):
+    n = w.numel()
+    assert V.dim() == 2 and V.is_contiguous() and 0 <= k <= min(V.shape[0], _MAX_VECTORS) and V.shape[1] >= n
+    if k:
+        _np(out)[:k] = _np(V)[:k, :n] @ _np(w)
+
+
+def multi_axpy(V, k, coef, w, partials=None, norm2=None, subtract=True):
+    n = w.numel()
+    assert V.dim() == 2 and V.is_contiguous() and 0 <= k <= min(V.shape[0], _MAX_VECTORS) and V.shape[1] >= n
+    ww, c = _np(w), _np(coef).copy()            # (coef may be a view of the buffer norm2 lives in)
+    for j in range(k):
+        ww[:] = ww - c[j] * _np(V)[j, :n] if subtract else ww + c[j] * _np(V)[j, :n]
+    if norm2 is not None:
+        assert partials is not None
+        _np(norm2)[0] = float(ww @ ww)
+
+
+# ---- namespaces: copies of the module that may offer more, and record ----------------------------------------------------
+def namespace(**replace):
+    """A fresh namespace with everything the module offers, an empty `calls` list, and the replacements given by keyword."""
+    shim = _sys.modules[__name__]
+    ns = _types.SimpleNamespace(**{k: getattr(shim, k) for k in dir(shim) if not k.startswith("__") and k not in FACTORIES})
+    ns.calls = []
+    vars(ns).update(replace)
+    return ns
+
+
+def recording_line():
+    """Every line_factor / line_solve / csr_residual_norm2 / copy call is appended to ns.calls, so that a test can read the
+    launch sequence of a cycle: ("factor", n, W, dir), ("solve", n, dir, first, step, omega), ("residual", n), ("copy", n)."""
+    ns = namespace()
+
+    def rec_line_factor(A, W, dir):
+        ns.calls.append(("factor", A.shape[0], int(W), dir))
+        return line_factor(A, W, dir)
+
+    def rec_line_solve(W, dir, first, step, fac, r, omega, x):
+        line_solve(W, dir, first, step, fac, r, omega, x)
+        ns.calls.append(("solve", x.numel(), dir, int(first), int(step), float(omega)))
+
+    def rec_csr_residual_norm2(A, x, b, r, partials, norm2):
+        csr_residual_norm2(A, x, b, r, partials, norm2)
+        ns.calls.append(("residual", A.shape[0]))
+
+    def rec_copy(src, dst):
+        copy(src, dst)
+        ns.calls.append(("copy", src.numel()))
+
+    ns.line_factor, ns.line_solve, ns.csr_residual_norm2, ns.copy = rec_line_factor, rec_line_solve, rec_csr_residual_norm2, rec_copy
+    return ns
+
+
+def _fused_pass(ns, sweep, A, x_in, b, x_out, r_out, prolong, restrict, *tag):
+    """What a fused pass computes, in the order of the separate launches and in oracle arithmetic: the correction
+    (prolong = (P, e)), x = sweep(A, x, b), the residual (r_out), its restriction (restrict = (R, b_coarse)); the call is
+    appended to ns.calls as (kind, n) + tag."""
+    assert prolong is None or restrict is None
+    As = _sp(A)
+    bb = _np(b)
+    x = np.zeros(A.shape[0]) if x_in is None else _np(x_in).copy()
+    if prolong is not None:
+        x = K.spmv(_sp(prolong[0]), _np(prolong[1]), x, 1.0, 1.0)
+    x = sweep(As, x, bb)
+    _np(x_out)[:] = x
+    r, _ = K.residual(As, x, bb)
+    if r_out is not None:
+        _np(r_out)[:] = r
+    if restrict is not None:
+        _np(restrict[1])[:] = K.matvec(_sp(restrict[0]), r)
+    ns.calls.append(("prolong" if prolong is not None else "restrict" if restrict is not None else "plain", A.shape[0]) + tag)
+
+
+def _product_gs_schedule(A_scipy_csr, kind, device):
+    # (the product's host-side builder: colour classes and reversed() exist; the shim sweeps the rows of a schedule in
+    # ascending order whatever its sets are, which is all a trace needs)
+    from learnmultigrid_amd import ops
+    return ops.build_gs_schedule(A_scipy_csr, kind, device)
+
+
+def fused(passes="jacobi", max_rows=None, turnaround=True):
+    """A namespace with stand-ins of the fused passes on matrices of at most max_rows rows (None: all); every fused call
+    is recorded in ns.calls.  passes:
+      "jacobi"  the Jacobi passes, recorded as (kind, n), kind in "plain" / "prolong" / "restrict"; the turnaround pass
+                (the correcting pass, then the restricting pass: ("turnaround", n) in place of the two) is selected
+                where `turnaround` is true
+      "cheby"   the Chebyshev pass, recorded as (kind, n, degree, x_is_zero).  The Jacobi predicates exist and say yes,
+                but there is no Jacobi pass and the turnaround raises: the Chebyshev cycle must not pick them up
+      "all"     both, the wavefront Gauss-Seidel stand-in and the package's own build_gs_schedule (multicolour
+                schedules): what the launch traces run on.  max_rows = 0: the schedules only, no fused name exists"""
+    if passes not in ("jacobi", "cheby", "all"):
+        raise ValueError("passes must be 'jacobi', 'cheby' or 'all', not %r" % (passes,))
+    ns = namespace()
+    if passes == "all":
+        ns.build_gs_schedule = _product_gs_schedule
+        if max_rows == 0:
+            return ns
+    ok = (lambda A: True) if max_rows is None else (lambda A: A.shape[0] <= max_rows)
+    ns.FUSED_MAX_SWEEPS = 3
+    if passes in ("cheby", "all"):
+        ns.stencil_cheby_available = ok
+        ns.stencil_cheby_prolong_available = lambda A, P: ok(A)
+        ns.stencil_cheby_restrict_available = lambda A, R: ok(A)
+
+        def stencil_cheby(A, x_in, b, coef, x_out, r_out=None, prolong=None, restrict=None):
+            assert 1 <= len(coef) <= 3
+            _fused_pass(ns, lambda As, x, bb: _CR.cheby_step(As, x, bb, coef), A, x_in, b, x_out, r_out, prolong, restrict,
+                        len(coef), x_in is None)
+
+        ns.stencil_cheby = stencil_cheby
+    if passes == "cheby":
+        ns.stencil_smooth_available = lambda A: True
+        ns.stencil_smooth_turnaround_selected = lambda A, P, R: True
+
+        def stencil_smooth_turnaround(A, x_in, b, omega, sweeps_post, sweeps_pre, x_out, prolong, restrict):
+            raise AssertionError("the Chebyshev cycle has no turnaround pass")
+
+        ns.stencil_smooth_turnaround = stencil_smooth_turnaround
+        return ns
+
+    def stencil_smooth(A, x_in, b, omega, sweeps, x_out, r_out=None, prolong=None, restrict=None):
+        def sweep(As, x, bb):
+            for _ in range(sweeps):
+                x = K.jacobi(As, x, bb, omega)
+            return x
+        _fused_pass(ns, sweep, A, x_in, b, x_out, r_out, prolong, restrict)
+
+    def stencil_smooth_turnaround(A, x_in, b, omega, sweeps_post, sweeps_pre, x_out, prolong, restrict):
+        tmp = torch.empty_like(x_out)
+        stencil_smooth(A, x_in, b, omega, sweeps_post, tmp, prolong=prolong)
+        stencil_smooth(A, tmp, b, omega, sweeps_pre, x_out, restrict=restrict)
+        ns.calls[-2:] = [("turnaround", A.shape[0])]
+
+    ns.stencil_smooth, ns.stencil_smooth_turnaround = stencil_smooth, stencil_smooth_turnaround
+    ns.stencil_smooth_available = ok
+    ns.stencil_smooth_prolong_available = lambda A, P: ok(A)
+    ns.stencil_smooth_restrict_available = lambda A, R: ok(A)
+    ns.stencil_smooth_turnaround_selected = lambda A, P, R: turnaround and ok(A)
+    if passes == "all":
+        ns.stencil_gs_available = lambda A, direction="forward": ok(A)
+        ns.stencil_gs_check = lambda A: None
+
+        def stencil_gs(A, x, b, sweeps=1, direction="forward"):
+            rows = np.flatnonzero(np.diff(_np(A.rowptr))).astype(np.int32)          # (ghost rows of a local block are empty)
+            rows = rows if direction == "forward" else rows[::-1].copy()
+            xx = _np(x)
+            for _ in range(int(sweeps)):
+                K.gs_rows(_sp(A), xx, _np(b), rows)
+
+        ns.stencil_gs = stencil_gs
+    return ns

@@ -12,12 +12,13 @@ logged.  all_traces() is what tests/golden/launch_traces.json holds (tools/launc
 import inspect
 import json
 import os
-import socket
 import sys
 import types
 
 import numpy as np
 import torch
+
+from support import free_port
 
 # the parameter each op writes its result to (only used to tell "prev" from "t" among unnamed vectors)
 WRITES = {"csr_jacobi": "x_out", "vmul": "out", "stencil_smooth": "x_out", "stencil_cheby": "x_out",
@@ -90,44 +91,11 @@ class Tracer:
 
 # ---- the ops namespaces the traces run on ------------------------------------------------------------------------------
 def trace_shim(fused_max_rows=0):
-    """cpu_ops_shim with the Chebyshev and Line ops, multicolour schedules, and -- on matrices of at most fused_max_rows
-    rows (None: all, 0: none; then the names are absent) -- stand-ins of the fused Jacobi and Chebyshev passes, the
-    turnaround pass and the wavefront Gauss-Seidel kernel."""
-    import cheby_ops_shim
-    import line_ops_shim
-    from learnmultigrid_amd import ops
-    from oracle import kernels as K
-    from test_cycle_shapes_cpu import _sp, fused_shim
-    ns = cheby_ops_shim.base() if fused_max_rows == 0 else cheby_ops_shim.fused(fused_max_rows)
-    ln = line_ops_shim.base()
-    ns.line_factor, ns.line_solve = ln.line_factor, ln.line_solve
-
-    def build_gs_schedule(A_scipy_csr, kind, device):
-        # (the product's host-side builder: colour classes and reversed() exist; the shim sweeps the rows of a schedule
-        # in ascending order whatever its sets are, which is all a trace needs)
-        return ops.build_gs_schedule(A_scipy_csr, kind, device)
-
-    ns.build_gs_schedule = build_gs_schedule
-    if fused_max_rows == 0:
-        return ns
-    ok = (lambda A: True) if fused_max_rows is None else (lambda A: A.shape[0] <= fused_max_rows)
-    fs = fused_shim(True)
-    ns.stencil_smooth, ns.stencil_smooth_turnaround = fs.stencil_smooth, fs.stencil_smooth_turnaround
-    ns.stencil_smooth_available = ok
-    ns.stencil_smooth_prolong_available = ns.stencil_smooth_restrict_available = lambda A, M: ok(A)
-    ns.stencil_smooth_turnaround_selected = lambda A, P_, R: ok(A)
-    ns.stencil_gs_available = lambda A, direction="forward": ok(A)
-
-    def stencil_gs(A, x, b, sweeps=1, direction="forward"):
-        rows = np.flatnonzero(np.diff(A.rowptr.numpy())).astype(np.int32)          # (ghost rows of a local block are empty)
-        rows = rows if direction == "forward" else rows[::-1].copy()
-        xx = x.numpy()
-        for _ in range(int(sweeps)):
-            K.gs_rows(_sp(A), xx, b.numpy(), rows)
-
-    ns.stencil_gs = stencil_gs
-    ns.stencil_gs_check = lambda A: None
-    return ns
+    """cpu_ops_shim with multicolour schedules, and -- on matrices of at most fused_max_rows rows (None: all, 0: none; then the
+    names are absent) -- stand-ins of the fused Jacobi and Chebyshev passes, the turnaround pass and the wavefront
+    Gauss-Seidel kernel."""
+    import cpu_ops_shim
+    return cpu_ops_shim.fused("all", max_rows=fused_max_rows)
 
 
 FUSED = {"none": 0, "small": 289, "all": None}        # trace_shim(fused_max_rows): no level, the 17 x 17 level, every level
@@ -182,14 +150,6 @@ DIST_JACOBI = [(2, 32, 4, 200, 2, 6, "geometric", 0), (2, 48, 3, 1, 2, 6, "geome
                (2, 48, 3, 1, 3, 8, "geometric", None), (2, 48, 3, 1, 4, 8, "geometric", None)]    # ... and on the fused stand-ins
 DIST_GS = [(2, 32, 3, 200, 1, 0), (3, 40, 3, 300, 1, 0), (2, 48, 3, 1, 6, 0),
            (2, 32, 3, 200, 1, None), (2, 48, 3, 1, 6, None)]                                       # ... and on the wavefront stand-in
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _dist_key(job, rank):
@@ -258,7 +218,7 @@ def dist_traces():
     jobs = [(c, False) for c in DIST_JACOBI] + [((w, m, lv, rb, 2, hd, "geometric", fz), True) for w, m, lv, rb, hd, fz in DIST_GS]
     for world in sorted({j[0][0] for j in jobs}):
         with tempfile.TemporaryDirectory() as tmp:
-            mp.spawn(_dist_worker, args=(world, _free_port(), [j for j in jobs if j[0][0] == world], tmp), nprocs=world, join=True)
+            mp.spawn(_dist_worker, args=(world, free_port(), [j for j in jobs if j[0][0] == world], tmp), nprocs=world, join=True)
             for r in range(world):
                 with open(os.path.join(tmp, "trace_%d.json" % r)) as f:
                     out.update(json.load(f))
@@ -266,42 +226,13 @@ def dist_traces():
 
 
 # ---- the operator handles of torch.ops.lmg ---------------------------------------------------------------------------------
-def _parent_operator(ns):
-    """The smoothing closures of register_torch_ops as they stood in ops.py before torch_ops.py existed, run on an ops
-    namespace in place of the module's globals: jacobi / chebyshev / gauss_seidel_ with the signatures of
-    torch_ops.Operator.  Only used to write the golden file from a checkout without torch_ops.py."""
-    import ast
-    import learnmultigrid_amd.ops as real
-    tree = ast.parse(open(real.__file__).read())
-    reg = next(n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == "register_torch_ops")
-    want = ("_csr", "op_gershgorin", "op_h_gershgorin", "op_h_jacobi", "op_h_chebyshev", "op_h_gs_", "op_h_gs_backward_")
-    mod = ast.Module(body=[n for n in reg.body if isinstance(n, ast.FunctionDef) and n.name in want], type_ignores=[])
-    g = {"stencil_cheby_available": lambda A: False, "stencil_gs_available": lambda A, direction="forward": False}
-    g.update(vars(ns))
-    g.update(torch=torch, np=np, F64=real.F64, DeviceCSR=real.DeviceCSR, __package__="learnmultigrid_amd", __name__="parent")
-
-    def make(A):
-        ent = {"A": A, "gs": None, "gs_backward": None}
-        env = dict(g, _get=lambda h: ent)
-        exec(compile(mod, "ops.py:register_torch_ops", "exec"), env)
-        return types.SimpleNamespace(
-            jacobi=lambda o, x, b, omega, sweeps: env["op_h_jacobi"](0, x, b, omega, sweeps),
-            chebyshev=lambda o, x, b, degree, lmax, ratio: env["op_h_chebyshev"](0, x, b, degree, lmax, ratio),
-            gauss_seidel_=lambda o, x, b, sweeps, direction="forward":
-                env["op_h_gs_" if direction == "forward" else "op_h_gs_backward_"](0, x, b, sweeps))
-    return make
-
-
 def operator_traces():
     from learnmultigrid_amd.ops import DeviceCSR
+    from learnmultigrid_amd.torch_ops import Operator
     A, rhs, _ = _problem()
     out = {}
     for fname, max_rows in (("none", 0), ("all", None)):
         tr = Tracer(trace_shim(max_rows))
-        try:
-            from learnmultigrid_amd.torch_ops import Operator
-        except ImportError:
-            Operator = _parent_operator(tr.ops)
         b = torch.from_numpy(rhs.ravel().copy())
         x = torch.from_numpy(np.random.default_rng(7).standard_normal(A.shape[0]))
         tr.name(x, "x")

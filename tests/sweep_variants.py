@@ -3,6 +3,7 @@ test_fused_decomposition_gpu.py; no kernel reads this file): tune keys set for t
 with a guarded tail, random matrices with prescribed row lengths, and the one checker that runs SpMV, residual and Jacobi
 through ops.csr_* against oracle.kernels on the CSR matrix -- bit for bit."""
 import contextlib
+import functools
 
 import numpy as np
 import scipy.sparse as sp
@@ -10,17 +11,12 @@ import torch
 
 from learnmultigrid_amd import _lib, ops
 from oracle import kernels as K
-
-DEV = "cuda:0"
+from support import DEV, dev                         # noqa: F401  (the variant tests read them from here)
 F64 = torch.float64
 GUARD = 64                     # elements behind every output vector ...
 SENTINEL = -2.5e300            # ... that must still hold this after every launch
 ALPHA_BETA = ((1.0, 0.0), (1.0, 1.0), (-0.5, 2.0))
 OMEGAS = (1.0, 0.8)
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 @contextlib.contextmanager
@@ -128,3 +124,42 @@ def check_sweeps(tag, dA, pr, spmv_only=False):
         ops.csr_jacobi(dA, dx, db, omega, out.out)
         got = out.result((tag, "jacobi", omega))
         assert np.array_equal(got, want), (tag, "jacobi", omega, first_diff(got, want))
+
+
+# ---- the sliced-ELL cases: the fp64 and the fp32 variant tests run the same ones -------------------------------------------
+SELL_JUS = (0, 5, 7, 8, 10)
+SELL_NTS = (0, 1)
+SELL_UNIFORM = (13, 35, 40, 41)
+SELL_CASES = ["uniform_%d" % L for L in SELL_UNIFORM] + ["short_9", "ragged_slices"]
+
+
+def sell_ragged_rows():
+    """(row lengths, diagonal present) of the ragged case, slice by slice."""
+    n = 321
+    i = np.arange(64)
+    lens = np.concatenate([
+        np.full(64, 20),                              # slice 0: uniform
+        (i * 7) % 31,                                 # slice 1: every length 0 .. 30, in no order
+        np.zeros(64, dtype=np.int64),                 # slice 2: nothing at all
+        (i % 3 == 0).astype(np.int64),                # slice 3: the longest row has one entry, two of three have none
+        np.where(i % 5 == 2, 0, 30),                  # slice 4: empty rows between long ones
+        [17]])                                        # slice 5: one row
+    rows = np.arange(n)
+    diag = (lens > 0) & ~((rows // 64 == 1) & (rows % 2 == 1)) & ~((rows // 64 == 3) & (rows % 2 == 1))
+    assert lens.size == n and set(lens[64:128]) == set(range(31))
+    return lens, diag
+
+
+@functools.lru_cache(maxsize=None)
+def sell_problem(name):
+    if name.startswith("uniform_"):
+        L, n = int(name.split("_")[1]), 200
+        lens, diag = np.full(n, L), np.ones(n, dtype=bool)
+    elif name == "short_9":
+        n = 130
+        lens, diag = np.full(n, 9), np.ones(n, dtype=bool)
+    else:
+        lens, diag = sell_ragged_rows()
+        n = lens.size
+    A = rows_matrix(n, n, lens, diag, seed=100 + n + int(lens.max()))
+    return Problem(A, seed=n)

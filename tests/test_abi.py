@@ -8,12 +8,7 @@ import pytest
 
 from conftest import ROOT
 from learnmultigrid_amd import _lib
-
-
-def header_symbols():
-    txt = open(os.path.join(ROOT, "include", "lmg.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(lmg_[a-z0-9_]+)\s*\(", txt)))
+from support import header_symbols
 
 
 @pytest.fixture(scope="module")

@@ -9,47 +9,12 @@ torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 import chebyshev_ref as C                                            # noqa: E402  (checker only)
+from fused_checks import (check_plain, check_transfers, cheby_histories as _histories,      # noqa: E402
+                          cheby_knobs as knobs, cheby_twin_history as _twin_history, two_launch)
 from learnmultigrid_amd import ops, problems as P                    # noqa: E402
 from learnmultigrid_amd.hierarchy import Hierarchy, chebyshev_coefficients   # noqa: E402
 from oracle import kernels as K                                      # noqa: E402  (checker only)
-
-DEV = "cuda:0"
-KNOBS = ("tile_hot_transfers", "tile_rows", "tile_rows_big", "tile_prol_wide_lines_hx", "dia_rows")
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def nan_vec(n):
-    return torch.full((n,), np.nan, dtype=torch.float64, device=DEV)
-
-
-class knobs:
-    def __init__(self, **kw):
-        self.kw = kw
-
-    def __enter__(self):
-        self.old = {k: ops.tune_get(k) for k in KNOBS}
-        for k, v in self.kw.items():
-            ops.tune_set(k, v)
-
-    def __exit__(self, *exc):
-        for k, v in self.old.items():
-            ops.tune_set(k, v)
-
-
-def operators(side, kind):
-    """(A, P, R) on a side^2 grid (side odd): the 5-point Poisson operator or the 9-point Galerkin operator of the next
-    finer grid, the tensor-product interpolation onto it from ((side + 1) / 2)^2 nodes and its transpose."""
-    if kind == "5pt":
-        A = K.as_csr(P.poisson_2d_structured(side - 1)[0])
-    else:
-        Af = P.poisson_2d_structured(2 * (side - 1))[0]
-        Pf = P.tensor_interpolator_2d(2 * (side - 1) + 1)
-        A = K.as_csr(sp.csr_matrix(Pf.T @ Af @ Pf))
-    Pm = sp.csr_matrix(P.tensor_interpolator_2d(side))
-    return A, K.as_csr(Pm), K.as_csr(sp.csr_matrix(Pm.T))
+from support import DEV, dev, nan_vec, operators                     # noqa: E402
 
 
 def gershgorin_on_device(A, dA):
@@ -58,66 +23,6 @@ def gershgorin_on_device(A, dA):
     g = float(out.item())
     assert g == C.gershgorin(A)                        # storage-order sums, one division, one maximum: the same bits
     return g
-
-
-def two_launch(dA, x0, b, coef):
-    """The step as every format without a fused pass runs it: residual launch + lmg_cheby_update per sweep."""
-    n = dA.shape[0]
-    x = torch.zeros(n, dtype=torch.float64, device=DEV) if x0 is None else dev(x0)
-    dinv = ops.csr_inverse_diagonal(dA)
-    d, r, db = nan_vec(n), nan_vec(n), dev(b)
-    for k, (a, c) in enumerate(coef):
-        ops.csr_residual_norm2(dA, x, db, r, None, None)
-        ops.cheby_update(a, c, dinv, r, d, x, first=(k == 0))
-    return x.cpu().numpy()
-
-
-def check_plain(A, dA, x0, b, lmax, ratio=4.0):
-    """plain, + residual, zero iterate: tiled pass == two-launch path == twin for the degrees 1..3."""
-    n = A.shape[0]
-    for S in (1, 2, 3):
-        coef = chebyshev_coefficients(lmax, ratio, S)
-        for zero in (False, True):
-            want = C.cheby_step(A, np.zeros(n) if zero else x0, b, coef)
-            wr, _ = K.residual(A, want, b)
-            unfused = two_launch(dA, None if zero else x0, b, coef)
-            assert np.array_equal(unfused, want), (n, S, zero, "two-launch path vs twin")
-            for resid in (False, True):
-                out, r = nan_vec(n), (nan_vec(n) if resid else None)
-                ops.stencil_cheby(dA, None if zero else dev(x0), dev(b), coef, out, r)
-                got = out.cpu().numpy()
-                assert not np.isnan(got).any(), (n, S, zero, resid)
-                assert np.array_equal(got, want), (n, S, zero, resid, np.flatnonzero(got != want)[:8])
-                assert np.array_equal(got, unfused)
-                if resid:
-                    assert np.array_equal(r.cpu().numpy(), wr), (n, S, zero)
-        if S == 1:          # degree 1 is weighted Jacobi with omega = 1 / theta: the oracle's sweep and the Jacobi pass
-            omega = coef[0][1]
-            assert np.array_equal(C.cheby_step(A, x0, b, coef), K.jacobi(A, x0, b, omega))
-            out = nan_vec(n)
-            ops.stencil_smooth(dA, dev(x0), dev(b), omega, 1, out)
-            assert np.array_equal(out.cpu().numpy(), C.cheby_step(A, x0, b, coef))
-
-
-def check_transfers(A, Pm, Rm, dA, dP, dR, x0, b, e, lmax):
-    n, nc = A.shape[0], Rm.shape[0]
-    for S in (1, 2, 3):
-        coef = chebyshev_coefficients(lmax, 4.0, S)
-        for zero in (False, True):                                   # REST (and ZERO + REST)
-            want = C.cheby_step(A, np.zeros(n) if zero else x0, b, coef)
-            wbc = K.spmv(Rm, K.residual(A, want, b)[0])
-            out, bc = nan_vec(n), nan_vec(nc)
-            ops.stencil_cheby(dA, None if zero else dev(x0), dev(b), coef, out, None, restrict=(dR, bc))
-            assert np.array_equal(out.cpu().numpy(), want), (n, S, zero, "restrict")
-            got = bc.cpu().numpy()
-            assert np.array_equal(got, wbc), (n, S, zero, np.flatnonzero(got != wbc)[:8])
-        xe = K.spmv(Pm, e, x0.copy(), 1.0, 1.0)                      # PROL
-        want = C.cheby_step(A, xe, b, coef)
-        out = nan_vec(n)
-        ops.stencil_cheby(dA, dev(x0), dev(b), coef, out, None, prolong=(dP, dev(e)))
-        got = out.cpu().numpy()
-        assert np.array_equal(got, want), (n, S, "prolong", np.flatnonzero(got != want)[:8])
-        assert np.array_equal(got, two_launch(dA, xe, b, coef))
 
 
 # 5-point at 257^2 and 1025^2, ragged widths (no multiple of a tile's inner part; 99: less than two tiles wide), 9-point
@@ -242,48 +147,6 @@ def test_entry_points_check_their_arguments():
 
 
 # ---- whole solves -----------------------------------------------------------------------------------------------------------
-def _histories(H, rhs, cycles, degree, shape="V", graph=False):
-    fine = H.levels[0]
-    with torch.cuda.stream(H.stream):
-        fine.b.copy_(dev(rhs.ravel()))
-        ops.zero(fine.x)
-        g = H.captured_cycle("Chebyshev", degree, 1.0, "lexicographic", shape=shape) if graph else None
-        norms = []
-        for _ in range(cycles):
-            norms.append(H.residual_norm())
-            if g is not None:
-                g.launch()
-            else:
-                H.cycle("Chebyshev", degree, shape=shape)
-        norms.append(H.residual_norm())
-        x = fine.x.cpu().numpy().copy()
-    return np.array(norms), x
-
-
-def _twin_history(A, rhs, hier, cycles, degree, shape="V", H=None):
-    """The twin's history.  H: solve the coarsest level with that hierarchy's own direct solver (Hierarchy.coarse_solve) --
-    the twin restates the smoother and the cycle, not the direct solver, and two direct solvers differ by rounding noise
-    that a pointwise relative comparison would meet a few cycles before convergence."""
-    ref = C.ChebyCycle.galerkin(A, hier)
-    if H is not None:
-        last = H.levels[-1]
-
-        def coarse(rc):
-            with torch.cuda.stream(H.stream):
-                last.b.copy_(dev(rc))
-                H.coarse_solve()
-                return last.x.cpu().numpy().copy()
-
-        ref.coarse = coarse
-    b = np.asarray(rhs, dtype=float).ravel()
-    x = np.zeros(A.shape[0])
-    out = [np.sqrt(K.residual(K.as_csr(A), x, b)[1])]
-    for _ in range(cycles):
-        x = ref.cycle(x, b, degree=degree, shape=shape)
-        out.append(np.sqrt(K.residual(K.as_csr(A), x, b)[1]))
-    return np.array(out), x, ref
-
-
 def _problem(name):
     if name == "cfg2_513":
         A, rhs = P.poisson_2d_structured(512)

@@ -9,14 +9,7 @@ import torch
 import cpu_ops_shim as shim
 from learnmultigrid_amd import coarse, problems as P
 from learnmultigrid_amd.ops import DeviceCSR
-
-
-def galerkin_operator(m):
-    A, _ = P.poisson_2d_structured(2 * m)
-    Pm = P.tensor_interpolator_2d(2 * m + 1)
-    Ac = sp.csr_matrix(Pm.T @ A @ Pm)
-    Ac.sort_indices()
-    return Ac
+from support import galerkin_operator
 
 
 def test_plan_prefers_banding_only_when_it_pays():

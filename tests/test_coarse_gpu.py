@@ -12,19 +12,7 @@ pytestmark = pytest.mark.gpu
 from learnmultigrid_amd import coarse, ops, problems as P                    # noqa: E402
 from learnmultigrid_amd.hierarchy import Hierarchy                           # noqa: E402
 from learnmultigrid_amd.ops import DeviceCSR                                 # noqa: E402
-
-DEV = "cuda:0"
-
-
-def galerkin_operator(m, coarsenings=1):
-    A, _ = P.poisson_2d_structured(m * 2 ** coarsenings)
-    side = m * 2 ** coarsenings + 1
-    for _ in range(coarsenings):
-        Pm = P.tensor_interpolator_2d(side)
-        A = sp.csr_matrix(Pm.T @ A @ Pm)
-        side = (side - 1) // 2 + 1
-    A.sort_indices()
-    return A
+from support import DEV, galerkin_operator                                   # noqa: E402
 
 
 def l2_galerkin(side):

@@ -32,10 +32,10 @@ pytestmark = pytest.mark.gpu
 
 import cpu_ops_shim as shim                                             # noqa: E402
 from conftest import ROOT                                               # noqa: E402
-from learnmultigrid_amd import _lib, coarse, ops, problems as P         # noqa: E402
+from learnmultigrid_amd import _lib, coarse, ops                        # noqa: E402
 from learnmultigrid_amd.ops import DeviceCSR                            # noqa: E402
+from support import DEV, dev, galerkin_operator                         # noqa: E402
 
-DEV = "cuda:0"
 KINDS = ["exact", "real"]
 U = fractions.Fraction(1, 2 ** 53)
 WIDE = np.finfo(np.longdouble).eps <= 2.0 ** -63
@@ -49,13 +49,6 @@ LDS_CAP_BYTES = 60000            # operand segment of the gather kernels
 
 
 # ---- helpers ----------------------------------------------------------------------------------------------------------------
-def dev(a, dtype=None):
-    t = torch.from_numpy(np.ascontiguousarray(a))
-    if dtype is not None:
-        t = t.to(dtype)
-    return t.to(DEV)
-
-
 def cpu(a, dtype=None):
     t = torch.from_numpy(np.array(a, copy=True))
     return t if dtype is None else t.to(dtype)
@@ -729,14 +722,6 @@ def test_shim_block_copy():
 
 
 # ---- solver paths that no other device test takes ---------------------------------------------------------------------------
-def galerkin_operator(m):
-    A, _ = P.poisson_2d_structured(2 * m)
-    Pm = P.tensor_interpolator_2d(2 * m + 1)
-    Ac = sp.csr_matrix(Pm.T @ A @ Pm)
-    Ac.sort_indices()
-    return Ac
-
-
 def scrambled_operator():
     """The operator of test_block_cyclic_reduction_reorders_scrambled_operators (test_coarse_cpu.py)."""
     Ac = galerkin_operator(40)

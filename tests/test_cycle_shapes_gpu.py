@@ -12,27 +12,12 @@ from learnmultigrid_amd import ops, problems as P    # noqa: E402
 from learnmultigrid_amd._lib import LmgError         # noqa: E402
 from oracle import kernels as K                      # noqa: E402  (checker only)
 from cycle_shapes_ref import ShapeCycle, history     # noqa: E402  (checker only)
+from fused_checks import knobs_over                  # noqa: E402
+from support import DEV, dev, operators              # noqa: E402
 
-DEV = "cuda:0"
 KNOBS = ("tile_hot_transfers", "tile_rows", "tile_rows_big", "tile_turnaround_rows")
+knobs = knobs_over(KNOBS)
 PAIRS = [(a, b) for a in (1, 2, 3) for b in (1, 2, 3)]
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def operators(side, kind):
-    """(A, P, R) on a side^2 grid: 5-point Poisson or the 9-point Galerkin operator of the next finer grid, the
-    tensor-product interpolation from ((side + 1) / 2)^2 nodes and its transpose."""
-    if kind == "5pt":
-        A = K.as_csr(P.poisson_2d_structured(side - 1)[0])
-    else:
-        Af = P.poisson_2d_structured(2 * (side - 1))[0]
-        Pf = P.tensor_interpolator_2d(2 * (side - 1) + 1)
-        A = K.as_csr(sp.csr_matrix(Pf.T @ Af @ Pf))
-    Pm = sp.csr_matrix(P.tensor_interpolator_2d(side))
-    return A, K.as_csr(Pm), K.as_csr(sp.csr_matrix(Pm.T))
 
 
 def packed(A, Pm, Rm):
@@ -41,20 +26,6 @@ def packed(A, Pm, Rm):
         d.pack()
     assert ops.stencil_smooth_turnaround_available(dA, dP, dR)
     return dA, dP, dR
-
-
-class knobs:
-    def __init__(self, **kw):
-        self.kw = kw
-
-    def __enter__(self):
-        self.old = {k: ops.tune_get(k) for k in KNOBS}
-        for k, v in self.kw.items():
-            ops.tune_set(k, v)
-
-    def __exit__(self, *exc):
-        for k, v in self.old.items():
-            ops.tune_set(k, v)
 
 
 def check_turnaround(A, Pm, Rm, dA, dP, dR, x0, b, e, pairs=PAIRS):

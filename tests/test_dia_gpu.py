@@ -12,12 +12,7 @@ from learnmultigrid_amd import ops, problems as P   # noqa: E402
 from learnmultigrid_amd.hierarchy import Hierarchy  # noqa: E402
 from oracle import kernels as K                     # noqa: E402  (checker only)
 from oracle import vcycle_ref as V                  # noqa: E402
-
-DEV = "cuda:0"
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+from support import DEV, dev                        # noqa: E402
 
 
 def matrix(name):

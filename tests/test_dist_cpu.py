@@ -7,7 +7,6 @@ the all-reduced residual norm agrees to 1e-13, partitions fall on grid lines, an
 ghost layout is what A, R and P need.
 """
 import os
-import socket
 import sys
 
 import numpy as np
@@ -17,14 +16,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 from conftest import ROOT
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+from support import free_port
 
 
 def _worker(rank, world, port, m, levels, replicate_below, steps, halo_depth, out_dir, transfer="geometric"):
@@ -112,7 +104,7 @@ def _worker(rank, world, port, m, levels, replicate_below, steps, halo_depth, ou
                           (4, 64, 4, 500, 3, 8),        # four ranks, V(3,3) like the bench
                           (8, 128, 4, 2000, 3, 8)])     # the bench's N = 8 topology in small: two distributed levels
 def test_distributed_vcycle_matches_single_process(tmp_path, world, m, levels, replicate_below, steps, halo_depth):
-    port = _free_port()
+    port = free_port()
     mp.spawn(_worker, args=(world, port, m, levels, replicate_below, steps, halo_depth, str(tmp_path)),
              nprocs=world, join=True)
     infos = [eval(str(np.load(os.path.join(str(tmp_path), "info_%d.npy" % r))[0])) for r in range(world)]
@@ -167,7 +159,7 @@ def test_distributed_vcycle_with_wide_learned_transfers(tmp_path, halo_depth, st
     """Wide transfer operators change what the halo must cover (r_need, p_need are measured from
     the matrices): whatever the depth allows, the iterate must stay bit-identical."""
     world, m, levels, replicate_below = 2, 48, 3, 1
-    port = _free_port()
+    port = free_port()
     mp.spawn(_worker, args=(world, port, m, levels, replicate_below, steps, halo_depth, str(tmp_path), "learned"),
              nprocs=world, join=True)
     counts = []
@@ -231,7 +223,7 @@ def test_distributed_processor_block_gauss_seidel_matches_its_cpu_twin(tmp_path,
     start of the sweep.  One smoothing step is bit-identical to the CPU twin (oracle.vcycle_ref.HybridGSVCycle), whole
     V-cycles agree with it at 1e-10 (the coarsest solve is SuperLU there, explicit block inverses here); with the classic
     one-layer halo and with a deep one (owned rows only are relaxed either way)."""
-    port = _free_port()
+    port = free_port()
     mp.spawn(_gs_worker, args=(world, port, m, levels, replicate_below, halo_depth, str(tmp_path)), nprocs=world, join=True)
     for r in range(world):
         info = eval(str(np.load(os.path.join(str(tmp_path), "gsinfo_%d.npy" % r))[0]))

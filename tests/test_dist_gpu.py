@@ -2,21 +2,13 @@
 a world_size-1 "nccl" group drives the partitioned code path (local rectangular matrices,
 ghost layout, all_gather of the replicated level, all-reduced norm).  The multi-rank
 logic itself is covered by tests/test_dist_cpu.py (gloo, world 2 and 3)."""
-import socket
-
 import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+from support import free_port            # noqa: E402
 
 
 def test_world1_nccl_path_matches_single_gpu_bitwise():
@@ -25,7 +17,7 @@ def test_world1_nccl_path_matches_single_gpu_bitwise():
     from learnmultigrid_amd.dist import DistributedVCycle
     from learnmultigrid_amd.hierarchy import Hierarchy
     torch.cuda.set_device(0)
-    dist.init_process_group("nccl", init_method="tcp://127.0.0.1:%d" % _free_port(), rank=0, world_size=1,
+    dist.init_process_group("nccl", init_method="tcp://127.0.0.1:%d" % free_port(), rank=0, world_size=1,
                             device_id=torch.device("cuda", 0))
     try:
         m, levels = 256, 5
@@ -139,7 +131,7 @@ def test_several_ranks_on_one_gpu_match_single_gpu_bitwise(tmp_path, world):
     refuses two ranks on one device.  RCCL itself is exercised by the world-1 test above."""
     import os
     import torch.multiprocessing as mp
-    mp.spawn(_gpu_worker, args=(world, _free_port(), str(tmp_path)), nprocs=world, join=True)
+    mp.spawn(_gpu_worker, args=(world, free_port(), str(tmp_path)), nprocs=world, join=True)
     for r in range(world):
         ok = np.load(os.path.join(str(tmp_path), "ok_%d.npy" % r))
         assert ok.all(), (r, ok)
@@ -150,7 +142,7 @@ def test_two_ranks_with_fused_smoothing_passes_match_single_gpu_bitwise(tmp_path
     (what a rank runs from 4 M local rows on: N = 2, 4 at cfg#4): same bits as the single-GPU cycle."""
     import os
     import torch.multiprocessing as mp
-    mp.spawn(_gpu_worker, args=(2, _free_port(), str(tmp_path), "geometric", True), nprocs=2, join=True)
+    mp.spawn(_gpu_worker, args=(2, free_port(), str(tmp_path), "geometric", True), nprocs=2, join=True)
     for r in range(2):
         ok = np.load(os.path.join(str(tmp_path), "ok_%d.npy" % r))
         assert ok.all(), (r, ok)
@@ -161,7 +153,7 @@ def test_two_ranks_with_learned_transfers_match_single_gpu_bitwise(tmp_path):
     ghost rows, halo requirements measured from the matrices."""
     import os
     import torch.multiprocessing as mp
-    mp.spawn(_gpu_worker, args=(2, _free_port(), str(tmp_path), "learned"), nprocs=2, join=True)
+    mp.spawn(_gpu_worker, args=(2, free_port(), str(tmp_path), "learned"), nprocs=2, join=True)
     for r in range(2):
         ok = np.load(os.path.join(str(tmp_path), "ok_%d.npy" % r))
         assert ok.all(), (r, ok)
@@ -224,7 +216,7 @@ def test_processor_block_gauss_seidel_on_the_device_matches_its_cpu_twin(tmp_pat
     halo: one smoothing step bit-identical to oracle.vcycle_ref.HybridGSVCycle, V-cycle histories at 1e-10."""
     import os
     import torch.multiprocessing as mp
-    mp.spawn(_gs_gpu_worker, args=(world, _free_port(), str(tmp_path), halo_depth), nprocs=world, join=True)
+    mp.spawn(_gs_gpu_worker, args=(world, free_port(), str(tmp_path), halo_depth), nprocs=world, join=True)
     for r in range(world):
         ok = np.load(os.path.join(str(tmp_path), "gs_%d.npy" % r))
         assert ok.all(), (r, ok)

@@ -13,7 +13,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 from conftest import ROOT
-from test_dist_cpu import _free_port
+from support import free_port
 
 
 def _csr(M):
@@ -144,7 +144,7 @@ def _worker(rank, world, port, m, levels, replicate_below, halo_depth, transfer,
                           (2, 48, 3, 1, 8, "learned")])        # wide rows, r_need >= 3, non-contiguous send lists
 def test_local_operators_and_plans_match_the_replicated_hierarchy(tmp_path, world, m, levels, replicate_below, halo_depth,
                                                                   transfer):
-    mp.spawn(_worker, args=(world, _free_port(), m, levels, replicate_below, halo_depth, transfer, str(tmp_path)),
+    mp.spawn(_worker, args=(world, free_port(), m, levels, replicate_below, halo_depth, transfer, str(tmp_path)),
              nprocs=world, join=True)
     infos = [eval(str(np.load(os.path.join(str(tmp_path), "layout_%d.npy" % r))[0])) for r in range(world)]
     for r, info in enumerate(infos):

@@ -16,18 +16,10 @@ pytestmark = pytest.mark.gpu
 from learnmultigrid_amd import ops, problems as P                           # noqa: E402
 from learnmultigrid_amd.hierarchy import chebyshev_coefficients             # noqa: E402
 from oracle import kernels as K                                             # noqa: E402  (checker only)
+from support import DEV, dev, nan_vec                                       # noqa: E402
 
-DEV = "cuda:0"
 NAMES = ("jittered7_65", "varcoeff5_65", "perturbed9_65")
 OMEGAS = (0.8, 1.0)
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def nan_vec(n):
-    return torch.full((n,), np.nan, dtype=torch.float64, device=DEV)
 
 
 def rounded(A):

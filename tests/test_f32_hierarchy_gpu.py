@@ -24,14 +24,10 @@ from learnmultigrid_amd import krylov, ops, problems as P                   # no
 from learnmultigrid_amd.hierarchy import Hierarchy                          # noqa: E402
 from learnmultigrid_amd.solvers import CG, GMRES                            # noqa: E402
 from oracle import kernels as K                                             # noqa: E402  (checker only)
+from support import DEV, dev                                                # noqa: E402
 
-DEV = "cuda:0"
 M, LEVELS, RTOL = 66, 3, 1e-10
 TWINS = ("patterns", "sell", "packed", "dia", "stencil", "prolong", "restrict")
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 def rounded(A):

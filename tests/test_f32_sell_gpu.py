@@ -13,11 +13,11 @@ torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 import sweep_variants as SV                                          # noqa: E402
-from test_sell_variants_gpu import CASES, JUS, NTS, problem          # noqa: E402
 from learnmultigrid_amd import ops                                   # noqa: E402
 from oracle import kernels as K                                      # noqa: E402  (checker only)
 
 DEV = SV.DEV
+CASES, JUS, NTS, problem = SV.SELL_CASES, SV.SELL_JUS, SV.SELL_NTS, SV.sell_problem
 
 
 def rounded(A):

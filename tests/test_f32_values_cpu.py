@@ -2,7 +2,6 @@
 keywords are checked before anything is built, and a hierarchy on matrices without twins (the CPU ops shim) is not
 affected by the keyword."""
 import ctypes
-import types
 
 import numpy as np
 import pytest
@@ -10,9 +9,9 @@ import scipy.sparse as sp
 import torch
 
 import cpu_ops_shim as shim
-from test_abi import header_symbols
 from learnmultigrid_amd import _lib, ops, problems as P
 from learnmultigrid_amd.hierarchy import Hierarchy
+from support import header_symbols
 
 NEW = ("lmg_sell_fill_f32", "lmg_sell_sweep_f32", "lmg_dia_fill_f32", "lmg_dia_smooth_f32", "lmg_dia_cheby_f32")
 
@@ -56,13 +55,12 @@ def _problem():
 def test_hierarchy_refuses_an_unknown_width_before_any_setup():
     A, _rhs, hier = _problem()
     built = []
-    ns = types.SimpleNamespace(**{k: getattr(shim, k) for k in dir(shim) if not k.startswith("__")})
 
     class Plan(shim.SpGEMMPlan):
         def __init__(self, *a, **k):
             built.append("plan")
             super().__init__(*a, **k)
-    ns.SpGEMMPlan = Plan
+    ns = shim.namespace(SpGEMMPlan=Plan)
     with pytest.raises(ValueError, match="cycle_values"):
         Hierarchy(A, hier, "cpu", ops_mod=ns, cycle_values="f16")
     assert built == []

@@ -19,10 +19,9 @@ import pytest
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
+import fused_checks as FC                                            # noqa: E402
 import grid_ops as G                                                 # noqa: E402
 import sweep_variants as SV                                          # noqa: E402
-import test_grid_shapes_gpu as TG                                    # noqa: E402  (check_smoothing, jacobi_wants, register_pass)
-import test_tile_passes_gpu as TT                                    # noqa: E402  (check_pre, check_post)
 from learnmultigrid_amd import ops                                   # noqa: E402
 
 DEV = SV.DEV
@@ -38,13 +37,13 @@ def problem(slots, lines):
     n = A.shape[0]
     rng = np.random.default_rng(n + slots)
     x0, b = rng.standard_normal(n), rng.standard_normal(n)
-    return A, x0, b, TG.jacobi_wants(A, x0, b)
+    return A, x0, b, FC.jacobi_wants(A, x0, b)
 
 
 @functools.lru_cache(maxsize=None)
 def transfers():
     """P from the 193 x 49 grid to the 385 x 97 grid, its transpose, and a coarse vector."""
-    Pm, Rm = TG.nested_pair(W, LINES)
+    Pm, Rm = FC.nested_pair(W, LINES)
     assert Pm.shape == (W * LINES, 193 * 49)
     return Pm, Rm, np.random.default_rng(193).standard_normal(Pm.shape[1])
 
@@ -72,7 +71,7 @@ def packed_transfers():
 @contextlib.contextmanager
 def register_pass(dA, seg_lines=0, **keys):
     """The register pass with `seg_lines` lines per segment (0: chosen per launch) and the tune keys given."""
-    with TG.register_pass(seg_lines), SV.tuned(**keys):
+    with FC.register_pass(seg_lines), SV.tuned(**keys):
         assert ops._fused_kind(dA) is None
         yield
 
@@ -85,7 +84,7 @@ def test_fast_body_and_general_body_give_the_same_bits(slots):
     dA = operator(slots, LINES)
     for fast in (1, 0):
         with register_pass(dA, fused_fast=fast):
-            TG.check_smoothing(("fused_fast", fast), dA, x0, b, wants)
+            FC.check_smoothing(("fused_fast", fast), dA, x0, b, wants)
 
 
 @pytest.mark.parametrize("slots", SLOTS, ids=IDS)
@@ -97,7 +96,7 @@ def test_balance_of_the_slow_items(slots):
     dA = operator(slots, LINES)
     for balance, pct in ((0, 55), (1, 10), (1, 55), (1, 100)):
         with register_pass(dA, fused_balance=balance, fused_slow_pct=pct):
-            TG.check_smoothing(("fused_balance", balance, "fused_slow_pct", pct), dA, x0, b, wants)
+            FC.check_smoothing(("fused_balance", balance, "fused_slow_pct", pct), dA, x0, b, wants)
 
 
 @pytest.mark.parametrize("slots", SLOTS, ids=IDS)
@@ -108,7 +107,7 @@ def test_segment_count_from_the_wanted_waves(slots):
     for waves in (1, 64, 5120):
         for halos in (1, 4):
             with register_pass(dA, fused_want_waves=waves, fused_floor_halos=halos):
-                TG.check_smoothing(("fused_want_waves", waves, "fused_floor_halos", halos), dA, x0, b, wants)
+                FC.check_smoothing(("fused_want_waves", waves, "fused_floor_halos", halos), dA, x0, b, wants)
 
 
 @pytest.mark.parametrize("slots", SLOTS, ids=IDS)
@@ -122,8 +121,8 @@ def test_segment_count_of_the_three_sweep_transfer_passes(slots):
     for waves in (1, 64):
         for halos in (1, 4):
             with register_pass(dA, fused_want_waves_rest3=waves, fused_want_waves=waves, fused_floor_halos=halos):
-                TT.check_pre(A, Rm, dA, dR, x0, b, sweeps=(3,))
-                TT.check_post(A, Pm, dA, dP, x0, b, e, sweeps=(3,))
+                FC.check_pre(A, Rm, dA, dR, x0, b, sweeps=(3,))
+                FC.check_post(A, Pm, dA, dP, x0, b, e, sweeps=(3,))
 
 
 @pytest.mark.parametrize("slots", SLOTS, ids=IDS)
@@ -136,7 +135,7 @@ def test_edge_segments_around_their_threshold(slots):
         A, x0, b, wants = problem(slots, lines)
         dA = operator(slots, lines)
         with register_pass(dA, 7):
-            TG.check_smoothing(("edge segments", lines), dA, x0, b, wants)
+            FC.check_smoothing(("edge segments", lines), dA, x0, b, wants)
 
 
 @pytest.mark.parametrize("slots", SLOTS, ids=IDS)
@@ -148,8 +147,8 @@ def test_segment_keys_of_the_transfer_passes(slots):
     dP, dR = packed_transfers()
     for seg in (3, 9):
         with register_pass(dA, 1000, fused_seg_lines_prol=seg, fused_seg_lines_rest=seg):
-            TT.check_pre(A, Rm, dA, dR, x0, b)
-            TT.check_post(A, Pm, dA, dP, x0, b, e)
+            FC.check_pre(A, Rm, dA, dR, x0, b)
+            FC.check_post(A, Pm, dA, dP, x0, b, e)
 
 
 @pytest.mark.parametrize("slots", SLOTS, ids=IDS)
@@ -160,4 +159,4 @@ def test_line_range_of_the_segment_key(slots):
     dA = operator(slots, LINES)
     for lo, hi in ((90, 100), (97, 97), (0, 96), (98, 1000)):
         with register_pass(dA, 7, fused_seg_min_lines=lo, fused_seg_max_lines=hi):
-            TG.check_smoothing(("fused_seg_lines 7 for lines", lo, hi), dA, x0, b, wants)
+            FC.check_smoothing(("fused_seg_lines 7 for lines", lo, hi), dA, x0, b, wants)

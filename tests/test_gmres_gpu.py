@@ -16,8 +16,7 @@ from krylov_ref import fgmres_ref                                  # noqa: E402
 from learnmultigrid_amd import ops, problems as P                  # noqa: E402
 from learnmultigrid_amd.hierarchy import Hierarchy                 # noqa: E402
 from learnmultigrid_amd.solvers import CG, GMRES                   # noqa: E402
-
-DEV = "cuda:0"
+from support import DEV                                            # noqa: E402
 
 
 def cycle_operator(H, smoother, steps, omega, shape="V", gs_sweep=("forward", "forward")):

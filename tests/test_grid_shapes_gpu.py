@@ -13,8 +13,6 @@ whose boundary rows keep their couplings (tests/grid_ops.py):
 
 Every case first asserts which twin, stride and slot mask the operator got, so that it cannot silently stop exercising
 its path; where a pass does not take an operator the refusal is asserted and the separate sweeps' bits are checked."""
-import contextlib
-
 import numpy as np
 import pytest
 import scipy.sparse as sp
@@ -23,20 +21,15 @@ torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 import chebyshev_ref as C                                            # noqa: E402  (checker only)
+import fused_checks as FC                                            # noqa: E402
 import grid_ops as G                                                 # noqa: E402
-import test_chebyshev_gpu as TC                                      # noqa: E402  (check_plain, knobs, histories)
-import test_tile_passes_gpu as TT                                    # noqa: E402  (check_pre, check_post)
-from learnmultigrid_amd import ops, problems as P                    # noqa: E402
+from fused_checks import (check_smoothing, cheby_knobs as knobs, first_diff, jacobi_wants, nested_pair,   # noqa: E402
+                          register_pass)
+from learnmultigrid_amd import ops                                   # noqa: E402
 from learnmultigrid_amd.hierarchy import Hierarchy                   # noqa: E402
 from oracle import kernels as K                                      # noqa: E402  (checker only)
 from oracle import vcycle_ref as V                                   # noqa: E402
-
-DEV = "cuda:0"
-dev, nan_vec, knobs = TC.dev, TC.nan_vec, TC.knobs
-
-
-def first_diff(got, want):
-    return np.flatnonzero(~((got == want) | (np.isnan(got) & np.isnan(want))))[:8]
+from support import DEV, dev, nan_vec                                # noqa: E402
 
 
 def expected_view(Wg, n, slots, periodic_x):
@@ -47,35 +40,6 @@ def expected_view(Wg, n, slots, periodic_x):
     if slots == 0x1BB and not periodic_x and n % (Wg + 1) == 0:
         return Wg + 1, 0x0FE
     return Wg, (slots | 0x44) if periodic_x else slots
-
-
-def jacobi_wants(A, x0, b):
-    """(omega, zero iterate, sweeps) -> (J^S x, b - A J^S x) of the oracle: computed once per operator."""
-    n = A.shape[0]
-    out = {}
-    for omega in (0.8, 1.0):
-        for zero in (False, True):
-            w = np.zeros(n) if zero else x0.copy()
-            for S in (1, 2, 3):
-                w = K.jacobi(A, w, b, omega)
-                out[omega, zero, S] = (w, K.residual(A, w, b)[0])
-    return out
-
-
-def check_smoothing(tag, dA, x0, b, wants):
-    """stencil_smooth for the sweeps 1..3, with and without the residual, zero and non-zero iterate, omega 0.8 and 1.0."""
-    n = dA.shape[0]
-    dx, db = dev(x0), dev(b)
-    for (omega, zero, S), (want, wr) in wants.items():
-        for resid in (False, True):
-            out, r = nan_vec(n), (nan_vec(n) if resid else None)
-            ops.stencil_smooth(dA, None if zero else dx, db, omega, S, out, r)
-            got = out.cpu().numpy()
-            assert not np.isnan(got).any(), (tag, omega, S, zero, resid, np.flatnonzero(np.isnan(got))[:8])
-            assert np.array_equal(got, want), (tag, omega, S, zero, resid, first_diff(got, want))
-            if resid:
-                gr = r.cpu().numpy()
-                assert np.array_equal(gr, wr), (tag, omega, S, zero, "residual", first_diff(gr, wr))
 
 
 def check_separate(tag, dA, x0, b, wants):
@@ -89,18 +53,6 @@ def check_separate(tag, dA, x0, b, wants):
         assert np.array_equal(got, wants[0.8, False, S][0]), (tag, S, "separate sweeps", first_diff(got, wants[0.8, False, S][0]))
     ops.csr_residual_norm2(dA, x, db, r, None, None)
     assert np.array_equal(r.cpu().numpy(), wants[0.8, False, 3][1]), (tag, "separate residual")
-
-
-@contextlib.contextmanager
-def register_pass(seg_lines):
-    """stencil_smooth on the register pass (levels of this size run the tiled one), `seg_lines` lines per segment."""
-    try:
-        ops.set_tiled_enabled(False)
-        ops.tune_set("fused_seg_lines", seg_lines)
-        yield
-    finally:
-        ops.tune_set("fused_seg_lines", 0)
-        ops.set_tiled_enabled(True)
 
 
 def run_operator(tag, Wg, Hg, slots, values, periodic_x=False, rows=None, line_end=False, seed=1):
@@ -131,14 +83,14 @@ def run_operator(tag, Wg, Hg, slots, values, periodic_x=False, rows=None, line_e
         for rr in (32, 64):
             with knobs(dia_rows=rr):
                 check_smoothing((tag, "dia_rows", rr), dA, x0, b, wants)
-                TC.check_plain(A, dA, x0, b, lmax)
+                FC.check_plain(A, dA, x0, b, lmax)
         return
     L = ops._lib.lib()
     if kind == "tile":
         for rr in (16, 32):
             with knobs(tile_rows=rr, tile_rows_big=rr):
                 check_smoothing((tag, "tile_rows", rr), dA, x0, b, wants)
-                TC.check_plain(A, dA, x0, b, lmax)
+                FC.check_plain(A, dA, x0, b, lmax)
     else:
         # neither stencil pass is built for this slot set: the hierarchy runs the separate sweeps (checked above), and a
         # direct call answers with an error instead of a result
@@ -196,7 +148,7 @@ def test_sheared_the_other_way_with_a_ragged_last_line():
     for rr in (32, 64):
         with knobs(dia_rows=rr):
             check_smoothing(("sheared7b", rr), dA, x0, b, wants)
-            TC.check_plain(A, dA, x0, b, C.gershgorin(A))
+            FC.check_plain(A, dA, x0, b, C.gershgorin(A))
 
 
 # ---- plain rectangles -----------------------------------------------------------------------------------------------------------
@@ -243,14 +195,6 @@ def test_ragged_last_line(short, slots, values):
 
 
 # ---- the transfers folded into the passes, on a rectangle ------------------------------------------------------------------
-def nested_pair(Wf, Hf):
-    """P between the Wf x Hf grid and the ((Wf + 1) / 2) x ((Hf + 1) / 2) grid -- the tensor product of the 1-D
-    interpolations along y and x -- and its transpose."""
-    Pm = sp.kron(P.geometric_interpolator_1d(Hf), P.geometric_interpolator_1d(Wf), format="csr")
-    Pm.sort_indices()
-    return K.as_csr(Pm), K.as_csr(sp.csr_matrix(Pm.T))
-
-
 @pytest.mark.parametrize("slots", [0x0BA, 0x1FF])
 def test_transfer_passes_on_a_rectangle(slots):
     """Fine 97 x 65, coarse 49 x 33: R (b - A J^S x) and J^S (x + P e) of the tiled and the register family against the
@@ -288,20 +232,20 @@ def test_transfer_passes_on_a_rectangle(slots):
     assert TP is not None and (TP.W, TP.Wc, TP.nc) == (Wf, 49, nc)
     assert TR is not None and (TR.W, TR.Wc, TR.nc, TR.n) == (Wf, 49, nc, n)
     assert ops.stencil_smooth_prolong_available(dA, dP) and ops.stencil_smooth_restrict_available(dA, dR)
-    for layout in TT.LAYOUTS:
+    for layout in FC.LAYOUTS:
         for hx in (1, 0):
-            with TT.knobs(tile_hot_transfers=hx, **layout):
-                TT.check_pre(A, Rm, dA, dR, x0, b)
-                TT.check_post(A, Pm, dA, dP, x0, b, e)
+            with FC.tile_knobs(tile_hot_transfers=hx, **layout):
+                FC.check_pre(A, Rm, dA, dR, x0, b)
+                FC.check_post(A, Pm, dA, dP, x0, b, e)
     lmax = C.gershgorin(A)
     for rr in (16, 32):
         with knobs(tile_rows=rr, tile_rows_big=rr):
-            TC.check_transfers(A, Pm, Rm, dA, dP, dR, x0, b, e, lmax)
+            FC.check_transfers(A, Pm, Rm, dA, dP, dR, x0, b, e, lmax)
     for seg in (0, 5):
         with register_pass(seg):
             assert ops._fused_kind(dA) is None
-            TT.check_pre(A, Rm, dA, dR, x0, b)
-            TT.check_post(A, Pm, dA, dP, x0, b, e)
+            FC.check_pre(A, Rm, dA, dR, x0, b)
+            FC.check_post(A, Pm, dA, dP, x0, b, e)
 
 
 def test_tiled_transfer_passes_on_an_operator_with_line_end_coupling():
@@ -321,11 +265,11 @@ def test_tiled_transfer_passes_on_an_operator_with_line_end_coupling():
     assert ops.stencil_smooth_prolong_available(dA, dP) and ops.stencil_smooth_restrict_available(dA, dR)
     rng = np.random.default_rng(71)
     x0, b, e = rng.standard_normal(n), rng.standard_normal(n), rng.standard_normal(nc)
-    for layout in TT.LAYOUTS:
+    for layout in FC.LAYOUTS:
         for hx in (1, 0):
-            with TT.knobs(tile_hot_transfers=hx, **layout):
-                TT.check_pre(A, Rm, dA, dR, x0, b)
-                TT.check_post(A, Pm, dA, dP, x0, b, e)
+            with FC.tile_knobs(tile_hot_transfers=hx, **layout):
+                FC.check_pre(A, Rm, dA, dR, x0, b)
+                FC.check_post(A, Pm, dA, dP, x0, b, e)
     assert dA.stencil.line_end_coupling
     with register_pass(0):
         with pytest.raises(ops.LmgError):
@@ -375,15 +319,15 @@ def test_three_level_cycles_on_a_rectangle_with_live_boundary_rows():
         want.append(np.linalg.norm(rhs - A @ x))
     print("Jacobi history", h1, "oracle", want)
     np.testing.assert_allclose(h1, want, rtol=1e-10, atol=1e-14 * max(want))
-    c1, xc1 = TC._histories(H, rhs, 3, 3)
-    cw, _, _ = TC._twin_history(A, rhs, hier, 3, 3, H=H)
+    c1, xc1 = FC.cheby_histories(H, rhs, 3, 3)
+    cw, _, _ = FC.cheby_twin_history(A, rhs, hier, 3, 3, H=H)
     print("Chebyshev history", c1, "twin", cw)
     np.testing.assert_allclose(c1, cw, rtol=1e-10, atol=1e-14 * max(cw))
     try:
         ops.set_fused_enabled(False)
         assert not ops.stencil_smooth_available(H.levels[0].A)
         h0, x0 = jacobi_history()
-        c0, xc0 = TC._histories(H, rhs, 3, 3)
+        c0, xc0 = FC.cheby_histories(H, rhs, 3, 3)
     finally:
         ops.set_fused_enabled(True)
     assert h1 == h0 and np.array_equal(x1, x0)

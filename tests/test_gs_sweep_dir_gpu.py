@@ -14,12 +14,7 @@ from learnmultigrid_amd import ops, problems as P                # noqa: E402
 from learnmultigrid_amd._lib import LmgError                     # noqa: E402
 from oracle import kernels as K                                  # noqa: E402  (checker only)
 from oracle import vcycle_ref as V                               # noqa: E402  (checker only)
-
-DEV = "cuda:0"
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+from support import DEV, dev, galerkin9                          # noqa: E402
 
 
 def backward_rows(n):
@@ -63,13 +58,6 @@ def grid_operator(nx, ny, kind="5pt", sym=False, var=False):
         A[3 * nx + 7, 3 * nx + 7] = 0.0                      # row without a diagonal entry
         A = sp.csr_matrix(A)
         A.eliminate_zeros()
-    return K.as_csr(A)
-
-
-def galerkin9(side):
-    Pm = P.tensor_interpolator_2d(2 * (side - 1) + 1)
-    A = sp.csr_matrix(Pm.T @ P.poisson_2d_structured(2 * (side - 1))[0] @ Pm)
-    A.sort_indices()
     return K.as_csr(A)
 
 

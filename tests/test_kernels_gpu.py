@@ -15,15 +15,7 @@ pytestmark = pytest.mark.gpu
 
 from learnmultigrid_amd import ops, problems as P   # noqa: E402
 from oracle import kernels as K                     # noqa: E402  (checker only)
-
-DEV = "cuda:0"
-
-
-def dev(a, dtype=None):
-    t = torch.from_numpy(np.ascontiguousarray(a))
-    if dtype is not None:
-        t = t.to(dtype)
-    return t.to(DEV)
+from support import DEV, dev                        # noqa: E402
 
 
 def ragged_matrix(n, seed, long_row=None, empty_every=7, long_len=5000):

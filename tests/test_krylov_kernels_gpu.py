@@ -13,8 +13,8 @@ torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 from learnmultigrid_amd import _lib, ops   # noqa: E402
+from support import DEV                    # noqa: E402
 
-DEV = "cuda:0"
 F64 = torch.float64
 NS = (1, 2, 255, 257, 4099, 262147, 1000003)
 MAXK = "max"

@@ -9,29 +9,15 @@ import scipy.sparse as sp
 import torch
 from scipy.linalg import solve_banded
 
-import line_ops_shim as lshim
+import cpu_ops_shim
 import line_ref as LR
 from cycle_shapes_ref import ShapeCycle
 from learnmultigrid_amd import problems as P
 from learnmultigrid_amd.hierarchy import Hierarchy, line_config, line_half_steps
 from oracle import kernels as K
+from support import galerkin9, to_numpy as _np, to_scipy as _sp
 
 U = 2.0 ** -53
-
-
-def _np(t):
-    return t.numpy()
-
-
-def _sp(A):
-    return sp.csr_matrix((_np(A.vals), _np(A.colidx), _np(A.rowptr)), shape=A.shape)
-
-
-def galerkin9(side):
-    """The 9-point Galerkin operator on a side^2 grid (side odd) of the 5-point operator of the next finer grid."""
-    Af = P.poisson_2d_structured(2 * (side - 1))[0]
-    Pf = P.tensor_interpolator_2d(2 * (side - 1) + 1)
-    return K.as_csr(sp.csr_matrix(Pf.T @ Af @ Pf))
 
 
 # ---- the twin's tridiagonal solves -----------------------------------------------------------------------------------------
@@ -167,7 +153,7 @@ def _run(H, rhs, cycles, steps, shape, omega, **kw):
                                                              ("xy", "jacobi", 0.8, 2)])
 def test_hierarchy_cycle_equals_the_twin(shape, line_dir, line_order, omega, steps):
     A, rhs, hier = _problem()
-    H = Hierarchy(A, hier, "cpu", ops_mod=lshim.base())
+    H = Hierarchy(A, hier, "cpu", ops_mod=cpu_ops_shim.recording_line())
     got, x = _run(H, rhs, 3, steps, shape, omega, line_dir=line_dir, line_order=line_order)
     assert H.line_key() == (line_dir, line_order)
     assert [lev.line["W"] for lev in H.levels[:-1]] == [33, 17]            # from the offsets, on the host
@@ -179,7 +165,7 @@ def test_hierarchy_cycle_equals_the_twin(shape, line_dir, line_order, omega, ste
 
 def test_launch_sequence_and_the_reversed_post_smoothing_half():
     A, rhs, hier = _problem(16, 2)
-    shim = lshim.base()
+    shim = cpu_ops_shim.recording_line()
     H = Hierarchy(A, hier, "cpu", ops_mod=shim)
     H.prepare_smoother("Line")                                               # the defaults: "xy", "zebra"
     n = A.shape[0]
@@ -207,7 +193,7 @@ def test_launch_sequence_and_the_reversed_post_smoothing_half():
 
 def test_zero_steps_and_unprepared_use():
     A, rhs, hier = _problem(16, 2)
-    H = Hierarchy(A, hier, "cpu", ops_mod=lshim.base())
+    H = Hierarchy(A, hier, "cpu", ops_mod=cpu_ops_shim.recording_line())
     with pytest.raises(RuntimeError):
         H.smooth(0, "Line", 1, 1.0, "lexicographic")
     H.prepare_smoother("Line", line_dir="x")
@@ -218,29 +204,29 @@ def test_zero_steps_and_unprepared_use():
 
 def test_levels_that_cannot_run_it_are_named():
     A1, _ = P.poisson_1d_fd(64)
-    H = Hierarchy(A1, P.geometric_hierarchy_1d(65, 2), "cpu", ops_mod=lshim.base())
+    H = Hierarchy(A1, P.geometric_hierarchy_1d(65, 2), "cpu", ops_mod=cpu_ops_shim.recording_line())
     with pytest.raises(ValueError, match=r"level 0.*W == n"):
         H.prepare_smoother("Line")
     # a 25-point operator (the square of the 9-point pattern): no 3x3 geometry
     A, rhs, hier = _problem(16, 2)
     G = K.as_csr(sp.csr_matrix(A @ A))
-    H = Hierarchy(G, hier, "cpu", ops_mod=lshim.base())
+    H = Hierarchy(G, hier, "cpu", ops_mod=cpu_ops_shim.recording_line())
     with pytest.raises(ValueError, match=r"level 0.*no 3x3 grid geometry"):
         H.prepare_smoother("Line")
     # row i coupled to row i + 1 everywhere: an entry across every line end
     W = 17
     helix = sp.diags([-1.0, -1.0, 4.5, -1.0, -1.0], [-W, -1, 0, 1, W], shape=(W * W, W * W)).tocsr()
     for bad in ("x", "xy"):
-        H = Hierarchy(helix, hier, "cpu", ops_mod=lshim.base())
+        H = Hierarchy(helix, hier, "cpu", ops_mod=cpu_ops_shim.recording_line())
         with pytest.raises(ValueError, match=r"level 0.*couples two x-lines"):
             H.prepare_smoother("Line", line_dir=bad)
-    H = Hierarchy(helix, hier, "cpu", ops_mod=lshim.base())
+    H = Hierarchy(helix, hier, "cpu", ops_mod=cpu_ops_shim.recording_line())
     H.prepare_smoother("Line", line_dir="y")
     H.cycle("Line", 1, 1.0)
     # a zero on the diagonal
     Z = K.as_csr(A).copy()
     Z.data[Z.indptr[4]] = 0.0                                                 # (an identity row: nothing else in its pivot)
-    H = Hierarchy(Z, hier, "cpu", ops_mod=lshim.base())
+    H = Hierarchy(Z, hier, "cpu", ops_mod=cpu_ops_shim.recording_line())
     with pytest.raises(ValueError, match=r"level 0.*pivot"):
         H.prepare_smoother("Line")
 
@@ -258,12 +244,12 @@ def test_rebuild_numeric_refreshes_the_factors():
 
     v0, v1 = perturbed(), perturbed()
     mk = lambda v: sp.csr_matrix((v, base.indices.copy(), base.indptr.copy()), shape=base.shape)
-    H = Hierarchy(mk(v0), hier, "cpu", ops_mod=lshim.base())
+    H = Hierarchy(mk(v0), hier, "cpu", ops_mod=cpu_ops_shim.recording_line())
     _run(H, rhs, 1, 1, "V", 1.0, line_dir="xy", line_order="zebra")
     H.rebuild_numeric(torch.from_numpy(v1))
     assert H.line_key() == ("xy", "zebra")
     got, x = _run(H, rhs, 2, 1, "V", 1.0)
-    fresh = Hierarchy(mk(v1), hier, "cpu", ops_mod=lshim.base())
+    fresh = Hierarchy(mk(v1), hier, "cpu", ops_mod=cpu_ops_shim.recording_line())
     want, xw = _run(fresh, rhs, 2, 1, "V", 1.0)
     assert np.array_equal(got, want) and np.array_equal(x, xw)
     for a, b in zip(H.levels[:-1], fresh.levels[:-1]):

@@ -16,13 +16,9 @@ import line_ref as LR                                               # noqa: E402
 from learnmultigrid_amd import _lib, ops, problems as P             # noqa: E402
 from learnmultigrid_amd.hierarchy import Hierarchy                  # noqa: E402
 from oracle import kernels as K                                     # noqa: E402  (checker only)
+from support import DEV, dev                                        # noqa: E402
 
-DEV = "cuda:0"
 GRIDS = [(65, 67), (40, 131), (130, 33)]                            # (W, H): line stride and number of lines
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 def _sub_grid(A, s, Wg, Hg):

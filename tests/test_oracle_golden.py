@@ -12,6 +12,7 @@ import scipy.sparse as sp
 from conftest import load_golden, coo_from
 from oracle import kernels as K
 from oracle import vcycle_ref as V
+from support import ReplayModel
 
 RTOL = 1e-12
 
@@ -164,22 +165,6 @@ def test_hoisted_cycle_matches_faithful_cycle():
     h = V.HoistedVCycle(A, hier)
     uh = h.cycle(np.zeros(65), rhs, "GaussSeidel", 2)
     np.testing.assert_allclose(uh, u.ravel(), rtol=1e-11, atol=1e-15)
-
-
-class ReplayModel:
-    """Feeds back the predictions recorded from the reference run (fixture g7), keyed by the
-    number of patches, and checks that it is shown the same features."""
-
-    def __init__(self, g):
-        self.table = {g["features_l0"].shape[0]: (g["features_l0"], g["pred_l0"]),
-                      g["features_l1"].shape[0]: (g["features_l1"], g["pred_l1"])}
-        self.calls = 0
-
-    def predict(self, data):
-        feats, pred = self.table[data.shape[0]]
-        np.testing.assert_allclose(data, feats, rtol=1e-11, atol=1e-16)
-        self.calls += 1
-        return pred
 
 
 def test_g7_neuralmg_multilevel():

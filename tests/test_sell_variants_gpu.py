@@ -13,8 +13,6 @@ hung on the operator, and sell_ju / sell_nt force every instantiation:
 
 Outputs are the head of a longer allocation whose tail must keep its sentinel, and start as NaN wherever the kernel must
 not read them (sweep_variants.check_sweeps)."""
-import functools
-
 import numpy as np
 import pytest
 
@@ -26,42 +24,7 @@ from learnmultigrid_amd import ops                                   # noqa: E40
 from oracle import kernels as K                                      # noqa: E402  (checker only)
 
 DEV = SV.DEV
-JUS = (0, 5, 7, 8, 10)
-NTS = (0, 1)
-UNIFORM = (13, 35, 40, 41)
-CASES = ["uniform_%d" % L for L in UNIFORM] + ["short_9", "ragged_slices"]
-
-
-def ragged_rows():
-    """(row lengths, diagonal present) of the ragged case, slice by slice."""
-    n = 321
-    i = np.arange(64)
-    lens = np.concatenate([
-        np.full(64, 20),                              # slice 0: uniform
-        (i * 7) % 31,                                 # slice 1: every length 0 .. 30, in no order
-        np.zeros(64, dtype=np.int64),                 # slice 2: nothing at all
-        (i % 3 == 0).astype(np.int64),                # slice 3: the longest row has one entry, two of three have none
-        np.where(i % 5 == 2, 0, 30),                  # slice 4: empty rows between long ones
-        [17]])                                        # slice 5: one row
-    rows = np.arange(n)
-    diag = (lens > 0) & ~((rows // 64 == 1) & (rows % 2 == 1)) & ~((rows // 64 == 3) & (rows % 2 == 1))
-    assert lens.size == n and set(lens[64:128]) == set(range(31))
-    return lens, diag
-
-
-@functools.lru_cache(maxsize=None)
-def problem(name):
-    if name.startswith("uniform_"):
-        L, n = int(name.split("_")[1]), 200
-        lens, diag = np.full(n, L), np.ones(n, dtype=bool)
-    elif name == "short_9":
-        n = 130
-        lens, diag = np.full(n, 9), np.ones(n, dtype=bool)
-    else:
-        lens, diag = ragged_rows()
-        n = lens.size
-    A = SV.rows_matrix(n, n, lens, diag, seed=100 + n + int(lens.max()))
-    return SV.Problem(A, seed=n)
+CASES, JUS, NTS, problem = SV.SELL_CASES, SV.SELL_JUS, SV.SELL_NTS, SV.sell_problem
 
 
 def sell_operator(A, colmode):

@@ -697,7 +697,7 @@ def test_degenerate_calls():
 
 def test_g7_neuralmg_constructor_and_multilevel_run():
     from learnmultigrid_amd.solvers import NeuralMG
-    from test_oracle_golden import ReplayModel
+    from support import ReplayModel
     g = load_golden("g7_neuralmg_ne64")
     A, rhs, M = coo_from(g, "A"), g["rhs"], g["M"]
     mg = NeuralMG(A, rhs, ReplayModel(g), M, np.ones(7), np.zeros(7))

@@ -5,33 +5,13 @@ transfers on and off (tile_hot_transfers), 16- and 32-line tiles, two and four l
 and odd grids, grids less than two tiles wide, and the pattern-table paths of P and R."""
 import numpy as np
 import pytest
-import scipy.sparse as sp
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-from learnmultigrid_amd import ops, problems as P   # noqa: E402
-from oracle import kernels as K                     # noqa: E402  (checker only)
-
-DEV = "cuda:0"
-KNOBS = ("tile_hot_transfers", "tile_rows", "tile_rows_big", "tile_prol_wide_lines_hx")
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def operators(side, kind):
-    """(A, P, R) on a side^2 grid (side odd): the 5-point Poisson operator or the 9-point Galerkin operator of the
-    next finer grid, the tensor-product interpolation onto it from ((side + 1) / 2)^2 nodes and its transpose."""
-    if kind == "5pt":
-        A = K.as_csr(P.poisson_2d_structured(side - 1)[0])
-    else:
-        Af = P.poisson_2d_structured(2 * (side - 1))[0]
-        Pf = P.tensor_interpolator_2d(2 * (side - 1) + 1)
-        A = K.as_csr(sp.csr_matrix(Pf.T @ Af @ Pf))
-    Pm = sp.csr_matrix(P.tensor_interpolator_2d(side))
-    return A, K.as_csr(Pm), K.as_csr(sp.csr_matrix(Pm.T))
+from fused_checks import LAYOUTS, check_post, check_pre, tile_knobs as knobs   # noqa: E402
+from learnmultigrid_amd import ops                  # noqa: E402
+from support import DEV, dev, operators             # noqa: E402
 
 
 def packed(A, Pm, Rm):
@@ -41,50 +21,6 @@ def packed(A, Pm, Rm):
     assert ops._fused_kind(dA) == "tile"
     assert ops.stencil_smooth_prolong_available(dA, dP) and ops.stencil_smooth_restrict_available(dA, dR)
     return dA, dP, dR
-
-
-class knobs:
-    def __init__(self, **kw):
-        self.kw = kw
-
-    def __enter__(self):
-        self.old = {k: ops.tune_get(k) for k in KNOBS}
-        for k, v in self.kw.items():
-            ops.tune_set(k, v)
-
-    def __exit__(self, *exc):
-        for k, v in self.old.items():
-            ops.tune_set(k, v)
-
-
-def check_pre(A, Rm, dA, dR, x0, b, sweeps=(1, 2, 3), zeros=(False, True)):
-    n, nc = A.shape[0], Rm.shape[0]
-    for zero in zeros:
-        want = np.zeros(n) if zero else x0.copy()
-        for S in range(1, max(sweeps) + 1):
-            want = K.jacobi(A, want, b, 0.8)
-            if S not in sweeps:
-                continue
-            wbc = K.spmv(Rm, K.residual(A, want, b)[0])
-            out = torch.full((n,), np.nan, dtype=torch.float64, device=DEV)
-            bc = torch.full((nc,), np.nan, dtype=torch.float64, device=DEV)
-            ops.stencil_smooth(dA, None if zero else dev(x0), dev(b), 0.8, S, out, None, restrict=(dR, bc))
-            assert np.array_equal(out.cpu().numpy(), want), (n, S, zero)
-            got = bc.cpu().numpy()
-            assert np.array_equal(got, wbc), (n, S, zero, np.flatnonzero(got != wbc)[:8])
-
-
-def check_post(A, Pm, dA, dP, x0, b, e, sweeps=(1, 2, 3)):
-    n = A.shape[0]
-    want = K.spmv(Pm, e, x0.copy(), 1.0, 1.0)
-    for S in range(1, max(sweeps) + 1):
-        want = K.jacobi(A, want, b, 0.8)
-        if S not in sweeps:
-            continue
-        out = torch.full((n,), np.nan, dtype=torch.float64, device=DEV)
-        ops.stencil_smooth(dA, dev(x0), dev(b), 0.8, S, out, None, prolong=(dP, dev(e)))
-        got = out.cpu().numpy()
-        assert np.array_equal(got, want), (n, S, np.flatnonzero(got != want)[:8])
 
 
 @pytest.fixture(scope="module")
@@ -128,9 +64,6 @@ def test_level1_hot_transfers_match_the_previous_kernels(level1):
 # grids: odd and uneven sizes, widths that are no multiple of a tile's inner part, 65 / 99 columns (less than two
 # 64-column tiles: the correction finds its coarse window by division)
 CASES = [(65, "5pt"), (99, "5pt"), (99, "9pt"), (769, "5pt"), (769, "9pt"), (1029, "9pt"), (1537, "5pt")]
-# every instantiation of the transfer passes: 16- / 32-line tiles, the correcting pass on 2 or 4 lines per wave
-LAYOUTS = [dict(tile_rows=16, tile_rows_big=16), dict(tile_rows=32, tile_rows_big=32, tile_prol_wide_lines_hx=1 << 30),
-           dict(tile_rows=32, tile_rows_big=32, tile_prol_wide_lines_hx=0)]
 
 
 @pytest.mark.parametrize("side,kind", CASES)

@@ -11,13 +11,9 @@ pytestmark = pytest.mark.gpu
 import chebyshev_ref as C                                        # noqa: E402
 from learnmultigrid_amd import ops, problems as P, torch_ops    # noqa: E402
 from oracle import kernels as K                                  # noqa: E402  (checker only)
+from support import dev                                          # noqa: E402
 
-DEV = "cuda:0"
 SWEEPS = (0, 1, 3, 4, 7)
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 def _operator(name):
