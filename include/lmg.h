@@ -418,6 +418,29 @@ int lmg_sell_fill_f32(int64_t n, const int32_t *d_rowptr, const int32_t *d_colid
                       const int64_t *d_slice_base, const int32_t *d_slice_cmin, int colmode, void *d_col_out,
                       float *d_val_out, int32_t *d_flag, void *stream);
 
+/* ---- the SELL sweeps on a block of k vectors: one pass over the matrix for k right-hand sides ----------------------------
+ * Layout: a block of k vectors of length n is ONE contiguous fp64 array, X[i * k + j] = row i, column j (row-major,
+ * interleaved), k = 2, 4 or 8 (LMG_ERR_ARG otherwise), base 16-byte aligned (LMG_ERR_ALIGN otherwise: d_X, d_B, d_Out).
+ * lmg_sell_sweep_block: modes, SELL arguments (fp64 values only) and null rules of lmg_sell_sweep; d_X has k columns of the
+ * matrix's column count, d_B and d_Out k columns of n rows.  An entry's column and value are loaded once, the k values of
+ * its row of d_X as 16-byte loads.  No overlap: d_Out must not alias d_X (mode 1, Jacobi, and mode 2; LMG_ERR_ARG where
+ * the bases are equal), the sweeps are not in place.  Summation order: column j accumulates its row in storage order
+ * with separately rounded products, like lmg_sell_sweep -- the diagonal rule, diag == 0 -> out = x and the alpha / beta
+ * special cases included --, so column j of d_Out carries the bits of lmg_sell_sweep run on column j alone.  A zero
+ * column stays zero.  Mode 0: d_norm2[j] (k doubles) = sum of r_ij^2 over i, reduced per column over the same row -> lane
+ * -> workgroup map and in the same order as lmg_sell_sweep's norm2; d_partials: lmg_block_partials_count(n, k) doubles of
+ * scratch.  n == 0: LMG_OK, nothing is touched.  Every argument error is returned before any HIP call.
+ * lmg_dense_gemv_block: Y = M X for a dense row-major n x m matrix and blocks X (m x k), Y (n x k): the coarsest-level
+ * solve with the dense inverse, M read once for all k columns.  One wave per row; a lane adds the pairs (m even) or
+ * elements (m odd) lmg_dense_gemv's one-wave-per-row kernel gives it, in its order, and the wave butterfly runs per column:
+ * column j of Y has the bits of that kernel on column j.  d_M, d_X, d_Y 16-byte aligned; d_Y must not alias d_X. */
+int64_t lmg_block_partials_count(int64_t n, int k);
+int lmg_sell_sweep_block(int mode, int k, int64_t n, const int64_t *d_slice_base, const int32_t *d_slice_len,
+                         const int32_t *d_slice_cmin, const int32_t *d_rowlen, const void *d_col, int colmode,
+                         const double *d_val, int32_t max_len, const double *d_X, const double *d_B, double *d_Out,
+                         double alpha, double beta, double *d_partials, double *d_norm2, void *stream);
+int lmg_dense_gemv_block(int k, int64_t n, int64_t m, const double *d_M, const double *d_X, double *d_Y, void *stream);
+
 /* ---- building the packed twin (setup) ----------------------------------------------
  * One streaming pass each; learnmultigrid_amd/ops.py PackedCSR.from_csr is the calling sequence.
  *   lmg_pcsr_tile_colrange   smallest / largest column of every tile of `tile_rows` rows

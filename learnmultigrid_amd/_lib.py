@@ -79,6 +79,10 @@ SIGNATURES = {
     "lmg_sell_fill": (_c.c_int, [_i64, _p, _p, _p, _p, _p, _c.c_int, _p, _p, _p]),
     "lmg_sell_sweep_f32": (_c.c_int, [_c.c_int, _i64, _p, _p, _p, _p, _p, _c.c_int, _p, _i32, _p, _p, _p, _f64, _f64, _p, _p, _p]),
     "lmg_sell_fill_f32": (_c.c_int, [_i64, _p, _p, _p, _p, _p, _c.c_int, _p, _p, _p, _p]),
+    "lmg_block_partials_count": (_i64, [_i64, _c.c_int]),
+    "lmg_sell_sweep_block": (_c.c_int, [_c.c_int, _c.c_int, _i64, _p, _p, _p, _p, _p, _c.c_int, _p, _i32, _p, _p, _p, _f64, _f64,
+                                        _p, _p, _p]),
+    "lmg_dense_gemv_block": (_c.c_int, [_c.c_int, _i64, _i64, _p, _p, _p, _p]),
     "lmg_pcsr_tile_colrange":(_c.c_int, [_i64, _i32, _p, _p, _p, _p, _p]),
     "lmg_pcsr_encode_cols16": (_c.c_int, [_i64, _i32, _p, _p, _p, _p, _p]),
     "lmg_value_set_collect": (_c.c_int, [_p, _i64, _p, _i32, _p, _p]),

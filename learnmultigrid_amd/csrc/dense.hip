@@ -86,6 +86,64 @@ __global__ void __launch_bounds__(kLmgBlock) dense_gemv_kernel(int64_t n, int64_
     }
 }
 
+// Y = M X on a block of K vectors (X[i * K + j]: row i, column j; K = 2, 4, 8): one wave per row like dense_gemv_kernel,
+// M is read once for all K columns.  A lane takes the pairs (even m) or elements (odd m) dense_gemv_kernel gives it and
+// adds them in lmg_row_partial's order, the wave butterfly runs per column: column j has the bits of dense_gemv_kernel
+// on column j.  The two rows of X a pair multiplies are 2 K contiguous doubles, read as 16-byte loads.
+template <int K>
+__global__ void __launch_bounds__(kLmgBlock) dense_gemv_block_kernel(int64_t n, int64_t m, const double *M, const double *X,
+                                                                     double *Y)
+{
+    const WaveRows w = wave_rows();
+    const d2 *X2 = reinterpret_cast<const d2 *>(X);
+    const bool vec_ok = (m % 2 == 0);
+    for (int64_t row = w.first; row < n; row += w.step) {
+        const double *Mr = M + row * m;
+        double s[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) s[k] = 0.0;
+        if (vec_ok) {
+            const double2 *M2 = reinterpret_cast<const double2 *>(Mr);
+            for (int64_t j = w.lane; j < m / 2; j += LMG_WAVE) {
+                const double2 mv = M2[j];
+                d2 xa[K / 2], xb[K / 2];
+#pragma unroll
+                for (int h = 0; h < K / 2; ++h) {
+                    xa[h] = X2[j * K + h];                      // row 2 j
+                    xb[h] = X2[j * K + K / 2 + h];              // row 2 j + 1
+                }
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    s[k] += mv.x * xa[k / 2][k & 1];
+                    s[k] += mv.y * xb[k / 2][k & 1];
+                }
+            }
+        } else {
+            for (int64_t j = w.lane; j < m; j += LMG_WAVE) {
+                const double mv = Mr[j];
+#pragma unroll
+                for (int h = 0; h < K / 2; ++h) {
+                    const d2 xv = X2[j * (K / 2) + h];
+                    s[2 * h] += mv * xv[0];
+                    s[2 * h + 1] += mv * xv[1];
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < K; ++k) s[k] = lmg_wave_sum(s[k]);
+        if (w.lane == 0) {
+            d2 *Y2 = reinterpret_cast<d2 *>(Y) + row * (K / 2);
+#pragma unroll
+            for (int h = 0; h < K / 2; ++h) {
+                d2 o;
+                o[0] = s[2 * h];
+                o[1] = s[2 * h + 1];
+                Y2[h] = o;
+            }
+        }
+    }
+}
+
 // The same product with one WORKGROUP (4 waves) per row: a few thousand long rows (the Schur-complement
 // inverse of the banded coarse solver, 2967 x 2967) give one wave per row too little to keep 256 CUs busy
 // (26 us for 70 MB; 4 waves per row: see DESIGN.md).  The four partial sums are added in wave order, so the
@@ -387,6 +445,22 @@ int lmg_dense_gemv(int64_t n, int64_t m, const double *M, const double *x, doubl
     }
     hipLaunchKernelGGL(dense_gemv_kernel, dim3(lmg_grid_for(n, kLmgBlock / LMG_WAVE)), dim3(kLmgBlock), 0,
                        lmg_stream(stream), n, m, M, x, y, (int64_t)0);
+    LMG_CHECK_LAUNCH();
+    return LMG_OK;
+}
+
+int lmg_dense_gemv_block(int k, int64_t n, int64_t m, const double *M, const double *X, double *Y, void *stream)
+{
+    if (k != 2 && k != 4 && k != 8) return LMG_ERR_ARG;
+    if (n < 0 || m < 0) return LMG_ERR_ARG;
+    if (n == 0) return LMG_OK;
+    if (!Y || (m > 0 && (!M || !X)) || X == Y) return LMG_ERR_ARG;
+    if (!lmg_aligned16(M) || !lmg_aligned16(X) || !lmg_aligned16(Y)) return LMG_ERR_ALIGN;
+    const dim3 grid(lmg_grid_for(n, kLmgBlock / LMG_WAVE)), block(kLmgBlock);
+    hipStream_t st = lmg_stream(stream);
+    if (k == 2) hipLaunchKernelGGL(dense_gemv_block_kernel<2>, grid, block, 0, st, n, m, M, X, Y);
+    else if (k == 4) hipLaunchKernelGGL(dense_gemv_block_kernel<4>, grid, block, 0, st, n, m, M, X, Y);
+    else hipLaunchKernelGGL(dense_gemv_block_kernel<8>, grid, block, 0, st, n, m, M, X, Y);
     LMG_CHECK_LAUNCH();
     return LMG_OK;
 }

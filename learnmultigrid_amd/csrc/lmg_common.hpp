@@ -56,6 +56,8 @@ static inline int lmg_check_sweep_args(int mode, const double *x, const double *
 
 // norm2[0] = sum of partials[0 .. count) in fixed order: the launch that follows a residual sweep (sweep.hip)
 int lmg_reduce_partials(const double *partials, int64_t count, double *norm2, hipStream_t st);
+// the strided form: norm2[j] = sum of partials[i * k + j], i < count, for j < k -- column j in lmg_reduce_partials' order
+int lmg_reduce_partials_strided(const double *partials, int64_t count, int k, double *norm2, hipStream_t st);
 
 // ---- XCD-aware tile ownership ---------------------------------------------------------------------------------------
 // Workgroup b runs on XCD b % 8 (round-robin dispatch), so XCD k is given the k-th contiguous eighth of the tiles and

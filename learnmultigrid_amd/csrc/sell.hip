@@ -113,6 +113,138 @@ __global__ void __launch_bounds__(kBlock) sell_sweep_kernel(SArgs a)
     }
 }
 
+// ---- the same sweeps on a block of K vectors ---------------------------------------------------
+// X[i * K + j] = row i, column j (K = 2, 4, 8; 16-byte aligned base).  One wave per slice, lane = row as above; an
+// entry's column and value are loaded ONCE and serve K accumulators, the K values x[c*K .. c*K + K) come as K/2
+// 16-byte loads, and the outputs leave as 16-byte stores: the matrix bytes of a sweep are shared by K columns.
+// Column j carries the bits of sell_sweep_kernel run on column j alone: storage order, separately rounded products,
+// the same diagonal sum (one per row, whatever the column), diag == 0 -> out = x, the same alpha / beta special cases.
+// The Jacobi iterate of the row is read once at the end instead of being carried from the diagonal entry -- the value
+// is x[row] either way -- which saves K registers per lane.  norm2[j]: the same lane -> wave -> workgroup sums per column;
+// workgroup blk leaves its K sums at partial[blk * K + j].
+template <int K>
+constexpr int block_ju()
+{
+    // entries of a row in flight (K doubles of x each): 5 divides the 25-entry rows and leaves one idle slot in ten
+    // trips over 49 entries; at K = 8 the gathered values alone are 16 registers per entry -- 4 keeps the kernel at
+    // 96 - 102 VGPRs (4 - 5 waves per SIMD, no scratch), see DESIGN.md section 3 (block of right-hand sides)
+    return K == 8 ? 4 : 5;
+}
+
+template <int MODE, bool COL16, int K, int JU, bool NT>
+__global__ void __launch_bounds__(kBlock) sell_sweep_block_kernel(SArgs a)
+{
+    __shared__ double s_red[K][kBlock / LMG_WAVE];
+    constexpr int H = K / 2;                                   // 16-byte pieces of a row of a block
+    typedef typename std::conditional<COL16, unsigned short, int>::type col_t;
+    const col_t *col = static_cast<const col_t *>(a.col);
+    const double *val = static_cast<const double *>(a.val);
+    const d2 *x2 = reinterpret_cast<const d2 *>(a.x);
+    const int lane = threadIdx.x & (LMG_WAVE - 1), wave = threadIdx.x / LMG_WAVE;
+    const int blk = lmg_xcd_tile(a.blocks_per_xcd);
+    const int slice = blk * kSlicesPerBlock + wave;
+    double local[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) local[k] = 0.0;
+    if (blk < a.nblocks && slice < a.nslices) {
+        const int row = slice * LMG_WAVE + lane;
+        const bool valid = row < a.n;
+        const int len = valid ? a.rowlen[row] : 0;
+        const int slen = a.slice_len[slice];
+        const long long base = a.slice_base[slice] + lane;
+        const int cb = COL16 ? a.slice_cmin[slice] : 0;
+        const long long rbase = (long long)row * H;
+        double acc[K], diag = 0.0;
+#pragma unroll
+        for (int k = 0; k < K; ++k) acc[k] = 0.0;
+        for (int j0 = 0; j0 < slen; j0 += JU) {
+            int c[JU];
+            double v[JU];
+            d2 xv[JU][H];
+#pragma unroll
+            for (int jj = 0; jj < JU; ++jj) {
+                const int j = (j0 + jj < slen) ? j0 + jj : slen - 1;      // padded storage: always readable
+                const long long e = base + (long long)j * LMG_WAVE;
+                c[jj] = cb + (int)(NT ? __builtin_nontemporal_load(col + e) : col[e]);
+                v[jj] = NT ? __builtin_nontemporal_load(val + e) : val[e];
+            }
+#pragma unroll
+            for (int jj = 0; jj < JU; ++jj) {
+                const long long xb = (long long)((j0 + jj < len) ? c[jj] : 0) * H;
+#pragma unroll
+                for (int h = 0; h < H; ++h) xv[jj][h] = x2[xb + h];
+            }
+#pragma unroll
+            for (int jj = 0; jj < JU; ++jj) {
+                const bool act = j0 + jj < len;
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    const double s2 = acc[k] + v[jj] * xv[jj][k / 2][k & 1];
+                    acc[k] = act ? s2 : acc[k];
+                }
+                if (MODE == MODE_JACOBI) diag = (act && c[jj] == row) ? diag + v[jj] : diag;
+            }
+        }
+        if (valid) {
+            d2 *o2 = reinterpret_cast<d2 *>(a.out);
+            if (MODE == MODE_RESIDUAL) {
+                const d2 *b2 = reinterpret_cast<const d2 *>(a.b);
+#pragma unroll
+                for (int h = 0; h < H; ++h) {
+                    const d2 bv = b2[rbase + h];
+                    d2 r;
+                    r[0] = bv[0] - acc[2 * h];
+                    r[1] = bv[1] - acc[2 * h + 1];
+                    if (a.out) o2[rbase + h] = r;
+                    local[2 * h] = r[0] * r[0];
+                    local[2 * h + 1] = r[1] * r[1];
+                }
+            } else if (MODE == MODE_JACOBI) {
+                const d2 *b2 = reinterpret_cast<const d2 *>(a.b);
+                const double rd = 1.0 / diag;
+#pragma unroll
+                for (int h = 0; h < H; ++h) {
+                    const d2 bv = b2[rbase + h], xi = x2[rbase + h];
+                    d2 o = xi;
+                    if (diag != 0.0) {
+                        o[0] = xi[0] + a.alpha * (rd * (bv[0] - acc[2 * h]));
+                        o[1] = xi[1] + a.alpha * (rd * (bv[1] - acc[2 * h + 1]));
+                    }
+                    o2[rbase + h] = o;
+                }
+            } else {
+#pragma unroll
+                for (int h = 0; h < H; ++h) {
+                    d2 s;
+                    s[0] = acc[2 * h];
+                    s[1] = acc[2 * h + 1];
+                    if (a.alpha != 1.0) {
+                        s[0] = a.alpha * s[0];
+                        s[1] = a.alpha * s[1];
+                    }
+                    if (a.beta == 1.0) {
+                        const d2 y = o2[rbase + h];
+                        s[0] = y[0] + s[0];
+                        s[1] = y[1] + s[1];
+                    } else if (a.beta != 0.0) {
+                        const d2 y = o2[rbase + h];
+                        s[0] = a.beta * y[0] + s[0];
+                        s[1] = a.beta * y[1] + s[1];
+                    }
+                    o2[rbase + h] = s;
+                }
+            }
+        }
+    }
+    if (MODE == MODE_RESIDUAL && a.partial != nullptr) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const double tot = lmg_block_sum<kBlock>(local[k], s_red[k]);      // (one LDS row per column: no reuse hazard)
+            if (threadIdx.x == 0 && blk < a.nblocks) a.partial[(long long)blk * K + k] = tot;
+        }
+    }
+}
+
 // ---- building the format (setup) -------------------------------------------------------------
 // one wave per slice: padded length and column range
 __global__ void __launch_bounds__(kBlock) sell_slice_info_kernel(int64_t n, int64_t nslices, const int *__restrict__ rowptr,
@@ -264,6 +396,25 @@ int sell_sweep(int mode, int64_t n, const int64_t *slice_base, const int32_t *sl
     return LMG_OK;
 }
 
+// The block sweep's kernel for (mode, colmode, k, nt): JU is fixed per K (block_ju), there is no tune key of its own.
+template <int MODE, bool COL16, int K>
+int launch_block(const SArgs &a, bool nt, hipStream_t st)
+{
+    const dim3 grid((unsigned)(a.blocks_per_xcd * 8)), block(kBlock);
+    if (nt) hipLaunchKernelGGL((sell_sweep_block_kernel<MODE, COL16, K, block_ju<K>(), true>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((sell_sweep_block_kernel<MODE, COL16, K, block_ju<K>(), false>), grid, block, 0, st, a);
+    LMG_CHECK_LAUNCH();
+    return LMG_OK;
+}
+template <int MODE, bool COL16>
+int launch_block_k(const SArgs &a, int k, bool nt, hipStream_t st)
+{
+    return k == 2 ? launch_block<MODE, COL16, 2>(a, nt, st)
+         : k == 4 ? launch_block<MODE, COL16, 4>(a, nt, st) : launch_block<MODE, COL16, 8>(a, nt, st);
+}
+
+inline bool block_width_ok(int k) { return k == 2 || k == 4 || k == 8; }
+
 // flag: the range flag of the fp32 form (null for fp64 values, which the kernel then never touches)
 template <typename VT>
 int sell_fill(int64_t n, const int32_t *rowptr, const int32_t *colidx, const double *vals, const int64_t *slice_base,
@@ -313,6 +464,58 @@ int lmg_sell_sweep_f32(int mode, int64_t n, const int64_t *slice_base, const int
 {
     return sell_sweep<float>(mode, n, slice_base, slice_len, slice_cmin, rowlen, col, colmode, val, max_len, x, b, out, alpha,
                              beta, partials, norm2, stream);
+}
+
+int64_t lmg_block_partials_count(int64_t n, int k)
+{
+    // one row of k sums per workgroup of the block sweep (kSlicesPerBlock slices of 64 rows), at least one row
+    const int64_t nslices = n > 0 ? (n + LMG_WAVE - 1) / LMG_WAVE : 0;
+    const int64_t nblocks = (nslices + kSlicesPerBlock - 1) / kSlicesPerBlock;
+    return (nblocks < 1 ? 1 : nblocks) * (int64_t)(k < 1 ? 1 : k);
+}
+
+int lmg_sell_sweep_block(int mode, int k, int64_t n, const int64_t *slice_base, const int32_t *slice_len,
+                         const int32_t *slice_cmin, const int32_t *rowlen, const void *col, int colmode, const double *val,
+                         int32_t max_len, const double *X, const double *B, double *Out, double alpha, double beta,
+                         double *partials, double *norm2, void *stream)
+{
+    if (!block_width_ok(k)) return LMG_ERR_ARG;
+    if (n < 0 || n >= INT32_MAX - 64 || (colmode != 0 && colmode != 1) || max_len < 0) return LMG_ERR_ARG;
+    if (n == 0) return LMG_OK;
+    if (!slice_base || !slice_len || !rowlen || !col || !val || !X) return LMG_ERR_ARG;
+    if (colmode == 0 && !slice_cmin) return LMG_ERR_ARG;
+    if (lmg_check_sweep_args(mode, X, B, Out, partials, norm2) != LMG_OK) return LMG_ERR_ARG;
+    if (!lmg_aligned16(X) || !lmg_aligned16(B) || !lmg_aligned16(Out)) return LMG_ERR_ALIGN;      // (null is aligned)
+    SArgs a;
+    a.n = (int)n;
+    a.nslices = (int)((n + LMG_WAVE - 1) / LMG_WAVE);
+    a.nblocks = (a.nslices + kSlicesPerBlock - 1) / kSlicesPerBlock;
+    a.blocks_per_xcd = (a.nblocks + 7) / 8;
+    a.slice_base = reinterpret_cast<const long long *>(slice_base);
+    a.slice_len = slice_len;
+    a.slice_cmin = slice_cmin;
+    a.rowlen = rowlen;
+    a.col = col;
+    a.val = val;
+    a.x = X;
+    a.b = B;
+    a.out = Out;
+    a.alpha = alpha;
+    a.beta = beta;
+    a.partial = (mode == MODE_RESIDUAL) ? partials : nullptr;
+    hipStream_t st = lmg_stream(stream);
+    const bool nt = g_sell_nt == 1 || (g_sell_nt < 0 && (int64_t)a.n * max_len >= g_sell_nt_entries);     // launch()'s rule
+    int rc;
+    if (colmode == 0) {
+        rc = mode == MODE_RESIDUAL ? launch_block_k<MODE_RESIDUAL, true>(a, k, nt, st)
+           : mode == MODE_JACOBI ? launch_block_k<MODE_JACOBI, true>(a, k, nt, st) : launch_block_k<MODE_SPMV, true>(a, k, nt, st);
+    } else {
+        rc = mode == MODE_RESIDUAL ? launch_block_k<MODE_RESIDUAL, false>(a, k, nt, st)
+           : mode == MODE_JACOBI ? launch_block_k<MODE_JACOBI, false>(a, k, nt, st) : launch_block_k<MODE_SPMV, false>(a, k, nt, st);
+    }
+    if (rc != LMG_OK) return rc;
+    if (mode == MODE_RESIDUAL && partials) return lmg_reduce_partials_strided(partials, a.nblocks, k, norm2, st);
+    return LMG_OK;
 }
 
 int lmg_sell_slice_info(int64_t n, const int32_t *rowptr, const int32_t *colidx, int32_t *slice_len, int32_t *cmin,

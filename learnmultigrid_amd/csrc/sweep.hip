@@ -138,21 +138,36 @@ __global__ void __launch_bounds__(BLOCK) csr_sweep_kernel(SweepArgs a)
 
 // Final deterministic reduction of the partial sums of a residual sweep of ANY format (lmg_reduce_partials): one
 // workgroup, fixed order, four independent chains per thread so the loads pipeline.
-__global__ void __launch_bounds__(1024) reduce_partials_kernel(const double *partial, int64_t count,
-                                                               double *out)
+// Stride: the distance between two partials of the sum -- the constant 1, or a launch argument (the block sweeps of
+// sell.hip keep the k sums of a workgroup side by side) -- the same chains and the same order either way.
+template <typename Stride>
+__device__ __forceinline__ void reduce_partials(const double *partial, int64_t count, Stride stride, double *out)
 {
     __shared__ double s_red[1024 / LMG_WAVE];
     double v0 = 0.0, v1 = 0.0, v2 = 0.0, v3 = 0.0;
     int64_t i = threadIdx.x;
     for (; i + 3 * 1024 < count; i += 4 * 1024) {
-        v0 += partial[i];
-        v1 += partial[i + 1024];
-        v2 += partial[i + 2048];
-        v3 += partial[i + 3072];
+        v0 += partial[i * stride];
+        v1 += partial[(i + 1024) * stride];
+        v2 += partial[(i + 2048) * stride];
+        v3 += partial[(i + 3072) * stride];
     }
-    for (; i < count; i += 1024) v0 += partial[i];
+    for (; i < count; i += 1024) v0 += partial[i * stride];
     const double tot = lmg_block_sum<1024>((v0 + v1) + (v2 + v3), s_red);
     if (threadIdx.x == 0) out[0] = tot;
+}
+
+__global__ void __launch_bounds__(1024) reduce_partials_kernel(const double *partial, int64_t count,
+                                                               double *out)
+{
+    reduce_partials(partial, count, std::integral_constant<int64_t, 1>{}, out);
+}
+
+// workgroup j: out[j] = sum of partial[i * stride + j], i < count
+__global__ void __launch_bounds__(1024) reduce_partials_strided_kernel(const double *partial, int64_t count, int64_t stride,
+                                                                       double *out)
+{
+    reduce_partials(partial + blockIdx.x, count, stride, out + blockIdx.x);
 }
 
 // ---- tile geometry variants -----------------------------------------------------------------
@@ -225,6 +240,13 @@ int check_csr(int64_t n, int64_t nnz, const void *rp, const void *ci, const void
 int lmg_reduce_partials(const double *partials, int64_t count, double *norm2, hipStream_t st)
 {
     hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(1024), 0, st, partials, count, norm2);
+    LMG_CHECK_LAUNCH();
+    return LMG_OK;
+}
+
+int lmg_reduce_partials_strided(const double *partials, int64_t count, int k, double *norm2, hipStream_t st)
+{
+    hipLaunchKernelGGL(reduce_partials_strided_kernel, dim3((unsigned)k), dim3(1024), 0, st, partials, count, (int64_t)k, norm2);
     LMG_CHECK_LAUNCH();
     return LMG_OK;
 }

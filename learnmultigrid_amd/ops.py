@@ -7,7 +7,7 @@ registers them) and the solver's internal calls.
 
 What lives here: DeviceCSR and its pack() policy -- which of the storage twins of twins.py an operator gets --, every
 enable switch and size threshold that picks a kernel, and one wrapper per entry point: sweeps, fused smoothing passes,
-Gauss-Seidel, vectors, dense blocks, SpGEMM, hipGraph capture.  The twins themselves -- their formats, their construction
+sweeps on blocks of right-hand sides, Gauss-Seidel, vectors, dense blocks, SpGEMM, hipGraph capture.  The twins themselves -- their formats, their construction
 and the C arguments that describe them -- are in twins.py and re-exported here under their old names.
 """
 import ctypes
@@ -726,6 +726,91 @@ def csr_spmv(A, x, y, alpha=1.0, beta=0.0):
     if x.numel() != A.shape[1] or y.numel() != A.shape[0]:
         raise ValueError("spmv shape mismatch: A %s, x %d, y %d" % (A.shape, x.numel(), y.numel()))
     _sweep(2, A, x, None, y, alpha, beta, None, None)
+
+
+# ---- sweeps on a block of right-hand sides ---------------------------------------------------------
+# A block of k vectors is a 2-D contiguous (n, k) tensor -- X[i, j] at i * k + j --, k in BLOCK_WIDTHS, 16-byte aligned: the
+# matrix bytes of a sweep are read once for the k columns (lmg_sell_sweep_block), column j with the bits of the
+# single-vector SELL sweep on column j.  The driver is block.py (BlockCycle); nothing here is a torch.ops.lmg op.
+BLOCK_WIDTHS = (2, 4, 8)
+
+
+def block_twin(A):
+    """The fp64 sliced-ELL twin the block sweeps read, of any DeviceCSR (square or rectangular): A.sell where pack() chose
+    one with fp64 values, else a twin of its own, built whatever the padding costs."""
+    S = A.sell
+    if S is None or S.values != "f64":
+        S = SellCSR.from_csr(A, max_padding=float("inf"))
+    if S is None:
+        raise ValueError("block_twin: a %s matrix with %d entries has no sliced-ELL twin" % (A.shape, A.nnz))
+    return S
+
+
+def _block_ok(*blocks):
+    """2-D contiguous float64 device tensors (rows, k) of one width k in BLOCK_WIDTHS, 16-byte aligned; returns k."""
+    k = None
+    for t in blocks:
+        if t is None:
+            continue
+        _vec_ok(t)
+        if t.dim() != 2 or t.shape[1] not in BLOCK_WIDTHS or t.shape[1] != (k or t.shape[1]):
+            raise ValueError("expected (rows, k) blocks of one width k in %s, got %s" % (BLOCK_WIDTHS, tuple(t.shape)))
+        if t.data_ptr() % 16:
+            raise ValueError("a block must start at a 16-byte aligned address")
+        k = t.shape[1]
+    return k
+
+
+def _block_sweep(mode, S, X, B, Out, alpha, beta, partials, norm2):
+    k = _block_ok(X, B, Out)
+    n, m = S.shape
+    if X.shape[0] != m or any(t is not None and t.shape[0] != n for t in (B, Out)):
+        raise ValueError("block %s: matrix %s, X %s, B %s, Out %s" % (_MODE_NAMES[mode], S.shape, tuple(X.shape),
+                                                                       None if B is None else tuple(B.shape),
+                                                                       None if Out is None else tuple(Out.shape)))
+    if S.values != "f64":
+        raise ValueError("the block sweeps read fp64 values: build the twin with block_twin()")
+    head, t = S.sweep_args()
+    check(_lib.lib().lmg_sell_sweep_block(mode, k, *head, _p(X), _p(B), _p(Out), float(alpha), float(beta), _p(partials),
+                                          _p(norm2), _s(t)), "lmg_sell_sweep_block(%s)" % _MODE_NAMES[mode])
+
+
+def block_partials_count(n, k):
+    return int(_lib.lib().lmg_block_partials_count(int(n), int(k)))
+
+
+def block_residual_norm2(S, X, B, R, partials, norm2):
+    """R = B - A X (R may be None), norm2[j] = sum_i R[i, j]^2 for the k columns (partials / norm2 may both be None)."""
+    _vec_ok(partials, norm2)
+    k = _block_ok(X)
+    if (partials is None) != (norm2 is None):
+        raise ValueError("block_residual_norm2: partials and norm2 come together")
+    if norm2 is not None and (norm2.numel() < k or partials.numel() < block_partials_count(S.n, k)):
+        raise ValueError("block_residual_norm2: norm2 or partials too short for %d columns" % k)
+    if S.shape[0] != S.shape[1]:
+        raise ValueError("block_residual_norm2 needs a square matrix, got %s" % (S.shape,))
+    _block_sweep(0, S, X, B, R, 0.0, 0.0, partials, norm2)
+
+
+def block_jacobi(S, X, B, omega, Out):
+    """Out = X + omega D^-1 (B - A X) column by column (rows without a diagonal keep X); Out must not overlap X."""
+    if S.shape[0] != S.shape[1]:
+        raise ValueError("block_jacobi needs a square matrix, got %s" % (S.shape,))
+    _block_sweep(1, S, X, B, Out, omega, 0.0, None, None)
+
+
+def block_spmv(S, X, Y, alpha=1.0, beta=0.0):
+    """Y = alpha A X + beta Y column by column; Y must not overlap X."""
+    _block_sweep(2, S, X, None, Y, alpha, beta, None, None)
+
+
+def dense_gemv_block(M, X, Y):
+    """Y = M X for a dense (n, m) matrix and blocks X (m, k), Y (n, k): M is read once for the k columns."""
+    _vec_ok(M)
+    k = _block_ok(X, Y)
+    if M.dim() != 2 or X.shape[0] != M.shape[1] or Y.shape[0] != M.shape[0]:
+        raise ValueError("dense_gemv_block: M %s, X %s, Y %s" % (tuple(M.shape), tuple(X.shape), tuple(Y.shape)))
+    check(_lib.lib().lmg_dense_gemv_block(k, M.shape[0], M.shape[1], _p(M), _p(X), _p(Y), _s(M)), "lmg_dense_gemv_block")
 
 
 # ---- Gauss-Seidel ---------------------------------------------------------------------

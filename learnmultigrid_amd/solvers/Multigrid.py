@@ -44,6 +44,7 @@ class Multigrid(IterativeSolver):
         self.hierarchy = None              # optional list of transfer operators (all levels)
         self._hier = None
         self._hier_key = None
+        self._block_cycles = {}            # solve_many: {"H": the hierarchy, k: its BlockCycle of width k}
 
     # -- transfer-operator dispatch (Multigrid.py:91 -> :126 / :171 / :188) --------------------
     def interpolator(self, dimension, _first_call=False):
@@ -80,6 +81,7 @@ class Multigrid(IterativeSolver):
     def _invalidate(self):
         super()._invalidate()
         self._hier = None
+        self._block_cycles = {}
 
     @staticmethod
     def _effective_smoother(smoother, semantics):
@@ -194,6 +196,85 @@ class Multigrid(IterativeSolver):
         self.track_res = np.array(track, dtype=float).reshape(-1, 1)         # :75
         self.level_dims = H.sizes
 
+    # -- several right-hand sides at once (no counterpart in the reference) ----------------------
+    _FIRST_CALL = False            # the first_call solve() defaults to: solve_many shares solve()'s cached hierarchy
+
+    @on_device
+    def solve_many(self, rhs, levels=2, smooth_steps=1, max_iterations=100, error=1e-08, initial_guess=None, *,
+                   omega=1.0, cycle_shape="V", coarse_refine="auto", use_graph=False, smoother="Jacobi"):
+        """Solve A X = rhs for the m >= 1 columns of rhs (n, m) with one multigrid cycle per iteration on all of them:
+        every sweep reads its matrix once for up to 8 columns (block.BlockCycle) instead of once per column -- what pays
+        on hierarchies of learned or L2-type transfers, whose levels stream 25- and 49-entry rows; on constant-coefficient
+        grid hierarchies m calls of solve() are faster.  Returns (X, track): X (n, m), and
+        track (iterations, m), the true residual norms ||b_j - A x_j||_2 taken before each cycle -- no sqrt(n) first
+        entry, that quirk belongs to the reference's solve().
+        The smoother is weighted Jacobi with `omega`, smooth_steps sweeps before and after the coarse correction: this is
+        smoother_semantics="as_named" with smoother="Jacobi" (any other smoother raises ValueError), cycle_shape as in
+        solve().  Column j carries the bits of a single-vector sliced-ELL cycle on column j.
+        Columns are padded with zero columns to a width of 2, 4 or 8 and worked through in chunks of 8.  All columns of
+        a chunk iterate until every one is <= error or max_iterations is reached: a column that has passed is not
+        deflated, it simply keeps being smoothed (its residual keeps falling and is still recorded).
+        self.iterations_many[j]: the number of cycles before column j first passed, or max_iterations.  Rows of track
+        beyond the last iteration of a column's chunk (another chunk needed more) hold NaN."""
+        B = np.asarray(rhs, dtype=np.float64)
+        if B.ndim != 2 or B.shape[0] != self.dim or B.shape[1] < 1:
+            raise ValueError("rhs must be (n, m) with n = %d and m >= 1, got %s" % (self.dim, B.shape))
+        if levels < 2:
+            raise ValueError("levels must be >= 2 (levels counts grids)")
+        if smoother != "Jacobi":
+            raise ValueError("solve_many smooths with weighted Jacobi only, got smoother=%r" % (smoother,))
+        cycle_children(cycle_shape)
+        m = B.shape[1]
+        X0 = None
+        if initial_guess is not None:
+            X0 = np.asarray(initial_guess, dtype=np.float64)
+            if X0.shape != B.shape:
+                raise ValueError("initial_guess must have the shape of rhs %s, got %s" % (B.shape, X0.shape))
+        from ..block import BlockCycle, block_width
+        H = self._setup(levels, self._FIRST_CALL, coarse_refine)
+        X = np.empty_like(B)
+        tracks, its = [], np.full(m, int(max_iterations), dtype=np.int64)
+        wmax = ops.BLOCK_WIDTHS[-1]
+        H.stream.wait_stream(torch.cuda.current_stream(self._device))
+        with torch.cuda.stream(H.stream):
+            for c0 in range(0, m, wmax):
+                mc = min(wmax, m - c0)
+                k = block_width(mc, ops.BLOCK_WIDTHS)
+                if self._block_cycles.get("H") is not H:           # (one hierarchy at a time: a new one drops the old blocks)
+                    self._block_cycles = {"H": H}
+                bc = self._block_cycles.get(k)
+                if bc is None:
+                    bc = self._block_cycles[k] = BlockCycle(H, mc)
+                bc.use_columns(mc)
+                fine = bc.levels[0]
+                fine.b[:, :mc].copy_(torch.from_numpy(np.ascontiguousarray(B[:, c0:c0 + mc])).to(self._device))
+                if X0 is not None:
+                    fine.x[:, :mc].copy_(torch.from_numpy(np.ascontiguousarray(X0[:, c0:c0 + mc])).to(self._device))
+                graph = bc.captured(smooth_steps, omega, cycle_shape) if use_graph else None
+                rows = []
+                for it in range(int(max_iterations)):
+                    norms = np.array(bc.residual_norms())
+                    rows.append(norms)
+                    passed = norms <= error
+                    first = passed & (its[c0:c0 + mc] == max_iterations)
+                    its[c0:c0 + mc][first] = it
+                    self._log("It: ", it + 1, norms)
+                    if passed.all():
+                        break
+                    if graph is not None:
+                        graph.launch()
+                    else:
+                        bc.cycle(smooth_steps, omega, cycle_shape)
+                X[:, c0:c0 + mc] = bc.levels[0].x[:, :mc].cpu().numpy()
+                tracks.append(np.array(rows, dtype=float).reshape(len(rows), mc))
+        torch.cuda.current_stream(self._device).wait_stream(H.stream)
+        track = np.full((max((t.shape[0] for t in tracks), default=0), m), np.nan)
+        for i, t in enumerate(tracks):
+            track[:t.shape[0], i * wmax:i * wmax + t.shape[1]] = t
+        self.iterations_many = its
+        self.level_dims = H.sizes
+        return X, track
+
     # -- Multigrid.v_cycle (Multigrid.py:77) ------------------------------------------------------
     @on_device
     def v_cycle(self, A, u0, rhs, smoother, smooth_steps, error, levels, first_call=False, *,
@@ -300,6 +381,8 @@ class SemiGeometricMG(Multigrid):
         self.l2_proj = sp.csr_matrix(l2_proj)                               # :182
         if hierarchy is not None:
             self.hierarchy = [sp.csr_matrix(h) for h in hierarchy]
+
+    _FIRST_CALL = True
 
     def solve(self, levels=2, smoother="Jacobi", smooth_steps=1, max_iterations=100, error=1e-08,
               initial_guess=None, cycle="V", first_call=True, **kw):       # :184-186
