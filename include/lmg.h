@@ -629,6 +629,40 @@ int lmg_multi_dot(int64_t n, int k, const double *d_V, int64_t ldv, const double
 int lmg_multi_axpy(int64_t n, int k, int subtract, const double *d_V, int64_t ldv, const double *d_coef, double *d_w,
                    double *d_partials, double *d_norm2, void *stream);
 
+/* ---- conjugate gradients on a block of k right-hand sides (csrc/krylov.hip) ------------------------------------------------
+ * Blocks as in lmg_sell_sweep_block: X[i * k + j] = row i, column j, k = 2, 4 or 8 (LMG_ERR_ARG otherwise), base 16-byte
+ * aligned (LMG_ERR_ALIGN otherwise).  Per-column scalars are DEVICE arrays of k doubles; the mask holds 1.0 for a column
+ * that still iterates and 0.0 for one that is frozen (padding, converged).  No atomics, fixed geometry: nothing depends on
+ * n, k or a tune key.  n == 0: LMG_OK, nothing is touched.  Every argument error is returned before any HIP call.
+ *
+ *   lmg_block_dot           d_out[j] = sum_i X[i,j] * Y[i,j], the k columns in one pass (d_X == d_Y allowed).  Column j has
+ *                           the BITS of lmg_dot on a contiguous copy of column j: 1024 workgroups of 256 lanes, lane t of
+ *                           workgroup g owns rows 256 g + t + 262144 m, m = 0, 1, ..., one accumulator per lane and column,
+ *                           acc = acc + x * y in ascending rows; the workgroup's sum is a 64-lane butterfly, then its four
+ *                           waves in ascending order; the 1024 partials of a column: one per lane of a second launch,
+ *                           butterfly, then the 16 waves.  d_partials: lmg_block_dot_partials_count(n, k) doubles.
+ *   lmg_block_cg_step       alpha_j = rz_j / pAp_j, one division, 0 where mask_j == 0 or pAp_j == 0.  For the columns
+ *                           with mask_j != 0:  x = alpha p + x,  r = (-alpha) ap + r,  product and sum rounded on their own:
+ *                           the bits of lmg_axpby(alpha, p, 1, x) and lmg_axpby(-alpha, ap, 1, r).  A column with
+ *                           mask_j == 0 is not stored: its bytes of d_X and d_R stay as they are, whatever d_P and
+ *                           d_AP hold there (NaN included).
+ *                           d_rr[j] = sum_i r_ij^2 of d_R as it is afterwards, every column, the bits of lmg_block_dot(R, R).
+ *                           The small second launch that sums the partials also sets
+ *                           mask_j = (mask_j != 0 && rr_j > tol2_j) ? 1 : 0.
+ *                           LMG_ERR_ARG where d_X, d_R, d_P, d_AP are not four different arrays, or d_rr is one of the
+ *                           other scalar arrays.
+ *   lmg_block_cg_direction  beta_j = rz_new_j / rz_old_j;  p = z + beta p for the columns with mask_j != 0, the bits of
+ *                           lmg_axpby(1, z, beta, p) (beta_j == 0: p = z);  the others are not stored.  LMG_ERR_ARG for
+ *                           d_P == d_Z or d_rz_new == d_rz_old: the driver alternates between two arrays, so no launch
+ *                           writes a scalar that another workgroup of the same launch reads. */
+int64_t lmg_block_dot_partials_count(int64_t n, int k);
+int lmg_block_dot(int k, int64_t n, const double *d_X, const double *d_Y, double *d_partials, double *d_out, void *stream);
+int lmg_block_cg_step(int k, int64_t n, const double *d_rz, const double *d_pAp, const double *d_tol2, double *d_mask,
+                      const double *d_P, const double *d_AP, double *d_X, double *d_R, double *d_partials, double *d_rr,
+                      void *stream);
+int lmg_block_cg_direction(int k, int64_t n, const double *d_rz_new, const double *d_rz_old, const double *d_mask,
+                           const double *d_Z, double *d_P, void *stream);
+
 /* ---- coarsest level --------------------------------------------------------------
  * y = M x for a dense row-major n x m matrix: applies a pre-factored coarse operator
  * (M = A_L^-1 computed once at setup) in place of the per-cycle SuperLU

@@ -121,6 +121,22 @@ class BlockCycle:
         """One V(steps, steps), W or F cycle (the shapes of Hierarchy.cycle) with weighted Jacobi on levels[0].x / .b."""
         self._visit(0, cycle_children(shape), int(steps), float(omega))
 
+    def apply(self, src, dst, steps, omega, shape="V", use_graph=False):
+        """One cycle on the right-hand sides src (an (n, k) block) from a zero guess: the cycle as a preconditioner.  The
+        result is levels[0].x, which is returned; dst (None: no copy) receives a copy of it.  use_graph: the cycle itself
+        is the replay of captured()."""
+        fine = self.levels[0]
+        self.ops.copy(src.view(-1), fine.b.view(-1))
+        self.ops.zero(fine.x.view(-1))
+        if use_graph:
+            self.captured(steps, omega, shape).launch()
+        else:
+            self.cycle(steps, omega, shape)
+        out = self.levels[0].x
+        if dst is not None:
+            self.ops.copy(out.view(-1), dst.view(-1))
+        return out
+
     def residual_norms(self):
         """||b_j - A x_j||_2 of the nrhs columns on the fine level: one block residual, one read of k doubles."""
         bl = self.levels[0]

@@ -3,6 +3,11 @@
 // deterministic: a fixed grid, one partial per workgroup and column, a second small launch for the final sums, no
 // atomics.  A basis is a row-major block V[k][ldv], ldv >= n and even (every row 16-byte aligned); the elements
 // n .. ldv-1 of a row and the rows >= k are never touched.
+//
+// Second half: conjugate gradients on a block of K right-hand sides (krylov.py block_pcg), blocks X[i * K + j] as in
+// sell.hip's block sweeps.  K dot products in one pass with the element <-> lane map and the order of lmg_dot (vec.hip),
+// and the two vector updates of an iteration with their coefficients divided on the device from per-column scalars, a
+// per-column mask that freezes a converged column, and |r|^2 folded into the first of them.
 #include "lmg_common.hpp"
 
 namespace {
@@ -138,6 +143,168 @@ int basis_check(int64_t n, int k, const double *V, int64_t ldv, const double *w)
     return LMG_OK;
 }
 
+// ---- conjugate gradients on a block of K columns -------------------------------------------------------------------------
+// One row <-> lane map for the three kernels, dot_kernel's (vec.hip): kKryGrid workgroups of 256 lanes, lane t of workgroup
+// g owns the rows g * 256 + t, + 262144, ...; a lane reads the K values of its row of a block as K / 2 16-byte loads.
+constexpr int64_t kBcgStride = (int64_t)kKryGrid * kLmgBlock;
+
+template <int K>
+__device__ __forceinline__ void bcg_load_row(const double *B, int64_t row, double (&v)[K])
+{
+    const d2 *b2 = reinterpret_cast<const d2 *>(B + row * K);
+#pragma unroll
+    for (int h = 0; h < K / 2; ++h) {
+        const d2 t = b2[h];
+        v[2 * h] = t.x;
+        v[2 * h + 1] = t.y;
+    }
+}
+
+// Row `row` of B <- v for the columns with on[j] (wave-uniform): a pair of columns as one 16-byte store where both are
+// on, 8 bytes where one is, nothing where neither is -- the bytes of a column that is off are never written.
+template <int K>
+__device__ __forceinline__ void bcg_store_row(double *B, int64_t row, const double (&v)[K], const bool (&on)[K])
+{
+    double *b = B + row * K;
+#pragma unroll
+    for (int h = 0; h < K / 2; ++h) {
+        if (on[2 * h] && on[2 * h + 1]) {
+            d2 t;
+            t.x = v[2 * h];
+            t.y = v[2 * h + 1];
+            reinterpret_cast<d2 *>(b)[h] = t;
+        } else if (on[2 * h]) {
+            b[2 * h] = v[2 * h];
+        } else if (on[2 * h + 1]) {
+            b[2 * h + 1] = v[2 * h + 1];
+        }
+    }
+}
+
+// partial[j * kKryGrid + blockIdx.x] = this workgroup's share of column j's sum, in lmg_block_sum<256>'s order (one LDS
+// row per column: no reuse hazard between the K reductions)
+template <int K>
+__device__ __forceinline__ void bcg_write_partials(const double (&acc)[K], double (*s_red)[kLmgBlock / LMG_WAVE], double *partial)
+{
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        const double tot = lmg_block_sum<kLmgBlock>(acc[j], s_red[j]);
+        if (threadIdx.x == 0) partial[(int64_t)j * kKryGrid + blockIdx.x] = tot;
+    }
+}
+
+// Column j: acc = acc + x * y over the lane's rows in ascending order -- dot_kernel's sum on a contiguous copy of column j.
+template <int K>
+__global__ void __launch_bounds__(kLmgBlock) block_dot_kernel(int64_t n, const double *X, const double *Y, double *partial)
+{
+    __shared__ double s_red[K][kLmgBlock / LMG_WAVE];
+    double acc[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) acc[j] = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * kLmgBlock + threadIdx.x; i < n; i += kBcgStride) {
+        double x[K], y[K];
+        bcg_load_row<K>(X, i, x);
+        bcg_load_row<K>(Y, i, y);
+#pragma unroll
+        for (int j = 0; j < K; ++j) acc[j] += x[j] * y[j];
+    }
+    bcg_write_partials<K>(acc, s_red, partial);
+}
+
+// out[j] = the kKryGrid partials of column j = blockIdx.x in dot_final_kernel's order (lmg_block_sum<1024>).  MASK, the
+// launch behind block_cg_step_kernel: a column stays on only while its |r|^2 is above its threshold.  Column j's scalars
+// are read and written by workgroup j alone.
+template <bool MASK>
+__global__ void __launch_bounds__(kKryGrid) block_final_kernel(const double *partial, double *out, const double *tol2, double *mask)
+{
+    __shared__ double s_red[kKryGrid / LMG_WAVE];
+    const double tot = lmg_block_sum<kKryGrid>(partial[(int64_t)blockIdx.x * kKryGrid + threadIdx.x], s_red);
+    if (threadIdx.x == 0) {
+        out[blockIdx.x] = tot;
+        if (MASK) mask[blockIdx.x] = (mask[blockIdx.x] != 0.0 && tot > tol2[blockIdx.x]) ? 1.0 : 0.0;
+    }
+}
+
+// alpha_j = rz_j / pAp_j (0 where the column is off or pAp_j == 0: every lane of every workgroup does the same division),
+// x = alpha p + x and r = (-alpha) ap + r with product and sum rounded on their own -- axpby_kernel's bits with beta = 1 --
+// for the columns that are on; a column that is off is neither computed nor stored.  Every column, on or off, adds the
+// squares of its r as it now stands to its partial: block_dot_kernel's sum of (R, R) after the update.
+template <int K>
+__global__ void __launch_bounds__(kLmgBlock) block_cg_step_kernel(int64_t n, const double *rz, const double *pAp, const double *mask,
+                                                                  const double *P, const double *AP, double *X, double *R,
+                                                                  double *partial)
+{
+    __shared__ double s_red[K][kLmgBlock / LMG_WAVE];
+    double alpha[K], acc[K];
+    bool on[K], any = false;
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        on[j] = mask[j] != 0.0;
+        const double d = pAp[j];
+        alpha[j] = (on[j] && d != 0.0) ? rz[j] / d : 0.0;
+        any = any || on[j];
+        acc[j] = 0.0;
+    }
+    for (int64_t i = (int64_t)blockIdx.x * kLmgBlock + threadIdx.x; i < n; i += kBcgStride) {
+        double r[K];
+        bcg_load_row<K>(R, i, r);
+        if (any) {
+            double p[K], ap[K], x[K];
+            bcg_load_row<K>(P, i, p);
+            bcg_load_row<K>(AP, i, ap);
+            bcg_load_row<K>(X, i, x);
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                if (on[j]) {
+                    x[j] = alpha[j] * p[j] + x[j];
+                    r[j] = (-alpha[j]) * ap[j] + r[j];
+                }
+            }
+            bcg_store_row<K>(X, i, x, on);
+            bcg_store_row<K>(R, i, r, on);
+        }
+#pragma unroll
+        for (int j = 0; j < K; ++j) acc[j] += r[j] * r[j];
+    }
+    bcg_write_partials<K>(acc, s_red, partial);
+}
+
+// beta_j = rz_new_j / rz_old_j, p = z + beta p for the columns that are on -- axpby_kernel's bits with alpha = 1, its
+// beta == 0 case (p = z, p is not read) included; a column that is off is neither computed nor stored.
+template <int K>
+__global__ void __launch_bounds__(kLmgBlock) block_cg_direction_kernel(int64_t n, const double *rz_new, const double *rz_old,
+                                                                       const double *mask, const double *Z, double *P)
+{
+    double beta[K];
+    bool on[K], any = false;
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        on[j] = mask[j] != 0.0;
+        beta[j] = on[j] ? rz_new[j] / rz_old[j] : 0.0;
+        any = any || on[j];
+    }
+    if (!any) return;
+    for (int64_t i = (int64_t)blockIdx.x * kLmgBlock + threadIdx.x; i < n; i += kBcgStride) {
+        double z[K], p[K];
+        bcg_load_row<K>(Z, i, z);
+        bcg_load_row<K>(P, i, p);
+#pragma unroll
+        for (int j = 0; j < K; ++j)
+            if (on[j]) p[j] = (beta[j] == 0.0) ? z[j] : z[j] + beta[j] * p[j];
+        bcg_store_row<K>(P, i, p, on);
+    }
+}
+
+inline bool bcg_width_ok(int k) { return k == 2 || k == 4 || k == 8; }
+
+// f(std::integral_constant<int, K>) for the block width k (checked by the caller)
+template <typename F>
+int bcg_with_width(int k, F &&f)
+{
+    return k == 2 ? f(std::integral_constant<int, 2>{}) : k == 4 ? f(std::integral_constant<int, 4>{})
+                                                                 : f(std::integral_constant<int, 8>{});
+}
+
 }  // namespace
 
 extern "C" {
@@ -197,6 +364,72 @@ int lmg_multi_axpy(int64_t n, int k, int subtract, const double *d_V, int64_t ld
         LMG_CHECK_LAUNCH();
     }
     return LMG_OK;
+}
+
+int64_t lmg_block_dot_partials_count(int64_t n, int k)
+{
+    (void)n;                                   // fixed geometry: kKryGrid partials per column for every n
+    return (int64_t)kKryGrid * (k > 1 ? k : 1);
+}
+
+int lmg_block_dot(int k, int64_t n, const double *d_X, const double *d_Y, double *d_partials, double *d_out, void *stream)
+{
+    if (!bcg_width_ok(k) || n < 0) return LMG_ERR_ARG;
+    if (n == 0) return LMG_OK;
+    if (!d_X || !d_Y || !d_partials || !d_out) return LMG_ERR_ARG;
+    if (!lmg_aligned16(d_X) || !lmg_aligned16(d_Y)) return LMG_ERR_ALIGN;
+    hipStream_t st = lmg_stream(stream);
+    const int rc = bcg_with_width(k, [&](auto kc) -> int {
+        hipLaunchKernelGGL(block_dot_kernel<LMG_CT(kc)>, dim3(kKryGrid), dim3(kLmgBlock), 0, st, n, d_X, d_Y, d_partials);
+        LMG_CHECK_LAUNCH();
+        return LMG_OK;
+    });
+    if (rc != LMG_OK) return rc;
+    hipLaunchKernelGGL(block_final_kernel<false>, dim3((unsigned)k), dim3(kKryGrid), 0, st, d_partials, d_out,
+                       (const double *)nullptr, (double *)nullptr);
+    LMG_CHECK_LAUNCH();
+    return LMG_OK;
+}
+
+int lmg_block_cg_step(int k, int64_t n, const double *d_rz, const double *d_pAp, const double *d_tol2, double *d_mask,
+                      const double *d_P, const double *d_AP, double *d_X, double *d_R, double *d_partials, double *d_rr,
+                      void *stream)
+{
+    if (!bcg_width_ok(k) || n < 0) return LMG_ERR_ARG;
+    if (n == 0) return LMG_OK;
+    if (!d_rz || !d_pAp || !d_tol2 || !d_mask || !d_P || !d_AP || !d_X || !d_R || !d_partials || !d_rr) return LMG_ERR_ARG;
+    // in / out blocks of one update, and the two blocks that are written, must be different arrays
+    if (d_X == d_P || d_R == d_AP || d_X == d_R || d_X == d_AP || d_R == d_P) return LMG_ERR_ARG;
+    // the scalars the update reads are not the ones the launch behind it writes (d_mask is: by then every workgroup has read it)
+    if (d_rr == d_rz || d_rr == d_pAp || d_rr == d_tol2 || d_rr == d_mask) return LMG_ERR_ARG;
+    if (!lmg_aligned16(d_P) || !lmg_aligned16(d_AP) || !lmg_aligned16(d_X) || !lmg_aligned16(d_R)) return LMG_ERR_ALIGN;
+    hipStream_t st = lmg_stream(stream);
+    const int rc = bcg_with_width(k, [&](auto kc) -> int {
+        hipLaunchKernelGGL(block_cg_step_kernel<LMG_CT(kc)>, dim3(kKryGrid), dim3(kLmgBlock), 0, st, n, d_rz, d_pAp,
+                           (const double *)d_mask, d_P, d_AP, d_X, d_R, d_partials);
+        LMG_CHECK_LAUNCH();
+        return LMG_OK;
+    });
+    if (rc != LMG_OK) return rc;
+    hipLaunchKernelGGL(block_final_kernel<true>, dim3((unsigned)k), dim3(kKryGrid), 0, st, d_partials, d_rr, d_tol2, d_mask);
+    LMG_CHECK_LAUNCH();
+    return LMG_OK;
+}
+
+int lmg_block_cg_direction(int k, int64_t n, const double *d_rz_new, const double *d_rz_old, const double *d_mask,
+                           const double *d_Z, double *d_P, void *stream)
+{
+    if (!bcg_width_ok(k) || n < 0) return LMG_ERR_ARG;
+    if (n == 0) return LMG_OK;
+    if (!d_rz_new || !d_rz_old || !d_mask || !d_Z || !d_P) return LMG_ERR_ARG;
+    if (d_rz_new == d_rz_old || d_P == d_Z) return LMG_ERR_ARG;
+    if (!lmg_aligned16(d_Z) || !lmg_aligned16(d_P)) return LMG_ERR_ALIGN;
+    return bcg_with_width(k, [&](auto kc) -> int {
+        hipLaunchKernelGGL(block_cg_direction_kernel<LMG_CT(kc)>, dim3(kKryGrid), dim3(kLmgBlock), 0, lmg_stream(stream), n,
+                           d_rz_new, d_rz_old, d_mask, d_Z, d_P);
+        LMG_CHECK_LAUNCH();
+        return LMG_OK;
+    });
 }
 
 }  // extern "C"

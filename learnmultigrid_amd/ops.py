@@ -804,6 +804,57 @@ def block_spmv(S, X, Y, alpha=1.0, beta=0.0):
     _block_sweep(2, S, X, None, Y, alpha, beta, None, None)
 
 
+def block_dot_partials_count(n, k):
+    return int(_lib.lib().lmg_block_dot_partials_count(int(n), int(k)))
+
+
+def _block_scalars_ok(k, *scalars):
+    """Per-column scalars: contiguous float64 device tensors of at least k elements."""
+    _vec_ok(*scalars)
+    if any(t.numel() < k for t in scalars):
+        raise ValueError("a per-column scalar array is shorter than the %d columns of the block" % k)
+
+
+def _block_same_shape(name, *blocks):
+    k = _block_ok(*blocks)
+    if any(t.shape != blocks[0].shape for t in blocks):
+        raise ValueError("%s: blocks of different shapes %s" % (name, [tuple(t.shape) for t in blocks]))
+    return k
+
+
+def block_dot(X, Y, partials, out):
+    """out[j] = X[:, j] . Y[:, j] for the k columns in one pass; column j has the bits of dot() on a contiguous column j."""
+    k = _block_same_shape("block_dot", X, Y)
+    _block_scalars_ok(k, out)
+    _vec_ok(partials)
+    if partials.numel() < block_dot_partials_count(X.shape[0], k):
+        raise ValueError("block_dot: partials too short for %d columns" % k)
+    check(_lib.lib().lmg_block_dot(k, X.shape[0], _p(X), _p(Y), _p(partials), _p(out), _s(X)), "lmg_block_dot")
+
+
+def block_cg_step(rz, pAp, tol2, mask, P, AP, X, R, partials, rr):
+    """The fused update of a CG iteration on a block, all scalars on the device: alpha_j = rz[j] / pAp[j] (0 where mask[j] or
+    pAp[j] is 0), X += alpha P and R -= alpha AP for the columns with mask[j] != 0 -- the bits of axpby(alpha, p, 1, x) and
+    axpby(-alpha, ap, 1, r); the other columns of X and R are not stored --, rr[j] = |R[:, j]|^2 with block_dot's bits, and
+    mask[j] = 1.0 if mask[j] != 0 and rr[j] > tol2[j] else 0.0."""
+    k = _block_same_shape("block_cg_step", P, AP, X, R)
+    _block_scalars_ok(k, rz, pAp, tol2, mask, rr)
+    _vec_ok(partials)
+    if partials.numel() < block_dot_partials_count(X.shape[0], k):
+        raise ValueError("block_cg_step: partials too short for %d columns" % k)
+    check(_lib.lib().lmg_block_cg_step(k, X.shape[0], _p(rz), _p(pAp), _p(tol2), _p(mask), _p(P), _p(AP), _p(X), _p(R),
+                                       _p(partials), _p(rr), _s(X)), "lmg_block_cg_step")
+
+
+def block_cg_direction(rz_new, rz_old, mask, Z, P):
+    """P = Z + beta P with beta_j = rz_new[j] / rz_old[j] for the columns with mask[j] != 0, the bits of axpby(1, z, beta, p);
+    the other columns of P are not stored.  rz_new and rz_old are two arrays: the caller alternates between them."""
+    k = _block_same_shape("block_cg_direction", Z, P)
+    _block_scalars_ok(k, rz_new, rz_old, mask)
+    check(_lib.lib().lmg_block_cg_direction(k, P.shape[0], _p(rz_new), _p(rz_old), _p(mask), _p(Z), _p(P), _s(P)),
+          "lmg_block_cg_direction")
+
+
 def dense_gemv_block(M, X, Y):
     """Y = M X for a dense (n, m) matrix and blocks X (m, k), Y (n, k): M is read once for the k columns."""
     _vec_ok(M)

@@ -36,6 +36,13 @@ class CG(IterativeSolver):
         super().__init__(matrix, rhs, **kw)
         self._log("Selected CG")
         self.label = "CG"
+        self._block_cycles = {}            # solve_many: {"H": the preconditioner, k: its BlockCycle of width k}
+        self._block_twin = None            # solve_many: the operator's fp64 sliced-ELL twin
+
+    def _invalidate(self):
+        super()._invalidate()
+        self._block_cycles = {}
+        self._block_twin = None
 
     @on_device
     def solve(self, max_iterations=1000, error=1e-08, initial_guess=None, *, preconditioner=None,
@@ -95,3 +102,67 @@ class CG(IterativeSolver):
         self.solution = self._column(x)
         self.residual_vector = self._column(r)
         self.track_res = np.array(track, dtype=float).reshape(-1, 1)
+
+    # -- several right-hand sides at once (no counterpart in the reference) ----------------------
+    @on_device
+    def solve_many(self, rhs, max_iterations=1000, error=1e-08, initial_guess=None, *, preconditioner=None,
+                   precond_steps=2, precond_omega=0.8, precond_cycle_shape="V", use_graph=False):
+        """Solve A X = rhs for the m >= 1 columns of rhs (n, m) by (multigrid-preconditioned) conjugate gradients on
+        blocks of columns (krylov.block_pcg): the operator and, with preconditioner=Hierarchy, every matrix of the
+        hierarchy are read once per iteration for up to 8 columns, and alpha, beta and the convergence test of every column
+        stay on the device -- one device-to-host read of 2 k doubles per iteration.  Every column runs its own CG recurrence;
+        a column whose recurrence norm is <= error is frozen: its solution is, bit for bit, the iterate of the iteration at
+        which it passed, while the other columns of its chunk go on.
+        Columns are padded with zero columns to a width of 2, 4 or 8 and worked through in chunks of 8, like
+        Multigrid.solve_many.  Returns (X, track): X (n, m); track row 0 holds the true ||b_j - A x_j||_2 of the initial
+        guess, every further row one iteration's recurrence norm sqrt(r_j . r_j) -- NaN after the iteration at which the
+        column passed, and in rows that its chunk did not reach because another chunk needed more.
+        self.iterations_many[j]: the iterations column j ran (0: it started at or below error).
+        The preconditioner is one precond_cycle_shape ("V" | "W") cycle of block.BlockCycle from a zero guess, which smooths
+        with weighted Jacobi only (precond_steps sweeps before and after, damping precond_omega): no other smoother can
+        be asked for here.  A hierarchy with cycle_values="f32" is refused by BlockCycle.  use_graph replays the cycle
+        from a captured hipGraph; everything else of an iteration is launched as it is.  solve() is not touched by any of
+        this."""
+        if precond_cycle_shape not in ("V", "W"):
+            raise ValueError("precond_cycle_shape must be 'V' or 'W' (CG needs a symmetric preconditioner), got %r"
+                             % (precond_cycle_shape,))
+        B = np.asarray(rhs, dtype=np.float64)
+        if B.ndim != 2 or B.shape[0] != self.dim or B.shape[1] < 1:
+            raise ValueError("rhs must be (n, m) with n = %d and m >= 1, got %s" % (self.dim, B.shape))
+        X0 = None
+        if initial_guess is not None:
+            X0 = np.asarray(initial_guess, dtype=np.float64)
+            if X0.shape != B.shape:
+                raise ValueError("initial_guess must have the shape of rhs %s, got %s" % (B.shape, X0.shape))
+        from .. import krylov
+        from ..block import BlockCycle, block_width
+        H = preconditioner
+        dev = self._device
+        A = self._device_matrix()
+        A.pack()
+        if self._block_twin is None:
+            self._block_twin = ops.block_twin(A)
+        if self._block_cycles.get("H") is not H:                   # (one hierarchy at a time: a new one drops the old blocks)
+            self._block_cycles = {"H": H}
+
+        def block_cycle(mc):
+            if H is None:
+                return None
+            k = block_width(mc, ops.BLOCK_WIDTHS)
+            bc = self._block_cycles.get(k)
+            if bc is None:
+                bc = self._block_cycles[k] = BlockCycle(H, mc)
+            bc.use_columns(mc)
+            return bc
+
+        side = None if H is None else H.stream                     # (a cycle is captured on the hierarchy's stream)
+        if side is not None:
+            side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):                              # (None: the current stream)
+            X, track, its = krylov.block_pcg_columns(ops, self._block_twin, block_cycle, B, X0, dev,
+                                                     max_iterations=int(max_iterations), error=error, steps=precond_steps,
+                                                     omega=precond_omega, shape=precond_cycle_shape, use_graph=bool(use_graph))
+        if side is not None:
+            torch.cuda.current_stream(dev).wait_stream(side)
+        self.iterations_many = its
+        return X, track
