@@ -663,6 +663,43 @@ int lmg_block_cg_step(int k, int64_t n, const double *d_rz, const double *d_pAp,
 int lmg_block_cg_direction(int k, int64_t n, const double *d_rz_new, const double *d_rz_old, const double *d_mask,
                            const double *d_Z, double *d_P, void *stream);
 
+/* ---- flexible GMRES on a block of k right-hand sides (csrc/krylov.hip) -----------------------------------------------------
+ * The Gram-Schmidt passes above on blocks: X[i * k + j] = row i, column j, k = 2, 4 or 8 (LMG_ERR_ARG otherwise), base
+ * 16-byte aligned (LMG_ERR_ALIGN otherwise).  A block basis is nb such blocks, block i at d_V + i * ldb doubles, ldb >= n * k
+ * and even (LMG_ERR_ARG otherwise); the doubles n * k .. ldb-1 of a block, and the blocks >= nb, are never read or written.
+ * nb and every count are 0 .. lmg_krylov_max_vectors() (LMG_ERR_ARG beyond).  Null pointers: LMG_ERR_ARG.  No atomics, fixed
+ * geometry.  nb == 0 and n == 0 are LMG_OK as for lmg_multi_*: d_out resp. d_norm2 are zeroed for n == 0.
+ *
+ *   lmg_block_multi_dot     d_out[i * k + j] = V_i[:, j] . W[:, j], i < nb, j < k, in one pass, with the BITS lmg_multi_dot
+ *                           returns for row i when column j of every block and of W is copied into a contiguous basis:
+ *                           1024 workgroups of 256 lanes, lane t of workgroup g owns the row pairs 256 g + t + 262144 m,
+ *                           one accumulator per (i, j) and lane, row 2 p before row 2 p + 1, the last row of an odd n to
+ *                           lane 0 of workgroup 0 after its pairs; then the sums of lmg_multi_dot (butterfly, four waves,
+ *                           second launch over the 1024 partials).  A row pair of a block is 2 k contiguous doubles: k
+ *                           16-byte loads per lane and block.  The blocks go through the registers 32 / k at a time
+ *                           (16, 8, 4 for k = 2, 4, 8): W is read ceil(nb k / 32) times, every V_i once.
+ *                           d_partials: lmg_block_multi_partials_count(n, k, nb) doubles.
+ *   lmg_block_multi_axpy    column j:  w = w - coef[i * k + j] * V_i[:, j]  for i = 0 .. h_counts[j] - 1 ascending
+ *                           (subtract == 0: +), every product and every sum rounded on its own: the bits of lmg_multi_axpy
+ *                           with k = h_counts[j] on contiguous copies.  h_counts is a HOST array of k ints, read before the
+ *                           call returns; d_coef is a DEVICE array in the layout of lmg_block_multi_dot's d_out, of
+ *                           max_j h_counts[j] * k doubles.  A column with h_counts[j] == 0 is neither computed nor stored:
+ *                           its bytes of d_W stay as they are (a pair of columns is one 16-byte store where both are on,
+ *                           8 bytes where one is).  d_norm2 != NULL: d_norm2[j] = |W[:, j]|^2 as W stands afterwards, for
+ *                           every column whatever its count, the bits of lmg_multi_axpy's folded norm on that column
+ *                           (d_partials needed: lmg_block_multi_partials_count(n, k, 1) doubles); NULL: no reduction.
+ *                           W is read and written once, V_0 .. V_(max count - 1) once.  d_W must not overlap the basis.
+ *   lmg_block_scale         W[:, j] = h_scale[j] * W[:, j], the bits of lmg_axpby(h_scale[j], w, 0, w) on the column.
+ *                           h_scale is a HOST array of k doubles, read before the call returns.  h_scale[j] == 0.0 stores
+ *                           +0.0 whatever the column held, NaN and Inf included: how a column that has left a cycle is
+ *                           emptied. */
+int64_t lmg_block_multi_partials_count(int64_t n, int k, int nb);
+int lmg_block_multi_dot(int k, int64_t n, int nb, const double *d_V, int64_t ldb, const double *d_W, double *d_partials,
+                        double *d_out, void *stream);
+int lmg_block_multi_axpy(int k, int64_t n, const int *h_counts, int subtract, const double *d_V, int64_t ldb, const double *d_coef,
+                         double *d_W, double *d_partials, double *d_norm2, void *stream);
+int lmg_block_scale(int k, int64_t n, const double *h_scale, double *d_W, void *stream);
+
 /* ---- coarsest level --------------------------------------------------------------
  * y = M x for a dense row-major n x m matrix: applies a pre-factored coarse operator
  * (M = A_L^-1 computed once at setup) in place of the per-cycle SuperLU

@@ -8,6 +8,10 @@
 // sell.hip's block sweeps.  K dot products in one pass with the element <-> lane map and the order of lmg_dot (vec.hip),
 // and the two vector updates of an iteration with their coefficients divided on the device from per-column scalars, a
 // per-column mask that freezes a converged column, and |r|^2 folded into the first of them.
+//
+// Third part: flexible GMRES on a block of K right-hand sides (krylov.py block_fgmres): the Gram-Schmidt kernels of the first
+// half on a basis of interleaved blocks, column j with the bits of the single-vector kernels on a contiguous copy of that
+// column, a count of basis vectors per column, and a per-column scaling that empties a column with a factor of 0.
 #include "lmg_common.hpp"
 
 namespace {
@@ -305,6 +309,206 @@ int bcg_with_width(int k, F &&f)
                                                                  : f(std::integral_constant<int, 8>{});
 }
 
+// ---- flexible GMRES on a block of K columns ------------------------------------------------------------------------------
+// The Gram-Schmidt kernels of the first half on the interleaved layout: a block basis is nb blocks, block i at V + i * ldb,
+// and column j of it does what multi_dot_kernel / multi_axpy_kernel do on a contiguous copy of that column.  The map is
+// theirs: lane t of workgroup g owns the ROW pairs g * 256 + t, + 262144, ... -- the 2 K contiguous doubles of a row pair
+// are K 16-byte loads --, one accumulator per (block, column) and lane, row 2 p before row 2 p + 1, the last row of an odd
+// n to lane 0 of workgroup 0 after its pairs.
+constexpr int kBgmDotAcc = 32;          // accumulators of one lane in block_multi_dot_kernel: blocks per chunk = 32 / K
+constexpr int kBgmAxpyCols = 16;        // columns of basis blocks one lane keeps in flight in block_multi_axpy_kernel: 16 / K blocks
+
+struct BgmCounts {
+    int c[8];
+};
+struct BgmScales {
+    double s[8];
+};
+
+// partial[((i0 + c) * K + j) * kKryGrid + blockIdx.x] = this workgroup's share of V_(i0+c)[:, j] . W[:, j], i0 = blockIdx.y
+// * C: W's row pair stays in registers over the C blocks of the chunk.
+template <int K>
+__global__ void __launch_bounds__(kLmgBlock) block_multi_dot_kernel(int64_t n, int nb, const double *V, int64_t ldb, const double *W,
+                                                                    double *partial)
+{
+    constexpr int C = kBgmDotAcc / K;
+    __shared__ double s_red[C * K][kLmgBlock / LMG_WAVE];
+    const int i0 = (int)blockIdx.y * C;
+    const int nc = min(nb - i0, C);
+    const double *Vc = V + (int64_t)i0 * ldb;
+    double acc[C][K];
+#pragma unroll
+    for (int c = 0; c < C; ++c)
+#pragma unroll
+        for (int j = 0; j < K; ++j) acc[c][j] = 0.0;
+    const int64_t n2 = n >> 1;
+    for (int64_t p = (int64_t)blockIdx.x * kLmgBlock + threadIdx.x; p < n2; p += kBcgStride) {
+        double w0[K], w1[K], v0[C][K], v1[C][K];
+        bcg_load_row<K>(W, 2 * p, w0);
+        bcg_load_row<K>(W, 2 * p + 1, w1);
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            if (c < nc) {
+                bcg_load_row<K>(Vc + (int64_t)c * ldb, 2 * p, v0[c]);
+                bcg_load_row<K>(Vc + (int64_t)c * ldb, 2 * p + 1, v1[c]);
+            } else {
+#pragma unroll
+                for (int j = 0; j < K; ++j) v0[c][j] = v1[c][j] = 0.0;
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            if (c < nc) {
+#pragma unroll
+                for (int j = 0; j < K; ++j) {
+                    acc[c][j] += v0[c][j] * w0[j];
+                    acc[c][j] += v1[c][j] * w1[j];
+                }
+            }
+        }
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+        double w[K];
+        bcg_load_row<K>(W, n - 1, w);
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            if (c < nc) {
+                double v[K];
+                bcg_load_row<K>(Vc + (int64_t)c * ldb, n - 1, v);
+#pragma unroll
+                for (int j = 0; j < K; ++j) acc[c][j] += v[j] * w[j];
+            }
+        }
+    }
+    const int lane = threadIdx.x & (LMG_WAVE - 1), wave = threadIdx.x / LMG_WAVE;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        if (c < nc) {
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                const double s = lmg_wave_sum(acc[c][j]);
+                if (lane == 0) s_red[c * K + j][wave] = s;
+            }
+        }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < nc * K) {
+        double tot = 0.0;
+#pragma unroll
+        for (int wv = 0; wv < kLmgBlock / LMG_WAVE; ++wv) tot += s_red[threadIdx.x][wv];
+        partial[((int64_t)i0 * K + (int)threadIdx.x) * kKryGrid + blockIdx.x] = tot;
+    }
+}
+
+// Column j: w = w + (sign * coef[i * K + j]) * V_i[:, j] for i = 0 .. cnt.c[j] - 1 ascending, every product and every sum
+// rounded on its own -- multi_axpy_kernel's loop with k = cnt.c[j] --, stored with bcg_store_row: a column with a count of
+// 0 is neither computed nor stored.  maxc = the largest count: the loop bound, the per-column test is wave-uniform.  NORM:
+// partial[j * kKryGrid + blockIdx.x] = this workgroup's share of |W[:, j]|^2 as it now stands, every column.
+template <int K, bool NORM>
+__global__ void __launch_bounds__(kLmgBlock) block_multi_axpy_kernel(int64_t n, BgmCounts cnt, int maxc, double sign, const double *V,
+                                                                     int64_t ldb, const double *coef, double *W, double *partial)
+{
+    constexpr int C = kBgmAxpyCols / K;
+    __shared__ double s_coef[kKryMaxVectors * K];
+    __shared__ double s_red[K][kLmgBlock / LMG_WAVE];
+    for (int t = threadIdx.x; t < maxc * K; t += kLmgBlock) s_coef[t] = sign * coef[t];
+    __syncthreads();
+    bool on[K];
+    double acc[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        on[j] = cnt.c[j] > 0;
+        acc[j] = 0.0;
+    }
+    const int64_t n2 = n >> 1;
+    for (int64_t p = (int64_t)blockIdx.x * kLmgBlock + threadIdx.x; p < n2; p += kBcgStride) {
+        double w0[K], w1[K];
+        bcg_load_row<K>(W, 2 * p, w0);
+        bcg_load_row<K>(W, 2 * p + 1, w1);
+        for (int i0 = 0; i0 < maxc; i0 += C) {
+            const int nc = min(maxc - i0, C);
+            const double *Vc = V + (int64_t)i0 * ldb;
+            double v0[C][K], v1[C][K];
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                if (c < nc) {
+                    bcg_load_row<K>(Vc + (int64_t)c * ldb, 2 * p, v0[c]);
+                    bcg_load_row<K>(Vc + (int64_t)c * ldb, 2 * p + 1, v1[c]);
+                } else {
+#pragma unroll
+                    for (int j = 0; j < K; ++j) v0[c][j] = v1[c][j] = 0.0;
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                if (c < nc) {
+#pragma unroll
+                    for (int j = 0; j < K; ++j) {
+                        if (i0 + c < cnt.c[j]) {
+                            const double cj = s_coef[(i0 + c) * K + j];
+                            w0[j] = w0[j] + cj * v0[c][j];
+                            w1[j] = w1[j] + cj * v1[c][j];
+                        }
+                    }
+                }
+            }
+        }
+        bcg_store_row<K>(W, 2 * p, w0, on);
+        bcg_store_row<K>(W, 2 * p + 1, w1, on);
+        if (NORM) {
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                acc[j] += w0[j] * w0[j];
+                acc[j] += w1[j] * w1[j];
+            }
+        }
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+        double w[K];
+        bcg_load_row<K>(W, n - 1, w);
+        for (int i = 0; i < maxc; ++i) {
+            double v[K];
+            bcg_load_row<K>(V + (int64_t)i * ldb, n - 1, v);
+#pragma unroll
+            for (int j = 0; j < K; ++j)
+                if (i < cnt.c[j]) w[j] = w[j] + s_coef[i * K + j] * v[j];
+        }
+        bcg_store_row<K>(W, n - 1, w, on);
+        if (NORM) {
+#pragma unroll
+            for (int j = 0; j < K; ++j) acc[j] += w[j] * w[j];
+        }
+    }
+    if (NORM) bcg_write_partials<K>(acc, s_red, partial);
+}
+
+// W[:, j] = sc.s[j] * W[:, j], one product per element (axpby_kernel with beta == 0); a scale of 0 stores +0.0 whatever
+// the element held.
+template <int K>
+__global__ void __launch_bounds__(kLmgBlock) block_scale_kernel(int64_t n, BgmScales sc, double *W)
+{
+    const int64_t stride = (int64_t)gridDim.x * kLmgBlock;
+    bool all[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) all[j] = true;
+    for (int64_t i = (int64_t)blockIdx.x * kLmgBlock + threadIdx.x; i < n; i += stride) {
+        double w[K];
+        bcg_load_row<K>(W, i, w);
+#pragma unroll
+        for (int j = 0; j < K; ++j) w[j] = (sc.s[j] == 0.0) ? 0.0 : sc.s[j] * w[j];
+        bcg_store_row<K>(W, i, w, all);
+    }
+}
+
+// what the two Gram-Schmidt entry points ask of a block basis of nb blocks and its block W
+int block_basis_check(int k, int64_t n, int nb, const double *V, int64_t ldb, const double *W)
+{
+    if (nb > 0 && (!V || ldb < n * k || (ldb & 1))) return LMG_ERR_ARG;
+    if (!W) return LMG_ERR_ARG;
+    if ((nb > 0 && !lmg_aligned16(V)) || !lmg_aligned16(W)) return LMG_ERR_ALIGN;
+    return LMG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -427,6 +631,93 @@ int lmg_block_cg_direction(int k, int64_t n, const double *d_rz_new, const doubl
     return bcg_with_width(k, [&](auto kc) -> int {
         hipLaunchKernelGGL(block_cg_direction_kernel<LMG_CT(kc)>, dim3(kKryGrid), dim3(kLmgBlock), 0, lmg_stream(stream), n,
                            d_rz_new, d_rz_old, d_mask, d_Z, d_P);
+        LMG_CHECK_LAUNCH();
+        return LMG_OK;
+    });
+}
+
+int64_t lmg_block_multi_partials_count(int64_t n, int k, int nb)
+{
+    (void)n;                                   // fixed geometry: kKryGrid partials per block and column for every n
+    return (int64_t)kKryGrid * (k > 1 ? k : 1) * (nb > 1 ? nb : 1);
+}
+
+int lmg_block_multi_dot(int k, int64_t n, int nb, const double *d_V, int64_t ldb, const double *d_W, double *d_partials,
+                        double *d_out, void *stream)
+{
+    if (!bcg_width_ok(k) || n < 0 || nb < 0 || nb > kKryMaxVectors) return LMG_ERR_ARG;
+    if (nb == 0) return LMG_OK;
+    if (!d_partials || !d_out) return LMG_ERR_ARG;
+    hipStream_t st = lmg_stream(stream);
+    if (n == 0) {
+        if (hipMemsetAsync(d_out, 0, (size_t)nb * k * sizeof(double), st) != hipSuccess) return LMG_ERR_LAUNCH;
+        return LMG_OK;
+    }
+    const int bad = block_basis_check(k, n, nb, d_V, ldb, d_W);
+    if (bad) return bad;
+    const int rc = bcg_with_width(k, [&](auto kc) -> int {
+        constexpr int C = kBgmDotAcc / LMG_CT(kc);
+        hipLaunchKernelGGL(block_multi_dot_kernel<LMG_CT(kc)>, dim3(kKryGrid, (unsigned)((nb + C - 1) / C)), dim3(kLmgBlock), 0, st,
+                           n, nb, d_V, ldb, d_W, d_partials);
+        LMG_CHECK_LAUNCH();
+        return LMG_OK;
+    });
+    if (rc != LMG_OK) return rc;
+    hipLaunchKernelGGL(multi_final_kernel, dim3((unsigned)(nb * k)), dim3(kKryGrid), 0, st, d_partials, d_out);
+    LMG_CHECK_LAUNCH();
+    return LMG_OK;
+}
+
+int lmg_block_multi_axpy(int k, int64_t n, const int *h_counts, int subtract, const double *d_V, int64_t ldb, const double *d_coef,
+                         double *d_W, double *d_partials, double *d_norm2, void *stream)
+{
+    if (!bcg_width_ok(k) || n < 0 || !h_counts) return LMG_ERR_ARG;
+    BgmCounts cnt = {};
+    int maxc = 0;
+    for (int j = 0; j < k; ++j) {
+        if (h_counts[j] < 0 || h_counts[j] > kKryMaxVectors) return LMG_ERR_ARG;
+        cnt.c[j] = h_counts[j];
+        if (h_counts[j] > maxc) maxc = h_counts[j];
+    }
+    if (d_norm2 && !d_partials) return LMG_ERR_ARG;
+    if (maxc > 0 && !d_coef) return LMG_ERR_ARG;
+    hipStream_t st = lmg_stream(stream);
+    if (n == 0) {
+        if (d_norm2 && hipMemsetAsync(d_norm2, 0, (size_t)k * sizeof(double), st) != hipSuccess) return LMG_ERR_LAUNCH;
+        return LMG_OK;
+    }
+    if (maxc == 0 && !d_norm2) return LMG_OK;
+    const int bad = block_basis_check(k, n, maxc, d_V, ldb, d_W);
+    if (bad) return bad;
+    const double sign = subtract ? -1.0 : 1.0;
+    const int rc = bcg_with_width(k, [&](auto kc) -> int {
+        if (d_norm2)
+            hipLaunchKernelGGL((block_multi_axpy_kernel<LMG_CT(kc), true>), dim3(kKryGrid), dim3(kLmgBlock), 0, st, n, cnt, maxc, sign,
+                               d_V, ldb, d_coef, d_W, d_partials);
+        else
+            hipLaunchKernelGGL((block_multi_axpy_kernel<LMG_CT(kc), false>), dim3(kKryGrid), dim3(kLmgBlock), 0, st, n, cnt, maxc, sign,
+                               d_V, ldb, d_coef, d_W, (double *)nullptr);
+        LMG_CHECK_LAUNCH();
+        return LMG_OK;
+    });
+    if (rc != LMG_OK || !d_norm2) return rc;
+    hipLaunchKernelGGL(block_final_kernel<false>, dim3((unsigned)k), dim3(kKryGrid), 0, st, d_partials, d_norm2,
+                       (const double *)nullptr, (double *)nullptr);
+    LMG_CHECK_LAUNCH();
+    return LMG_OK;
+}
+
+int lmg_block_scale(int k, int64_t n, const double *h_scale, double *d_W, void *stream)
+{
+    if (!bcg_width_ok(k) || n < 0 || !h_scale) return LMG_ERR_ARG;
+    if (n == 0) return LMG_OK;
+    if (!d_W) return LMG_ERR_ARG;
+    if (!lmg_aligned16(d_W)) return LMG_ERR_ALIGN;
+    BgmScales sc = {};
+    for (int j = 0; j < k; ++j) sc.s[j] = h_scale[j];
+    return bcg_with_width(k, [&](auto kc) -> int {
+        hipLaunchKernelGGL(block_scale_kernel<LMG_CT(kc)>, dim3(lmg_grid_for(n, kLmgBlock)), dim3(kLmgBlock), 0, lmg_stream(stream), n,
+                           sc, d_W);
         LMG_CHECK_LAUNCH();
         return LMG_OK;
     });

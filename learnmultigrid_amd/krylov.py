@@ -1,5 +1,6 @@
 """Krylov iterations written against an ops module: restarted flexible GMRES (fgmres) and, on blocks of right-hand sides,
-multigrid-preconditioned conjugate gradients with per-column scalars that stay on the device (block_pcg, block_pcg_columns).
+multigrid-preconditioned conjugate gradients with per-column scalars that stay on the device (block_pcg, block_pcg_columns)
+and flexible GMRES with a per-column Arnoldi recurrence on the host (block_fgmres, block_fgmres_columns).
 
 Restarted flexible GMRES, right-preconditioned: FGMRES(m) of Saad, with the Gram-Schmidt passes fused on the device.
 
@@ -91,13 +92,13 @@ def block_pcg(ops_mod, A, bc, B, X, *, ncols, max_iterations, error, steps=2, om
     return track, its
 
 
-def block_pcg_columns(ops_mod, A, block_cycle, B, X0, device, *, max_iterations, error, steps=2, omega=0.8, shape="V",
-                      use_graph=False):
-    """block_pcg on the m >= 1 columns of the NumPy array B (n, m) from X0 (None: zero), in chunks of the widest block,
-    each padded with zero columns to the narrowest width that holds it (block.block_width).  block_cycle(mc) returns the
-    BlockCycle that preconditions a chunk of mc columns, ready for them (use_columns), or None: no preconditioner.
-    Returns (X, track, iterations) as NumPy arrays: track has one row more than the longest chunk ran iterations, NaN
-    where a column did not get that far."""
+def _columns_in_chunks(ops_mod, block_cycle, B, X0, device, solve_chunk):
+    """The m >= 1 columns of the NumPy array B (n, m) from X0 (None: zero) in chunks of the widest block, each padded with
+    zero columns to the narrowest width that holds it (block.block_width).  block_cycle(mc) returns the BlockCycle that
+    preconditions a chunk of mc columns, ready for them (use_columns), or None: no preconditioner.  solve_chunk(bc, Bk, Xk, mc)
+    solves the chunk in the (n, k) blocks Bk, Xk and returns (rows, iterations): rows of mc floats, mc iteration counts.
+    Returns (X, track, iterations) as NumPy arrays: track has as many rows as the longest chunk returned, NaN where a chunk
+    returned fewer.  A padding column that is not zero afterwards is an error."""
     widths = tuple(ops_mod.BLOCK_WIDTHS)
     n, m = B.shape
     X = np.empty((n, m))
@@ -110,8 +111,7 @@ def block_pcg_columns(ops_mod, A, block_cycle, B, X0, device, *, max_iterations,
         Bk[:, :mc].copy_(torch.from_numpy(np.ascontiguousarray(B[:, c0:c0 + mc])).to(device))
         if X0 is not None:
             Xk[:, :mc].copy_(torch.from_numpy(np.ascontiguousarray(X0[:, c0:c0 + mc])).to(device))
-        rows, it_c = block_pcg(ops_mod, A, bc, Bk, Xk, ncols=mc, max_iterations=max_iterations, error=error, steps=steps,
-                               omega=omega, shape=shape, use_graph=use_graph and bc is not None)
+        rows, it_c = solve_chunk(bc, Bk, Xk, mc)
         Xh = Xk.cpu().numpy()
         if Xh[:, mc:].any():
             raise RuntimeError("a padding column of the block left zero")
@@ -122,6 +122,155 @@ def block_pcg_columns(ops_mod, A, block_cycle, B, X0, device, *, max_iterations,
     for i, t in enumerate(tracks):
         track[:t.shape[0], i * widths[-1]:i * widths[-1] + t.shape[1]] = t
     return X, track, its
+
+
+def block_pcg_columns(ops_mod, A, block_cycle, B, X0, device, *, max_iterations, error, steps=2, omega=0.8, shape="V",
+                      use_graph=False):
+    """block_pcg on the m >= 1 columns of the NumPy array B (n, m) from X0 (None: zero), in chunks of the widest block,
+    each padded with zero columns to the narrowest width that holds it (_columns_in_chunks).  block_cycle(mc) returns the
+    BlockCycle that preconditions a chunk of mc columns, ready for them (use_columns), or None: no preconditioner.
+    Returns (X, track, iterations) as NumPy arrays: track has one row more than the longest chunk ran iterations, NaN
+    where a column did not get that far."""
+    def solve_chunk(bc, Bk, Xk, mc):
+        return block_pcg(ops_mod, A, bc, Bk, Xk, ncols=mc, max_iterations=max_iterations, error=error, steps=steps,
+                         omega=omega, shape=shape, use_graph=use_graph and bc is not None)
+
+    return _columns_in_chunks(ops_mod, block_cycle, B, X0, device, solve_chunk)
+
+
+def block_fgmres(ops_mod, A, bc, B, X, *, ncols, restart, max_iterations, error, steps=2, omega=0.8, shape="V",
+                 use_graph=False):
+    """Right-preconditioned FGMRES(restart) on the columns 0 .. ncols-1 of the (n, k) blocks B and X, k in
+    ops_mod.BLOCK_WIDTHS: A X = B from the iterate in X, which is updated in place.  A is the operator's block twin; bc is a
+    block.BlockCycle of the same width whose cycle(steps, omega, shape) from a zero guess is the preconditioner M ("V", "W" or
+    "F": nothing here needs a symmetric one), or None: Z is V.
+
+    Every column runs the recurrence of fgmres on its own numbers; the block shares the matrix bytes of the cycle and of
+    A Z, the launches and the host read.  Step s of a block's cycle:
+        Z_s = M V_s,  W = A Z_s into V_(s+1)
+        CGS2 against V_0 .. V_s as four launches (block_multi_dot, block_multi_axpy, and again with |w_j|^2 folded in);
+        ONE device-to-host read of h1, h2 and the norms, (2 (restart + 1) + 1) k doubles
+        per column on the host what fgmres does: h = h1 + h2, the Givens rotations, the estimate |g_(s+1)|
+        one block_scale: 1 / |w_j| for the columns that go on, 0 for those that do not (none after the last step of a
+        cycle: that block is not read again)
+    A column leaves the block's cycle at its own step k_j -- its estimate is <= error, |w_j| == 0, or its own iteration
+    count has reached max_iterations -- and rides through the remaining steps as zeros.  The cycle ends when no column is
+    on or after `restart` steps; then X += Z y is one block_multi_axpy with k_j vectors for column j, and the true residuals
+    of all columns are recomputed into V_0.  A column whose true norm is <= error, or that has used up max_iterations, is
+    off for good and its X is not stored again; the others restart together.  Columns that start at or below error (or at
+    zero) and the padding columns ncols .. k-1 are off from the beginning: their X keeps its bits.  Everything is
+    allocated before the first step: 2 restart + 1 blocks (restart + 1 without a preconditioner).
+
+    Returns (track, iterations): iterations[j] the inner iterations column j ran; track a list of rows of ncols floats in
+    which column j is the track fgmres returns for it, written in ITS OWN iteration count -- row 0 the true initial norm, row
+    i its i-th inner iteration: the Arnoldi estimate, replaced by the recomputed true norm for the last inner iteration of
+    each of its cycles --, NaN behind its last iteration.  A column's history does not depend on the other columns."""
+    m = int(restart)
+    if m < 1:
+        raise ValueError("restart must be >= 1, got %r" % (restart,))
+    n, k = X.shape
+    if k not in tuple(ops_mod.BLOCK_WIDTHS) or B.shape != X.shape or not 1 <= ncols <= k:
+        raise ValueError("block_fgmres: blocks %s / %s with %r columns in use" % (tuple(B.shape), tuple(X.shape), ncols))
+    if bc is not None and (bc.k != k or bc.levels[0].n != n):
+        raise ValueError("block_fgmres: the preconditioner works on (%d, %d) blocks, not (%d, %d)"
+                         % (bc.levels[0].n, bc.k, n, k))
+    dev = X.device
+    V = torch.zeros((m + 1, n, k), dtype=F64, device=dev)
+    Z = V if bc is None else torch.zeros((m, n, k), dtype=F64, device=dev)
+    part = torch.empty(max(ops_mod.block_partials_count(n, k), ops_mod.block_multi_partials_count(n, k, m + 1)), dtype=F64,
+                       device=dev)
+    nh = (m + 1) * k
+    hbuf = torch.zeros(2 * nh + k, dtype=F64, device=dev)                # h1 | h2 | |w_j|^2, h[i * k + j]
+    h1, h2, nrm = hbuf[:nh], hbuf[nh:2 * nh], hbuf[2 * nh:]
+    ybuf = torch.zeros(m * k, dtype=F64, device=dev)
+
+    ops_mod.block_residual_norm2(A, X, B, V[0], part, nrm)
+    beta = [math.sqrt(v) for v in nrm.tolist()]
+    tracks = [[beta[j]] for j in range(ncols)]
+    its = [0] * ncols
+
+    def goes_on(j):
+        return j < ncols and beta[j] > error and beta[j] > 0.0 and its[j] < max_iterations
+
+    on = [goes_on(j) for j in range(k)]
+    while any(on):
+        ops_mod.block_scale([1.0 / beta[j] if on[j] else 0.0 for j in range(k)], V[0])
+        g = [[beta[j]] for j in range(k)]
+        cs, sn, R = ([[] for _ in range(k)] for _ in range(3))
+        kj = [0] * k
+        for s in range(m):
+            W = V[s + 1]
+            zs = V[s] if bc is None else bc.apply(V[s], Z[s], steps, omega, shape, use_graph=use_graph)
+            ops_mod.block_spmv(A, zs, W, 1.0, 0.0)
+            counts = [s + 1 if on[j] else 0 for j in range(k)]
+            ops_mod.block_multi_dot(V, s + 1, W, part, h1)
+            ops_mod.block_multi_axpy(V, counts, h1, W)
+            ops_mod.block_multi_dot(V, s + 1, W, part, h2)
+            ops_mod.block_multi_axpy(V, counts, h2, W, part, nrm)
+            hb = hbuf.tolist()                                           # the one device-to-host read of the step
+            scale = [0.0] * k
+            for j in range(k):
+                if not on[j]:
+                    continue
+                h = [hb[i * k + j] + hb[nh + i * k + j] for i in range(s + 1)]
+                hn = math.sqrt(hb[2 * nh + j])
+                its[j] += 1
+                kj[j] = s + 1
+                c_, s_, g_ = cs[j], sn[j], g[j]
+                for i in range(s):                                       # the rotations of the earlier steps
+                    t = c_[i] * h[i] + s_[i] * h[i + 1]
+                    h[i + 1] = -s_[i] * h[i] + c_[i] * h[i + 1]
+                    h[i] = t
+                d = math.hypot(h[s], hn)
+                c, sj = (1.0, 0.0) if d == 0.0 else (h[s] / d, hn / d)
+                h[s] = c * h[s] + sj * hn
+                c_.append(c)
+                s_.append(sj)
+                g_.append(-sj * g_[s])
+                g_[s] = c * g_[s]
+                R[j].append(h)
+                est = abs(g_[s + 1])
+                tracks[j].append(est)
+                if est <= error or hn == 0.0 or its[j] == max_iterations:
+                    on[j] = False                                        # leaves the cycle at k_j = s + 1
+                else:
+                    scale[j] = 1.0 / hn
+            if not any(on) or s + 1 == m:
+                break
+            ops_mod.block_scale(scale, W)
+        y = [0.0] * (m * k)                                              # R y = g[:k_j] per column, R[c][r] = entry (r, c)
+        for j in range(k):
+            Rj, yj = R[j], [0.0] * kj[j]
+            for i in range(kj[j] - 1, -1, -1):
+                t = g[j][i]
+                for c in range(i + 1, kj[j]):
+                    t -= Rj[c][i] * yj[c]
+                yj[i] = t / Rj[i][i] if Rj[i][i] != 0.0 else 0.0
+                y[i * k + j] = yj[i]
+        ybuf.copy_(torch.tensor(y, dtype=F64))
+        ops_mod.block_multi_axpy(Z, kj, ybuf, X, subtract=False)
+        ops_mod.block_residual_norm2(A, X, B, V[0], part, nrm)
+        true = nrm.tolist()
+        for j in range(k):
+            if kj[j]:
+                beta[j] = math.sqrt(true[j])
+                tracks[j][-1] = beta[j]
+        on = [goes_on(j) for j in range(k)]
+    nan = float("nan")
+    rows = max(len(t) for t in tracks)
+    return [[t[i] if i < len(t) else nan for t in tracks] for i in range(rows)], its
+
+
+def block_fgmres_columns(ops_mod, A, block_cycle, B, X0, device, *, restart, max_iterations, error, steps=2, omega=0.8,
+                         shape="V", use_graph=False):
+    """block_fgmres on the m >= 1 columns of the NumPy array B (n, m) from X0 (None: zero), chunked and padded like
+    block_pcg_columns (_columns_in_chunks, which also checks that the padding columns are still zero).  Returns
+    (X, track, iterations) as NumPy arrays: column j of track is that column's own history, NaN behind its last iteration."""
+    def solve_chunk(bc, Bk, Xk, mc):
+        return block_fgmres(ops_mod, A, bc, Bk, Xk, ncols=mc, restart=restart, max_iterations=max_iterations, error=error,
+                            steps=steps, omega=omega, shape=shape, use_graph=use_graph and bc is not None)
+
+    return _columns_in_chunks(ops_mod, block_cycle, B, X0, device, solve_chunk)
 
 
 def fgmres(ops_mod, A, b, x, apply_M, *, restart, max_iterations, error, residual_out=None):

@@ -855,6 +855,58 @@ def block_cg_direction(rz_new, rz_old, mask, Z, P):
           "lmg_block_cg_direction")
 
 
+def block_multi_partials_count(n, k, nb):
+    return int(_lib.lib().lmg_block_multi_partials_count(int(n), int(k), int(nb)))
+
+
+def _block_basis_ok(name, V, nb, W):
+    """A block basis V (nb_max, n, k), contiguous, of which nb blocks are in use, and a block W (n, k); returns (k, ldb)."""
+    k = _block_ok(W)
+    _vec_ok(V)
+    if V.dim() != 3 or tuple(V.shape[1:]) != tuple(W.shape) or not 0 <= int(nb) <= V.shape[0]:
+        raise ValueError("%s: a basis %s does not hold %d blocks of shape %s" % (name, tuple(V.shape), nb, tuple(W.shape)))
+    if V.data_ptr() % 16:
+        raise ValueError("a block must start at a 16-byte aligned address")
+    return k, V.shape[1] * V.shape[2]
+
+
+def block_multi_dot(V, nb, W, partials, out):
+    """out[i * k + j] = V[i, :, j] . W[:, j] for i < nb and the k columns in one pass; the bits of multi_dot on contiguous
+    copies of column j."""
+    k, ldb = _block_basis_ok("block_multi_dot", V, nb, W)
+    _vec_ok(partials, out)
+    if out.numel() < int(nb) * k or partials.numel() < block_multi_partials_count(W.shape[0], k, nb):
+        raise ValueError("block_multi_dot: out or partials too short for %d blocks of %d columns" % (nb, k))
+    check(_lib.lib().lmg_block_multi_dot(k, W.shape[0], int(nb), _p(V), ldb, _p(W), _p(partials), _p(out), _s(W)),
+          "lmg_block_multi_dot")
+
+
+def block_multi_axpy(V, counts, coef, W, partials=None, norm2=None, subtract=True):
+    """Column j: W[:, j] -= sum_i coef[i * k + j] V[i, :, j], i < counts[j] ascending (subtract=False: +=), the bits of
+    multi_axpy with counts[j] rows; a column with counts[j] == 0 is not stored.  counts: k Python ints; coef a DEVICE tensor
+    in block_multi_dot's layout.  norm2[j] = |W[:, j]|^2 afterwards for every column, if given (partials needed)."""
+    counts = [int(c) for c in counts]
+    k, ldb = _block_basis_ok("block_multi_axpy", V, 0, W)
+    _vec_ok(coef, partials, norm2)
+    if len(counts) != k or min(counts) < 0 or max(counts) > V.shape[0]:
+        raise ValueError("block_multi_axpy: counts %s for a block of %d columns and a basis of %d blocks" % (counts, k, V.shape[0]))
+    if coef.numel() < max(counts) * k or (norm2 is not None and (
+            norm2.numel() < k or partials is None or partials.numel() < block_multi_partials_count(W.shape[0], k, 1))):
+        raise ValueError("block_multi_axpy: coef, norm2 or partials too short for %s rows of %d columns" % (counts, k))
+    check(_lib.lib().lmg_block_multi_axpy(k, W.shape[0], (ctypes.c_int * k)(*counts), 1 if subtract else 0, _p(V), ldb, _p(coef),
+                                          _p(W), _p(partials), _p(norm2), _s(W)), "lmg_block_multi_axpy")
+
+
+def block_scale(scale, W):
+    """W[:, j] = scale[j] * W[:, j] with axpby's bits (scale: k Python floats); a scale of 0.0 stores +0.0 whatever the
+    column held."""
+    k = _block_ok(W)
+    scale = [float(s) for s in scale]
+    if len(scale) != k:
+        raise ValueError("block_scale: %d factors for a block of %d columns" % (len(scale), k))
+    check(_lib.lib().lmg_block_scale(k, W.shape[0], (ctypes.c_double * k)(*scale), _p(W), _s(W)), "lmg_block_scale")
+
+
 def dense_gemv_block(M, X, Y):
     """Y = M X for a dense (n, m) matrix and blocks X (m, k), Y (n, k): M is read once for the k columns."""
     _vec_ok(M)

@@ -26,23 +26,17 @@ import torch
 
 from .. import ops
 from ..ops import F64
-from ._precond import check_smoother, make_apply
+from ._precond import BlockSolves, check_smoother, make_apply
 from .Solver import IterativeSolver, on_device
 
 
-class CG(IterativeSolver):
+class CG(BlockSolves, IterativeSolver):
 
     def __init__(self, matrix, rhs, **kw):
         super().__init__(matrix, rhs, **kw)
         self._log("Selected CG")
         self.label = "CG"
-        self._block_cycles = {}            # solve_many: {"H": the preconditioner, k: its BlockCycle of width k}
-        self._block_twin = None            # solve_many: the operator's fp64 sliced-ELL twin
-
-    def _invalidate(self):
-        super()._invalidate()
-        self._block_cycles = {}
-        self._block_twin = None
+        self._reset_blocks()               # solve_many's caches
 
     @on_device
     def solve(self, max_iterations=1000, error=1e-08, initial_guess=None, *, preconditioner=None,
@@ -126,43 +120,11 @@ class CG(IterativeSolver):
         if precond_cycle_shape not in ("V", "W"):
             raise ValueError("precond_cycle_shape must be 'V' or 'W' (CG needs a symmetric preconditioner), got %r"
                              % (precond_cycle_shape,))
-        B = np.asarray(rhs, dtype=np.float64)
-        if B.ndim != 2 or B.shape[0] != self.dim or B.shape[1] < 1:
-            raise ValueError("rhs must be (n, m) with n = %d and m >= 1, got %s" % (self.dim, B.shape))
-        X0 = None
-        if initial_guess is not None:
-            X0 = np.asarray(initial_guess, dtype=np.float64)
-            if X0.shape != B.shape:
-                raise ValueError("initial_guess must have the shape of rhs %s, got %s" % (B.shape, X0.shape))
         from .. import krylov
-        from ..block import BlockCycle, block_width
-        H = preconditioner
-        dev = self._device
-        A = self._device_matrix()
-        A.pack()
-        if self._block_twin is None:
-            self._block_twin = ops.block_twin(A)
-        if self._block_cycles.get("H") is not H:                   # (one hierarchy at a time: a new one drops the old blocks)
-            self._block_cycles = {"H": H}
 
-        def block_cycle(mc):
-            if H is None:
-                return None
-            k = block_width(mc, ops.BLOCK_WIDTHS)
-            bc = self._block_cycles.get(k)
-            if bc is None:
-                bc = self._block_cycles[k] = BlockCycle(H, mc)
-            bc.use_columns(mc)
-            return bc
+        def columns(A, block_cycle, B, X0, dev):
+            return krylov.block_pcg_columns(ops, A, block_cycle, B, X0, dev, max_iterations=int(max_iterations), error=error,
+                                            steps=precond_steps, omega=precond_omega, shape=precond_cycle_shape,
+                                            use_graph=bool(use_graph))
 
-        side = None if H is None else H.stream                     # (a cycle is captured on the hierarchy's stream)
-        if side is not None:
-            side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):                              # (None: the current stream)
-            X, track, its = krylov.block_pcg_columns(ops, self._block_twin, block_cycle, B, X0, dev,
-                                                     max_iterations=int(max_iterations), error=error, steps=precond_steps,
-                                                     omega=precond_omega, shape=precond_cycle_shape, use_graph=bool(use_graph))
-        if side is not None:
-            torch.cuda.current_stream(dev).wait_stream(side)
-        self.iterations_many = its
-        return X, track
+        return self._solve_many(rhs, initial_guess, preconditioner, columns)
