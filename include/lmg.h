@@ -505,6 +505,30 @@ int lmg_line_factor(int64_t n, int32_t line_stride, int dir, const int32_t *d_ro
 int lmg_line_solve(int64_t n, int32_t line_stride, int dir, int64_t first, int64_t step, const double *d_lo,
                    const double *d_minv, const double *d_cp, double *d_r, double omega, double *d_x, void *stream);
 
+/* The same for the wider lines of 25- and 49-point levels: band = p = 2 or 3 (anything else: LMG_ERR_ARG; p = 1 is the pair
+ * above).  dir 0: the entries of A at column - row = m, |m| <= p, that stay inside the row's line -- one that leaves it
+ * belongs to no system, and a non-zero one sets bit 0 of *d_flags --; dir 1: the entries at column - row = c W, |c| <= p.
+ * Every other entry of a row is off-line coupling and is not looked at: the caller forms the true residual.
+ * d_fac is one block of (2 p + 1) n doubles, 2 p + 1 planes of n doubles indexed by row:
+ *     plane t - 1, t = 1 .. p   the multiplier l_(j,t) of row j for row j - t
+ *     plane p                   minv_j = 1.0 / u_(j,0)
+ *     plane p + q, q = 1 .. p   the upper entry u_(j,q), column j + q of row j of U
+ * with j the row's place in its system.  Rows before the first and behind the last of a system count as zero rows.
+ *   lmg_line_factor_banded  banded LU without pivoting, row by row: w = the band of row j; for t = p .. 1 (the rows
+ *                    j - p .. j - 1 in that order)  l_(j,t) = w_(-t) * minv_(j-t),  then
+ *                    w_(-t+q) = w_(-t+q) - l_(j,t) * u_(j-t,q)  for q = 1 .. p;  what is left of w is the upper row
+ *                    u_(j,0..p), and minv_j = 1.0 / u_(j,0).  Bit 1 of *d_flags: a pivot u_(j,0) is zero or not finite.
+ *                    d_fac must not be d_vals.  Two launches.
+ *   lmg_line_solve_banded   x <- x + omega * (L U)^-1 r on the systems first, first + step, ...; every other row of d_x
+ *                    and d_r keeps its bits.  Forward  s = r_j,  s = s - l_(j,t) * d_(j-t) for t = p .. 1,  d_j = s
+ *                    overwrites d_r; backward  s = d_j,  s = s - u_(j,q) * e_(j+q) for q = p .. 1,  e_j = s * minv_j,
+ *                    x_i = x_i + omega * e_j.  Products and sums round separately.  d_r and d_x must be distinct and
+ *                    outside d_fac.  No division, no scratch. */
+int lmg_line_factor_banded(int64_t n, int32_t line_stride, int dir, int band, const int32_t *d_rowptr,
+                           const int32_t *d_colidx, const double *d_vals, double *d_fac, int32_t *d_flags, void *stream);
+int lmg_line_solve_banded(int64_t n, int32_t line_stride, int dir, int band, int64_t first, int64_t step,
+                          const double *d_fac, double *d_r, double omega, double *d_x, void *stream);
+
 /* CSR transpose by counting sort (setup: the restriction R = P^T as an explicit CSR, `i.T` of
  * Multigrid.py:93).  lmg_csr_transpose_count: d_counts[c] (zeroed by the caller, ncols entries) += number of
  * entries in column c; the caller scans d_counts into d_t_rowptr with lmg_exclusive_scan_i32;

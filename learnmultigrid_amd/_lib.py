@@ -93,6 +93,8 @@ SIGNATURES = {
     "lmg_csr_gershgorin": (_c.c_int, [_i64, _p, _p, _p, _p, _p]),
     "lmg_line_factor": (_c.c_int, [_i64, _i32, _c.c_int, _p, _p, _p, _p, _p, _p, _p, _p]),
     "lmg_line_solve": (_c.c_int, [_i64, _i32, _c.c_int, _i64, _i64, _p, _p, _p, _p, _f64, _p, _p]),
+    "lmg_line_factor_banded": (_c.c_int, [_i64, _i32, _c.c_int, _c.c_int, _p, _p, _p, _p, _p, _p]),
+    "lmg_line_solve_banded": (_c.c_int, [_i64, _i32, _c.c_int, _c.c_int, _i64, _i64, _p, _p, _f64, _p, _p]),
     "lmg_csr_transpose_max_row": (_c.c_int, []),
     "lmg_csr_transpose_count": (_c.c_int, [_i64, _i64, _p, _p, _p]),
     "lmg_csr_transpose_fill": (_c.c_int, [_i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p]),

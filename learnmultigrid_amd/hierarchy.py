@@ -24,8 +24,8 @@ from . import ops, smoothing
 from .coarse import make_coarse_solver
 from .ops import DeviceCSR, F64
 from .smoothing import (CHEBY_RATIO, GS_SWEEPS, LINE_DIRS, LINE_ORDERS, _directions, chebyshev_coefficients,  # noqa: F401
-                        gs_sweep_pair, line_config, line_half_steps)
-from .twins import DiaTwin, check_values, line_stride
+                        gs_sweep_pair, line_band_value, line_config, line_half_steps)
+from .twins import DiaTwin, check_values, line_reach, line_stride
 
 
 CYCLE_SHAPES = ("V", "W", "F")                         # pyamg's multilevel_solver.solve(cycle=...)
@@ -57,7 +57,7 @@ def _to_csr_host(M):
 
 class Level:
     __slots__ = ("n", "A", "P", "R", "x", "b", "r", "tmp", "plan_RA", "plan_RAP", "RA",
-                 "gs_sched", "host_pattern", "dinv", "M", "plan_RM", "plan_RMP", "RM", "d", "line")
+                 "gs_sched", "host_pattern", "dinv", "M", "plan_RM", "plan_RMP", "RM", "d", "line", "line_band")
 
     def __init__(self, A):
         self.n = A.shape[0]
@@ -74,6 +74,7 @@ class Level:
         self.dinv = None
         self.d = None                  # Chebyshev smoother: the step vector of the two-launch path (prepare_smoother)
         self.line = None               # "Line" smoother: {"W": line stride, "x" / "y": factor triple} (prepare_smoother)
+        self.line_band = None          # ... {"x" / "y": half-bandwidth p}; p > 1: the factors are one (2 p + 1) n block
         self.M = None                  # mass matrix of the level (optional, see Hierarchy(mass=...))
         self.plan_RM = self.plan_RMP = self.RM = None
 
@@ -151,6 +152,7 @@ class Hierarchy:
         self._graphs = {}
         self._cheby = None             # Chebyshev smoother: bounds and coefficient tables (prepare_smoother)
         self._line = None              # "Line" smoother: the (line_dir, line_order) in use (prepare_smoother)
+        self._line_band = 1            # ... and the largest half-bandwidth a level may use (line_band)
 
     # ------------------------------------------------------------------ setup ----------
     @property
@@ -247,60 +249,137 @@ class Hierarchy:
         if self._line is not None:                   # new values: new factors, for every direction that had them
             had = [sorted(k for k in (lev.line or ()) if k != "W") for lev in self.levels[:-1]]
             for lev in self.levels[:-1]:
-                lev.line = None
+                lev.line = lev.line_band = None
             for dirs in sorted({d for h in had for d in h}):
                 self._factor_lines(dirs)
 
     # ------------------------------------------------------------------ line relaxation --
-    def _line_stride(self, l):
-        """The line stride of level l: that of its grid twin, or -- small levels only, whose twins are never built -- the one
-        its offsets fit on the host (twins.line_stride).  None: no 3x3 grid geometry."""
+    OFFSET_CHUNK_ROWS = 1 << 16        # rows per step of _device_offsets
+
+    def _device_offsets(self, l):
+        """The distinct values of column - row of level l, ascending, found on the device in chunks of OFFSET_CHUNK_ROWS
+        rows: no host copy of the pattern and a transient of one chunk's entries.  The chunk boundaries of rowptr come to
+        the host in one read; every chunk then costs the synchronisations of two torch.unique calls and a size read, and
+        the result (at most 49 values) one more read.  Stops with None once there are more than 49 values (no 7x7 window
+        holds them)."""
+        A = self.levels[l].A
+        n = A.shape[0]
+        cuts = list(range(0, n, self.OFFSET_CHUNK_ROWS)) + [n]
+        ends = A.rowptr[torch.tensor(cuts, dtype=torch.int64, device=A.rowptr.device)].cpu().tolist()
+        seen = None
+        for (r0, r1), (e0, e1) in zip(zip(cuts[:-1], cuts[1:]), zip(ends[:-1], ends[1:])):
+            counts = (A.rowptr[r0 + 1:r1 + 1] - A.rowptr[r0:r1]).to(torch.int64)
+            rows = torch.repeat_interleave(torch.arange(r0, r1, dtype=torch.int64, device=counts.device), counts,
+                                           output_size=e1 - e0)
+            u = torch.unique(A.colidx[e0:e1].to(torch.int64) - rows)
+            seen = u if seen is None else torch.unique(torch.cat((seen, u)))
+            if seen.numel() > 49:
+                return None
+        return np.zeros(0, dtype=np.int64) if seen is None else seen.cpu().numpy()
+
+    def _line_stride(self, l, radius=1):
+        """(W, reach): the line stride of level l and the half-bandwidths (x, y) its line systems need -- those of its grid
+        twin (3x3: (1, 1)), or the stride its offsets fit with the smallest window radius <= `radius` (twins.line_stride):
+        on the host for small levels, whose twins are never built, and for radius > 1 from the offsets the device lists
+        for the larger ones (_device_offsets).  (None, None): no such geometry."""
         lev = self.levels[l]
         for twin in (getattr(lev.A, "stencil", None), getattr(lev.A, "dia", None)):
             if twin is not None:
-                return int(twin.W)
+                return int(twin.W), (1, 1)
         if lev.n >= DiaTwin.MIN_ROWS:
-            return None
-        if lev.host_pattern is None:
-            lev.host_pattern = (lev.A.rowptr.cpu().numpy(), lev.A.colidx.cpu().numpy())
-        rp, ci = lev.host_pattern
-        rows = np.repeat(np.arange(lev.n, dtype=np.int64), np.diff(rp))
-        W = line_stride(np.unique(ci.astype(np.int64) - rows), lev.n)
-        return None if W is None else int(W)
+            off = self._device_offsets(l) if radius > 1 else None
+        else:
+            if lev.host_pattern is None:
+                lev.host_pattern = (lev.A.rowptr.cpu().numpy(), lev.A.colidx.cpu().numpy())
+            rp, ci = lev.host_pattern
+            rows = np.repeat(np.arange(lev.n, dtype=np.int64), np.diff(rp))
+            off = np.unique(ci.astype(np.int64) - rows)
+        if off is None:
+            return None, None
+        for rad in range(1, radius + 1):
+            W = line_stride(off, lev.n, rad)
+            if W is not None:
+                return int(W), line_reach(off, int(W), rad)
+        return None, None
+
+    def _line_geometry(self, l, band):
+        """(W, {"x": p, "y": p}) of level l under the largest half-bandwidth `band`, or the ValueError that names the level
+        and why it cannot run the Line smoother."""
+        lev = self.levels[l]
+        W, reach = self._line_stride(l, band)
+        if W is None:
+            raise ValueError("the Line smoother cannot run on level %d (%d rows): no %dx%d grid geometry"
+                             % (l, lev.n, 2 * band + 1, 2 * band + 1))
+        if lev.n % W != 0:
+            raise ValueError("the Line smoother cannot run on level %d: its %d rows are no whole lines of %d "
+                             "(n %% W != 0)" % (l, lev.n, W))
+        if W == lev.n:
+            raise ValueError("the Line smoother cannot run on level %d: one line of %d rows (W == n, a 1-D operator)"
+                             % (l, lev.n))
+        return W, {"x": reach[0], "y": reach[1]}
 
     def _factor_lines(self, dirs):
         """The factors of every smoothed level for the directions `dirs` that it does not have yet (one flag read each)."""
         for l, lev in enumerate(self.levels[:-1]):
             if lev.line is None:
-                W = self._line_stride(l)
-                if W is None:
-                    raise ValueError("the Line smoother cannot run on level %d (%d rows): no 3x3 grid geometry" % (l, lev.n))
-                if lev.n % W != 0:
-                    raise ValueError("the Line smoother cannot run on level %d: its %d rows are no whole lines of %d "
-                                     "(n %% W != 0)" % (l, lev.n, W))
-                if W == lev.n:
-                    raise ValueError("the Line smoother cannot run on level %d: one line of %d rows (W == n, a 1-D operator)"
-                                     % (l, lev.n))
+                W, lev.line_band = self._line_geometry(l, self._line_band)
                 lev.line = {"W": W}
             for d in dirs:
                 if d not in lev.line:
+                    p = lev.line_band[d]
                     try:
-                        lev.line[d] = self.ops.line_factor(lev.A, lev.line["W"], d)
+                        lev.line[d] = (self.ops.line_factor(lev.A, lev.line["W"], d) if p == 1 else
+                                       self.ops.line_factor_banded(lev.A, lev.line["W"], d, p))
                     except ValueError as e:
                         raise ValueError("the Line smoother cannot run on level %d (%d rows, line stride %d): %s"
                                          % (l, lev.n, lev.line["W"], e)) from None
 
-    def _prepare_line(self, line_dir=None, line_order=None):
-        """Both None: keep what is prepared (the defaults when nothing is)."""
-        if self._line is not None and line_dir is None and line_order is None:
+    def _discard_lines(self, levels):
+        """Forget the line factors of `levels`.  A captured Line cycle holds their addresses, not the tensors: every
+        captured Line cycle goes with them."""
+        for lev in levels:
+            lev.line = lev.line_band = None
+        self._graphs = {k: g for k, g in self._graphs.items() if k[0] != "Line"}
+
+    def _use_line_band(self, band):
+        """Make `band` the largest half-bandwidth in use.  A level the new window refuses raises before anything changes:
+        the band in use, its factors and the captured cycles stay.  A level whose stride and half-bandwidths are the same
+        under both windows keeps its factors (a 3x3 level always does); only a level that reads differently is
+        factored anew."""
+        smoothed = self.levels[:-1]
+        geometry = [self._line_geometry(l, band) for l in range(len(smoothed))]
+        stale = [lev for lev, (W, p) in zip(smoothed, geometry) if lev.line is not None and (lev.line["W"], lev.line_band) != (W, p)]
+        if stale:
+            self._discard_lines(stale)
+        for lev, (W, p) in zip(smoothed, geometry):
+            if lev.line is None:
+                lev.line, lev.line_band = {"W": W}, p
+        self._line_band = band
+
+    def _prepare_line(self, line_dir=None, line_order=None, line_band=None):
+        """All None: keep what is prepared (the defaults when nothing is).  line_band None: the band in use (1 at first)."""
+        band = line_band_value(line_band)
+        keep = self._line is not None and line_dir is None and line_order is None
+        if keep and band in (None, self._line_band):
             return
-        cfg = line_config(line_dir, line_order)
-        self._factor_lines(cfg[0])
+        cfg = self._line if keep else line_config(line_dir, line_order)
+        if band not in (None, self._line_band):
+            self._use_line_band(band)
+            self._line = None
+            try:
+                self._factor_lines(cfg[0])
+            except ValueError:                       # (a pivot, a coupled line: nothing is prepared, back to the default)
+                self._discard_lines(self.levels[:-1])
+                self._line_band = 1
+                raise
+        else:
+            self._factor_lines(cfg[0])
         self._line = cfg
 
     def line_key(self):
-        """What a captured Line cycle depends on besides the cycle's own arguments: (line_dir, line_order) in use."""
-        return self._line
+        """What a captured Line cycle depends on besides the cycle's own arguments: (line_dir, line_order) in use, and the
+        largest half-bandwidth line_band where it is not 1."""
+        return self._line if self._line is None or self._line_band == 1 else self._line + (self._line_band,)
 
     # ------------------------------------------------------------------ Chebyshev ------
     def _prepare_chebyshev(self, cheby_lmax=None, cheby_ratio=None):
@@ -426,7 +505,11 @@ class Hierarchy:
                         x_is_zero = False
                     else:
                         self.ops.csr_residual_norm2(lev.A, lev.x, lev.b, lev.r, None, None)
-                    self.ops.line_solve(lev.line["W"], d, first, step, lev.line[d], lev.r, omega, lev.x)
+                    if lev.line_band[d] == 1:
+                        self.ops.line_solve(lev.line["W"], d, first, step, lev.line[d], lev.r, omega, lev.x)
+                    else:
+                        self.ops.line_solve_banded(lev.line["W"], d, lev.line_band[d], first, step, lev.line[d], lev.r,
+                                                   omega, lev.x)
         else:
             raise ValueError("unknown smoother %r" % (smoother,))
 
@@ -478,7 +561,7 @@ class Hierarchy:
 
     def cycle(self, smoother, steps, omega=1.0, gs_mode="lexicographic", l=0, depth=None,
               after_presmooth=None, x_is_zero=False, gs_sweep=("forward", "forward"), shape="V", *,
-              cheby_lmax=None, cheby_ratio=None, line_dir=None, line_order=None):
+              cheby_lmax=None, cheby_ratio=None, line_dir=None, line_order=None, line_band=None):
         """One V(steps, steps) cycle on level l: levels[l].x is the iterate, levels[l].b the
         right-hand side (Multigrid.py:77-124).  depth = number of grids used.
         gs_sweep: directions of the Gauss-Seidel pre- and post-smoothing, a pyamg sweep name for both or a (pre, post)
@@ -495,7 +578,8 @@ class Hierarchy:
         prepare_smoother; left None they are what was prepared (the Gershgorin bounds and CHEBY_RATIO by default).
         smoother "Line": `steps` line relaxation steps with damping omega on either side -- line_dir "x" | "y" | "xy",
         line_order "zebra" | "jacobi" as in prepare_smoother, left None what was prepared ("xy", "zebra" by default); the
-        post-smoothing half runs the directions and colours in reverse (gs_sweep is not used)."""
+        post-smoothing half runs the directions and colours in reverse (gs_sweep is not used).  line_band as in
+        prepare_smoother, left None the band in use."""
         children = cycle_children(shape)
         if smoother == "Chebyshev":
             if steps < 1:
@@ -503,7 +587,7 @@ class Hierarchy:
             self._prepare_chebyshev(cheby_lmax, cheby_ratio)
         pair = gs_sweep_pair(gs_sweep)
         if smoother == "Line":
-            self._prepare_line(line_dir, line_order)
+            self._prepare_line(line_dir, line_order, line_band)
             pair = ("forward", "backward")
         self._visit(smoother, steps, omega, gs_mode, l, (len(self.levels) if depth is None else depth) - 1, children,
                     pair, x_is_zero, after_presmooth)
@@ -596,7 +680,7 @@ class Hierarchy:
             self._ask("stencil_gs_check", lev.A)
 
     def prepare_smoother(self, smoother, gs_mode="lexicographic", l_from=0, gs_sweep=("forward", "forward"), *,
-                         cheby_lmax=None, cheby_ratio=None, line_dir=None, line_order=None):
+                         cheby_lmax=None, cheby_ratio=None, line_dir=None, line_order=None, line_band=None):
         """Everything a Gauss-Seidel cycle would otherwise do lazily on its first sweep -- the wavefront kernel's eligibility
         test (a device -> host read) and work buffer, the level schedules -- from level l_from down, for every direction
         gs_sweep uses: nothing of it may happen while a hipGraph is being captured.
@@ -608,12 +692,18 @@ class Hierarchy:
         default "xy") -- per level and direction two launches and one flag read --, and line_order ("zebra" | "jacobi",
         default "zebra").  A level that cannot run it raises a ValueError that names the level and the reason: no 3x3 grid
         geometry, rows that are no whole lines, a single line, an entry that couples two x-lines, a zero pivot.
+        line_band (1 | 2 | 3; None: the band in use, 1 at first) is the largest half-bandwidth a level's line systems may
+        have: per level and direction the smallest p <= line_band whose (2 p + 1)^2 window holds the level's offsets is used
+        -- tridiagonal systems (p = 1) on 5-, 7- and 9-point levels, pentadiagonal (2) on the 25-point and heptadiagonal (3) on
+        the 49-point Galerkin levels of learned or L2-type transfers.  Entries of a level outside the lines only enter
+        through the residual; with wide stencils the lines of one zebra colour are still coupled, a colour is then a
+        block-Jacobi step.  A level whose offsets fit no window up to line_band is refused with the window in the message.
         rebuild_numeric() renews the factors."""
         if smoother == "Chebyshev":
             self._prepare_chebyshev(cheby_lmax, cheby_ratio)
             return
         if smoother == "Line":
-            self._prepare_line(line_dir, line_order)
+            self._prepare_line(line_dir, line_order, line_band)
             return
         if smoother != "GaussSeidel":
             return
@@ -628,7 +718,7 @@ class Hierarchy:
                     self.gs_schedule(l, gs_mode, d)
 
     def captured_cycle(self, smoother, steps, omega, gs_mode, gs_sweep=("forward", "forward"), shape="V", *,
-                       cheby_lmax=None, cheby_ratio=None, line_dir=None, line_order=None):
+                       cheby_lmax=None, cheby_ratio=None, line_dir=None, line_order=None, line_band=None):
         """The same launch sequence as cycle(), captured once into a hipGraph and replayed (one graph per sweep pair and
         cycle shape)."""
         pair = gs_sweep_pair(gs_sweep)
@@ -636,7 +726,7 @@ class Hierarchy:
         if smoother == "Chebyshev":                 # (before the key: the bounds in use are part of it)
             self.prepare_smoother(smoother, cheby_lmax=cheby_lmax, cheby_ratio=cheby_ratio)
         if smoother == "Line":                      # (the factors: flag reads, never inside the capture)
-            self.prepare_smoother(smoother, line_dir=line_dir, line_order=line_order)
+            self.prepare_smoother(smoother, line_dir=line_dir, line_order=line_order, line_band=line_band)
         key = (smoother, steps, omega, gs_mode, pair, shape) + ((self.cheby_key(),) if smoother == "Chebyshev" else ())
         key += (self.line_key(),) if smoother == "Line" else ()
         g = self._graphs.get(key)
@@ -681,7 +771,7 @@ class Hierarchy:
         tot = 0
         for lev in self.levels:
             tot += lev.A.bytes() + (4 + (lev.d is not None)) * 8 * lev.n
-            tot += 0 if lev.line is None else 24 * lev.n * (len(lev.line) - 1)
+            tot += 0 if lev.line is None else sum(8 * (2 * lev.line_band[d] + 1) * lev.n for d in lev.line if d != "W")
             for M in (lev.P, lev.R, lev.RA):
                 if M is not None:
                     tot += M.bytes()

@@ -628,6 +628,59 @@ def line_solve(W, dir, first, step, fac, r, omega, x):
                                     float(omega), _p(x), _s(x)), "lmg_line_solve")
 
 
+LINE_SOLVE_BANDS = (2, 3)           # the half-bandwidths of lmg_line_factor_banded / lmg_line_solve_banded (1: the pair above)
+
+
+def _line_band(band):
+    if band not in LINE_SOLVE_BANDS or isinstance(band, bool):
+        raise ValueError("the banded line kernels take band 2 or 3, got %r" % (band,))
+    return int(band)
+
+
+def line_factor_banded_flags(A, W, dir, band):
+    """(fac, flags): the factored banded systems (half-bandwidth `band`, 2 | 3) of the grid lines of A in direction "x" | "y"
+    for line stride W, and the flag word of line_factor_flags.  fac is one tensor of (2 band + 1) n doubles, 2 band + 1 planes
+    indexed by row: `band` multipliers, minv, `band` upper entries (lmg_line_factor_banded: two launches, setup).  One
+    4-byte device -> host read: never while a hipGraph is being captured."""
+    if dir not in LINE_DIRS:
+        raise ValueError("line direction must be 'x' or 'y', got %r" % (dir,))
+    band = _line_band(band)
+    n = A.shape[0]
+    if A.shape[0] != A.shape[1] or int(W) < 1 or n % int(W) != 0:
+        raise ValueError("line relaxation needs a square operator whose %d rows are whole lines of %r" % (n, W))
+    dev = A.vals.device
+    fac = torch.empty((2 * band + 1) * n, dtype=F64, device=dev)
+    flags = torch.zeros(1, dtype=I32, device=dev)
+    check(_lib.lib().lmg_line_factor_banded(n, int(W), LINE_DIRS[dir], band, _p(A.rowptr), _p(A.colidx), _p(A.vals), _p(fac),
+                                            _p(flags), _s(A.rowptr)), "lmg_line_factor_banded")
+    return fac, int(flags.item())
+
+
+def line_factor_banded(A, W, dir, band):
+    """The factors of line_factor_banded_flags, or a ValueError that says which flag was set."""
+    fac, flags = line_factor_banded_flags(A, W, dir, band)
+    if flags & LINE_COUPLED:
+        raise ValueError("a non-zero entry couples two x-lines (an entry across the end of a line)")
+    if flags & LINE_PIVOT:
+        raise ValueError("a zero or non-finite pivot in the %s-line systems" % dir)
+    return fac
+
+
+def line_solve_banded(W, dir, band, first, step, fac, r, omega, x):
+    """x += omega * (L U)^-1 r on the systems first, first + step, ... of direction dir, L U the banded factors `fac` of
+    line_factor_banded; r (the residual, formed before the call) is overwritten on those systems, every other row of x and
+    r keeps its bits (lmg_line_solve_banded)."""
+    band = _line_band(band)
+    _vec_ok(fac, r, x)
+    n = x.numel()
+    if r.numel() != n or fac.numel() != (2 * band + 1) * n:
+        raise ValueError("line_solve_banded: r and x must have one entry per row, the factors %d" % (2 * band + 1))
+    if dir not in LINE_DIRS:
+        raise ValueError("line direction must be 'x' or 'y', got %r" % (dir,))
+    check(_lib.lib().lmg_line_solve_banded(n, int(W), LINE_DIRS[dir], band, int(first), int(step), _p(fac), _p(r),
+                                           float(omega), _p(x), _s(x)), "lmg_line_solve_banded")
+
+
 def _use_stencil(A, *vecs):
     if not (_PACKED_ENABLED and _STENCIL_ENABLED and A.stencil is not None):
         return False

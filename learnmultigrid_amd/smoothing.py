@@ -66,6 +66,18 @@ def line_config(line_dir=None, line_order=None):
     return line_dir, line_order
 
 
+LINE_BANDS = (1, 2, 3)                # its line_band: the largest half-bandwidth of a level's line systems (3x3, 5x5, 7x7 stencils)
+
+
+def line_band_value(line_band=None):
+    """line_band as an int, None as it is (the caller's default), or a ValueError (reads no state, like line_config)."""
+    if line_band is None:
+        return None
+    if isinstance(line_band, bool) or line_band not in LINE_BANDS:
+        raise ValueError("line_band must be one of %s, got %r" % (LINE_BANDS, line_band))
+    return int(line_band)
+
+
 def line_half_steps(line_dir, line_order, reverse=False):
     """The launches of one "Line" smoothing step as (direction, first, step) of ops.line_solve, each after a fresh residual:
     per direction of line_dir the even systems then the odd ones (zebra) or all systems (jacobi).  reverse: the

@@ -18,7 +18,9 @@ parameter (precond_omega is not used; bounds as prepared on the hierarchy, Hiera
 precond_smoother="Line" smooths with precond_steps line relaxation steps (precond_line_dir "x" | "y" | "xy",
 precond_line_order "zebra" | "jacobi", damping precond_omega: pass 1.0 for zebra) on either side; the post-smoothing half
 runs the directions and colours in reverse, the adjoint of the pre-smoothing half, so the cycle is a symmetric operator --
-the preconditioner for operators with a strong direction."""
+the preconditioner for operators with a strong direction.  precond_line_band (1 | 2 | 3, None = 1) is the largest
+half-bandwidth of the line systems (Hierarchy.prepare_smoother): 3 for the 25- and 49-point levels of learned transfers; the
+banded line solves are symmetric when A is, so the cycle stays a symmetric operator."""
 import math
 
 import numpy as np
@@ -26,7 +28,7 @@ import torch
 
 from .. import ops
 from ..ops import F64
-from ._precond import BlockSolves, check_smoother, make_apply
+from ._precond import BlockSolves, check_smoother, make_apply, prepare_line_band
 from .Solver import IterativeSolver, on_device
 
 
@@ -41,8 +43,8 @@ class CG(BlockSolves, IterativeSolver):
     @on_device
     def solve(self, max_iterations=1000, error=1e-08, initial_guess=None, *, preconditioner=None,
               precond_steps=2, precond_omega=0.8, precond_smoother="Jacobi", precond_cycle_shape="V",
-              precond_line_dir="xy", precond_line_order="zebra"):
-        check_smoother(precond_smoother, precond_line_dir, precond_line_order)
+              precond_line_dir="xy", precond_line_order="zebra", precond_line_band=None):
+        check_smoother(precond_smoother, precond_line_dir, precond_line_order, precond_line_band)
         if precond_cycle_shape not in ("V", "W"):
             raise ValueError("precond_cycle_shape must be 'V' or 'W' (CG needs a symmetric preconditioner), got %r"
                              % (precond_cycle_shape,))
@@ -60,6 +62,7 @@ class CG(BlockSolves, IterativeSolver):
         self.residual = math.sqrt(s.item())
         track = [self.residual]
         H = preconditioner
+        prepare_line_band(H, precond_smoother, precond_line_dir, precond_line_order, precond_line_band)
         # forward sweeps before, backward sweeps after the coarse correction: the symmetric Gauss-Seidel cycle
         apply_M = make_apply(H, precond_smoother, precond_steps, precond_omega, precond_cycle_shape, ("forward", "backward"),
                              precond_line_dir, precond_line_order)

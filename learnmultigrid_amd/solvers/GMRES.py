@@ -6,7 +6,7 @@ entry per iteration after it, stop on ||r|| <= error.
 
 `preconditioner=Hierarchy` preconditions from the right with one cycle from a zero guess per iteration, with CG's
 keywords; `precond_cycle_shape` also takes "F", and `precond_gs_sweep` any sweep name or (pre, post) pair of
-Hierarchy.cycle (default forward / forward).  The iteration is krylov.fgmres: classical Gram-Schmidt applied twice in four
+Hierarchy.cycle (default forward / forward); `precond_line_band` as in CG.solve.  The iteration is krylov.fgmres: classical Gram-Schmidt applied twice in four
 fused launches and one device-to-host read per iteration; its residual estimate is the true residual norm in exact
 arithmetic, and the true norm is recomputed at the end of every cycle of `restart` iterations.  Memory: 2 restart + 1
 vectors for the bases, (2 restart + 4) 8 n bytes with x, b and the scratch.
@@ -20,16 +20,16 @@ import torch
 from .. import krylov, ops
 from ..hierarchy import cycle_children, gs_sweep_pair
 from ..ops import F64
-from ._precond import BlockSolves, check_smoother, make_apply
+from ._precond import BlockSolves, check_smoother, make_apply, prepare_line_band
 from .Solver import IterativeSolver, on_device
 
 
 def check_keywords(restart, max_vectors, precond_smoother, precond_cycle_shape, precond_gs_sweep, precond_line_dir,
-                   precond_line_order):
+                   precond_line_order, precond_line_band=None):
     """The keyword checks of GMRES.solve (ValueError); returns the (pre, post) Gauss-Seidel directions.  max_vectors:
     the most basis rows a Gram-Schmidt launch takes (ops.krylov_max_vectors()): a cycle holds restart + 1."""
     check_restart(restart, max_vectors)
-    check_smoother(precond_smoother, precond_line_dir, precond_line_order)
+    check_smoother(precond_smoother, precond_line_dir, precond_line_order, precond_line_band)
     cycle_children(precond_cycle_shape)
     return gs_sweep_pair(precond_gs_sweep)
 
@@ -55,9 +55,10 @@ class GMRES(BlockSolves, IterativeSolver):
     @on_device
     def solve(self, max_iterations=1000, error=1e-08, initial_guess=None, *, restart=30, preconditioner=None,
               precond_steps=2, precond_omega=0.8, precond_smoother="Jacobi", precond_cycle_shape="V",
-              precond_gs_sweep="forward", precond_line_dir="xy", precond_line_order="zebra"):
+              precond_gs_sweep="forward", precond_line_dir="xy", precond_line_order="zebra",
+              precond_line_band=None):
         pair = check_keywords(restart, ops.krylov_max_vectors(), precond_smoother, precond_cycle_shape, precond_gs_sweep,
-                              precond_line_dir, precond_line_order)
+                              precond_line_dir, precond_line_order, precond_line_band)
         A = self._device_matrix()
         A.pack()
         n = self.dim
@@ -68,6 +69,7 @@ class GMRES(BlockSolves, IterativeSolver):
         H = preconditioner
         apply_M = None
         if H is not None:
+            prepare_line_band(H, precond_smoother, precond_line_dir, precond_line_order, precond_line_band)
             apply_M = make_apply(H, precond_smoother, precond_steps, precond_omega, precond_cycle_shape, pair,
                                  precond_line_dir, precond_line_order)
         track, self.iterations = krylov.fgmres(ops, A, b, x, apply_M, restart=int(restart), max_iterations=max_iterations,

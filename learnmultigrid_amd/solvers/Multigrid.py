@@ -28,7 +28,7 @@ import scipy.sparse as sp
 import torch
 
 from .. import ops, problems
-from ..hierarchy import Hierarchy, cycle_children, gs_sweep_pair, line_config
+from ..hierarchy import Hierarchy, cycle_children, gs_sweep_pair, line_band_value, line_config
 from .Solver import IterativeSolver, on_device
 
 _SMOOTHERS = ("GaussSeidel", "Jacobi", "CG")          # Multigrid.py:149-155
@@ -107,10 +107,12 @@ class Multigrid(IterativeSolver):
             raise ValueError("cheby_ratio must be > 1 (lambda_min = lambda_max / cheby_ratio), got %r" % (cheby_ratio,))
 
     @staticmethod
-    def _check_line(eff, line_dir, line_order):
-        """The keyword checks of the Line smoother (before any setup work); not looked at for any other smoother."""
+    def _check_line(eff, line_dir, line_order, line_band=None):
+        """The keyword checks of the Line smoother (before any setup work); not looked at for any other smoother.  Returns
+        line_band with its default (None = 1) filled in."""
         if eff == "Line":
             line_config(line_dir, line_order)
+            return 1 if line_band is None else line_band_value(line_band)
 
     # -- Multigrid.solve (Multigrid.py:36-75) ---------------------------------------------------
     @on_device
@@ -118,13 +120,14 @@ class Multigrid(IterativeSolver):
               initial_guess=None, cycle="V", first_call=False, *, omega=1.0,
               smoother_semantics="as_shipped", gs_mode="lexicographic", coarse_refine="auto",
               use_graph=False, mutate_initial_guess=False, gs_sweep="forward", cycle_shape="V",
-              cheby_lmax=None, cheby_ratio=None, line_dir="xy", line_order="zebra"):
+              cheby_lmax=None, cheby_ratio=None, line_dir="xy", line_order="zebra", line_band=None):
         """smoother="Line" (under smoother_semantics="as_named"; as shipped the name is ignored like every other): line
         relaxation -- smooth_steps steps with damping omega before and after the coarse correction, each solving the
         tridiagonal systems of the grid lines in direction line_dir ("x": storage lines, "y": grid columns, "xy": x then y;
         the post-smoothing half runs the reverse order), even systems then odd ones (line_order="zebra", omega = 1.0 suits)
         or all from one residual (line_order="jacobi", omega ~ 0.8).  The smoother for operators with a strong direction;
-        grid levels with a 3x3 stencil only (Hierarchy.prepare_smoother says which level cannot run it, and why).
+        grid levels with a 3x3 stencil only unless line_band (1 | 2 | 3, None = 1) allows the wider lines of 25-point (2) and
+        49-point (3) Galerkin levels (Hierarchy.prepare_smoother, which also says which level cannot run it, and why).
         smoother="Chebyshev" (under smoother_semantics="as_named"; as shipped the name is ignored like every other): one
         Chebyshev polynomial smoothing step of degree smooth_steps on D^-1 A before and after the coarse correction, on
         [lmax / cheby_ratio, lmax] per level.  cheby_lmax: None = each level's Gershgorin bound, a float, or one value per
@@ -143,14 +146,14 @@ class Multigrid(IterativeSolver):
         pair = gs_sweep_pair(gs_sweep)
         cycle_children(cycle_shape)
         self._check_cheby(eff, smooth_steps, cheby_ratio)
-        self._check_line(eff, line_dir, line_order)
+        line_band = self._check_line(eff, line_dir, line_order, line_band)
         H = self._setup(levels, first_call, coarse_refine)
         H.stream.wait_stream(torch.cuda.current_stream(self._device))
         with torch.cuda.stream(H.stream):
             if eff == "Chebyshev":
                 H.prepare_smoother(eff, cheby_lmax=cheby_lmax, cheby_ratio=cheby_ratio)
             elif eff == "Line":
-                H.prepare_smoother(eff, line_dir=line_dir, line_order=line_order)
+                H.prepare_smoother(eff, line_dir=line_dir, line_order=line_order, line_band=line_band)
             self._solve_on_stream(H, eff, smooth_steps, max_iterations, error, initial_guess, omega,
                                   gs_mode, use_graph, mutate_initial_guess, pair, cycle_shape)
         torch.cuda.current_stream(self._device).wait_stream(H.stream)
@@ -280,39 +283,40 @@ class Multigrid(IterativeSolver):
     def v_cycle(self, A, u0, rhs, smoother, smooth_steps, error, levels, first_call=False, *,
                 omega=1.0, smoother_semantics="as_shipped", gs_mode="lexicographic",
                 coarse_refine="auto", gs_sweep="forward", cheby_lmax=None, cheby_ratio=None, line_dir="xy",
-                line_order="zebra"):
+                line_order="zebra", line_band=None):
         """One V-cycle on (A, rhs) from u0; returns a fresh (n,1) array.  u0 receives the
-        pre-smoothed iterate like in the reference (:88-89).  gs_sweep, cheby_lmax, cheby_ratio, line_dir, line_order as in
-        solve()."""
+        pre-smoothed iterate like in the reference (:88-89).  gs_sweep, cheby_lmax, cheby_ratio, line_dir, line_order, line_band
+        as in solve()."""
         return self._one_cycle("V", A, u0, rhs, smoother, smooth_steps, levels, first_call, omega, smoother_semantics,
-                               gs_mode, coarse_refine, gs_sweep, cheby_lmax, cheby_ratio, line_dir, line_order)
+                               gs_mode, coarse_refine, gs_sweep, cheby_lmax, cheby_ratio, line_dir, line_order, line_band)
 
     @on_device
     def w_cycle(self, A, u0, rhs, smoother, smooth_steps, error, levels, first_call=False, *,
                 omega=1.0, smoother_semantics="as_shipped", gs_mode="lexicographic",
                 coarse_refine="auto", gs_sweep="forward", cheby_lmax=None, cheby_ratio=None, line_dir="xy",
-                line_order="zebra"):
+                line_order="zebra", line_band=None):
         """One W-cycle (solve(cycle_shape="W")) with v_cycle's arguments and behaviour."""
         return self._one_cycle("W", A, u0, rhs, smoother, smooth_steps, levels, first_call, omega, smoother_semantics,
-                               gs_mode, coarse_refine, gs_sweep, cheby_lmax, cheby_ratio, line_dir, line_order)
+                               gs_mode, coarse_refine, gs_sweep, cheby_lmax, cheby_ratio, line_dir, line_order, line_band)
 
     @on_device
     def f_cycle(self, A, u0, rhs, smoother, smooth_steps, error, levels, first_call=False, *,
                 omega=1.0, smoother_semantics="as_shipped", gs_mode="lexicographic",
                 coarse_refine="auto", gs_sweep="forward", cheby_lmax=None, cheby_ratio=None, line_dir="xy",
-                line_order="zebra"):
+                line_order="zebra", line_band=None):
         """One F-cycle (solve(cycle_shape="F")) with v_cycle's arguments and behaviour."""
         return self._one_cycle("F", A, u0, rhs, smoother, smooth_steps, levels, first_call, omega, smoother_semantics,
-                               gs_mode, coarse_refine, gs_sweep, cheby_lmax, cheby_ratio, line_dir, line_order)
+                               gs_mode, coarse_refine, gs_sweep, cheby_lmax, cheby_ratio, line_dir, line_order, line_band)
 
     def _one_cycle(self, shape, A, u0, rhs, smoother, smooth_steps, levels, first_call, omega, smoother_semantics,
-                   gs_mode, coarse_refine, gs_sweep, cheby_lmax=None, cheby_ratio=None, line_dir="xy", line_order="zebra"):
+                   gs_mode, coarse_refine, gs_sweep, cheby_lmax=None, cheby_ratio=None, line_dir="xy", line_order="zebra",
+                   line_band=None):
         if levels < 2:
             raise ValueError("levels must be >= 2")
         eff = self._effective_smoother(smoother, smoother_semantics)
         pair = gs_sweep_pair(gs_sweep)
         self._check_cheby(eff, smooth_steps, cheby_ratio)
-        self._check_line(eff, line_dir, line_order)
+        line_band = self._check_line(eff, line_dir, line_order, line_band)
         if A is self.matrix:
             H = self._setup(levels, first_call, coarse_refine)
         else:
@@ -337,7 +341,7 @@ class Multigrid(IterativeSolver):
             if eff == "Chebyshev":
                 H.prepare_smoother(eff, cheby_lmax=cheby_lmax, cheby_ratio=cheby_ratio)
             elif eff == "Line":
-                H.prepare_smoother(eff, line_dir=line_dir, line_order=line_order)
+                H.prepare_smoother(eff, line_dir=line_dir, line_order=line_order, line_band=line_band)
             H.cycle(eff, smooth_steps, omega, gs_mode, after_presmooth=hook, gs_sweep=pair, shape=shape)
             out = fine.x.cpu().numpy().reshape(n, 1).copy()
             if eff == "GaussSeidel":

@@ -4,7 +4,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from ..hierarchy import line_config
+from ..hierarchy import line_band_value, line_config
 
 SMOOTHERS = ("Jacobi", "GaussSeidel", "Chebyshev", "Line")
 
@@ -63,12 +63,20 @@ class BlockSolves:
         return X, track
 
 
-def check_smoother(smoother, line_dir, line_order):
+def check_smoother(smoother, line_dir, line_order, line_band=None):
     """The smoother name and, for "Line", its keywords: what CG.solve and GMRES.solve check before any device work."""
     if smoother not in SMOOTHERS:
         raise ValueError("precond_smoother must be 'Jacobi', 'GaussSeidel', 'Chebyshev' or 'Line', got %r" % (smoother,))
     if smoother == "Line":
         line_config(line_dir, line_order)
+        line_band_value(line_band)
+
+
+def prepare_line_band(H, smoother, line_dir, line_order, line_band):
+    """For the "Line" smoother: factor H's levels with the largest half-bandwidth line_band (None = 1) before make_apply,
+    which then keeps the band in use."""
+    if H is not None and smoother == "Line":
+        H.prepare_smoother("Line", line_dir=line_dir, line_order=line_order, line_band=1 if line_band is None else line_band)
 
 
 def make_apply(H, smoother, steps, omega, shape, gs_sweep, line_dir, line_order):

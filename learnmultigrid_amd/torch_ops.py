@@ -119,6 +119,10 @@ def _line_factor(rowptr, colidx, vals, line_stride, dir):
     return lo, minv, cp, flags
 
 
+def _line_factor_banded(rowptr, colidx, vals, line_stride, dir, band):
+    return ops.line_factor_banded_flags(_csr(rowptr, colidx, vals, rowptr.numel() - 1), line_stride, dir, band)
+
+
 def _spgemm(arp, aci, ava, acols, brp, bci, bva, bcols):
     C = ops.spgemm(_csr(arp, aci, ava, acols), _csr(brp, bci, bva, bcols))
     return C.rowptr, C.colidx, C.vals
@@ -208,6 +212,12 @@ OPS = [
      "float omega, Tensor(b!) x) -> ()",
      lambda line_stride, dir, first, step, lo, minv, cp, r, omega, x:
          ops.line_solve(line_stride, dir, first, step, (lo, minv, cp), r, omega, x), CUDA),
+    ("line_factor_banded(Tensor rowptr, Tensor colidx, Tensor vals, int line_stride, str dir, int band) -> (Tensor, int)",
+     _line_factor_banded, CUDA),
+    ("line_solve_banded(int line_stride, str dir, int band, int first, int step, Tensor fac, Tensor(a!) r, float omega, "
+     "Tensor(b!) x) -> ()",
+     lambda line_stride, dir, band, first, step, fac, r, omega, x:
+         ops.line_solve_banded(line_stride, dir, band, first, step, fac, r, omega, x), CUDA),
     # the fused Gram-Schmidt passes of the Krylov solvers: V is a 2-D contiguous basis, k its rows in use
     ("multi_dot(Tensor V, int k, Tensor w) -> Tensor", _multi_dot, CUDA),
     ("multi_axpy_(Tensor V, int k, Tensor coef, Tensor(a!) w, bool subtract) -> Tensor", _multi_axpy_, CUDA),

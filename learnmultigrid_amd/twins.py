@@ -52,11 +52,11 @@ def _p(t):
 
 
 # ---- decoding a pattern table: ptr[npat + 1], off[nent] (column - base(row), int64), val[nent] -----------------------------
-def _decompose(off, W):
-    """(c, d) of a linear offset for line stride W, or None."""
-    for c in (-1, 0, 1):
+def _decompose(off, W, radius=1):
+    """(c, d) of a linear offset for line stride W, |c|, |d| <= radius, or None."""
+    for c in range(-radius, radius + 1):
         d = off - c * W
-        if -1 <= d <= 1:
+        if -radius <= d <= radius:
             return c, d
     return None
 
@@ -94,17 +94,31 @@ def decode_window(ptr, off, val, nslots, slot_of):
     return values, mask
 
 
-def line_stride(off, n):
+def line_stride(off, n, radius=1):
     """The line stride W for which every offset of a square operator with n rows is a slot of the 3x3 window, or None.
     Several strides can fit (a 7-point operator {-W-1, -W, -1, 0, 1, W, W+1} also reads as a sheared stencil of stride
-    W + 1): the one that cuts the rows into whole lines is preferred."""
+    W + 1): the one that cuts the rows into whole lines is preferred.
+    radius 2 | 3: the same for the 5x5 | 7x7 window  c * W + d, |c|, |d| <= radius  (W >= 2 radius + 1: one reading per
+    offset).  The largest offset is cy * W + dx for some 1 <= cy <= radius, |dx| <= radius: those are the candidates."""
     mx = int(np.abs(off).max()) if off.size else 0
     if mx <= 1:
         cands = [n] if n >= 3 else []                         # 1-D: one line, only the centre slots are used
     else:
-        cands = [w for w in (mx, mx - 1, mx + 1) if 3 <= w < n]
-    fits = [w for w in cands if all(_decompose(int(o), w) is not None for o in off)]
+        cands = []
+        for cy in range(1, radius + 1):
+            for dx in [0] + [s * k for k in range(1, radius + 1) for s in (1, -1)]:
+                w, rem = divmod(mx - dx, cy)
+                if rem == 0 and 2 * radius + 1 <= w < n and w not in cands:
+                    cands.append(w)
+    fits = [w for w in cands if all(_decompose(int(o), w, radius) is not None for o in off)]
     return next((w for w in fits if n % w == 0), fits[0]) if fits else None
+
+
+def line_reach(off, W, radius):
+    """(reach in x, reach in y): the largest |d| and |c| of the offsets  c * W + d  of a level whose offsets all fit the
+    (2 radius + 1)^2 window of line stride W -- the half-bandwidths its x- and y-line systems need (at least 1)."""
+    cd = [_decompose(int(o), W, radius) for o in off]
+    return max([1] + [abs(d) for _, d in cd]), max([1] + [abs(c) for c, _ in cd])
 
 
 def hot_pattern(cand, counts):
