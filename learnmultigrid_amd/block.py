@@ -28,14 +28,18 @@ def block_width(ncols, widths):
 
 
 class _BlockLevel:
-    __slots__ = ("n", "A", "P", "R", "x", "b", "r", "tmp")
+    __slots__ = ("n", "A", "P", "R", "x", "b", "r", "tmp", "shared_A")
 
 
 class BlockCycle:
     """The cycle of a finished Hierarchy H on blocks of up to nrhs columns (padded with zero columns to the next width
     in ops.BLOCK_WIDTHS; a single column runs at the narrowest).  levels[0].x / .b are the fine blocks, (n, k) tensors
     the caller fills; columns nrhs .. k-1 stay zero through every kernel.  Everything is allocated here, nothing later:
-    a cycle can be captured into a hipGraph (captured())."""
+    a cycle can be captured into a hipGraph (captured()).
+    What is derived from the values of H -- the twins of every level's A that are not the matrix's own, the captured
+    cycles, which coarse solver there is -- follows H.rebuild_numeric(): every public method compares H.generation first
+    (_sync) and gives what a BlockCycle built after the rebuild gives.  (The one allocation after construction: the two
+    column vectors, when a rebuild leaves H with a coarse solver that has no block form.)"""
 
     def __init__(self, H, nrhs):
         if getattr(H, "cycle_values", "f64") != "f64":
@@ -55,18 +59,46 @@ class BlockCycle:
             bl = _BlockLevel()
             bl.n = lev.n
             bl.A = ops_.block_twin(lev.A)
+            # the matrix's own fp64 twin (repack_values keeps it current), or a copy of the values that _sync rewrites
+            bl.shared_A = bl.A is getattr(lev.A, "sell", None)
             bl.P = None if lev.P is None else ops_.block_twin(lev.P)
             bl.R = None if lev.R is None else ops_.block_twin(lev.R)
             bl.x, bl.b, bl.r, bl.tmp = (torch.zeros((lev.n, k), dtype=F64, device=dev) for _ in range(4))
             self.levels.append(bl)
         self.partials = torch.empty(ops_.block_partials_count(self.levels[0].n, k), dtype=F64, device=dev)
         self.norm2 = torch.zeros(k, dtype=F64, device=dev)
-        self.dense_coarse = getattr(H.coarse, "kind", None) == "dense"
-        nc = self.levels[-1].n
-        # the column loop of a coarse solver without a block form: one right-hand side and one solution at a time
-        self.col_b = None if self.dense_coarse else torch.zeros(nc, dtype=F64, device=dev)
-        self.col_x = None if self.dense_coarse else torch.zeros(nc, dtype=F64, device=dev)
+        self.col_b = self.col_x = None
+        self._coarse_kind()
         self._graphs = {}
+        self._generation = getattr(H, "generation", 0)
+
+    def _coarse_kind(self):
+        """Which coarse solver H has now, and the vectors of the column loop where it has no block form."""
+        self.dense_coarse = getattr(self.H.coarse, "kind", None) == "dense"
+        if not self.dense_coarse and self.col_b is None:
+            # the column loop of a coarse solver without a block form: one right-hand side and one solution at a time
+            nc, dev = self.levels[-1].n, self.H.device
+            self.col_b = torch.zeros(nc, dtype=F64, device=dev)
+            self.col_x = torch.zeros(nc, dtype=F64, device=dev)
+
+    def _sync(self):
+        """Follow H.rebuild_numeric(): nothing to do while H.generation is what it was.  After a rebuild every level's A has
+        new values on the same pattern (P and R have not changed): a twin that was the matrix's own is asked for again
+        (repack_values may have put another object there), a twin of this cycle's own gets the new value stream in place.
+        The captured cycles hold the addresses of the old coarse inverse and are dropped; the coarse solver may be one of
+        another kind.  Never runs inside a capture: captured() has called it before."""
+        gen = getattr(self.H, "generation", 0)
+        if gen == self._generation:
+            return
+        for bl, lev in zip(self.levels, self.H.levels):
+            if bl.shared_A or not hasattr(bl.A, "update_values"):    # (not a twin at all: the CPU stand-ins hand out the matrix)
+                bl.A = self.ops.block_twin(lev.A)
+                bl.shared_A = bl.A is getattr(lev.A, "sell", None)
+            elif not bl.A.update_values(lev.A):
+                raise RuntimeError("the block twin of a level with %d rows refused its new values" % bl.n)
+        self._graphs = {}
+        self._coarse_kind()
+        self._generation = gen
 
     def use_columns(self, nrhs):
         """Start over with nrhs columns of the same width: the fine iterate and right-hand side are cleared (the caller
@@ -74,6 +106,7 @@ class BlockCycle:
         nrhs = int(nrhs)
         if nrhs < 1 or block_width(nrhs, tuple(self.ops.BLOCK_WIDTHS)) != self.k:
             raise ValueError("%d columns do not belong in a block of width %d" % (nrhs, self.k))
+        self._sync()
         self.nrhs = nrhs
         # (the coarsest blocks too: the column loop of a coarse solver without a block form writes nrhs columns only)
         for t in (self.levels[0].x, self.levels[0].b, self.levels[-1].x, self.levels[-1].tmp):
@@ -119,12 +152,14 @@ class BlockCycle:
 
     def cycle(self, steps, omega, shape="V"):
         """One V(steps, steps), W or F cycle (the shapes of Hierarchy.cycle) with weighted Jacobi on levels[0].x / .b."""
+        self._sync()
         self._visit(0, cycle_children(shape), int(steps), float(omega))
 
     def apply(self, src, dst, steps, omega, shape="V", use_graph=False):
         """One cycle on the right-hand sides src (an (n, k) block) from a zero guess: the cycle as a preconditioner.  The
         result is levels[0].x, which is returned; dst (None: no copy) receives a copy of it.  use_graph: the cycle itself
         is the replay of captured()."""
+        self._sync()
         fine = self.levels[0]
         self.ops.copy(src.view(-1), fine.b.view(-1))
         self.ops.zero(fine.x.view(-1))
@@ -139,12 +174,14 @@ class BlockCycle:
 
     def residual_norms(self):
         """||b_j - A x_j||_2 of the nrhs columns on the fine level: one block residual, one read of k doubles."""
+        self._sync()
         bl = self.levels[0]
         self.ops.block_residual_norm2(bl.A, bl.x, bl.b, None, self.partials, self.norm2)
         return [math.sqrt(max(v, 0.0)) for v in self.norm2.cpu().tolist()[:self.nrhs]]
 
     def captured(self, steps, omega, shape="V"):
         """The launch sequence of cycle(), captured once into a hipGraph on H.stream's capture and replayed."""
+        self._sync()                                   # (before the capture: cycle() inside it finds nothing to do)
         key = (int(steps), float(omega), shape, self.nrhs)
         g = self._graphs.get(key)
         if g is None:

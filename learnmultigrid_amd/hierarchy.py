@@ -149,6 +149,7 @@ class Hierarchy:
         self.outer_r = torch.zeros(self.levels[0].n, dtype=F64, device=self.device)
         self.norm2 = torch.zeros(1, dtype=F64, device=self.device)
         self._factor_coarsest()
+        self.generation = 0            # counts rebuild_numeric(): holders of state derived from the values compare it (block.py)
         self._graphs = {}
         self._cheby = None             # Chebyshev smoother: bounds and coefficient tables (prepare_smoother)
         self._line = None              # "Line" smoother: the (line_dir, line_order) in use (prepare_smoother)
@@ -241,6 +242,7 @@ class Hierarchy:
         if self.levels[0].dinv is not None:          # (made on first use by a smoother that needs it: follows the values too)
             self.levels[0].dinv = self._inverse_diagonal(self.levels[0])
         self._factor_coarsest()
+        self.generation += 1                         # (after the factorisation: H.coarse may be a solver of another kind now)
         self._graphs = {}
         if self._cheby is not None:                  # new values: new bounds, new tables
             lmax_arg, ratio = self._cheby["args"]
