@@ -24,7 +24,7 @@ from . import ops, smoothing
 from .coarse import make_coarse_solver
 from .ops import DeviceCSR, F64
 from .smoothing import (CHEBY_RATIO, GS_SWEEPS, LINE_DIRS, LINE_ORDERS, _directions, chebyshev_coefficients,  # noqa: F401
-                        gs_sweep_pair, line_band_value, line_config, line_half_steps)
+                        chebyshev_degree, gs_sweep_pair, line_band_value, line_config, line_half_steps)
 from .twins import DiaTwin, check_values, line_reach, line_stride
 
 
@@ -244,16 +244,8 @@ class Hierarchy:
         self._factor_coarsest()
         self.generation += 1                         # (after the factorisation: H.coarse may be a solver of another kind now)
         self._graphs = {}
-        if self._cheby is not None:                  # new values: new bounds, new tables
-            lmax_arg, ratio = self._cheby["args"]
-            self._cheby = None
-            self._prepare_chebyshev(lmax_arg, ratio)
-        if self._line is not None:                   # new values: new factors, for every direction that had them
-            had = [sorted(k for k in (lev.line or ()) if k != "W") for lev in self.levels[:-1]]
-            for lev in self.levels[:-1]:
-                lev.line = lev.line_band = None
-            for dirs in sorted({d for h in had for d in h}):
-                self._factor_lines(dirs)
+        for smoother in smoothing.STATEFUL:          # new values: new bounds and tables, new factors
+            self._prepare(smoother, renew=True)
 
     # ------------------------------------------------------------------ line relaxation --
     OFFSET_CHUNK_ROWS = 1 << 16        # rows per step of _device_offsets
@@ -328,10 +320,9 @@ class Hierarchy:
                 lev.line = {"W": W}
             for d in dirs:
                 if d not in lev.line:
-                    p = lev.line_band[d]
+                    factor, _ = smoothing.line_ops(self.ops, lev.line_band[d])
                     try:
-                        lev.line[d] = (self.ops.line_factor(lev.A, lev.line["W"], d) if p == 1 else
-                                       self.ops.line_factor_banded(lev.A, lev.line["W"], d, p))
+                        lev.line[d] = factor(lev.A, lev.line["W"], d)
                     except ValueError as e:
                         raise ValueError("the Line smoother cannot run on level %d (%d rows, line stride %d): %s"
                                          % (l, lev.n, lev.line["W"], e)) from None
@@ -358,8 +349,17 @@ class Hierarchy:
                 lev.line, lev.line_band = {"W": W}, p
         self._line_band = band
 
-    def _prepare_line(self, line_dir=None, line_order=None, line_band=None):
-        """All None: keep what is prepared (the defaults when nothing is).  line_band None: the band in use (1 at first)."""
+    def _prepare_line(self, line_dir=None, line_order=None, line_band=None, renew=False):
+        """All None: keep what is prepared (the defaults when nothing is).  line_band None: the band in use (1 at first).
+        renew: the values have changed -- new factors for every direction that had them (none where nothing is prepared)."""
+        if renew:
+            if self._line is not None:
+                had = sorted({d for lev in self.levels[:-1] for d in (lev.line or ()) if d != "W"})
+                for lev in self.levels[:-1]:
+                    lev.line = lev.line_band = None
+                for d in had:
+                    self._factor_lines(d)
+            return
         band = line_band_value(line_band)
         keep = self._line is not None and line_dir is None and line_order is None
         if keep and band in (None, self._line_band):
@@ -384,10 +384,15 @@ class Hierarchy:
         return self._line if self._line is None or self._line_band == 1 else self._line + (self._line_band,)
 
     # ------------------------------------------------------------------ Chebyshev ------
-    def _prepare_chebyshev(self, cheby_lmax=None, cheby_ratio=None):
+    def _prepare_chebyshev(self, cheby_lmax=None, cheby_ratio=None, renew=False):
         """Bounds [lmax / ratio, lmax] of D^-1 A on every smoothed level, the inverse diagonals and the step vectors of
         the two-launch path.  cheby_lmax: None = the Gershgorin bound of each level (one small launch and one 8-byte
-        read per level), a float for all levels, or one value per smoothed level.  Both None: keep what is prepared."""
+        read per level), a float for all levels, or one value per smoothed level.  Both None: keep what is prepared.
+        renew: the values have changed -- new bounds and tables from the arguments in use, nothing where none were prepared."""
+        if renew:
+            if self._cheby is None:
+                return
+            (cheby_lmax, cheby_ratio), self._cheby = self._cheby["args"], None
         if self._cheby is not None and cheby_lmax is None and cheby_ratio is None:
             return
         ratio = CHEBY_RATIO if cheby_ratio is None else float(cheby_ratio)
@@ -427,6 +432,18 @@ class Hierarchy:
         if key not in ch["coef"]:
             ch["coef"][key] = chebyshev_coefficients(ch["lmax"][l], ch["ratio"], degree)
         return ch["coef"][key]
+
+    def _prepare(self, smoother, cheby_lmax=None, cheby_ratio=None, line_dir=None, line_order=None, line_band=None, renew=False):
+        """Bring the state of `smoother` to what its own keywords of prepare_smoother ask for (renew: to the new values of the
+        matrices); those of another smoother are not looked at.  The one place that knows which smoothers keep state here."""
+        if smoother == "Chebyshev":
+            self._prepare_chebyshev(cheby_lmax, cheby_ratio, renew)
+        elif smoother == "Line":
+            self._prepare_line(line_dir, line_order, line_band, renew)
+
+    def _smoother_key(self, smoother):
+        """What a captured cycle of `smoother` depends on besides the cycle's own arguments, as the tail of its key."""
+        return {"Chebyshev": (self.cheby_key(),), "Line": (self.line_key(),)}.get(smoother, ())
 
     def rebuild_mass_numeric(self, new_vals):
         """New values of the fine mass matrix on the same pattern: numeric SpGEMM passes only."""
@@ -507,11 +524,8 @@ class Hierarchy:
                         x_is_zero = False
                     else:
                         self.ops.csr_residual_norm2(lev.A, lev.x, lev.b, lev.r, None, None)
-                    if lev.line_band[d] == 1:
-                        self.ops.line_solve(lev.line["W"], d, first, step, lev.line[d], lev.r, omega, lev.x)
-                    else:
-                        self.ops.line_solve_banded(lev.line["W"], d, lev.line_band[d], first, step, lev.line[d], lev.r,
-                                                   omega, lev.x)
+                    _, solve = smoothing.line_ops(self.ops, lev.line_band[d])
+                    solve(lev.line["W"], d, first, step, lev.line[d], lev.r, omega, lev.x)
         else:
             raise ValueError("unknown smoother %r" % (smoother,))
 
@@ -584,12 +598,10 @@ class Hierarchy:
         prepare_smoother, left None the band in use."""
         children = cycle_children(shape)
         if smoother == "Chebyshev":
-            if steps < 1:
-                raise ValueError("the Chebyshev smoother needs smooth_steps >= 1 (the degree), got %r" % (steps,))
-            self._prepare_chebyshev(cheby_lmax, cheby_ratio)
+            chebyshev_degree(steps)
         pair = gs_sweep_pair(gs_sweep)
+        self._prepare(smoother, cheby_lmax, cheby_ratio, line_dir, line_order, line_band)
         if smoother == "Line":
-            self._prepare_line(line_dir, line_order, line_band)
             pair = ("forward", "backward")
         self._visit(smoother, steps, omega, gs_mode, l, (len(self.levels) if depth is None else depth) - 1, children,
                     pair, x_is_zero, after_presmooth)
@@ -701,12 +713,7 @@ class Hierarchy:
         through the residual; with wide stencils the lines of one zebra colour are still coupled, a colour is then a
         block-Jacobi step.  A level whose offsets fit no window up to line_band is refused with the window in the message.
         rebuild_numeric() renews the factors."""
-        if smoother == "Chebyshev":
-            self._prepare_chebyshev(cheby_lmax, cheby_ratio)
-            return
-        if smoother == "Line":
-            self._prepare_line(line_dir, line_order, line_band)
-            return
+        self._prepare(smoother, cheby_lmax, cheby_ratio, line_dir, line_order, line_band)
         if smoother != "GaussSeidel":
             return
         dirs = []
@@ -725,12 +732,8 @@ class Hierarchy:
         cycle shape)."""
         pair = gs_sweep_pair(gs_sweep)
         cycle_children(shape)
-        if smoother == "Chebyshev":                 # (before the key: the bounds in use are part of it)
-            self.prepare_smoother(smoother, cheby_lmax=cheby_lmax, cheby_ratio=cheby_ratio)
-        if smoother == "Line":                      # (the factors: flag reads, never inside the capture)
-            self.prepare_smoother(smoother, line_dir=line_dir, line_order=line_order, line_band=line_band)
-        key = (smoother, steps, omega, gs_mode, pair, shape) + ((self.cheby_key(),) if smoother == "Chebyshev" else ())
-        key += (self.line_key(),) if smoother == "Line" else ()
+        self._prepare(smoother, cheby_lmax, cheby_ratio, line_dir, line_order, line_band)   # (before the key and the capture)
+        key = (smoother, steps, omega, gs_mode, pair, shape) + self._smoother_key(smoother)
         g = self._graphs.get(key)
         if g is None:
             self.prepare_smoother(smoother, gs_mode, gs_sweep=pair)

@@ -118,10 +118,15 @@ def _columns_in_chunks(ops_mod, block_cycle, B, X0, device, solve_chunk):
         X[:, c0:c0 + mc] = Xh[:, :mc]
         its[c0:c0 + mc] = it_c
         tracks.append(np.array(rows, dtype=float).reshape(len(rows), mc))
+    return X, chunk_tracks(tracks, m, widths[-1]), its
+
+
+def chunk_tracks(tracks, m, width):
+    """One (rows, m) track from those of the chunks of `width` columns each: the rows of the longest, NaN where one has fewer."""
     track = np.full((max(t.shape[0] for t in tracks), m), np.nan)
     for i, t in enumerate(tracks):
-        track[:t.shape[0], i * widths[-1]:i * widths[-1] + t.shape[1]] = t
-    return X, track, its
+        track[:t.shape[0], i * width:i * width + t.shape[1]] = t
+    return track
 
 
 def block_pcg_columns(ops_mod, A, block_cycle, B, X0, device, *, max_iterations, error, steps=2, omega=0.8, shape="V",

@@ -52,6 +52,7 @@ def chebyshev_coefficients(lmax, ratio, degree):
 CHEBY_RATIO = 4.0       # lambda_max / lambda_min: the oscillatory modes of D^-1 A under full coarsening in two dimensions
 LINE_DIRS = ("x", "y", "xy")          # the line_dir of the "Line" smoother: the systems one step solves, in this order
 LINE_ORDERS = ("zebra", "jacobi")     # its line_order: even systems then odd ones with a fresh residual, or all from one
+STATEFUL = ("Chebyshev", "Line")      # the smoothers with keywords: Hierarchy.prepare_smoother keeps state for them
 
 
 def line_config(line_dir=None, line_order=None):
@@ -76,6 +77,37 @@ def line_band_value(line_band=None):
     if isinstance(line_band, bool) or line_band not in LINE_BANDS:
         raise ValueError("line_band must be one of %s, got %r" % (LINE_BANDS, line_band))
     return int(line_band)
+
+
+def chebyshev_degree(steps):
+    """The degree of a Chebyshev smoothing step (the smooth_steps of the solvers, the `steps` of a cycle), or a ValueError."""
+    if steps < 1:
+        raise ValueError("the Chebyshev smoother needs smooth_steps >= 1 (the degree), got %r" % (steps,))
+
+
+def smoother_options(smoother, steps, *, cheby_lmax=None, cheby_ratio=None, line_dir=None, line_order=None, line_band=None):
+    """The keywords of `smoother` as the solver classes hand them to Hierarchy.prepare_smoother(smoother, **options), or a
+    ValueError for a value it cannot take; the keywords of another smoother are not looked at ({} for Jacobi and Gauss-Seidel).
+    Reads no state and touches no device: every solver class calls it before any setup.  What a keyword left None means to
+    a solver class is decided here: "Line" runs ("xy", "zebra") with line_band 1 (to the hierarchy itself None is "what is
+    prepared"), "Chebyshev" keeps the bounds the hierarchy has (its defaults at first)."""
+    if smoother == "Chebyshev":
+        chebyshev_degree(steps)
+        if cheby_ratio is not None and not float(cheby_ratio) > 1.0:
+            raise ValueError("cheby_ratio must be > 1 (lambda_min = lambda_max / cheby_ratio), got %r" % (cheby_ratio,))
+        return {"cheby_lmax": cheby_lmax, "cheby_ratio": cheby_ratio}
+    if smoother == "Line":
+        line_dir, line_order = line_config(line_dir, line_order)
+        return {"line_dir": line_dir, "line_order": line_order, "line_band": 1 if line_band is None else line_band_value(line_band)}
+    return {}
+
+
+def line_ops(o, p):
+    """(factor(A, W, dir), solve(W, dir, first, step, fac, r, omega, x)) of line systems with half-bandwidth p: the
+    tridiagonal kernels for p = 1, the banded ones otherwise (they round differently and stay two sets of kernels)."""
+    if p == 1:
+        return o.line_factor, o.line_solve
+    return (lambda A, W, d: o.line_factor_banded(A, W, d, p)), (lambda W, d, *rest: o.line_solve_banded(W, d, p, *rest))
 
 
 def line_half_steps(line_dir, line_order, reverse=False):

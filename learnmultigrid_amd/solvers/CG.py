@@ -28,7 +28,7 @@ import torch
 
 from .. import ops
 from ..ops import F64
-from ._precond import BlockSolves, check_smoother, make_apply, prepare_line_band
+from ._precond import BlockSolves, check_smoother, make_apply
 from .Solver import IterativeSolver, on_device
 
 
@@ -44,7 +44,8 @@ class CG(BlockSolves, IterativeSolver):
     def solve(self, max_iterations=1000, error=1e-08, initial_guess=None, *, preconditioner=None,
               precond_steps=2, precond_omega=0.8, precond_smoother="Jacobi", precond_cycle_shape="V",
               precond_line_dir="xy", precond_line_order="zebra", precond_line_band=None):
-        check_smoother(precond_smoother, precond_line_dir, precond_line_order, precond_line_band)
+        options = check_smoother(precond_smoother, precond_steps, line_dir=precond_line_dir, line_order=precond_line_order,
+                                 line_band=precond_line_band)
         if precond_cycle_shape not in ("V", "W"):
             raise ValueError("precond_cycle_shape must be 'V' or 'W' (CG needs a symmetric preconditioner), got %r"
                              % (precond_cycle_shape,))
@@ -62,10 +63,9 @@ class CG(BlockSolves, IterativeSolver):
         self.residual = math.sqrt(s.item())
         track = [self.residual]
         H = preconditioner
-        prepare_line_band(H, precond_smoother, precond_line_dir, precond_line_order, precond_line_band)
         # forward sweeps before, backward sweeps after the coarse correction: the symmetric Gauss-Seidel cycle
         apply_M = make_apply(H, precond_smoother, precond_steps, precond_omega, precond_cycle_shape, ("forward", "backward"),
-                             precond_line_dir, precond_line_order)
+                             options)
         z = torch.empty_like(x)
         apply_M(r, z)
         p = z.clone()

@@ -20,16 +20,17 @@ import torch
 from .. import krylov, ops
 from ..hierarchy import cycle_children, gs_sweep_pair
 from ..ops import F64
-from ._precond import BlockSolves, check_smoother, make_apply, prepare_line_band
+from ._precond import BlockSolves, check_smoother, make_apply
 from .Solver import IterativeSolver, on_device
 
 
 def check_keywords(restart, max_vectors, precond_smoother, precond_cycle_shape, precond_gs_sweep, precond_line_dir,
-                   precond_line_order, precond_line_band=None):
+                   precond_line_order, precond_line_band=None, precond_steps=2):
     """The keyword checks of GMRES.solve (ValueError); returns the (pre, post) Gauss-Seidel directions.  max_vectors:
     the most basis rows a Gram-Schmidt launch takes (ops.krylov_max_vectors()): a cycle holds restart + 1."""
     check_restart(restart, max_vectors)
-    check_smoother(precond_smoother, precond_line_dir, precond_line_order, precond_line_band)
+    check_smoother(precond_smoother, precond_steps, line_dir=precond_line_dir, line_order=precond_line_order,
+                   line_band=precond_line_band)
     cycle_children(precond_cycle_shape)
     return gs_sweep_pair(precond_gs_sweep)
 
@@ -58,7 +59,7 @@ class GMRES(BlockSolves, IterativeSolver):
               precond_gs_sweep="forward", precond_line_dir="xy", precond_line_order="zebra",
               precond_line_band=None):
         pair = check_keywords(restart, ops.krylov_max_vectors(), precond_smoother, precond_cycle_shape, precond_gs_sweep,
-                              precond_line_dir, precond_line_order, precond_line_band)
+                              precond_line_dir, precond_line_order, precond_line_band, precond_steps)
         A = self._device_matrix()
         A.pack()
         n = self.dim
@@ -69,9 +70,10 @@ class GMRES(BlockSolves, IterativeSolver):
         H = preconditioner
         apply_M = None
         if H is not None:
-            prepare_line_band(H, precond_smoother, precond_line_dir, precond_line_order, precond_line_band)
+            # (check_keywords returns the directions alone: the options it has checked are put together here)
             apply_M = make_apply(H, precond_smoother, precond_steps, precond_omega, precond_cycle_shape, pair,
-                                 precond_line_dir, precond_line_order)
+                                 check_smoother(precond_smoother, precond_steps, line_dir=precond_line_dir,
+                                                line_order=precond_line_order, line_band=precond_line_band))
         track, self.iterations = krylov.fgmres(ops, A, b, x, apply_M, restart=int(restart), max_iterations=max_iterations,
                                                error=error, residual_out=r)
         if track[-1] <= error:

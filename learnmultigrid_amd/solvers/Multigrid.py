@@ -27,15 +27,17 @@ import numpy as np
 import scipy.sparse as sp
 import torch
 
-from .. import ops, problems
-from ..hierarchy import Hierarchy, cycle_children, gs_sweep_pair, line_band_value, line_config
+from .. import krylov, ops, problems
+from ..hierarchy import Hierarchy, cycle_children, gs_sweep_pair
+from ..smoothing import smoother_options
+from ._precond import BlockSolves, check_columns, hierarchy_stream
 from .Solver import IterativeSolver, on_device
 
 _SMOOTHERS = ("GaussSeidel", "Jacobi", "CG")          # Multigrid.py:149-155
 _EXTRA_SMOOTHERS = ("Chebyshev", "Line")                    # not in the reference: honoured under smoother_semantics="as_named"
 
 
-class Multigrid(IterativeSolver):
+class Multigrid(BlockSolves, IterativeSolver):
 
     def __init__(self, matrix, rhs, **kw):
         super().__init__(matrix, rhs, **kw)
@@ -44,7 +46,7 @@ class Multigrid(IterativeSolver):
         self.hierarchy = None              # optional list of transfer operators (all levels)
         self._hier = None
         self._hier_key = None
-        self._block_cycles = {}            # solve_many: {"H": the hierarchy, k: its BlockCycle of width k}
+        self._reset_blocks()               # solve_many's cache of block cycles
 
     # -- transfer-operator dispatch (Multigrid.py:91 -> :126 / :171 / :188) --------------------
     def interpolator(self, dimension, _first_call=False):
@@ -81,7 +83,6 @@ class Multigrid(IterativeSolver):
     def _invalidate(self):
         super()._invalidate()
         self._hier = None
-        self._block_cycles = {}
 
     @staticmethod
     def _effective_smoother(smoother, semantics):
@@ -96,23 +97,10 @@ class Multigrid(IterativeSolver):
             raise ValueError("CG is not a V-cycle smoother in this build (unused by the reference too)")
         return smoother
 
-    @staticmethod
-    def _check_cheby(eff, smooth_steps, cheby_ratio):
-        """The keyword checks of the Chebyshev smoother that need no hierarchy (before any setup work)."""
-        if eff != "Chebyshev":
-            return
-        if smooth_steps < 1:
-            raise ValueError("the Chebyshev smoother needs smooth_steps >= 1 (the degree), got %r" % (smooth_steps,))
-        if cheby_ratio is not None and not float(cheby_ratio) > 1.0:
-            raise ValueError("cheby_ratio must be > 1 (lambda_min = lambda_max / cheby_ratio), got %r" % (cheby_ratio,))
-
-    @staticmethod
-    def _check_line(eff, line_dir, line_order, line_band=None):
-        """The keyword checks of the Line smoother (before any setup work); not looked at for any other smoother.  Returns
-        line_band with its default (None = 1) filled in."""
-        if eff == "Line":
-            line_config(line_dir, line_order)
-            return 1 if line_band is None else line_band_value(line_band)
+    def _ready(self, H, eff, options):
+        """Prepare H for the smoother as its options ask (smoother_options); one without any sets itself up in its first sweep."""
+        if options:
+            H.prepare_smoother(eff, **options)
 
     # -- Multigrid.solve (Multigrid.py:36-75) ---------------------------------------------------
     @on_device
@@ -145,18 +133,13 @@ class Multigrid(IterativeSolver):
         eff = self._effective_smoother(smoother, smoother_semantics)
         pair = gs_sweep_pair(gs_sweep)
         cycle_children(cycle_shape)
-        self._check_cheby(eff, smooth_steps, cheby_ratio)
-        line_band = self._check_line(eff, line_dir, line_order, line_band)
+        options = smoother_options(eff, smooth_steps, cheby_lmax=cheby_lmax, cheby_ratio=cheby_ratio, line_dir=line_dir,
+                                   line_order=line_order, line_band=line_band)
         H = self._setup(levels, first_call, coarse_refine)
-        H.stream.wait_stream(torch.cuda.current_stream(self._device))
-        with torch.cuda.stream(H.stream):
-            if eff == "Chebyshev":
-                H.prepare_smoother(eff, cheby_lmax=cheby_lmax, cheby_ratio=cheby_ratio)
-            elif eff == "Line":
-                H.prepare_smoother(eff, line_dir=line_dir, line_order=line_order, line_band=line_band)
+        with hierarchy_stream(H, self._device):
+            self._ready(H, eff, options)
             self._solve_on_stream(H, eff, smooth_steps, max_iterations, error, initial_guess, omega,
                                   gs_mode, use_graph, mutate_initial_guess, pair, cycle_shape)
-        torch.cuda.current_stream(self._device).wait_stream(H.stream)
 
     def _solve_on_stream(self, H, eff, smooth_steps, max_iterations, error, initial_guess, omega,
                          gs_mode, use_graph, mutate_initial_guess, gs_sweep=("forward", "forward"), shape="V"):
@@ -219,36 +202,21 @@ class Multigrid(IterativeSolver):
         deflated, it simply keeps being smoothed (its residual keeps falling and is still recorded).
         self.iterations_many[j]: the number of cycles before column j first passed, or max_iterations.  Rows of track
         beyond the last iteration of a column's chunk (another chunk needed more) hold NaN."""
-        B = np.asarray(rhs, dtype=np.float64)
-        if B.ndim != 2 or B.shape[0] != self.dim or B.shape[1] < 1:
-            raise ValueError("rhs must be (n, m) with n = %d and m >= 1, got %s" % (self.dim, B.shape))
+        B, X0 = check_columns(rhs, initial_guess, self.dim)
         if levels < 2:
             raise ValueError("levels must be >= 2 (levels counts grids)")
         if smoother != "Jacobi":
             raise ValueError("solve_many smooths with weighted Jacobi only, got smoother=%r" % (smoother,))
         cycle_children(cycle_shape)
         m = B.shape[1]
-        X0 = None
-        if initial_guess is not None:
-            X0 = np.asarray(initial_guess, dtype=np.float64)
-            if X0.shape != B.shape:
-                raise ValueError("initial_guess must have the shape of rhs %s, got %s" % (B.shape, X0.shape))
-        from ..block import BlockCycle, block_width
         H = self._setup(levels, self._FIRST_CALL, coarse_refine)
         X = np.empty_like(B)
         tracks, its = [], np.full(m, int(max_iterations), dtype=np.int64)
         wmax = ops.BLOCK_WIDTHS[-1]
-        H.stream.wait_stream(torch.cuda.current_stream(self._device))
-        with torch.cuda.stream(H.stream):
+        with hierarchy_stream(H, self._device):
             for c0 in range(0, m, wmax):
                 mc = min(wmax, m - c0)
-                k = block_width(mc, ops.BLOCK_WIDTHS)
-                if self._block_cycles.get("H") is not H:           # (one hierarchy at a time: a new one drops the old blocks)
-                    self._block_cycles = {"H": H}
-                bc = self._block_cycles.get(k)
-                if bc is None:
-                    bc = self._block_cycles[k] = BlockCycle(H, mc)
-                bc.use_columns(mc)
+                bc = self._block_cycle(H, mc)
                 fine = bc.levels[0]
                 fine.b[:, :mc].copy_(torch.from_numpy(np.ascontiguousarray(B[:, c0:c0 + mc])).to(self._device))
                 if X0 is not None:
@@ -270,13 +238,9 @@ class Multigrid(IterativeSolver):
                         bc.cycle(smooth_steps, omega, cycle_shape)
                 X[:, c0:c0 + mc] = bc.levels[0].x[:, :mc].cpu().numpy()
                 tracks.append(np.array(rows, dtype=float).reshape(len(rows), mc))
-        torch.cuda.current_stream(self._device).wait_stream(H.stream)
-        track = np.full((max((t.shape[0] for t in tracks), default=0), m), np.nan)
-        for i, t in enumerate(tracks):
-            track[:t.shape[0], i * wmax:i * wmax + t.shape[1]] = t
         self.iterations_many = its
         self.level_dims = H.sizes
-        return X, track
+        return X, krylov.chunk_tracks(tracks, m, wmax)
 
     # -- Multigrid.v_cycle (Multigrid.py:77) ------------------------------------------------------
     @on_device
@@ -309,14 +273,13 @@ class Multigrid(IterativeSolver):
                                gs_mode, coarse_refine, gs_sweep, cheby_lmax, cheby_ratio, line_dir, line_order, line_band)
 
     def _one_cycle(self, shape, A, u0, rhs, smoother, smooth_steps, levels, first_call, omega, smoother_semantics,
-                   gs_mode, coarse_refine, gs_sweep, cheby_lmax=None, cheby_ratio=None, line_dir="xy", line_order="zebra",
-                   line_band=None):
+                   gs_mode, coarse_refine, gs_sweep, cheby_lmax, cheby_ratio, line_dir, line_order, line_band):
         if levels < 2:
             raise ValueError("levels must be >= 2")
         eff = self._effective_smoother(smoother, smoother_semantics)
         pair = gs_sweep_pair(gs_sweep)
-        self._check_cheby(eff, smooth_steps, cheby_ratio)
-        line_band = self._check_line(eff, line_dir, line_order, line_band)
+        options = smoother_options(eff, smooth_steps, cheby_lmax=cheby_lmax, cheby_ratio=cheby_ratio, line_dir=line_dir,
+                                   line_order=line_order, line_band=line_band)
         if A is self.matrix:
             H = self._setup(levels, first_call, coarse_refine)
         else:
@@ -336,17 +299,12 @@ class Multigrid(IterativeSolver):
         def hook(x_dev):
             if u0a.dtype == np.float64 and u0a.flags.writeable:
                 u0a.reshape(-1)[:] = x_dev.cpu().numpy()
-        H.stream.wait_stream(torch.cuda.current_stream(self._device))
-        with torch.cuda.stream(H.stream):
-            if eff == "Chebyshev":
-                H.prepare_smoother(eff, cheby_lmax=cheby_lmax, cheby_ratio=cheby_ratio)
-            elif eff == "Line":
-                H.prepare_smoother(eff, line_dir=line_dir, line_order=line_order, line_band=line_band)
+        with hierarchy_stream(H, self._device):
+            self._ready(H, eff, options)
             H.cycle(eff, smooth_steps, omega, gs_mode, after_presmooth=hook, gs_sweep=pair, shape=shape)
             out = fine.x.cpu().numpy().reshape(n, 1).copy()
             if eff == "GaussSeidel":
                 H.check_smoothers()
-        torch.cuda.current_stream(self._device).wait_stream(H.stream)
         return out
 
     def smoother_to_method(self, smoother):

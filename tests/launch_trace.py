@@ -23,8 +23,8 @@ from support import free_port
 # the parameter each op writes its result to (only used to tell "prev" from "t" among unnamed vectors)
 WRITES = {"csr_jacobi": "x_out", "vmul": "out", "stencil_smooth": "x_out", "stencil_cheby": "x_out",
           "stencil_smooth_turnaround": "x_out", "stencil_gs": "x", "csr_gs_schedule": "x", "cheby_update": "x",
-          "line_solve": "x", "zero": "x", "csr_spmv": "y", "axpby": "y", "copy": "dst", "csr_residual_norm2": "r",
-          "gather": "buf", "scatter": "x"}
+          "line_solve": "x", "line_solve_banded": "x", "zero": "x", "csr_spmv": "y", "axpby": "y", "copy": "dst",
+          "csr_residual_norm2": "r", "gather": "buf", "scatter": "x"}
 QUIET = ("_available", "_selected")
 
 
@@ -268,15 +268,142 @@ def operator_traces():
     return out
 
 
+# ---- the preconditioner of the Krylov solvers: make_apply, then two applications ---------------------------------------------
+PRECOND = [("Jacobi", 2, {}), ("GaussSeidel", 2, {}), ("Chebyshev", 2, {}),
+           ("Line", 1, {"line_band": 1}), ("Line", 1, {"line_band": 2})]
+
+
+def _make_apply(H, smoother, steps, omega, shape, gs_sweep, line_dir="xy", line_order="zebra", line_band=None):
+    """What CG.solve and GMRES.solve do between their keyword check and the first application."""
+    from learnmultigrid_amd.solvers import _precond
+    options = _precond.check_smoother(smoother, steps, line_dir=line_dir, line_order=line_order, line_band=line_band)
+    return _precond.make_apply(H, smoother, steps, omega, shape, gs_sweep, options)
+
+
+def precond_traces():
+    """solvers/_precond.make_apply on a 3-level hierarchy of the 33 x 33 problem, then two applications (the module's ops
+    is the tracer's namespace while they run)."""
+    from learnmultigrid_amd.hierarchy import Hierarchy
+    from learnmultigrid_amd.solvers import _precond
+    A, rhs, hier = _problem()
+    out = {}
+    saved = _precond.ops
+    try:
+        for fname in ("none", "all"):
+            for smoother, steps, kw in PRECOND:
+                for shape in ("V", "W"):
+                    tr = Tracer(trace_shim(FUSED[fname]))
+                    _precond.ops = tr.ops
+                    H = Hierarchy(A.copy(), hier, "cpu", ops_mod=tr.ops)
+                    src, dst = torch.from_numpy(rhs.ravel().copy()), torch.zeros(A.shape[0], dtype=torch.float64)
+                    tr.name(src, "src")
+                    tr.name(dst, "dst")
+                    for l, lev in enumerate(H.levels):
+                        tr.name_level(lev, "L%d" % l)
+                    tr.clear()
+                    apply_M = _make_apply(H, smoother, steps, 0.8, shape, ("forward", "backward"), **kw)
+                    for l, lev in enumerate(H.levels):               # (the Chebyshev step vectors exist now)
+                        tr.name_level(lev, "L%d" % l)
+                    for _ in range(2):
+                        tr.mark("apply")
+                        apply_M(src, dst)
+                    tag = "".join(" %s=%s" % kv for kv in kw.items())
+                    out["precond %s %s%d%s %s" % (fname, smoother, steps, tag, shape)] = tr.log
+    finally:
+        _precond.ops = saved
+    return out
+
+
+# ---- a banded Line cycle: the 25-point level of learned-like transfers -----------------------------------------------------
+def lineband_traces():
+    """prepare_smoother("Line", line_dir="x", line_band=2), a cycle, prepare_smoother(line_dir="xy"), a cycle: 33 x 33 stretched
+    operator, learned-like transfers (level 1 has 25-point rows), on the banded stand-ins of tests/line_band_ref.py."""
+    import line_band_ref as LB
+    from learnmultigrid_amd import problems as P
+    from learnmultigrid_amd.hierarchy import Hierarchy
+    from oracle import kernels as K
+    A, rhs = P.anisotropic_poisson_2d_structured(32, 1e-3, 1.0)
+    hier = LB.transfers("learned_like", side=33, levels=3)
+    out = {}
+    for shape in ("V", "W"):
+        for zero in (False, True):
+            tr = Tracer(LB.stand_in())
+            H = Hierarchy(K.as_csr(A), hier, "cpu", ops_mod=tr.ops)
+            H.levels[0].b.copy_(torch.from_numpy(rhs.ravel().copy()))
+            for l, lev in enumerate(H.levels):
+                tr.name_level(lev, "L%d" % l)
+            tr.clear()
+            H.prepare_smoother("Line", line_dir="x", line_band=2)
+            tr.mark("cycle")
+            H.cycle("Line", 1, 1.0, shape=shape, x_is_zero=zero)
+            tr.mark("prepare xy")
+            H.prepare_smoother("Line", line_dir="xy")
+            tr.mark("cycle")
+            H.cycle("Line", 1, 1.0, shape=shape, x_is_zero=zero)
+            tr.mark("bands %s key %r" % ([lev.line_band for lev in H.levels[:-1]], H.line_key()))
+            out["lineband %s zero=%d" % (shape, zero)] = tr.log
+    return out
+
+
+# ---- what a captured cycle is filed under ------------------------------------------------------------------------------------
+class _EagerGraph:
+    """Stands for ops.CapturedGraph: the launches run (and are logged) while they are 'captured'; there is no replay."""
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        return False
+
+
+# (smoother, steps, the keywords of the first captured_cycle, the one keyword changed for the second)
+GRAPH_KEYS = [("Jacobi", 2, {}, {"omega": 0.7}),
+              ("GaussSeidel", 2, {}, {"gs_sweep": ("forward", "backward")}),
+              ("Chebyshev", 2, {}, {"cheby_ratio": 8.0}),
+              ("Chebyshev", 2, {"cheby_lmax": 1.9}, {"cheby_lmax": 2.0}),
+              ("Line", 1, {}, {"line_dir": "x"}),
+              ("Line", 1, {"line_order": "jacobi"}, {"line_band": 3})]
+
+
+def graphkey_traces():
+    """The keys of Hierarchy._graphs, as strings, after prepare_smoother + captured_cycle and after a second captured_cycle
+    with one keyword changed; the launches of both are part of the trace."""
+    from learnmultigrid_amd.hierarchy import Hierarchy
+    A, rhs, hier = _problem()
+    out = {}
+    for smoother, steps, kw, change in GRAPH_KEYS:
+        tr = Tracer(trace_shim(0), CapturedGraph=_EagerGraph)
+        H = Hierarchy(A.copy(), hier, "cpu", ops_mod=tr.ops)
+        H.levels[0].b.copy_(torch.from_numpy(rhs.ravel().copy()))
+        for l, lev in enumerate(H.levels):
+            tr.name_level(lev, "L%d" % l)
+        tr.clear()
+        args = {"omega": 0.8, "gs_mode": "lexicographic", "gs_sweep": ("forward", "forward")}
+        H.prepare_smoother(smoother, **kw)
+        for l, lev in enumerate(H.levels):
+            tr.name_level(lev, "L%d" % l)
+        for more in ({}, change):
+            args.update({k: v for k, v in more.items() if k in args})
+            kw = dict(kw, **{k: v for k, v in more.items() if k not in args})
+            tr.mark("captured_cycle")
+            H.captured_cycle(smoother, steps, args["omega"], args["gs_mode"], args["gs_sweep"], "V", **kw)
+            tr.mark("keys " + " | ".join(sorted(repr(k) for k in H._graphs)))
+        tag = "".join(" %s=%s" % kv for kv in change.items())
+        out["graphkey %s%d%s" % (smoother, steps, tag)] = tr.log
+    return out
+
+
+PARTS = ("hierarchy", "dist", "operator", "precond", "lineband", "graphkey")
+
+
 def all_traces():
     here = os.path.dirname(os.path.abspath(__file__))
     for p in (here, os.path.dirname(here)):
         if p not in sys.path:
             sys.path.insert(0, p)
     out = {}
-    out.update(hierarchy_traces())
-    out.update(dist_traces())
-    out.update(operator_traces())
+    for part in PARTS:
+        out.update(globals()[part + "_traces"]())
     return out
 
 

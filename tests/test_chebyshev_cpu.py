@@ -279,13 +279,14 @@ def test_solver_keywords():
     assert eff("Chebyshev", "as_named") == "Chebyshev"
     with pytest.raises(ValueError):
         eff("Tschebyscheff", "as_named")
+    from learnmultigrid_amd.smoothing import smoother_options
     for bad in (1.0, 0.3, -2.0):
         with pytest.raises(ValueError):
-            Multigrid._check_cheby("Chebyshev", 3, bad)
+            smoother_options("Chebyshev", 3, cheby_ratio=bad)
     with pytest.raises(ValueError):
-        Multigrid._check_cheby("Chebyshev", 0, None)
-    Multigrid._check_cheby("Chebyshev", 3, 4.0)
-    Multigrid._check_cheby("GaussSeidel", 3, 0.5)                 # not the Chebyshev smoother: the keyword is not looked at
+        smoother_options("Chebyshev", 0, cheby_ratio=None)
+    assert smoother_options("Chebyshev", 3, cheby_ratio=4.0) == {"cheby_lmax": None, "cheby_ratio": 4.0}
+    assert smoother_options("GaussSeidel", 3, cheby_ratio=0.5) == {}    # not the Chebyshev smoother: the keyword is not looked at
     import inspect
     for name in ("solve", "v_cycle", "w_cycle", "f_cycle"):
         sig = inspect.signature(getattr(Multigrid, name))
@@ -317,6 +318,6 @@ def test_cg_accepts_the_name():
     from learnmultigrid_amd.solvers.CG import CG, check_smoother
     # CG.solve checks its smoother with the Krylov solvers' shared check, which knows the name (and says so to others)
     assert "check_smoother(precond_smoother, " in inspect.getsource(CG.solve)
-    check_smoother("Chebyshev", "xy", "zebra")
+    check_smoother("Chebyshev", 2, line_dir="xy", line_order="zebra")
     with pytest.raises(ValueError, match="'Chebyshev'"):
-        check_smoother("Tschebyscheff", "xy", "zebra")
+        check_smoother("Tschebyscheff", 2, line_dir="xy", line_order="zebra")

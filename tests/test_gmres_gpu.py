@@ -165,9 +165,9 @@ def test_g6_cg_still_matches_its_golden_history():
     np.testing.assert_allclose(c.get_solution(), g["solution"], rtol=1e-9, atol=1e-12)
 
 
-def inline_make_apply(H, precond_smoother, precond_steps, precond_omega, precond_cycle_shape, gs_sweep, precond_line_dir,
-                      precond_line_order):
+def inline_make_apply(H, precond_smoother, precond_steps, precond_omega, precond_cycle_shape, gs_sweep, options):
     """What CG.solve did inline before the preconditioner moved to solvers/_precond.py, kept here for the comparison."""
+    precond_line_dir, precond_line_order = options.get("line_dir"), options.get("line_order")
     assert gs_sweep == ("forward", "backward")
     if H is not None and precond_smoother == "Chebyshev":
         H.prepare_smoother("Chebyshev")

@@ -16,7 +16,7 @@ def golden():
         return launch_trace.load(f)
 
 
-@pytest.mark.parametrize("part", ["hierarchy", "dist", "operator"])
+@pytest.mark.parametrize("part", launch_trace.PARTS)
 def test_launch_traces_equal_the_recorded_ones(golden, part):
     got = getattr(launch_trace, part + "_traces")()
     want = {k: v for k, v in golden.items() if k.startswith(part + " ")}

@@ -269,16 +269,21 @@ def test_line_config():
 
 
 def test_solver_keywords():
+    from learnmultigrid_amd.smoothing import smoother_options
     from learnmultigrid_amd.solvers.Multigrid import Multigrid
     eff = Multigrid._effective_smoother
     assert eff("Line", "as_shipped") == "GaussSeidel"             # as shipped, the name is ignored: Gauss-Seidel runs
     assert eff("Line", "as_named") == "Line"
     with pytest.raises(ValueError):
-        Multigrid._check_line("Line", "yx", "zebra")
+        smoother_options("Line", 1, line_dir="yx", line_order="zebra")
     with pytest.raises(ValueError):
-        Multigrid._check_line("Line", "xy", "red-black")
-    Multigrid._check_line("Line", "x", "jacobi")
-    Multigrid._check_line("GaussSeidel", "nonsense", "nonsense")  # not the Line smoother: the keywords are not looked at
+        smoother_options("Line", 1, line_dir="xy", line_order="red-black")
+    assert smoother_options("Line", 1, line_dir="x", line_order="jacobi") == {"line_dir": "x", "line_order": "jacobi", "line_band": 1}
+    # what the solver classes mean by a keyword left out: ("xy", "zebra"), band 1; Chebyshev keeps what the hierarchy has
+    assert smoother_options("Line", 1) == {"line_dir": "xy", "line_order": "zebra", "line_band": 1}
+    assert smoother_options("Chebyshev", 1) == {"cheby_lmax": None, "cheby_ratio": None}
+    # not the Line smoother: the keywords are not looked at
+    assert smoother_options("GaussSeidel", 1, line_dir="nonsense", line_order="nonsense") == {}
     for name in ("solve", "v_cycle", "w_cycle", "f_cycle"):
         sig = inspect.signature(getattr(Multigrid, name))
         assert sig.parameters["line_dir"].kind is inspect.Parameter.KEYWORD_ONLY and sig.parameters["line_dir"].default == "xy"
