@@ -612,6 +612,12 @@ int64_t lmg_host_gs_levels(int64_t n, const int32_t *h_rowptr, const int32_t *h_
 /* Greedy natural-order colouring of A + A^T; returns the number of colours. */
 int64_t lmg_host_greedy_colors(int64_t n, const int32_t *h_rowptr, const int32_t *h_colidx,
                                int32_t *h_color_out);
+/* The C/F split of NeuralMG_2D.coarsening (Multigrid.py:401-426, which walks a dense n x n copy of the mass matrix
+ * and rebuilds Python sets per node): node i is coarse iff no coarse c < i has A[c][i] > 0 -- row c, so an unsymmetric
+ * pattern is taken as it stands.  The lexicographically first maximal independent set, sequential, O(nnz).
+ * h_is_coarse_out[i] = 1 | 0; returns the number of coarse nodes or a negative lmg_status. */
+int64_t lmg_host_greedy_cf(int64_t n, const int32_t *h_rowptr, const int32_t *h_colidx, const double *h_vals,
+                           int32_t *h_is_coarse_out);
 
 /* ---- vectors --------------------------------------------------------------------*/
 int lmg_axpby(int64_t n, double alpha, const double *d_x, double beta, double *d_y, void *stream);
@@ -891,6 +897,57 @@ int lmg_l2_coupling_count(int64_t nf, int64_t nc, const double *d_xf, const doub
                           void *stream);
 int lmg_l2_coupling_fill(int kind, int64_t nf, int64_t nc, const double *d_xf, const double *d_xc,
                          const int32_t *d_rowptr, int32_t *d_colidx, double *d_vals, void *stream);
+
+/* ---- 2-D learned transfers: what NeuralMG_2D.define_hierarchy does around model.predict ---------------------
+ * (Multigrid.py:373-765; the rules: DESIGN.md section 3.)  M: sorted CSR, device.  d_status: ONE 64-bit word the
+ * caller sets to UINT64_MAX before a stage and reads after it; a lane that has to refuse writes
+ * (order << 8 | rule) with an atomic minimum and leaves, so the word names the first offender: `order` is the row
+ * (check), the position among the coarse nodes (count) or the patch (patches, contrib). */
+typedef enum {
+    LMG_NMG2D_NEGATIVE = 1, /* a negative off-diagonal entry                               */
+    LMG_NMG2D_DIAGONAL = 2, /* no positive diagonal entry                                  */
+    LMG_NMG2D_VALENCE = 3,  /* a coarse node with 8 or more positive neighbours            */
+    LMG_NMG2D_FEW = 4,      /* a coarse node with fewer than 2 neighbours                  */
+    LMG_NMG2D_ISOLATED = 5, /* a neighbour whose only positive neighbour is the coarse node */
+    LMG_NMG2D_SECOND = 6,   /* more than 6 coarse second neighbours                        */
+    LMG_NMG2D_COLUMN = 7    /* an index outside the matrix / a fill index that is not coarse */
+} lmg_nmg2d_rule;
+/* The domain of the rules, whole matrix, one lane per row: every column inside [0, n), no negative off-diagonal
+ * entry, a positive diagonal.  (The reference misaligns `row.nonzero()` and `row[row > 0]` outside it, :634-636.) */
+int lmg_nmg2d_check(int64_t n, const int32_t *d_rowptr, const int32_t *d_colidx, const double *d_vals,
+                    uint64_t *d_status, void *stream);
+/* d_extra[r] = 1 if coarse node d_coarse_nodes[r] has 7 positive neighbours (it gets a second patch), else 0; 8 and
+ * more are refused (the first loop of extract_patches, :607-615, whose "works only if neighs are 6 + 1" this is). */
+int lmg_nmg2d_count(int64_t nc, const int32_t *d_coarse_nodes, const int32_t *d_rowptr, const int32_t *d_colidx,
+                    const double *d_vals, int32_t *d_extra, uint64_t *d_status, void *stream);
+/* One lane per patch: d_patches[npatch][43] and d_fill_idx[npatch][31] of coarse node d_patch_node[j], leaving out
+ * the d_patch_variant[j]-th smallest neighbour (0 | 1) where the node has 7.  d_rank[n]: position among the coarse
+ * nodes, -1 for fine ones.  Replaces extract_patches / single_extraction / direct_neighs / intersecting_rows /
+ * create_virtual_nodes (:438-677), which copy and edit one lil row per visit. */
+int lmg_nmg2d_patches(int64_t npatch, const int32_t *d_patch_node, const int32_t *d_patch_variant, int64_t n,
+                      const int32_t *d_rowptr, const int32_t *d_colidx, const double *d_vals, const int32_t *d_rank,
+                      double *d_patches, int32_t *d_fill_idx, uint64_t *d_status, void *stream);
+/* fill_B (:687-732) without the dense n x n_c array, in three steps.  contrib: d_keys[j * 31 + t] = row * nc + col
+ * of the entry of B that slot t of patch j is folded into, INT64_MAX for an empty slot.  The caller sorts the keys
+ * STABLY (d_slot: the permutation) and finds where the runs of equal keys start (d_start[nentries + 1]).
+ * fold: one lane per distinct entry walks its run -- patch order, the order of :691 -- with cur = p if cur == 0 else
+ * (cur + p) / 2 (:710-728), p = d_res[slot], and writes the entry as (row, col, val), rows and columns ascending. */
+int lmg_nmg2d_contrib(int64_t npatch, int64_t n, int64_t nc, const int32_t *d_fill_idx, const int32_t *d_rank,
+                      int64_t *d_keys, uint64_t *d_status, void *stream);
+int lmg_nmg2d_fold(int64_t nentries, const int64_t *d_start, const int64_t *d_keys, const int64_t *d_slot,
+                   const double *d_res, int64_t nc, int32_t *d_row, int32_t *d_col, double *d_val, void *stream);
+/* Q = B with every row divided by its sum, taken in storage order (:758-759 on CSR values; q may be b). */
+int lmg_nmg2d_normalize(int64_t n, const int32_t *d_rowptr, const double *d_b_vals, double *d_q_vals, void *stream);
+/* d_neighs[nc][6], padded with -1: the coarse positions of fill_idx[7:13] of patch d_last_patch[r] (:704-707). */
+int lmg_nmg2d_dneighs(int64_t nc, const int32_t *d_last_patch, const int32_t *d_fill_idx, const int32_t *d_rank,
+                      int32_t *d_neighs, void *stream);
+/* pre_process (:735-739): entry (i, j) of the coarse mass matrix stays iff j == i or j is in d_neighs[i].  mark
+ * counts the kept entries per row; the caller scans them into d_cut_rowptr (lmg_exclusive_scan_i32); fill compacts. */
+int lmg_nmg2d_cut_mark(int64_t n, const int32_t *d_rowptr, const int32_t *d_colidx, const int32_t *d_neighs,
+                       int32_t *d_rownnz, void *stream);
+int lmg_nmg2d_cut_fill(int64_t n, const int32_t *d_rowptr, const int32_t *d_colidx, const double *d_vals,
+                       const int32_t *d_neighs, const int32_t *d_cut_rowptr, int32_t *d_cut_colidx,
+                       double *d_cut_vals, void *stream);
 
 /* ---- hipGraph capture of a launch sequence (one V-cycle) -----------------------------
  * begin/end bracket launches issued on `stream`; end returns an opaque executable graph. */

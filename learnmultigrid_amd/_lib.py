@@ -107,6 +107,7 @@ SIGNATURES = {
     "lmg_stencil_gs_sweep_backward": (_c.c_int, [_i64, _i32, _p, _i32, _p, _p, _c.c_uint32, _i32, _p, _p, _p, _p, _c.c_int, _p]),
     "lmg_host_gs_levels": (_i64, [_i64, _p, _p, _p]),
     "lmg_host_greedy_colors": (_i64, [_i64, _p, _p, _p]),
+    "lmg_host_greedy_cf": (_i64, [_i64, _p, _p, _p, _p]),
     "lmg_axpby": (_c.c_int, [_i64, _f64, _p, _f64, _p, _p]),
     "lmg_vmul": (_c.c_int, [_i64, _f64, _p, _p, _p, _p]),
     "lmg_copy": (_c.c_int, [_i64, _p, _p, _p]),
@@ -151,6 +152,15 @@ SIGNATURES = {
     "lmg_p1_assemble_2d": (_c.c_int, [_i64, _p, _p, _p, _p, _p, _p, _p, _f64, _p, _p, _p, _p, _p, _p]),
     "lmg_l2_coupling_count": (_c.c_int, [_i64, _i64, _p, _p, _p, _p]),
     "lmg_l2_coupling_fill": (_c.c_int, [_c.c_int, _i64, _i64, _p, _p, _p, _p, _p, _p]),
+    "lmg_nmg2d_check": (_c.c_int, [_i64, _p, _p, _p, _p, _p]),
+    "lmg_nmg2d_count": (_c.c_int, [_i64, _p, _p, _p, _p, _p, _p, _p]),
+    "lmg_nmg2d_patches": (_c.c_int, [_i64, _p, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "lmg_nmg2d_contrib": (_c.c_int, [_i64, _i64, _i64, _p, _p, _p, _p, _p]),
+    "lmg_nmg2d_fold": (_c.c_int, [_i64, _p, _p, _p, _p, _i64, _p, _p, _p, _p]),
+    "lmg_nmg2d_normalize": (_c.c_int, [_i64, _p, _p, _p, _p]),
+    "lmg_nmg2d_dneighs": (_c.c_int, [_i64, _p, _p, _p, _p, _p]),
+    "lmg_nmg2d_cut_mark": (_c.c_int, [_i64, _p, _p, _p, _p, _p]),
+    "lmg_nmg2d_cut_fill": (_c.c_int, [_i64, _p, _p, _p, _p, _p, _p, _p, _p]),
     "lmg_graph_begin": (_c.c_int, [_p]),
     "lmg_graph_end": (_c.c_int, [_p, _c.POINTER(_p)]),
     "lmg_graph_launch": (_c.c_int, [_p, _p]),

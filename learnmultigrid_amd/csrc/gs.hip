@@ -393,4 +393,23 @@ int64_t lmg_host_greedy_colors(int64_t n, const int32_t *Ap, const int32_t *Aj, 
     return ncol;
 }
 
+int64_t lmg_host_greedy_cf(int64_t n, const int32_t *Ap, const int32_t *Aj, const double *Av, int32_t *is_coarse)
+{
+    if (n < 0 || !Ap || (n > 0 && !is_coarse)) return LMG_ERR_ARG;
+    if (n == 0) return 0;
+    if (Ap[n] > 0 && (!Aj || !Av)) return LMG_ERR_ARG;
+    // is_coarse doubles as the mark: 1 until a coarse node before it reaches it through its own row
+    for (int64_t i = 0; i < n; ++i) is_coarse[i] = 1;
+    int64_t nc = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        if (!is_coarse[i]) continue;
+        ++nc;
+        for (int32_t k = Ap[i]; k < Ap[i + 1]; ++k) {
+            const int32_t j = Aj[k];
+            if (j > i && j < n && Av[k] > 0.0) is_coarse[j] = 0;
+        }
+    }
+    return nc;
+}
+
 }  // extern "C"

@@ -1476,6 +1476,116 @@ def spgemm(A, B):
     return SpGEMMPlan(A, B).numeric(A, B)
 
 
+# ---- 2-D learned transfers (csrc/nmg2d.hip; the stages: learned_q2d.py) -----------------------
+NMG2D_RULES = {1: "negative_offdiagonal", 2: "diagonal", 3: "valence", 4: "few_neighbours", 5: "isolated_neighbour",
+               6: "second_neighbours", 7: "index_range"}        # lmg_nmg2d_rule
+
+
+def host_greedy_cf(A):
+    """is_coarse (int32, n) of the SciPy CSR matrix A by lmg_host_greedy_cf: node i is coarse iff no coarse c < i has
+    A[c, i] > 0."""
+    rp, ci = np.ascontiguousarray(A.indptr, dtype=np.int32), np.ascontiguousarray(A.indices, dtype=np.int32)
+    va = np.ascontiguousarray(A.data, dtype=np.float64)
+    out = np.empty(A.shape[0], dtype=np.int32)
+    check(_lib.lib().lmg_host_greedy_cf(A.shape[0], rp.ctypes.data, ci.ctypes.data, va.ctypes.data, out.ctypes.data),
+          "lmg_host_greedy_cf")
+    return out
+
+
+def nmg2d_status(device):
+    """The status word of one stage, set to "nothing refused" (all bits)."""
+    return torch.full((1,), -1, dtype=torch.int64, device=device)
+
+
+def nmg2d_read_status(status):
+    """None, or (rule name, order) of the first refusal: one read back (it synchronises)."""
+    word = int(status.item())
+    return None if word == -1 else (NMG2D_RULES.get(word & 0xFF, "rule %d" % (word & 0xFF)), word >> 8)
+
+
+def _i32_ok(*ts):
+    for t in ts:
+        if t.dtype != I32 or not t.is_contiguous() or not t.is_cuda:
+            raise TypeError("expected contiguous int32 device tensors, got %s %s" % (t.dtype, t.device))
+
+
+def nmg2d_check(A, status):
+    check(_lib.lib().lmg_nmg2d_check(A.shape[0], _p(A.rowptr), _p(A.colidx), _p(A.vals), _p(status), _s(A.vals)),
+          "lmg_nmg2d_check")
+
+
+def nmg2d_count(A, coarse_nodes, extra, status):
+    _i32_ok(coarse_nodes, extra)
+    if extra.numel() != coarse_nodes.numel():
+        raise ValueError("extra must have one entry per coarse node")
+    check(_lib.lib().lmg_nmg2d_count(coarse_nodes.numel(), _p(coarse_nodes), _p(A.rowptr), _p(A.colidx), _p(A.vals),
+                                     _p(extra), _p(status), _s(A.vals)), "lmg_nmg2d_count")
+
+
+def nmg2d_patches(A, patch_node, patch_variant, rank, patches, fill_idx, status):
+    _i32_ok(patch_node, patch_variant, rank, fill_idx)
+    _vec_ok(patches)
+    p = patch_node.numel()
+    if patch_variant.numel() != p or rank.numel() != A.shape[0] or patches.numel() != 43 * p or fill_idx.numel() != 31 * p:
+        raise ValueError("nmg2d_patches: inconsistent array sizes")
+    check(_lib.lib().lmg_nmg2d_patches(p, _p(patch_node), _p(patch_variant), A.shape[0], _p(A.rowptr), _p(A.colidx),
+                                       _p(A.vals), _p(rank), _p(patches), _p(fill_idx), _p(status), _s(A.vals)),
+          "lmg_nmg2d_patches")
+
+
+def nmg2d_contrib(nc, fill_idx, rank, keys, status):
+    _i32_ok(fill_idx, rank)
+    p = fill_idx.numel() // 31
+    if fill_idx.numel() != 31 * p or keys.dtype != torch.int64 or keys.numel() != 31 * p or not keys.is_contiguous():
+        raise ValueError("nmg2d_contrib: inconsistent array sizes")
+    check(_lib.lib().lmg_nmg2d_contrib(p, rank.numel(), nc, _p(fill_idx), _p(rank), _p(keys), _p(status), _s(fill_idx)),
+          "lmg_nmg2d_contrib")
+
+
+def nmg2d_fold(start, keys, slot, res, nc, row, col, val):
+    _i32_ok(row, col)
+    _vec_ok(res, val)
+    ne = start.numel() - 1
+    if (start.dtype, keys.dtype, slot.dtype) != (torch.int64,) * 3 or min(row.numel(), col.numel(), val.numel()) < ne \
+            or keys.numel() != slot.numel() or res.numel() != keys.numel():
+        raise ValueError("nmg2d_fold: inconsistent arrays")
+    check(_lib.lib().lmg_nmg2d_fold(ne, _p(start.contiguous()), _p(keys.contiguous()), _p(slot.contiguous()), _p(res), nc,
+                                    _p(row), _p(col), _p(val), _s(res)), "lmg_nmg2d_fold")
+
+
+def nmg2d_normalize(B):
+    """Q: the DeviceCSR B with every row divided by its sum (pattern arrays shared with B)."""
+    q = torch.empty_like(B.vals)
+    check(_lib.lib().lmg_nmg2d_normalize(B.shape[0], _p(B.rowptr), _p(B.vals), _p(q), _s(B.vals)), "lmg_nmg2d_normalize")
+    return DeviceCSR(B.rowptr, B.colidx, q, B.shape)
+
+
+def nmg2d_dneighs(last_patch, fill_idx, rank, d_neighs):
+    _i32_ok(last_patch, fill_idx, rank, d_neighs)
+    nc = last_patch.numel()
+    if d_neighs.numel() != 6 * nc or fill_idx.numel() % 31:
+        raise ValueError("nmg2d_dneighs: inconsistent array sizes")
+    check(_lib.lib().lmg_nmg2d_dneighs(nc, _p(last_patch), _p(fill_idx), _p(rank), _p(d_neighs), _s(rank)), "lmg_nmg2d_dneighs")
+
+
+def nmg2d_cut(A, d_neighs):
+    """The DeviceCSR A without the entries (i, j) with j != i and j not in d_neighs[i] ((n, 6) int32, padded with -1)."""
+    _i32_ok(d_neighs)
+    n = A.shape[0]
+    if d_neighs.numel() != 6 * n:
+        raise ValueError("d_neighs must be (n, 6)")
+    L, dev = _lib.lib(), A.device
+    rownnz = torch.empty(max(n, 1), dtype=I32, device=dev)
+    check(L.lmg_nmg2d_cut_mark(n, _p(A.rowptr), _p(A.colidx), _p(d_neighs), _p(rownnz), _s(A.vals)), "lmg_nmg2d_cut_mark")
+    rp = torch.empty(n + 1, dtype=I32, device=dev)
+    exclusive_scan_i32(rownnz[:n], rp)
+    nnz = int(rp[-1].item())
+    cj, cv = torch.empty(nnz, dtype=I32, device=dev), torch.empty(nnz, dtype=F64, device=dev)
+    check(L.lmg_nmg2d_cut_fill(n, _p(A.rowptr), _p(A.colidx), _p(A.vals), _p(d_neighs), _p(rp), _p(cj), _p(cv), _s(A.vals)),
+          "lmg_nmg2d_cut_fill")
+    return DeviceCSR(rp, cj, cv, A.shape)
+
+
 # ---- hipGraph ---------------------------------------------------------------------------------
 class CapturedGraph:
     """A launch sequence captured on the current stream (lmg_graph_*), replayable."""

@@ -400,3 +400,145 @@ class NeuralMG(Multigrid):
             dM = ops.DeviceCSR.from_scipy(M, self._device)
             M = ops.spgemm(ops.spgemm(dQ.transpose(), dM), dQ).to_scipy()
         return out
+
+
+class NeuralMG_2D(Multigrid):
+    """Multigrid.py:373-765: `NeuralMG_2D(matrix, rhs, model, M, std, mean)`, the 2-D learned multigrid.
+    define_hierarchy(levels) builds l_hierarchy, one transfer operator Q_l per coarsening (SciPy CSR, unit row sums), from
+    the mass matrix M and the caller's model -- any object with `predict(ndarray (p, 43)) -> ndarray (p, 31)` -- on the
+    device (learned_q2d.py, csrc/nmg2d.hip; the rules: DESIGN.md section 3).  The stages are callable one at a time under
+    the reference's names, argument orders and result shapes, on host arrays.
+    Deviations, all declared: solve() runs its cycles on l_hierarchy (the reference inherits
+    Multigrid.solve, which asks the 1-D geometric interpolator and never reads l_hierarchy); fill_B returns B as CSR, not
+    dense; matrices go in and out as CSR, not lil; a mass matrix the rules cannot take is refused with a ValueError
+    (learned_q2d.Refused: .rule, .node) where the reference crashes late or corrupts its patches silently."""
+
+    def __init__(self, matrix, rhs, model, M, std, mean, **kw):
+        super().__init__(matrix, rhs, **kw)
+        self._log("Selected 2D Neural Multigrid")
+        self.label = "NeuralMG"                                              # :378
+        self.model, self.M, self.std, self.mean = model, M, std, mean
+        self.l_hierarchy = []
+        self.setup_timings = {}            # seconds per stage of the last define_hierarchy(..., timed=True)
+
+    # -- the stages (:400-739) ------------------------------------------------------------------
+    @staticmethod
+    def coarsening(M):
+        """(CC, FF, CC_neighs, FF_neighs) of :401-426: the coarse and the fine nodes, both ascending, and per node the
+        index array of its positive neighbours."""
+        from .. import learned_q2d as L
+        M = L.canonical(M)
+        CC, rank = L.cf_split(M)
+        rows = np.repeat(np.arange(M.shape[0]), np.diff(M.indptr))
+        off = (M.data > 0) & (M.indices != rows)
+        neighs = np.split(M.indices[off].astype(np.int64), np.cumsum(np.bincount(rows[off], minlength=M.shape[0]))[:-1])
+        FF = np.flatnonzero(rank < 0)
+        return ([int(c) for c in CC], [int(f) for f in FF], {int(c): neighs[c] for c in CC}, {int(f): neighs[f] for f in FF})
+
+    @staticmethod
+    def map_coarse(C):
+        """{coarse node: its position among the coarse nodes} (:680-684)."""
+        return dict(zip((int(c) for c in C), range(len(C))))
+
+    def _checked_mass(self, M):
+        from .. import learned_q2d as L
+        host = L.canonical(M)
+        dM = ops.DeviceCSR.from_scipy(host, self._device)
+        L.check_domain(dM)
+        return host, dM
+
+    @on_device
+    def extract_patches(self, CC, M):
+        """(patches (p, 43) float64, fill_idxs (p, 31) int64) of :591-677: the first patch of every coarse node at the
+        node's position in CC, the second patches of the nodes with 7 neighbours after them."""
+        from .. import learned_q2d as L
+        host, dM = self._checked_mass(M)
+        rank = L.rank_of(CC, host.shape[0])
+        dCC = torch.from_numpy(np.asarray(CC, dtype=np.int32).reshape(-1)).to(self._device)
+        P = L.extract_patches(dM, dCC, torch.from_numpy(rank).to(self._device))
+        return P.patches.cpu().numpy(), P.fill_idx.cpu().numpy().astype(np.int64)
+
+    @on_device
+    def fill_B(self, res, idx_fill, total_size, mapping, CC):
+        """(B, d_neighs) of :687-732: B (total_size x len(CC)) as SciPy CSR, and {coarse position: the coarse positions
+        of its coarse second neighbours}.  `mapping` must be map_coarse(CC); the patches must be placed as
+        extract_patches places them."""
+        from .. import learned_q2d as L
+        CC = np.asarray(CC, dtype=np.int64).reshape(-1)
+        nc = CC.size
+        idx = np.ascontiguousarray(np.asarray(idx_fill), dtype=np.int64).reshape(-1, 31)
+        res = np.ascontiguousarray(np.asarray(res, dtype=np.float64)).reshape(-1, 31)
+        rank = L.rank_of(CC, int(total_size))
+        if len(mapping) != nc or any(mapping.get(int(c)) != r for r, c in enumerate(CC)):
+            raise ValueError("NeuralMG_2D.fill_B: mapping is not map_coarse(CC)")
+        if idx.shape[0] < nc or res.shape[0] != idx.shape[0] or not np.array_equal(idx[:nc, 0], CC) \
+                or idx.min() < -1 or idx.max() >= total_size or np.any(rank[idx[nc:, 0]] < 0) \
+                or np.unique(idx[nc:, 0]).size != idx.shape[0] - nc:
+            raise ValueError("NeuralMG_2D.fill_B: patch j < len(CC) must belong to CC[j], each later one to a coarse node "
+                             "of its own, and every index must lie in [-1, total_size)")
+        last = np.arange(nc, dtype=np.int32)
+        last[rank[idx[nc:, 0]]] = np.arange(nc, idx.shape[0], dtype=np.int32)
+        dev = self._device
+        dB, dn = L.fill_B(torch.from_numpy(res).to(dev), torch.from_numpy(idx.astype(np.int32)).to(dev),
+                          torch.from_numpy(last).to(dev), torch.from_numpy(rank).to(dev), nc)
+        dn = dn.cpu().numpy()
+        return dB.to_scipy(), {r: dn[r][dn[r] >= 0].astype(np.int64) for r in range(nc)}
+
+    @on_device
+    def pre_process(self, mass, d_neighs):
+        """The coarse mass matrix without the entries (i, j), j != i, j not in d_neighs[i] (:735-739), as SciPy CSR.
+        d_neighs: fill_B's dict, or an (n, 6) integer array padded with -1."""
+        from .. import learned_q2d as L
+        host = L.canonical(mass)
+        n = host.shape[0]
+        if isinstance(d_neighs, dict):
+            dn = np.full((n, 6), -1, dtype=np.int32)
+            for i in range(n):
+                row = np.asarray(d_neighs[i], dtype=np.int32).reshape(-1)
+                if row.size > 6:
+                    raise ValueError("NeuralMG_2D.pre_process: d_neighs[%d] has more than 6 entries" % i)
+                dn[i, :row.size] = row
+        else:
+            dn = np.ascontiguousarray(np.asarray(d_neighs), dtype=np.int32)
+            if dn.shape != (n, 6):
+                raise ValueError("NeuralMG_2D.pre_process: d_neighs must be (%d, 6), got %s" % (n, dn.shape))
+        dM = ops.DeviceCSR.from_scipy(host, self._device)
+        return ops.nmg2d_cut(dM, torch.from_numpy(dn).to(self._device)).to_scipy()
+
+    # -- :741-765 -------------------------------------------------------------------------------
+    @on_device
+    def define_hierarchy(self, levels=2, timed=False):
+        """Sets l_hierarchy to the levels - 1 operators Q_l.  timed=True: setup_timings receives the seconds per stage."""
+        from ..learned_q2d import define_hierarchy
+        if levels == 1:
+            self._log("Coarse grid correction not required")               # :743-744
+            return
+        if levels < 1:
+            raise ValueError("levels must be >= 1 (levels counts grids)")
+        self.setup_timings = {} if timed else self.setup_timings
+        self.l_hierarchy = define_hierarchy(self.model, self.M, self.mean, self.std, levels, self._device,
+                                            timings=self.setup_timings if timed else None)
+        self.hierarchy = self.l_hierarchy
+        self._hier = None
+
+    def _levels(self, levels):
+        if not self.l_hierarchy:
+            self.define_hierarchy(2 if levels is None else levels)
+        have = len(self.l_hierarchy) + 1
+        if levels is not None and levels != have:
+            raise ValueError("levels=%d, but the hierarchy that is defined has %d (define_hierarchy(levels) builds another)"
+                             % (levels, have))
+        self.hierarchy = self.l_hierarchy
+        return have
+
+    _FIRST_CALL = True
+
+    def solve(self, levels=None, smoother="Jacobi", smooth_steps=1, max_iterations=100, error=1e-08,
+              initial_guess=None, cycle="V", first_call=True, **kw):
+        """The cycles of HierarchyMG(matrix, rhs, l_hierarchy) with Multigrid.solve's keywords; levels None: the levels of
+        the hierarchy that is defined (define_hierarchy(2) if none is); another number: ValueError."""
+        super().solve(self._levels(levels), smoother, smooth_steps, max_iterations, error, initial_guess, cycle,
+                      first_call, **kw)
+
+    def solve_many(self, rhs, levels=None, *args, **kw):
+        return super().solve_many(rhs, self._levels(levels), *args, **kw)
