@@ -15,7 +15,7 @@ import math
 
 import torch
 
-from .hierarchy import cycle_children
+from .hierarchy import capture_cycle, cycle_children
 from .ops import F64
 
 
@@ -186,12 +186,5 @@ class BlockCycle:
         g = self._graphs.get(key)
         if g is None:
             cycle_children(shape)
-            before = [(bl.x, bl.tmp) for bl in self.levels]
-            g = self.ops.CapturedGraph()
-            with g:
-                self.cycle(steps, omega, shape)
-            for bl, (x, tmp) in zip(self.levels, before):
-                if bl.x is not x or bl.tmp is not tmp:
-                    raise RuntimeError("ping-pong buffers did not return to their slots")
-            self._graphs[key] = g
+            g = self._graphs[key] = capture_cycle(self.ops, self.levels, lambda: self.cycle(steps, omega, shape))
         return g

@@ -60,6 +60,7 @@ import torch
 import torch.distributed as dist
 
 from . import smoothing
+from .hierarchy import Hierarchy, capture_cycle
 from .ops import DeviceCSR, F64, I32
 
 _UNREACHED = 1 << 20           # _layer_of: "in none of the layers" (deeper than any halo)
@@ -250,7 +251,6 @@ class DistributedVCycle:
 
     @classmethod
     def from_problem(cls, A, transfers, device, ops_mod=None, **kw):
-        from .hierarchy import Hierarchy
         return cls(Hierarchy(A, transfers, device, ops_mod=ops_mod), device, ops_mod=ops_mod, **kw)
 
     # ---- setup, in the order __init__ runs it ----------------------------------------------------------
@@ -668,14 +668,7 @@ class DistributedVCycle:
             prep = getattr(self.full, "prepare_smoother", None)
             if prep is not None:
                 prep(smoother, "lexicographic", l)               # (device -> host reads, allocations: not inside a capture)
-            before = [(lev.x, lev.tmp) for lev in self.full.levels]
-            g = self.ops.CapturedGraph()
-            with g:
-                run()
-            after = [(lev.x, lev.tmp) for lev in self.full.levels]
-            if any(a[0] is not b[0] for a, b in zip(before, after)):
-                raise RuntimeError("ping-pong buffers did not return to their slots")
-            self._tail_graphs[key] = g
+            g = self._tail_graphs[key] = capture_cycle(self.ops, self.full.levels, run)
         g.launch()
 
     def rebuild_numeric(self, new_vals):

@@ -39,6 +39,24 @@ def cycle_children(shape):
     return _CHILDREN[shape]
 
 
+def capture_cycle(ops_mod, levels, run, swap_from=None):
+    """The launches of run() captured into an ops_mod.CapturedGraph (a hipGraph), which is returned.  They hold the addresses
+    of the ping-pong buffers x and tmp of `levels`, so afterwards every level must hold the tensors it held, in their
+    slots.  From level swap_from on (None: nowhere) the two may have changed places: a coarse level's first visit starts
+    from a zero iterate and never reads x, so a graph does not depend on where that level's iterate starts -- with
+    turnaround passes (W- and F-cycles) it may end in the other buffer -- and the two are put back."""
+    before = [(lev.x, lev.tmp) for lev in levels]
+    g = ops_mod.CapturedGraph()
+    with g:
+        run()
+    for l, (lev, (x, tmp)) in enumerate(zip(levels, before)):
+        swapped = swap_from is not None and l >= swap_from and lev.x is tmp and lev.tmp is x
+        if not swapped and (lev.x is not x or lev.tmp is not tmp):
+            raise RuntimeError("ping-pong buffers did not return to their slots")
+        lev.x, lev.tmp = x, tmp
+    return g
+
+
 # the ops predicates of the fused Chebyshev passes, by the Jacobi predicate each stands in for (Hierarchy._ask)
 CHEBY_TWIN = {"stencil_smooth_available": "stencil_cheby_available",
               "stencil_smooth_prolong_available": "stencil_cheby_prolong_available",
@@ -737,19 +755,8 @@ class Hierarchy:
         g = self._graphs.get(key)
         if g is None:
             self.prepare_smoother(smoother, gs_mode, gs_sweep=pair)
-            before = [(lev.x, lev.tmp) for lev in self.levels]
-            g = self.ops.CapturedGraph()
-            with g:
-                self.cycle(smoother, steps, omega, gs_mode, gs_sweep=pair, shape=shape)
-            if self.levels[0].x is not before[0][0]:
-                raise RuntimeError("ping-pong buffers did not return to their slots")
-            # a coarse level's first visit starts from a zero iterate, never reading x: a level with turnaround passes
-            # (W- and F-cycles) may end in the other buffer, the graph does not depend on where its iterate starts
-            for lev, (x, tmp) in zip(self.levels, before):
-                if {id(lev.x), id(lev.tmp)} != {id(x), id(tmp)}:
-                    raise RuntimeError("ping-pong buffers did not return to their slots")
-                lev.x, lev.tmp = x, tmp
-            self._graphs[key] = g
+            g = self._graphs[key] = capture_cycle(self.ops, self.levels, swap_from=1, run=lambda: self.cycle(
+                smoother, steps, omega, gs_mode, gs_sweep=pair, shape=shape))
         return g
 
     def twin_bytes(self):

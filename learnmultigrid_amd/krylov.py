@@ -25,6 +25,54 @@ from .block import block_width
 F64 = torch.float64
 
 
+class Arnoldi:
+    """The least-squares problem of one column in one restart cycle, on the host: the Givens rotations (cs, sn) that keep
+    the Hessenberg matrix triangular (R, column by column: R[c][r] = entry (r, c)) and the rotated right-hand side g, which
+    starts as [beta]."""
+
+    def __init__(self, beta):
+        self.cs, self.sn, self.R, self.g = [], [], [], [beta]
+
+    def step(self, h, hn):
+        """Step j = len(R): h holds the j + 1 sums h1[i] + h2[i] of CGS2, hn = |w|.  Returns the estimate |g_(j+1)|."""
+        cs, sn, g = self.cs, self.sn, self.g
+        j = len(self.R)
+        for i in range(j):                                               # the rotations of the earlier steps
+            t = cs[i] * h[i] + sn[i] * h[i + 1]
+            h[i + 1] = -sn[i] * h[i] + cs[i] * h[i + 1]
+            h[i] = t
+        d = math.hypot(h[j], hn)
+        c, sj = (1.0, 0.0) if d == 0.0 else (h[j] / d, hn / d)
+        h[j] = c * h[j] + sj * hn
+        cs.append(c)
+        sn.append(sj)
+        g.append(-sj * g[j])
+        g[j] = c * g[j]
+        self.R.append(h)
+        return abs(g[j + 1])
+
+    def solution(self):
+        """y of R y = g[:k] for the k steps taken; a zero pivot gives y[i] = 0.0."""
+        R, k = self.R, len(self.R)
+        y = [0.0] * k
+        for i in range(k - 1, -1, -1):
+            t = self.g[i]
+            for c in range(i + 1, k):
+                t -= R[c][i] * y[c]
+            y[i] = t / R[i][i] if R[i][i] != 0.0 else 0.0
+        return y
+
+
+def _check_blocks(name, ops_mod, bc, B, X, ncols):
+    """(n, k) of the blocks of block_pcg / block_fgmres, which the width, B, ncols and the BlockCycle must fit (ValueError)."""
+    n, k = X.shape
+    if k not in tuple(ops_mod.BLOCK_WIDTHS) or B.shape != X.shape or not 1 <= ncols <= k:
+        raise ValueError("%s: blocks %s / %s with %r columns in use" % (name, tuple(B.shape), tuple(X.shape), ncols))
+    if bc is not None and (bc.k != k or bc.levels[0].n != n):
+        raise ValueError("%s: the preconditioner works on (%d, %d) blocks, not (%d, %d)" % (name, bc.levels[0].n, bc.k, n, k))
+    return n, k
+
+
 def block_pcg(ops_mod, A, bc, B, X, *, ncols, max_iterations, error, steps=2, omega=0.8, shape="V", use_graph=False):
     """Preconditioned conjugate gradients on the columns 0 .. ncols-1 of the (n, k) blocks B and X, k in
     ops_mod.BLOCK_WIDTHS: A X = B from the iterate in X, which is updated in place.  A is the fine operator's block twin
@@ -42,11 +90,7 @@ def block_pcg(ops_mod, A, bc, B, X, *, ncols, max_iterations, error, steps=2, om
     Returns (track, iterations): track is a list of rows of ncols floats -- row 0 the true ||b_j - A x_j||, then per
     iteration sqrt(rr_j), NaN for a column that was frozen before that iteration; iterations[j] counts the iterations
     column j took part in.  The loop ends when every column is frozen or after max_iterations."""
-    n, k = X.shape
-    if k not in tuple(ops_mod.BLOCK_WIDTHS) or B.shape != X.shape or not 1 <= ncols <= k:
-        raise ValueError("block_pcg: blocks %s / %s with %r columns in use" % (tuple(B.shape), tuple(X.shape), ncols))
-    if bc is not None and (bc.k != k or bc.levels[0].n != n):
-        raise ValueError("block_pcg: the preconditioner works on (%d, %d) blocks, not (%d, %d)" % (bc.levels[0].n, bc.k, n, k))
+    n, k = _check_blocks("block_pcg", ops_mod, bc, B, X, ncols)
     dev = X.device
     R, P, AP = (torch.zeros((n, k), dtype=F64, device=dev) for _ in range(3))
     part = torch.empty(max(ops_mod.block_partials_count(n, k), ops_mod.block_dot_partials_count(n, k)), dtype=F64, device=dev)
@@ -92,11 +136,13 @@ def block_pcg(ops_mod, A, bc, B, X, *, ncols, max_iterations, error, steps=2, om
     return track, its
 
 
-def _columns_in_chunks(ops_mod, block_cycle, B, X0, device, solve_chunk):
+def columns_in_chunks(ops_mod, block_cycle, B, X0, device, solve_chunk, in_cycle=False):
     """The m >= 1 columns of the NumPy array B (n, m) from X0 (None: zero) in chunks of the widest block, each padded with
     zero columns to the narrowest width that holds it (block.block_width).  block_cycle(mc) returns the BlockCycle that
     preconditions a chunk of mc columns, ready for them (use_columns), or None: no preconditioner.  solve_chunk(bc, Bk, Xk, mc)
     solves the chunk in the (n, k) blocks Bk, Xk and returns (rows, iterations): rows of mc floats, mc iteration counts.
+    in_cycle: Bk and Xk are the cycle's own fine blocks, which use_columns has cleared (nothing is allocated here), and the
+    solution is its levels[0].x after the solve, whichever of the two iterate buffers that is by then.
     Returns (X, track, iterations) as NumPy arrays: track has as many rows as the longest chunk returned, NaN where a chunk
     returned fewer.  A padding column that is not zero afterwards is an error."""
     widths = tuple(ops_mod.BLOCK_WIDTHS)
@@ -105,34 +151,31 @@ def _columns_in_chunks(ops_mod, block_cycle, B, X0, device, solve_chunk):
     tracks, its = [], np.zeros(m, dtype=np.int64)
     for c0 in range(0, m, widths[-1]):
         mc = min(widths[-1], m - c0)
-        k = block_width(mc, widths)
         bc = block_cycle(mc)
-        Bk, Xk = (torch.zeros((n, k), dtype=F64, device=device) for _ in range(2))
+        if in_cycle:
+            Bk, Xk = bc.levels[0].b, bc.levels[0].x
+        else:
+            Bk, Xk = (torch.zeros((n, block_width(mc, widths)), dtype=F64, device=device) for _ in range(2))
         Bk[:, :mc].copy_(torch.from_numpy(np.ascontiguousarray(B[:, c0:c0 + mc])).to(device))
         if X0 is not None:
             Xk[:, :mc].copy_(torch.from_numpy(np.ascontiguousarray(X0[:, c0:c0 + mc])).to(device))
         rows, it_c = solve_chunk(bc, Bk, Xk, mc)
-        Xh = Xk.cpu().numpy()
+        Xh = (bc.levels[0].x if in_cycle else Xk).cpu().numpy()
         if Xh[:, mc:].any():
             raise RuntimeError("a padding column of the block left zero")
         X[:, c0:c0 + mc] = Xh[:, :mc]
         its[c0:c0 + mc] = it_c
         tracks.append(np.array(rows, dtype=float).reshape(len(rows), mc))
-    return X, chunk_tracks(tracks, m, widths[-1]), its
-
-
-def chunk_tracks(tracks, m, width):
-    """One (rows, m) track from those of the chunks of `width` columns each: the rows of the longest, NaN where one has fewer."""
     track = np.full((max(t.shape[0] for t in tracks), m), np.nan)
     for i, t in enumerate(tracks):
-        track[:t.shape[0], i * width:i * width + t.shape[1]] = t
-    return track
+        track[:t.shape[0], i * widths[-1]:i * widths[-1] + t.shape[1]] = t
+    return X, track, its
 
 
 def block_pcg_columns(ops_mod, A, block_cycle, B, X0, device, *, max_iterations, error, steps=2, omega=0.8, shape="V",
                       use_graph=False):
     """block_pcg on the m >= 1 columns of the NumPy array B (n, m) from X0 (None: zero), in chunks of the widest block,
-    each padded with zero columns to the narrowest width that holds it (_columns_in_chunks).  block_cycle(mc) returns the
+    each padded with zero columns to the narrowest width that holds it (columns_in_chunks).  block_cycle(mc) returns the
     BlockCycle that preconditions a chunk of mc columns, ready for them (use_columns), or None: no preconditioner.
     Returns (X, track, iterations) as NumPy arrays: track has one row more than the longest chunk ran iterations, NaN
     where a column did not get that far."""
@@ -140,7 +183,7 @@ def block_pcg_columns(ops_mod, A, block_cycle, B, X0, device, *, max_iterations,
         return block_pcg(ops_mod, A, bc, Bk, Xk, ncols=mc, max_iterations=max_iterations, error=error, steps=steps,
                          omega=omega, shape=shape, use_graph=use_graph and bc is not None)
 
-    return _columns_in_chunks(ops_mod, block_cycle, B, X0, device, solve_chunk)
+    return columns_in_chunks(ops_mod, block_cycle, B, X0, device, solve_chunk)
 
 
 def block_fgmres(ops_mod, A, bc, B, X, *, ncols, restart, max_iterations, error, steps=2, omega=0.8, shape="V",
@@ -155,7 +198,7 @@ def block_fgmres(ops_mod, A, bc, B, X, *, ncols, restart, max_iterations, error,
         Z_s = M V_s,  W = A Z_s into V_(s+1)
         CGS2 against V_0 .. V_s as four launches (block_multi_dot, block_multi_axpy, and again with |w_j|^2 folded in);
         ONE device-to-host read of h1, h2 and the norms, (2 (restart + 1) + 1) k doubles
-        per column on the host what fgmres does: h = h1 + h2, the Givens rotations, the estimate |g_(s+1)|
+        per column on the host what fgmres does (one Arnoldi each): h = h1 + h2, the rotations, the estimate |g_(s+1)|
         one block_scale: 1 / |w_j| for the columns that go on, 0 for those that do not (none after the last step of a
         cycle: that block is not read again)
     A column leaves the block's cycle at its own step k_j -- its estimate is <= error, |w_j| == 0, or its own iteration
@@ -173,12 +216,7 @@ def block_fgmres(ops_mod, A, bc, B, X, *, ncols, restart, max_iterations, error,
     m = int(restart)
     if m < 1:
         raise ValueError("restart must be >= 1, got %r" % (restart,))
-    n, k = X.shape
-    if k not in tuple(ops_mod.BLOCK_WIDTHS) or B.shape != X.shape or not 1 <= ncols <= k:
-        raise ValueError("block_fgmres: blocks %s / %s with %r columns in use" % (tuple(B.shape), tuple(X.shape), ncols))
-    if bc is not None and (bc.k != k or bc.levels[0].n != n):
-        raise ValueError("block_fgmres: the preconditioner works on (%d, %d) blocks, not (%d, %d)"
-                         % (bc.levels[0].n, bc.k, n, k))
+    n, k = _check_blocks("block_fgmres", ops_mod, bc, B, X, ncols)
     dev = X.device
     V = torch.zeros((m + 1, n, k), dtype=F64, device=dev)
     Z = V if bc is None else torch.zeros((m, n, k), dtype=F64, device=dev)
@@ -200,8 +238,7 @@ def block_fgmres(ops_mod, A, bc, B, X, *, ncols, restart, max_iterations, error,
     on = [goes_on(j) for j in range(k)]
     while any(on):
         ops_mod.block_scale([1.0 / beta[j] if on[j] else 0.0 for j in range(k)], V[0])
-        g = [[beta[j]] for j in range(k)]
-        cs, sn, R = ([[] for _ in range(k)] for _ in range(3))
+        ls = [Arnoldi(beta[j]) for j in range(k)]
         kj = [0] * k
         for s in range(m):
             W = V[s + 1]
@@ -221,20 +258,7 @@ def block_fgmres(ops_mod, A, bc, B, X, *, ncols, restart, max_iterations, error,
                 hn = math.sqrt(hb[2 * nh + j])
                 its[j] += 1
                 kj[j] = s + 1
-                c_, s_, g_ = cs[j], sn[j], g[j]
-                for i in range(s):                                       # the rotations of the earlier steps
-                    t = c_[i] * h[i] + s_[i] * h[i + 1]
-                    h[i + 1] = -s_[i] * h[i] + c_[i] * h[i + 1]
-                    h[i] = t
-                d = math.hypot(h[s], hn)
-                c, sj = (1.0, 0.0) if d == 0.0 else (h[s] / d, hn / d)
-                h[s] = c * h[s] + sj * hn
-                c_.append(c)
-                s_.append(sj)
-                g_.append(-sj * g_[s])
-                g_[s] = c * g_[s]
-                R[j].append(h)
-                est = abs(g_[s + 1])
+                est = ls[j].step(h, hn)
                 tracks[j].append(est)
                 if est <= error or hn == 0.0 or its[j] == max_iterations:
                     on[j] = False                                        # leaves the cycle at k_j = s + 1
@@ -243,15 +267,9 @@ def block_fgmres(ops_mod, A, bc, B, X, *, ncols, restart, max_iterations, error,
             if not any(on) or s + 1 == m:
                 break
             ops_mod.block_scale(scale, W)
-        y = [0.0] * (m * k)                                              # R y = g[:k_j] per column, R[c][r] = entry (r, c)
+        y = [0.0] * (m * k)                                              # y[i * k + j]: k_j entries for column j
         for j in range(k):
-            Rj, yj = R[j], [0.0] * kj[j]
-            for i in range(kj[j] - 1, -1, -1):
-                t = g[j][i]
-                for c in range(i + 1, kj[j]):
-                    t -= Rj[c][i] * yj[c]
-                yj[i] = t / Rj[i][i] if Rj[i][i] != 0.0 else 0.0
-                y[i * k + j] = yj[i]
+            y[j:kj[j] * k:k] = ls[j].solution()
         ybuf.copy_(torch.tensor(y, dtype=F64))
         ops_mod.block_multi_axpy(Z, kj, ybuf, X, subtract=False)
         ops_mod.block_residual_norm2(A, X, B, V[0], part, nrm)
@@ -269,13 +287,13 @@ def block_fgmres(ops_mod, A, bc, B, X, *, ncols, restart, max_iterations, error,
 def block_fgmres_columns(ops_mod, A, block_cycle, B, X0, device, *, restart, max_iterations, error, steps=2, omega=0.8,
                          shape="V", use_graph=False):
     """block_fgmres on the m >= 1 columns of the NumPy array B (n, m) from X0 (None: zero), chunked and padded like
-    block_pcg_columns (_columns_in_chunks, which also checks that the padding columns are still zero).  Returns
+    block_pcg_columns (columns_in_chunks, which also checks that the padding columns are still zero).  Returns
     (X, track, iterations) as NumPy arrays: column j of track is that column's own history, NaN behind its last iteration."""
     def solve_chunk(bc, Bk, Xk, mc):
         return block_fgmres(ops_mod, A, bc, Bk, Xk, ncols=mc, restart=restart, max_iterations=max_iterations, error=error,
                             steps=steps, omega=omega, shape=shape, use_graph=use_graph and bc is not None)
 
-    return _columns_in_chunks(ops_mod, block_cycle, B, X0, device, solve_chunk)
+    return columns_in_chunks(ops_mod, block_cycle, B, X0, device, solve_chunk)
 
 
 def fgmres(ops_mod, A, b, x, apply_M, *, restart, max_iterations, error, residual_out=None):
@@ -305,8 +323,7 @@ def fgmres(ops_mod, A, b, x, apply_M, *, restart, max_iterations, error, residua
     its = 0
     while beta > error and beta > 0.0 and its < max_iterations:
         ops_mod.axpby(1.0 / beta, v0, 0.0, v0)
-        g = [beta]
-        cs, sn, R = [], [], []
+        ls = Arnoldi(beta)
         k = 0
         for j in range(m):
             if its == max_iterations:
@@ -326,30 +343,12 @@ def fgmres(ops_mod, A, b, x, apply_M, *, restart, max_iterations, error, residua
             hn = math.sqrt(hb[2 * (m + 1)])
             its += 1
             k = j + 1
-            for i in range(j):                                           # the rotations of the earlier steps
-                t = cs[i] * h[i] + sn[i] * h[i + 1]
-                h[i + 1] = -sn[i] * h[i] + cs[i] * h[i + 1]
-                h[i] = t
-            d = math.hypot(h[j], hn)
-            c, sj = (1.0, 0.0) if d == 0.0 else (h[j] / d, hn / d)
-            h[j] = c * h[j] + sj * hn
-            cs.append(c)
-            sn.append(sj)
-            g.append(-sj * g[j])
-            g[j] = c * g[j]
-            R.append(h)
-            est = abs(g[j + 1])
+            est = ls.step(h, hn)
             track.append(est)
             if est <= error or hn == 0.0:
                 break
             ops_mod.axpby(1.0 / hn, w, 0.0, w)
-        y = [0.0] * k                                                    # R y = g[:k], R[c][r] = entry (r, c)
-        for i in range(k - 1, -1, -1):
-            t = g[i]
-            for c in range(i + 1, k):
-                t -= R[c][i] * y[c]
-            y[i] = t / R[i][i] if R[i][i] != 0.0 else 0.0
-        ybuf[:k].copy_(torch.tensor(y, dtype=F64))
+        ybuf[:k].copy_(torch.tensor(ls.solution(), dtype=F64))
         ops_mod.multi_axpy(Z, k, ybuf, x, subtract=False)
         ops_mod.csr_residual_norm2(A, x, b, v0, part, s)
         beta = math.sqrt(s.item())

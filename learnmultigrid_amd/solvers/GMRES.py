@@ -26,13 +26,14 @@ from .Solver import IterativeSolver, on_device
 
 def check_keywords(restart, max_vectors, precond_smoother, precond_cycle_shape, precond_gs_sweep, precond_line_dir,
                    precond_line_order, precond_line_band=None, precond_steps=2):
-    """The keyword checks of GMRES.solve (ValueError); returns the (pre, post) Gauss-Seidel directions.  max_vectors:
-    the most basis rows a Gram-Schmidt launch takes (ops.krylov_max_vectors()): a cycle holds restart + 1."""
+    """The keyword checks of GMRES.solve (ValueError); returns (pair, options): the (pre, post) Gauss-Seidel directions and
+    the smoother options make_apply prepares the hierarchy with (check_smoother).  max_vectors: the most basis rows a
+    Gram-Schmidt launch takes (ops.krylov_max_vectors()): a cycle holds restart + 1."""
     check_restart(restart, max_vectors)
-    check_smoother(precond_smoother, precond_steps, line_dir=precond_line_dir, line_order=precond_line_order,
-                   line_band=precond_line_band)
+    options = check_smoother(precond_smoother, precond_steps, line_dir=precond_line_dir, line_order=precond_line_order,
+                             line_band=precond_line_band)
     cycle_children(precond_cycle_shape)
-    return gs_sweep_pair(precond_gs_sweep)
+    return gs_sweep_pair(precond_gs_sweep), options
 
 
 def check_restart(restart, max_vectors):
@@ -58,8 +59,8 @@ class GMRES(BlockSolves, IterativeSolver):
               precond_steps=2, precond_omega=0.8, precond_smoother="Jacobi", precond_cycle_shape="V",
               precond_gs_sweep="forward", precond_line_dir="xy", precond_line_order="zebra",
               precond_line_band=None):
-        pair = check_keywords(restart, ops.krylov_max_vectors(), precond_smoother, precond_cycle_shape, precond_gs_sweep,
-                              precond_line_dir, precond_line_order, precond_line_band, precond_steps)
+        pair, options = check_keywords(restart, ops.krylov_max_vectors(), precond_smoother, precond_cycle_shape, precond_gs_sweep,
+                                       precond_line_dir, precond_line_order, precond_line_band, precond_steps)
         A = self._device_matrix()
         A.pack()
         n = self.dim
@@ -70,10 +71,7 @@ class GMRES(BlockSolves, IterativeSolver):
         H = preconditioner
         apply_M = None
         if H is not None:
-            # (check_keywords returns the directions alone: the options it has checked are put together here)
-            apply_M = make_apply(H, precond_smoother, precond_steps, precond_omega, precond_cycle_shape, pair,
-                                 check_smoother(precond_smoother, precond_steps, line_dir=precond_line_dir,
-                                                line_order=precond_line_order, line_band=precond_line_band))
+            apply_M = make_apply(H, precond_smoother, precond_steps, precond_omega, precond_cycle_shape, pair, options)
         track, self.iterations = krylov.fgmres(ops, A, b, x, apply_M, restart=int(restart), max_iterations=max_iterations,
                                                error=error, residual_out=r)
         if track[-1] <= error:

@@ -208,39 +208,30 @@ class Multigrid(BlockSolves, IterativeSolver):
         if smoother != "Jacobi":
             raise ValueError("solve_many smooths with weighted Jacobi only, got smoother=%r" % (smoother,))
         cycle_children(cycle_shape)
-        m = B.shape[1]
         H = self._setup(levels, self._FIRST_CALL, coarse_refine)
-        X = np.empty_like(B)
-        tracks, its = [], np.full(m, int(max_iterations), dtype=np.int64)
-        wmax = ops.BLOCK_WIDTHS[-1]
+
+        def solve_chunk(bc, Bk, Xk, mc):
+            graph = bc.captured(smooth_steps, omega, cycle_shape) if use_graph else None
+            rows, its = [], np.full(mc, int(max_iterations), dtype=np.int64)
+            for it in range(int(max_iterations)):
+                norms = np.array(bc.residual_norms())
+                rows.append(norms)
+                passed = norms <= error
+                its[passed & (its == max_iterations)] = it
+                self._log("It: ", it + 1, norms)
+                if passed.all():
+                    break
+                if graph is not None:
+                    graph.launch()
+                else:
+                    bc.cycle(smooth_steps, omega, cycle_shape)
+            return rows, its
+
         with hierarchy_stream(H, self._device):
-            for c0 in range(0, m, wmax):
-                mc = min(wmax, m - c0)
-                bc = self._block_cycle(H, mc)
-                fine = bc.levels[0]
-                fine.b[:, :mc].copy_(torch.from_numpy(np.ascontiguousarray(B[:, c0:c0 + mc])).to(self._device))
-                if X0 is not None:
-                    fine.x[:, :mc].copy_(torch.from_numpy(np.ascontiguousarray(X0[:, c0:c0 + mc])).to(self._device))
-                graph = bc.captured(smooth_steps, omega, cycle_shape) if use_graph else None
-                rows = []
-                for it in range(int(max_iterations)):
-                    norms = np.array(bc.residual_norms())
-                    rows.append(norms)
-                    passed = norms <= error
-                    first = passed & (its[c0:c0 + mc] == max_iterations)
-                    its[c0:c0 + mc][first] = it
-                    self._log("It: ", it + 1, norms)
-                    if passed.all():
-                        break
-                    if graph is not None:
-                        graph.launch()
-                    else:
-                        bc.cycle(smooth_steps, omega, cycle_shape)
-                X[:, c0:c0 + mc] = bc.levels[0].x[:, :mc].cpu().numpy()
-                tracks.append(np.array(rows, dtype=float).reshape(len(rows), mc))
-        self.iterations_many = its
+            X, track, self.iterations_many = krylov.columns_in_chunks(ops, lambda mc: self._block_cycle(H, mc), B, X0,
+                                                                      self._device, solve_chunk, in_cycle=True)
         self.level_dims = H.sizes
-        return X, krylov.chunk_tracks(tracks, m, wmax)
+        return X, track
 
     # -- Multigrid.v_cycle (Multigrid.py:77) ------------------------------------------------------
     @on_device

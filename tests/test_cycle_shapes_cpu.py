@@ -8,7 +8,7 @@ import torch
 import cpu_ops_shim as shim
 from cycle_shapes_ref import ShapeCycle, history
 from learnmultigrid_amd import problems as P
-from learnmultigrid_amd.hierarchy import CYCLE_SHAPES, Hierarchy, cycle_children
+from learnmultigrid_amd.hierarchy import CYCLE_SHAPES, Hierarchy, capture_cycle, cycle_children
 
 
 def _problem(m=64, levels=5):
@@ -91,3 +91,36 @@ def test_cycle_rejects_unknown_shapes():
     H = Hierarchy(A, hier, "cpu", ops_mod=shim)
     with pytest.raises(ValueError):
         H.cycle("Jacobi", 1, 0.8, shape="X")
+
+
+def test_a_captured_cycle_must_leave_the_ping_pong_buffers_in_their_slots():
+    """capture_cycle on a stand-in of CapturedGraph: from swap_from on a level may end with x and tmp exchanged and gets them
+    back; below it, without it, and for any other tensor in a slot, the capture is refused."""
+    import types
+
+    class Graph:
+        def __enter__(self):
+            return self
+
+        def __exit__(self, *exc):
+            return False
+
+    ops = types.SimpleNamespace(CapturedGraph=Graph)
+
+    def levels():
+        return [types.SimpleNamespace(x=torch.zeros(2), tmp=torch.zeros(2)) for _ in range(3)]
+
+    def swap(lev):
+        lev.x, lev.tmp = lev.tmp, lev.x
+
+    L = levels()
+    before = [(lev.x, lev.tmp) for lev in L]
+    ran = []
+    assert isinstance(capture_cycle(ops, L, lambda: ran.append(1)), Graph) and ran == [1]
+    assert isinstance(capture_cycle(ops, L, lambda: (swap(L[1]), swap(L[2])), swap_from=1), Graph)
+    assert all(lev.x is x and lev.tmp is tmp for lev, (x, tmp) in zip(L, before))
+    for run, swap_from in ((lambda L: swap(L[0]), 1), (lambda L: swap(L[1]), None), (lambda L: swap(L[1]), 2),
+                           (lambda L: setattr(L[2], "x", torch.zeros(2)), 1), (lambda L: setattr(L[2], "tmp", L[2].x), 1)):
+        L = levels()
+        with pytest.raises(RuntimeError, match="ping-pong buffers did not return to their slots"):
+            capture_cycle(ops, L, lambda: run(L), swap_from=swap_from)

@@ -194,13 +194,85 @@ def test_restart_below_one_is_refused():
 def test_gmres_keyword_checks():
     ok = dict(restart=30, max_vectors=65, precond_smoother="Jacobi", precond_cycle_shape="V", precond_gs_sweep="forward",
               precond_line_dir="xy", precond_line_order="zebra")
-    assert check_keywords(**ok) == ("forward", "forward")
+    assert check_keywords(**ok) == (("forward", "forward"), {})
     assert check_keywords(**dict(ok, restart=64, precond_cycle_shape="F", precond_gs_sweep=("forward", "backward"))) == \
-        ("forward", "backward")
-    assert check_keywords(**dict(ok, precond_cycle_shape="W", precond_gs_sweep="symmetric")) == ("symmetric", "symmetric")
+        (("forward", "backward"), {})
+    assert check_keywords(**dict(ok, precond_cycle_shape="W", precond_gs_sweep="symmetric")) == (("symmetric", "symmetric"), {})
+    assert check_keywords(**dict(ok, precond_smoother="Line")) == \
+        (("forward", "forward"), {"line_dir": "xy", "line_order": "zebra", "line_band": 1})
+    assert check_keywords(**dict(ok, precond_smoother="Line", precond_line_dir="y", precond_line_order="jacobi",
+                                 precond_line_band=2))[1] == {"line_dir": "y", "line_order": "jacobi", "line_band": 2}
     for bad in (dict(restart=0), dict(restart=-3), dict(restart=65), dict(restart=1000), dict(restart=2.5),
                 dict(precond_smoother="SOR"), dict(precond_cycle_shape="X"), dict(precond_gs_sweep="sideways"),
                 dict(precond_gs_sweep=("forward",)), dict(precond_smoother="Line", precond_line_dir="z"),
                 dict(precond_smoother="Line", precond_line_order="red-black")):
         with pytest.raises(ValueError):
             check_keywords(**dict(ok, **bad))
+
+
+# ---- 7. the host recurrence of fgmres and block_fgmres ---------------------------------------------------------------------
+def hessenberg():
+    """A fixed 6 x 5 upper-Hessenberg matrix with a subdiagonal in [0.5, 1.5)."""
+    rng = np.random.default_rng(3)
+    H = np.triu(rng.standard_normal((6, 5)), -1)
+    H[np.arange(1, 6), np.arange(5)] = 0.5 + rng.random(5)
+    return H
+
+
+def lstsq_bounds(Hk, y, rho):
+    """(bound on |y_got - y|_2, bound on |est - rho|) against the least-squares solution y of Hk y = e_1 with residual norm rho.
+
+    u = 2^-53.  One Givens rotation -- c and s from a hypot and two divisions, two products and a sum per rotated entry --
+    moves the pair it turns by at most 10 u of its norm, a column of the k-step problem goes through at most k + 1 of them,
+    and the back substitution solves (R + dR) y = g with |dR| <= k u |R| (Higham, Accuracy and Stability, Theorem 8.5): the
+    computed y and g are exact for Hk + dH and e_1 + db with |dH|_F <= 11 (k + 1) u |Hk|_F, that is, with |Hk|_F <= sqrt(k) |Hk|_2,
+    a relative backward error of eps_b = 11 (k + 1) sqrt(k) u in the 2-norm.  numpy.linalg.lstsq (LAPACK, backward stable)
+    is allowed the same, hence the factor 2.  Theorem 20.1 there turns a backward error into
+        |dy| / |y| <= kappa eps_b / (1 - kappa eps_b) (2 + (kappa + 1) rho / (|Hk|_2 |y|)),   |d rho| <= (1 + 2 kappa) eps_b |e_1|
+    with kappa = cond_2(Hk): multiples of eps cond(Hk) that are computed from the reference alone."""
+    k = Hk.shape[1]
+    eps_b = 11.0 * (k + 1) * np.sqrt(k) * 2.0 ** -53
+    kappa = np.linalg.cond(Hk)
+    assert kappa * eps_b < 1e-3
+    ny = np.linalg.norm(y)
+    return (2.0 * kappa * eps_b / (1.0 - kappa * eps_b) * (2.0 + (kappa + 1.0) * rho / (np.linalg.norm(Hk, 2) * ny)) * ny,
+            2.0 * (1.0 + 2.0 * kappa) * eps_b)
+
+
+def test_arnoldi_recurrence_solves_the_least_squares_problems():
+    H = hessenberg()
+    ls = krylov.Arnoldi(1.0)
+    assert ls.solution() == []
+    for j in range(5):
+        est = ls.step(H[:j + 1, j].tolist(), float(H[j + 1, j]))
+        Hk, e1 = H[:j + 2, :j + 1], np.eye(j + 2)[0]
+        want = np.linalg.lstsq(Hk, e1, rcond=None)[0]
+        rho = np.linalg.norm(e1 - Hk @ want)
+        got = np.array(ls.solution())
+        by, br = lstsq_bounds(Hk, want, rho)
+        print("step %d: cond %.2f, |y - lstsq| %.2e (bound %.2e), |est - rho| %.2e (bound %.2e)"
+              % (j, np.linalg.cond(Hk), np.linalg.norm(got - want), by, abs(est - rho), br))
+        assert got.shape == (j + 1,) and len(ls.g) == j + 2 and len(ls.cs) == len(ls.sn) == len(ls.R) == j + 1
+        assert 0.0 < rho < 1.0 and est == abs(ls.g[j + 1])
+        assert np.linalg.norm(got - want) <= by
+        assert abs(est - rho) <= br
+
+
+def test_arnoldi_recurrence_breakdowns():
+    # |w| == 0 at the last step: the Krylov space is invariant, the square system is solved exactly
+    H = hessenberg()
+    ls = krylov.Arnoldi(1.0)
+    for j in range(4):
+        assert ls.step(H[:j + 1, j].tolist(), float(H[j + 1, j])) > 0.0
+    assert ls.step(H[:5, 4].tolist(), 0.0) == 0.0 and ls.sn[4] == 0.0
+    want = np.linalg.solve(H[:5, :5], np.eye(5)[0])
+    by, _ = lstsq_bounds(H[:5, :5], want, 0.0)
+    assert np.linalg.norm(np.array(ls.solution()) - want) <= by
+    # a column that is zero after the earlier rotations, with |w| == 0: the (1, 0) rotation, and y = 0 at the zero pivot
+    ls = krylov.Arnoldi(1.0)
+    assert ls.step([2.0], 0.0) == 0.0
+    assert ls.step([3.0, 0.0], 0.0) == 0.0
+    assert (ls.cs, ls.sn) == ([1.0, 1.0], [0.0, 0.0]) and ls.R[1] == [3.0, 0.0]
+    assert ls.solution() == [0.5, 0.0]
+    ls = krylov.Arnoldi(7.0)
+    assert ls.step([0.0], 0.0) == 0.0 and ls.solution() == [0.0] and ls.g[0] == 7.0

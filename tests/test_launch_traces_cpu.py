@@ -1,7 +1,9 @@
 """The smoothing paths launch what they launched before smoothing.py and torch_ops.py were split off (no GPU): every ops
 call of Hierarchy.cycle, DistributedVCycle.cycle and the operator handles of torch.ops.lmg on the ops shims -- its name,
 its flags, the buffers it reads and writes -- against the traces recorded on the commit before the split
-(tests/golden/launch_traces.json, written by tools/launch_traces.py; tests/launch_trace.py says what a trace line holds)."""
+(tests/golden/launch_traces.json, written by tools/launch_traces.py; tests/launch_trace.py says what a trace line holds).
+The krylov part -- fgmres, block_fgmres, block_pcg and Multigrid.solve_many -- was recorded on the commit before the drivers came
+to share their Givens recurrence, their chunk loop and the graph capture."""
 import os
 
 import pytest
