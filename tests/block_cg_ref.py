@@ -158,7 +158,8 @@ def block_cg_direction(rz_new, rz_old, mask, Z, P):
     for j in range(P.shape[1]):
         if _np(mask)[j] != 0.0:
             beta = _np(rz_new)[j] / _np(rz_old)[j]
-            _np(P)[:, j] = _np(Z)[:, j] + beta * _np(P)[:, j]
+            # (beta == 0 stores Z and does not read P, like the kernel: axpby's beta == 0 case)
+            _np(P)[:, j] = _np(Z)[:, j] if beta == 0.0 else _np(Z)[:, j] + beta * _np(P)[:, j]
 
 
 def block_namespace(shim, **replace):

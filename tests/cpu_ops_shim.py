@@ -177,8 +177,18 @@ class SpGEMMPlan:
         self.shape = (A.shape[0], B.shape[1])
 
     def numeric(self, A, B, out=None):
-        C = sp.csr_matrix(_sp(A) @ _sp(B))
+        As, Bs = _sp(A), _sp(B)
+        C = sp.csr_matrix(As @ Bs)
         C.sort_indices()
+        # the pattern is the structural one, like the kernel's: SciPy drops the entries that cancel to exactly 0.0, the
+        # symbolic phase of the device product keeps them as explicit zeros (csrc/spgemm.hip)
+        ones = lambda M: sp.csr_matrix((np.ones(M.nnz), M.indices, M.indptr), shape=M.shape)
+        S = sp.csr_matrix(ones(As) @ ones(Bs))
+        S.sort_indices()
+        key = lambda M: np.repeat(np.arange(M.shape[0], dtype=np.int64), np.diff(M.indptr)) * M.shape[1] + M.indices
+        vals = np.zeros(S.nnz)
+        vals[np.searchsorted(key(S), key(C))] = C.data
+        C = sp.csr_matrix((vals, S.indices, S.indptr), shape=S.shape)
         new = DeviceCSR.from_scipy(C, "cpu")
         if out is not None:
             out.vals.copy_(new.vals)
@@ -215,7 +225,16 @@ def cheby_update(a, c, dinv, r, d, x, first=False):
 
 
 def csr_gershgorin(A, out):
-    _np(out)[0] = _CR.gershgorin(_sp(A))
+    # the entries as they are stored, like the kernel: no canonicalisation (chebyshev_ref.gershgorin sorts the rows and sums
+    # duplicates first, which moves |a| + |b| to |a + b| for a duplicated entry)
+    n, rp, ci, va = _raw(A)
+    rows = np.repeat(np.arange(n), np.diff(rp))
+    asum, diag = np.zeros(n), np.zeros(n)
+    np.add.at(asum, rows, np.abs(va))
+    on = ci == rows
+    np.add.at(diag, rows[on], va[on])
+    ok = diag != 0
+    _np(out)[0] = float(np.max(asum[ok] / np.abs(diag[ok]))) if ok.any() else 0.0
 
 
 def line_factor(A, W, dir):

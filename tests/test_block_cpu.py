@@ -6,6 +6,7 @@ import pytest
 import scipy.sparse as sp
 import torch
 
+import block_cg_ref
 import cpu_ops_shim as shim
 from cycle_shapes_ref import ShapeCycle
 from learnmultigrid_amd import _lib, problems as P
@@ -13,7 +14,6 @@ from learnmultigrid_amd.block import BlockCycle, block_width
 from learnmultigrid_amd.hierarchy import Hierarchy
 from learnmultigrid_amd.solvers import HierarchyMG
 from oracle.vcycle_ref import HoistedVCycle
-from support import to_numpy as _np, to_scipy as _sp
 
 OK, ERR_ARG, ERR_ALIGN = 0, -1, -2
 WIDTHS = (2, 4, 8)
@@ -117,29 +117,11 @@ def test_block_partials_count_covers_every_workgroup():
 
 # ---- the driver on a NumPy stand-in ---------------------------------------------------------------------------------------
 def block_namespace():
-    """cpu_ops_shim.namespace() plus the block ops on (n, k) CPU tensors: a "twin" is the matrix itself."""
-    def block_residual_norm2(S, X, B, R, partials, norm2):
-        r = _np(B) - _sp(S) @ _np(X)
-        if R is not None:
-            _np(R)[:] = r
-        if norm2 is not None:
-            _np(norm2)[:r.shape[1]] = (r * r).sum(axis=0)
-
-    def block_jacobi(S, X, B, omega, Out):
-        A = _sp(S)
-        d = A.diagonal()[:, None]
-        with np.errstate(divide="ignore", invalid="ignore"):
-            _np(Out)[:] = np.where(d != 0, _np(X) + omega * ((1.0 / d) * (_np(B) - A @ _np(X))), _np(X))
-
-    def block_spmv(S, X, Y, alpha=1.0, beta=0.0):
-        _np(Y)[:] = alpha * (_sp(S) @ _np(X)) + (beta * _np(Y) if beta != 0.0 else 0.0)
-
-    def dense_gemv_block(M, X, Y):
-        _np(Y)[:] = _np(M) @ _np(X)
-
+    """cpu_ops_shim.namespace() plus the block sweeps on (n, k) CPU tensors, block_cg_ref's stand-ins: a "twin" is the matrix
+    itself.  No Krylov op: the package reads an absent name as "not offered"."""
     return shim.namespace(BLOCK_WIDTHS=WIDTHS, block_twin=lambda A: A, block_partials_count=lambda n, k: (n // 256 + 1) * k,
-                          block_residual_norm2=block_residual_norm2, block_jacobi=block_jacobi, block_spmv=block_spmv,
-                          dense_gemv_block=dense_gemv_block)
+                          block_residual_norm2=block_cg_ref.block_residual_norm2, block_jacobi=block_cg_ref.block_jacobi,
+                          block_spmv=block_cg_ref.block_spmv, dense_gemv_block=block_cg_ref.dense_gemv_block)
 
 
 def learned_like_hierarchy(side, levels, seed=43):

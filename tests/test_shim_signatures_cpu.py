@@ -68,6 +68,45 @@ def test_the_plain_module_offers_no_more_than_it_should():
     assert a.calls == [] and a.calls is not b.calls and b.SpGEMMPlan is None and a.SpGEMMPlan is shim.SpGEMMPlan
 
 
+def test_every_offered_name_has_a_parity_entry():
+    """Every function or class a stand-in namespace offers is registered in tests/stand_in_parity.py -- with cases for
+    test_stand_in_parity_gpu.py, the GPU test that already compares it with its kernel, or the reason why there is nothing to
+    compare --, and the registry names nothing that no namespace offers.  A covering test is looked up in the file's syntax
+    tree: GPU test modules are not imported here."""
+    import ast
+    import os
+
+    import stand_in_parity as SP
+    names = SP.all_offered()
+    assert {"csr_jacobi", "stencil_smooth", "block_cg_step", "block_scale", "line_solve_banded", "SpGEMMPlan"} <= set(names)
+    assert len(SP.NAMESPACES) == 10 and all(names.values())
+    missing = sorted(set(names) - set(SP.REGISTRY))
+    assert not missing, "offered by a stand-in namespace without an entry in stand_in_parity.REGISTRY: %s" % missing
+    stale = sorted(set(SP.REGISTRY) - set(names))
+    assert not stale, "registered, but offered by no namespace: %s" % stale
+    here = os.path.dirname(os.path.abspath(__file__))
+    for op, entry in SP.REGISTRY.items():
+        if isinstance(entry, SP.Cases):
+            assert entry.cases and len({c.label for c in entry.cases}) == len(entry.cases), op
+            assert SP.implementations(op, entry.only), op
+        elif isinstance(entry, SP.CoveredBy):
+            path, test = entry.test_id.split("::")
+            tree = ast.parse(open(os.path.join(here, path)).read())
+            found = [f for f in tree.body if isinstance(f, ast.FunctionDef) and f.name == test]
+            assert found and "shim" in ast.unparse(found[0]), (op, entry.test_id)
+        else:
+            assert isinstance(entry, SP.NoValues) and entry.reason.strip(), op
+
+
+def test_constants_equal_the_library():
+    """What a stand-in hard-codes is what the library says (no device is needed for any of these)."""
+    import block_cg_ref
+    assert shim._MAX_VECTORS == ops.krylov_max_vectors()
+    assert block_cg_ref.WIDTHS == ops.BLOCK_WIDTHS
+    for passes in ("jacobi", "cheby", "all"):
+        assert shim.fused(passes).FUSED_MAX_SWEEPS == ops.FUSED_MAX_SWEEPS, passes
+
+
 def test_the_check_tells_a_drifted_stand_in():
     def real(A, x, sweeps=1, reverse=False):
         pass
