@@ -898,6 +898,54 @@ int lmg_l2_coupling_count(int64_t nf, int64_t nc, const double *d_xf, const doub
 int lmg_l2_coupling_fill(int kind, int64_t nf, int64_t nc, const double *d_xf, const double *d_xc,
                          const int32_t *d_rowptr, int32_t *d_colidx, double *d_vals, void *stream);
 
+/* ---- 2-D L2-projection coupling operator between two P1 triangle meshes (the step before the hot path) ---------
+ * B[i][j] = integral of fine basis i x coarse basis j over the intersections of the fine with the coarse elements; the
+ * meshes need not be nested or cover the same domain, and elements may have either orientation.  The reference has no
+ * 2-D path (L2Projection.compute_transfer_2d is a stub); the rules -- Sutherland-Hodgman clipping, the drop rule
+ * area > area_tol * min(|T_e|, |T_c|), the three-point rule of Quadrature.py:87-97 on a fan -- are stated on the host
+ * by l2_projection.coupling_operator_2d and in csrc/l2proj2d.hip.  A mesh is d_px / d_py[n] and d_conn[3 * ne]
+ * (0-based); f = fine, c = coarse.  Every count must fit int32 (LMG_ERR_ARG otherwise).
+ *   limits      candidates per fine element / distinct columns per row the kernels hold (both 64)
+ *   d_grid      6 doubles: origin x, y and far corner x, y of the coarse mesh's bounding box, cells per unit length in
+ *               x, y (0 for a direction without extent); ncell cells per direction, at most 46340
+ *   cell_count  d_count[c] = cells the box of coarse element c overlaps; the caller scans them into d_ptr
+ *               (lmg_exclusive_scan_i32), total = their sum
+ *   cell_fill   d_keys[d_ptr[c] + k] = cell << 32 | c.  The caller sorts the keys; d_cellptr[cell] is then the first key
+ *               of the cell (ncell^2 + 1 entries), d_cellent the low words.
+ *   cand_count  d_count[e] = coarse elements whose boxes overlap the box of fine element e (closed boxes); scan into
+ *               d_candptr, pairs = their sum, max_count = the largest
+ *   cand_fill   d_cand[d_candptr[e] ..]: those elements, ascending, each once.  LMG_ERR_CAPACITY, and nothing launched,
+ *               if max_count exceeds the limit.
+ *   rows_count  d_rownnz[i] = distinct coarse nodes of row i, limit + 1 for a row with more (one lane per fine node;
+ *               d_n2e_*: node -> element adjacency, elements ascending, as for lmg_p1_assemble_2d); scan into
+ *               d_rowptr, nnz = their sum, max_row = the largest
+ *   rows_fill   sorted CSR rows, each entry accumulated in the order element, candidate, fan triangle, quadrature point,
+ *               coarse vertex.  kind 0: B; 1: "pseudo", row i / sum over its elements of |det_e| / 6; 2: "quasi", row i /
+ *               its sum.  A row without entries stays empty.  LMG_ERR_CAPACITY, and nothing launched, if max_row
+ *               exceeds the limit.  No atomics; two calls give the same bits. */
+int lmg_l2p2d_limits(int32_t *max_candidates, int32_t *max_columns);
+int lmg_l2p2d_cell_count(int64_t ne_c, const double *d_cpx, const double *d_cpy, const int32_t *d_cconn,
+                         const double *d_grid, int32_t ncell, int32_t *d_count, void *stream);
+int lmg_l2p2d_cell_fill(int64_t ne_c, const double *d_cpx, const double *d_cpy, const int32_t *d_cconn,
+                        const double *d_grid, int32_t ncell, int64_t total, const int32_t *d_ptr, int64_t *d_keys,
+                        void *stream);
+int lmg_l2p2d_cand_count(int64_t ne_f, const double *d_fpx, const double *d_fpy, const int32_t *d_fconn, int64_t ne_c,
+                         const double *d_cpx, const double *d_cpy, const int32_t *d_cconn, const double *d_grid,
+                         int32_t ncell, const int32_t *d_cellptr, const int32_t *d_cellent, int32_t *d_count, void *stream);
+int lmg_l2p2d_cand_fill(int64_t ne_f, const double *d_fpx, const double *d_fpy, const int32_t *d_fconn, int64_t ne_c,
+                        const double *d_cpx, const double *d_cpy, const int32_t *d_cconn, const double *d_grid,
+                        int32_t ncell, const int32_t *d_cellptr, const int32_t *d_cellent, int64_t pairs,
+                        int32_t max_count, const int32_t *d_candptr, int32_t *d_cand, void *stream);
+int lmg_l2p2d_rows_count(int64_t nf, int64_t ne_f, const double *d_fpx, const double *d_fpy, const int32_t *d_fconn,
+                         const int32_t *d_n2e_ptr, const int32_t *d_n2e_elem, const int32_t *d_n2e_loc, int64_t nc,
+                         int64_t ne_c, const double *d_cpx, const double *d_cpy, const int32_t *d_cconn,
+                         const int32_t *d_candptr, const int32_t *d_cand, double area_tol, int32_t *d_rownnz, void *stream);
+int lmg_l2p2d_rows_fill(int kind, int64_t nf, int64_t ne_f, const double *d_fpx, const double *d_fpy,
+                        const int32_t *d_fconn, const int32_t *d_n2e_ptr, const int32_t *d_n2e_elem,
+                        const int32_t *d_n2e_loc, int64_t nc, int64_t ne_c, const double *d_cpx, const double *d_cpy,
+                        const int32_t *d_cconn, const int32_t *d_candptr, const int32_t *d_cand, double area_tol, int64_t nnz,
+                        int32_t max_row, const int32_t *d_rowptr, int32_t *d_colidx, double *d_vals, void *stream);
+
 /* ---- 2-D learned transfers: what NeuralMG_2D.define_hierarchy does around model.predict ---------------------
  * (Multigrid.py:373-765; the rules: DESIGN.md section 3.)  M: sorted CSR, device.  d_status: ONE 64-bit word the
  * caller sets to UINT64_MAX before a stage and reads after it; a lane that has to refuse writes

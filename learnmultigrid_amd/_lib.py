@@ -152,6 +152,14 @@ SIGNATURES = {
     "lmg_p1_assemble_2d": (_c.c_int, [_i64, _p, _p, _p, _p, _p, _p, _p, _f64, _p, _p, _p, _p, _p, _p]),
     "lmg_l2_coupling_count": (_c.c_int, [_i64, _i64, _p, _p, _p, _p]),
     "lmg_l2_coupling_fill": (_c.c_int, [_c.c_int, _i64, _i64, _p, _p, _p, _p, _p, _p]),
+    "lmg_l2p2d_limits": (_c.c_int, [_p, _p]),
+    "lmg_l2p2d_cell_count": (_c.c_int, [_i64, _p, _p, _p, _p, _i32, _p, _p]),
+    "lmg_l2p2d_cell_fill": (_c.c_int, [_i64, _p, _p, _p, _p, _i32, _i64, _p, _p, _p]),
+    "lmg_l2p2d_cand_count": (_c.c_int, [_i64, _p, _p, _p, _i64, _p, _p, _p, _p, _i32, _p, _p, _p, _p]),
+    "lmg_l2p2d_cand_fill": (_c.c_int, [_i64, _p, _p, _p, _i64, _p, _p, _p, _p, _i32, _p, _p, _i64, _i32, _p, _p, _p]),
+    "lmg_l2p2d_rows_count": (_c.c_int, [_i64, _i64, _p, _p, _p, _p, _p, _p, _i64, _i64, _p, _p, _p, _p, _p, _f64, _p, _p]),
+    "lmg_l2p2d_rows_fill": (_c.c_int, [_c.c_int, _i64, _i64, _p, _p, _p, _p, _p, _p, _i64, _i64, _p, _p, _p, _p, _p, _f64,
+                                       _i64, _i32, _p, _p, _p, _p]),
     "lmg_nmg2d_check": (_c.c_int, [_i64, _p, _p, _p, _p, _p]),
     "lmg_nmg2d_count": (_c.c_int, [_i64, _p, _p, _p, _p, _p, _p, _p]),
     "lmg_nmg2d_patches": (_c.c_int, [_i64, _p, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p]),

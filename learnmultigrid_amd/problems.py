@@ -252,6 +252,44 @@ def jittered_poisson_2d(m, seed=42, jitter=0.25, coeff_sigma=None, coeff_seed=44
     return A, rhs
 
 
+def structured_triangles(m):
+    """(2 m^2, 3) connectivity of the structured triangulation p1_stiffness_2d assembles on: every square k of the
+    (m+1)^2 grid gives (k, k+1, k+m+2), then every square gives (k, k+m+2, k+m+1)."""
+    s = m + 1
+    sq = (np.arange(m)[:, None] * s + np.arange(m)[None, :]).ravel()
+    return np.concatenate([np.stack([sq, sq + 1, sq + s + 1], axis=1), np.stack([sq, sq + s + 1, sq + s], axis=1)], axis=0)
+
+
+def jittered_mesh_2d(m, seed=42, jitter=0.25):
+    """(p, conn) of the mesh jittered_poisson_2d(m, seed, jitter) assembles on: p (n, 2) the node coordinates, interior
+    nodes moved by U(-jitter*h, jitter*h), conn (2 m^2, 3) the triangles of p1_stiffness_2d."""
+    s = m + 1
+    h = 1.0 / m
+    g = np.linspace(0.0, 1.0, s)
+    px = np.tile(g, s)
+    py = np.repeat(g, s)
+    idx = np.arange(s * s)
+    i, j = idx % s, idx // s
+    boundary = (i == 0) | (i == m) | (j == 0) | (j == m)
+    rng = np.random.default_rng(seed)
+    dx = rng.uniform(-jitter * h, jitter * h, s * s)
+    dy = rng.uniform(-jitter * h, jitter * h, s * s)
+    px = np.where(boundary, px, px + dx)
+    py = np.where(boundary, py, py + dy)
+    return np.stack([px, py], axis=1), structured_triangles(m)
+
+
+def coarsen_mesh_2d(p, m):
+    """Every second node of an (m+1)^2 mesh (p in grid order, m even) with the structured triangulation on m/2: the
+    coarse mesh of a semi-geometric hierarchy.  Its elements are not unions of fine ones once the nodes were moved."""
+    m = int(m)
+    p = np.asarray(p, dtype=np.float64)
+    if m < 2 or m % 2 or p.shape != ((m + 1) * (m + 1), 2):
+        raise ValueError("coarsen_mesh_2d wants the (m+1)^2 x 2 coordinates of a grid with an even m >= 2")
+    pc = p.reshape(m + 1, m + 1, 2)[::2, ::2].reshape(-1, 2)
+    return np.ascontiguousarray(pc), structured_triangles(m // 2)
+
+
 def variable_coeff_poisson_2d_structured(m, seed=44, sigma=0.5, coeff=None):
     """cfg#5 problem: -div(k grad u) with one coefficient per triangle, P1 on the structured
     triangulation, Dirichlet identity rows, load vector of f == -1 -- built directly as CSR
