@@ -997,6 +997,61 @@ int lmg_nmg2d_cut_fill(int64_t n, const int32_t *d_rowptr, const int32_t *d_coli
                        const int32_t *d_neighs, const int32_t *d_cut_rowptr, int32_t *d_cut_colidx,
                        double *d_cut_vals, void *stream);
 
+/* ---- triangle meshes: build, refine, index (the stage before lmg_p1_assemble_2d; csrc/mesh2d.hip) -----------------------
+ * What learn_multigrid/mesh/Mesh2D.py does with Python loops (construct :63-93, refine :95-160), the mesh graph that
+ * assembly.P1Mesh2D.__init__ states on the host, and the identity rows of thesis_structured_2d.py:407-414.  A mesh is
+ * d_px / d_py[n] and d_conn[3 * ne] (0-based).  Sizes: n < 2^31 - 1, 3 * ne < 2^31 - 1, and for a refinement
+ * n + edges < 2^31 - 1 (LMG_ERR_ARG otherwise, nothing launched).  d_status: ONE 64-bit word the caller sets to
+ * UINT64_MAX before a stage and reads after it, as for lmg_nmg2d_check; the order is the element (check) or the row
+ * (identity rows), so the lowest offender is named.  A slot s = 3 e + k is the directed edge conn[e][k] ->
+ * conn[e][(k + 1) % 3].
+ *   limits      distinct columns per pattern row the kernels hold (64)
+ *   construct   h_el x v_el squares on the unit square: nodes row-major, h fastest, coordinate i * (1.0 / N) and exactly
+ *               1.0 for i = N (np.linspace); square k gives (k, k+1, k+W+1) then (k, k+W+1, k+W), W = h_el + 1.
+ *               d_px / d_py[(h_el + 1)(v_el + 1)], d_conn[6 h_el v_el]
+ *   check       one lane per element: every index inside [0, n), no repeated vertex
+ *   edge_keys   d_keys[s] = min(left, right) << 32 | max(left, right).  The caller sorts the keys STABLY with their
+ *               slots (d_slot: the permutation); a run of equal keys is one undirected edge, its head its smallest slot.
+ *   edge_runs   d_head[s] = the head slot of the run of s, d_is_head[s] = 1 for a head, else 0 (the caller scans them
+ *               into d_rank with lmg_exclusive_scan_i32: edges = their sum).  d_mask (bytes, zeroed by the caller, may
+ *               be null): 1 on both ends of every run of length 1 -- the boundary nodes.  Runs longer than 2 are allowed.
+ *   refine      nodes 0 .. n-1 are copied; the midpoint of a run is node n + d_rank[head], written by the head slot's
+ *               lane as r * p[left] + (1 - r) * p[right], r = 0.5 or d_ratio[node - n]; element e becomes
+ *               [t0 v1 t1] [t1 v2 t2] [t0 t1 t2] [v0 t0 t2] at 4 e .. 4 e + 3, t_k the midpoint of slot k.  Outputs
+ *               d_px_out / d_py_out[n + edges], d_conn_out[12 ne] must not be the inputs.
+ *   n2e_fill    d_order: the permutation of a STABLE sort of d_conn by node; d_elem = order / 3, d_loc = order % 3 (the
+ *               adjacency of lmg_p1_assemble_2d, elements ascending per node; d_n2e_ptr is the caller's search)
+ *   rows_count  d_rownnz[i] = distinct vertices of the elements of node i (0 for a node in no element), limit + 1 for a
+ *               row with more; one lane per node, the set sorted in LDS; scan into d_rowptr, nnz = their sum,
+ *               max_row = the largest
+ *   rows_fill   d_colidx: the sorted pattern rows.  LMG_ERR_CAPACITY, and nothing launched, if max_row exceeds the limit.
+ *   lmg_csr_identity_rows   for every row i with d_mask[i] != 0: 1.0 on the diagonal, 0.0 on the row's other stored
+ *               entries, in place (columns untouched), and d_rhs[i] = 0, or d_value[i] where d_value is given (d_rhs may
+ *               be null).  A masked row without a stored diagonal is refused, and then no row is changed.
+ * No floating-point atomics; two calls give the same bits in every output array. */
+typedef enum {
+    LMG_MESH2D_INDEX = 1,    /* a vertex index outside [0, n)            */
+    LMG_MESH2D_REPEATED = 2, /* an element with a repeated vertex        */
+    LMG_MESH2D_DIAGONAL = 3  /* a masked row without a stored diagonal   */
+} lmg_mesh2d_rule;
+int lmg_mesh2d_limits(int32_t *max_columns);
+int lmg_mesh2d_construct(int64_t h_el, int64_t v_el, double *d_px, double *d_py, int32_t *d_conn, void *stream);
+int lmg_mesh2d_check(int64_t n, int64_t ne, const int32_t *d_conn, uint64_t *d_status, void *stream);
+int lmg_mesh2d_edge_keys(int64_t ne, const int32_t *d_conn, int64_t *d_keys, void *stream);
+int lmg_mesh2d_edge_runs(int64_t n, int64_t ne, const int64_t *d_keys, const int64_t *d_slot, int32_t *d_head,
+                         int32_t *d_is_head, uint8_t *d_mask, void *stream);
+int lmg_mesh2d_refine(int64_t n, int64_t ne, int64_t edges, const double *d_px, const double *d_py, const int32_t *d_conn,
+                      const int32_t *d_head, const int32_t *d_rank, const double *d_ratio, double *d_px_out,
+                      double *d_py_out, int32_t *d_conn_out, void *stream);
+int lmg_mesh2d_n2e_fill(int64_t ne, const int64_t *d_order, int32_t *d_elem, int32_t *d_loc, void *stream);
+int lmg_mesh2d_rows_count(int64_t n, int64_t ne, const int32_t *d_conn, const int32_t *d_n2e_ptr,
+                          const int32_t *d_n2e_elem, int32_t *d_rownnz, void *stream);
+int lmg_mesh2d_rows_fill(int64_t n, int64_t ne, const int32_t *d_conn, const int32_t *d_n2e_ptr,
+                         const int32_t *d_n2e_elem, int64_t nnz, int32_t max_row, const int32_t *d_rowptr,
+                         int32_t *d_colidx, void *stream);
+int lmg_csr_identity_rows(int64_t n, const int32_t *d_rowptr, const int32_t *d_colidx, double *d_vals,
+                          const uint8_t *d_mask, const double *d_value, double *d_rhs, uint64_t *d_status, void *stream);
+
 /* ---- hipGraph capture of a launch sequence (one V-cycle) -----------------------------
  * begin/end bracket launches issued on `stream`; end returns an opaque executable graph. */
 int lmg_graph_begin(void *stream);

@@ -169,6 +169,16 @@ SIGNATURES = {
     "lmg_nmg2d_dneighs": (_c.c_int, [_i64, _p, _p, _p, _p, _p]),
     "lmg_nmg2d_cut_mark": (_c.c_int, [_i64, _p, _p, _p, _p, _p]),
     "lmg_nmg2d_cut_fill": (_c.c_int, [_i64, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "lmg_mesh2d_limits": (_c.c_int, [_p]),
+    "lmg_mesh2d_construct": (_c.c_int, [_i64, _i64, _p, _p, _p, _p]),
+    "lmg_mesh2d_check": (_c.c_int, [_i64, _i64, _p, _p, _p]),
+    "lmg_mesh2d_edge_keys": (_c.c_int, [_i64, _p, _p, _p]),
+    "lmg_mesh2d_edge_runs": (_c.c_int, [_i64, _i64, _p, _p, _p, _p, _p, _p]),
+    "lmg_mesh2d_refine": (_c.c_int, [_i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "lmg_mesh2d_n2e_fill": (_c.c_int, [_i64, _p, _p, _p, _p]),
+    "lmg_mesh2d_rows_count": (_c.c_int, [_i64, _i64, _p, _p, _p, _p, _p]),
+    "lmg_mesh2d_rows_fill": (_c.c_int, [_i64, _i64, _p, _p, _p, _i64, _i32, _p, _p, _p]),
+    "lmg_csr_identity_rows": (_c.c_int, [_i64, _p, _p, _p, _p, _p, _p, _p, _p]),
     "lmg_graph_begin": (_c.c_int, [_p]),
     "lmg_graph_end": (_c.c_int, [_p, _c.POINTER(_p)]),
     "lmg_graph_launch": (_c.c_int, [_p, _p]),

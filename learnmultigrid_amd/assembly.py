@@ -1,9 +1,10 @@
 """P1 finite-element assembly on the device -- what
 learn_multigrid/assembly/{StiffnessMatrix,MassMatrix,LoadVector}.py do with per-element Python
 loops, as one atomic-free HIP kernel (csrc/assembly.hip).  The mesh graph (CSR pattern and the
-node->element adjacency) is integer work done once per mesh on the host; values are assembled
-on the GPU and can be re-assembled for new coordinates or coefficients without touching the
-pattern."""
+node->element adjacency) is integer work done once per mesh: on the host by the constructor,
+which states the rules, or on the device by P1Mesh2D.from_device (csrc/mesh2d.hip, the same
+integers); values are assembled on the GPU and can be re-assembled for new coordinates or
+coefficients without touching the pattern."""
 import numpy as np
 import scipy.sparse as sp
 import torch
@@ -44,6 +45,26 @@ class P1Mesh2D:
         self.rowptr = torch.from_numpy(pat.indptr.astype(np.int32)).to(d)
         self.colidx = torch.from_numpy(pat.indices.astype(np.int32)).to(d)
         self.nnz = int(pat.nnz)
+
+    @classmethod
+    def from_device(cls, px, py, conn, checked=False):
+        """The same object from device tensors -- px, py (n,) float64, conn (3 * ne,) or (ne, 3) int32 -- with the mesh
+        graph built by csrc/mesh2d.hip (mesh.topology_device) instead of on the host: the same integers.  A node with
+        more neighbours than mesh.limits() allows raises _lib.LmgError; checked: the caller has run mesh.check_device."""
+        from . import mesh
+        if px.dtype != F64 or py.dtype != F64 or conn.dtype != I32 or not (px.is_cuda and py.is_cuda and conn.is_cuda):
+            raise TypeError("from_device wants float64 coordinates and int32 connectivity on the device")
+        if px.numel() != py.numel() or conn.numel() % 3 or not (px.device == py.device == conn.device):
+            raise ValueError("px, py of one length and three vertices per element, on one device")
+        self = cls.__new__(cls)
+        self.px, self.py, self.conn = px.contiguous().view(-1), py.contiguous().view(-1), conn.contiguous().view(-1)
+        self.n, self.ne = int(px.numel()), int(conn.numel() // 3)
+        self.device = px.device
+        if not checked:
+            mesh.check_device(self.n, self.conn)
+        self.n2e_ptr, self.n2e_elem, self.n2e_loc, self.rowptr, self.colidx = mesh.topology_device(self.n, self.conn)
+        self.nnz = int(self.colidx.numel())
+        return self
 
     def assemble(self, stiffness=True, mass=True, load=None, coeff=None):
         """Returns (A, M, rhs): DeviceCSR / DeviceCSR / (n,) tensor, None for parts not asked for.

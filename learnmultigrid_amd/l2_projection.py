@@ -305,6 +305,9 @@ def _device_mesh_2d(mesh, device):
     from .assembly import P1Mesh2D
     if isinstance(mesh, P1Mesh2D):
         return mesh
+    from .mesh import Mesh2D
+    if isinstance(mesh, Mesh2D):
+        return mesh.p1()
     if device is None:
         raise ValueError("a mesh given as (p, conn) needs device=")
     p, conn = _mesh(*mesh)
@@ -389,8 +392,8 @@ def rows_2d_device(code, fine, coarse, candptr, cand, area_tol=1e-14):
 
 
 def transfer_2d_device(kind, fine, coarse, area_tol=1e-14, device=None, cells=None):
-    """transfer_2d on an MI355X (csrc/l2proj2d.hip): kind in B | pseudo | quasi.  fine, coarse: assembly.P1Mesh2D, or
-    (p, conn) with device=.  Returns an ops.DeviceCSR (n_fine, n_coarse) with sorted columns.  A fine element with more
+    """transfer_2d on an MI355X (csrc/l2proj2d.hip): kind in B | pseudo | quasi.  fine, coarse: assembly.P1Mesh2D,
+    mesh.Mesh2D (through its p1()), or (p, conn) with device=.  Returns an ops.DeviceCSR (n_fine, n_coarse) with sorted columns.  A fine element with more
     candidates, or a row with more columns, than limits_2d() raises _lib.LmgError: nothing is truncated.  cells: see
     candidates_2d_device."""
     code = _device_kind_2d(kind)
