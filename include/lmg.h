@@ -1052,6 +1052,70 @@ int lmg_mesh2d_rows_fill(int64_t n, int64_t ne, const int32_t *d_conn, const int
 int lmg_csr_identity_rows(int64_t n, const int32_t *d_rowptr, const int32_t *d_colidx, double *d_vals,
                           const uint8_t *d_mask, const double *d_value, double *d_rhs, uint64_t *d_status, void *stream);
 
+/* ---- classical AMG setup: from A to P with nothing else given (csrc/amg.hip; the stages: amg.py) ------------------------------
+ * What pyamg.ruge_stuben_solver does on the host in the reference's experiment scripts (test_pyAMG.py), with the PMIS split in
+ * place of Ruge-Stueben's sequential passes.  The rules: DESIGN.md section 3, "Classical AMG setup".  A: sorted, duplicate-free
+ * CSR on the device, n < 2^31 - 257.  One lane per row, no atomics, no scratch; two calls give the same integers and bits.
+ * Every pointer an entry point names must be non-null (LMG_ERR_ARG, nothing launched) -- a matrix without entries hands in
+ * any valid address for its entry arrays --, theta and trunc lie in [0, 1], omega is finite.  n == 0: LMG_OK.
+ *   strength    m_ij = -sign(a_ii) a_ij, j != i; j is strong iff m_ij > 0 and m_ij >= theta * max_k m_ik.  count: entries per
+ *               row of S (0 for a row with no or a zero diagonal); the caller scans them (lmg_exclusive_scan_i32); fill: the
+ *               strong columns in A's order.
+ *   pmis_keys   d_count[i] = row length of S^T (how many rows i is strong for), d_state[i] = LMG_AMG_FINE0 for an empty row of
+ *               S, else LMG_AMG_UNDECIDED, d_is_coarse[i] = 0.
+ *   pmis_select d_flag[i] = 1 iff i is undecided and (count, hash, index) of i exceeds that of every undecided neighbour in
+ *               S_i and S^T_i, compared lexicographically; hash: x ^= x >> 16, x *= 0x7feb352d, x ^= x >> 15,
+ *               x *= 0x846ca68b, x ^= x >> 16 on uint32.
+ *   pmis_update a flagged node becomes LMG_AMG_COARSE, another undecided node with a flagged j in S_i LMG_AMG_FINE;
+ *               d_is_coarse[i] = 1 | 0 for every i; d_block_undecided[b], b < lmg_amg_pmis_blocks(n): the undecided nodes left
+ *               among rows 256 b .. 256 b + 255.  The host sums them and launches the next round while the sum is positive.
+ *   interp      direct interpolation into P (n x n_c).  d_rank[i]: the number of coarse nodes below i.  A coarse row: 1.0 at
+ *               rank[i].  A fine row i with C_i = S_i and coarse: d = a_ii + (sum of the a_ik, k != i, of a_ii's sign),
+ *               alpha = (sum of the a_ik of the other sign) / (sum over C_i), P_ij = -(alpha a_ij) / d at column rank[j],
+ *               sums in storage order.  FINE0 rows and fine rows with an empty C_i stay empty.  d zero or not finite: refused
+ *               through d_status (ONE 64-bit word set to UINT64_MAX by the caller, row << 8 | LMG_AMG_PIVOT by an atomic
+ *               minimum, as for lmg_nmg2d_check).  count: entries per row; fill: after the caller's scan.
+ *   smooth      one Jacobi step on P with truncation, AP = A P from lmg_spgemm_*: a fine row takes the pattern of AP_i and
+ *               v_c = P_ic - (omega AP_ic) / a_ii (P_ic = 0 where absent); entries with |v_c| < trunc * max_c |v_c| leave, the
+ *               others are multiplied by (sum of all v_c) / (sum of the kept) unless that sum is 0.  Coarse rows stay 1.0 at
+ *               rank[i], FINE0 rows empty.  count: entries per row; fill: after the caller's scan. */
+typedef enum {
+    LMG_AMG_UNDECIDED = 0,
+    LMG_AMG_COARSE = 1,
+    LMG_AMG_FINE = 2,
+    LMG_AMG_FINE0 = 3 /* a row with no strong entry: fine at once, never coarse, empty row of P */
+} lmg_amg_state;
+typedef enum {
+    LMG_AMG_PIVOT = 1 /* d_i of a fine row is zero or not finite */
+} lmg_amg_rule;
+int lmg_amg_strength_count(int64_t n, const int32_t *d_rowptr, const int32_t *d_colidx, const double *d_vals, double theta,
+                           int32_t *d_rownnz, void *stream);
+int lmg_amg_strength_fill(int64_t n, const int32_t *d_rowptr, const int32_t *d_colidx, const double *d_vals, double theta,
+                          const int32_t *d_s_rowptr, int32_t *d_s_colidx, void *stream);
+int lmg_amg_pmis_keys(int64_t n, const int32_t *d_s_rowptr, const int32_t *d_st_rowptr, int32_t *d_count, int32_t *d_state,
+                      int32_t *d_is_coarse, void *stream);
+int lmg_amg_pmis_select(int64_t n, const int32_t *d_s_rowptr, const int32_t *d_s_colidx, const int32_t *d_st_rowptr,
+                        const int32_t *d_st_colidx, const int32_t *d_count, const int32_t *d_state, int32_t *d_flag,
+                        void *stream);
+int64_t lmg_amg_pmis_blocks(int64_t n);
+int lmg_amg_pmis_update(int64_t n, const int32_t *d_s_rowptr, const int32_t *d_s_colidx, const int32_t *d_flag,
+                        int32_t *d_state, int32_t *d_is_coarse, int32_t *d_block_undecided, void *stream);
+int lmg_amg_interp_count(int64_t n, const int32_t *d_s_rowptr, const int32_t *d_s_colidx, const int32_t *d_state,
+                         int32_t *d_rownnz, void *stream);
+int lmg_amg_interp_fill(int64_t n, const int32_t *d_rowptr, const int32_t *d_colidx, const double *d_vals,
+                        const int32_t *d_s_rowptr, const int32_t *d_s_colidx, const int32_t *d_state, const int32_t *d_rank,
+                        const int32_t *d_p_rowptr, int32_t *d_p_colidx, double *d_p_vals, uint64_t *d_status, void *stream);
+int lmg_amg_smooth_count(int64_t n, const int32_t *d_rowptr, const int32_t *d_colidx, const double *d_vals,
+                         const int32_t *d_p_rowptr, const int32_t *d_p_colidx, const double *d_p_vals,
+                         const int32_t *d_ap_rowptr, const int32_t *d_ap_colidx, const double *d_ap_vals,
+                         const int32_t *d_state, const int32_t *d_rank, double omega, double trunc, int32_t *d_rownnz,
+                         void *stream);
+int lmg_amg_smooth_fill(int64_t n, const int32_t *d_rowptr, const int32_t *d_colidx, const double *d_vals,
+                        const int32_t *d_p_rowptr, const int32_t *d_p_colidx, const double *d_p_vals,
+                        const int32_t *d_ap_rowptr, const int32_t *d_ap_colidx, const double *d_ap_vals,
+                        const int32_t *d_state, const int32_t *d_rank, double omega, double trunc,
+                        const int32_t *d_q_rowptr, int32_t *d_q_colidx, double *d_q_vals, void *stream);
+
 /* ---- hipGraph capture of a launch sequence (one V-cycle) -----------------------------
  * begin/end bracket launches issued on `stream`; end returns an opaque executable graph. */
 int lmg_graph_begin(void *stream);

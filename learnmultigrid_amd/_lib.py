@@ -179,6 +179,16 @@ SIGNATURES = {
     "lmg_mesh2d_rows_count": (_c.c_int, [_i64, _i64, _p, _p, _p, _p, _p]),
     "lmg_mesh2d_rows_fill": (_c.c_int, [_i64, _i64, _p, _p, _p, _i64, _i32, _p, _p, _p]),
     "lmg_csr_identity_rows": (_c.c_int, [_i64, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "lmg_amg_strength_count": (_c.c_int, [_i64, _p, _p, _p, _f64, _p, _p]),
+    "lmg_amg_strength_fill": (_c.c_int, [_i64, _p, _p, _p, _f64, _p, _p, _p]),
+    "lmg_amg_pmis_keys": (_c.c_int, [_i64, _p, _p, _p, _p, _p, _p]),
+    "lmg_amg_pmis_select": (_c.c_int, [_i64, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "lmg_amg_pmis_blocks": (_i64, [_i64]),
+    "lmg_amg_pmis_update": (_c.c_int, [_i64, _p, _p, _p, _p, _p, _p, _p]),
+    "lmg_amg_interp_count": (_c.c_int, [_i64, _p, _p, _p, _p, _p]),
+    "lmg_amg_interp_fill": (_c.c_int, [_i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "lmg_amg_smooth_count": (_c.c_int, [_i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _f64, _f64, _p, _p]),
+    "lmg_amg_smooth_fill": (_c.c_int, [_i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _f64, _f64, _p, _p, _p, _p]),
     "lmg_graph_begin": (_c.c_int, [_p]),
     "lmg_graph_end": (_c.c_int, [_p, _c.POINTER(_p)]),
     "lmg_graph_launch": (_c.c_int, [_p, _p]),

@@ -98,7 +98,9 @@ class Level:
 
 
 class Hierarchy:
-    """levels[0] is the fine grid; transfers[l] (n_l x n_{l+1}) prolongates level l+1 -> l."""
+    """levels[0] is the fine grid; transfers[l] (n_l x n_{l+1}) prolongates level l+1 -> l.  transfers: a list of matrices
+    (anything SciPy takes, or ops.DeviceCSR with sorted, duplicate-free rows, used as they are), or a callable
+    f(l, A_l) -> P or None (_each_transfer)."""
 
     def __init__(self, A, transfers, device, coarse_refine="auto", verbose=False, ops_mod=None,
                  use_packed=True, coarse_solver="auto", spgemm_record="lazy", mass=None, cycle_values="f64"):
@@ -142,13 +144,14 @@ class Hierarchy:
             self.levels[0].M = mass if isinstance(mass, DeviceCSR) else DeviceCSR.from_scipy(_to_csr_host(mass), self.device)
             if self.levels[0].M.shape != A0.shape:
                 raise ValueError("mass matrix %s does not match the operator %s" % (self.levels[0].M.shape, A0.shape))
-        for P in transfers:
+        for P in self._each_transfer(transfers):
             lev = self.levels[-1]
-            Ph = _to_csr_host(P)
+            # a DeviceCSR (sorted, duplicate-free rows) is used as it is: no host copy
+            Ph = P if isinstance(P, DeviceCSR) else _to_csr_host(P)
             if Ph.shape[0] != lev.n:
                 raise ValueError("transfer operator of level %d has %d rows, level has %d unknowns"
                                  % (len(self.levels) - 1, Ph.shape[0], lev.n))
-            lev.P = DeviceCSR.from_scipy(Ph, self.device)
+            lev.P = Ph if isinstance(P, DeviceCSR) else DeviceCSR.from_scipy(Ph, self.device)
             lev.R = lev.P.transpose()
             lev.plan_RA = ops_.SpGEMMPlan(lev.R, lev.A, spgemm_record)
             lev.RA = lev.plan_RA.numeric(lev.R, lev.A)
@@ -172,6 +175,18 @@ class Hierarchy:
         self._cheby = None             # Chebyshev smoother: bounds and coefficient tables (prepare_smoother)
         self._line = None              # "Line" smoother: the (line_dir, line_order) in use (prepare_smoother)
         self._line_band = 1            # ... and the largest half-bandwidth a level may use (line_band)
+
+    def _each_transfer(self, transfers):
+        """The transfers one by one.  A callable f(l, A_l) -> P or None is asked once per level with that level's DeviceCSR,
+        after the level was formed (a setup that builds P from A_l: amg.classical_hierarchy); None ends the coarsening."""
+        if not callable(transfers):
+            yield from transfers
+            return
+        while True:
+            P = transfers(len(self.levels) - 1, self.levels[-1].A)
+            if P is None:
+                return
+            yield P
 
     # ------------------------------------------------------------------ setup ----------
     @property

@@ -1586,6 +1586,100 @@ def nmg2d_cut(A, d_neighs):
     return DeviceCSR(rp, cj, cv, A.shape)
 
 
+# ---- classical AMG setup (csrc/amg.hip; the stages: amg.py) -------------------------------------
+AMG_UNDECIDED, AMG_COARSE, AMG_FINE, AMG_FINE0 = 0, 1, 2, 3          # lmg_amg_state
+AMG_RULES = {1: "pivot"}                                             # lmg_amg_rule
+
+
+def _pe(t):
+    """The address of an entry array for an entry point that refuses null pointers: a matrix without entries hands in a
+    one-element array of its own (an empty tensor has no address)."""
+    return _p(t if t.numel() else torch.empty(1, dtype=t.dtype, device=t.device))
+
+
+def _scan_rows(rownnz, n):
+    """(rowptr (n + 1), total) of the per-row counts: the scan, and the one read back of its last element."""
+    rp = torch.empty(n + 1, dtype=I32, device=rownnz.device)
+    exclusive_scan_i32(rownnz[:n], rp)
+    return rp, int(rp[-1].item())
+
+
+def amg_strength(A, theta):
+    """(s_rowptr, s_colidx) of the strength pattern S of the DeviceCSR A: count, scan, fill."""
+    n, dev, L = A.shape[0], A.device, _lib.lib()
+    rownnz = torch.empty(max(n, 1), dtype=I32, device=dev)
+    check(L.lmg_amg_strength_count(n, _p(A.rowptr), _pe(A.colidx), _pe(A.vals), float(theta), _p(rownnz), _s(A.vals)),
+          "lmg_amg_strength_count")
+    rp, nnz = _scan_rows(rownnz, n)
+    sj = torch.empty(nnz, dtype=I32, device=dev)
+    check(L.lmg_amg_strength_fill(n, _p(A.rowptr), _pe(A.colidx), _pe(A.vals), float(theta), _p(rp), _pe(sj), _s(A.vals)),
+          "lmg_amg_strength_fill")
+    return rp, sj
+
+
+def amg_pmis_keys(S, ST, count, state, is_coarse):
+    _i32_ok(count, state, is_coarse)
+    n = S.shape[0]
+    if ST.shape != S.shape or min(count.numel(), state.numel(), is_coarse.numel()) < n:
+        raise ValueError("amg_pmis_keys: inconsistent array sizes")
+    check(_lib.lib().lmg_amg_pmis_keys(n, _p(S.rowptr), _p(ST.rowptr), _p(count), _p(state), _p(is_coarse), _s(state)),
+          "lmg_amg_pmis_keys")
+
+
+def amg_pmis_round(S, ST, count, state, flag, is_coarse, block_undecided):
+    """One round: select, then update.  block_undecided (amg_pmis_blocks(n) int32) receives the undecided nodes left."""
+    _i32_ok(count, state, flag, is_coarse, block_undecided)
+    n, L = S.shape[0], _lib.lib()
+    if min(count.numel(), state.numel(), flag.numel(), is_coarse.numel()) < n \
+            or block_undecided.numel() < int(L.lmg_amg_pmis_blocks(n)):
+        raise ValueError("amg_pmis_round: inconsistent array sizes")
+    check(L.lmg_amg_pmis_select(n, _p(S.rowptr), _pe(S.colidx), _p(ST.rowptr), _pe(ST.colidx), _p(count), _p(state), _p(flag),
+                                _s(state)), "lmg_amg_pmis_select")
+    check(L.lmg_amg_pmis_update(n, _p(S.rowptr), _pe(S.colidx), _p(flag), _p(state), _p(is_coarse), _p(block_undecided),
+                                _s(state)), "lmg_amg_pmis_update")
+
+
+def amg_pmis_blocks(n):
+    return int(_lib.lib().lmg_amg_pmis_blocks(n))
+
+
+def amg_interp(A, S, state, rank, n_c, status):
+    """Direct interpolation: the DeviceCSR P (n x n_c).  A refusal is left in `status` (nmg2d_status / amg_read_status)."""
+    _i32_ok(state, rank)
+    n, dev, L = A.shape[0], A.device, _lib.lib()
+    if S.shape != A.shape or state.numel() < n or rank.numel() < n:
+        raise ValueError("amg_interp: inconsistent array sizes")
+    rownnz = torch.empty(max(n, 1), dtype=I32, device=dev)
+    check(L.lmg_amg_interp_count(n, _p(S.rowptr), _pe(S.colidx), _p(state), _p(rownnz), _s(state)), "lmg_amg_interp_count")
+    rp, nnz = _scan_rows(rownnz, n)
+    pj, pv = torch.empty(nnz, dtype=I32, device=dev), torch.empty(nnz, dtype=F64, device=dev)
+    check(L.lmg_amg_interp_fill(n, _p(A.rowptr), _pe(A.colidx), _pe(A.vals), _p(S.rowptr), _pe(S.colidx), _p(state), _p(rank),
+                                _p(rp), _pe(pj), _pe(pv), _p(status), _s(state)), "lmg_amg_interp_fill")
+    return DeviceCSR(rp, pj, pv, (n, int(n_c)))
+
+
+def amg_smooth(A, P, AP, state, rank, omega, trunc):
+    """One Jacobi step on P with truncation (AP = A P): the new DeviceCSR P."""
+    _i32_ok(state, rank)
+    n, dev, L = A.shape[0], A.device, _lib.lib()
+    if P.shape[0] != n or AP.shape != P.shape or state.numel() < n or rank.numel() < n:
+        raise ValueError("amg_smooth: inconsistent array sizes")
+    args = (n, _p(A.rowptr), _pe(A.colidx), _pe(A.vals), _p(P.rowptr), _pe(P.colidx), _pe(P.vals), _p(AP.rowptr),
+            _pe(AP.colidx), _pe(AP.vals), _p(state), _p(rank), float(omega), float(trunc))
+    rownnz = torch.empty(max(n, 1), dtype=I32, device=dev)
+    check(L.lmg_amg_smooth_count(*args, _p(rownnz), _s(state)), "lmg_amg_smooth_count")
+    rp, nnz = _scan_rows(rownnz, n)
+    qj, qv = torch.empty(nnz, dtype=I32, device=dev), torch.empty(nnz, dtype=F64, device=dev)
+    check(L.lmg_amg_smooth_fill(*args, _p(rp), _pe(qj), _pe(qv), _s(state)), "lmg_amg_smooth_fill")
+    return DeviceCSR(rp, qj, qv, P.shape)
+
+
+def amg_read_status(status):
+    """None, or (rule name, row) of the first refusal: one read back (it synchronises)."""
+    word = int(status.item())
+    return None if word == -1 else (AMG_RULES.get(word & 0xFF, "rule %d" % (word & 0xFF)), word >> 8)
+
+
 # ---- hipGraph ---------------------------------------------------------------------------------
 class CapturedGraph:
     """A launch sequence captured on the current stream (lmg_graph_*), replayable."""

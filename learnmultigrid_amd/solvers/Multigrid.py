@@ -533,3 +533,52 @@ class NeuralMG_2D(Multigrid):
 
     def solve_many(self, rhs, levels=None, *args, **kw):
         return super().solve_many(rhs, self._levels(levels), *args, **kw)
+
+
+class ClassicalAMG(Multigrid):
+    """Classical AMG from the matrix alone: what the reference's scripts call as their algebraic baseline,
+    `pyamg.ruge_stuben_solver(A, max_levels=2, presmoother=('gauss_seidel', {'iterations': 3}), coarse_solver='splu')`
+    (test_pyAMG.py), with the setup on the device (amg.classical_hierarchy, csrc/amg.hip; the rules: DESIGN.md section 3).
+    The C/F split is PMIS, not Ruge-Stueben's two sequential passes, so the levels differ from pyamg's.
+    theta, split ("pmis" | "greedy"), interp_sweeps, interp_omega, interp_trunc and max_coarse as in classical_hierarchy;
+    max_levels is the default of solve(levels=...), which counts grids as everywhere and is an upper limit here: the
+    coarsening also stops at a level of at most max_coarse rows.  solve, v_cycle / w_cycle / f_cycle and solve_many are the
+    inherited ones; level_dims reports the sizes, hierarchy_info() the setup."""
+
+    def __init__(self, matrix, rhs, *, theta=0.25, split="pmis", interp_sweeps=1, interp_omega=1.0, interp_trunc=0.2,
+                 max_coarse=500, max_levels=10, **kw):
+        super().__init__(matrix, rhs, **kw)
+        self._log("Selected Classical AMG")
+        self.label = "ClassicalAMG"
+        self.max_levels = int(max_levels)
+        self._amg = dict(theta=theta, split=split, interp_sweeps=interp_sweeps, interp_omega=interp_omega,
+                         interp_trunc=interp_trunc, max_coarse=max_coarse)
+
+    def _setup(self, levels, first_call, coarse_refine):
+        from ..amg import classical_hierarchy
+        key = (levels, id(self.matrix), str(coarse_refine), tuple(sorted(self._amg.items())))
+        if self._hier is None or self._hier_key != key:
+            H = classical_hierarchy(sp.csr_matrix(self.matrix), self._device, max_levels=levels,
+                                    coarse_refine=coarse_refine, verbose=self.verbose, **self._amg)
+            if len(H.levels) < 2:
+                raise ValueError("classical AMG found no coarse level for this matrix (%d rows, max_coarse=%d, n_c=%s): "
+                                 "nothing to cycle on" % (H.levels[0].n, self._amg["max_coarse"], H.amg_info[0]["n_c"]))
+            self._hier, self._hier_key = H, key
+        return self._hier
+
+    @on_device
+    def setup(self, levels=None, coarse_refine="auto"):
+        """The Hierarchy solve(levels) would run on, built now: a preconditioner= for CG and GMRES."""
+        return self._setup(self.max_levels if levels is None else levels, False, coarse_refine)
+
+    def hierarchy_info(self, levels=None):
+        """{"levels": [per level n, nnz, n_c, rounds], "operator_complexity", "grid_complexity"} (amg.hierarchy_info) of the
+        hierarchy in use, built first where there is none."""
+        from ..amg import hierarchy_info
+        return hierarchy_info(self._hier if self._hier is not None and levels is None else self.setup(levels))
+
+    def solve(self, levels=None, *args, **kw):
+        super().solve(self.max_levels if levels is None else levels, *args, **kw)
+
+    def solve_many(self, rhs, levels=None, *args, **kw):
+        return super().solve_many(rhs, self.max_levels if levels is None else levels, *args, **kw)

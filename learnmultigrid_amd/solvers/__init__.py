@@ -4,7 +4,7 @@ from .Jacobi import Jacobi
 from .GaussSeidel import GaussSeidel
 from .CG import CG
 from .GMRES import GMRES
-from .Multigrid import Multigrid, GeometricMG, SemiGeometricMG, HierarchyMG, NeuralMG, NeuralMG_2D
+from .Multigrid import Multigrid, GeometricMG, SemiGeometricMG, HierarchyMG, NeuralMG, NeuralMG_2D, ClassicalAMG
 
 __all__ = ["Solver", "DirectSolver", "IterativeSolver", "Jacobi", "GaussSeidel", "CG", "GMRES", "Multigrid",
-           "GeometricMG", "SemiGeometricMG", "HierarchyMG", "NeuralMG", "NeuralMG_2D"]
+           "GeometricMG", "SemiGeometricMG", "HierarchyMG", "NeuralMG", "NeuralMG_2D", "ClassicalAMG"]
