@@ -1086,7 +1086,9 @@ typedef enum {
     LMG_AMG_FINE0 = 3 /* a row with no strong entry: fine at once, never coarse, empty row of P */
 } lmg_amg_state;
 typedef enum {
-    LMG_AMG_PIVOT = 1 /* d_i of a fine row is zero or not finite */
+    LMG_AMG_PIVOT = 1,     /* d_i of a fine row is zero or not finite */
+    LMG_AMG_CANDIDATE = 2, /* lmg_sa_norms: the candidate's sum of squares over an aggregate is zero or not finite */
+    LMG_AMG_MEMBERS = 3    /* lmg_sa_norms: the member list of an aggregate does not ascend (order: the aggregate) */
 } lmg_amg_rule;
 int lmg_amg_strength_count(int64_t n, const int32_t *d_rowptr, const int32_t *d_colidx, const double *d_vals, double theta,
                            int32_t *d_rownnz, void *stream);
@@ -1115,6 +1117,77 @@ int lmg_amg_smooth_fill(int64_t n, const int32_t *d_rowptr, const int32_t *d_col
                         const int32_t *d_ap_rowptr, const int32_t *d_ap_colidx, const double *d_ap_vals,
                         const int32_t *d_state, const int32_t *d_rank, double omega, double trunc,
                         const int32_t *d_q_rowptr, int32_t *d_q_colidx, double *d_q_vals, void *stream);
+
+/* ---- smoothed-aggregation setup: from A and one candidate B to the tentative prolongator (csrc/sa.hip; the stages:
+ * aggregation.py).  What pyamg.smoothed_aggregation_solver does on the host, with MIS-2 aggregates in place of pyamg's sequential
+ * standard aggregation.  The rules: DESIGN.md section 3, "Smoothed aggregation setup".  A: sorted, duplicate-free CSR on the
+ * device, n < 2^31 - 257.  One lane per row (lmg_sa_norms: per aggregate), no atomics but the refusals, no scratch; every kernel
+ * reads what an earlier launch wrote and writes its own lane's entries, so two calls give the same integers and bits.  Every
+ * pointer an entry point names must be non-null (LMG_ERR_ARG, nothing launched), theta lies in [0, 1].  n == 0: LMG_OK.
+ *   diagonal    d_diag[i] = the stored a_ii, 0.0 where there is none.
+ *   strength    j is strong in row i iff j != i, a_ij != 0, a_ii != 0, a_jj != 0 and a_ij a_ij >= (theta theta) |a_ii a_jj|,
+ *               every product rounded on its own.  count: entries per row of S; fill: the strong columns in A's order, after the
+ *               caller's scan.  A node whose row of S is empty is isolated.
+ *   graph       G_i = the ascending merge of S_i and S^T_i (lmg_csr_transpose_*) without i and without isolated nodes; empty
+ *               for an isolated i.  count / fill as above.
+ *   mis2_init   d_state[i] = LMG_SA_ISOLATED for an empty row of S, else LMG_SA_UNDECIDED; d_is_root[i] = 0.
+ *   mis2_t1     d_t1[i] = the undecided node of the largest key in N[i] = {i} u G_i, or -1.  Key: (row length of G, hash, index),
+ *               compared lexicographically, the hash of lmg_amg_pmis_select.
+ *   mis2_t2     d_flag[i] = 1 iff i is undecided and the node of the largest key among d_t1[j], j in N[i], is i.
+ *   mis2_c1     d_c1[i] = 1 iff some node of N[i] is flagged.
+ *   mis2_update a flagged node becomes LMG_SA_ROOT, another undecided node with some d_c1[j], j in N[i], LMG_SA_COVERED;
+ *               d_is_root[i] = 1 | 0 for every i; d_block_undecided[b], b < lmg_sa_blocks(n): the undecided nodes left among
+ *               rows 256 b .. 256 b + 255.  The host sums them and launches the next round while the sum is positive.
+ *   assign1     d_rank[i]: the number of roots below i.  A root: d_a1[i] = d_rank[i]; a covered node with roots in G_i: the
+ *               rank of the one of the largest key; every other node -1.
+ *   assign2     d_a2[i] = d_a1[i] where that is >= 0 or i is isolated, else d_a1[j] of the largest-key j in G_i with
+ *               d_a1[j] >= 0 (-1 without one).  d_a1 != d_a2.
+ *   tentative   count: 1 for a row with 0 <= d_agg[i] < n_agg, else 0.  pattern, after the caller's scan: column d_agg[i], value
+ *               d_cand[i] -- the transpose of this matrix lists the members of every aggregate with their candidate values.
+ *               fill: d_t_vals = d_cand[i] / d_coarse_cand[d_agg[i]] on the same pattern.
+ *   norms       one lane per aggregate j on that transpose: s = the sum of the squared values in storage order,
+ *               d_coarse_cand[j] = sqrt(s).  s zero or not finite: refused through d_status (as lmg_amg_interp_fill) with the
+ *               first member row and LMG_AMG_CANDIDATE; a member list that does not ascend: the aggregate and LMG_AMG_MEMBERS.
+ *   row_states  d_state[i] = LMG_AMG_FINE for a row of T with an entry, else LMG_AMG_FINE0: what lmg_amg_smooth_* reads for
+ *               the Jacobi step on T (omega = omega_sa / rho, trunc = 0). */
+typedef enum {
+    LMG_SA_UNDECIDED = 0,
+    LMG_SA_ROOT = 1,
+    LMG_SA_COVERED = 2, /* within two edges of a root */
+    LMG_SA_ISOLATED = 3 /* an empty row of S: no aggregate, never a neighbour, empty row of P */
+} lmg_sa_state;
+int lmg_sa_diagonal(int64_t n, const int32_t *d_rowptr, const int32_t *d_colidx, const double *d_vals, double *d_diag,
+                    void *stream);
+int lmg_sa_strength_count(int64_t n, const int32_t *d_rowptr, const int32_t *d_colidx, const double *d_vals,
+                          const double *d_diag, double theta, int32_t *d_rownnz, void *stream);
+int lmg_sa_strength_fill(int64_t n, const int32_t *d_rowptr, const int32_t *d_colidx, const double *d_vals,
+                         const double *d_diag, double theta, const int32_t *d_s_rowptr, int32_t *d_s_colidx, void *stream);
+int lmg_sa_graph_count(int64_t n, const int32_t *d_s_rowptr, const int32_t *d_s_colidx, const int32_t *d_st_rowptr,
+                       const int32_t *d_st_colidx, int32_t *d_rownnz, void *stream);
+int lmg_sa_graph_fill(int64_t n, const int32_t *d_s_rowptr, const int32_t *d_s_colidx, const int32_t *d_st_rowptr,
+                      const int32_t *d_st_colidx, const int32_t *d_g_rowptr, int32_t *d_g_colidx, void *stream);
+int lmg_sa_mis2_init(int64_t n, const int32_t *d_s_rowptr, int32_t *d_state, int32_t *d_is_root, void *stream);
+int lmg_sa_mis2_t1(int64_t n, const int32_t *d_g_rowptr, const int32_t *d_g_colidx, const int32_t *d_state, int32_t *d_t1,
+                   void *stream);
+int lmg_sa_mis2_t2(int64_t n, const int32_t *d_g_rowptr, const int32_t *d_g_colidx, const int32_t *d_state,
+                   const int32_t *d_t1, int32_t *d_flag, void *stream);
+int lmg_sa_mis2_c1(int64_t n, const int32_t *d_g_rowptr, const int32_t *d_g_colidx, const int32_t *d_state,
+                   const int32_t *d_flag, int32_t *d_c1, void *stream);
+int64_t lmg_sa_blocks(int64_t n);
+int lmg_sa_mis2_update(int64_t n, const int32_t *d_g_rowptr, const int32_t *d_g_colidx, const int32_t *d_flag,
+                       const int32_t *d_c1, int32_t *d_state, int32_t *d_is_root, int32_t *d_block_undecided, void *stream);
+int lmg_sa_assign1(int64_t n, const int32_t *d_g_rowptr, const int32_t *d_g_colidx, const int32_t *d_state,
+                   const int32_t *d_rank, int32_t *d_a1, void *stream);
+int lmg_sa_assign2(int64_t n, const int32_t *d_g_rowptr, const int32_t *d_g_colidx, const int32_t *d_state,
+                   const int32_t *d_a1, int32_t *d_a2, void *stream);
+int lmg_sa_tentative_count(int64_t n, int64_t n_agg, const int32_t *d_agg, int32_t *d_rownnz, void *stream);
+int lmg_sa_tentative_pattern(int64_t n, int64_t n_agg, const int32_t *d_agg, const double *d_cand, const int32_t *d_t_rowptr,
+                             int32_t *d_t_colidx, double *d_t_vals, void *stream);
+int lmg_sa_norms(int64_t n_agg, const int32_t *d_m_rowptr, const int32_t *d_m_colidx, const double *d_m_vals,
+                 double *d_coarse_cand, uint64_t *d_status, void *stream);
+int lmg_sa_tentative_fill(int64_t n, int64_t n_agg, const int32_t *d_agg, const double *d_cand, const double *d_coarse_cand,
+                          const int32_t *d_t_rowptr, double *d_t_vals, void *stream);
+int lmg_sa_row_states(int64_t n, const int32_t *d_t_rowptr, int32_t *d_state, void *stream);
 
 /* ---- hipGraph capture of a launch sequence (one V-cycle) -----------------------------
  * begin/end bracket launches issued on `stream`; end returns an opaque executable graph. */

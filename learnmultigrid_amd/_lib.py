@@ -189,6 +189,24 @@ SIGNATURES = {
     "lmg_amg_interp_fill": (_c.c_int, [_i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "lmg_amg_smooth_count": (_c.c_int, [_i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _f64, _f64, _p, _p]),
     "lmg_amg_smooth_fill": (_c.c_int, [_i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _f64, _f64, _p, _p, _p, _p]),
+    "lmg_sa_diagonal": (_c.c_int, [_i64, _p, _p, _p, _p, _p]),
+    "lmg_sa_strength_count": (_c.c_int, [_i64, _p, _p, _p, _p, _f64, _p, _p]),
+    "lmg_sa_strength_fill": (_c.c_int, [_i64, _p, _p, _p, _p, _f64, _p, _p, _p]),
+    "lmg_sa_graph_count": (_c.c_int, [_i64, _p, _p, _p, _p, _p, _p]),
+    "lmg_sa_graph_fill": (_c.c_int, [_i64, _p, _p, _p, _p, _p, _p, _p]),
+    "lmg_sa_mis2_init": (_c.c_int, [_i64, _p, _p, _p, _p]),
+    "lmg_sa_mis2_t1": (_c.c_int, [_i64, _p, _p, _p, _p, _p]),
+    "lmg_sa_mis2_t2": (_c.c_int, [_i64, _p, _p, _p, _p, _p, _p]),
+    "lmg_sa_mis2_c1": (_c.c_int, [_i64, _p, _p, _p, _p, _p, _p]),
+    "lmg_sa_blocks": (_i64, [_i64]),
+    "lmg_sa_mis2_update": (_c.c_int, [_i64, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "lmg_sa_assign1": (_c.c_int, [_i64, _p, _p, _p, _p, _p, _p]),
+    "lmg_sa_assign2": (_c.c_int, [_i64, _p, _p, _p, _p, _p, _p]),
+    "lmg_sa_tentative_count": (_c.c_int, [_i64, _i64, _p, _p, _p]),
+    "lmg_sa_tentative_pattern": (_c.c_int, [_i64, _i64, _p, _p, _p, _p, _p, _p]),
+    "lmg_sa_norms": (_c.c_int, [_i64, _p, _p, _p, _p, _p, _p]),
+    "lmg_sa_tentative_fill": (_c.c_int, [_i64, _i64, _p, _p, _p, _p, _p, _p]),
+    "lmg_sa_row_states": (_c.c_int, [_i64, _p, _p, _p]),
     "lmg_graph_begin": (_c.c_int, [_p]),
     "lmg_graph_end": (_c.c_int, [_p, _c.POINTER(_p)]),
     "lmg_graph_launch": (_c.c_int, [_p, _p]),

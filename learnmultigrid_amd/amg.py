@@ -27,9 +27,12 @@ SPLITS = ("pmis", "greedy")
 class Refused(ValueError):
     """A matrix the rules cannot take: .rule (ops.AMG_RULES) and .row."""
 
+    WHY = {"candidate": "smoothed-aggregation setup refuses row %d: %s (the candidate's sum of squares over the row's "
+                        "aggregate is zero or not finite)"}
+
     def __init__(self, rule, row):
-        super().__init__("classical AMG setup refuses row %d: %s (d_i = a_ii + the couplings of its sign is zero or not "
-                         "finite)" % (row, rule))
+        super().__init__(self.WHY.get(rule, "classical AMG setup refuses row %d: %s (d_i = a_ii + the couplings of its sign "
+                                            "is zero or not finite)") % (row, rule))
         self.rule, self.row = rule, int(row)
 
 

@@ -1588,7 +1588,7 @@ def nmg2d_cut(A, d_neighs):
 
 # ---- classical AMG setup (csrc/amg.hip; the stages: amg.py) -------------------------------------
 AMG_UNDECIDED, AMG_COARSE, AMG_FINE, AMG_FINE0 = 0, 1, 2, 3          # lmg_amg_state
-AMG_RULES = {1: "pivot"}                                             # lmg_amg_rule
+AMG_RULES = {1: "pivot", 2: "candidate", 3: "members"}                 # lmg_amg_rule
 
 
 def _pe(t):
@@ -1678,6 +1678,117 @@ def amg_read_status(status):
     """None, or (rule name, row) of the first refusal: one read back (it synchronises)."""
     word = int(status.item())
     return None if word == -1 else (AMG_RULES.get(word & 0xFF, "rule %d" % (word & 0xFF)), word >> 8)
+
+
+# ---- smoothed-aggregation setup (csrc/sa.hip; the stages: aggregation.py) ------------------------
+SA_UNDECIDED, SA_ROOT, SA_COVERED, SA_ISOLATED = 0, 1, 2, 3          # lmg_sa_state
+
+
+def _count_scan_fill(n, dev, count, fill):
+    """(rowptr, colidx) of a pattern built in the usual three steps: count(rownnz), the scan, fill(rowptr, colidx)."""
+    rownnz = torch.empty(max(n, 1), dtype=I32, device=dev)
+    count(rownnz)
+    rp, nnz = _scan_rows(rownnz, n)
+    cj = torch.empty(nnz, dtype=I32, device=dev)
+    fill(rp, cj)
+    return rp, cj
+
+
+def sa_strength(A, theta):
+    """(s_rowptr, s_colidx) of the symmetric strength pattern S of the DeviceCSR A: the diagonal, count, scan, fill."""
+    n, dev, L = A.shape[0], A.device, _lib.lib()
+    diag = torch.empty(max(n, 1), dtype=F64, device=dev)
+    a = (n, _p(A.rowptr), _pe(A.colidx), _pe(A.vals))
+    check(L.lmg_sa_diagonal(*a, _p(diag), _s(A.vals)), "lmg_sa_diagonal")
+    return _count_scan_fill(
+        n, dev,
+        lambda c: check(L.lmg_sa_strength_count(*a, _p(diag), float(theta), _p(c), _s(A.vals)), "lmg_sa_strength_count"),
+        lambda rp, sj: check(L.lmg_sa_strength_fill(*a, _p(diag), float(theta), _p(rp), _pe(sj), _s(A.vals)),
+                             "lmg_sa_strength_fill"))
+
+
+def sa_graph(S, ST):
+    """(g_rowptr, g_colidx) of the aggregation graph: the merge of the rows of S and ST = S^T without isolated nodes."""
+    n, L = S.shape[0], _lib.lib()
+    if ST.shape != S.shape:
+        raise ValueError("sa_graph: inconsistent array sizes")
+    a = (n, _p(S.rowptr), _pe(S.colidx), _p(ST.rowptr), _pe(ST.colidx))
+    return _count_scan_fill(
+        n, S.device,
+        lambda c: check(L.lmg_sa_graph_count(*a, _p(c), _s(c)), "lmg_sa_graph_count"),
+        lambda rp, gj: check(L.lmg_sa_graph_fill(*a, _p(rp), _pe(gj), _s(rp)), "lmg_sa_graph_fill"))
+
+
+def sa_blocks(n):
+    return int(_lib.lib().lmg_sa_blocks(n))
+
+
+def sa_mis2_init(S, state, is_root):
+    _i32_ok(state, is_root)
+    n = S.shape[0]
+    if min(state.numel(), is_root.numel()) < n:
+        raise ValueError("sa_mis2_init: inconsistent array sizes")
+    check(_lib.lib().lmg_sa_mis2_init(n, _p(S.rowptr), _p(state), _p(is_root), _s(state)), "lmg_sa_mis2_init")
+
+
+def sa_mis2_round(G, state, t1, flag, c1, is_root, block_undecided):
+    """One round: t1, t2, c1, update.  block_undecided (sa_blocks(n) int32) receives the undecided nodes left."""
+    _i32_ok(state, t1, flag, c1, is_root, block_undecided)
+    n, L = G.shape[0], _lib.lib()
+    if min(state.numel(), t1.numel(), flag.numel(), c1.numel(), is_root.numel()) < n \
+            or block_undecided.numel() < int(L.lmg_sa_blocks(n)):
+        raise ValueError("sa_mis2_round: inconsistent array sizes")
+    g, st = (n, _p(G.rowptr), _pe(G.colidx)), _s(state)
+    check(L.lmg_sa_mis2_t1(*g, _p(state), _p(t1), st), "lmg_sa_mis2_t1")
+    check(L.lmg_sa_mis2_t2(*g, _p(state), _p(t1), _p(flag), st), "lmg_sa_mis2_t2")
+    check(L.lmg_sa_mis2_c1(*g, _p(state), _p(flag), _p(c1), st), "lmg_sa_mis2_c1")
+    check(L.lmg_sa_mis2_update(*g, _p(flag), _p(c1), _p(state), _p(is_root), _p(block_undecided), st), "lmg_sa_mis2_update")
+
+
+def sa_assign(G, state, rank, a1, a2):
+    """The two assignment phases: a1 (roots and their neighbours), then a2 (the nodes two edges from a root)."""
+    _i32_ok(state, rank, a1, a2)
+    n, L = G.shape[0], _lib.lib()
+    if min(state.numel(), rank.numel(), a1.numel(), a2.numel()) < n:
+        raise ValueError("sa_assign: inconsistent array sizes")
+    g, st = (n, _p(G.rowptr), _pe(G.colidx)), _s(state)
+    check(L.lmg_sa_assign1(*g, _p(state), _p(rank), _p(a1), st), "lmg_sa_assign1")
+    check(L.lmg_sa_assign2(*g, _p(state), _p(a1), _p(a2), st), "lmg_sa_assign2")
+
+
+def sa_tentative(agg, n_agg, B, status):
+    """(T, Bc): the tentative prolongator (n x n_agg DeviceCSR, one entry per aggregated row) of the candidate B and the
+    coarse candidate.  A refusal is left in `status` (nmg2d_status / amg_read_status)."""
+    _i32_ok(agg)
+    _vec_ok(B)
+    n, dev, L = B.numel(), B.device, _lib.lib()
+    n_agg = int(n_agg)
+    if agg.numel() < n or not 0 < n_agg <= n:
+        raise ValueError("sa_tentative: inconsistent array sizes")
+    st = _s(B)
+    vals = []
+
+    def pattern(rp, tj):
+        vals.append(torch.empty(tj.numel(), dtype=F64, device=dev))
+        check(L.lmg_sa_tentative_pattern(n, n_agg, _p(agg), _p(B), _p(rp), _pe(tj), _pe(vals[0]), st), "lmg_sa_tentative_pattern")
+
+    rp, tj = _count_scan_fill(n, dev, lambda c: check(L.lmg_sa_tentative_count(n, n_agg, _p(agg), _p(c), st),
+                                                      "lmg_sa_tentative_count"), pattern)
+    members = DeviceCSR(rp, tj, vals[0], (n, n_agg)).transpose()
+    Bc = torch.empty(n_agg, dtype=F64, device=dev)
+    check(L.lmg_sa_norms(n_agg, _p(members.rowptr), _pe(members.colidx), _pe(members.vals), _p(Bc), _p(status), st),
+          "lmg_sa_norms")
+    tv = torch.empty_like(vals[0])
+    check(L.lmg_sa_tentative_fill(n, n_agg, _p(agg), _p(B), _p(Bc), _p(rp), _pe(tv), st), "lmg_sa_tentative_fill")
+    return DeviceCSR(rp, tj, tv, (n, n_agg)), Bc
+
+
+def sa_row_states(T):
+    """int32 per row of T: AMG_FINE where the row has an entry, AMG_FINE0 where it is empty (what amg_smooth reads)."""
+    n = T.shape[0]
+    state = torch.empty(max(n, 1), dtype=I32, device=T.device)
+    check(_lib.lib().lmg_sa_row_states(n, _p(T.rowptr), _p(state), _s(state)), "lmg_sa_row_states")
+    return state
 
 
 # ---- hipGraph ---------------------------------------------------------------------------------

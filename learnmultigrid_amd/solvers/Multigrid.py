@@ -554,15 +554,24 @@ class ClassicalAMG(Multigrid):
         self._amg = dict(theta=theta, split=split, interp_sweeps=interp_sweeps, interp_omega=interp_omega,
                          interp_trunc=interp_trunc, max_coarse=max_coarse)
 
-    def _setup(self, levels, first_call, coarse_refine):
+    _METHOD, _COUNT = "classical AMG", "n_c"          # for the "no coarse level" message
+
+    def _build_hierarchy(self, levels, coarse_refine):
         from ..amg import classical_hierarchy
-        key = (levels, id(self.matrix), str(coarse_refine), tuple(sorted(self._amg.items())))
+        return classical_hierarchy(sp.csr_matrix(self.matrix), self._device, max_levels=levels,
+                                   coarse_refine=coarse_refine, verbose=self.verbose, **self._amg)
+
+    def _setup_key(self):
+        return tuple(sorted(self._amg.items()))
+
+    def _setup(self, levels, first_call, coarse_refine):
+        key = (levels, id(self.matrix), str(coarse_refine), self._setup_key())
         if self._hier is None or self._hier_key != key:
-            H = classical_hierarchy(sp.csr_matrix(self.matrix), self._device, max_levels=levels,
-                                    coarse_refine=coarse_refine, verbose=self.verbose, **self._amg)
+            H = self._build_hierarchy(levels, coarse_refine)
             if len(H.levels) < 2:
-                raise ValueError("classical AMG found no coarse level for this matrix (%d rows, max_coarse=%d, n_c=%s): "
-                                 "nothing to cycle on" % (H.levels[0].n, self._amg["max_coarse"], H.amg_info[0]["n_c"]))
+                raise ValueError("%s found no coarse level for this matrix (%d rows, max_coarse=%d, %s=%s): "
+                                 "nothing to cycle on" % (self._METHOD, H.levels[0].n, self._amg["max_coarse"], self._COUNT,
+                                                          H.amg_info[0][self._COUNT]))
             self._hier, self._hier_key = H, key
         return self._hier
 
@@ -582,3 +591,36 @@ class ClassicalAMG(Multigrid):
 
     def solve_many(self, rhs, levels=None, *args, **kw):
         return super().solve_many(rhs, self.max_levels if levels is None else levels, *args, **kw)
+
+
+class SmoothedAggregationAMG(ClassicalAMG):
+    """Smoothed-aggregation AMG from the matrix and one near-nullspace candidate: what a pyamg user calls as
+    `pyamg.smoothed_aggregation_solver(A, B)`, with the setup on the device (aggregation.sa_hierarchy, csrc/sa.hip; the
+    rules: DESIGN.md section 3).  The aggregates grow around MIS-2 roots, not by pyamg's sequential standard aggregation, and
+    the Jacobi step on the tentative prolongator is scaled by the Gershgorin bound, so the levels differ from pyamg's
+    (INTEGRATION.md).  theta, B (an n-vector, default ones), omega and max_coarse as in sa_hierarchy; max_levels, setup(),
+    hierarchy_info(), solve, the cycle methods and solve_many as for ClassicalAMG."""
+
+    _METHOD, _COUNT = "smoothed aggregation", "n_agg"
+
+    def __init__(self, matrix, rhs, *, theta=0.0, B=None, omega=4.0 / 3.0, max_coarse=500, max_levels=10, **kw):
+        Multigrid.__init__(self, matrix, rhs, **kw)
+        self._log("Selected Smoothed Aggregation AMG")
+        self.label = "SmoothedAggregationAMG"
+        self.max_levels = int(max_levels)
+        self._amg = dict(theta=theta, omega=omega, max_coarse=max_coarse)
+        self._candidate = B
+
+    def _build_hierarchy(self, levels, coarse_refine):
+        from ..aggregation import sa_hierarchy
+        return sa_hierarchy(sp.csr_matrix(self.matrix), self._device, B=self._candidate, max_levels=levels,
+                            coarse_refine=coarse_refine, verbose=self.verbose, **self._amg)
+
+    def _setup_key(self):
+        return tuple(sorted(self._amg.items())) + (id(self._candidate),)
+
+    def hierarchy_info(self, levels=None):
+        """{"levels": [per level n, nnz, n_agg, rounds], "operator_complexity", "grid_complexity"}
+        (aggregation.hierarchy_info) of the hierarchy in use, built first where there is none."""
+        from ..aggregation import hierarchy_info
+        return hierarchy_info(self._hier if self._hier is not None and levels is None else self.setup(levels))

@@ -4,7 +4,8 @@ from .Jacobi import Jacobi
 from .GaussSeidel import GaussSeidel
 from .CG import CG
 from .GMRES import GMRES
-from .Multigrid import Multigrid, GeometricMG, SemiGeometricMG, HierarchyMG, NeuralMG, NeuralMG_2D, ClassicalAMG
+from .Multigrid import Multigrid, GeometricMG, SemiGeometricMG, HierarchyMG, NeuralMG, NeuralMG_2D, ClassicalAMG, SmoothedAggregationAMG
 
 __all__ = ["Solver", "DirectSolver", "IterativeSolver", "Jacobi", "GaussSeidel", "CG", "GMRES", "Multigrid",
-           "GeometricMG", "SemiGeometricMG", "HierarchyMG", "NeuralMG", "NeuralMG_2D", "ClassicalAMG"]
+           "GeometricMG", "SemiGeometricMG", "HierarchyMG", "NeuralMG", "NeuralMG_2D", "ClassicalAMG",
+           "SmoothedAggregationAMG"]
