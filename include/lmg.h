@@ -1189,6 +1189,54 @@ int lmg_sa_tentative_fill(int64_t n, int64_t n_agg, const int32_t *d_agg, const 
                           const int32_t *d_t_rowptr, double *d_t_vals, void *stream);
 int lmg_sa_row_states(int64_t n, const int32_t *d_t_rowptr, int32_t *d_state, void *stream);
 
+/* ---- multicolour Gauss-Seidel with its setup on the device (csrc/color.hip; the stages: ops.build_gs_schedule_device) ---------
+ * The rules: DESIGN.md section 3, "Multicolour Gauss-Seidel on the device".  A: CSR on the device, n < 2^31 - 257; T: its
+ * transpose (lmg_csr_transpose_*); G: the pattern of A and T without the diagonal, stored zeros included.  One lane per row (the
+ * twin and the sweep: one wave per slice of 64 scheduled rows), no atomics but the refusal, no scratch; every kernel reads what
+ * an earlier launch wrote and writes its own lane's entries, so two calls give the same integers and bits.  Every pointer an
+ * entry point names must be non-null (LMG_ERR_ARG, nothing launched) -- a matrix without entries hands in any valid address for
+ * its entry arrays.  n == 0 (nslices == 0, padded == 0, ncolors == 0, sweeps == 0): LMG_OK.
+ *   select      d_color[i] < 0: uncoloured (the caller starts with -1 everywhere).  d_flag[i] = 1 iff i is uncoloured and
+ *               (hash, index) of i exceeds that of every uncoloured neighbour in G, compared lexicographically; the hash of
+ *               lmg_amg_pmis_select.  A node without neighbours is flagged in the first round.
+ *   assign      a flagged node takes the smallest colour c >= 0 that no coloured neighbour has.  One that would need colour
+ *               LMG_COLOR_MAX is refused through d_status (ONE 64-bit word set to UINT64_MAX by the caller, the node's number
+ *               by an atomic minimum) and stays uncoloured.  d_block_uncolored[b], b < lmg_color_blocks(n): the uncoloured nodes
+ *               left among rows 256 b .. 256 b + 255.  The host sums them and launches the next round while the sum is positive;
+ *               a round that colours nothing means a refusal.
+ *   twin_count  the schedule: d_rows ordered by (colour, row), d_color_ptr[c] its first position of colour c (ncolors + 1
+ *               entries, every colour with a row).  Colour c owns the slices d_color_slice[c] .. d_color_slice[c + 1] - 1,
+ *               (rows of c + 63) / 64 of them.  d_twin_row[64 s + t] = the row of lane t of slice s, -1 beyond the colour's
+ *               last row; d_twin_len: its entries (0 for -1); d_slice_len[s]: the longest of the slice.
+ *   twin_fill   d_slice_base[s] = 64 * (the sum of d_slice_len below s).  Entry j of the row at lane t of slice s goes to
+ *               position d_slice_base[s] + 64 j + t of d_col, d_val and d_src (its index in d_vals); positions no entry goes to
+ *               keep what the caller put there (d_src: -1).
+ *   twin_refill d_val[p] = d_vals[d_src[p]] for the padded positions with d_src[p] >= 0: new values on the same pattern.
+ *   sweep       `sweeps` sweeps in place on d_x over the colours 0 .. ncolors - 1 (backward = 1: ncolors - 1 .. 0), one launch
+ *               per colour; h_color_slice: the HOST copy of d_color_slice.  Per row the update of lmg_csr_gs_schedule: rsum over
+ *               the entries off the diagonal in storage order with separately rounded products, diag the last stored entry
+ *               on it, x[row] = (b[row] - rsum) / diag; a row without a diagonal or with diag == 0 is left as it is.  The same
+ *               bits as lmg_csr_gs_schedule on d_rows / d_color_ptr (backward: on the reversed row list).  max_len: the
+ *               largest d_slice_len, padded: 64 * their sum (they pick the unroll factor and the nontemporal loads of
+ *               lmg_sell_sweep).  No LDS, no barrier, capture-safe. */
+#define LMG_COLOR_MAX 64 /* colours 0 .. 63 */
+int lmg_color_select(int64_t n, const int32_t *d_rowptr, const int32_t *d_colidx, const int32_t *d_t_rowptr,
+                     const int32_t *d_t_colidx, const int32_t *d_color, int32_t *d_flag, void *stream);
+int64_t lmg_color_blocks(int64_t n);
+int lmg_color_assign(int64_t n, const int32_t *d_rowptr, const int32_t *d_colidx, const int32_t *d_t_rowptr,
+                     const int32_t *d_t_colidx, const int32_t *d_flag, int32_t *d_color, int32_t *d_block_uncolored,
+                     uint64_t *d_status, void *stream);
+int lmg_color_twin_count(int64_t nslices, int32_t ncolors, const int32_t *d_color_ptr, const int32_t *d_color_slice,
+                         const int32_t *d_rows, const int32_t *d_rowptr, int32_t *d_twin_row, int32_t *d_twin_len,
+                         int32_t *d_slice_len, void *stream);
+int lmg_color_twin_fill(int64_t nslices, const int32_t *d_twin_row, const int32_t *d_rowptr, const int32_t *d_colidx,
+                        const double *d_vals, const int64_t *d_slice_base, int32_t *d_col, double *d_val, int32_t *d_src,
+                        void *stream);
+int lmg_color_twin_refill(int64_t padded, const int32_t *d_src, const double *d_vals, double *d_val, void *stream);
+int lmg_color_sweep(int32_t ncolors, const int32_t *h_color_slice, const int64_t *d_slice_base, const int32_t *d_slice_len,
+                    const int32_t *d_twin_row, const int32_t *d_twin_len, const int32_t *d_col, const double *d_val,
+                    int32_t max_len, int64_t padded, double *d_x, const double *d_b, int sweeps, int backward, void *stream);
+
 /* ---- hipGraph capture of a launch sequence (one V-cycle) -----------------------------
  * begin/end bracket launches issued on `stream`; end returns an opaque executable graph. */
 int lmg_graph_begin(void *stream);

@@ -207,6 +207,13 @@ SIGNATURES = {
     "lmg_sa_norms": (_c.c_int, [_i64, _p, _p, _p, _p, _p, _p]),
     "lmg_sa_tentative_fill": (_c.c_int, [_i64, _i64, _p, _p, _p, _p, _p, _p]),
     "lmg_sa_row_states": (_c.c_int, [_i64, _p, _p, _p]),
+    "lmg_color_select": (_c.c_int, [_i64, _p, _p, _p, _p, _p, _p, _p]),
+    "lmg_color_blocks": (_i64, [_i64]),
+    "lmg_color_assign": (_c.c_int, [_i64, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "lmg_color_twin_count": (_c.c_int, [_i64, _i32, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "lmg_color_twin_fill": (_c.c_int, [_i64, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "lmg_color_twin_refill": (_c.c_int, [_i64, _p, _p, _p, _p]),
+    "lmg_color_sweep": (_c.c_int, [_i32, _p, _p, _p, _p, _p, _p, _p, _i32, _i64, _p, _p, _c.c_int, _c.c_int, _p]),
     "lmg_graph_begin": (_c.c_int, [_p]),
     "lmg_graph_end": (_c.c_int, [_p, _c.POINTER(_p)]),
     "lmg_graph_launch": (_c.c_int, [_p, _p]),

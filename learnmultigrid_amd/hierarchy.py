@@ -271,6 +271,11 @@ class Hierarchy:
         if self.use_packed:
             for lev in self.levels:
                 lev.A.repack_values()            # same pattern: only the value streams change
+        for lev in self.levels:
+            for sched in lev.gs_sched.values():
+                # the one schedule that holds values: its twin follows them (the backward schedule shares the forward one's)
+                if sched.kind == "multicolor_device" and not sched.backward:
+                    self._ask("gs_refresh", lev.A, sched)
         self._inverse_diagonals()
         if self.levels[0].dinv is not None:          # (made on first use by a smoother that needs it: follows the values too)
             self.levels[0].dinv = self._inverse_diagonal(self.levels[0])
@@ -501,6 +506,13 @@ class Hierarchy:
                 self._ask("gs_prepare", lev.A, lev.gs_sched[key])
             elif direction != "forward":
                 raise ValueError("unknown Gauss-Seidel sweep direction %r" % (direction,))
+            elif kind == "multicolor_device":
+                # coloured, ordered and re-encoded on the device (one colouring per level: the backward schedule above
+                # shares its twin); the pattern never comes to the host
+                sched = self._ask("build_gs_schedule_device", lev.A)
+                if sched is False:
+                    raise ValueError("gs_mode 'multicolor_device' needs an ops module with build_gs_schedule_device")
+                lev.gs_sched[key] = sched
             else:
                 if lev.host_pattern is None:
                     lev.host_pattern = (lev.A.rowptr.cpu().numpy(), lev.A.colidx.cpu().numpy())

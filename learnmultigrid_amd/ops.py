@@ -17,7 +17,7 @@ import torch
 
 from . import _lib
 from ._lib import LmgError, check
-from .twins import (F32, F64, I32, DiaTwin, PackedCSR, ProlongTwin, RestrictTwin, RowPatterns, SellCSR,  # noqa: F401
+from .twins import (F32, F64, I32, ColorSell, DiaTwin, PackedCSR, ProlongTwin, RestrictTwin, RowPatterns, SellCSR,  # noqa: F401
                     StencilTwin, _p, _s, check_values)
 
 
@@ -973,7 +973,7 @@ def dense_gemv_block(M, X, Y):
 class GSSchedule:
     """Ordered independent sets of rows (level schedule or colour classes)."""
 
-    __slots__ = ("kind", "d_rows", "d_ptr", "h_ptr", "nsets", "max_set", "ell")
+    __slots__ = ("kind", "d_rows", "d_ptr", "h_ptr", "nsets", "max_set", "ell", "twin", "backward")
 
     def __init__(self, kind, order, ptr, device):
         self.kind = kind
@@ -983,13 +983,35 @@ class GSSchedule:
         self.nsets = int(self.h_ptr.size - 1)
         self.max_set = int(np.diff(self.h_ptr).max()) if self.nsets else 0
         self.ell = None              # pattern copy in schedule order, built on first use (see _gs_ell)
+        self.twin = None             # "multicolor_device": the ColorSell of the forward schedule, shared with reversed()
+        self.backward = False        # "multicolor_device": the colours of `twin` run in reverse
+
+    @classmethod
+    def from_device(cls, kind, d_rows, h_ptr):
+        """A schedule whose row list was built on the device: d_rows (int32, ordered by set) stays where it is, h_ptr
+        is the host copy of the set pointers (the only part the host ever sees)."""
+        self = cls.__new__(cls)
+        self.kind = kind
+        self.h_ptr = np.ascontiguousarray(h_ptr, dtype=np.int32)
+        self.d_rows = d_rows.contiguous()
+        self.d_ptr = torch.from_numpy(self.h_ptr).to(d_rows.device)
+        self.nsets = int(self.h_ptr.size - 1)
+        self.max_set = int(np.diff(self.h_ptr).max()) if self.nsets else 0
+        self.ell, self.twin, self.backward = None, None, False
+        return self
 
     def reversed(self):
         """The same sets in reverse order: on a level schedule (levels of A + A^T) the exact BACKWARD sweep, rows
         n-1 .. 0; on colour classes backward multicolour Gauss-Seidel.  Every executor of csr_gs_schedule follows the
-        order of d_rows, so no other kernel is needed.  The copy gets its own schedule-ordered pattern (gs_prepare)."""
-        rows = self.d_rows.cpu().numpy()[::-1]
+        order of d_rows, so no other kernel is needed.  The copy gets its own schedule-ordered pattern (gs_prepare).
+        "multicolor_device": the row list is flipped on the device and the copy shares the ColorSell, whose colours the
+        sweep then launches in reverse (the rows of a colour are independent: the same bits as a walk of the flipped list)."""
         ptr = int(self.h_ptr[-1]) - self.h_ptr[::-1] if self.nsets else self.h_ptr
+        if self.kind == "multicolor_device":
+            out = GSSchedule.from_device(self.kind, torch.flip(self.d_rows, (0,)), ptr)
+            out.twin, out.backward = self.twin, not self.backward
+            return out
+        rows = self.d_rows.cpu().numpy()[::-1]
         return GSSchedule(self.kind, rows, ptr, self.d_rows.device)
 
 
@@ -1117,14 +1139,92 @@ def stencil_gs_check(A):
             raise LmgError("wavefront Gauss-Seidel: a band timed out waiting for the previous one")
 
 
+COLOR_MAX = 64                   # LMG_COLOR_MAX: colours 0 .. 63 (one 64-bit mask per lane)
+
+
+def color_device(A):
+    """(colour, ncolours, rounds) of the parallel greedy colouring of the square DeviceCSR A (csrc/color.hip): colour is an
+    int32 device tensor, one entry per row.  The graph is the pattern of A and A^T without the diagonal; per round the
+    uncoloured nodes whose key (hash, index) beats every uncoloured neighbour take the smallest colour no coloured
+    neighbour has.  The host reads one count per round, so this cannot be captured into a graph.  A node that would need
+    colour COLOR_MAX raises LmgError (no partial result: use gs_mode="multicolor" for such a matrix)."""
+    if A.shape[0] != A.shape[1]:
+        raise ValueError("a colouring needs a square matrix, got %s" % (A.shape,))
+    n, dev, L = A.shape[0], A.device, _lib.lib()
+    color = torch.full((max(n, 1),), -1, dtype=I32, device=dev)
+    if n == 0:
+        return color[:0], 0, 0
+    T = A.transpose()
+    flag = torch.empty(n, dtype=I32, device=dev)
+    nb = int(L.lmg_color_blocks(n))
+    left = torch.zeros(nb, dtype=I32, device=dev)
+    status = nmg2d_status(dev)
+    graph = (n, _p(A.rowptr), _pe(A.colidx), _p(T.rowptr), _pe(T.colidx))
+    before, rounds = n, 0
+    while before > 0:
+        check(L.lmg_color_select(*graph, _p(color), _p(flag), _s(color)), "lmg_color_select")
+        check(L.lmg_color_assign(*graph, _p(flag), _p(color), _p(left), _p(status), _s(color)), "lmg_color_assign")
+        rounds += 1
+        now = _scan_rows(left, nb)[1]
+        if now >= before:
+            word = int(status.item())
+            if word != -1:
+                raise LmgError("the colouring needs more than %d colours at node %d (use gs_mode='multicolor')"
+                               % (COLOR_MAX, word))
+            raise RuntimeError("colouring round %d coloured nothing (%d nodes uncoloured)" % (rounds, now))
+        before = now
+    return color[:n], int(color.max()) + 1, rounds
+
+
+def build_gs_schedule_device(A):
+    """The GSSchedule of kind "multicolor_device" of the DeviceCSR A, with its ColorSell: color_device, the rows ordered by
+    (colour, row) with a stable sort on the device, and the twin.  Only the ncolours + 1 colour pointers come to the host;
+    neither the pattern nor the row list does."""
+    color, nc, _rounds = color_device(A)
+    dev = A.device
+    if nc == 0:
+        sched = GSSchedule.from_device("multicolor_device", torch.empty(0, dtype=I32, device=dev), np.zeros(1, dtype=np.int32))
+    else:
+        sorted_color, order = torch.sort(color, stable=True)              # ascending row inside a colour
+        ptr = torch.searchsorted(sorted_color, torch.arange(nc + 1, dtype=I32, device=dev)).to(I32)
+        sched = GSSchedule.from_device("multicolor_device", order.to(I32), ptr.cpu().numpy())
+    gs_prepare(A, sched)
+    return sched
+
+
+def _color_twin(A, sched):
+    if sched.twin is None:
+        fwd = torch.flip(sched.d_rows, (0,)) if sched.backward else sched.d_rows
+        h_ptr = int(sched.h_ptr[-1]) - sched.h_ptr[::-1] if sched.backward and sched.nsets else sched.h_ptr
+        sched.twin = ColorSell.from_schedule(A, fwd, h_ptr)
+    elif sched.twin.key != (A.rowptr.data_ptr(), A.colidx.data_ptr(), A.nnz):
+        raise LmgError("this multicolor_device schedule was built for another matrix")
+    return sched.twin
+
+
+def gs_refresh(A, sched):
+    """After the values of A changed in place (same pattern): what a schedule holds of them follows.  Only the ColorSell of
+    a "multicolor_device" schedule holds values; every other executor reads A.vals."""
+    if sched.kind == "multicolor_device" and sched.twin is not None:
+        sched.twin.update_values(A)
+
+
 def gs_prepare(A, sched):
     """Everything csr_gs_schedule would otherwise build lazily on its first call (allocations, a
     device -> host size read): call it at setup so that the sweep itself is capture-safe."""
+    if sched.kind == "multicolor_device":
+        _color_twin(A, sched)
+        return
     _gs_ell(A, sched)
 
 
 def csr_gs_schedule(A, x, b, sched, sweeps=1):
     _vec_ok(x, b)
+    if sched.kind == "multicolor_device":
+        if x.numel() != A.shape[0] or b.numel() != A.shape[0]:
+            raise ValueError("csr_gs_schedule: x and b must have the %d rows of A" % A.shape[0])
+        _color_twin(A, sched).sweep(x, b, sweeps, sched.backward)
+        return
     ell = _gs_ell(A, sched)
     if ell is not None and ell[1] is not None:
         _key, K, rows, start, ln, cols, total = ell

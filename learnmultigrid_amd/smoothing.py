@@ -10,6 +10,9 @@ import scipy.sparse as sp
 
 
 GS_SWEEPS = ("forward", "backward", "symmetric")       # pyamg's gauss_seidel(sweep=...)
+# the orderings of a Gauss-Seidel sweep (gs_mode): the exact sweep, colour classes found on the host, and colour classes
+# found on the device with the sweep on a sliced-ELL copy in colour order (ops.build_gs_schedule_device)
+GS_MODES = ("lexicographic", "multicolor", "multicolor_device")
 
 
 def gs_sweep_pair(gs_sweep):
@@ -18,6 +21,13 @@ def gs_sweep_pair(gs_sweep):
     if len(pair) != 2 or any(d not in GS_SWEEPS for d in pair):
         raise ValueError("gs_sweep must be one of %s or a (pre, post) pair of them, got %r" % (GS_SWEEPS, gs_sweep))
     return pair
+
+
+def gs_mode_name(gs_mode, what="gs_mode"):
+    """gs_mode as it is, or a ValueError (reads no state: the Krylov solvers check their keyword with it before any setup)."""
+    if gs_mode not in GS_MODES:
+        raise ValueError("%s must be one of %s, got %r" % (what, GS_MODES, gs_mode))
+    return gs_mode
 
 
 def _directions(sweep):

@@ -20,7 +20,10 @@ precond_line_order "zebra" | "jacobi", damping precond_omega: pass 1.0 for zebra
 runs the directions and colours in reverse, the adjoint of the pre-smoothing half, so the cycle is a symmetric operator --
 the preconditioner for operators with a strong direction.  precond_line_band (1 | 2 | 3, None = 1) is the largest
 half-bandwidth of the line systems (Hierarchy.prepare_smoother): 3 for the 25- and 49-point levels of learned transfers; the
-banded line solves are symmetric when A is, so the cycle stays a symmetric operator."""
+banded line solves are symmetric when A is, so the cycle stays a symmetric operator.
+precond_gs_mode (smoothing.GS_MODES, Gauss-Seidel only): the ordering of the sweeps.  "multicolor_device" runs the colours
+forward before and in reverse after the coarse correction -- the symmetric multicolour cycle, with the colouring and the
+colour-ordered sliced-ELL copy of every level made on the device."""
 import math
 
 import numpy as np
@@ -28,7 +31,7 @@ import torch
 
 from .. import ops
 from ..ops import F64
-from ._precond import BlockSolves, check_smoother, make_apply
+from ._precond import BlockSolves, check_smoother, gs_mode_keyword, make_apply
 from .Solver import IterativeSolver, on_device
 
 
@@ -43,7 +46,9 @@ class CG(BlockSolves, IterativeSolver):
     @on_device
     def solve(self, max_iterations=1000, error=1e-08, initial_guess=None, *, preconditioner=None,
               precond_steps=2, precond_omega=0.8, precond_smoother="Jacobi", precond_cycle_shape="V",
-              precond_line_dir="xy", precond_line_order="zebra", precond_line_band=None):
+              precond_line_dir="xy", precond_line_order="zebra", precond_line_band=None,
+              precond_gs_mode="lexicographic"):
+        gs_mode_keyword(precond_gs_mode)
         options = check_smoother(precond_smoother, precond_steps, line_dir=precond_line_dir, line_order=precond_line_order,
                                  line_band=precond_line_band)
         if precond_cycle_shape not in ("V", "W"):
@@ -65,7 +70,7 @@ class CG(BlockSolves, IterativeSolver):
         H = preconditioner
         # forward sweeps before, backward sweeps after the coarse correction: the symmetric Gauss-Seidel cycle
         apply_M = make_apply(H, precond_smoother, precond_steps, precond_omega, precond_cycle_shape, ("forward", "backward"),
-                             options)
+                             options, **gs_mode_keyword(precond_gs_mode))
         z = torch.empty_like(x)
         apply_M(r, z)
         p = z.clone()

@@ -6,7 +6,7 @@ entry per iteration after it, stop on ||r|| <= error.
 
 `preconditioner=Hierarchy` preconditions from the right with one cycle from a zero guess per iteration, with CG's
 keywords; `precond_cycle_shape` also takes "F", and `precond_gs_sweep` any sweep name or (pre, post) pair of
-Hierarchy.cycle (default forward / forward); `precond_line_band` as in CG.solve.  The iteration is krylov.fgmres: classical Gram-Schmidt applied twice in four
+Hierarchy.cycle (default forward / forward); `precond_line_band` and `precond_gs_mode` as in CG.solve.  The iteration is krylov.fgmres: classical Gram-Schmidt applied twice in four
 fused launches and one device-to-host read per iteration; its residual estimate is the true residual norm in exact
 arithmetic, and the true norm is recomputed at the end of every cycle of `restart` iterations.  Memory: 2 restart + 1
 vectors for the bases, (2 restart + 4) 8 n bytes with x, b and the scratch.
@@ -20,7 +20,7 @@ import torch
 from .. import krylov, ops
 from ..hierarchy import cycle_children, gs_sweep_pair
 from ..ops import F64
-from ._precond import BlockSolves, check_smoother, make_apply
+from ._precond import BlockSolves, check_smoother, gs_mode_keyword, make_apply
 from .Solver import IterativeSolver, on_device
 
 
@@ -58,7 +58,8 @@ class GMRES(BlockSolves, IterativeSolver):
     def solve(self, max_iterations=1000, error=1e-08, initial_guess=None, *, restart=30, preconditioner=None,
               precond_steps=2, precond_omega=0.8, precond_smoother="Jacobi", precond_cycle_shape="V",
               precond_gs_sweep="forward", precond_line_dir="xy", precond_line_order="zebra",
-              precond_line_band=None):
+              precond_line_band=None, precond_gs_mode="lexicographic"):
+        gs_mode_keyword(precond_gs_mode)
         pair, options = check_keywords(restart, ops.krylov_max_vectors(), precond_smoother, precond_cycle_shape, precond_gs_sweep,
                                        precond_line_dir, precond_line_order, precond_line_band, precond_steps)
         A = self._device_matrix()
@@ -71,7 +72,8 @@ class GMRES(BlockSolves, IterativeSolver):
         H = preconditioner
         apply_M = None
         if H is not None:
-            apply_M = make_apply(H, precond_smoother, precond_steps, precond_omega, precond_cycle_shape, pair, options)
+            apply_M = make_apply(H, precond_smoother, precond_steps, precond_omega, precond_cycle_shape, pair, options,
+                                 **gs_mode_keyword(precond_gs_mode))
         track, self.iterations = krylov.fgmres(ops, A, b, x, apply_M, restart=int(restart), max_iterations=max_iterations,
                                                error=error, residual_out=r)
         if track[-1] <= error:

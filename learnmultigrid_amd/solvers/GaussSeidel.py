@@ -2,7 +2,8 @@
 The reference forms (D+L)^-1 explicitly (O(n^2) fill) and does x += (D+L)^-1 (b - A x);
 that is one lexicographic forward sweep, executed here exactly (level-scheduled HIP
 kernel, same row arithmetic as pyamg's sweep) or, with gs_mode="multicolor", in colour
-order (faster, different ordering).  sweep="backward" | "symmetric" (pyamg's gauss_seidel sweep) relaxes
+order (faster, different ordering; gs_mode="multicolor_device": colours found on the device, sweeps on a sliced-ELL
+copy of the matrix in colour order).  sweep="backward" | "symmetric" (pyamg's gauss_seidel sweep) relaxes
 the rows in reverse order / forward then backward in every iteration."""
 import math
 
@@ -37,7 +38,9 @@ class GaussSeidel(IterativeSolver):
             if gs_mode == "lexicographic" and ops.stencil_gs_available(A, d):
                 plan.append((d, None))
                 continue
-            if fwd_sched is None:
+            if fwd_sched is None and gs_mode == "multicolor_device":
+                fwd_sched = ops.build_gs_schedule_device(A)        # coloured on the device; reversed() shares its twin
+            elif fwd_sched is None:
                 fwd_sched = ops.build_gs_schedule(sp.csr_matrix(self.matrix), gs_mode, self._device)
             plan.append((d, fwd_sched if d == "forward" else fwd_sched.reversed()))
         wave = any(sc is None for _, sc in plan)

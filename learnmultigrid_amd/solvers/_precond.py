@@ -6,7 +6,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from ..smoothing import smoother_options
+from ..smoothing import gs_mode_name, smoother_options
 
 SMOOTHERS = ("Jacobi", "GaussSeidel", "Chebyshev", "Line")
 
@@ -85,11 +85,19 @@ def check_smoother(smoother, steps, **keywords):
     return smoother_options(smoother, steps, **keywords)
 
 
-def make_apply(H, smoother, steps, omega, shape, gs_sweep, options):
+def gs_mode_keyword(precond_gs_mode):
+    """The precond_gs_mode of CG.solve and GMRES.solve as the keyword of make_apply, checked (ValueError): {} for the default
+    ordering, which make_apply is not told -- it was called with seven arguments before it had the keyword, and still is."""
+    gs_mode_name(precond_gs_mode, "precond_gs_mode")
+    return {} if precond_gs_mode == "lexicographic" else {"gs_mode": precond_gs_mode}
+
+
+def make_apply(H, smoother, steps, omega, shape, gs_sweep, options, gs_mode="lexicographic"):
     """apply_M(src, dst): dst = one `shape` cycle of H on the right-hand side src from a zero guess (H None: dst = src).
     Prepares what the smoother needs on the hierarchy (options, from check_smoother: Chebyshev bounds and work vectors, line
     factors) before the first application; a smoother without options sets itself up in its first sweep.  gs_sweep: the
-    (pre, post) directions of a Gauss-Seidel cycle; a smoother with no use for it, or for omega, hands it to no launch."""
+    (pre, post) directions of a Gauss-Seidel cycle and gs_mode its ordering (smoothing.GS_MODES); a smoother with no use for
+    them, or for omega, hands them to no launch."""
     if H is not None and options:
         H.prepare_smoother(smoother, **options)
 
@@ -99,7 +107,7 @@ def make_apply(H, smoother, steps, omega, shape, gs_sweep, options):
             return
         fine = H.levels[0]
         ops.copy(src, fine.b)
-        H.cycle(smoother, steps, omega, x_is_zero=True, gs_sweep=gs_sweep, shape=shape)
+        H.cycle(smoother, steps, omega, gs_mode, x_is_zero=True, gs_sweep=gs_sweep, shape=shape)
         ops.copy(fine.x, dst)
 
     return apply_M

@@ -5,6 +5,7 @@ decoding of a verified pattern table into the grid views of it:
   StencilTwin                         3x3-window view of a RowPatterns twin (lmg_stencil_sweep and the fused passes)
   ProlongTwin, RestrictTwin           2x2- / 3x3-window views of the row patterns of grid transfers (fused passes)
   DiaTwin                             slot arrays of grid operators with per-row values (lmg_dia_smooth)
+  ColorSell                           the matrix in the order of a colour schedule, sliced ELL (lmg_color_sweep)
 
 Every class builds itself from device arrays and knows the C arguments that describe it (sweep_args, c_args).  WHICH twin
 an operator gets, and which kernel then runs, is decided in ops.py (DeviceCSR.pack, the switches and thresholds there):
@@ -406,6 +407,70 @@ class SellCSR:
         """New values, same pattern (Galerkin rebuild): only the value stream is rewritten, at the width it has.  False
         when fp32 values fail the range rule (the caller rebuilds the twin in fp64)."""
         return self._fill(A, None)
+
+
+class ColorSell:
+    """The matrix in the order of a colour schedule, sliced-ELL as SellCSR, for lmg_color_sweep (see include/lmg.h): every
+    colour starts on a slice boundary -- its last slice is filled up with empty rows, id -1 --, slice s is padded to its
+    longest row, entry j of scheduled row k lives at slice_base[s] + 64 j + (k mod 64).  int32 columns, fp64 copies of the
+    values, and per entry its index in A.vals (`src`, -1 for padding) for update_values.  Built on the device from the
+    schedule's row list (count, scan, fill); the host only handles the per-colour pointers."""
+
+    __slots__ = ("n", "ncolors", "nslices", "h_color_slice", "trow", "tlen", "slice_len", "slice_base", "col", "val", "src",
+                 "max_len", "padded", "key")
+
+    @classmethod
+    def from_schedule(cls, A, d_rows, h_ptr):
+        """d_rows: the rows ordered by (colour, row) on A's device; h_ptr: the host pointers of the colours into it."""
+        L = _lib.lib()
+        dev = A.vals.device
+        self = cls()
+        self.n = A.shape[0]
+        self.key = (A.rowptr.data_ptr(), A.colidx.data_ptr(), A.nnz)
+        h_ptr = np.ascontiguousarray(h_ptr, dtype=np.int32)
+        self.ncolors = nc = int(h_ptr.size - 1)
+        self.h_color_slice = np.zeros(nc + 1, dtype=np.int32)
+        np.cumsum((np.diff(h_ptr) + 63) // 64, out=self.h_color_slice[1:])
+        self.nslices = nsl = int(self.h_color_slice[-1])
+        self.trow = torch.empty(max(64 * nsl, 1), dtype=I32, device=dev)
+        self.tlen = torch.empty(max(64 * nsl, 1), dtype=I32, device=dev)
+        self.slice_len = torch.empty(max(nsl, 1), dtype=I32, device=dev)
+        if nsl == 0:
+            self.slice_base = torch.zeros(1, dtype=torch.int64, device=dev)
+            self.max_len = self.padded = 0
+            self.col, self.src = (torch.zeros(64, dtype=I32, device=dev) for _ in range(2))
+            self.val = torch.zeros(64, dtype=F64, device=dev)
+            return self
+        d_ptr = torch.from_numpy(h_ptr).to(dev)
+        d_cs = torch.from_numpy(self.h_color_slice).to(dev)
+        check(L.lmg_color_twin_count(nsl, nc, _p(d_ptr), _p(d_cs), _p(d_rows), _p(A.rowptr), _p(self.trow), _p(self.tlen),
+                                     _p(self.slice_len), _s(A.rowptr)), "lmg_color_twin_count")
+        sl = self.slice_len.long() * 64
+        ends = torch.cumsum(sl, 0)
+        self.slice_base = (ends - sl).contiguous()
+        self.padded, self.max_len = (int(v) for v in torch.stack((ends[-1], self.slice_len.max().long())).cpu())
+        self.col = torch.zeros(self.padded + 64, dtype=I32, device=dev)
+        self.val = torch.zeros(self.padded + 64, dtype=F64, device=dev)
+        self.src = torch.full((self.padded + 64,), -1, dtype=I32, device=dev)
+        entries = A.colidx if A.nnz else torch.zeros(1, dtype=I32, device=dev)      # (no row has entries then)
+        values = A.vals if A.nnz else torch.zeros(1, dtype=F64, device=dev)
+        check(L.lmg_color_twin_fill(nsl, _p(self.trow), _p(A.rowptr), _p(entries), _p(values), _p(self.slice_base),
+                                    _p(self.col), _p(self.val), _p(self.src), _s(A.rowptr)), "lmg_color_twin_fill")
+        return self
+
+    def update_values(self, A):
+        """New values, same pattern (Galerkin rebuild): the value stream again from the source indices."""
+        if self.padded and A.nnz:
+            check(_lib.lib().lmg_color_twin_refill(self.padded, _p(self.src), _p(A.vals), _p(self.val), _s(A.vals)),
+                  "lmg_color_twin_refill")
+
+    def bytes(self):
+        return 16 * self.padded + 12 * self.nslices + 8 * 64 * self.nslices
+
+    def sweep(self, x, b, sweeps, backward):
+        check(_lib.lib().lmg_color_sweep(self.ncolors, self.h_color_slice.ctypes.data, _p(self.slice_base), _p(self.slice_len),
+                                         _p(self.trow), _p(self.tlen), _p(self.col), _p(self.val), self.max_len, self.padded,
+                                         _p(x), _p(b), int(sweeps), int(bool(backward)), _s(x)), "lmg_color_sweep")
 
 
 def _pid_counts(R):
