@@ -197,6 +197,10 @@ class SpGEMMPlan:
 
 
 class _Sched:
+    """What the package reads of an ops.GSSchedule: its rows, and its kind (Hierarchy.rebuild_numeric asks every schedule of
+    every level for it)."""
+    kind, backward = "lexicographic", False
+
     def __init__(self, rows):
         self.d_rows = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int32))
 
