@@ -387,6 +387,63 @@ int lmg_stencil_smooth_restrict(int64_t n, int32_t line_stride, const uint8_t *d
                                 int32_t r_npat, const double *d_r_val, const int32_t *d_r_mask, int32_t hot_r,
                                 const double *h_hot_rval, void *stream);
 
+/* Census of the rows that do NOT hold the expected pattern, for the three passes above.  On the benchmark's fine
+ * level -- on any constant-coefficient grid level -- every row away from the boundary is the hot pattern of A, the
+ * hot pair of P for its parities, the hot pattern of R.  Where that holds for everything a wave reads, the pass runs
+ * a third, UNIFORM body that never loads or tests a pattern id (csrc/stencil_fused.hip); which waves those are is
+ * read from a table built once per twin:
+ *   lmg_pattern_census       d_table [lines + 1][cells + 1] int32, lines = ceil(n / line_stride), cells =
+ *                            ceil(line_stride / 32): entry [y + 1][c + 1] = number of rows on the lines 0 .. y, columns
+ *                            0 .. 32 c + 31 whose id differs from h_expected[2 * (line & 1) + (column & 1)] (HOST, 4 ints;
+ *                            -1: nothing is expected there, every row counts), 2-D inclusive prefix sums behind a border
+ *                            of zeros, so that a rectangle of cells is counted with four loads.  Columns of a cell beyond
+ *                            the line stride and rows beyond n count as well.  Every entry is written.
+ *   lmg_pattern_census_count its number of entries (0: arguments out of range).
+ * The rules: A  all four = hot_pattern;  P  {pairs[0] & 255, pairs[0] >> 8, pairs[1] & 255, pairs[1] >> 8} of
+ * h_hot_pairs;  R  all four = hot_r, over the COARSE grid (n_coarse, coarse_stride).
+ * OWNERSHIP AND STALENESS: the caller owns the tables (learnmultigrid_amd/twins.py: each of StencilTwin, ProlongTwin,
+ * RestrictTwin builds its own where it decides its hot ids, and holds it next to them).  A table is valid exactly as
+ * long as the id array AND the hot ids it was built from: whoever writes or replaces either rebuilds or drops the table
+ * with them, before the next launch.  A stale table makes the pass apply the hot values to rows that do not hold them.
+ *   lmg_stencil_smooth*_census   the three passes with the tables: d_census (A), d_p_census (P), d_r_census (R), each NULL
+ *                            = not given, and census_stride / r_census_stride = cells + 1 of the grid the table is
+ *                            over (LMG_ERR_ARG otherwise).  A wave takes the UNIFORM body only where every table its
+ *                            pass needs is given and zero over all it reads; same bits as the entry points above,
+ *                            which take no tables and never run that body.  Only the kernels of THREE sweeps have the
+ *                            body (not the plain pass from a zero iterate: it cost the others registers); with any other
+ *                            sweep count the tables are accepted and not read.
+ *   lmg_stencil_smooth_uniform_items   the kernels' own predicate on the host: h_counts[0..2] (HOST) = items (waves) of
+ *                            the launch that run the general, the FAST and the UNIFORM body, for this geometry, the
+ *                            tune keys as they stand and HOST copies of the tables.  form: 0 plain (with_residual,
+ *                            zero_iterate as the launch), 1 correcting, 2 restricting (n_coarse, coarse_stride). */
+int64_t lmg_pattern_census_count(int64_t n, int32_t line_stride);
+int lmg_pattern_census(int64_t n, int32_t line_stride, const uint8_t *d_pid, const int32_t *h_expected, int32_t *d_table,
+                       void *stream);
+int lmg_stencil_smooth_census(int64_t n, int32_t line_stride, const uint8_t *d_pid, int32_t npat,
+                              const double *d_st_val, const int32_t *d_st_mask, uint32_t union_mask,
+                              int32_t hot_pattern, const double *h_hot_val, int sweeps, const double *d_x_in,
+                              const double *d_b, double omega, double *d_x_out, double *d_r_out,
+                              const int32_t *d_census, int32_t census_stride, void *stream);
+int lmg_stencil_smooth_prolong_census(int64_t n, int32_t line_stride, const uint8_t *d_pid, int32_t npat,
+                                      const double *d_st_val, const int32_t *d_st_mask, uint32_t union_mask,
+                                      int32_t hot_pattern, const double *h_hot_val, int sweeps, const double *d_x_in,
+                                      const double *d_b, double omega, double *d_x_out, int64_t n_coarse,
+                                      int32_t coarse_stride, const double *d_e_coarse, const uint8_t *d_p_pid,
+                                      int32_t p_npat, const double *d_p_val, const int32_t *d_p_mask,
+                                      const int32_t *h_hot_pairs, const double *h_hot_pval, const int32_t *d_census,
+                                      const int32_t *d_p_census, int32_t census_stride, void *stream);
+int lmg_stencil_smooth_restrict_census(int64_t n, int32_t line_stride, const uint8_t *d_pid, int32_t npat,
+                                       const double *d_st_val, const int32_t *d_st_mask, uint32_t union_mask,
+                                       int32_t hot_pattern, const double *h_hot_val, int sweeps, const double *d_x_in,
+                                       const double *d_b, double omega, double *d_x_out, int64_t n_coarse,
+                                       int32_t coarse_stride, double *d_b_coarse, const uint8_t *d_r_pid,
+                                       int32_t r_npat, const double *d_r_val, const int32_t *d_r_mask, int32_t hot_r,
+                                       const double *h_hot_rval, const int32_t *d_census, int32_t census_stride,
+                                       const int32_t *d_r_census, int32_t r_census_stride, void *stream);
+int lmg_stencil_smooth_uniform_items(int64_t n, int32_t line_stride, int sweeps, int with_residual, int zero_iterate,
+                                     int form, int64_t n_coarse, int32_t coarse_stride, const int32_t *h_census,
+                                     const int32_t *h_p_census, const int32_t *h_r_census, int64_t *h_counts);
+
 /* ---- sliced-ELL ("SELL-64") sweeps: matrices with long rows ---------------------------
  * Third lossless twin.  Slice s = rows 64 s .. 64 s + 63, padded to its longest row
  * d_slice_len[s]; entry j of row r lives at d_slice_base[s] + 64 j + (r mod 64) of d_col

@@ -74,6 +74,15 @@ SIGNATURES = {
                                               _i64, _i32, _p, _p, _i32, _p, _p, _p, _p, _p]),
     "lmg_stencil_smooth_restrict": (_c.c_int, [_i64, _i32, _p, _i32, _p, _p, _c.c_uint32, _i32, _p, _c.c_int, _p, _p, _f64, _p,
                                                _i64, _i32, _p, _p, _i32, _p, _p, _i32, _p, _p]),
+    "lmg_pattern_census_count": (_i64, [_i64, _i32]),
+    "lmg_pattern_census": (_c.c_int, [_i64, _i32, _p, _p, _p, _p]),
+    "lmg_stencil_smooth_census": (_c.c_int, [_i64, _i32, _p, _i32, _p, _p, _c.c_uint32, _i32, _p, _c.c_int, _p, _p, _f64, _p, _p,
+                                             _p, _i32, _p]),
+    "lmg_stencil_smooth_prolong_census": (_c.c_int, [_i64, _i32, _p, _i32, _p, _p, _c.c_uint32, _i32, _p, _c.c_int, _p, _p, _f64, _p,
+                                                     _i64, _i32, _p, _p, _i32, _p, _p, _p, _p, _p, _p, _i32, _p]),
+    "lmg_stencil_smooth_restrict_census": (_c.c_int, [_i64, _i32, _p, _i32, _p, _p, _c.c_uint32, _i32, _p, _c.c_int, _p, _p, _f64, _p,
+                                                      _i64, _i32, _p, _p, _i32, _p, _p, _i32, _p, _p, _i32, _p, _i32, _p]),
+    "lmg_stencil_smooth_uniform_items": (_c.c_int, [_i64, _i32, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _i64, _i32, _p, _p, _p, _p]),
     "lmg_sell_sweep": (_c.c_int, [_c.c_int, _i64, _p, _p, _p, _p, _p, _c.c_int, _p, _i32, _p, _p, _p, _f64, _f64, _p, _p, _p]),
     "lmg_sell_slice_info": (_c.c_int, [_i64, _p, _p, _p, _p, _p, _p]),
     "lmg_sell_fill": (_c.c_int, [_i64, _p, _p, _p, _p, _p, _c.c_int, _p, _p, _p]),

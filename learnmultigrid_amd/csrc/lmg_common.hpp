@@ -164,6 +164,26 @@ constexpr unsigned kMaskLower = 0x1C0u;       // the line below
 constexpr unsigned kMaskCorners = 0x145u;     // slots 0, 2, 6, 8: the diagonal neighbours
 constexpr unsigned kMaskOffLine = kMaskUpper | kMaskLower;      // 0x1C7: any slot that needs the line stride
 
+// ---- census of the rows that do not hold the expected pattern (lmg_pattern_census, vec.hip) ------------------------
+// A table of int32 over (line, cell of kLmgCensusCell columns) of a grid with `lines` lines of stride W, with a border
+// of zeros in front: entry [y + 1][c + 1] of (lines + 1) x (cells + 1) is the number of such rows on the lines 0 .. y in
+// the cells 0 .. c (2-D inclusive prefix sums), so any rectangle of cells is counted with four loads.  A cell counts the
+// columns it has beyond the line end and the rows a short last line lacks as well: what is not there is not expected.
+constexpr int kLmgCensusCell = 32;
+__host__ __device__ inline int lmg_census_cells(int W) { return (W + kLmgCensusCell - 1) / kLmgCensusCell; }
+__host__ __device__ inline int64_t lmg_census_count(int lines, int W) { return (int64_t)(lines + 1) * (lmg_census_cells(W) + 1); }
+// Whether every row on the lines y0 .. y1, columns x0 .. x1 (all inclusive) holds the expected pattern: the one
+// function the fused register pass and the host (lmg_stencil_smooth_uniform_items) decide with.  Conservative: the
+// rectangle is widened to whole cells, and one that leaves the grid -- or a missing table -- answers no.
+__host__ __device__ inline bool lmg_census_all_expected(const int32_t *table, int lines, int W, int y0, int y1, int x0, int x1)
+{
+    if (!table || y0 < 0 || y1 >= lines || y0 > y1 || x0 < 0 || x1 >= W || x0 > x1) return false;
+    const int64_t cs = lmg_census_cells(W) + 1;
+    const int ca = x0 / kLmgCensusCell, cb = x1 / kLmgCensusCell + 1;
+    const int32_t *lo = table + (int64_t)y0 * cs, *hi = table + (int64_t)(y1 + 1) * cs;
+    return hi[cb] - lo[cb] - hi[ca] + lo[ca] == 0;
+}
+
 // The loops that stage a pattern table (st_val, st_mask) into LDS stay in the kernels: handed to a helper, the table
 // pointers are read from the kernel arguments at the call instead of inside the guarded loops, which reorders the
 // scalar loads of every kernel of gs_wave.hip, stencil_tile.hip and stencil_fused.hip.

@@ -83,6 +83,9 @@ struct MArgs {
     int rp_npat;
     int rhot;                 // the frequent pattern with all nine slots, or -1
     double rhv[9];            // its values
+    // census tables (lmg_common.hpp) of the rows that are not hot: A's and P's over this grid, R's over the coarse one.
+    // NULL: not given -- no wave takes the UNIFORM body
+    const int *cen_a, *cen_p, *cen_r;
 };
 
 // strip geometry: columns left of the stored part / stored columns of a 128-column window
@@ -218,7 +221,7 @@ struct Item {
     int strip, out_y0, out_y1;
 };
 
-__device__ __forceinline__ Item decode_item(const MArgs &a, int item)
+__host__ __device__ __forceinline__ Item decode_item(const MArgs &a, int item)
 {
     Item it;
     const int nb_items = a.nb_strips * a.segs_b;
@@ -250,6 +253,46 @@ __device__ __forceinline__ Item decode_item(const MArgs &a, int item)
     return it;
 }
 
+// Which body an item runs: decided once per wave from scalar quantities, by the kernel and -- the same function -- by the
+// host (lmg_stencil_smooth_uniform_items).
+//   FAST      every line the march touches -- [y_begin, last prefetched line] -- and the coarse lines that travel with
+//             them lie strictly inside the vectors, for all 128 window columns of the strip;
+//   UNIFORM   FAST, and the census tables say that every row of A in that rectangle is the hot pattern, with PROL every
+//             row of P there the hot pair's for its parities, with REST every row of R in the coarse window (64 columns
+//             from c0 / 2) on the coarse lines whose ids the march would load the hot one.
+enum { BODY_GENERAL = 0, BODY_FAST = 1, BODY_UNIFORM = 2 };
+// Which kernels HAVE the UNIFORM body: the passes of three sweeps -- what a V(3,3) cycle launches on its fine level --
+// except the plain pass from a zero iterate.  A kernel's registers are the maximum over its bodies, and the straight-line
+// UNIFORM body lets the scheduler spend registers up to the launch bound: in the one- and two-sweep kernels and in
+// <3, 5-point, ZERO> it cost an occupancy step (12 of 54 instantiations) or SGPR spills (4), so those are compiled without
+// it, as the parent had them (profiles/fused_uniform_resources.txt); their items are never UNIFORM, on the device or in
+// lmg_stencil_smooth_uniform_items.
+template <int S, bool RESID, bool ZERO>
+constexpr bool kHasUniform = S == 3 && (RESID || !ZERO);
+template <int S, bool RESID, bool ZERO, int PF, bool PROL, bool REST>
+__host__ __device__ __forceinline__ int item_body(const MArgs &a, const Item &it)
+{
+    constexpr int H = S + (RESID ? 1 : 0) - (ZERO ? 1 : 0);
+    constexpr int U = StripGeom<H, PROL, REST>::U, ML = StripGeom<H, PROL, REST>::ML;
+    constexpr int HL = H + (REST ? 1 : 0);
+    const int c0 = it.strip * U - ML;
+    const int y_begin = it.out_y0 - HL - ((it.out_y0 - HL) & 1);
+    const int t_last = it.out_y1 - 1 + S + (RESID ? 1 : 0) + (REST ? 1 : 0);
+    const int y_fetch = y_begin + ((t_last - y_begin) / kUF + 1) * kUF - 1 + PF;     // last line fetched
+    bool fast = a.allow_fast && y_begin >= (REST ? S + 2 : 1) && y_fetch <= a.lines - 2 &&
+                (int64_t)y_begin * a.W + c0 >= 0 && (int64_t)y_fetch * a.W + c0 + kStripCols < (int64_t)a.n;
+    if (PROL) fast = fast && (int64_t)((y_fetch + 1) >> 1) * a.Wc + (c0 >> 1) + LMG_WAVE <= (int64_t)a.nc;
+    if (REST) fast = fast && (int64_t)((y_fetch - S) >> 1) * a.Wc + (c0 >> 1) + LMG_WAVE <= (int64_t)a.nc;
+    if (!fast) return BODY_GENERAL;
+    if (!kHasUniform<S, RESID, ZERO>) return BODY_FAST;
+    bool uni = a.hot >= 0 && lmg_census_all_expected(a.cen_a, a.lines, a.W, y_begin, y_fetch, c0, c0 + kStripCols - 1);
+    if (PROL) uni = uni && a.phot[0] >= 0 && a.phot[1] >= 0 && lmg_census_all_expected(a.cen_p, a.lines, a.W, y_begin, y_fetch, c0, c0 + kStripCols - 1);
+    if (REST)
+        uni = uni && a.rhot >= 0 &&
+              lmg_census_all_expected(a.cen_r, a.nc / a.Wc, a.Wc, (y_begin - S) >> 1, (y_fetch - S) >> 1, c0 >> 1, (c0 >> 1) + LMG_WAVE - 1);
+    return uni ? BODY_UNIFORM : BODY_FAST;
+}
+
 struct Tables {
     const double *val;          // [npat][9]
     const int *mask;            // [npat], bit 16: no usable diagonal
@@ -263,9 +306,13 @@ struct Tables {
 // The march of one wave down its segment.  FAST: every load of the wave (halo lines, prefetched lines and the coarse
 // vectors included) is inside its array and every element is a row of the matrix -- decided once per wave from scalar
 // quantities; the general body keeps the clamped, validity-tracking code for the waves at the first / last lines.
+// UNI (with FAST): every row the march reads -- of A, and of P / R with PROL / REST -- is the hot one (item_body).  The body
+// then never looks at a pattern id: no loads of pid / ppid / rpid (5 vector-memory instructions per line instead of 7 in the
+// transfer passes), no id or "all lanes hot" rings, no __all tests, and every stage is the hot branch -- straight-line
+// code with the same products and sums in the same order, hence the same bits.
 // UM: the union slot mask of the matrix, compile time (5-point, 9-point, 1-D chain: anything else runs
 // the separate sweeps) -- a run-time mask costs a scalar branch per slot, stage and line.
-template <int S, unsigned UM, bool RESID, bool ZERO, int PF, bool PROL, bool REST, bool FAST>
+template <int S, unsigned UM, bool RESID, bool ZERO, int PF, bool PROL, bool REST, bool FAST, bool UNI>
 __device__ __forceinline__ void fused_march(const MArgs &a, const Tables &T, const int lane, const int strip, const int out_y0,
                                             const int out_y1)
 {
@@ -325,8 +372,12 @@ __device__ __forceinline__ void fused_march(const MArgs &a, const Tables &T, con
             const int64_t i0 = (int64_t)y * W + c0;
 #endif
             L.ok = 3;
-            const unsigned short *pp2 = reinterpret_cast<const unsigned short *>(reinterpret_cast<const char *>(a.pid + i0) + lane2);
-            L.praw = (int)((NTL & 4) ? __builtin_nontemporal_load(pp2) : *pp2);
+            if (!UNI) {
+                const unsigned short *pp2 = reinterpret_cast<const unsigned short *>(reinterpret_cast<const char *>(a.pid + i0) + lane2);
+                L.praw = (int)((NTL & 4) ? __builtin_nontemporal_load(pp2) : *pp2);
+            } else {
+                L.praw = 0;         // (the ids are constants the UNIFORM body never reads: they occupy no register)
+            }
             typedef double dv2 __attribute__((ext_vector_type(2), aligned(8)));    // (an odd line stride: 8-byte aligned windows)
             const dv2 *pb = reinterpret_cast<const dv2 *>(reinterpret_cast<const char *>(a.b + i0) + lane16);
             const dv2 bb = (NTL & 1) ? __builtin_nontemporal_load(pb) : *pb;
@@ -341,16 +392,19 @@ __device__ __forceinline__ void fused_march(const MArgs &a, const Tables &T, con
                 L.x.x = L.x.y = 0.0;
             }
             if (PROL) {
-                unsigned short twop;
-                __builtin_memcpy(&twop, reinterpret_cast<const char *>(a.ppid + i0) + lane2, 2);
-                L.pp = (int)twop;
+                L.pp = 0;
+                if (!UNI) {
+                    unsigned short twop;
+                    __builtin_memcpy(&twop, reinterpret_cast<const char *>(a.ppid + i0) + lane2, 2);
+                    L.pp = (int)twop;
+                }
                 const int64_t jc0 = (int64_t)((y + 1) >> 1) * a.Wc + (c0 >> 1);
                 L.e = *reinterpret_cast<const double *>(reinterpret_cast<const char *>(a.ec + jc0) + lane8);
             } else {
                 L.pp = 0;
                 L.e = 0.0;
             }
-            if (REST) {
+            if (REST && !UNI) {
                 const int64_t jr0 = (int64_t)((y - S) >> 1) * a.Wc + (c0 >> 1);
                 L.rp = (int)*(reinterpret_cast<const unsigned char *>(a.rpid + jr0) + lane);
             } else {
@@ -509,7 +563,7 @@ __device__ __forceinline__ void fused_march(const MArgs &a, const Tables &T, con
                     const double e0 = odd ? e_prev : en, e1 = en;
                     const double e0r = dpp_upper<true>(e0), e1r = dpp_upper<true>(e1);
                     double accA, accB;
-                    if (__all(q2 == (odd ? hotq_odd : hotq_even))) {          // wave-uniform
+                    if (UNI || __all(q2 == (odd ? hotq_odd : hotq_even))) {   // wave-uniform
                         if (!odd) {
                             accA = 0.0 + hp[0] * e0;
                             accB = (0.0 + hp[1] * e0) + hp[2] * e0r;
@@ -536,7 +590,7 @@ __device__ __forceinline__ void fused_march(const MArgs &a, const Tables &T, con
                 Bq[q0] = bv;
                 X[0][u % 3] = xv;
                 Pq[q0] = FAST ? L.praw : ((okA ? pa : 0) | ((okB ? pb : 0) << 8) | ((L.ok & 3) << 16));
-                Hq[q0] = __all(Pq[q0] == hot2);
+                Hq[q0] = UNI || __all(Pq[q0] == hot2);
             }
             LMG_TRACE(1);
             fetch(t + PF, pre[u % PF]);
@@ -549,7 +603,7 @@ __device__ __forceinline__ void fused_march(const MArgs &a, const Tables &T, con
                 const int p2 = Pq[q];
                 const d2 bq = Bq[q];
                 d2 nx;
-                if (Hq[q]) {                                                 // wave-uniform
+                if (UNI || Hq[q]) {                                          // wave-uniform (UNI: compile time)
                     if (ZERO && s == 1) {
                         nx.x = omega * (hrd * bq.x);
                         nx.y = omega * (hrd * bq.y);
@@ -591,7 +645,7 @@ __device__ __forceinline__ void fused_march(const MArgs &a, const Tables &T, con
                 const int xm = ((u - S - 2) % 3 + 3) % 3, xc = ((u - S - 1) % 3 + 3) % 3, xp = ((u - S) % 3 + 3) % 3;
                 const int p2 = Pq[q];
                 double accA, accB;
-                if (Hq[q]) {
+                if (UNI || Hq[q]) {
                     apply_rows_hot<UM>(hv, X[S][xm], X[S][xc], X[S][xp], accA, accB);
                 } else {
                     const int pA = p2 & 0xff, pB = (p2 >> 8) & 0xff;
@@ -612,7 +666,7 @@ __device__ __forceinline__ void fused_march(const MArgs &a, const Tables &T, con
                     bool emit_line = false;                                    // FAST: the finished row's line is stored by this wave
                     double emit = 0.0;
                     if (!y_odd) {
-                        if (hot_cur) {
+                        if (UNI || hot_cur) {
 #pragma unroll
                             for (int k = 0; k < 3; ++k) acc_cur = acc_cur + hr[3 + k] * wl[k];
                         } else {
@@ -625,7 +679,7 @@ __device__ __forceinline__ void fused_march(const MArgs &a, const Tables &T, con
                         }
                     } else {
                         // finish the row above ...
-                        if (hot_cur) {
+                        if (UNI || hot_cur) {
 #pragma unroll
                             for (int k = 0; k < 3; ++k) acc_cur = acc_cur + hr[6 + k] * wl[k];
                         } else {
@@ -643,9 +697,9 @@ __device__ __forceinline__ void fused_march(const MArgs &a, const Tables &T, con
                         rp_cur = rp_now;
                         sty_cur = y + 1 >= out_y0 && y + 1 < out_y1;
                         st_cur = sty_cur && colA;
-                        hot_cur = __all(!st_cur || rp_cur == a.rhot);
+                        hot_cur = UNI || __all(!st_cur || rp_cur == a.rhot);
                         acc_cur = 0.0;
-                        if (hot_cur) {
+                        if (UNI || hot_cur) {
 #pragma unroll
                             for (int k = 0; k < 3; ++k) acc_cur = acc_cur + hr[k] * wl[k];
                         } else {
@@ -683,7 +737,6 @@ __global__ void __launch_bounds__(kBlock, (REST && S >= 3) ? 2 : 3) stencil_fuse
     static_assert(!PROL || (!RESID && !ZERO), "the correction is fused into post-smoothing passes only");
     static_assert(!REST || (RESID && !PROL), "the restriction replaces the store of the residual");
     static_assert(kUF % 3 == 0 && kUF % kNBR == 0 && kUF % PF == 0 && S + 2 <= kNBR, "ring periods");
-    constexpr int H = S + (RESID ? 1 : 0) - (ZERO ? 1 : 0);      // halo in lines and columns
     __shared__ double s_val[kMaxPat * 9];
     __shared__ int s_mask[kMaxPat];
     __shared__ double s_rdiag[kMaxPat];
@@ -718,23 +771,36 @@ __global__ void __launch_bounds__(kBlock, (REST && S >= 3) ? 2 : 3) stencil_fuse
     const Item it = decode_item(a, item);
     const Tables T = {s_val, s_mask, s_rdiag, s_pv, s_pm, s_rv, s_rm};
 
-    // FAST?  Every line the march touches -- [y_begin, last prefetched line] -- and the coarse lines that travel
-    // with them must lie strictly inside the vectors, for all 128 window columns of the strip.
-    constexpr int U = StripGeom<H, PROL, REST>::U, ML = StripGeom<H, PROL, REST>::ML;
-    constexpr int HL = H + (REST ? 1 : 0);
-    const int c0 = it.strip * U - ML;
-    const int y_begin = it.out_y0 - HL - ((it.out_y0 - HL) & 1);
-    const int t_last = it.out_y1 - 1 + S + (RESID ? 1 : 0) + (REST ? 1 : 0);
-    const int y_fetch = y_begin + ((t_last - y_begin) / kUF + 1) * kUF - 1 + PF;     // last line fetched
-    bool fast = a.allow_fast && y_begin >= (REST ? S + 2 : 1) && y_fetch <= a.lines - 2 &&
-                (int64_t)y_begin * a.W + c0 >= 0 && (int64_t)y_fetch * a.W + c0 + kStripCols < (int64_t)a.n;
-    if (PROL) fast = fast && (int64_t)((y_fetch + 1) >> 1) * a.Wc + (c0 >> 1) + LMG_WAVE <= (int64_t)a.nc;
-    if (REST) fast = fast && (int64_t)((y_fetch - S) >> 1) * a.Wc + (c0 >> 1) + LMG_WAVE <= (int64_t)a.nc;
 #ifdef LMG_FUSED_WAVETIME
     const unsigned long long wt0 = __builtin_amdgcn_s_memrealtime();
 #endif
-    if (fast) fused_march<S, UM, RESID, ZERO, PF, PROL, REST, true>(a, T, lane, it.strip, it.out_y0, it.out_y1);
-    else fused_march<S, UM, RESID, ZERO, PF, PROL, REST, false>(a, T, lane, it.strip, it.out_y0, it.out_y1);
+    bool fast;
+    if constexpr (kHasUniform<S, RESID, ZERO>) {
+        // which body: scalar work, and four scalar loads from each census table the pass needs (item_body)
+        const int body = item_body<S, RESID, ZERO, PF, PROL, REST>(a, it);
+        fast = body != BODY_GENERAL;
+        if (body == BODY_UNIFORM) fused_march<S, UM, RESID, ZERO, PF, PROL, REST, true, true>(a, T, lane, it.strip, it.out_y0, it.out_y1);
+        else if (fast) fused_march<S, UM, RESID, ZERO, PF, PROL, REST, true, false>(a, T, lane, it.strip, it.out_y0, it.out_y1);
+        else fused_march<S, UM, RESID, ZERO, PF, PROL, REST, false, false>(a, T, lane, it.strip, it.out_y0, it.out_y1);
+    } else {
+        // The kernels without the third body keep the text they had, to the letter: moved into item_body -- the same
+        // conditions (it is what lmg_stencil_smooth_uniform_items evaluates for them) -- it cost them SGPR spills.
+        // FAST?  Every line the march touches -- [y_begin, last prefetched line] -- and the coarse lines that travel
+        // with them must lie strictly inside the vectors, for all 128 window columns of the strip.
+        constexpr int H = S + (RESID ? 1 : 0) - (ZERO ? 1 : 0);
+        constexpr int U = StripGeom<H, PROL, REST>::U, ML = StripGeom<H, PROL, REST>::ML;
+        constexpr int HL = H + (REST ? 1 : 0);
+        const int c0 = it.strip * U - ML;
+        const int y_begin = it.out_y0 - HL - ((it.out_y0 - HL) & 1);
+        const int t_last = it.out_y1 - 1 + S + (RESID ? 1 : 0) + (REST ? 1 : 0);
+        const int y_fetch = y_begin + ((t_last - y_begin) / kUF + 1) * kUF - 1 + PF;     // last line fetched
+        fast = a.allow_fast && y_begin >= (REST ? S + 2 : 1) && y_fetch <= a.lines - 2 &&
+               (int64_t)y_begin * a.W + c0 >= 0 && (int64_t)y_fetch * a.W + c0 + kStripCols < (int64_t)a.n;
+        if (PROL) fast = fast && (int64_t)((y_fetch + 1) >> 1) * a.Wc + (c0 >> 1) + LMG_WAVE <= (int64_t)a.nc;
+        if (REST) fast = fast && (int64_t)((y_fetch - S) >> 1) * a.Wc + (c0 >> 1) + LMG_WAVE <= (int64_t)a.nc;
+        if (fast) fused_march<S, UM, RESID, ZERO, PF, PROL, REST, true, false>(a, T, lane, it.strip, it.out_y0, it.out_y1);
+        else fused_march<S, UM, RESID, ZERO, PF, PROL, REST, false, false>(a, T, lane, it.strip, it.out_y0, it.out_y1);
+    }
 #ifdef LMG_FUSED_WAVETIME
     if (lane == 0 && item < LMG_FUSED_WAVETIME) {
         g_fused_wavetime[2 * item] = wt0;
@@ -757,8 +823,11 @@ int g_fused_balance = 1;        // shorter segments for the items that run the s
 int g_fused_slow_pct = 55;      // their steps, per cent of a normal item's
 int g_fused_fast = 1;           // 0: every wave runs the general body (tests)
 
-template <int S, unsigned UM, bool RESID, bool ZERO, bool PROL = false, bool REST = false>
-int launch4(MArgs a, hipStream_t st)
+constexpr int kPF = 2;          // lines in flight (see launch4)
+
+// The items of a launch: strips, segments and their numbering (decode_item), from the grid and the tune keys.
+template <int S, bool RESID, bool ZERO, bool PROL, bool REST>
+void decompose(MArgs &a)
 {
     constexpr int H = S + (RESID ? 1 : 0) - (ZERO ? 1 : 0);
     constexpr int U = StripGeom<H, PROL, REST>::U;
@@ -804,11 +873,17 @@ int launch4(MArgs a, hipStream_t st)
     if (a.edge_lines > 0) a.segs = 2 + (a.lines - 2 * a.edge_lines + seg_lines - 1) / seg_lines;
     else a.segs = (a.lines + seg_lines - 1) / seg_lines;
     a.items = a.nb_strips * a.segs_b + (a.strips - a.nb_strips) * a.segs;
+}
+
+template <int S, unsigned UM, bool RESID, bool ZERO, bool PROL = false, bool REST = false>
+int launch4(MArgs a, hipStream_t st)
+{
+    decompose<S, RESID, ZERO, PROL, REST>(a);
     const int grid = (a.items + kWavesPerBlock - 1) / kWavesPerBlock;
     // (deeper prefetch, measured round 3 on the scalarised kernel, 4097^2: 3 lines spills in the restricting pass, 0.238 ms;
     // 6 lines at 2 waves / SIMD with 48 - 64-line segments 0.143 vs 0.149 ms with 2 lines and 28-line segments, the
     // correcting pass unchanged -- a wave's step is bound by the dependent chain of its S + 1 stages, not by the loads)
-    hipLaunchKernelGGL((stencil_fused_kernel<S, UM, RESID, ZERO, 2, PROL, REST>), dim3((unsigned)grid), dim3(kBlock), 0, st, a);
+    hipLaunchKernelGGL((stencil_fused_kernel<S, UM, RESID, ZERO, kPF, PROL, REST>), dim3((unsigned)grid), dim3(kBlock), 0, st, a);
     LMG_CHECK_LAUNCH();
     return LMG_OK;
 }
@@ -839,14 +914,33 @@ int launch_rest(MArgs a, int sweeps, bool zero, hipStream_t st)
 }
 
 // the fields only this pass has: the slot set, and the decomposition that launch4 decides
-MArgs own_fields(uint32_t union_mask)
+// -- and the census tables an entry point was handed (none: no wave takes the UNIFORM body)
+MArgs own_fields(uint32_t union_mask, const int32_t *cen_a = nullptr, const int32_t *cen_p = nullptr, const int32_t *cen_r = nullptr)
 {
     MArgs a;
     a.umask = union_mask;
     a.strips = a.segs = a.seg_lines = 0;
     a.items = a.nb_strips = a.edge_lines = a.allow_fast = 0;
     a.segs_b = a.seg_lines_b = 1;
+    a.cen_a = cen_a;
+    a.cen_p = cen_p;
+    a.cen_r = cen_r;
     return a;
+}
+
+// a census table comes with the row stride its grid gives it (cells + 1), or not at all
+bool census_fits(const int32_t *table, int32_t census_stride, int32_t grid_stride)
+{
+    return !table || (grid_stride >= 1 && census_stride == lmg_census_cells(grid_stride) + 1);
+}
+
+// how many items of a launch run each body (host copies of the tables in `a`)
+template <int S, bool RESID, bool ZERO, bool PROL, bool REST>
+int count_bodies(MArgs a, int64_t *counts)
+{
+    decompose<S, RESID, ZERO, PROL, REST>(a);
+    for (int item = 0; item < a.items; ++item) ++counts[item_body<S, RESID, ZERO, kPF, PROL, REST>(a, decode_item(a, item))];
+    return LMG_OK;
 }
 
 }  // namespace
@@ -869,16 +963,43 @@ constexpr LmgTuneKey lmg_tune_fused[] = {
 
 extern "C" {
 
+int lmg_stencil_smooth_census(int64_t n, int32_t line_stride, const uint8_t *pid, int32_t npat, const double *st_val,
+                              const int32_t *st_mask, uint32_t union_mask, int32_t hot_pattern, const double *h_hot_val,
+                              int sweeps, const double *x_in, const double *b, double omega, double *x_out, double *r_out,
+                              const int32_t *census, int32_t census_stride, void *stream)
+{
+    if (!census_fits(census, census_stride, line_stride)) return LMG_ERR_ARG;
+    return lmg_fused_pass<kMask5, kMask9, kMask1D>(      // other slot sets: run the separate sweeps
+        own_fields(union_mask, census), {n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val},
+        {sweeps, x_in, b, omega, x_out, r_out}, nullptr, nullptr, [&](const MArgs &a, auto m) {
+            return launch_plain<LMG_CT(m)>(a, sweeps, r_out != nullptr, x_in == nullptr, lmg_stream(stream));
+        });
+}
+
 int lmg_stencil_smooth(int64_t n, int32_t line_stride, const uint8_t *pid, int32_t npat, const double *st_val,
                        const int32_t *st_mask, uint32_t union_mask, int32_t hot_pattern, const double *h_hot_val,
                        int sweeps, const double *x_in, const double *b, double omega, double *x_out, double *r_out,
                        void *stream)
 {
-    return lmg_fused_pass<kMask5, kMask9, kMask1D>(      // other slot sets: run the separate sweeps
-        own_fields(union_mask), {n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val},
-        {sweeps, x_in, b, omega, x_out, r_out}, nullptr, nullptr, [&](const MArgs &a, auto m) {
-            return launch_plain<LMG_CT(m)>(a, sweeps, r_out != nullptr, x_in == nullptr, lmg_stream(stream));
-        });
+    return lmg_stencil_smooth_census(n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val, sweeps, x_in,
+                                     b, omega, x_out, r_out, nullptr, 0, stream);
+}
+
+int lmg_stencil_smooth_prolong_census(int64_t n, int32_t line_stride, const uint8_t *pid, int32_t npat, const double *st_val,
+                                      const int32_t *st_mask, uint32_t union_mask, int32_t hot_pattern,
+                                      const double *h_hot_val, int sweeps, const double *x_in, const double *b, double omega,
+                                      double *x_out, int64_t n_coarse, int32_t coarse_stride, const double *e_coarse,
+                                      const uint8_t *p_pid, int32_t p_npat, const double *p_val, const int32_t *p_mask,
+                                      const int32_t *h_hot_pairs, const double *h_hot_pval, const int32_t *census,
+                                      const int32_t *p_census, int32_t census_stride, void *stream)
+{
+    if (!census_fits(census, census_stride, line_stride) || !census_fits(p_census, census_stride, line_stride)) return LMG_ERR_ARG;
+    const LmgProl p = {n_coarse, coarse_stride, e_coarse, p_pid, p_npat, p_val, p_mask, h_hot_pairs, h_hot_pval};
+    return lmg_fused_pass<kMask5, kMask9>(
+        own_fields(union_mask, census, p_census),
+        {n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val},
+        {sweeps, x_in, b, omega, x_out, nullptr}, &p, nullptr,
+        [&](const MArgs &a, auto m) { return launch_prol<LMG_CT(m)>(a, sweeps, lmg_stream(stream)); });
 }
 
 int lmg_stencil_smooth_prolong(int64_t n, int32_t line_stride, const uint8_t *pid, int32_t npat, const double *st_val,
@@ -888,11 +1009,26 @@ int lmg_stencil_smooth_prolong(int64_t n, int32_t line_stride, const uint8_t *pi
                                int32_t p_npat, const double *p_val, const int32_t *p_mask, const int32_t *h_hot_pairs,
                                const double *h_hot_pval, void *stream)
 {
-    const LmgProl p = {n_coarse, coarse_stride, e_coarse, p_pid, p_npat, p_val, p_mask, h_hot_pairs, h_hot_pval};
+    return lmg_stencil_smooth_prolong_census(n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val,
+                                             sweeps, x_in, b, omega, x_out, n_coarse, coarse_stride, e_coarse, p_pid, p_npat,
+                                             p_val, p_mask, h_hot_pairs, h_hot_pval, nullptr, nullptr, 0, stream);
+}
+
+int lmg_stencil_smooth_restrict_census(int64_t n, int32_t line_stride, const uint8_t *pid, int32_t npat, const double *st_val,
+                                       const int32_t *st_mask, uint32_t union_mask, int32_t hot_pattern,
+                                       const double *h_hot_val, int sweeps, const double *x_in, const double *b, double omega,
+                                       double *x_out, int64_t n_coarse, int32_t coarse_stride, double *b_coarse,
+                                       const uint8_t *r_pid, int32_t r_npat, const double *r_val, const int32_t *r_mask,
+                                       int32_t hot_r, const double *h_hot_rval, const int32_t *census, int32_t census_stride,
+                                       const int32_t *r_census, int32_t r_census_stride, void *stream)
+{
+    if (!census_fits(census, census_stride, line_stride) || !census_fits(r_census, r_census_stride, coarse_stride)) return LMG_ERR_ARG;
+    const LmgRest r = {n_coarse, coarse_stride, b_coarse, r_pid, r_npat, r_val, r_mask, hot_r, h_hot_rval};
     return lmg_fused_pass<kMask5, kMask9>(
-        own_fields(union_mask), {n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val},
-        {sweeps, x_in, b, omega, x_out, nullptr}, &p, nullptr,
-        [&](const MArgs &a, auto m) { return launch_prol<LMG_CT(m)>(a, sweeps, lmg_stream(stream)); });
+        own_fields(union_mask, census, nullptr, r_census),
+        {n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val},
+        {sweeps, x_in, b, omega, x_out, nullptr}, nullptr, &r,
+        [&](const MArgs &a, auto m) { return launch_rest<LMG_CT(m)>(a, sweeps, x_in == nullptr, lmg_stream(stream)); });
 }
 
 int lmg_stencil_smooth_restrict(int64_t n, int32_t line_stride, const uint8_t *pid, int32_t npat, const double *st_val,
@@ -902,11 +1038,36 @@ int lmg_stencil_smooth_restrict(int64_t n, int32_t line_stride, const uint8_t *p
                                 int32_t r_npat, const double *r_val, const int32_t *r_mask, int32_t hot_r,
                                 const double *h_hot_rval, void *stream)
 {
-    const LmgRest r = {n_coarse, coarse_stride, b_coarse, r_pid, r_npat, r_val, r_mask, hot_r, h_hot_rval};
-    return lmg_fused_pass<kMask5, kMask9>(
-        own_fields(union_mask), {n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val},
-        {sweeps, x_in, b, omega, x_out, nullptr}, nullptr, &r,
-        [&](const MArgs &a, auto m) { return launch_rest<LMG_CT(m)>(a, sweeps, x_in == nullptr, lmg_stream(stream)); });
+    return lmg_stencil_smooth_restrict_census(n, line_stride, pid, npat, st_val, st_mask, union_mask, hot_pattern, h_hot_val,
+                                              sweeps, x_in, b, omega, x_out, n_coarse, coarse_stride, b_coarse, r_pid, r_npat,
+                                              r_val, r_mask, hot_r, h_hot_rval, nullptr, 0, nullptr, 0, stream);
+}
+
+int lmg_stencil_smooth_uniform_items(int64_t n, int32_t line_stride, int sweeps, int with_residual, int zero_iterate, int form,
+                                     int64_t n_coarse, int32_t coarse_stride, const int32_t *h_census,
+                                     const int32_t *h_p_census, const int32_t *h_r_census, int64_t *h_counts)
+{
+    const bool prol = form == 1, rest = form == 2;
+    if (n < 2 || n >= MArgs::kRowLimit || line_stride < 3 || line_stride > n || sweeps < 1 || sweeps > 3 || form < 0 || form > 2 ||
+        !h_counts)
+        return LMG_ERR_ARG;
+    if ((prol && (with_residual || zero_iterate)) || (rest && !with_residual)) return LMG_ERR_ARG;
+    if ((prol || rest) && (coarse_stride < 1 || n_coarse < coarse_stride || n_coarse >= (1ll << 31))) return LMG_ERR_ARG;
+    MArgs a = own_fields(0, h_census, h_p_census, h_r_census);
+    a.n = (int)n;
+    a.W = line_stride;
+    a.lines = (int)((n + line_stride - 1) / line_stride);
+    a.nc = (prol || rest) ? (int)n_coarse : 0;
+    a.Wc = (prol || rest) ? coarse_stride : 0;
+    a.hot = a.phot[0] = a.phot[1] = a.rhot = 0;        // a table stands for a hot pattern
+    h_counts[0] = h_counts[1] = h_counts[2] = 0;
+    return lmg_with_sweeps<1, 3>(sweeps, [&](auto s) {
+        if (prol) return count_bodies<LMG_CT(s), false, false, true, false>(a, h_counts);
+        return lmg_with_flag(zero_iterate != 0, [&](auto z) {
+            if (rest) return count_bodies<LMG_CT(s), true, LMG_CT(z), false, true>(a, h_counts);
+            return lmg_with_flag(with_residual != 0, [&](auto r) { return count_bodies<LMG_CT(s), LMG_CT(r), LMG_CT(z), false, false>(a, h_counts); });
+        });
+    });
 }
 
 int lmg_stencil_smooth_supported(uint32_t union_mask)

@@ -158,6 +158,66 @@ __global__ void __launch_bounds__(kLmgBlock) pattern_parity_counts_kernel(int64_
         if (s_cnt[i]) atomicAdd(&counts[i], s_cnt[i]);
 }
 
+// ---- census of the rows that do not hold the expected pattern (table layout: lmg_common.hpp) --------------------------
+// First launch: one wave per table row.  Wave 0 clears the border row; wave y + 1 counts line y -- lane l the cell
+// 64 k + l in round k -- and writes the running sum along the line.  expect: the id wanted at (line parity, column parity),
+// packed one byte each in the order 00, 01, 10, 11; bit 8 + k of `none` set: nothing is wanted there (every row counts).
+__global__ void __launch_bounds__(kLmgBlock) pattern_census_lines_kernel(int64_t n, int W, int lines, const unsigned char *pid,
+                                                                         unsigned expect, unsigned none, int *table)
+{
+    const int lane = threadIdx.x & (LMG_WAVE - 1);
+    const int row = (int)blockIdx.x * (kLmgBlock / LMG_WAVE) + (int)(threadIdx.x / LMG_WAVE);
+    if (row > lines) return;
+    const int cells = lmg_census_cells(W);
+    int *out = table + (int64_t)row * (cells + 1);
+    if (row == 0) {
+        for (int c = lane; c <= cells; c += LMG_WAVE) out[c] = 0;
+        return;
+    }
+    const int y = row - 1;
+    if (lane == 0) out[0] = 0;
+    int carry = 0;
+    for (int cb = 0; cb < cells; cb += LMG_WAVE) {
+        const int c = cb + lane;
+        int bad = 0;
+        if (c < cells) {
+            for (int k = 0; k < kLmgCensusCell; ++k) {
+                const int x = c * kLmgCensusCell + k;
+                const int64_t i = (int64_t)y * W + x;
+                const int par = ((y & 1) << 1) | (x & 1);
+                const bool ok = x < W && i < n && !((none >> par) & 1u) && pid[i] == ((expect >> (8 * par)) & 0xffu);
+                bad += ok ? 0 : 1;
+            }
+        }
+        // inclusive sum over the lanes, then the cells of the rounds before
+        for (int d = 1; d < LMG_WAVE; d <<= 1) {
+            const int up = __shfl_up(bad, d, LMG_WAVE);
+            if (lane >= d) bad += up;
+        }
+        if (c < cells) out[c + 1] = carry + bad;
+        carry += __shfl(bad, LMG_WAVE - 1, LMG_WAVE);
+    }
+}
+
+// Second launch: one thread per table column sums down the lines, eight loads in flight.
+__global__ void __launch_bounds__(kLmgBlock) pattern_census_columns_kernel(int lines, int cells, int *table)
+{
+    const int c = (int)blockIdx.x * kLmgBlock + (int)threadIdx.x + 1;
+    if (c > cells) return;
+    const int64_t cs = cells + 1;
+    int sum = 0;
+    for (int y0 = 1; y0 <= lines; y0 += 8) {
+        int v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = y0 + k <= lines ? table[(int64_t)(y0 + k) * cs + c] : 0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            sum += v[k];
+            if (y0 + k <= lines) table[(int64_t)(y0 + k) * cs + c] = sum;
+        }
+    }
+}
+
 // ---- exclusive scan (int32): per-block scan + block sums + add-back -------------------
 constexpr int kScanBlock = 1024;
 constexpr int kScanItems = 4;
@@ -391,6 +451,33 @@ int lmg_pattern_parity_counts(int64_t n, int32_t line_stride, const uint8_t *pid
     if (n == 0) return LMG_OK;
     hipLaunchKernelGGL(pattern_parity_counts_kernel, dim3(lmg_grid_for(n, kLmgBlock * 16)), dim3(kLmgBlock), 0, lmg_stream(stream), n,
                        line_stride, pid, counts);
+    LMG_CHECK_LAUNCH();
+    return LMG_OK;
+}
+
+int64_t lmg_pattern_census_count(int64_t n, int32_t line_stride)
+{
+    if (n < 1 || line_stride < 1 || (n + line_stride - 1) / line_stride >= INT_MAX) return 0;
+    return lmg_census_count((int)((n + line_stride - 1) / line_stride), line_stride);
+}
+
+int lmg_pattern_census(int64_t n, int32_t line_stride, const uint8_t *pid, const int32_t *h_expected, int32_t *table, void *stream)
+{
+    if (n < 0 || n >= (1ll << 31) - 8 || line_stride < 1 || !h_expected || (n > 0 && (!pid || !table))) return LMG_ERR_ARG;
+    if (n == 0) return LMG_OK;
+    unsigned expect = 0, none = 0;
+    for (int k = 0; k < 4; ++k) {
+        if (h_expected[k] > 255) return LMG_ERR_ARG;
+        if (h_expected[k] < 0) none |= 1u << k;
+        else expect |= (unsigned)h_expected[k] << (8 * k);
+    }
+    const int lines = (int)((n + line_stride - 1) / line_stride), cells = lmg_census_cells(line_stride);
+    constexpr int kWaves = kLmgBlock / LMG_WAVE;
+    hipLaunchKernelGGL(pattern_census_lines_kernel, dim3((unsigned)((lines + 1 + kWaves - 1) / kWaves)), dim3(kLmgBlock), 0,
+                       lmg_stream(stream), n, line_stride, lines, pid, expect, none, table);
+    LMG_CHECK_LAUNCH();
+    hipLaunchKernelGGL(pattern_census_columns_kernel, dim3((unsigned)((cells + kLmgBlock - 1) / kLmgBlock)), dim3(kLmgBlock), 0,
+                       lmg_stream(stream), lines, cells, table);
     LMG_CHECK_LAUNCH();
     return LMG_OK;
 }

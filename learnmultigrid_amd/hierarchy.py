@@ -789,13 +789,18 @@ class Hierarchy:
     def twin_bytes(self):
         """Bytes of the storage twins of every level's A, P and R at the width they have (fp32 value streams count 4 B a
         value): what the cycle's launches stream, next to the CSR arrays memory_bytes() counts -- those stay fp64 whatever
-        cycle_values is, the Galerkin products and rebuild_numeric read them."""
+        cycle_values is, the Galerkin products and rebuild_numeric read them.  The census tables of the grid views (twins.py:
+        census_table; 4 B an entry) are counted here and not in StencilTwin.bytes(), which bench.py reads as the traffic of
+        one sweep: no sweep reads a table, a wave of a fused register pass reads four words of each."""
         tot = 0
         for lev in self.levels:
             for M in (lev.A, lev.P, lev.R):
                 for name in ("patterns", "sell", "packed", "dia"):
                     T = getattr(M, name, None) if M is not None else None
                     tot += 0 if T is None else T.bytes()
+                for name in ("stencil", "prolong", "restrict"):
+                    census = getattr(getattr(M, name, None), "census", None)
+                    tot += 0 if census is None else 4 * census.numel()
         return tot
 
     @staticmethod

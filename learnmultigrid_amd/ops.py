@@ -18,7 +18,7 @@ import torch
 from . import _lib
 from ._lib import LmgError, check
 from .twins import (F32, F64, I32, ColorSell, DiaTwin, PackedCSR, ProlongTwin, RestrictTwin, RowPatterns, SellCSR,  # noqa: F401
-                    StencilTwin, _p, _s, check_values)
+                    StencilTwin, _p, _s, census_stride, check_values)
 
 
 def _vec_ok(*ts):
@@ -387,7 +387,50 @@ def _run_pass(stem, kind, A, head, x_in, r_out, prolong, restrict):
             raise LmgError("%s: the register pass folds no transfer into an operator with entries across a line end" % who)
         tail = T.c_args(vec)
     name = "lmg_stencil_%s%s%s" % (stem, "_tiled" if tiled else "", "_" + form if form else "")
+    if not tiled and stem == "smooth" and _FUSED_UNIFORM_ENABLED and S.census is not None:
+        # the register pass with the census tables of the twins: waves that meet only hot rows never look at an id
+        name += "_census"
+        tail += _census_args(S, T if form else None, form)
     check(getattr(_lib.lib(), name)(*S.c_args(), *head, *tail, _s(S.pid)), name)
+
+
+_FUSED_UNIFORM_ENABLED = True
+
+
+def set_fused_uniform_enabled(flag):
+    """Whether the register-fused passes are handed the census tables of their twins (default), i.e. whether waves that
+    read nothing but hot rows run the id-free body, or every launch goes to the entry points without tables (A/B runs
+    and parity tests).  Same bits either way."""
+    global _FUSED_UNIFORM_ENABLED
+    _FUSED_UNIFORM_ENABLED = bool(flag)
+
+
+def _census_args(S, T, form):
+    """The trailing arguments of lmg_stencil_smooth[_prolong | _restrict]_census: the tables of the operator's twin S and
+    of the transfer's twin T (None where a twin has none) and their row strides."""
+    if form is None:
+        return (_p(S.census), census_stride(S.W))
+    if form == "prolong":
+        return (_p(S.census), _p(T.census), census_stride(S.W))
+    return (_p(S.census), census_stride(S.W), _p(T.census), census_stride(T.Wc))
+
+
+def fused_uniform_items(A, sweeps, with_residual=False, zero=False, prolong=None, restrict=None):
+    """(general, fast, uniform): how many items (waves) of the register-fused pass that stencil_smooth would launch on A
+    with these arguments run each body -- the kernel's own predicate, evaluated on the host from copies of the census
+    tables (lmg_stencil_smooth_uniform_items), with the tune keys as they stand.  prolong / restrict: the transfer
+    matrix whose twin the pass folds in.  Twins without a table count as the kernel sees them: no uniform item."""
+    S = A.stencil
+    form, T = (1, prolong.prolong) if prolong is not None else (2, restrict.restrict) if restrict is not None else (0, None)
+    use = _FUSED_UNIFORM_ENABLED
+    host = [None if (t is None or not use) else t.cpu().numpy() for t in
+            (S.census, T.census if form == 1 else None, T.census if form == 2 else None)]
+    counts = (ctypes.c_int64 * 3)()
+    check(_lib.lib().lmg_stencil_smooth_uniform_items(
+        S.n, S.W, int(sweeps), int(bool(with_residual or form == 2)), int(bool(zero)), form, T.nc if T is not None else 0,
+        T.Wc if T is not None else 0, *[None if h is None else h.ctypes.data for h in host], ctypes.addressof(counts)),
+        "lmg_stencil_smooth_uniform_items")
+    return tuple(int(c) for c in counts)
 
 
 # The transfers are folded into the fused passes only on levels that do not fit the Infinity Cache: what is saved is

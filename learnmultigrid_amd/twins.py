@@ -158,6 +158,33 @@ def _hot_values(values, hot):
     return None if hot < 0 else (ctypes.c_double * 9)(*[float(v) for v in values[hot * 9: hot * 9 + 9]])
 
 
+CENSUS_CELL = 32               # columns per cell of a census table (kLmgCensusCell)
+
+
+def census_stride(W):
+    """Row stride of the census table of a grid with line stride W: its cells and the border column."""
+    return (int(W) + CENSUS_CELL - 1) // CENSUS_CELL + 1
+
+
+def census_table(pid, n, W, expected):
+    """The census (lmg_pattern_census, include/lmg.h) of the rows of the id array `pid` -- n rows in lines of W -- that do
+    not hold the id expected[2 * (line & 1) + (column & 1)]: int32 2-D prefix sums over (line, cell of 32 columns), from
+    which the register-fused passes read which waves meet nothing but hot rows.  Built by the twin that decides the hot
+    ids, next to them, from the ids it holds: a table lives and dies with its twin, and a twin is never changed in place
+    (DeviceCSR.pack / repack_values build new ones), so it cannot go stale.  None when any expected id is missing, and for
+    ids that are not on a device (the passes then run without)."""
+    if min(expected) < 0 or not pid.is_cuda:
+        return None
+    L = _lib.lib()
+    count = int(L.lmg_pattern_census_count(int(n), int(W)))
+    if count <= 0:
+        return None
+    table = torch.empty(count, dtype=I32, device=pid.device)
+    exp = (ctypes.c_int32 * 4)(*[int(e) for e in expected])
+    check(L.lmg_pattern_census(int(n), int(W), _p(pid), ctypes.addressof(exp), _p(table), _s(pid)), "lmg_pattern_census")
+    return table
+
+
 class PackedCSR:
     """Lossless packed twin of a DeviceCSR for lmg_pcsr_sweep (see include/lmg.h):
     uint8 row lengths, uint16 tile-relative columns when every 512-row tile spans < 65536
@@ -605,7 +632,7 @@ class StencilTwin:
     from_patterns returns None for everything that does not fit (the RPAT kernel then runs)."""
 
     __slots__ = ("n", "W", "npat", "pid", "st_val", "st_mask", "umask", "bytes_", "patterns", "hot", "_hot_val",
-                 "_gs_ok", "_gs_work", "_line_end")
+                 "_gs_ok", "_gs_work", "_line_end", "census")
     _decompose = staticmethod(_decompose)
 
     @classmethod
@@ -634,6 +661,12 @@ class StencilTwin:
         cand = [p for p in range(R.npat) if st_mask[p] == self.umask and (st_mask[p] & 16) and st_val[p * 9 + 4] != 0.0]
         self.hot = hot_pattern(cand, _pid_counts(R) if len(cand) > 1 else None)
         self._hot_val = _hot_values(st_val, self.hot)
+        # where the rows are that are NOT the hot one: the register pass runs its id-free body everywhere else
+        self.census = None
+        if self.hot >= 0 and _lib.lib().lmg_stencil_smooth_supported(self.umask):
+            self.census = census_table(R.pid, self.n, self.W, [self.hot] * 4)
+        # (bytes() stays what a sweep over the twin moves -- bench.py reads it as that --: no sweep reads the table, one wave
+        # of a fused pass four words of it.  The tables are counted in Hierarchy.twin_bytes)
         # wavefront Gauss-Seidel (lmg_stencil_gs_sweep): see gs_ok below (decided on first use)
         self._gs_work = None
         self._gs_ok = None
@@ -689,7 +722,7 @@ class ProlongTwin:
     table of a RowPatterns twin with the column-base map (W, Wc, 1, 1, 0); from_patterns returns None for
     everything else (the correction then runs as its own lmg_rpat_sweep_grid launch)."""
 
-    __slots__ = ("n", "W", "nc", "Wc", "npat", "pid", "p_val", "p_mask", "_hot_pairs", "_hot_pval", "patterns")
+    __slots__ = ("n", "W", "nc", "Wc", "npat", "pid", "p_val", "p_mask", "_hot_pairs", "_hot_pval", "patterns", "census")
 
     @classmethod
     def from_patterns(cls, R, shape):
@@ -719,6 +752,9 @@ class ProlongTwin:
         # (the values of the hot pairs travel in scalar registers)
         self._hot_pairs = (ctypes.c_int32 * 2)(*hot[0])
         self._hot_pval = (ctypes.c_double * 9)(*hot[1])
+        # rows that are not the hot pair's pattern for their (line parity, column parity); no table without both pairs
+        pe, po = hot[0]
+        self.census = census_table(R.pid, n, W, [-1] * 4 if min(pe, po) < 0 else [pe & 255, pe >> 8, po & 255, po >> 8])
         return self
 
     def c_args(self, e):
@@ -734,7 +770,7 @@ class RestrictTwin:
     tensor-product interpolation.  Derived on the host from the pattern table of a RowPatterns twin with the
     column-base map (Wc, 2 W, 0, 0, 1); None for everything else (the restriction then is its own launch)."""
 
-    __slots__ = ("nc", "Wc", "n", "W", "npat", "pid", "r_val", "r_mask", "hot", "_hot_val", "patterns")
+    __slots__ = ("nc", "Wc", "n", "W", "npat", "pid", "r_val", "r_mask", "hot", "_hot_val", "patterns", "census")
 
     @classmethod
     def from_patterns(cls, R, shape):
@@ -761,6 +797,7 @@ class RestrictTwin:
         cand = [p for p in range(R.npat) if r_mask[p] == 0x1FF]
         self.hot = hot_pattern(cand, _pid_counts(R) if len(cand) > 1 else None)
         self._hot_val = _hot_values(r_val, self.hot)
+        self.census = census_table(R.pid, self.nc, self.Wc, [self.hot] * 4)       # over the COARSE grid
         return self
 
     def c_args(self, bc):
