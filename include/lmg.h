@@ -787,6 +787,54 @@ int lmg_block_multi_axpy(int k, int64_t n, const int *h_counts, int subtract, co
                          double *d_W, double *d_partials, double *d_norm2, void *stream);
 int lmg_block_scale(int k, int64_t n, const double *h_scale, double *d_W, void *stream);
 
+/* ---- the two inner Krylov steps of a K-cycle visit (csrc/krylov.hip) -------------------------------------------------------
+ * On a level of n rows with operator A, c1 and c2 the results of the two child visits, v1 = A c1, v2 = A c2, b the right-hand
+ * side of the level.  gcr != 0: p = v (GCR, any A); gcr == 0: p = c (flexible CG, symmetric positive definite A and cycle).
+ *
+ *   lmg_kcycle_step1   alpha1 = <p1, b>, rho1 = <p1, v1>, t1 = rho1 != 0 ? alpha1 / rho1 : 0, rt = b + (-t1) * v1.
+ *   lmg_kcycle_step2   gamma = <p2, v1>, beta = <p2, v2>, alpha2 = <p2, rt>;  rho1 and t1 are READ from d_scal;
+ *                      q = rho1 != 0 ? gamma / rho1 : 0, rho2 = beta - gamma * q, t2 = rho2 != 0 ? alpha2 / rho2 : 0,
+ *                      a = t1 - q * t2, x_out = a * c1 + t2 * c2.
+ *
+ * Every product and every sum is rounded on its own in the order written; non-finite values are not masked (NaN != 0).
+ * d_scal: LMG_KC_SCALARS doubles on the DEVICE at the indices below, written by the device only (step 1 writes 0 .. 2, step 2
+ * writes 3 .. 8).  Inputs are never written and nothing beyond element n - 1 is touched.  d_x_out may be d_c2 (same bits as
+ * a separate output); an output that is any other input of its step is LMG_ERR_ARG.  Null pointers, n < 1, a form outside
+ * 0 .. 2 and partials_count < lmg_kcycle_partials_count(n) are LMG_ERR_ARG, a vector off 16 bytes is LMG_ERR_ALIGN, all
+ * before any launch.  d_partials: partials_count doubles of scratch.  With gcr != 0 step 1 does not read d_c1.
+ *
+ * Launches.  G = lmg_kcycle_grid(n) = min(ceil(n / 2048), 512) workgroups of 256 lanes, a function of n alone.  Lane t of
+ * workgroup g owns the element pairs (2 i, 2 i + 1), i = 256 g + t + 256 G m, m = 0, 1, ..., one 16-byte load per vector
+ * and step, one accumulator per product, first element of the pair first; the last element of an odd n goes to lane 0 of
+ * workgroup 0 after its pairs.  A workgroup's share of a product: 64-lane butterfly, then its four waves in ascending order.
+ * A product: lane t adds share t and share t + 256 (0.0 for a share >= G), butterfly, four waves.  No atomics.
+ *   form 2 (two launches): the first writes one share per workgroup and product; in the second every workgroup sums the
+ *          shares itself, forms the coefficients and updates its pairs; workgroup 0 writes d_scal.
+ *   form 1 (one launch): one workgroup of 1024 lanes computes the G shares -- four at a time, quarter w of the workgroup
+ *          being workgroup 4 m + w of form 2 -- keeps them in LDS, and goes on as every workgroup of the second launch.
+ *   form 0: form 1 for n <= lmg_kcycle_one_launch_max(), else form 2.
+ * The bits of d_rt, d_x_out and d_scal depend on the inputs and n only: not on the form, a tune key or the call history. */
+enum {
+    LMG_KC_ALPHA1 = 0,
+    LMG_KC_RHO1 = 1,
+    LMG_KC_T1 = 2,
+    LMG_KC_GAMMA = 3,
+    LMG_KC_BETA = 4,
+    LMG_KC_ALPHA2 = 5,
+    LMG_KC_RHO2 = 6,
+    LMG_KC_T2 = 7,
+    LMG_KC_A = 8,
+    LMG_KC_SCALARS = 9
+};
+int lmg_kcycle_grid(int64_t n);
+int64_t lmg_kcycle_partials_count(int64_t n);
+int64_t lmg_kcycle_one_launch_max(void);
+int lmg_kcycle_step1(int64_t n, int gcr, int form, const double *d_c1, const double *d_v1, const double *d_b, double *d_rt,
+                     double *d_scal, double *d_partials, int64_t partials_count, void *stream);
+int lmg_kcycle_step2(int64_t n, int gcr, int form, const double *d_c1, const double *d_v1, const double *d_c2,
+                     const double *d_v2, const double *d_rt, double *d_scal, double *d_x_out, double *d_partials,
+                     int64_t partials_count, void *stream);
+
 /* ---- coarsest level --------------------------------------------------------------
  * y = M x for a dense row-major n x m matrix: applies a pre-factored coarse operator
  * (M = A_L^-1 computed once at setup) in place of the per-cycle SuperLU

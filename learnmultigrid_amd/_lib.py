@@ -136,6 +136,11 @@ SIGNATURES = {
     "lmg_block_multi_dot": (_c.c_int, [_c.c_int, _i64, _c.c_int, _p, _i64, _p, _p, _p, _p]),
     "lmg_block_multi_axpy": (_c.c_int, [_c.c_int, _i64, _p, _c.c_int, _p, _i64, _p, _p, _p, _p, _p]),
     "lmg_block_scale": (_c.c_int, [_c.c_int, _i64, _p, _p, _p]),
+    "lmg_kcycle_grid": (_c.c_int, [_i64]),
+    "lmg_kcycle_partials_count": (_i64, [_i64]),
+    "lmg_kcycle_one_launch_max": (_i64, []),
+    "lmg_kcycle_step1": (_c.c_int, [_i64, _c.c_int, _c.c_int, _p, _p, _p, _p, _p, _p, _i64, _p]),
+    "lmg_kcycle_step2": (_c.c_int, [_i64, _c.c_int, _c.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
     "lmg_dense_gemv": (_c.c_int, [_i64, _i64, _p, _p, _p, _p]),
     "lmg_dense_gemv_blockdiag": (_c.c_int, [_i64, _i64, _p, _p, _p, _p]),
     "lmg_dense_gemv_windows": (_c.c_int, [_i64, _i64, _i64, _p, _p, _i64, _p, _i64, _f64, _p, _i64, _p]),

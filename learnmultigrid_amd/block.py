@@ -15,7 +15,7 @@ import math
 
 import torch
 
-from .hierarchy import capture_cycle, cycle_children
+from .hierarchy import capture_cycle, cycle_children, linear_cycle_children
 from .ops import F64
 
 
@@ -151,9 +151,11 @@ class BlockCycle:
         self._smooth(bl, steps, omega)
 
     def cycle(self, steps, omega, shape="V"):
-        """One V(steps, steps), W or F cycle (the shapes of Hierarchy.cycle) with weighted Jacobi on levels[0].x / .b."""
+        """One V(steps, steps), W or F cycle (the linear shapes of Hierarchy.cycle; "K" raises ValueError) with weighted
+        Jacobi on levels[0].x / .b."""
+        children = linear_cycle_children(shape, "BlockCycle")
         self._sync()
-        self._visit(0, cycle_children(shape), int(steps), float(omega))
+        self._visit(0, children, int(steps), float(omega))
 
     def apply(self, src, dst, steps, omega, shape="V", use_graph=False):
         """One cycle on the right-hand sides src (an (n, k) block) from a zero guess: the cycle as a preconditioner.  The
@@ -185,6 +187,6 @@ class BlockCycle:
         key = (int(steps), float(omega), shape, self.nrhs)
         g = self._graphs.get(key)
         if g is None:
-            cycle_children(shape)
+            linear_cycle_children(shape, "BlockCycle")
             g = self._graphs[key] = capture_cycle(self.ops, self.levels, lambda: self.cycle(steps, omega, shape))
         return g

@@ -509,9 +509,270 @@ int block_basis_check(int k, int64_t n, int nb, const double *V, int64_t ldb, co
     return LMG_OK;
 }
 
+// ---- the two inner Krylov steps of a K-cycle visit -----------------------------------------------------------------------
+// A step is: NP dot products of one vector p with NP vectors q in one pass, the coefficients from them, one vector update.
+// The products are cut into G = kc_grid(n) shares whatever runs them: share g is what lane t = 0 .. 255 of "workgroup g"
+// adds up over the element pairs g * 256 + t, + 256 G, ..., summed in lmg_block_sum<256>'s order.  Form 2 gives every share
+// a workgroup of its own and a second launch that sums them; form 1 is one workgroup of 1024 lanes whose quarters take four
+// shares at a time.  Both run the same three functions below, so no bit depends on the form.
+constexpr int kKcShareElems = 2048;         // elements a share is sized for: four pair steps of 256 lanes
+constexpr int kKcMaxGrid = 512;             // most shares; grid-stride beyond kKcShareElems * kKcMaxGrid elements
+constexpr int kKcOneBlock = 1024;           // lanes of the one-launch form
+constexpr int kKcQuarters = kKcOneBlock / kLmgBlock;
+// Largest n that takes the one-launch form under form 0: the largest power of two at which it was no slower than two
+// launches on an MI355X, replayed from a graph and launched eagerly (tools/time_kcycle.py steps; the table is in DESIGN.md
+// section 3: from a graph one launch wins up to 4096 and loses from 8192, eagerly it wins up to 16384).
+constexpr int64_t kKcOneLaunchMax = 1 << 12;
+
+inline int kc_grid(int64_t n)
+{
+    int64_t g = (n + kKcShareElems - 1) / kKcShareElems;
+    return (int)(g < 1 ? 1 : g > kKcMaxGrid ? kKcMaxGrid : g);
+}
+
+struct KcArgs {
+    int64_t n;
+    int G;
+    const double *c1, *v1, *c2, *v2, *r;    // r: the right-hand side b (step 1), rt (step 2)
+    double *out, *scal, *partial;           // out: rt (step 1), x_out (step 2)
+};
+
+template <int STEP>
+struct KcStep {
+    static constexpr int NP = STEP == 1 ? 2 : 3;
+};
+
+// acc[c] = lane t's part of share g of p . q_c.  Step 1: q = (b, v1), p = v1 (GCR) or c1; step 2: q = (v1, v2, rt), p = v2
+// (GCR) or c2.  With GCR p is q_1 and is loaded once.
+template <int STEP, bool GCR>
+__device__ __forceinline__ void kc_lane_products(const KcArgs &a, int g, int t, double (&acc)[3])
+{
+    constexpr int NP = KcStep<STEP>::NP;
+    const double *q[3] = {STEP == 1 ? a.r : a.v1, STEP == 1 ? a.v1 : a.v2, STEP == 1 ? nullptr : a.r};
+    const double *p = STEP == 1 ? a.c1 : a.c2;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) acc[c] = 0.0;
+    const int64_t n2 = a.n >> 1;
+    const int64_t stride = (int64_t)a.G * kLmgBlock;
+    for (int64_t i = (int64_t)g * kLmgBlock + t; i < n2; i += stride) {
+        d2 qv[NP];
+#pragma unroll
+        for (int c = 0; c < NP; ++c) qv[c] = reinterpret_cast<const d2 *>(q[c])[i];
+        const d2 pv = GCR ? qv[1] : reinterpret_cast<const d2 *>(p)[i];
+#pragma unroll
+        for (int c = 0; c < NP; ++c) {
+            acc[c] += pv.x * qv[c].x;
+            acc[c] += pv.y * qv[c].y;
+        }
+    }
+    if ((a.n & 1) && g == 0 && t == 0) {
+        const int64_t e = a.n - 1;
+        double ql[NP];
+#pragma unroll
+        for (int c = 0; c < NP; ++c) ql[c] = q[c][e];
+        const double pl = GCR ? ql[1] : p[e];
+#pragma unroll
+        for (int c = 0; c < NP; ++c) acc[c] += pl * ql[c];
+    }
+}
+
+// tot[c] = product c from its G shares, in every lane of the workgroup: lane t < 256 adds share t and share t + 256 (0.0
+// beyond G), 64-lane butterfly, the four waves in ascending order.  Lanes from 256 on (form 1) only keep the barriers.
+template <int NP>
+__device__ __forceinline__ void kc_totals(const double *share, int G, double (*s_red)[kLmgBlock / LMG_WAVE], double *s_tot,
+                                          double (&tot)[3])
+{
+    const int t = threadIdx.x;
+    if (t < kLmgBlock) {
+        const int lane = t & (LMG_WAVE - 1), wave = t / LMG_WAVE;
+#pragma unroll
+        for (int c = 0; c < NP; ++c) {
+            const double lo = t < G ? share[c * G + t] : 0.0;
+            const double hi = t + kLmgBlock < G ? share[c * G + t + kLmgBlock] : 0.0;
+            const double s = lmg_wave_sum(lo + hi);
+            if (lane == 0) s_red[c][wave] = s;
+        }
+    }
+    __syncthreads();
+    if (t < NP) {
+        double sum = 0.0;
+#pragma unroll
+        for (int w = 0; w < kLmgBlock / LMG_WAVE; ++w) sum += s_red[t][w];
+        s_tot[t] = sum;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < 3; ++c) tot[c] = c < NP ? s_tot[c] : 0.0;
+}
+
+// The coefficients from the products, in every lane alike, and the update of the pairs first, first + stride, ...; the
+// writer (one lane of the launch) stores the scalars and the last element of an odd n.
+template <int STEP>
+__device__ __forceinline__ void kc_finish(const KcArgs &a, const double (&tot)[3], int64_t first, int64_t stride, bool writer)
+{
+    const int64_t n2 = a.n >> 1;
+    d2 *out2 = reinterpret_cast<d2 *>(a.out);
+    if (STEP == 1) {
+        const double alpha1 = tot[0], rho1 = tot[1];
+        const double t1 = rho1 != 0.0 ? alpha1 / rho1 : 0.0;
+        if (writer) {
+            a.scal[LMG_KC_ALPHA1] = alpha1;
+            a.scal[LMG_KC_RHO1] = rho1;
+            a.scal[LMG_KC_T1] = t1;
+        }
+        const double nt = -t1;
+        for (int64_t i = first; i < n2; i += stride) {
+            const d2 bv = reinterpret_cast<const d2 *>(a.r)[i], vv = reinterpret_cast<const d2 *>(a.v1)[i];
+            d2 o;
+            o.x = bv.x + nt * vv.x;
+            o.y = bv.y + nt * vv.y;
+            out2[i] = o;
+        }
+        if ((a.n & 1) && writer) a.out[a.n - 1] = a.r[a.n - 1] + nt * a.v1[a.n - 1];
+    } else {
+        const double gamma = tot[0], beta = tot[1], alpha2 = tot[2];
+        const double rho1 = a.scal[LMG_KC_RHO1], t1 = a.scal[LMG_KC_T1];
+        const double q = rho1 != 0.0 ? gamma / rho1 : 0.0;
+        const double rho2 = beta - gamma * q;
+        const double t2 = rho2 != 0.0 ? alpha2 / rho2 : 0.0;
+        const double ca = t1 - q * t2;
+        if (writer) {
+            a.scal[LMG_KC_GAMMA] = gamma;
+            a.scal[LMG_KC_BETA] = beta;
+            a.scal[LMG_KC_ALPHA2] = alpha2;
+            a.scal[LMG_KC_RHO2] = rho2;
+            a.scal[LMG_KC_T2] = t2;
+            a.scal[LMG_KC_A] = ca;
+        }
+        for (int64_t i = first; i < n2; i += stride) {
+            const d2 x1 = reinterpret_cast<const d2 *>(a.c1)[i], x2 = reinterpret_cast<const d2 *>(a.c2)[i];
+            d2 o;
+            o.x = ca * x1.x + t2 * x2.x;
+            o.y = ca * x1.y + t2 * x2.y;
+            out2[i] = o;                    // (out may be c2: this lane has read its pair)
+        }
+        if ((a.n & 1) && writer) a.out[a.n - 1] = ca * a.c1[a.n - 1] + t2 * a.c2[a.n - 1];
+    }
+}
+
+// form 2, first launch: workgroup g writes share g of every product to partial[c * G + g]
+template <int STEP, bool GCR>
+__global__ void __launch_bounds__(kLmgBlock) kc_shares_kernel(KcArgs a)
+{
+    constexpr int NP = KcStep<STEP>::NP;
+    __shared__ double s_red[NP][kLmgBlock / LMG_WAVE];
+    double acc[3];
+    kc_lane_products<STEP, GCR>(a, (int)blockIdx.x, (int)threadIdx.x, acc);
+#pragma unroll
+    for (int c = 0; c < NP; ++c) {
+        const double tot = lmg_block_sum<kLmgBlock>(acc[c], s_red[c]);
+        if (threadIdx.x == 0) a.partial[c * a.G + (int)blockIdx.x] = tot;
+    }
+}
+
+// form 2, second launch: every workgroup sums the shares, forms the coefficients and updates the pairs of its share
+template <int STEP>
+__global__ void __launch_bounds__(kLmgBlock) kc_update_kernel(KcArgs a)
+{
+    constexpr int NP = KcStep<STEP>::NP;
+    __shared__ double s_red[NP][kLmgBlock / LMG_WAVE];
+    __shared__ double s_tot[NP];
+    double tot[3];
+    kc_totals<NP>(a.partial, a.G, s_red, s_tot, tot);
+    kc_finish<STEP>(a, tot, (int64_t)blockIdx.x * kLmgBlock + threadIdx.x, (int64_t)a.G * kLmgBlock,
+                    blockIdx.x == 0 && threadIdx.x == 0);
+}
+
+// form 1: one workgroup.  Quarter w (lanes 256 w .. 256 w + 255) is workgroup g0 + w of form 2 for g0 = 0, 4, ...; the
+// shares stay in LDS.
+template <int STEP, bool GCR>
+__global__ void __launch_bounds__(kKcOneBlock) kc_one_kernel(KcArgs a)
+{
+    constexpr int NP = KcStep<STEP>::NP;
+    __shared__ double s_share[NP * kKcMaxGrid];
+    __shared__ double s_quarter[kKcQuarters][NP][kLmgBlock / LMG_WAVE];
+    __shared__ double s_red[NP][kLmgBlock / LMG_WAVE];
+    __shared__ double s_tot[NP];
+    const int w = (int)threadIdx.x / kLmgBlock, t = (int)threadIdx.x % kLmgBlock;
+    const int lane = t & (LMG_WAVE - 1), wave = t / LMG_WAVE;
+    for (int g0 = 0; g0 < a.G; g0 += kKcQuarters) {
+        const int g = g0 + w;
+        if (g < a.G) {                      // (uniform over the waves of a quarter)
+            double acc[3];
+            kc_lane_products<STEP, GCR>(a, g, t, acc);
+#pragma unroll
+            for (int c = 0; c < NP; ++c) {
+                const double s = lmg_wave_sum(acc[c]);
+                if (lane == 0) s_quarter[w][c][wave] = s;
+            }
+        }
+        __syncthreads();
+        if (g < a.G && t < NP) {
+            double tot = 0.0;
+#pragma unroll
+            for (int k = 0; k < kLmgBlock / LMG_WAVE; ++k) tot += s_quarter[w][t][k];
+            s_share[t * a.G + g] = tot;
+        }
+        __syncthreads();
+    }
+    double tot[3];
+    kc_totals<NP>(s_share, a.G, s_red, s_tot, tot);
+    kc_finish<STEP>(a, tot, (int64_t)threadIdx.x, (int64_t)kKcOneBlock, threadIdx.x == 0);
+}
+
+template <int STEP>
+int kc_launch(const KcArgs &a, bool gcr, int form, hipStream_t st)
+{
+    const bool one = form == 1 || (form == 0 && a.n <= kKcOneLaunchMax);
+    if (one) {
+        if (gcr) hipLaunchKernelGGL((kc_one_kernel<STEP, true>), dim3(1), dim3(kKcOneBlock), 0, st, a);
+        else hipLaunchKernelGGL((kc_one_kernel<STEP, false>), dim3(1), dim3(kKcOneBlock), 0, st, a);
+        LMG_CHECK_LAUNCH();
+        return LMG_OK;
+    }
+    if (gcr) hipLaunchKernelGGL((kc_shares_kernel<STEP, true>), dim3((unsigned)a.G), dim3(kLmgBlock), 0, st, a);
+    else hipLaunchKernelGGL((kc_shares_kernel<STEP, false>), dim3((unsigned)a.G), dim3(kLmgBlock), 0, st, a);
+    LMG_CHECK_LAUNCH();
+    hipLaunchKernelGGL(kc_update_kernel<STEP>, dim3((unsigned)a.G), dim3(kLmgBlock), 0, st, a);
+    LMG_CHECK_LAUNCH();
+    return LMG_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int lmg_kcycle_grid(int64_t n) { return kc_grid(n); }
+
+int64_t lmg_kcycle_partials_count(int64_t n) { return 3 * (int64_t)kc_grid(n); }
+
+int64_t lmg_kcycle_one_launch_max(void) { return kKcOneLaunchMax; }
+
+int lmg_kcycle_step1(int64_t n, int gcr, int form, const double *d_c1, const double *d_v1, const double *d_b, double *d_rt,
+                     double *d_scal, double *d_partials, int64_t partials_count, void *stream)
+{
+    if (n < 1 || form < 0 || form > 2 || !d_c1 || !d_v1 || !d_b || !d_rt || !d_scal || !d_partials) return LMG_ERR_ARG;
+    if (partials_count < lmg_kcycle_partials_count(n)) return LMG_ERR_ARG;
+    if (d_rt == d_c1 || d_rt == d_v1 || d_rt == d_b) return LMG_ERR_ARG;
+    if (!lmg_aligned16(d_c1) || !lmg_aligned16(d_v1) || !lmg_aligned16(d_b) || !lmg_aligned16(d_rt)) return LMG_ERR_ALIGN;
+    const KcArgs a = {n, kc_grid(n), d_c1, d_v1, nullptr, nullptr, d_b, d_rt, d_scal, d_partials};
+    return kc_launch<1>(a, gcr != 0, form, lmg_stream(stream));
+}
+
+int lmg_kcycle_step2(int64_t n, int gcr, int form, const double *d_c1, const double *d_v1, const double *d_c2,
+                     const double *d_v2, const double *d_rt, double *d_scal, double *d_x_out, double *d_partials,
+                     int64_t partials_count, void *stream)
+{
+    if (n < 1 || form < 0 || form > 2 || !d_c1 || !d_v1 || !d_c2 || !d_v2 || !d_rt || !d_scal || !d_x_out || !d_partials)
+        return LMG_ERR_ARG;
+    if (partials_count < lmg_kcycle_partials_count(n)) return LMG_ERR_ARG;
+    if (d_x_out == d_c1 || d_x_out == d_v1 || d_x_out == d_v2 || d_x_out == d_rt) return LMG_ERR_ARG;
+    if (!lmg_aligned16(d_c1) || !lmg_aligned16(d_v1) || !lmg_aligned16(d_c2) || !lmg_aligned16(d_v2) || !lmg_aligned16(d_rt) ||
+        !lmg_aligned16(d_x_out))
+        return LMG_ERR_ALIGN;
+    const KcArgs a = {n, kc_grid(n), d_c1, d_v1, d_c2, d_v2, d_rt, d_x_out, d_scal, d_partials};
+    return kc_launch<2>(a, gcr != 0, form, lmg_stream(stream));
+}
 
 int lmg_krylov_max_vectors(void) { return kKryMaxVectors; }
 

@@ -60,7 +60,7 @@ import torch
 import torch.distributed as dist
 
 from . import smoothing
-from .hierarchy import Hierarchy, capture_cycle
+from .hierarchy import Hierarchy, capture_cycle, linear_cycle_children
 from .ops import DeviceCSR, F64, I32
 
 _UNREACHED = 1 << 20           # _layer_of: "in none of the layers" (deeper than any halo)
@@ -207,11 +207,20 @@ def _check_smoother(smoother):
                          "(processor-block Gauss-Seidel), not %r" % (smoother,))
 
 
+def _check_shape(cycle_shape):
+    """The distributed cycle is a V-cycle: a K-cycle (its dot products would be all-reduces inside the cycle) and the other
+    shapes of Hierarchy.cycle are refused by name."""
+    if linear_cycle_children(cycle_shape, "the distributed cycle") != ("V",):
+        raise ValueError("the distributed cycle runs the 'V' shape only, got %r" % (cycle_shape,))
+
+
 class DistributedVCycle:
     def __init__(self, full, device, ops_mod=None, grid_side=None, replicate_below=2_000_000,
-                 group=None, halo_depth=8):
+                 group=None, halo_depth=8, cycle_shape="V"):
         """full: a replicated hierarchy (learnmultigrid_amd.hierarchy.Hierarchy or anything
-        with the same .levels[l].A/.P/.R, .coarse_solve(), .cycle())."""
+        with the same .levels[l].A/.P/.R, .coarse_solve(), .cycle()).  cycle_shape: "V", the one shape the distributed
+        cycle has; anything else is refused here, before any collective call."""
+        _check_shape(cycle_shape)
         if ops_mod is None:
             from . import ops as ops_mod
         self.ops = ops_mod

@@ -29,14 +29,33 @@ from .twins import DiaTwin, check_values, line_reach, line_stride
 
 
 CYCLE_SHAPES = ("V", "W", "F")                         # pyamg's multilevel_solver.solve(cycle=...)
-_CHILDREN = {"V": ("V",), "W": ("W", "W"), "F": ("F", "V")}
+KRYLOV_SHAPES = ("K",)                                 # ... and the nonlinear cycle pyamg spells cycle='AMLI' (Hierarchy.cycle)
+K_INNER = ops.K_INNER                                  # the inner Krylov method of a K-cycle
+_CHILDREN = {"V": ("V",), "W": ("W", "W"), "F": ("F", "V"), "K": ("K", "K")}
 
 
 def cycle_children(shape):
-    """The cycles a `shape` cycle runs on the next coarser level, one after the other (pyamg's convention)."""
-    if shape not in _CHILDREN:
-        raise ValueError("cycle shape must be one of %s, got %r" % (CYCLE_SHAPES, shape))
+    """The cycles a `shape` cycle runs on the next coarser level, one after the other (pyamg's convention).  A K-cycle
+    runs two, each from a zero iterate, and combines them (Hierarchy._accelerated); whoever cannot do that asks
+    linear_cycle_children."""
+    if not isinstance(shape, str) or shape not in _CHILDREN:
+        raise ValueError("cycle shape must be one of %s, got %r" % (CYCLE_SHAPES + KRYLOV_SHAPES, shape))
     return _CHILDREN[shape]
+
+
+def linear_cycle_children(shape, who):
+    """cycle_children for a cycle that has the linear shapes only: `who` (named in the ValueError) has no K-cycle."""
+    if isinstance(shape, str) and shape in KRYLOV_SHAPES:
+        raise ValueError("%s has no %r cycle: the Krylov-accelerated cycle runs on single right-hand sides of a "
+                         "single-GPU Hierarchy only (Multigrid.solve, GMRES.solve); use one of %s"
+                         % (who, shape, CYCLE_SHAPES))
+    return cycle_children(shape)
+
+
+def k_inner_name(k_inner):
+    if not isinstance(k_inner, str) or k_inner not in K_INNER:
+        raise ValueError("k_inner must be one of %s, got %r" % (K_INNER, k_inner))
+    return k_inner
 
 
 def capture_cycle(ops_mod, levels, run, swap_from=None):
@@ -75,7 +94,7 @@ def _to_csr_host(M):
 
 class Level:
     __slots__ = ("n", "A", "P", "R", "x", "b", "r", "tmp", "plan_RA", "plan_RAP", "RA",
-                 "gs_sched", "host_pattern", "dinv", "M", "plan_RM", "plan_RMP", "RM", "d", "line", "line_band")
+                 "gs_sched", "host_pattern", "dinv", "M", "plan_RM", "plan_RMP", "RM", "d", "line", "line_band", "kc")
 
     def __init__(self, A):
         self.n = A.shape[0]
@@ -93,6 +112,7 @@ class Level:
         self.d = None                  # Chebyshev smoother: the step vector of the two-launch path (prepare_smoother)
         self.line = None               # "Line" smoother: {"W": line stride, "x" / "y": factor triple} (prepare_smoother)
         self.line_band = None          # ... {"x" / "y": half-bandwidth p}; p > 1: the factors are one (2 p + 1) n block
+        self.kc = None                 # K-cycle: the work vectors (rt, v1, v2, x2) of an accelerated level (_prepare_kcycle)
         self.M = None                  # mass matrix of the level (optional, see Hierarchy(mass=...))
         self.plan_RM = self.plan_RMP = self.RM = None
 
@@ -175,6 +195,7 @@ class Hierarchy:
         self._cheby = None             # Chebyshev smoother: bounds and coefficient tables (prepare_smoother)
         self._line = None              # "Line" smoother: the (line_dir, line_order) in use (prepare_smoother)
         self._line_band = 1            # ... and the largest half-bandwidth a level may use (line_band)
+        self.kscal = self.kpartials = None   # K-cycle: the scalars of every accelerated level, the scratch of the steps
 
     def _each_transfer(self, transfers):
         """The transfers one by one.  A callable f(l, A_l) -> P or None is asked once per level with that level's DeviceCSR,
@@ -620,9 +641,56 @@ class Hierarchy:
                 self.coarse.apply(lev.r, lev.tmp)
                 self.ops.axpby(1.0, lev.tmp, 1.0, lev.x)
 
+    # ------------------------------------------------------------------ K-cycle --------
+    def _prepare_kcycle(self):
+        """What a K-cycle needs beyond the other shapes, made once (never inside a capture: cycle() and captured_cycle() come
+        here first): four work vectors on every accelerated level -- the levels 1 .. L-1, whose visits the level above
+        combines --, nine scalars for each of them in one buffer, and the scratch of the two steps."""
+        missing = [name for name in ("kcycle_step1", "kcycle_step2") if not hasattr(self.ops, name)]
+        if missing:
+            raise ValueError("cycle shape 'K' needs an ops module with kcycle_step1 and kcycle_step2; this one (%s) lacks %s"
+                             % (getattr(self.ops, "__name__", type(self.ops).__name__), " and ".join(missing)))
+        inner = self.levels[1:-1]
+        if self.kscal is not None or not inner:
+            return
+        for lev in inner:
+            lev.kc = tuple(torch.zeros(lev.n, dtype=F64, device=self.device) for _ in range(4))
+        ns = len(ops.KCYCLE_SCALARS)
+        scal = torch.zeros(ns * len(inner), dtype=F64, device=self.device)
+        self.kscal = [None] + [scal[ns * i:ns * (i + 1)] for i in range(len(inner))]
+        count = self._ask("kcycle_partials_count", inner[0].n)           # (the largest accelerated level)
+        self.kpartials = torch.zeros(max(int(count), 1), dtype=F64, device=self.device)
+
+    def _accelerated(self, smoother, steps, omega, gs_mode, l, last, pair, k_inner):
+        """The coarse correction of a K-cycle on level l < last: levels[l].b holds the right-hand side b_c, levels[l].x
+        receives two steps of flexible GCR or CG on A_l x = b_c from zero, preconditioned by one K-cycle visit of level l
+        (cycle()).  Per call: the two visits, two products with A_l, one launch sequence each of ops.kcycle_step1 and
+        kcycle_step2; the coefficients never leave the device.  The second visit runs on other buffers -- its right-hand
+        side is rt where step 1 wrote it, its iterate and scratch are the level's spare buffer and a work vector -- so b_c, c1
+        and v1 stay as they are; afterwards b is back in its slot and x and tmp hold the level's own two buffers."""
+        lev = self.levels[l]
+        rt, v1, v2, x2 = lev.kc
+        scal = self.kscal[l]
+
+        def visit():
+            self._visit(smoother, steps, omega, gs_mode, l, last, cycle_children("K"), pair, x_is_zero=True, k_inner=k_inner)
+
+        visit()
+        b, c1, spare = lev.b, lev.x, lev.tmp
+        self.ops.csr_spmv(lev.A, c1, v1, 1.0, 0.0)
+        self.ops.kcycle_step1(k_inner, c1, v1, b, rt, scal, self.kpartials)
+        lev.b, lev.x = rt, x2
+        try:
+            visit()
+            c2 = lev.x                                                    # (the spare buffer or x2)
+            self.ops.csr_spmv(lev.A, c2, v2, 1.0, 0.0)
+            self.ops.kcycle_step2(k_inner, c1, v1, c2, v2, rt, scal, spare, self.kpartials)
+        finally:
+            lev.b, lev.x, lev.tmp = b, spare, c1
+
     def cycle(self, smoother, steps, omega=1.0, gs_mode="lexicographic", l=0, depth=None,
               after_presmooth=None, x_is_zero=False, gs_sweep=("forward", "forward"), shape="V", *,
-              cheby_lmax=None, cheby_ratio=None, line_dir=None, line_order=None, line_band=None):
+              cheby_lmax=None, cheby_ratio=None, line_dir=None, line_order=None, line_band=None, k_inner="gcr"):
         """One V(steps, steps) cycle on level l: levels[l].x is the iterate, levels[l].b the
         right-hand side (Multigrid.py:77-124).  depth = number of grids used.
         gs_sweep: directions of the Gauss-Seidel pre- and post-smoothing, a pyamg sweep name for both or a (pre, post)
@@ -634,6 +702,17 @@ class Hierarchy:
         starting from the first one's iterate with the same right-hand side; the coarsest level is solved once per
         visit of the level above it.  Where a level runs the tiled Jacobi passes, the post-smoothing of one visit and
         the pre-smoothing of the next run as one turnaround pass (ops.stencil_smooth_turnaround).
+        shape "K" (KRYLOV_SHAPES; Notay and Vassilevski's K-cycle, pyamg's cycle='AMLI'): on every level below the finest
+        but the coarsest, the coarse system A x_c = b_c is solved by two steps of a flexible Krylov method preconditioned by
+        the K-cycle of that level, each visit from a zero iterate (pyamg starts from ones):
+            c1 = visit(b_c), v1 = A c1, p1 = v1 ("gcr") | c1 ("fcg"), t1 = <p1, b_c> / <p1, v1>, rt = b_c - t1 v1,
+            c2 = visit(rt),  v2 = A c2, p2 likewise, gamma = <p2, v1>, beta = <p2, v2>, alpha2 = <p2, rt>, q = gamma / rho1,
+            rho2 = beta - gamma q, t2 = alpha2 / rho2, x_c = (t1 - q t2) c1 + t2 c2      (a quotient by 0 is 0)
+        with the products, coefficients and updates in ops.kcycle_step1 / kcycle_step2 on the device: always two steps, no
+        early exit, the launch sequence is fixed (captured_cycle) and the work is a W-cycle's plus two products with A per
+        visit.  The cycle is a nonlinear operator: a preconditioner for flexible methods (GMRES.solve), not for CG.
+        k_inner "gcr" (default) minimises the residual and takes any operator; "fcg" is for symmetric positive definite
+        operators with symmetric cycles.  A two-level hierarchy runs the V-cycle, bit for bit.  No turnaround passes.
         smoother "Chebyshev": `steps` is the DEGREE of the one polynomial smoothing step run before and after the coarse
         correction, on [lmax / cheby_ratio, lmax] of D^-1 A per level (omega is not used).  cheby_lmax / cheby_ratio as in
         prepare_smoother; left None they are what was prepared (the Gershgorin bounds and CHEBY_RATIO by default).
@@ -642,25 +721,30 @@ class Hierarchy:
         post-smoothing half runs the directions and colours in reverse (gs_sweep is not used).  line_band as in
         prepare_smoother, left None the band in use."""
         children = cycle_children(shape)
+        k_inner = k_inner_name(k_inner) if shape in KRYLOV_SHAPES else None
         if smoother == "Chebyshev":
             chebyshev_degree(steps)
         pair = gs_sweep_pair(gs_sweep)
         self._prepare(smoother, cheby_lmax, cheby_ratio, line_dir, line_order, line_band)
+        if k_inner is not None:
+            self._prepare_kcycle()
         if smoother == "Line":
             pair = ("forward", "backward")
         self._visit(smoother, steps, omega, gs_mode, l, (len(self.levels) if depth is None else depth) - 1, children,
-                    pair, x_is_zero, after_presmooth)
+                    pair, x_is_zero, after_presmooth, k_inner=k_inner)
 
     def _visit(self, smoother, steps, omega, gs_mode, l, last, children, pair, x_is_zero=False, after_presmooth=None,
-               entered=False, leave_open=False):
+               entered=False, leave_open=False, k_inner=None):
         """One cycle on level l whose recursion below is `children` (cycle_children of its shape).  entered: the
         pre-smoothing and the restriction have run already (in a turnaround pass).  leave_open: a visit of the same level
         follows -- return True without the post-smoothing where a turnaround pass can run it together with that visit's
-        pre-smoothing."""
+        pre-smoothing.  k_inner: a K-cycle -- the two visits of the next level are combined by _accelerated."""
         if not entered:
             self._presmooth(smoother, steps, omega, gs_mode, l, x_is_zero, pair[0], after_presmooth)
         if l + 1 == last:
             self.coarse_solve()                                               # :106
+        elif k_inner is not None:
+            self._accelerated(smoother, steps, omega, gs_mode, l + 1, last, pair, k_inner)
         else:
             open_ = False
             for i, sub in enumerate(children):
@@ -772,18 +856,21 @@ class Hierarchy:
                     self.gs_schedule(l, gs_mode, d)
 
     def captured_cycle(self, smoother, steps, omega, gs_mode, gs_sweep=("forward", "forward"), shape="V", *,
-                       cheby_lmax=None, cheby_ratio=None, line_dir=None, line_order=None, line_band=None):
+                       cheby_lmax=None, cheby_ratio=None, line_dir=None, line_order=None, line_band=None, k_inner="gcr"):
         """The same launch sequence as cycle(), captured once into a hipGraph and replayed (one graph per sweep pair and
-        cycle shape)."""
+        cycle shape, and per k_inner of a K-cycle)."""
         pair = gs_sweep_pair(gs_sweep)
         cycle_children(shape)
+        krylov = (k_inner_name(k_inner),) if shape in KRYLOV_SHAPES else ()
         self._prepare(smoother, cheby_lmax, cheby_ratio, line_dir, line_order, line_band)   # (before the key and the capture)
-        key = (smoother, steps, omega, gs_mode, pair, shape) + self._smoother_key(smoother)
+        if krylov:
+            self._prepare_kcycle()
+        key = (smoother, steps, omega, gs_mode, pair, shape) + krylov + self._smoother_key(smoother)
         g = self._graphs.get(key)
         if g is None:
             self.prepare_smoother(smoother, gs_mode, gs_sweep=pair)
             g = self._graphs[key] = capture_cycle(self.ops, self.levels, swap_from=1, run=lambda: self.cycle(
-                smoother, steps, omega, gs_mode, gs_sweep=pair, shape=shape))
+                smoother, steps, omega, gs_mode, gs_sweep=pair, shape=shape, k_inner=k_inner))
         return g
 
     def twin_bytes(self):
@@ -814,11 +901,13 @@ class Hierarchy:
     def memory_bytes(self):
         tot = 0
         for lev in self.levels:
-            tot += lev.A.bytes() + (4 + (lev.d is not None)) * 8 * lev.n
+            tot += lev.A.bytes() + (4 + (lev.d is not None) + (0 if lev.kc is None else len(lev.kc))) * 8 * lev.n
             tot += 0 if lev.line is None else sum(8 * (2 * lev.line_band[d] + 1) * lev.n for d in lev.line if d != "W")
             for M in (lev.P, lev.R, lev.RA):
                 if M is not None:
                     tot += M.bytes()
+        if self.kscal is not None:                     # (K-cycle: the scalars of the accelerated levels and the steps' scratch)
+            tot += 8 * (sum(s.numel() for s in self.kscal[1:]) + self.kpartials.numel())
         return tot + self.coarse.bytes_per_apply()
 
     def cycle_bytes(self, steps):

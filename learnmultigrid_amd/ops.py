@@ -1352,6 +1352,57 @@ def multi_axpy(V, k, coef, w, partials=None, norm2=None, subtract=True):
                                     _p(norm2), _s(w)), "lmg_multi_axpy")
 
 
+# ---- the inner Krylov steps of a K-cycle visit (csrc/krylov.hip) --------------------------------------------------------------
+K_INNER = ("gcr", "fcg")
+# where kcycle_step1 / kcycle_step2 leave their scalars (include/lmg.h: LMG_KC_*)
+KCYCLE_SCALARS = ("alpha1", "rho1", "t1", "gamma", "beta", "alpha2", "rho2", "t2", "a")
+KCYCLE_FORMS = {"auto": 0, "one": 1, "two": 2}
+
+
+def kcycle_partials_count(n):
+    return int(_lib.lib().lmg_kcycle_partials_count(int(n)))
+
+
+def kcycle_grid(n):
+    """Workgroups of the two-launch form on n rows = shares every product is cut into."""
+    return int(_lib.lib().lmg_kcycle_grid(int(n)))
+
+
+def kcycle_one_launch_max():
+    """Largest n whose steps run as one launch under form "auto"."""
+    return int(_lib.lib().lmg_kcycle_one_launch_max())
+
+
+def _kcycle_args(name, k_inner, form, vecs, scal, partials):
+    if k_inner not in K_INNER:
+        raise ValueError("k_inner must be 'gcr' or 'fcg', got %r" % (k_inner,))
+    if form not in KCYCLE_FORMS:
+        raise ValueError("%s: form must be 'auto', 'one' or 'two', got %r" % (name, form))
+    _vec_ok(*vecs, scal, partials)
+    n = vecs[0].numel()
+    if any(v.numel() != n for v in vecs) or scal.numel() < len(KCYCLE_SCALARS):
+        raise ValueError("%s: vectors of one length and %d scalars are needed" % (name, len(KCYCLE_SCALARS)))
+    return n, 1 if k_inner == "gcr" else 0, KCYCLE_FORMS[form]
+
+
+def kcycle_step1(k_inner, c1, v1, b, rt, scal, partials, form="auto"):
+    """First inner step of a K-cycle visit: alpha1 = <p1, b>, rho1 = <p1, v1> with p1 = v1 ("gcr") or c1 ("fcg"),
+    t1 = alpha1 / rho1 (0 where rho1 == 0), rt = b - t1 v1; scal[0:3] = (alpha1, rho1, t1), all on the device
+    (lmg_kcycle_step1).  partials: kcycle_partials_count(n) doubles of scratch."""
+    n, gcr, f = _kcycle_args("kcycle_step1", k_inner, form, (c1, v1, b, rt), scal, partials)
+    check(_lib.lib().lmg_kcycle_step1(n, gcr, f, _p(c1), _p(v1), _p(b), _p(rt), _p(scal), _p(partials), partials.numel(), _s(b)),
+          "lmg_kcycle_step1")
+
+
+def kcycle_step2(k_inner, c1, v1, c2, v2, rt, scal, x_out, partials, form="auto"):
+    """Second inner step: gamma = <p2, v1>, beta = <p2, v2>, alpha2 = <p2, rt> with p2 = v2 ("gcr") or c2 ("fcg"), the
+    coefficients from them and from rho1, t1 in scal, x_out = a c1 + t2 c2; scal[3:9] = (gamma, beta, alpha2, rho2, t2, a)
+    (lmg_kcycle_step2).  x_out may be c2."""
+    n, gcr, f = _kcycle_args("kcycle_step2", k_inner, form, (c1, v1, c2, v2, rt, x_out), scal, partials)
+    check(_lib.lib().lmg_kcycle_step2(n, gcr, f, _p(c1), _p(v1), _p(c2), _p(v2), _p(rt), _p(scal), _p(x_out), _p(partials),
+                                      partials.numel(), _s(rt)), "lmg_kcycle_step2")
+
+
 def gather(idx, x, buf):
     check(_lib.lib().lmg_gather(idx.numel(), _p(idx), _p(x), _p(buf), _s(idx)), "lmg_gather")
 

@@ -5,7 +5,8 @@ F-cycles).  The reference has no such class; the conventions are those of CG: th
 entry per iteration after it, stop on ||r|| <= error.
 
 `preconditioner=Hierarchy` preconditions from the right with one cycle from a zero guess per iteration, with CG's
-keywords; `precond_cycle_shape` also takes "F", and `precond_gs_sweep` any sweep name or (pre, post) pair of
+keywords; `precond_cycle_shape` also takes "F" and "K" (the Krylov-accelerated cycle with `precond_k_inner` = "gcr" | "fcg": a
+nonlinear preconditioner, which a flexible method may take), and `precond_gs_sweep` any sweep name or (pre, post) pair of
 Hierarchy.cycle (default forward / forward); `precond_line_band` and `precond_gs_mode` as in CG.solve.  The iteration is krylov.fgmres: classical Gram-Schmidt applied twice in four
 fused launches and one device-to-host read per iteration; its residual estimate is the true residual norm in exact
 arithmetic, and the true norm is recomputed at the end of every cycle of `restart` iterations.  Memory: 2 restart + 1
@@ -18,7 +19,7 @@ import numpy as np
 import torch
 
 from .. import krylov, ops
-from ..hierarchy import cycle_children, gs_sweep_pair
+from ..hierarchy import KRYLOV_SHAPES, cycle_children, gs_sweep_pair, k_inner_name, linear_cycle_children
 from ..ops import F64
 from ._precond import BlockSolves, check_smoother, gs_mode_keyword, make_apply
 from .Solver import IterativeSolver, on_device
@@ -58,8 +59,9 @@ class GMRES(BlockSolves, IterativeSolver):
     def solve(self, max_iterations=1000, error=1e-08, initial_guess=None, *, restart=30, preconditioner=None,
               precond_steps=2, precond_omega=0.8, precond_smoother="Jacobi", precond_cycle_shape="V",
               precond_gs_sweep="forward", precond_line_dir="xy", precond_line_order="zebra",
-              precond_line_band=None, precond_gs_mode="lexicographic"):
+              precond_line_band=None, precond_gs_mode="lexicographic", precond_k_inner="gcr"):
         gs_mode_keyword(precond_gs_mode)
+        k_inner_name(precond_k_inner)
         pair, options = check_keywords(restart, ops.krylov_max_vectors(), precond_smoother, precond_cycle_shape, precond_gs_sweep,
                                        precond_line_dir, precond_line_order, precond_line_band, precond_steps)
         A = self._device_matrix()
@@ -72,8 +74,9 @@ class GMRES(BlockSolves, IterativeSolver):
         H = preconditioner
         apply_M = None
         if H is not None:
+            krylov_kw = {"k_inner": precond_k_inner} if precond_cycle_shape in KRYLOV_SHAPES else {}
             apply_M = make_apply(H, precond_smoother, precond_steps, precond_omega, precond_cycle_shape, pair, options,
-                                 **gs_mode_keyword(precond_gs_mode))
+                                 **gs_mode_keyword(precond_gs_mode), **krylov_kw)
         track, self.iterations = krylov.fgmres(ops, A, b, x, apply_M, restart=int(restart), max_iterations=max_iterations,
                                                error=error, residual_out=r)
         if track[-1] <= error:
@@ -101,13 +104,13 @@ class GMRES(BlockSolves, IterativeSolver):
         iteration (the Arnoldi estimate; the recomputed true norm for the last iteration of each of its cycles) --, NaN
         behind its last iteration.  self.iterations_many[j]: the inner iterations column j ran (0: it started at or below
         error).
-        The preconditioner is one precond_cycle_shape ("V" | "W" | "F") cycle of block.BlockCycle from a zero guess per
-        iteration, which smooths with weighted Jacobi only (precond_steps sweeps before and after, damping precond_omega):
+        The preconditioner is one precond_cycle_shape ("V" | "W" | "F"; "K" raises ValueError) cycle of block.BlockCycle from
+        a zero guess per iteration, which smooths with weighted Jacobi only (precond_steps sweeps before and after, damping precond_omega):
         no other smoother can be asked for here.  A hierarchy with cycle_values="f32" is refused by BlockCycle.  use_graph
         replays the cycle from a captured hipGraph; everything else of an iteration is launched as it is.  solve() is not
         touched by any of this."""
         check_restart(restart, ops.krylov_max_vectors())
-        cycle_children(precond_cycle_shape)
+        linear_cycle_children(precond_cycle_shape, "GMRES.solve_many")
 
         def columns(A, block_cycle, B, X0, dev):
             return krylov.block_fgmres_columns(ops, A, block_cycle, B, X0, dev, restart=int(restart),

@@ -28,7 +28,7 @@ import scipy.sparse as sp
 import torch
 
 from .. import krylov, ops, problems
-from ..hierarchy import Hierarchy, cycle_children, gs_sweep_pair
+from ..hierarchy import KRYLOV_SHAPES, Hierarchy, cycle_children, gs_sweep_pair, k_inner_name, linear_cycle_children
 from ..smoothing import smoother_options
 from ._precond import BlockSolves, check_columns, hierarchy_stream
 from .Solver import IterativeSolver, on_device
@@ -108,7 +108,7 @@ class Multigrid(BlockSolves, IterativeSolver):
               initial_guess=None, cycle="V", first_call=False, *, omega=1.0,
               smoother_semantics="as_shipped", gs_mode="lexicographic", coarse_refine="auto",
               use_graph=False, mutate_initial_guess=False, gs_sweep="forward", cycle_shape="V",
-              cheby_lmax=None, cheby_ratio=None, line_dir="xy", line_order="zebra", line_band=None):
+              cheby_lmax=None, cheby_ratio=None, line_dir="xy", line_order="zebra", line_band=None, k_inner="gcr"):
         """smoother="Line" (under smoother_semantics="as_named"; as shipped the name is ignored like every other): line
         relaxation -- smooth_steps steps with damping omega before and after the coarse correction, each solving the
         tridiagonal systems of the grid lines in direction line_dir ("x": storage lines, "y": grid columns, "xy": x then y;
@@ -124,8 +124,10 @@ class Multigrid(BlockSolves, IterativeSolver):
         runs) -- a pyamg sweep name ("forward" | "backward" | "symmetric") for pre- and post-smoothing, or a (pre, post)
         pair.  ("forward", "backward") gives a symmetric V-cycle at one pipelined launch per smoothing half; "symmetric"
         costs a launch per direction and step.
-        cycle_shape: "V" | "W" | "F", what pyamg's cycle= selects (Hierarchy.cycle).  `cycle` keeps the reference's
-        V-only switch (:55-57)."""
+        cycle_shape: "V" | "W" | "F", what pyamg's cycle= selects, or "K", the Krylov-accelerated cycle (pyamg's 'AMLI';
+        Hierarchy.cycle): every coarse visit is two steps of k_inner = "gcr" (any operator, the default) or "fcg" (symmetric
+        positive definite operators and symmetric cycles) preconditioned by the cycle below, at the cost of a W-cycle; for
+        hierarchies that coarsen aggressively.  `cycle` keeps the reference's V-only switch (:55-57)."""
         if cycle != "V":
             raise ValueError("Cycle type unknown: %r" % (cycle,))            # :55-57
         if levels < 2:
@@ -133,16 +135,18 @@ class Multigrid(BlockSolves, IterativeSolver):
         eff = self._effective_smoother(smoother, smoother_semantics)
         pair = gs_sweep_pair(gs_sweep)
         cycle_children(cycle_shape)
+        k_inner_name(k_inner)
         options = smoother_options(eff, smooth_steps, cheby_lmax=cheby_lmax, cheby_ratio=cheby_ratio, line_dir=line_dir,
                                    line_order=line_order, line_band=line_band)
         H = self._setup(levels, first_call, coarse_refine)
         with hierarchy_stream(H, self._device):
             self._ready(H, eff, options)
             self._solve_on_stream(H, eff, smooth_steps, max_iterations, error, initial_guess, omega,
-                                  gs_mode, use_graph, mutate_initial_guess, pair, cycle_shape)
+                                  gs_mode, use_graph, mutate_initial_guess, pair, cycle_shape, k_inner)
 
     def _solve_on_stream(self, H, eff, smooth_steps, max_iterations, error, initial_guess, omega,
-                         gs_mode, use_graph, mutate_initial_guess, gs_sweep=("forward", "forward"), shape="V"):
+                         gs_mode, use_graph, mutate_initial_guess, gs_sweep=("forward", "forward"), shape="V", k_inner="gcr"):
+        krylov_kw = {"k_inner": k_inner} if shape in KRYLOV_SHAPES else {}
         fine = H.levels[0]
         if initial_guess is None:
             self._log("You should put an initial guess. Used zero vector")
@@ -158,7 +162,7 @@ class Multigrid(BlockSolves, IterativeSolver):
                 if not state["done"]:
                     np.asarray(initial_guess).reshape(-1)[:] = x_dev.cpu().numpy()
                     state["done"] = True
-        graph = H.captured_cycle(eff, smooth_steps, omega, gs_mode, gs_sweep, shape) if use_graph else None
+        graph = H.captured_cycle(eff, smooth_steps, omega, gs_mode, gs_sweep, shape, **krylov_kw) if use_graph else None
         track = []
         for _ in range(max_iterations):                                      # :59
             self.iterations += 1
@@ -174,7 +178,8 @@ class Multigrid(BlockSolves, IterativeSolver):
             if graph is not None and hook is None:
                 graph.launch()
             else:
-                H.cycle(eff, smooth_steps, omega, gs_mode, after_presmooth=hook, gs_sweep=gs_sweep, shape=shape)   # :73
+                H.cycle(eff, smooth_steps, omega, gs_mode, after_presmooth=hook, gs_sweep=gs_sweep, shape=shape,
+                        **krylov_kw)                                                                        # :73
                 hook = None
         self.solution = self._column(fine.x)
         self.residual_vector = (np.ones(shape=(self.dim, 1)) if self.iterations <= 1
@@ -195,8 +200,9 @@ class Multigrid(BlockSolves, IterativeSolver):
         track (iterations, m), the true residual norms ||b_j - A x_j||_2 taken before each cycle -- no sqrt(n) first
         entry, that quirk belongs to the reference's solve().
         The smoother is weighted Jacobi with `omega`, smooth_steps sweeps before and after the coarse correction: this is
-        smoother_semantics="as_named" with smoother="Jacobi" (any other smoother raises ValueError), cycle_shape as in
-        solve().  Column j carries the bits of a single-vector sliced-ELL cycle on column j.
+        smoother_semantics="as_named" with smoother="Jacobi" (any other smoother raises ValueError), cycle_shape "V" | "W" |
+        "F" as in solve() ("K" raises ValueError: the block cycle has no K-cycle).  Column j carries the bits of a
+        single-vector sliced-ELL cycle on column j.
         Columns are padded with zero columns to a width of 2, 4 or 8 and worked through in chunks of 8.  All columns of
         a chunk iterate until every one is <= error or max_iterations is reached: a column that has passed is not
         deflated, it simply keeps being smoothed (its residual keeps falling and is still recorded).
@@ -207,7 +213,7 @@ class Multigrid(BlockSolves, IterativeSolver):
             raise ValueError("levels must be >= 2 (levels counts grids)")
         if smoother != "Jacobi":
             raise ValueError("solve_many smooths with weighted Jacobi only, got smoother=%r" % (smoother,))
-        cycle_children(cycle_shape)
+        linear_cycle_children(cycle_shape, "Multigrid.solve_many")
         H = self._setup(levels, self._FIRST_CALL, coarse_refine)
 
         def solve_chunk(bc, Bk, Xk, mc):
@@ -263,8 +269,18 @@ class Multigrid(BlockSolves, IterativeSolver):
         return self._one_cycle("F", A, u0, rhs, smoother, smooth_steps, levels, first_call, omega, smoother_semantics,
                                gs_mode, coarse_refine, gs_sweep, cheby_lmax, cheby_ratio, line_dir, line_order, line_band)
 
+    @on_device
+    def k_cycle(self, A, u0, rhs, smoother, smooth_steps, error, levels, first_call=False, *,
+                omega=1.0, smoother_semantics="as_shipped", gs_mode="lexicographic",
+                coarse_refine="auto", gs_sweep="forward", cheby_lmax=None, cheby_ratio=None, line_dir="xy",
+                line_order="zebra", line_band=None, k_inner="gcr"):
+        """One K-cycle (solve(cycle_shape="K", k_inner=...)) with v_cycle's arguments and behaviour."""
+        return self._one_cycle("K", A, u0, rhs, smoother, smooth_steps, levels, first_call, omega, smoother_semantics,
+                               gs_mode, coarse_refine, gs_sweep, cheby_lmax, cheby_ratio, line_dir, line_order, line_band,
+                               k_inner=k_inner_name(k_inner))
+
     def _one_cycle(self, shape, A, u0, rhs, smoother, smooth_steps, levels, first_call, omega, smoother_semantics,
-                   gs_mode, coarse_refine, gs_sweep, cheby_lmax, cheby_ratio, line_dir, line_order, line_band):
+                   gs_mode, coarse_refine, gs_sweep, cheby_lmax, cheby_ratio, line_dir, line_order, line_band, **krylov_kw):
         if levels < 2:
             raise ValueError("levels must be >= 2")
         eff = self._effective_smoother(smoother, smoother_semantics)
@@ -292,7 +308,7 @@ class Multigrid(BlockSolves, IterativeSolver):
                 u0a.reshape(-1)[:] = x_dev.cpu().numpy()
         with hierarchy_stream(H, self._device):
             self._ready(H, eff, options)
-            H.cycle(eff, smooth_steps, omega, gs_mode, after_presmooth=hook, gs_sweep=pair, shape=shape)
+            H.cycle(eff, smooth_steps, omega, gs_mode, after_presmooth=hook, gs_sweep=pair, shape=shape, **krylov_kw)
             out = fine.x.cpu().numpy().reshape(n, 1).copy()
             if eff == "GaussSeidel":
                 H.check_smoothers()

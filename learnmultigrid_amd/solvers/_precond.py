@@ -92,14 +92,15 @@ def gs_mode_keyword(precond_gs_mode):
     return {} if precond_gs_mode == "lexicographic" else {"gs_mode": precond_gs_mode}
 
 
-def make_apply(H, smoother, steps, omega, shape, gs_sweep, options, gs_mode="lexicographic"):
+def make_apply(H, smoother, steps, omega, shape, gs_sweep, options, gs_mode="lexicographic", k_inner=None):
     """apply_M(src, dst): dst = one `shape` cycle of H on the right-hand side src from a zero guess (H None: dst = src).
     Prepares what the smoother needs on the hierarchy (options, from check_smoother: Chebyshev bounds and work vectors, line
     factors) before the first application; a smoother without options sets itself up in its first sweep.  gs_sweep: the
     (pre, post) directions of a Gauss-Seidel cycle and gs_mode its ordering (smoothing.GS_MODES); a smoother with no use for
-    them, or for omega, hands them to no launch."""
+    them, or for omega, hands them to no launch.  k_inner: the inner method of a "K" cycle (None: Hierarchy.cycle's default)."""
     if H is not None and options:
         H.prepare_smoother(smoother, **options)
+    krylov_kw = {} if k_inner is None else {"k_inner": k_inner}
 
     def apply_M(src, dst):
         if H is None:
@@ -107,7 +108,7 @@ def make_apply(H, smoother, steps, omega, shape, gs_sweep, options, gs_mode="lex
             return
         fine = H.levels[0]
         ops.copy(src, fine.b)
-        H.cycle(smoother, steps, omega, gs_mode, x_is_zero=True, gs_sweep=gs_sweep, shape=shape)
+        H.cycle(smoother, steps, omega, gs_mode, x_is_zero=True, gs_sweep=gs_sweep, shape=shape, **krylov_kw)
         ops.copy(fine.x, dst)
 
     return apply_M
