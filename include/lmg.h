@@ -1294,6 +1294,48 @@ int lmg_sa_tentative_fill(int64_t n, int64_t n_agg, const int32_t *d_agg, const 
                           const int32_t *d_t_rowptr, double *d_t_vals, void *stream);
 int lmg_sa_row_states(int64_t n, const int32_t *d_t_rowptr, int32_t *d_state, void *stream);
 
+/* ---- smoothed aggregation for systems: node blocks of bs unknowns and k <= LMG_NSP_MAX_CANDIDATES candidates (csrc/nsp.hip; the
+ * stages: aggregation.py).  What pyamg.smoothed_aggregation_solver(A, B) does with a BSR matrix and B of shape (n, k).  The rules:
+ * DESIGN.md section 3, "Smoothed aggregation for systems".  A: sorted, duplicate-free CSR on the device, n = bs n_nodes unknowns,
+ * n < 2^31 - 257 and k n_agg < 2^31 - 257; the unknowns bs I .. bs I + bs - 1 belong to node I.  One lane per row (condense: per
+ * node row; gram_chol, tri_product: per aggregate), no atomics but the refusals, no scratch; every kernel reads what an earlier
+ * launch wrote and writes its own lane's entries, so two calls give the same integers and bits.  Every product and sum rounds on
+ * its own, every sum starts from 0.0.  Every pointer an entry point names must be non-null (LMG_ERR_ARG, nothing launched), bs >= 1,
+ * 1 <= k <= LMG_NSP_MAX_CANDIDATES, 0 <= n_agg <= n_nodes, rank_tol finite and positive.  Nothing to do (n_nodes == 0, n == 0,
+ * n_agg == 0): LMG_OK.
+ *   condense    C (n_nodes x n_nodes): an entry (I, J) iff some stored a_ij lies in that block, explicit zeros included; columns
+ *               ascend; c_IJ = sqrt(sum a_ij a_ij) over the rows of the block ascending and in storage order within a row.
+ *               count: entries per node row; fill: after the caller's scan.  lmg_sa_* run on C unchanged.
+ *   gram_chol   d_m_rowptr / d_m_colidx: row j lists the member NODES of aggregate j in ascending order (the transpose of
+ *               lmg_sa_tentative_pattern on the node aggregates).  d_x: n x k row-major.  g_pq = sum x_ip x_iq (p <= q) over the
+ *               member rows, the nodes ascending and the unknowns within a node ascending.  For c = 0 .. k-1, r = 0 .. c:
+ *               s = g_rc - R_0r R_0c - ... - R_(r-1)r R_(r-1)c in that order; r < c: R_rc = s / R_rr; r = c: R_cc = sqrt(s), and
+ *               unless s is finite and s > rank_tol g_cc the aggregate is refused through d_status (as lmg_sa_norms) with
+ *               bs * (its smallest member node) and LMG_AMG_CANDIDATE; a member list that does not ascend: the aggregate and
+ *               LMG_AMG_MEMBERS.  d_r: n_agg x k x k row-major, zeros below the diagonal.
+ *   apply       for every unknown i of a node with 0 <= d_agg[node] < n_agg: y_0 = x_0 / R_00,
+ *               y_c = (x_c - y_0 R_0c - ... - y_(c-1) R_(c-1)c) / R_cc with the R of that aggregate; other rows of d_y are left
+ *               as they are.  d_agg: per NODE.  d_x != d_y.
+ *   tri_product d_coarse_cand (k n_agg x k row-major): block j = R2_j R1_j, entry (r, c) = sum over q = r .. c of
+ *               R2_rq R1_qc, q ascending; zeros below the diagonal.
+ *   tentative   count: k for a row of an aggregated node, else 0.  fill, after the caller's scan: the columns k agg + c,
+ *               c = 0 .. k-1, with the values y R2^-1 (as apply) of row i of d_y -- the second round written straight into T. */
+#define LMG_NSP_MAX_CANDIDATES 6
+int lmg_nsp_condense_count(int64_t n_nodes, int32_t bs, const int32_t *d_rowptr, const int32_t *d_colidx, int32_t *d_rownnz,
+                           void *stream);
+int lmg_nsp_condense_fill(int64_t n_nodes, int32_t bs, const int32_t *d_rowptr, const int32_t *d_colidx, const double *d_vals,
+                          const int32_t *d_c_rowptr, int32_t *d_c_colidx, double *d_c_vals, void *stream);
+int lmg_nsp_gram_chol(int64_t n_agg, int64_t n_nodes, int32_t bs, int32_t k, const int32_t *d_m_rowptr,
+                      const int32_t *d_m_colidx, const double *d_x, double rank_tol, double *d_r, uint64_t *d_status,
+                      void *stream);
+int lmg_nsp_apply(int64_t n, int64_t n_agg, int32_t bs, int32_t k, const int32_t *d_agg, const double *d_x, const double *d_r,
+                  double *d_y, void *stream);
+int lmg_nsp_tri_product(int64_t n_agg, int32_t k, const double *d_r2, const double *d_r1, double *d_coarse_cand, void *stream);
+int lmg_nsp_tentative_count(int64_t n, int64_t n_agg, int32_t bs, int32_t k, const int32_t *d_agg, int32_t *d_rownnz,
+                            void *stream);
+int lmg_nsp_tentative_fill(int64_t n, int64_t n_agg, int32_t bs, int32_t k, const int32_t *d_agg, const double *d_y,
+                           const double *d_r2, const int32_t *d_t_rowptr, int32_t *d_t_colidx, double *d_t_vals, void *stream);
+
 /* ---- multicolour Gauss-Seidel with its setup on the device (csrc/color.hip; the stages: ops.build_gs_schedule_device) ---------
  * The rules: DESIGN.md section 3, "Multicolour Gauss-Seidel on the device".  A: CSR on the device, n < 2^31 - 257; T: its
  * transpose (lmg_csr_transpose_*); G: the pattern of A and T without the diagonal, stored zeros included.  One lane per row (the

@@ -221,6 +221,13 @@ SIGNATURES = {
     "lmg_sa_norms": (_c.c_int, [_i64, _p, _p, _p, _p, _p, _p]),
     "lmg_sa_tentative_fill": (_c.c_int, [_i64, _i64, _p, _p, _p, _p, _p, _p]),
     "lmg_sa_row_states": (_c.c_int, [_i64, _p, _p, _p]),
+    "lmg_nsp_condense_count": (_c.c_int, [_i64, _i32, _p, _p, _p, _p]),
+    "lmg_nsp_condense_fill": (_c.c_int, [_i64, _i32, _p, _p, _p, _p, _p, _p, _p]),
+    "lmg_nsp_gram_chol": (_c.c_int, [_i64, _i64, _i32, _i32, _p, _p, _p, _f64, _p, _p, _p]),
+    "lmg_nsp_apply": (_c.c_int, [_i64, _i64, _i32, _i32, _p, _p, _p, _p, _p]),
+    "lmg_nsp_tri_product": (_c.c_int, [_i64, _i32, _p, _p, _p, _p]),
+    "lmg_nsp_tentative_count": (_c.c_int, [_i64, _i64, _i32, _i32, _p, _p, _p]),
+    "lmg_nsp_tentative_fill": (_c.c_int, [_i64, _i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _p]),
     "lmg_color_select": (_c.c_int, [_i64, _p, _p, _p, _p, _p, _p, _p]),
     "lmg_color_blocks": (_i64, [_i64]),
     "lmg_color_assign": (_c.c_int, [_i64, _p, _p, _p, _p, _p, _p, _p, _p, _p]),

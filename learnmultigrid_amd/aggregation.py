@@ -9,8 +9,16 @@ What a pyamg user gets from `pyamg.smoothed_aggregation_solver(A, B)`, in stages
     H         = sa_hierarchy(A, device)                      the level loop; every A_(l+1) = (P^T A) P is formed once, by
                                                              Hierarchy, and neither P nor a candidate crosses the bus
 
-The rules are DESIGN.md section 3, "Smoothed aggregation setup"; tests/sa_ref.py restates them in plain Python and the
-kernels give the same integers and bits.  There is no CPU path: every stage is a launch on the device that holds A.
+Systems (csrc/nsp.hip): nodes of block_size unknowns and up to six candidates, pyamg's BSR matrix with B of shape (n, k):
+
+    C         = condense_device(A, block_size)               one entry per node block, its Frobenius norm; S and agg from C
+    X         = candidates_device(B, n, block_size, device)  (n, k); None: ones, or the block_size unit translations
+    T, Bc     = tentative_block_device(agg, n_agg, bs, X)    two rounds of Cholesky-QR per aggregate; Bc (k n_agg x k) is the
+                                                             candidate block of the next level, whose block size is k
+
+The rules are DESIGN.md section 3, "Smoothed aggregation setup" and "Smoothed aggregation for systems"; tests/sa_ref.py and
+tests/nsp_ref.py restate them in plain Python and the kernels give the same integers and bits.  There is no CPU path: every
+stage is a launch on the device that holds A.
 """
 import numpy as np
 import torch
@@ -94,6 +102,73 @@ def candidate_device(B, n, device):
     return B
 
 
+def condense_device(A, block_size):
+    """C, the condensed matrix of the node blocks of the DeviceCSR A (N x N, N = n / block_size): c_IJ the Frobenius norm
+    of block (I, J), an entry wherever the block stores one.  block_size 1: A itself."""
+    bs = _check_block(block_size, A.shape[0])
+    if A.shape[0] != A.shape[1]:
+        raise ValueError("the condensation needs a square matrix, got %s" % (A.shape,))
+    return A if bs == 1 else ops.nsp_condense(A, bs)
+
+
+def _check_block(block_size, n):
+    bs = int(block_size)
+    if bs != block_size or bs < 1:
+        raise ValueError("block_size must be an integer >= 1, got %r" % (block_size,))
+    if n % bs:
+        raise ValueError("block_size %d does not divide the %d rows" % (bs, n))
+    return bs
+
+
+def _check_rank_tol(rank_tol):
+    rank_tol = float(rank_tol)
+    if not np.isfinite(rank_tol) or rank_tol <= 0.0:
+        raise ValueError("rank_tol must be finite and positive, got %r" % (rank_tol,))
+    return rank_tol
+
+
+def candidates_device(B, n, block_size, device):
+    """The candidates as a contiguous fp64 (n, k) tensor on `device`, 1 <= k <= 6.  B: a vector of n, an (n, 1) or an
+    (n, k) array; None: ones for block_size 1, else the block_size unit translations (B[i, i % block_size] = 1)."""
+    bs = _check_block(block_size, n)
+    if B is None:
+        if bs == 1:
+            return torch.ones(n, 1, dtype=F64, device=device)
+        if bs > ops.NSP_MAX_CANDIDATES:
+            raise ValueError("block_size %d needs %d unit translations, more than the %d candidates supported: pass B"
+                             % (bs, bs, ops.NSP_MAX_CANDIDATES))
+        X = np.zeros((n, bs))
+        X[np.arange(n), np.arange(n) % bs] = 1.0
+        return torch.from_numpy(X).to(device)
+    if not isinstance(B, torch.Tensor):
+        B = torch.from_numpy(np.ascontiguousarray(np.asarray(B, dtype=np.float64)))
+    if B.dim() <= 1 or (B.dim() == 2 and B.shape[1] == 1):
+        return candidate_device(B, n, device).reshape(n, 1)
+    if B.dim() != 2 or B.shape[0] != n:
+        raise ValueError("the candidates B must have one row per row of A: %d, got %s" % (n, tuple(B.shape)))
+    if not 1 <= B.shape[1] <= ops.NSP_MAX_CANDIDATES:
+        raise ValueError("at most %d candidates are supported, got %d" % (ops.NSP_MAX_CANDIDATES, B.shape[1]))
+    return B.to(device=device, dtype=F64).contiguous()
+
+
+def tentative_block_device(agg, n_agg, block_size, X, rank_tol=1e-12):
+    """(T, Bc) of the candidates X (n x k) on aggregates of nodes of block_size unknowns (agg: per node): two rounds of
+    Cholesky-QR per aggregate.  T (n x k n_agg DeviceCSR): k entries per row of an aggregated node, the row of Q;
+    Bc (k n_agg x k): the blocks R' R.  Raises Refused("candidate", row) for an aggregate whose Gram matrix has a pivot
+    that is not finite or not above rank_tol g_cc -- fewer rows than candidates, or candidates that are locally dependent --
+    with row = block_size * (its smallest node); of several, the smallest row of the first round that refuses."""
+    status = torch.full((2,), -1, dtype=torch.int64, device=X.device)
+    T, Bc = ops.nsp_tentative(agg.contiguous(), n_agg, block_size, X, _check_rank_tol(rank_tol), status)
+    words = status.cpu()
+    for r in range(2):
+        bad = ops.amg_read_status(words[r:r + 1])
+        if bad is not None:
+            if bad[0] != "candidate":
+                raise RuntimeError("the members of aggregate %d are not listed in ascending order" % bad[1])
+            raise Refused(*bad)
+    return T, Bc
+
+
 def tentative_device(agg, n_agg, B):
     """(T, Bc): T (n x n_agg DeviceCSR) with T_ij = B_i / Bc_j for i in aggregate j, Bc_j the 2-norm of B over the
     aggregate (members in ascending order).  Raises Refused("candidate", row) where that norm is zero or not finite."""
@@ -123,40 +198,61 @@ def smooth_prolongator_device(A, T, omega=4.0 / 3.0):
     return ops.amg_smooth(A, T, ops.spgemm(A, T), state, state, jacobi_scale(A, omega), 0.0)
 
 
-def transfer_device(A, B, theta=0.0, omega=4.0 / 3.0):
-    """(P or None, Bc or None, info) of one level: None where the aggregation gives no coarse level (n_agg = 0 or n)."""
-    S = symmetric_strength_device(A, theta)
+def transfer_device(A, B, theta=0.0, omega=4.0 / 3.0, block_size=1, rank_tol=1e-12):
+    """(P or None, Bc or None, info) of one level: None where the aggregation gives no coarse level (n_agg = 0 or the
+    number of nodes).  B: a vector with block_size 1 runs the single-candidate path (Bc a vector); an (n, k) tensor, or any
+    B with block_size > 1, the path of csrc/nsp.hip: strength and aggregates of the condensed matrix, the tentative
+    prolongator of k candidates (Bc: k n_agg x k, the candidates of the next level, whose block size is k)."""
+    bs = _check_block(block_size, A.shape[0])
+    scalar = bs == 1 and B.dim() == 1
+    S = symmetric_strength_device(A if scalar else condense_device(A, bs), theta)
     agg, n_agg, rounds = aggregate_device(S)
     info = {"n": A.shape[0], "nnz": A.nnz, "n_agg": n_agg, "rounds": rounds}
-    if n_agg == 0 or n_agg == A.shape[0]:
+    if n_agg == 0 or n_agg == S.shape[0]:
         return None, None, info
-    T, Bc = tentative_device(agg, n_agg, B)
+    if scalar:
+        T, Bc = tentative_device(agg, n_agg, B)
+    else:
+        T, Bc = tentative_block_device(agg, n_agg, bs, B.reshape(A.shape[0], -1), rank_tol)
     return smooth_prolongator_device(A, T, omega), Bc, info
 
 
-def sa_hierarchy(A, device, *, theta=0.0, B=None, omega=4.0 / 3.0, max_levels=10, max_coarse=500, **hierarchy_kw):
+def sa_hierarchy(A, device, *, theta=0.0, B=None, omega=4.0 / 3.0, block_size=1, rank_tol=1e-12, max_levels=10,
+                 max_coarse=500, **hierarchy_kw):
     """The Hierarchy of A (SciPy or ops.DeviceCSR) by smoothed aggregation: per level the symmetric strength pattern, MIS-2
     aggregates, the tentative prolongator of the candidate (B on the fine level, default ones; the Bc of the level above
     below it) and one Jacobi step on it; A_(l+1) = (P^T A) P as Hierarchy forms it.  The coarsening stops at a level of at
     most max_coarse rows, at max_levels grids, or where the aggregation gives n_agg = 0 or n_agg = n.  H.amg_info: per level
-    n, nnz, and for the levels that were aggregated n_agg and the MIS-2 rounds."""
+    n, nnz, and for the levels that were aggregated n_agg (aggregates, not coarse unknowns), the MIS-2 rounds, block_size
+    and candidates.
+
+    Systems: block_size = bs > 1 makes the unknowns bs I .. bs I + bs - 1 one node; strength and aggregates are those of
+    the condensed matrix (condense_device).  B may be a vector of n, an (n, 1) or an (n, k) array, k <= 6: the tentative
+    prolongator of k candidates is tentative_block_device, and the level loop carries (candidates, block size) down: the
+    Bc of the level above and k.  B None: ones for block_size 1, else the bs unit translations.  One candidate on block
+    size 1 runs the single-candidate path and gives its bits.  rank_tol: the Cholesky pivot below which an aggregate is
+    refused (amg.Refused), relative to the Gram diagonal."""
     from .hierarchy import Hierarchy
     if int(max_levels) < 1:
         raise ValueError("max_levels must be >= 1")
-    theta, omega = _check_unit("theta", theta), _check_omega(omega)
+    theta, omega, rank_tol = _check_unit("theta", theta), _check_omega(omega), _check_rank_tol(rank_tol)
     device = torch.device(device)
+    # (candidates (n x k), block size) of the level at hand: bs on the fine level, k below it; checked before any launch
+    cand = [candidates_device(B, A.shape[0], block_size, device), int(block_size)]
     info = []
 
     def build():
         dA = as_device_csr(A, device)
-        cand = [candidate_device(B, dA.shape[0], device)]
 
         def transfers(l, Al):
             if l + 1 >= int(max_levels) or Al.shape[0] <= int(max_coarse):
                 return None
-            P, Bc, level = transfer_device(Al, cand[0], theta, omega)
-            info.append(level)
-            cand[0] = Bc
+            X, bs = cand
+            k = X.shape[1]
+            P, Bc, level = transfer_device(Al, X.reshape(-1) if k == 1 and bs == 1 else X, theta, omega, bs, rank_tol)
+            info.append(dict(level, block_size=bs, candidates=k))
+            if Bc is not None:
+                cand[:] = [Bc.reshape(-1, k), k]
             return P
 
         return Hierarchy(dA, transfers, device, **hierarchy_kw)
@@ -172,8 +268,9 @@ def sa_hierarchy(A, device, *, theta=0.0, B=None, omega=4.0 / 3.0, max_levels=10
 
 
 def hierarchy_info(H):
-    """Per level n, nnz, n_agg and MIS-2 rounds (None on a level that was not aggregated), and the operator and grid
-    complexity: the sums of nnz and of n over the levels by those of the fine level."""
+    """Per level n, nnz, n_agg and MIS-2 rounds (None on a level that was not aggregated; an aggregated level also has its
+    block_size and candidates), and the operator and grid complexity: the sums of nnz and of n over the levels by those of
+    the fine level."""
     levels = [dict(d) for d in getattr(H, "amg_info", [{"n": lev.n, "nnz": lev.A.nnz, "n_agg": None, "rounds": None}
                                                        for lev in H.levels])]
     nnz0, n0 = max(levels[0]["nnz"], 1), max(levels[0]["n"], 1)

@@ -1985,6 +1985,75 @@ def sa_row_states(T):
     return state
 
 
+# ---- smoothed aggregation for systems (csrc/nsp.hip; the stages: aggregation.py) -------------------
+NSP_MAX_CANDIDATES = 6                                                 # LMG_NSP_MAX_CANDIDATES
+
+
+def nsp_condense(A, bs):
+    """C, the condensed DeviceCSR (N x N, N = n / bs) of the node blocks of A: c_IJ the Frobenius norm of block (I, J),
+    an entry wherever the block stores one.  Count, scan, fill."""
+    n, dev, L, bs = A.shape[0], A.device, _lib.lib(), int(bs)
+    if bs < 1 or n % bs or A.shape[1] != n:
+        raise ValueError("nsp_condense: a square matrix of n = block_size * nodes rows, got %s and %d" % (A.shape, bs))
+    N, st = n // bs, _s(A.vals)
+    vals = []
+
+    def fill(rp, cj):
+        vals.append(torch.empty(cj.numel(), dtype=F64, device=dev))
+        check(L.lmg_nsp_condense_fill(N, bs, _p(A.rowptr), _pe(A.colidx), _pe(A.vals), _p(rp), _pe(cj), _pe(vals[0]), st),
+              "lmg_nsp_condense_fill")
+
+    rp, cj = _count_scan_fill(N, dev, lambda c: check(L.lmg_nsp_condense_count(N, bs, _p(A.rowptr), _pe(A.colidx), _p(c), st),
+                                                      "lmg_nsp_condense_count"), fill)
+    return DeviceCSR(rp, cj, vals[0], (N, N))
+
+
+def nsp_tentative(agg_nodes, n_agg, bs, X, rank_tol, status):
+    """(T, Bc): the tentative prolongator (n x k n_agg DeviceCSR, k entries per row of an aggregated node) of the candidates
+    X (n x k, row-major) by two rounds of Cholesky-QR per aggregate, and the coarse candidates (k n_agg x k).  agg_nodes:
+    the aggregate per NODE of bs unknowns.  status: TWO words (nmg2d_status semantics), one per round; refusals are left
+    there (amg_read_status on status[0:1], then on status[1:2])."""
+    _i32_ok(agg_nodes)
+    if X.dtype != F64 or X.dim() != 2 or not X.is_contiguous() or not X.is_cuda:
+        raise TypeError("expected a contiguous fp64 (n, k) device tensor, got %s %s" % (X.dtype, tuple(X.shape)))
+    n, k = X.shape
+    dev, L, bs, n_agg = X.device, _lib.lib(), int(bs), int(n_agg)
+    if bs < 1 or n % bs or not 1 <= k <= NSP_MAX_CANDIDATES or agg_nodes.numel() < n // bs or not 0 < n_agg <= n // bs \
+            or status.numel() != 2:
+        raise ValueError("nsp_tentative: inconsistent array sizes")
+    N, st, rank_tol = n // bs, _s(X), float(rank_tol)
+    # the member nodes of every aggregate, ascending: the transpose of the node pattern (one entry per aggregated node)
+    ones = torch.ones(N, dtype=F64, device=dev)
+    vals = []
+
+    def pattern(rp, tj):
+        vals.append(torch.empty(tj.numel(), dtype=F64, device=dev))
+        check(L.lmg_sa_tentative_pattern(N, n_agg, _p(agg_nodes), _p(ones), _p(rp), _pe(tj), _pe(vals[0]), st),
+              "lmg_sa_tentative_pattern")
+
+    rp, tj = _count_scan_fill(N, dev, lambda c: check(L.lmg_sa_tentative_count(N, n_agg, _p(agg_nodes), _p(c), st),
+                                                      "lmg_sa_tentative_count"), pattern)
+    members = DeviceCSR(rp, tj, vals[0], (N, n_agg)).transpose()
+    m = (_p(members.rowptr), _pe(members.colidx))
+    R1, R2 = (torch.empty(n_agg * k * k, dtype=F64, device=dev) for _ in range(2))
+    Y = torch.zeros(n, k, dtype=F64, device=dev)
+    check(L.lmg_nsp_gram_chol(n_agg, N, bs, k, *m, _p(X), rank_tol, _p(R1), _p(status[0:1]), st), "lmg_nsp_gram_chol")
+    check(L.lmg_nsp_apply(n, n_agg, bs, k, _p(agg_nodes), _p(X), _p(R1), _p(Y), st), "lmg_nsp_apply")
+    check(L.lmg_nsp_gram_chol(n_agg, N, bs, k, *m, _p(Y), rank_tol, _p(R2), _p(status[1:2]), st), "lmg_nsp_gram_chol")
+    Bc = torch.empty(n_agg * k, k, dtype=F64, device=dev)
+    check(L.lmg_nsp_tri_product(n_agg, k, _p(R2), _p(R1), _p(Bc), st), "lmg_nsp_tri_product")
+    tv = []
+
+    def fill(rp, tj):
+        tv.append(torch.empty(tj.numel(), dtype=F64, device=dev))
+        check(L.lmg_nsp_tentative_fill(n, n_agg, bs, k, _p(agg_nodes), _p(Y), _p(R2), _p(rp), _pe(tj), _pe(tv[0]), st),
+              "lmg_nsp_tentative_fill")
+
+    rp, tj = _count_scan_fill(n, dev, lambda c: check(L.lmg_nsp_tentative_count(n, n_agg, bs, k, _p(agg_nodes), _p(c), st),
+                                                      "lmg_nsp_tentative_count"), fill)
+    return DeviceCSR(rp, tj, tv[0], (n, k * n_agg)), Bc
+
+
 # ---- hipGraph ---------------------------------------------------------------------------------
 class CapturedGraph:
     """A launch sequence captured on the current stream (lmg_graph_*), replayable."""

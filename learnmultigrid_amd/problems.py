@@ -341,3 +341,55 @@ def variable_coeff_poisson_2d_structured(m, seed=44, sigma=0.5, coeff=None):
     A = sp.csr_matrix((vals, colidx, rowptr.astype(np.int32)), shape=(n, n))
     rhs = np.where(boundary, 0.0, -(h * h)).reshape(n, 1)
     return A, rhs
+
+
+def elasticity_2d(m, E=1.0, nu=0.3, seed=None, jitter=0.25):
+    """(A, rhs, B, p): P1 plane-strain elasticity on structured_triangles(m), the nodes those of the grid or, with a seed,
+    of jittered_mesh_2d(m, seed, jitter).  Unknowns are interleaved (u_x, u_y) per node: n = 2 (m+1)^2.  Per triangle
+    K_e = area B_e^T D B_e with the strains (e_xx, e_yy, 2 e_xy) of the linear shape functions and
+    D = E / ((1+nu)(1-2nu)) [[1-nu, nu, 0], [nu, 1-nu, 0], [0, 0, (1-2nu)/2]].  A unit body force acts in -y, lumped as in
+    jittered_poisson_2d (-area/3 to the y unknown of each corner).  Both unknowns of the nodes at x = 0 are clamped by
+    symmetric elimination -- rows and columns zeroed, unit diagonal, rhs 0 -- so A stays symmetric.  B (n x 3): the rigid-body
+    modes, the two translations and the rotation (-y, x); p ((m+1)^2 x 2): the node coordinates.  No such assembly exists
+    in the reference; this is written from the weak form."""
+    m = int(m)
+    s = m + 1
+    if seed is None:
+        g = np.linspace(0.0, 1.0, s)
+        p = np.stack([np.tile(g, s), np.repeat(g, s)], axis=1)
+    else:
+        p = jittered_mesh_2d(m, seed, jitter)[0]
+    tri = structured_triangles(m)
+    x, y = p[:, 0][tri], p[:, 1][tri]
+    bx = np.stack([y[:, 1] - y[:, 2], y[:, 2] - y[:, 0], y[:, 0] - y[:, 1]], axis=1)      # det * dN_a/dx
+    by = np.stack([x[:, 2] - x[:, 1], x[:, 0] - x[:, 2], x[:, 1] - x[:, 0]], axis=1)      # det * dN_a/dy
+    det = (x[:, 1] - x[:, 0]) * (y[:, 2] - y[:, 0]) - (x[:, 2] - x[:, 0]) * (y[:, 1] - y[:, 0])
+    ne = tri.shape[0]
+    Be = np.zeros((ne, 3, 6))
+    Be[:, 0, 0::2] = bx
+    Be[:, 1, 1::2] = by
+    Be[:, 2, 0::2] = by
+    Be[:, 2, 1::2] = bx
+    Be /= det[:, None, None]
+    c = E / ((1.0 + nu) * (1.0 - 2.0 * nu))
+    D = c * np.array([[1.0 - nu, nu, 0.0], [nu, 1.0 - nu, 0.0], [0.0, 0.0, 0.5 * (1.0 - 2.0 * nu)]])
+    Ke = np.einsum("eai,ab,ebj->eij", Be, D, Be) * (0.5 * np.abs(det))[:, None, None]
+    Ke = 0.5 * (Ke + Ke.transpose(0, 2, 1))
+    dofs = np.stack([2 * tri, 2 * tri + 1], axis=2).reshape(ne, 6)
+    n = 2 * s * s
+    A = sp.coo_matrix((Ke.ravel(), (np.repeat(dofs, 6, axis=1).ravel(), np.tile(dofs, (1, 6)).ravel())), shape=(n, n)).tocsr()
+    A.sum_duplicates()
+    rhs = np.zeros(n)
+    np.add.at(rhs, (2 * tri + 1).ravel(), np.repeat(-np.abs(det) / 6.0, 3))
+    clamped = np.repeat(np.arange(s * s) % s == 0, 2)
+    keep = sp.diags((~clamped).astype(np.float64))
+    A = sp.csr_matrix(keep @ A @ keep + sp.diags(clamped.astype(np.float64)))
+    A.eliminate_zeros()
+    A.sort_indices()
+    rhs[clamped] = 0.0
+    B = np.zeros((n, 3))
+    B[0::2, 0] = 1.0
+    B[1::2, 1] = 1.0
+    B[0::2, 2] = -p[:, 1]
+    B[1::2, 2] = p[:, 0]
+    return A, rhs.reshape(n, 1), B, p

@@ -615,16 +615,21 @@ class SmoothedAggregationAMG(ClassicalAMG):
     rules: DESIGN.md section 3).  The aggregates grow around MIS-2 roots, not by pyamg's sequential standard aggregation, and
     the Jacobi step on the tentative prolongator is scaled by the Gershgorin bound, so the levels differ from pyamg's
     (INTEGRATION.md).  theta, B (an n-vector, default ones), omega and max_coarse as in sa_hierarchy; max_levels, setup(),
-    hierarchy_info(), solve, the cycle methods and solve_many as for ClassicalAMG."""
+    hierarchy_info(), solve, the cycle methods and solve_many as for ClassicalAMG.
+
+    Systems: block_size = bs makes every bs consecutive unknowns one node (pyamg: the blocksize of a BSR matrix) and B may
+    be an (n, k) array of k <= 6 candidates -- rigid-body modes for elasticity; rank_tol is the Cholesky pivot below which
+    an aggregate whose candidates are locally dependent is refused (amg.Refused).  Both as in sa_hierarchy (csrc/nsp.hip)."""
 
     _METHOD, _COUNT = "smoothed aggregation", "n_agg"
 
-    def __init__(self, matrix, rhs, *, theta=0.0, B=None, omega=4.0 / 3.0, max_coarse=500, max_levels=10, **kw):
+    def __init__(self, matrix, rhs, *, theta=0.0, B=None, omega=4.0 / 3.0, block_size=1, rank_tol=1e-12, max_coarse=500,
+                 max_levels=10, **kw):
         Multigrid.__init__(self, matrix, rhs, **kw)
         self._log("Selected Smoothed Aggregation AMG")
         self.label = "SmoothedAggregationAMG"
         self.max_levels = int(max_levels)
-        self._amg = dict(theta=theta, omega=omega, max_coarse=max_coarse)
+        self._amg = dict(theta=theta, omega=omega, block_size=block_size, rank_tol=rank_tol, max_coarse=max_coarse)
         self._candidate = B
 
     def _build_hierarchy(self, levels, coarse_refine):
